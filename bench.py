@@ -5,8 +5,12 @@ A *step* is one ``GeneralDiffusion.p_sample`` call on the batch: the full WavBES
 branches, 172.39 conv-GFLOP per sample -- exactly the work the reference does per step) plus the
 fused DDPM update.  Inputs are resident in HBM before the timed region.  fp32 throughout.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode sample|train]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode sample|train] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the JSON line; everything else it can measure is behind
+--full.  --dump-outputs DIR writes the batch the last timed step returned (rank 0's) to DIR/x_prev.npy in float32; the
+inputs, weights and noise are seeded, so two builds given the same arguments can be compared output for output.
 
 With N > 1 every rank denoises its own batch of 32 tiles (inference is batch-parallel: no collective on
 the data path, "scaling": "weak"); value = N*K / max-over-ranks time.  Started WITHOUT a launcher (no WORLD_SIZE in
@@ -16,9 +20,9 @@ for them and exits with their status -- it never initialises HIP and never re-ex
 
 --mode train measures the finetune step of BASELINE configs[3] instead (local batch 8 per GPU, ch 32-256, dropout on,
 forward + backward + SUM all-reduce of the gradients over RCCL overlapped with backward + AdamW + EMA); the default
-mode also reports a short run of it as `train_step`, beside `value`.
+mode with --full also reports a short run of it as `train_step`, beside `value`.
 
-Extra objects on the JSON line (tier contract):
+Extra objects on the JSON line of a --full run (tier contract):
   roofline      conv3d 3x3x3 MFMA kernel: algorithmic FLOPs / summed HIP-event kernel durations measured
                 inside the timed region, against the 157.3 TFLOP/s fp32 matrix peak.
   cpu_baseline  the CPU oracle (parity-locked restatement of the reference) timed on this box's host
@@ -482,11 +486,19 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--mode", choices=["sample", "train"], default="sample")
+    ap.add_argument("--full", action="store_true", help="sample mode: after the timed steps also the instrumented roofline "
+                    "pass, the cond-cached / bf16 / train legs, the parity chain and the CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed region and the instrumented pass "
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the timed region and the instrumented pass "
                     "(no cond-cached / bf16 / train / parity / cpu legs): what tools/bench_traffic.sh profiles")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="sample mode: write the batch the last timed step returned "
+                    "to DIR/x_prev.npy (float32)")
     ap.add_argument("--rehearse", action="store_true", help="CPU-only launcher rehearsal over gloo (tests)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.mode != "sample" or args.rehearse):
+        ap.error("--dump-outputs writes the sample mode's outputs: not with --mode train or --rehearse")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))          # parent: starts the ranks, never touches the GPU
@@ -557,8 +569,8 @@ def main():
     torch.cuda.manual_seed(1234 + rank)
 
     def run(steps, first_t, x):
-        for i in range(steps):
-            x = diff.p_sample(x, first_t - i, condition_x=d, prompt="WV3")
+        for i in range(steps):       # (past t = 0 the schedule starts again at T - 1: warm-up + steps may exceed T)
+            x = diff.p_sample(x, (first_t - i) % T, condition_x=d, prompt="WV3")
         return x
 
     log(f"rank {rank}/{world}: model and inputs on {torch.cuda.get_device_name(dev)}")
@@ -576,24 +588,30 @@ def main():
     log(f"timed region: {args.steps} steps in {dt:.3f} s")
     rank_ms = per_rank_ms(dist, world, dt, args.steps, dev)
     evidence = dict(evidence, after_timed_region=collective_evidence(dist, world, rank, backend, dev, torch.cuda.current_device()))
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "x_prev.npy"), x.float().cpu().numpy())
+        log(f"last timed step's output written to {args.dump_outputs}")
 
-    # ---- the same K steps again with a HIP event pair around every conv launch (roofline object).  Kept out of the
-    # run that produces `value`; its wall time is reported so the two can be compared. -------------------------------
-    ops.TIMER = ops.ConvTimer()
-    barrier()
-    ti = time.perf_counter()
-    xi = run(args.steps, T - 1 - args.warmup, x)
-    barrier()
-    dt_instr = time.perf_counter() - ti
-    timer, ops.TIMER = ops.TIMER, None
-    conv = timer.summary()
-    conv_by_entry = timer.summary(by_entry=True)
-    k1_n, k1_ms, k1_bytes = timer.bytes_summary(1)
-    del xi
-
-    dt_cached = dt_bf16 = bf16_levels = None
+    dt_instr = dt_cached = dt_bf16 = bf16_levels = None
     train = None
-    if not args.no_extras:
+    if args.full:
+        # ---- the same K steps again with a HIP event pair around every conv launch (roofline object).  Kept out of the
+        # run that produces `value`; its wall time is reported so the two can be compared. ---------------------------
+        ops.TIMER = ops.ConvTimer()
+        barrier()
+        ti = time.perf_counter()
+        xi = run(args.steps, T - 1 - args.warmup, x)
+        barrier()
+        dt_instr = time.perf_counter() - ti
+        timer, ops.TIMER = ops.TIMER, None
+        conv = timer.summary()
+        conv_by_entry = timer.summary(by_entry=True)
+        k1_n, k1_ms, k1_bytes = timer.bytes_summary(1)
+        del xi
+
+    if args.full and not args.no_extras:
         # ---- the same loop with the condition branch hoisted (a real sampling run), outside `value` -------
         barrier()
         t1 = time.perf_counter()
@@ -623,25 +641,12 @@ def main():
         del x2, x3
 
     if dist is not None:
-        tt = torch.tensor([dt, dt_cached or 0.0, dt_bf16 or 0.0, dt_instr], device=dev, dtype=torch.float64)
+        tt = torch.tensor([dt, dt_cached or 0.0, dt_bf16 or 0.0, dt_instr or 0.0], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt, dt_cached, dt_bf16, dt_instr = (float(v) for v in tt)
 
     line = None
     if rank == 0:
-        n3, ms3, fl3 = conv.get(3, (0, 0.0, 0.0))
-        n1, ms1, fl1 = conv.get(1, (0, 0.0, 0.0))
-        n0, ms0, by0 = conv.get(0, (0, 0.0, 0.0))        # Winograd input-transform passes (HBM-bound; "flops" slot = bytes)
-        achieved = fl3 / (ms3 * 1e-3) / 1e12 if ms3 > 0 else 0.0
-        # FLOPs in the reference's operator order: a conv3d_ll_fwd launch (Conv_0 + halved LL band of a main-branch down
-        # block as one strided convolution, csrc/conv3d_ll.hip) executes 48 of the 4 x 27 multiply-adds per output
-        # ... and a conv3d_wino{4,2}_fwd launch (Winograd F(4,3) / F(2,3) along the band axis, csrc/conv3d_wino.hip; its
-        # input-transform pass is timed apart) 54 of the 4 x 27 per four output bands / 36 of the 2 x 27 per pair
-        ref_factor = {"conv3d_ll_fwd": 108.0 / 48.0, "conv3d_wfll_fwd": 108.0 / 24.0, "conv3d_wino2_fwd": 1.5, "conv3d_wino4_fwd": 2.0,
-                      "conv3d_wf_fwd": 2.0}   # composed LL (+ F(4,3) on top) / F(2,3) / F(4,3)
-        fl3_ref = fl3 + sum(fl * (ref_factor[what] - 1.0) for (k, what), (n, ms, fl) in conv_by_entry.items()
-                            if k == 3 and what in ref_factor)
-        traffic, traffic_src = load_traffic()
         line = {
             "metric": "UNet denoise-steps/sec (8-ch 64x64, batch 32)",
             "value": round(world * args.steps / dt, 4),
@@ -664,55 +669,69 @@ def main():
             # reference (the Winograd / composed kernels execute about half of these multiply-adds, so it may exceed the
             # 157.3 TFLOP/s matrix peak); the roofline object counts executed FLOPs
             "unet_reference_order_tflops": round(BATCH * GFLOP_PER_SAMPLE * 1e-3 * args.steps / dt, 2),
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_FP32_MFMA, "unit": "TFLOP/s",
-                         "frac": round(achieved / PEAK_FP32_MFMA, 4), "traffic": traffic, "traffic_source": traffic_src,
-                         # every pass in front of a convolution kernel (Winograd input transform of the 8x8 level, prologue
-                         # pass of the three-segment inputs) counted INTO the time: the figure DESIGN.md quotes
-                         "frac_with_transforms": round(fl3 / ((ms3 + ms0) * 1e-3) / 1e12 / PEAK_FP32_MFMA, 4) if ms3 > 0 else 0.0,
-                         "kernel": "3x3x3 conv launches, fp32 v_mfma_f32_32x32x2_f32.  Dominant: conv3d_wf_kernel (Winograd F(4,3) "
-                                   "along the band axis, input transform inside the kernel: 2x fewer multiply-adds, no transform "
-                                   "pass; its prologue pass for three-segment inputs and the reduction kernel of its split-K "
-                                   "launches are inside its time).  At the benchmark batch it runs EVERY 3x3x3 convolution: "
-                                   "conv3d_wf_fwd = the stride-1 ones (8x8 level: two images per tile), conv3d_wfll_fwd = Conv_0 + "
-                                   "LL band of the main branch's down blocks as one convolution with Winograd on top (24 instead of "
-                                   "48 / 108 multiply-adds per output, on the producer's space-to-depth output).  Fallbacks for other "
-                                   "shapes: conv3d_ll_kernel, wino_input_kernel + conv3d_wino_kernel, conv3d_dma / conv3d_mfma (direct)",
-                         "flops_counted": "EXECUTED on the matrix pipe (what the roofline bounds); in the reference's operator "
-                                          "order the same launches are worth `reference_order_tflops`",
-                         "reference_order_tflops": round(fl3_ref / (ms3 * 1e-3) / 1e12, 2) if ms3 > 0 else 0.0,
-                         "measured_in": f"a second pass of the same {args.steps} steps with a HIP event pair around every conv "
-                                        f"launch ({round(dt_instr / args.steps * 1e3, 3)} ms/step), outside the run that gives `value`",
-                         "launches": n3, "avg_launch_us": round(ms3 / max(n3, 1) * 1e3, 2),
-                         "executed_gflop_per_launch": round(fl3 / max(n3, 1) / 1e9, 2),
-                         "algorithmic_gflop_per_launch": round(fl3_ref / max(n3, 1) / 1e9, 2),
-                         # per entry point, to set beside the rocprofv3 kernel averages in profiles/: "conv3d_fwd" =
-                         # conv3d_mfma_kernel<3,..>; "conv3d_fwd_staged" = prologue_apply_kernel (when the input has a
-                         # prologue) + conv3d_dma_kernel<3,..>; "conv3d_ll_fwd" = conv3d_ll_kernel (executed FLOPs)
-                         "by_entry": {what: {"launches": n, "avg_launch_us": round(ms / n * 1e3, 2),
-                                             "tflops": round(fl / (ms * 1e-3) / 1e12, 2)}
-                                      for (k, what), (n, ms, fl) in sorted(conv_by_entry.items()) if k == 3},
-                         "input_transform_passes": {"launches": n0, "avg_launch_us": round(ms0 / max(n0, 1) * 1e3, 2),
-                                                    "tb_per_s": round(by0 / (ms0 * 1e-3) / 1e12, 2) if ms0 > 0 else 0.0,
-                                                    "note": "wino_input_kernel in front of the conv3d_wino_kernel launches that remain "
-                                                            "(the 8x8 level: planes too narrow for conv3d_wf's 8x16 tiles): "
-                                                            "HBM-bound (4 B read + 6.6 B (F(4,3)) / 8.8 B (F(2,3)) written per "
-                                                            "input element), timed apart and NOT inside `achieved`; with them "
-                                                            "the 3x3x3 launches run at "
-                                                            f"{round(fl3 / ((ms3 + ms0) * 1e-3) / 1e12, 2) if ms3 > 0 else 0.0} "
-                                                            "TFLOP/s executed = `frac_with_transforms`"},
-                         # the 1x1x1 convolutions are bandwidth kernels: algorithmic bytes (input + output (+ residual) once) over
-                         # their summed durations, against the box's 6.29 TB/s copy rate (tools/bench_hbm_kernels.py)
-                         "k1_conv": {"launches": n1, "avg_launch_us": round(ms1 / max(n1, 1) * 1e3, 2), "bound": "hbm",
-                                     "ms_per_step": round(ms1 / args.steps, 3),
-                                     "tb_per_s": round(k1_bytes / (k1_ms * 1e-3) / 1e12, 2) if k1_ms > 0 else 0.0,
-                                     "frac_of_copy_rate": round(k1_bytes / (k1_ms * 1e-3) / 1e12 / COPY_RATE_TB_S, 3) if k1_ms > 0 else 0.0,
-                                     "copy_rate_tb_s": COPY_RATE_TB_S,
-                                     "note": f"{n1 // max(args.steps, 1)} launches per step (the res_conv / Conv_2 launches that do not ride in a "
-                                             "3x3x3 epilogue), most of them small (8x8 / 16x16 levels: 4-60 MB each, 10-30 us = launch + "
-                                             "ramp + a short channel loop, not bandwidth); the two level-0 / level-1 ones, which also "
-                                             "write conv20's prologue output, run at 4.9-5.1 TB/s"}},
         }
-        if not args.no_extras:
+        if args.full:
+            n3, ms3, fl3 = conv.get(3, (0, 0.0, 0.0))
+            n1, ms1, fl1 = conv.get(1, (0, 0.0, 0.0))
+            n0, ms0, by0 = conv.get(0, (0, 0.0, 0.0))        # Winograd input-transform passes (HBM-bound; "flops" slot = bytes)
+            achieved = fl3 / (ms3 * 1e-3) / 1e12 if ms3 > 0 else 0.0
+            # FLOPs in the reference's operator order: a conv3d_ll_fwd launch (Conv_0 + halved LL band of a main-branch down
+            # block as one strided convolution, csrc/conv3d_ll.hip) executes 48 of the 4 x 27 multiply-adds per output
+            # ... and a conv3d_wino{4,2}_fwd launch (Winograd F(4,3) / F(2,3) along the band axis, csrc/conv3d_wino.hip; its
+            # input-transform pass is timed apart) 54 of the 4 x 27 per four output bands / 36 of the 2 x 27 per pair
+            ref_factor = {"conv3d_ll_fwd": 108.0 / 48.0, "conv3d_wfll_fwd": 108.0 / 24.0, "conv3d_wino2_fwd": 1.5, "conv3d_wino4_fwd": 2.0,
+                          "conv3d_wf_fwd": 2.0}   # composed LL (+ F(4,3) on top) / F(2,3) / F(4,3)
+            fl3_ref = fl3 + sum(fl * (ref_factor[what] - 1.0) for (k, what), (n, ms, fl) in conv_by_entry.items()
+                                if k == 3 and what in ref_factor)
+            traffic, traffic_src = load_traffic()
+            line["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_FP32_MFMA, "unit": "TFLOP/s",
+                                "frac": round(achieved / PEAK_FP32_MFMA, 4), "traffic": traffic, "traffic_source": traffic_src,
+                                # every pass in front of a convolution kernel (Winograd input transform of the 8x8 level, prologue
+                                # pass of the three-segment inputs) counted INTO the time: the figure DESIGN.md quotes
+                                "frac_with_transforms": round(fl3 / ((ms3 + ms0) * 1e-3) / 1e12 / PEAK_FP32_MFMA, 4) if ms3 > 0 else 0.0,
+                                "kernel": "3x3x3 conv launches, fp32 v_mfma_f32_32x32x2_f32.  Dominant: conv3d_wf_kernel (Winograd F(4,3) "
+                                          "along the band axis, input transform inside the kernel: 2x fewer multiply-adds, no transform "
+                                          "pass; its prologue pass for three-segment inputs and the reduction kernel of its split-K "
+                                          "launches are inside its time).  At the benchmark batch it runs EVERY 3x3x3 convolution: "
+                                          "conv3d_wf_fwd = the stride-1 ones (8x8 level: two images per tile), conv3d_wfll_fwd = Conv_0 + "
+                                          "LL band of the main branch's down blocks as one convolution with Winograd on top (24 instead of "
+                                          "48 / 108 multiply-adds per output, on the producer's space-to-depth output).  Fallbacks for other "
+                                          "shapes: conv3d_ll_kernel, wino_input_kernel + conv3d_wino_kernel, conv3d_dma / conv3d_mfma (direct)",
+                                "flops_counted": "EXECUTED on the matrix pipe (what the roofline bounds); in the reference's operator "
+                                                 "order the same launches are worth `reference_order_tflops`",
+                                "reference_order_tflops": round(fl3_ref / (ms3 * 1e-3) / 1e12, 2) if ms3 > 0 else 0.0,
+                                "measured_in": f"a second pass of the same {args.steps} steps with a HIP event pair around every conv "
+                                               f"launch ({round(dt_instr / args.steps * 1e3, 3)} ms/step), outside the run that gives `value`",
+                                "launches": n3, "avg_launch_us": round(ms3 / max(n3, 1) * 1e3, 2),
+                                "executed_gflop_per_launch": round(fl3 / max(n3, 1) / 1e9, 2),
+                                "algorithmic_gflop_per_launch": round(fl3_ref / max(n3, 1) / 1e9, 2),
+                                # per entry point, to set beside the rocprofv3 kernel averages in profiles/: "conv3d_fwd" =
+                                # conv3d_mfma_kernel<3,..>; "conv3d_fwd_staged" = prologue_apply_kernel (when the input has a
+                                # prologue) + conv3d_dma_kernel<3,..>; "conv3d_ll_fwd" = conv3d_ll_kernel (executed FLOPs)
+                                "by_entry": {what: {"launches": n, "avg_launch_us": round(ms / n * 1e3, 2),
+                                                    "tflops": round(fl / (ms * 1e-3) / 1e12, 2)}
+                                             for (k, what), (n, ms, fl) in sorted(conv_by_entry.items()) if k == 3},
+                                "input_transform_passes": {"launches": n0, "avg_launch_us": round(ms0 / max(n0, 1) * 1e3, 2),
+                                                           "tb_per_s": round(by0 / (ms0 * 1e-3) / 1e12, 2) if ms0 > 0 else 0.0,
+                                                           "note": "wino_input_kernel in front of the conv3d_wino_kernel launches that remain "
+                                                                   "(the 8x8 level: planes too narrow for conv3d_wf's 8x16 tiles): "
+                                                                   "HBM-bound (4 B read + 6.6 B (F(4,3)) / 8.8 B (F(2,3)) written per "
+                                                                   "input element), timed apart and NOT inside `achieved`; with them "
+                                                                   "the 3x3x3 launches run at "
+                                                                   f"{round(fl3 / ((ms3 + ms0) * 1e-3) / 1e12, 2) if ms3 > 0 else 0.0} "
+                                                                   "TFLOP/s executed = `frac_with_transforms`"},
+                                # the 1x1x1 convolutions are bandwidth kernels: algorithmic bytes (input + output (+ residual) once) over
+                                # their summed durations, against the box's 6.29 TB/s copy rate (tools/bench_hbm_kernels.py)
+                                "k1_conv": {"launches": n1, "avg_launch_us": round(ms1 / max(n1, 1) * 1e3, 2), "bound": "hbm",
+                                            "ms_per_step": round(ms1 / args.steps, 3),
+                                            "tb_per_s": round(k1_bytes / (k1_ms * 1e-3) / 1e12, 2) if k1_ms > 0 else 0.0,
+                                            "frac_of_copy_rate": round(k1_bytes / (k1_ms * 1e-3) / 1e12 / COPY_RATE_TB_S, 3) if k1_ms > 0 else 0.0,
+                                            "copy_rate_tb_s": COPY_RATE_TB_S,
+                                            "note": f"{n1 // max(args.steps, 1)} launches per step (the res_conv / Conv_2 launches that do not ride in a "
+                                                    "3x3x3 epilogue), most of them small (8x8 / 16x16 levels: 4-60 MB each, 10-30 us = launch + "
+                                                    "ramp + a short channel loop, not bandwidth); the two level-0 / level-1 ones, which also "
+                                                    "write conv20's prologue output, run at 4.9-5.1 TB/s"}}
+        if args.full and not args.no_extras:
             line["cond_cached"] = {"value": round(world * args.steps / dt_cached, 4), "unit": "batch32-steps/s",
                                    "note": "condition branch (62.82 of 172.39 GFLOP/sample, independent of x_t and t) "
                                            "evaluated once inside the timed run instead of every step; outputs are "
@@ -723,12 +742,12 @@ def main():
                                     "note": "same full-forward steps with bf16 conv operands / fp32 accumulation "
                                             "(set_compute_dtype('bf16'), the config-3 mode; forward rel-L2 7e-3 vs fp32, "
                                             "tests/test_gpu_bf16.py) -- reduced precision, never `value`"}
-        if world == 1 and not args.no_cpu_baseline and not args.no_extras:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.no_extras:
             line["parity"] = parity_check(dev)
             log(f"parity: PSNR {line['parity']['psnr_db']} dB")
             line["cpu_baseline"] = cpu_baseline()
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # ---- finetune step (BASELINE configs[3] share of this GPU), a short run beside `value`, LAST: at N > 1 it is the
         # first code to push 123 MB gradient buckets through RCCL.  Everything measured so far is already in `line`; if
         # this leg raises, or a collective never completes (watchdog), the line is still printed, with the reason. -------

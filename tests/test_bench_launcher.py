@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -75,5 +77,24 @@ def test_visible_gpus_needs_no_gpu_runtime():
             f"sys.path.insert(0, {ROOT!r}); import bench; assert bench.visible_gpus() == 3; "
             "os.environ['ROCR_VISIBLE_DEVICES']='4'; assert bench.visible_gpus() == 1; "
             "assert 'torch' not in sys.modules; print('ok')")
-    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    # (lists already set in the environment the suite runs in would count too)
+    env = {k: v for k, v in os.environ.items() if k not in ("ROCR_VISIBLE_DEVICES", "HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")}
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=120)
     assert p.returncode == 0 and p.stdout.strip() == "ok", p.stderr[-2000:]
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_step_reproducibly(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps and does nothing beside them (the roofline pass and the other
+    legs are --full's); --dump-outputs writes the batch of the last timed step, and the same arguments give the same
+    inputs, hence (the forward path has no atomics) the same bits."""
+    import numpy as np
+    outs = []
+    for run in ("a", "b"):
+        line = _run("--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / run))
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "batch32-steps/s" and line["dtype"] == "f32" and line["higher_is_better"] is True
+        assert not {"roofline", "cpu_baseline", "parity", "cond_cached", "bf16_compute", "train_step"} & set(line)
+        outs.append(np.load(tmp_path / run / "x_prev.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (32, 8, 64, 64) and np.isfinite(outs[0]).all()
+    assert np.array_equal(outs[0], outs[1])

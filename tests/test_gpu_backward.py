@@ -443,14 +443,17 @@ def test_composed_conv_ll_gradients_vs_cpu_autograd(shape):
     from tmdiff_amd import autograd as A
     B, cin, cout, N, H, W = shape
     torch.manual_seed(23)
-    x = torch.randn(B, cin, N, H, W, requires_grad=True)
-    w = (torch.randn(cout, cin, 3, 3, 3) / (cin * 27) ** 0.5).requires_grad_()
-    b = torch.randn(cout, requires_grad=True)
+    x = torch.randn(B, cin, N, H, W)
+    w = torch.randn(cout, cin, 3, 3, 3) / (cin * 27) ** 0.5
+    b = torch.randn(cout)
     r = torch.randn(B, cout, N, H // 2, W // 2)
+    # the CPU autograd in fp64: an fp32 one is itself off the exact gradients by as much as the tolerances below (its
+    # reductions sum up to 2^17 terms per bias / weight element, in an order that follows the host's thread count)
+    x, w, b = (t.double().requires_grad_() for t in (x, w, b))
     full = F.conv3d(F.silu(x), w, b, padding=1)
     want = 0.25 * (full[..., 0::2, 0::2] + full[..., 0::2, 1::2] + full[..., 1::2, 0::2] + full[..., 1::2, 1::2])
-    (want * r).sum().backward()
-    xg, wg, bg = (t.detach().cuda().requires_grad_() for t in (x, w, b))
+    (want * r.double()).sum().backward()
+    xg, wg, bg = (t.detach().float().cuda().requires_grad_() for t in (x, w, b))
     from tmdiff_amd import ops
     counts, ops.COUNTS = ops.COUNTS, __import__("collections").Counter()
     try:

@@ -4,7 +4,7 @@
 # only --kernel-trace beside them, the program itself after `--`.  Writes profiles/${TAG}_bench_traffic.json (read back
 # by bench.py into roofline.traffic) and a kernel-stats pass of the same command (profiles/${TAG}_bench_kernel_stats.csv).
 R=$PWD; TAG=${1:-r04}; OUT=$R/gpurun_out/${TAG}_traffic
-CMD="python3 $R/bench.py --steps 3 --warmup 1 --no-extras"
+CMD="python3 $R/bench.py --steps 3 --warmup 1 --full --no-extras"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch -o p --output-format csv -- $CMD > $OUT.fetch.log 2>&1 &&
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/write -o p --output-format csv -- $CMD > $OUT.write.log 2>&1 &&

@@ -5,7 +5,7 @@ R=$PWD; TAG=${1:-r04}; O=$R/gpurun_out/${TAG}_final; mkdir -p $O
 # (the PMC traffic first: bench.py reads profiles/${TAG}_bench_traffic.json back into roofline.traffic and marks it stale when it
 #  was collected from other sources)
 bash tools/bench_traffic.sh $TAG > $O/traffic.log 2>&1; echo "traffic rc=$?"
-python3 bench.py --steps 20 --warmup 3 > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"
+python3 bench.py --steps 20 --warmup 3 --full > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"
 python3 bench.py --mode train --steps 10 --warmup 3 > $O/bench_train_line.json 2>> $O/bench.err; echo "train rc=$?"
 python3 tools/bench_configs.py c1 c3 c4 2>&1 | grep config > $O/configs.txt
 python3 tools/bench_attention.py 2>&1 | grep -v amdgpu > $O/attention.txt
@@ -39,5 +39,5 @@ cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_train -o p --output-format csv -- python3 $R/bench.py --mode train --steps 6 --warmup 2 > /dev/null 2>&1; echo "train prof rc=$?"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_bf16 -o p --output-format csv -- python3 $R/tools/prof_bf16_step.py 10 > /dev/null 2>&1; echo "bf16 prof rc=$?"
 TMDIFF_BENCH_BACKEND=gloo timeout -k 10 300 python3 $R/bench.py --gpus 2 --mode train --steps 4 --warmup 2 > $O/train_2rank_gloo.json 2> /dev/null; echo "2-rank rc=$?"
-TMDIFF_BENCH_BACKEND=gloo timeout -k 10 300 python3 $R/bench.py --gpus 2 --steps 5 --warmup 2 --no-extras > $O/bench_2rank_gloo.json 2> /dev/null; echo "2-rank sample rc=$?"
+TMDIFF_BENCH_BACKEND=gloo timeout -k 10 300 python3 $R/bench.py --gpus 2 --steps 5 --warmup 2 --full --no-extras > $O/bench_2rank_gloo.json 2> /dev/null; echo "2-rank sample rc=$?"
 python3 $R/tools/exp_half_batches.py 10 2>&1 | grep -v amdgpu > $O/half_batches.txt
