@@ -12,13 +12,11 @@
 // in-lane reductions plus one exchange between the two half-waves, the rescale of the output accumulator
 // O^T[d, query] is a per-lane multiply, and P^T feeds the second product O^T += V^T P^T directly from the
 // accumulator registers: register r of half-wave h is key (r&3)+8(r>>2)+4h, exactly the K-pair of MFMA step r.
-#include <cstdlib>
-
 #include "common.h"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
+using namespace tmdiff;
 
 // ---------------------------------------------------------------------------------------------------------
 // attention.  q [BH, Nq, D], k [BH, Nk, D], v [BH, Nk, D] with arbitrary row / head strides (elements).
@@ -516,8 +514,8 @@ extern "C" int tmdiff_attn_fwd(const float* q, const float* k, const float* v, f
   a.H = H; a.Nq = Nq; a.Nk = Nk; a.D = D; a.scale = scale;
   dim3 grid((Nq + 127) / 128, B * H);
   hipStream_t st = as_stream(stream);
-  static const bool no_dma = getenv("TMDIFF_ATTN_SIMPLE") != nullptr;   // experiments: the un-pipelined kernel everywhere
-  static const bool no_ctx = getenv("TMDIFF_ATTN_NO_CTX") != nullptr;   // experiments: never the small-context kernel
+  static const bool no_dma = env_flag("TMDIFF_ATTN_SIMPLE");   // experiments: the un-pipelined kernel everywhere
+  static const bool no_ctx = env_flag("TMDIFF_ATTN_NO_CTX");   // experiments: never the small-context kernel
   // a short context (the 77 CLIP tokens) with d_head 64: K / V resident in LDS, single-pass softmax.  Needs 16-byte aligned
   // query / output rows (float4 row pieces).
   if (!no_dma && !no_ctx && D == 64 && Nk <= 96 && a.q_rs % 4 == 0 && a.o_rs % 4 == 0 && a.q_bs % 4 == 0 && a.q_hs % 4 == 0 &&

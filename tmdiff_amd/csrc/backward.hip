@@ -23,16 +23,7 @@
 
 namespace {
 
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, E>(f);
-  }
-}
-
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
+using namespace tmdiff;
 
 __device__ __forceinline__ bool tmdiff_aligned16_dev(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -736,8 +727,8 @@ int tmdiff::launch_prologue_apply(const tmdiff_conv3d_desc* d, float* xp, hipStr
   q.in_shift = d->in_shift; q.in_scale = d->in_scale; q.in_mask = d->in_mask; q.in_act = d->in_act;
   q.drop_seed = d->drop_seed; q.drop_seed_dev = d->drop_seed_dev; q.drop_thresh = drop_threshold(d->drop_p);
   q.drop_inv = d->drop_p > 0.f ? 1.0f / (1.0f - d->drop_p) : 0.f;
-  q.shift_stride = d->in_shift_stride > 0 ? d->in_shift_stride : (d->in_shift_stride < 0 ? 0 : d->Cin);
-  q.scale_stride = d->in_scale_stride > 0 ? d->in_scale_stride : (d->in_scale_stride < 0 ? 0 : d->Cin);
+  q.shift_stride = bank_stride(d->in_shift_stride, d->Cin);
+  q.scale_stride = bank_stride(d->in_scale_stride, d->Cin);
   q.xp = xp;
   q.plane = plane;
   long pb = (plane + 1023) / 1024;
@@ -898,8 +889,8 @@ int prologue_bwd_impl(const tmdiff_conv3d_desc* d, const float* gp, float* const
   }
   TMDIFF_REQUIRE(csum == d->Cin, "prologue_bwd: segments hold %d channels, Cin=%d", csum, d->Cin);
   a.in_shift = d->in_shift; a.in_scale = d->in_scale; a.in_mask = d->in_mask; a.in_act = d->in_act;
-  a.shift_stride = d->in_shift_stride > 0 ? d->in_shift_stride : (d->in_shift_stride < 0 ? 0 : d->Cin);
-  a.scale_stride = d->in_scale_stride > 0 ? d->in_scale_stride : (d->in_scale_stride < 0 ? 0 : d->Cin);
+  a.shift_stride = bank_stride(d->in_shift_stride, d->Cin);
+  a.scale_stride = bank_stride(d->in_scale_stride, d->Cin);
   a.drop_seed = d->drop_seed; a.drop_seed_dev = d->drop_seed_dev; a.drop_thresh = drop_threshold(d->drop_p);
   a.drop_inv = d->drop_p > 0.f ? 1.0f / (1.0f - d->drop_p) : 0.f;
   a.gp = gp; a.d_shift = d_shift; a.d_scale = d_scale;

@@ -1,9 +1,11 @@
-// Shared host-side helpers for libtmdiff_hip.so (gfx950 only).
+// Shared host- and device-side helpers for libtmdiff_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
+#include <type_traits>
 
 #include "tmdiff_hip.h"
 
@@ -30,6 +32,64 @@ inline int check_launch(const char* what) {
 inline hipStream_t as_stream(tmdiff_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// Row stride of a per-(sample, channel) shift / scale bank (tmdiff_hip.h): a stride > 0 is used as it is, 0 means dense rows
+// of c channels, a negative stride means one row broadcast over the batch (stride 0).
+inline int bank_stride(int s, int c) { return s > 0 ? s : (s < 0 ? 0 : c); }
+
+// Experiment switches read from the environment.  Callers keep the value in a function-local static: each switch is read
+// once per process.
+inline bool env_flag(const char* name) { return getenv(name) != nullptr; }   // set at all
+inline bool env_off(const char* name) {                                       // set to "0..."
+  const char* e = getenv(name);
+  return e && e[0] == '0';
+}
+inline long env_long(const char* name, long dflt) {
+  const char* e = getenv(name);
+  return e ? atol(e) : dflt;
+}
+inline double env_double(const char* name, double dflt) {
+  const char* e = getenv(name);
+  return e ? atof(e) : dflt;
+}
+
+using f32x16 = __attribute__((ext_vector_type(16))) float;   // one 32x32 MFMA accumulator (16 registers per lane)
+
+// compile-time loop: f(std::integral_constant<int, I>) for I in [B, E) -- indices must be constants so that
+// register arrays indexed by them are addressed statically (a runtime index would send them to scratch).
+template <int B, int E, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (B < E) {
+    f(std::integral_constant<int, B>{});
+    static_for<B + 1, E>(f);
+  }
+}
+
+// XCD-aware block id: blocks b and b+8 share an XCD (round-robin dispatch), so hand each XCD a
+// contiguous run of logical tiles -- neighbouring tiles (same input box, other channel tile;
+// adjacent boxes sharing halo lines) then hit in that XCD's L2.  Bijective for any grid size.
+__device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
+  const unsigned q = nwg / 8, r = nwg % 8, xcd = bid % 8, k = bid / 8;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+}
+
+// Two workgroups share a CU (LDS-limited) and one matrix pipe per SIMD.  Launched together and with equal tile times they
+// stay in lockstep for the whole launch: both run their MFMA phases together (each at half the pipe) and both reach their
+// epilogues together -- the pipe idles while every CU of the chip stores its outputs at once (HBM-bound burst: 64 -> 64 at
+// 64x64, B = 32 writes / reads 0.8 GB per launch in four bursts).  Delaying the second resident workgroup of every CU ONCE,
+// by about an epilogue, puts the pairs in anti-phase for good: one computes at the full pipe rate while its partner stores.
+// The second resident is the one whose LDS allocation does not start at 0 (HW_REG_LDS_ALLOC, base field).  Only blocks
+// below first_round (resident at launch) wait.  The Winograd kernels take it for experiments (conv3d_wino.hip, conv3d_wf.hip).
+__device__ __forceinline__ void stagger_start(int cycles, unsigned first_round) {
+  if (cycles <= 0 || blockIdx.x >= first_round) return;
+  const unsigned lds_alloc = __builtin_amdgcn_s_getreg(6 | (0 << 6) | (11 << 11));   // hwreg(HW_REG_LDS_ALLOC, 0, 12): LDS_BASE
+  if (lds_alloc == 0) return;
+  const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+  while ((long long)(__builtin_amdgcn_s_memtime() - t0) < (long long)cycles) __builtin_amdgcn_s_sleep(32);
+}
+
+// source of zero padding / filler lanes of the LDS-DMA staging (internal linkage: one copy per translation unit)
+static __device__ const float4 kZero4 = {0.f, 0.f, 0.f, 0.f};
 
 __device__ __forceinline__ float silu_f(float v) {
   // x * sigmoid(x); __expf -> v_exp_f32 on a pre-scaled argument, 1 ulp-level accurate for our range

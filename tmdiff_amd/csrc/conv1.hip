@@ -14,13 +14,11 @@
 // a workgroup (KS = 4: small planes, where the channel loop was a chain of memory round trips).  The 16-byte and the KS = 4 form
 // can also write act(x + shift) of their input as a by-product (desc.xp_*: the prologue output another convolution of the same
 // input wants), stored through a buffer descriptor.
-#include <cstdlib>
-
 #include "common.h"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
+using namespace tmdiff;
 
 constexpr int G = 8;  // K-steps per register group (16 input channels)
 
@@ -423,25 +421,22 @@ int tmdiff::conv1_fp32_try(const tmdiff_conv3d_desc* d, hipStream_t st, bool dry
   }
   a.wp = d->w_packed; a.bias = d->bias; a.bias_scale = d->bias_scale;
   a.in_shift = d->in_shift; a.in_scale = d->in_scale;
-  a.shift_stride = d->in_shift_stride > 0 ? d->in_shift_stride : (d->in_shift_stride < 0 ? 0 : d->Cin);
-  a.scale_stride = d->in_scale_stride > 0 ? d->in_scale_stride : (d->in_scale_stride < 0 ? 0 : d->Cin);
+  a.shift_stride = bank_stride(d->in_shift_stride, d->Cin);
+  a.scale_stride = bank_stride(d->in_scale_stride, d->Cin);
   a.residual = d->residual; a.out_scale = d->out_scale; a.y = d->y;
   a.plane = plane;
   a.xp_out = d->xp_out; a.xp_shift = d->xp_shift; a.xp_act = d->xp_act;
-  a.xp_shift_stride = d->xp_shift_stride > 0 ? d->xp_shift_stride : (d->xp_shift_stride < 0 ? 0 : d->Cin);
+  a.xp_shift_stride = bank_stride(d->xp_shift_stride, d->Cin);
   // channel tiles follow the weight packing: 64-channel interleaved rows when cout_g % 64 == 0
   // (its 512-position tiles must still fill the chip: the 8x8x8 level keeps the dword kernel's 256-position tiles)
   const long blocks_vec = (long)d->B * d->groups * ((plane + 511) / 512) * (cout_g % 64 == 0 ? cout_g / 64 : cout_g / 32);
-  static const bool force_vec = getenv("TMDIFF_CONV1_VEC") != nullptr;     // experiments / tests: wherever it is legal
+  static const bool force_vec = env_flag("TMDIFF_CONV1_VEC");     // experiments / tests: wherever it is legal
   bool vec = plane % 4 == 0 && (blocks_vec >= 512 || force_vec) && aligned16(d->y) && aligned16(d->residual) && aligned16(d->xp_out);
   for (int i = 0; i < d->nseg; ++i) vec = vec && aligned16(d->seg_x[i]);
-  static const bool no_vec = getenv("TMDIFF_CONV1_DWORD") != nullptr;      // experiments: the dword kernel everywhere
+  static const bool no_vec = env_flag("TMDIFF_CONV1_DWORD");      // experiments: the dword kernel everywhere
   // small grids (fewer than two workgroups per CU of 256-position tiles) with at least 8 channel groups: the four waves of a
   // workgroup split the channels (KS = 4).  TMDIFF_CONV1_KSPLIT=0: never (experiments; tests force either form).
-  static const int ksplit_mode = [] {
-    const char* e = getenv("TMDIFF_CONV1_KSPLIT");
-    return e ? atoi(e) : -1;      // -1: by grid size, 0: never, 1: wherever it is legal
-  }();
+  static const int ksplit_mode = (int)env_long("TMDIFF_CONV1_KSPLIT", -1);   // -1: by grid size, 0: never, 1: wherever it is legal
   const long blocks_dword = (long)d->B * d->groups * ((plane + 255) / 256) * (cout_g % 64 == 0 ? cout_g / 64 : cout_g / 32);
   const bool ks = ksplit_mode != 0 && cin_g / (2 * G) >= 8 && (ksplit_mode == 1 || blocks_dword < 512);
   // (xp_supported: a raw input on the 16-byte kernel or on the small-grid kernel)

@@ -18,7 +18,6 @@
 // sub-tiles.  All LDS operand reads are ds_read_b32 with compile-time offsets; the fp32 MFMA
 // needs only two operand dwords per 64 cycles, so LDS bandwidth is not the limiter -- the
 // MFMA pipe is, and several workgroups per CU overlap one's staging with another's MFMAs.
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -30,17 +29,7 @@
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-// compile-time loop: f(std::integral_constant<int, I>) for I in [B, E) -- indices must be constants so that
-// the register arrays below are addressed statically (a runtime index would send them to scratch).
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, E>(f);
-  }
-}
+using namespace tmdiff;
 
 struct ConvArgs {
   int B, N, H, W;
@@ -97,14 +86,6 @@ struct Geo {
   static_assert(KC % 2 == 0, "K step is 2 channels");
   static_assert(LDS_IN % 4 == 0, "weight slab must start 16-B aligned");
 };
-
-// XCD-aware block id: blocks b and b+8 share an XCD (round-robin dispatch), so hand each XCD a
-// contiguous run of logical tiles -- neighbouring tiles (same input box, other channel tile;
-// adjacent boxes sharing halo lines) then hit in that XCD's L2.  Bijective for any grid size.
-__device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
-  const unsigned q = nwg / 8, r = nwg % 8, xcd = bid % 8, k = bid / 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
 
 // Software pipeline (one barrier per chunk, two LDS stages):
 //   issue global loads of chunk c+1 into registers -> MFMA loop over chunk c (stage c&1) -> apply the
@@ -637,18 +618,12 @@ int launch_splitk_reduce(const SplitKReduceArgs& r, hipStream_t st) {
 // Split target: once a launch has fewer workgroups than this, its input channels are divided until it has at least that
 // many (the chip holds 256 CUs x 2 workgroups of these kernels).  TMDIFF_SPLITK=<n> overrides (0 = never split).
 static long splitk_target() {
-  static const long t = [] {
-    const char* e = getenv("TMDIFF_SPLITK");
-    return e ? atol(e) : 384L;
-  }();
+  static const long t = env_long("TMDIFF_SPLITK", 384);
   return t;
 }
 
 bool epilogue_vec_ok(const tmdiff_conv3d_desc* d) {
-  static const bool on = [] {
-    const char* e = getenv("TMDIFF_EPILOGUE_VEC");   // experiments: "0" = the scalar epilogue everywhere
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = !env_off("TMDIFF_EPILOGUE_VEC");   // experiments: "0" = the scalar epilogue everywhere
   // (the dwordx4 epilogue addresses up to 128 channels of a sample through one descriptor of 32-bit offsets: planes <= 2^23)
   return on && d->W % 4 == 0 && aligned16(d->y) && aligned16(d->residual) && (d->y2_bf16 || aligned16(d->y2)) &&
          (long)d->N * d->H * d->W <= (1L << 23);
@@ -662,7 +637,7 @@ Conv3Plan plan_conv3(const tmdiff_conv3d_desc* d) {
   const long wg256 = boxes48 * ((cout_g + 63) / 64);
   // Layers whose 256-position grid would leave CUs idle or badly quantised (the 8x8x8 level: 128-384 workgroups) use
   // 128-position tiles; 32-channel tiles take 512 positions when that still gives every CU a workgroup.
-  static const long small_limit = getenv("TMDIFF_SMALLGRID") ? atol(getenv("TMDIFF_SMALLGRID")) : 2 * 256;  // experiments
+  static const long small_limit = env_long("TMDIFF_SMALLGRID", 2 * 256);  // experiments
   if (c64 && wg256 < small_limit && d->N > 2) {
     p.tile = 0;
     p.blocks = (long)d->B * d->groups * ((d->N + 1) / 2) * ((d->H + 7) / 8) * ((d->W + 7) / 8) * (cout_g / 64);
@@ -784,12 +759,12 @@ extern "C" int tmdiff_conv3d_fwd(const tmdiff_conv3d_desc* d, tmdiff_stream_t st
   TMDIFF_REQUIRE(d->drop_p >= 0.f && d->drop_p < 1.f, "conv3d_fwd: drop_p=%g", (double)d->drop_p);
   a.drop_seed = d->drop_seed; a.drop_seed_dev = d->drop_seed_dev; a.drop_thresh = drop_threshold(d->drop_p);
   a.drop_inv = d->drop_p > 0.f ? 1.0f / (1.0f - d->drop_p) : 0.f;
-  a.shift_stride = d->in_shift_stride > 0 ? d->in_shift_stride : (d->in_shift_stride < 0 ? 0 : d->Cin);
-  a.scale_stride = d->in_scale_stride > 0 ? d->in_scale_stride : (d->in_scale_stride < 0 ? 0 : d->Cin);
+  a.shift_stride = bank_stride(d->in_shift_stride, d->Cin);
+  a.scale_stride = bank_stride(d->in_scale_stride, d->Cin);
   a.residual = d->residual; a.out_scale = d->out_scale; a.y = d->y;
   a.y2 = d->y2; a.y2_shift = d->y2_shift; a.y2_scale = d->y2_scale; a.y2_act = d->y2_act;
-  a.y2_shift_stride = d->y2_shift_stride > 0 ? d->y2_shift_stride : (d->y2_shift_stride < 0 ? 0 : d->Cout);
-  a.y2_scale_stride = d->y2_scale_stride > 0 ? d->y2_scale_stride : (d->y2_scale_stride < 0 ? 0 : d->Cout);
+  a.y2_shift_stride = bank_stride(d->y2_shift_stride, d->Cout);
+  a.y2_scale_stride = bank_stride(d->y2_scale_stride, d->Cout);
   a.w_vec4 = (a.cout_g % 4 == 0) && aligned16(d->w_packed);
   a.vec4 = epilogue_vec_ok(d);
   hipStream_t st = as_stream(stream);

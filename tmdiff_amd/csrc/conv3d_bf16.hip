@@ -40,7 +40,8 @@
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
+using namespace tmdiff;
+
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
 struct BfArgs {
@@ -67,19 +68,6 @@ struct BfArgs {
   int vec4;                     // W % 4 == 0 and y / residual 16-byte aligned: dwordx4 epilogue through LDS
   unsigned long long* stamps;   // diagnostic builds only
 };
-
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, E>(f);
-  }
-}
-
-__device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
-  const unsigned q = nwg / 8, r = nwg % 8, xcd = bid % 8, k = bid / 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
 
 // stand-ins for absent shift / scale rows, so that the hand-off has no branches
 __device__ const float kZeros[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -1002,12 +990,12 @@ extern "C" int tmdiff_conv3d_fwd_bf16(const tmdiff_conv3d_desc* d, void* workspa
   a.wp = reinterpret_cast<const uint4*>(d->w_packed);
   a.bias = d->bias; a.bias_scale = d->bias_scale;
   a.in_shift = d->in_shift; a.in_scale = d->in_scale; a.in_act = d->in_act;
-  a.shift_stride = d->in_shift_stride > 0 ? d->in_shift_stride : (d->in_shift_stride < 0 ? 0 : d->Cin);
-  a.scale_stride = d->in_scale_stride > 0 ? d->in_scale_stride : (d->in_scale_stride < 0 ? 0 : d->Cin);
+  a.shift_stride = bank_stride(d->in_shift_stride, d->Cin);
+  a.scale_stride = bank_stride(d->in_scale_stride, d->Cin);
   a.residual = d->residual; a.out_scale = d->out_scale; a.y = d->y;
   a.y2 = reinterpret_cast<uint4*>(d->y2); a.y2_shift = d->y2_shift; a.y2_scale = d->y2_scale; a.y2_act = d->y2_act;
-  a.y2_shift_stride = d->y2_shift_stride > 0 ? d->y2_shift_stride : (d->y2_shift_stride < 0 ? 0 : d->Cout);
-  a.y2_scale_stride = d->y2_scale_stride > 0 ? d->y2_scale_stride : (d->y2_scale_stride < 0 ? 0 : d->Cout);
+  a.y2_shift_stride = bank_stride(d->y2_shift_stride, d->Cout);
+  a.y2_scale_stride = bank_stride(d->y2_scale_stride, d->Cout);
   // (the dwordx4 epilogue addresses its tensors through descriptors of 32-bit offsets: planes of at most 2^24 positions)
   a.vec4 = d->W % 4 == 0 && (!d->y || aligned16(d->y)) && (!d->residual || aligned16(d->residual)) && (long)d->N * d->H * d->W <= (1L << 24);
   a.stamps = TMDIFF_BF16_STAMPS ? static_cast<unsigned long long*>(d->splitk_ws) : nullptr;

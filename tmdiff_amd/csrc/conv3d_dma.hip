@@ -12,7 +12,6 @@
 //      word in device memory.
 // Two LDS stages, one barrier per chunk of KC input channels; the wave's instruction stream is MFMAs, their
 // operand ds_reads (compile-time offsets) and ~16 DMA issues per chunk.
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -20,15 +19,7 @@
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, E>(f);
-  }
-}
+using namespace tmdiff;
 
 struct DmaArgs {
   int B, N, H, W;
@@ -50,24 +41,6 @@ struct DmaArgs {
   float* part;               // split-K partial outputs [ksplit][B][Cout][plane] (NULL = no split)
   int vec4;                  // W % 4 == 0 and y / y2 / residual 16-byte aligned: dwordx4 epilogue (epilogue.h)
 };
-
-__device__ const float4 kZero4 = {0.f, 0.f, 0.f, 0.f};  // source of zero padding / filler lanes
-
-__device__ __forceinline__ void dma_b32(const float* src, float* dst) {
-#if defined(__HIP_DEVICE_COMPILE__)  // the builtin exists in the device pass only
-  __builtin_amdgcn_global_load_lds(src, dst, 4, 0, 0);
-#endif
-}
-__device__ __forceinline__ void dma_b128(const float* src, float* dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
-#endif
-}
-
-__device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
-  const unsigned q = nwg / 8, r = nwg % 8, xcd = bid % 8, k = bid / 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
 
 template <int KS, int NS, int MSUB, int KC, int TN, int TH, int TW>
 struct Geo {
@@ -140,12 +113,12 @@ __global__ void __launch_bounds__(256, 2) conv3d_dma_kernel(const DmaArgs a) {
     if constexpr (i < XK) {
       constexpr int k = i;
       const int q = wv + 4 * k;
-      if (G::XP % 4 == 0 || q < G::XP) dma_b32(xsrc[k] >= 0 ? xg + (long)c * KC * plane + xsrc[k] : zero, st + q * 64);
+      if (G::XP % 4 == 0 || q < G::XP) buf::dma_b32(xsrc[k] >= 0 ? xg + (long)c * KC * plane + xsrc[k] : zero, st + q * 64);
     } else if constexpr (i < NPIECE) {
       constexpr int k = i - XK;
       const int q = wv + 4 * k;
       if (G::WP % 4 == 0 || q < G::WP)
-        dma_b128(wsrc[k] >= 0 ? wg + (long)c * KC * G::TAPS * a.cout_g + wsrc[k] : zero, st + G::X_FLOATS + q * 256);
+        buf::dma_b128(wsrc[k] >= 0 ? wg + (long)c * KC * G::TAPS * a.cout_g + wsrc[k] : zero, st + G::X_FLOATS + q * 256);
     }
   };
 
@@ -379,8 +352,8 @@ extern "C" int tmdiff_conv3d_fwd_staged(const tmdiff_conv3d_desc* d, void* works
   a.wp = d->w_packed; a.bias = d->bias; a.bias_scale = d->bias_scale;
   a.residual = d->residual; a.out_scale = d->out_scale; a.y = d->y;
   a.y2 = d->y2; a.y2_shift = d->y2_shift; a.y2_scale = d->y2_scale; a.y2_act = d->y2_act;
-  a.y2_shift_stride = d->y2_shift_stride > 0 ? d->y2_shift_stride : (d->y2_shift_stride < 0 ? 0 : d->Cout);
-  a.y2_scale_stride = d->y2_scale_stride > 0 ? d->y2_scale_stride : (d->y2_scale_stride < 0 ? 0 : d->Cout);
+  a.y2_shift_stride = bank_stride(d->y2_shift_stride, d->Cout);
+  a.y2_scale_stride = bank_stride(d->y2_scale_stride, d->Cout);
   a.vec4 = tmdiff::epilogue_vec_ok(d);
 
   // tile configuration and split-K factor: plan_conv3 (conv3d.hip), the same rule as tmdiff_conv3d_fwd

@@ -18,7 +18,6 @@
 // (i, j) is then, per group, the 2 x 2 cells (hz, wz) = (i - i0 + e, j - j0 + f), e, f in {0, 1}: a tap is (group, dn, e, f)
 // = 48 per input channel, every operand read has a compile-time offset, and consecutive lanes read consecutive LDS words.
 // Weights arrive composed and packed as [ci][48 taps][co] (tmdiff_conv3d_ll_pack_weights).
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -26,15 +25,7 @@
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, E>(f);
-  }
-}
+using namespace tmdiff;
 
 struct LlArgs {
   int B, N, H, W;       // OUTPUT extents (H = Hi / 2, W = Wi / 2)
@@ -57,24 +48,6 @@ struct LlArgs {
   int ksplit, split_chunks;  // split-K over the input channels: ksplit ranges of split_chunks chunks (1, Cin / KC = no split)
   float* part;               // partial outputs [ksplit][B][Cout][plane] (NULL = no split), summed by splitk_reduce_kernel
 };
-
-__device__ const float4 kZero4 = {0.f, 0.f, 0.f, 0.f};  // source of zero padding / filler lanes
-
-__device__ __forceinline__ void dma_b32(const float* src, float* dst) {
-#if defined(__HIP_DEVICE_COMPILE__)  // the builtin exists in the device pass only
-  __builtin_amdgcn_global_load_lds(src, dst, 4, 0, 0);
-#endif
-}
-__device__ __forceinline__ void dma_b128(const float* src, float* dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
-#endif
-}
-
-__device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
-  const unsigned q = nwg / 8, r = nwg % 8, xcd = bid % 8, k = bid / 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
 
 constexpr int LL_TAPS = 48;   // (group p,q) x dn x e x f = 4 x 3 x 2 x 2
 
@@ -149,12 +122,12 @@ __global__ void __launch_bounds__(256, 2) conv3d_ll_kernel(const LlArgs a) {
     if constexpr (i < XK) {
       constexpr int k = i;
       const int q = wv + 4 * k;
-      if (G::XP % 4 == 0 || q < G::XP) dma_b32(xsrc[k] >= 0 ? xg + (long)c * KC * plane_in + xsrc[k] : zero, st + q * 64);
+      if (G::XP % 4 == 0 || q < G::XP) buf::dma_b32(xsrc[k] >= 0 ? xg + (long)c * KC * plane_in + xsrc[k] : zero, st + q * 64);
     } else if constexpr (i < NPIECE) {
       constexpr int k = i - XK;
       const int q = wv + 4 * k;
       if (G::WP % 4 == 0 || q < G::WP)
-        dma_b128(wsrc[k] >= 0 ? wg + (long)c * KC * LL_TAPS * a.cout_g + wsrc[k] : zero, st + G::X_FLOATS + q * 256);
+        buf::dma_b128(wsrc[k] >= 0 ? wg + (long)c * KC * LL_TAPS * a.cout_g + wsrc[k] : zero, st + G::X_FLOATS + q * 256);
     }
   };
   static_for<0, NPIECE>([&](auto ic) __attribute__((always_inline)) { issue_piece(ic, 0, st0); });
@@ -345,10 +318,7 @@ LlPlan plan_ll(const tmdiff_conv3d_desc* d) {
   const long wg256 = (long)d->B * ((N + 3) / 4) * ((H + 7) / 8) * ((W + 7) / 8) * (d->Cout / 64);
   p.small = wg256 < 2 * 256 && N > 2;
   p.blocks = p.small ? (long)d->B * ((N + 1) / 2) * ((H + 7) / 8) * ((W + 7) / 8) * (d->Cout / 64) : wg256;
-  static const long target = [] {
-    const char* e = getenv("TMDIFF_SPLITK");
-    return e ? atol(e) : 384L;
-  }();
+  static const long target = env_long("TMDIFF_SPLITK", 384);
   if (target <= 0 || p.blocks >= target) return p;
   const int nchunks = d->Cin / 2;
   for (int s = 2; s <= nchunks / 2; ++s) {            // at least two chunks per range
@@ -403,12 +373,9 @@ extern "C" int tmdiff_conv3d_ll_fwd(const tmdiff_conv3d_desc* d, float ll_scale,
   a.bias = d->bias; a.bias_scale = d->bias_scale * 2.0f * ll_scale;   // the (scaled) LL band of a constant
   a.residual = d->residual; a.out_scale = d->out_scale; a.y = d->y;
   a.y2 = d->y2; a.y2_shift = d->y2_shift; a.y2_scale = d->y2_scale; a.y2_act = d->y2_act;
-  a.y2_shift_stride = d->y2_shift_stride > 0 ? d->y2_shift_stride : (d->y2_shift_stride < 0 ? 0 : d->Cout);
-  a.y2_scale_stride = d->y2_scale_stride > 0 ? d->y2_scale_stride : (d->y2_scale_stride < 0 ? 0 : d->Cout);
-  static const bool vec_on = [] {
-    const char* e = getenv("TMDIFF_EPILOGUE_VEC");
-    return !(e && e[0] == '0');
-  }();
+  a.y2_shift_stride = bank_stride(d->y2_shift_stride, d->Cout);
+  a.y2_scale_stride = bank_stride(d->y2_scale_stride, d->Cout);
+  static const bool vec_on = !env_off("TMDIFF_EPILOGUE_VEC");
   a.vec4 = vec_on && a.W % 4 == 0 && aligned16(d->y) && aligned16(d->y2) && aligned16(d->residual) && (long)a.N * a.H * a.W <= (1L << 23);
   hipStream_t st = as_stream(stream);
   const LlPlan plan = plan_ll(d);

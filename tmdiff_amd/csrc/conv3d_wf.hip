@@ -23,7 +23,6 @@
 // the other stage -- 6 ds_read_b128, ~90 VALU operations and 24 ds_write_b32 per wave and chunk, placed between the MFMAs --
 // then (2) requests raw(c+2) into the same regions, and (3) requests the weights of chunk c+1.  A region is written (DMA) and
 // read (transform) by one wave only, so the single raw buffer needs no barrier of its own: one barrier per chunk.
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -38,17 +37,10 @@
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
+using namespace tmdiff;
+
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
-
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, E>(f);
-  }
-}
 
 struct WfArgs {
   int B, N, H, W;
@@ -98,10 +90,6 @@ using KArgs = const WfArgs*;
 __device__ __forceinline__ KArgs kargs() { return nullptr; }
 #endif
 
-// LDS-DMA through a buffer descriptor: 16 bytes per lane from base + voff (bytes) to dst + 16 * lane.  An offset at or beyond
-// the descriptor's size -- kOutside -- reads as zero: the zero padding of the convolution costs a select, not a second
-// source pointer (the address is one 32-bit register per lane; the base lives in scalar registers).
-constexpr unsigned kOutside = 0xFFFFFFF0u;
 // The compiler hoists every address that does not change from chunk to chunk out of the chunk loop and then, with 192 of the
 // 256 registers holding accumulators, spills it -- a scratch reload (and its vmcnt(0), which also waits for the LDS-DMA in
 // flight) in the middle of the MFMA stream.  opaque() hides a value's loop invariance: the few VALU operations that derive an
@@ -110,56 +98,6 @@ template <class T>
 __device__ __forceinline__ T opaque(T v) {
   asm volatile("" : "+v"(v));
   return v;
-}
-#if defined(__HIP_DEVICE_COMPILE__)  // the builtins exist in the device pass only
-using buf_rsrc = __amdgpu_buffer_rsrc_t;
-__device__ __forceinline__ buf_rsrc make_rsrc(const float* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ void dma_b128(buf_rsrc r, unsigned voff, float* dst) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, voff, 0, 0, 0);
-}
-// one dword per lane from base + voff + soff (soff uniform): the address is a 32-bit register, nothing 64-bit per lane
-__device__ __forceinline__ float buf_load(buf_rsrc r, unsigned voff, unsigned soff) {
-  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-// the epilogue's quads: 16 / 8 bytes per lane at base + voff; a lane at kOutside reads zero / stores nothing
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-__device__ __forceinline__ float4 buf_load4(buf_rsrc r, unsigned voff) {
-  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0);
-  return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-__device__ __forceinline__ void buf_store4(buf_rsrc r, unsigned voff, float a, float b, float c, float d) {
-  const u32x4 v = {__float_as_uint(a), __float_as_uint(b), __float_as_uint(c), __float_as_uint(d)};
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, 0, 0);
-}
-__device__ __forceinline__ void buf_store2(buf_rsrc r, unsigned voff, float a, float b) {
-  const u32x2 v = {__float_as_uint(a), __float_as_uint(b)};
-  __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, 0, 0);
-}
-#else
-struct buf_rsrc {};
-__device__ __forceinline__ buf_rsrc make_rsrc(const float*, unsigned) { return {}; }
-__device__ __forceinline__ void dma_b128(buf_rsrc, unsigned, float*) {}
-__device__ __forceinline__ float buf_load(buf_rsrc, unsigned, unsigned) { return 0.f; }
-__device__ __forceinline__ float4 buf_load4(buf_rsrc, unsigned) { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ void buf_store4(buf_rsrc, unsigned, float, float, float, float) {}
-__device__ __forceinline__ void buf_store2(buf_rsrc, unsigned, float, float) {}
-#endif
-
-__device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
-  const unsigned q = nwg / 8, r = nwg % 8, xcd = bid % 8, k = bid / 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
-
-// see conv3d_wino.hip: the second resident workgroup of a CU (LDS allocation not at 0) may wait once (experiments)
-__device__ __forceinline__ void stagger_start(int cycles, unsigned first_round) {
-  if (cycles <= 0 || blockIdx.x >= first_round) return;
-  const unsigned lds_alloc = __builtin_amdgcn_s_getreg(6 | (0 << 6) | (11 << 11));
-  if (lds_alloc == 0) return;
-  const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-  while ((long long)(__builtin_amdgcn_s_memtime() - t0) < (long long)cycles) __builtin_amdgcn_s_sleep(32);
 }
 
 // PAIR (planes of exactly 8 columns -- the 8x8 level): the tile's 16 columns are TWO IMAGES side by side, 8 columns each.  The
@@ -236,9 +174,9 @@ __device__ __forceinline__ void epilogue_wf(KArgs a, f32x16 (&out)[8], float bia
   // descriptors: 32 channels of sample b from channel g * cout_g + co0 on (PAIR and a second image: up to its 32 channels)
   const long cb = ((long)b * a->Cout + g * a->cout_g + co0) * plane;
   const unsigned span = (unsigned)(((PAIR && pimg_ok ? (long)a->Cout * plane : 0) + 32 * plane) * 4);
-  const buf_rsrc ry = make_rsrc(ydst ? ydst + cb : nullptr, ydst ? span : 0);
-  const buf_rsrc rr = make_rsrc(a->residual ? a->residual + cb : nullptr, a->residual ? span : 0);
-  const buf_rsrc r2 = make_rsrc(a->y2 ? a->y2 + cb : nullptr, a->y2 ? span : 0);
+  const buf::rsrc ry = buf::make(ydst ? ydst + cb : nullptr, ydst ? span : 0);
+  const buf::rsrc rr = buf::make(a->residual ? a->residual + cb : nullptr, a->residual ? span : 0);
+  const buf::rsrc r2 = buf::make(a->y2 ? a->y2 + cb : nullptr, a->y2 ? span : 0);
   unsigned toff[2], s2off[2];     // byte offsets of the lane's quad inside the descriptor (channel tc, band 0 of its band tile)
   const unsigned qplane4 = (unsigned)plane;                 // a quarter plane in bytes
 #pragma unroll
@@ -261,11 +199,9 @@ __device__ __forceinline__ void epilogue_wf(KArgs a, f32x16 (&out)[8], float bia
       // base is the same (4 channels of a quarter plane each); the lane's four columns are two of either column parity
       e2 = (h & 1) * 2 * (int)(plane >> 2) + (MO * bt) * (hw >> 2) + (h >> 1) * (a->W >> 1) + (w >> 1);
     }
-    toff[s] = ok ? (unsigned)((tc * (int)plane + e) * 4) : kOutside;
-    s2off[s] = ok ? (unsigned)((tc * (int)plane + e2) * 4) : kOutside;
+    toff[s] = ok ? (unsigned)((tc * (int)plane + e) * 4) : buf::kOutside;
+    s2off[s] = ok ? (unsigned)((tc * (int)plane + e2) * 4) : buf::kOutside;
   }
-  // (offset of channel tc + 8 j, band n from the lane's base: added only where the base is inside -- kOutside + anything would wrap)
-  auto at = [&](unsigned base, unsigned add) __attribute__((always_inline)) { return base >= kOutside ? kOutside : base + add; };
   float bias_t[4], sh2_t[4], sc2_t[4];
   const bool second = PAIR && ((tq & 3) >> 1);
 #pragma unroll
@@ -289,20 +225,20 @@ __device__ __forceinline__ void epilogue_wf(KArgs a, f32x16 (&out)[8], float bia
     constexpr int p = decltype(pc)::value, s = p & 1, n = p >> 1;
 #pragma unroll
     for (int j = 0; j < 4; ++j)     // (outside the image: zero, never stored)
-      rs[p % (DEPTH + 1)][j] = buf_load4(rr, at(toff[s], (unsigned)((8 * j * (int)plane + n * hw) * 4)));
+      rs[p % (DEPTH + 1)][j] = buf::load4(rr, buf::at(toff[s], (unsigned)((8 * j * (int)plane + n * hw) * 4)));
   };
   constexpr bool LL_OK = !Y && TT == 2 && !PAIR;
   const bool want_ll = LL_OK && a->yll != nullptr;
   // the quarter-size outputs: the same 32 channels, a quarter plane each (the LL pair of a lane: both rows inside or neither)
   const long cbq = cb >> 2;
   const unsigned spanq = (unsigned)(32 * plane);
-  const buf_rsrc rll = make_rsrc(want_ll ? a->yll + cbq : nullptr, want_ll ? spanq : 0);
+  const buf::rsrc rll = buf::make(want_ll ? a->yll + cbq : nullptr, want_ll ? spanq : 0);
   const bool want_hi = want_ll && a->yhi[0] != nullptr;
-  const buf_rsrc rh0 = make_rsrc(want_hi ? a->yhi[0] + cbq : nullptr, want_hi ? spanq : 0);
-  const buf_rsrc rh1 = make_rsrc(want_hi ? a->yhi[1] + cbq : nullptr, want_hi ? spanq : 0);
-  const buf_rsrc rh2 = make_rsrc(want_hi ? a->yhi[2] + cbq : nullptr, want_hi ? spanq : 0);
+  const buf::rsrc rh0 = buf::make(want_hi ? a->yhi[0] + cbq : nullptr, want_hi ? spanq : 0);
+  const buf::rsrc rh1 = buf::make(want_hi ? a->yhi[1] + cbq : nullptr, want_hi ? spanq : 0);
+  const buf::rsrc rh2 = buf::make(want_hi ? a->yhi[2] + cbq : nullptr, want_hi ? spanq : 0);
   // (s2off[0] of row 2 wv, whose row-parity term is zero, IS the quad's place in a quarter plane; channel stride plane / 4)
-  const unsigned lloff = (toff[0] >= kOutside || toff[1] >= kOutside) ? kOutside : s2off[0] - (unsigned)(tc * (int)plane * 4) + (unsigned)(tc * (int)plane);
+  const unsigned lloff = (toff[0] >= buf::kOutside || toff[1] >= buf::kOutside) ? buf::kOutside : s2off[0] - (unsigned)(tc * (int)plane * 4) + (unsigned)(tc * (int)plane);
   float vk[4][4];                   // row 2 wv of the current band (LL output only)
   if constexpr (RES) static_for<0, DEPTH>([&](auto pc) __attribute__((always_inline)) { load_res(pc); });
   static_for<0, 8>([&](auto pc) __attribute__((always_inline)) {
@@ -323,7 +259,7 @@ __device__ __forceinline__ void epilogue_wf(KArgs a, f32x16 (&out)[8], float bia
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = (v[e] + bias_t[j] + q[e]) * oscale;   // as the scalar epilogue
       const unsigned cj = (unsigned)((8 * j * (int)plane + n * hw) * 4);
-      if constexpr (Y) buf_store4(ry, at(toff[s], cj), v[0], v[1], v[2], v[3]);
+      if constexpr (Y) buf::store4(ry, buf::at(toff[s], cj), make_float4(v[0], v[1], v[2], v[3]));
       if constexpr (LL_OK) {
         if (want_ll) {      // (uniform)
           if constexpr (s == 0) {
@@ -331,7 +267,7 @@ __device__ __forceinline__ void epilogue_wf(KArgs a, f32x16 (&out)[8], float bia
             for (int e = 0; e < 4; ++e) vk[j][e] = v[e];
           } else {
             // band MO * bt + n, row (h0 + 2 wv) / 2, columns (w0 + 4 (tq & 3)) / 2 and the next of the quarter-size plane
-            const unsigned ol = at(lloff, (unsigned)((8 * j * (int)(plane >> 2) + n * (hw >> 2)) * 4));
+            const unsigned ol = buf::at(lloff, (unsigned)((8 * j * (int)(plane >> 2) + n * (hw >> 2)) * 4));
             const float ll0 = ((vk[j][0] + vk[j][1]) + (v[0] + v[1])) * 0.25f, ll1 = ((vk[j][2] + vk[j][3]) + (v[2] + v[3])) * 0.25f;
             if (want_hi) {  // (uniform)
               // the whole transform of the 2 x 2 blocks (a b / c d): LL / 2 through the consumer's prologue, LH = (a - b + c - d) / 2,
@@ -339,13 +275,13 @@ __device__ __forceinline__ void epilogue_wf(KArgs a, f32x16 (&out)[8], float bia
               if constexpr (Y2) {
                 const float x0 = ll0 + sh2_t[j], x1 = ll1 + sh2_t[j];
                 const float a0 = tmdiff::silu_f(x0), a1 = tmdiff::silu_f(x1);
-                buf_store2(rll, ol, (a->y2_act ? a0 : x0) * sc2_t[j], (a->y2_act ? a1 : x1) * sc2_t[j]);
-                buf_store2(rh0, ol, ((vk[j][0] - vk[j][1]) + (v[0] - v[1])) * 0.5f, ((vk[j][2] - vk[j][3]) + (v[2] - v[3])) * 0.5f);
-                buf_store2(rh1, ol, ((vk[j][0] + vk[j][1]) - (v[0] + v[1])) * 0.5f, ((vk[j][2] + vk[j][3]) - (v[2] + v[3])) * 0.5f);
-                buf_store2(rh2, ol, ((vk[j][0] - vk[j][1]) - (v[0] - v[1])) * 0.5f, ((vk[j][2] - vk[j][3]) - (v[2] - v[3])) * 0.5f);
+                buf::store2(rll, ol, make_float2((a->y2_act ? a0 : x0) * sc2_t[j], (a->y2_act ? a1 : x1) * sc2_t[j]));
+                buf::store2(rh0, ol, make_float2(((vk[j][0] - vk[j][1]) + (v[0] - v[1])) * 0.5f, ((vk[j][2] - vk[j][3]) + (v[2] - v[3])) * 0.5f));
+                buf::store2(rh1, ol, make_float2(((vk[j][0] + vk[j][1]) - (v[0] + v[1])) * 0.5f, ((vk[j][2] + vk[j][3]) - (v[2] + v[3])) * 0.5f));
+                buf::store2(rh2, ol, make_float2(((vk[j][0] - vk[j][1]) - (v[0] - v[1])) * 0.5f, ((vk[j][2] - vk[j][3]) - (v[2] - v[3])) * 0.5f));
               }
             } else {
-              buf_store2(rll, ol, ll0, ll1);
+              buf::store2(rll, ol, make_float2(ll0, ll1));
             }
           }
         }
@@ -359,11 +295,11 @@ __device__ __forceinline__ void epilogue_wf(KArgs a, f32x16 (&out)[8], float bia
           u[e] = (a->y2_act ? xa : x) * sc2_t[j];
         }
         if (a->y2_s2d) {                   // (uniform)
-          const unsigned o2 = at(s2off[s], (unsigned)((8 * j * (int)plane + n * (hw >> 2)) * 4));
-          buf_store2(r2, o2, u[0], u[2]);
-          buf_store2(r2, at(o2, qplane4), u[1], u[3]);
+          const unsigned o2 = buf::at(s2off[s], (unsigned)((8 * j * (int)plane + n * (hw >> 2)) * 4));
+          buf::store2(r2, o2, make_float2(u[0], u[2]));
+          buf::store2(r2, buf::at(o2, qplane4), make_float2(u[1], u[3]));
         } else {
-          buf_store4(r2, at(toff[s], cj), u[0], u[1], u[2], u[3]);
+          buf::store4(r2, buf::at(toff[s], cj), make_float4(u[0], u[1], u[2], u[3]));
         }
       }
     }
@@ -422,23 +358,23 @@ __global__ void __launch_bounds__(256, 2) conv3d_wf_kernel(const WfArgs a) {
   unsigned xlane_off;
   if constexpr (PAIR) {     // quad (image, half row): no halo columns, they are the padding
     const int img = (xq % RQ) >> 1;
-    xlane_off = (lane < G::PLANES && (img == 0 || pimg_ok)) ? (unsigned)((img * xbs + (xq / RQ) * hw + 4 * (xq & 1)) * 4) : kOutside;
+    xlane_off = (lane < G::PLANES && (img == 0 || pimg_ok)) ? (unsigned)((img * xbs + (xq / RQ) * hw + 4 * (xq & 1)) * 4) : buf::kOutside;
   } else {
     const int xwq = w0 - 4 + 4 * (xq % RQ);
-    xlane_off = (lane < G::PLANES && xwq >= 0 && xwq < a.W) ? (unsigned)(((xq / RQ) * hw + xwq) * 4) : kOutside;
+    xlane_off = (lane < G::PLANES && xwq >= 0 && xwq < a.W) ? (unsigned)(((xq / RQ) * hw + xwq) * 4) : buf::kOutside;
   }
   auto issue_raw = [&](auto kc_, int c) __attribute__((always_inline)) {
     constexpr int k = decltype(kc_)::value;
     const int p = wv + 4 * k;
     if (G::XP % 4 == 0 || p < G::XP) {
-      const buf_rsrc r = make_rsrc(xg + (long)c * KC * plane, xbytes);
+      const buf::rsrc r = buf::make(xg + (long)c * KC * plane, xbytes);
       const int region = p * G::RPP + (G::RPP > 1 ? xsub : 0);
       const int kc = region / HH, row = region - kc * HH;
       const int h = h0 - 1 + row;
       const bool ok = h >= 0 && h < a.H && region < G::NREG;
       const unsigned lo = opaque(xlane_off);
-      const unsigned voff = ok ? lo + (unsigned)((kc * (int)plane + h * a.W) * 4) : kOutside;
-      if (lane < G::PLANES) dma_b128(r, lo >= kOutside ? kOutside : voff, raw + p * G::PSTRIDE);
+      const unsigned voff = ok ? lo + (unsigned)((kc * (int)plane + h * a.W) * 4) : buf::kOutside;
+      if (lane < G::PLANES) buf::dma_b128(r, lo >= buf::kOutside ? buf::kOutside : voff, 0, raw + p * G::PSTRIDE);
     }
   };
   const unsigned wlane_off = (unsigned)(((lane >> 3) * a.cout_g + (lane & 7) * 4) * 4);
@@ -446,9 +382,9 @@ __global__ void __launch_bounds__(256, 2) conv3d_wf_kernel(const WfArgs a) {
     constexpr int k = decltype(kc_)::value;
     const int q = wv + 4 * k;
     if (G::WP % 4 == 0 || q < G::WP) {
-      const buf_rsrc r = make_rsrc(wg + (long)c * KC * W_TAPS * a.cout_g, wbytes);
+      const buf::rsrc r = buf::make(wg + (long)c * KC * W_TAPS * a.cout_g, wbytes);
       // (rows beyond the chunk's slab -- the tail lanes of the last piece -- read as zero into the stage's padding)
-      dma_b128(r, opaque(wlane_off) + (unsigned)(q * 8 * a.cout_g * 4), st + G::V_FLOATS + q * 256);
+      buf::dma_b128(r, opaque(wlane_off) + (unsigned)(q * 8 * a.cout_g * 4), 0, st + G::V_FLOATS + q * 256);
     }
   };
 
@@ -653,7 +589,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_wf_kernel(const WfArgs a) {
       __syncthreads();
       // x through a buffer descriptor over this sample's rc_cin channels: per-lane byte offset (channel parity, band, row,
       // column) in one 32-bit register per output block, the channel pair of a K-step as a scalar offset
-      const buf_rsrc xr = make_rsrc(a.rc_x + (long)b * a.rc_cin * plane, (unsigned)((long)a.rc_cin * plane * 4));
+      const buf::rsrc xr = buf::make(a.rc_x + (long)b * a.rc_cin * plane, (unsigned)((long)a.rc_cin * plane * 4));
       unsigned xo[8];                                     // lane offset of block (s, n): band, row, column of MFMA column l31
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
@@ -667,21 +603,21 @@ __global__ void __launch_bounds__(256, 2) conv3d_wf_kernel(const WfArgs a) {
       const int ngrp = a.rc_cin / (2 * GJ);               // rc_cin % 32 == 0 (host)
       const unsigned pair_bytes = (unsigned)(2 * plane * 4);
       float xv[2][GJ];
-      auto fetch = [&](int jg, auto ic, auto bufc) __attribute__((always_inline)) {
-        constexpr int i = decltype(ic)::value, buf = decltype(bufc)::value;
+      auto fetch = [&](int jg, auto ic, auto slotc) __attribute__((always_inline)) {
+        constexpr int i = decltype(ic)::value, slot = decltype(slotc)::value;
         const unsigned s0 = (unsigned)(jg * GJ) * pair_bytes;
 #pragma unroll
-        for (int j = 0; j < GJ; ++j) xv[buf][j] = buf_load(xr, xo[i], s0 + (unsigned)j * pair_bytes);
+        for (int j = 0; j < GJ; ++j) xv[slot][j] = buf::load(xr, xo[i], s0 + (unsigned)j * pair_bytes);
       };
       fetch(0, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
       for (int jg = 0; jg < ngrp; ++jg) {
         const float* wrow = wl + (jg * 2 * GJ + khalf) * 32 + l31;
         static_for<0, 8>([&](auto ic) __attribute__((always_inline)) {
-          constexpr int i = decltype(ic)::value, buf = i & 1;
-          if constexpr (i < 7) fetch(jg, std::integral_constant<int, i + 1>{}, std::integral_constant<int, buf ^ 1>{});
+          constexpr int i = decltype(ic)::value, slot = i & 1;
+          if constexpr (i < 7) fetch(jg, std::integral_constant<int, i + 1>{}, std::integral_constant<int, slot ^ 1>{});
           else if (jg + 1 < ngrp) fetch(jg + 1, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
 #pragma unroll
-          for (int j = 0; j < GJ; ++j) out[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(wrow[2 * j * 32], xv[buf][j], out[i], 0, 0, 0);
+          for (int j = 0; j < GJ; ++j) out[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(wrow[2 * j * 32], xv[slot][j], out[i], 0, 0, 0);
         });
       }
       __syncthreads();                                    // the slab is dead before the epilogue borrows the same LDS
@@ -724,10 +660,8 @@ int launch(WfArgs& a, hipStream_t st) {
   const long blocks = (long)a.ksplit * (PAIR ? (a.B + 1) / 2 : a.B) * a.groups * a.tiles_h * a.tiles_w * a.tiles_co;
   if (blocks <= 0 || blocks > 0x7fffffffL) return tmdiff::fail(TMDIFF_E_INVALID, "conv3d_wf_fwd: grid of %ld blocks", blocks);
   a.total_blocks = (unsigned)blocks;
-  static const double stagger_chunks = [] {
-    const char* e = getenv("TMDIFF_WF_STAGGER");     // experiments: delay of every CU's second resident workgroup, in chunk times
-    return e ? atof(e) : 0.0;
-  }();
+  // experiments: delay of every CU's second resident workgroup, in chunk times
+  static const double stagger_chunks = env_double("TMDIFF_WF_STAGGER", 0.0);
   a.first_round = 512;
   a.stagger = blocks > 512 ? (int)(stagger_chunks * 2.0 * 54 * 2 * 64) : 0;
   conv3d_wf_kernel<TT, TH, TW, PAIR, LLM><<<(unsigned)blocks, 256, 0, st>>>(a);
@@ -766,10 +700,7 @@ long wf_tiles(const tmdiff_conv3d_desc* d) {
 // TMDIFF_SPLITK=0: never.  pairs: the ranges must hold whole pairs of chunks (the composed-LL mode, whose chunks alternate in
 // row parity).
 int wf_ksplit(const tmdiff_conv3d_desc* d, bool pairs = false) {
-  static const long target = [] {
-    const char* e = getenv("TMDIFF_SPLITK");
-    return e ? atol(e) : 256L;
-  }();
+  static const long target = env_long("TMDIFF_SPLITK", 256);
   const long tiles = wf_tiles(d);
   const int nchunks = d->Cin / d->groups / 2;
   const int ksteps = pairs ? 24 : 54;
@@ -782,10 +713,8 @@ int wf_ksplit(const tmdiff_conv3d_desc* d, bool pairs = false) {
       best = s;
       if (tiles * s >= target) break;
     }
-  static const long long_range = [] {      // (experiments: TMDIFF_SPLITK_LONG=<K-steps per range from which a range counts as long>)
-    const char* e = getenv("TMDIFF_SPLITK_LONG");
-    return e ? atol(e) : 1700L;
-  }();
+  // (experiments: TMDIFF_SPLITK_LONG=<K-steps per range from which a range counts as long>)
+  static const long long_range = env_long("TMDIFF_SPLITK_LONG", 1700);
   if (tiles * best < 384 && ok(2 * best) && (long)(nchunks / (2 * best)) * ksteps >= long_range) best *= 2;
   return best;
 }
@@ -870,8 +799,8 @@ int wf_forward(const tmdiff_conv3d_desc* d, void* workspace, tmdiff_stream_t str
   a.y2 = d->y2; a.y2_shift = d->y2_shift; a.y2_scale = d->y2_scale; a.y2_act = d->y2_act;
   a.y2_s2d = d->y2 && d->y2_s2d ? 1 : 0;
   if (a.y2_s2d) TMDIFF_REQUIRE(d->H % 2 == 0 && d->W % 4 == 0, "conv3d_wf_fwd: the space-to-depth second output needs even H and W %% 4 == 0");
-  a.y2_shift_stride = d->y2_shift_stride > 0 ? d->y2_shift_stride : (d->y2_shift_stride < 0 ? 0 : d->Cout);
-  a.y2_scale_stride = d->y2_scale_stride > 0 ? d->y2_scale_stride : (d->y2_scale_stride < 0 ? 0 : d->Cout);
+  a.y2_shift_stride = bank_stride(d->y2_shift_stride, d->Cout);
+  a.y2_scale_stride = bank_stride(d->y2_scale_stride, d->Cout);
   a.vec4 = 1;
   a.stamps = TMDIFF_WF_STAMPS ? static_cast<unsigned long long*>(d->splitk_ws) : nullptr;
   a.ksplit = 1; a.split_chunks = a.cin_g / 2; a.part = nullptr;

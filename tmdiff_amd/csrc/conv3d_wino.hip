@@ -18,7 +18,6 @@
 // channel, the TT x NP planes (t, k) with a one-pixel halo in (h, w); tap (dh, dw, k) multiplies plane k shifted by (dh, dw)
 // into accumulator k; at the end of the tile the waves exchange partial output sums through LDS and hand the output bands
 // to the shared vector epilogue.
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -33,15 +32,7 @@
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, E>(f);
-  }
-}
+using namespace tmdiff;
 
 // transform matrices (NP = 4: F(2,3); NP = 6: F(4,3))
 template <int NP> struct WM;
@@ -190,33 +181,6 @@ __global__ void __launch_bounds__(256) wino_input_kernel(const WinoInArgs a) {
   }
 }
 
-__device__ const float4 kZero4 = {0.f, 0.f, 0.f, 0.f};  // source of zero padding / filler lanes
-
-__device__ __forceinline__ void dma_b128(const float* src, float* dst) {
-#if defined(__HIP_DEVICE_COMPILE__)  // the builtin exists in the device pass only
-  __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
-#endif
-}
-
-__device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
-  const unsigned q = nwg / 8, r = nwg % 8, xcd = bid % 8, k = bid / 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
-
-// Two workgroups share a CU (LDS-limited) and one matrix pipe per SIMD.  Launched together and with equal tile times they
-// stay in lockstep for the whole launch: both run their MFMA phases together (each at half the pipe) and both reach their
-// epilogues together -- the pipe idles while every CU of the chip stores its outputs at once (HBM-bound burst: 64 -> 64 at
-// 64x64, B = 32 writes / reads 0.8 GB per launch in four bursts).  Delaying the second resident workgroup of every CU ONCE,
-// by about an epilogue, puts the pairs in anti-phase for good: one computes at the full pipe rate while its partner stores.
-// The second resident is the one whose LDS allocation does not start at 0 (HW_REG_LDS_ALLOC, base field).
-__device__ __forceinline__ void stagger_start(int cycles, unsigned first_round) {
-  if (cycles <= 0 || blockIdx.x >= first_round) return;
-  const unsigned lds_alloc = __builtin_amdgcn_s_getreg(6 | (0 << 6) | (11 << 11));   // hwreg(HW_REG_LDS_ALLOC, 0, 12): LDS_BASE
-  if (lds_alloc == 0) return;
-  const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-  while ((long long)(__builtin_amdgcn_s_memtime() - t0) < (long long)cycles) __builtin_amdgcn_s_sleep(32);
-}
-
 template <int NS, int MSUB, int KC, int TT, int TH, int TW, int NP>
 struct GeoW {
   static constexpr int CO = 32 * MSUB;
@@ -307,12 +271,12 @@ __global__ void __launch_bounds__(256, 2) conv3d_wino_kernel(const WinoArgs a) {
     if constexpr (i < XK) {
       constexpr int k = i;
       const int q = wv + 4 * k;
-      if (G::XP % 4 == 0 || q < G::XP) dma_b128(xsrc[k] >= 0 ? xg + (long)c * KC * plane_v + xsrc[k] : zero, st + q * 256);
+      if (G::XP % 4 == 0 || q < G::XP) buf::dma_b128(xsrc[k] >= 0 ? xg + (long)c * KC * plane_v + xsrc[k] : zero, st + q * 256);
     } else if constexpr (i < NPIECE) {
       constexpr int k = i - XK;
       const int q = wv + 4 * k;
       if (G::WP % 4 == 0 || q < G::WP)
-        dma_b128(wsrc[k] >= 0 ? wg + (long)c * KC * W_TAPS * a.cout_g + wsrc[k] : zero, st + G::X_FLOATS + q * 256);
+        buf::dma_b128(wsrc[k] >= 0 ? wg + (long)c * KC * W_TAPS * a.cout_g + wsrc[k] : zero, st + G::X_FLOATS + q * 256);
     }
   };
   static_for<0, NPIECE>([&](auto ic) __attribute__((always_inline)) { issue_piece(ic, 0, st0); });
@@ -488,10 +452,7 @@ int launch(WinoArgs& a, hipStream_t st) {
   a.total_blocks = (unsigned)blocks;
   // stagger (see stagger_start): TMDIFF_WINO_STAGGER = delay in units of one chunk's MFMA time of a workgroup pair
   // (2 x KSTEPS x MF x 64 cycles); only worth it when there are several rounds of workgroups
-  static const double stagger_chunks = [] {
-    const char* e = getenv("TMDIFF_WINO_STAGGER");
-    return e ? atof(e) : 0.0;
-  }();
+  static const double stagger_chunks = env_double("TMDIFF_WINO_STAGGER", 0.0);
   constexpr int NPIECE_UNUSED = 0; (void)NPIECE_UNUSED;
   const double chunk_cycles = 2.0 * (KC / 2) * 9 * (NP / 2) * NS * MSUB * 64;
   a.first_round = 512;
@@ -571,10 +532,7 @@ bool wino_ok(const tmdiff_conv3d_desc* d) {
 // would (a workgroup covers TT = 2 tiles along the bands: with N = 4 the second F(4,3) tile would be empty -- 2 x 13.5
 // multiply-adds per output against F(2,3)'s 18), else F(2,3); TMDIFF_WINO_F4=0 (experiments): always F(2,3)
 int planes_for(int N) {
-  static const bool f4 = [] {
-    const char* e = getenv("TMDIFF_WINO_F4");
-    return !(e && e[0] == '0');
-  }();
+  static const bool f4 = !env_off("TMDIFF_WINO_F4");
   if (!f4 || N % 4) return 4;
   const int t6 = N / 4, t4 = N / 2;
   const double cost6 = 13.5 * (2 * ((t6 + 1) / 2)) / t6, cost4 = 18.0 * (2 * ((t4 + 1) / 2)) / t4;
@@ -665,8 +623,8 @@ extern "C" int tmdiff_conv3d_wino_fwd_planes(const tmdiff_conv3d_desc* d, void* 
   q.B = d->B; q.Cin = d->Cin; q.N = d->N; q.H = d->H; q.W = d->W; q.nseg = d->nseg;
   for (int i = 0; i < 3; ++i) { q.seg_c[i] = i < d->nseg ? d->seg_c[i] : 0; q.seg_x[i] = i < d->nseg ? d->seg_x[i] : nullptr; }
   q.in_shift = d->in_shift; q.in_scale = d->in_scale; q.in_act = d->in_act;
-  q.shift_stride = d->in_shift_stride > 0 ? d->in_shift_stride : (d->in_shift_stride < 0 ? 0 : d->Cin);
-  q.scale_stride = d->in_scale_stride > 0 ? d->in_scale_stride : (d->in_scale_stride < 0 ? 0 : d->Cin);
+  q.shift_stride = bank_stride(d->in_shift_stride, d->Cin);
+  q.scale_stride = bank_stride(d->in_scale_stride, d->Cin);
   q.v = static_cast<float*>(workspace);
   q.xp = xp_out;
   q.drop_seed = d->drop_seed; q.drop_seed_dev = d->drop_seed_dev; q.drop_thresh = drop_threshold(d->drop_p);
@@ -690,8 +648,8 @@ extern "C" int tmdiff_conv3d_wino_fwd_planes(const tmdiff_conv3d_desc* d, void* 
   a.bias = d->bias; a.bias_scale = d->bias_scale;
   a.residual = d->residual; a.out_scale = d->out_scale; a.y = d->y;
   a.y2 = d->y2; a.y2_shift = d->y2_shift; a.y2_scale = d->y2_scale; a.y2_act = d->y2_act;
-  a.y2_shift_stride = d->y2_shift_stride > 0 ? d->y2_shift_stride : (d->y2_shift_stride < 0 ? 0 : d->Cout);
-  a.y2_scale_stride = d->y2_scale_stride > 0 ? d->y2_scale_stride : (d->y2_scale_stride < 0 ? 0 : d->Cout);
+  a.y2_shift_stride = bank_stride(d->y2_shift_stride, d->Cout);
+  a.y2_scale_stride = bank_stride(d->y2_scale_stride, d->Cout);
   a.vec4 = 1;
   a.stamps = TMDIFF_WINO_STAMPS ? static_cast<unsigned long long*>(d->splitk_ws) : nullptr;
   if (!(d->W % 4 == 0 && aligned16(d->y) && aligned16(d->y2) && aligned16(d->residual) && (long)d->N * d->H * d->W <= (1L << 23)))

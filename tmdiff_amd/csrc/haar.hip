@@ -288,8 +288,8 @@ int make_prologue(const tmdiff_plane_prologue* p, int64_t planes, PlanePrologue&
   TMDIFF_REQUIRE(p->C > 0 && p->n_per_channel > 0 && planes % ((int64_t)p->C * p->n_per_channel) == 0,
                  "haar prologue: planes=%ld is not B * C=%d * n=%d", (long)planes, p->C, p->n_per_channel);
   q.shift = p->shift; q.scale = p->scale; q.C = p->C; q.n_per_channel = p->n_per_channel; q.act = p->act; q.on = 1;
-  q.shift_stride = p->shift_stride > 0 ? p->shift_stride : (p->shift_stride < 0 ? 0 : p->C);
-  q.scale_stride = p->scale_stride > 0 ? p->scale_stride : (p->scale_stride < 0 ? 0 : p->C);
+  q.shift_stride = tmdiff::bank_stride(p->shift_stride, p->C);
+  q.scale_stride = tmdiff::bank_stride(p->scale_stride, p->C);
   return TMDIFF_OK;
 }
 }  // namespace

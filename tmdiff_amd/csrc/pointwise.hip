@@ -188,7 +188,7 @@ extern "C" int tmdiff_stem_fwd_scaled(const float* xin, const float* pan, const 
                                       const float* out_scale, int32_t out_scale_stride, float* y, int32_t B, int32_t Cout,
                                       int32_t N, int32_t H, int32_t W, int32_t apply_silu, tmdiff_stream_t stream) {
   using namespace tmdiff;
-  const int oss = out_scale_stride > 0 ? out_scale_stride : (out_scale_stride < 0 ? 0 : Cout);
+  const int oss = bank_stride(out_scale_stride, Cout);
   TMDIFF_REQUIRE(w && y, "stem_fwd: NULL weights/output");
   TMDIFF_REQUIRE((ms && pan) || (!ms && xin), "stem_fwd: give either (pan, ms) or xin");
   TMDIFF_REQUIRE(B >= 0 && Cout > 0 && N > 0 && H > 0 && W > 0 && B <= 65535, "stem_fwd: bad extents");
@@ -214,7 +214,7 @@ extern "C" int tmdiff_stem_fwd_pack_bf16(const float* xin, const float* pan, con
   TMDIFF_REQUIRE((ms && pan) || (!ms && xin), "stem_fwd_pack_bf16: give either (pan, ms) or xin");
   TMDIFF_REQUIRE(B >= 0 && Cout > 0 && Cout % 8 == 0 && N > 0 && H > 0 && W > 0 && B <= 65535, "stem_fwd_pack_bf16: bad extents");
   if (B == 0) return TMDIFF_OK;
-  const int oss = out_scale_stride > 0 ? out_scale_stride : (out_scale_stride < 0 ? 0 : Cout);
+  const int oss = bank_stride(out_scale_stride, Cout);
   const long HW = (long)H * W, P = HW * N;
   stem_pack_bf16_kernel<<<dim3((unsigned)((P + 255) / 256), B), 256, 0, as_stream(stream)>>>(
       xin, pan, ms, w, bias, static_cast<uint4*>(units), Cout, P, HW, apply_silu, out_scale, oss);
@@ -227,7 +227,7 @@ extern "C" int tmdiff_head_fwd(const float* x, const float* w, const float* scal
   TMDIFF_REQUIRE(x && w && y, "head_fwd: NULL pointer");
   TMDIFF_REQUIRE(B >= 0 && C > 0 && C <= 4096 && P > 0 && B <= 65535, "head_fwd: bad extents B=%d C=%d", B, C);
   if (B == 0) return TMDIFF_OK;
-  const int ss = scale_stride > 0 ? scale_stride : (scale_stride < 0 ? 0 : C);
+  const int ss = bank_stride(scale_stride, C);
   const bool vec = P % 4 == 0 && aligned16(x) && aligned16(y);
   if (vec) {
     dim3 grid((unsigned)((P / 4 + 255) / 256), B);

@@ -23,42 +23,14 @@
 // the 9 (dh, dw) accumulators and takes two rows of each box; two workgroups per CU (78 KB of LDS each, double-buffered
 // boxes); at the end the four waves' partial sums are added through LDS in a fixed order and go to
 // ws[split][group][k][(dh, dw)][CoP][CiP]; ww_reduce_kernel sums the splits (fixed order: deterministic) and applies A'^T.
-#include <cstdlib>
 #include <type_traits>
 
+#include "bufaddr.h"
 #include "common.h"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, E>(f);
-  }
-}
-
-#if defined(__HIP_DEVICE_COMPILE__)  // the builtins exist in the device pass only
-using buf_rsrc = __amdgpu_buffer_rsrc_t;
-__device__ __forceinline__ buf_rsrc make_rsrc(const float* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, bytes, 0x00020000);
-}
-// 16 bytes per lane from base + voff + soff (bytes; soff wave-uniform) to dst + 16 * lane
-__device__ __forceinline__ void dma_b128(buf_rsrc r, unsigned voff, unsigned soff, float* dst) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, voff, soff, 0, 0);
-}
-#else
-struct buf_rsrc {};
-__device__ __forceinline__ buf_rsrc make_rsrc(const float*, unsigned) { return {}; }
-__device__ __forceinline__ void dma_b128(buf_rsrc, unsigned, unsigned, float*) {}
-#endif
-
-__device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
-  const unsigned q = nwg / 8, r = nwg % 8, xcd = bid % 8, k = bid / 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
+using namespace tmdiff;
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Transform passes.  One workgroup = one row of the padded plane x one band tile x 32 channels x 64 columns: it reads the
@@ -235,8 +207,8 @@ __global__ void __launch_bounds__(256, 2) ww_gemm_kernel(const WwArgs a) {
   const int g = __builtin_amdgcn_readfirstlane(id / 6);
   const int Hp = a.Hb + 2, Wp = a.Wb + 2;
   const long gplane = (long)a.Q * a.Hb * a.Wb * a.CoP, xplane = (long)a.Q * Hp * Wp * a.CiP;
-  const buf_rsrc rg = make_rsrc(a.gh + ((long)g * 6 + k) * gplane, (unsigned)(gplane * 4));
-  const buf_rsrc rx = make_rsrc(a.xh + ((long)g * 6 + k) * xplane, (unsigned)(xplane * 4));
+  const buf::rsrc rg = buf::make(a.gh + ((long)g * 6 + k) * gplane, (unsigned)(gplane * 4));
+  const buf::rsrc rx = buf::make(a.xh + ((long)g * 6 + k) * xplane, (unsigned)(xplane * 4));
 
   // per-lane byte offsets of this wave's pieces inside a box (piece j = wv + 4 i: positions 8 j .. 8 j + 7, lane = (position, quad))
   unsigned gv[G::GPW], xv[G::XPW];
@@ -273,10 +245,10 @@ __global__ void __launch_bounds__(256, 2) ww_gemm_kernel(const WwArgs a) {
   auto issue_piece = [&](auto ic, float* st) __attribute__((always_inline)) {
     constexpr int i = decltype(ic)::value;
     if constexpr (i < G::GPW) {
-      dma_b128(rg, gv[i], gso, st + (wv + 4 * i) * 256);
+      buf::dma_b128(rg, gv[i], gso, st + (wv + 4 * i) * 256);
     } else if constexpr (i < G::NPW) {
       constexpr int ii = i - G::GPW;
-      if (G::XP % 4 == 0 || wv + 4 * ii < G::XP) dma_b128(rx, xv[ii], xso, st + G::G_FLOATS + (wv + 4 * ii) * 256);
+      if (G::XP % 4 == 0 || wv + 4 * ii < G::XP) buf::dma_b128(rx, xv[ii], xso, st + G::G_FLOATS + (wv + 4 * ii) * 256);
     }
   };
 
@@ -553,10 +525,7 @@ extern "C" int tmdiff_conv3d_wgrad_wino_bias(const tmdiff_conv3d_desc* d, const 
   }
   // (timing experiments: TMDIFF_WW_PHASES = bit mask of the phases that run -- 1 transform passes, 2 accumulation, 4 reduction;
   //  anything but 7 leaves dw wrong or stale)
-  static const int phases = [] {
-    const char* e = getenv("TMDIFF_WW_PHASES");
-    return e ? atoi(e) : 7;
-  }();
+  static const int phases = (int)env_long("TMDIFF_WW_PHASES", 7);
   int rc = TMDIFF_OK;
   if (phases & 1) {
     const float* gseg[3] = {g, nullptr, nullptr};
