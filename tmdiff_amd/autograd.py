@@ -67,13 +67,11 @@ def _conv_forward(meta, weight, bias, shift, scale, residual, mask, segs, need_w
             xp = torch.empty(b, cin, n, h, wd, device=segs[0].device, dtype=torch.float32)
     kw = dict(bias=bias, bias_scale=bias_scale, in_act=act, in_mask=mask, drop=drop, residual=residual, out_scale=out_scale,
               xp_out=xp, **_rows(shift, "shift"), **_rows(scale, "scale"))
-    cin = sum(s.shape[1] for s in segs)
     # 3x3x3 convolutions (in-kernel dropout included): the family tmdiff_amd.routing picks -- Winograd along the bands where
     # its grid fills the chip (conv3d_wf's prologue pass writes x' where the weight gradient will read it), else direct
     if ksize == 3:
-        wino_ok = ops.config.winograd and ops.wino_conv_supported(cout, cin, ksize, groups)
-        weights = ops.ConvWeights(lambda: wp, (lambda: _wf_weights(w, groups, 2)) if wino_ok else None,
-                                  (lambda planes: ops.pack_conv_weight_wino(w, groups, planes=planes)) if wino_ok else None)
+        weights = ops.ConvWeights(lambda: wp, lambda: _wf_weights(w, groups, 2),
+                                  lambda planes: ops.pack_conv_weight_wino(w, groups, planes=planes))
         y = ops.conv3d_auto(segs, weights, cout, groups=groups, **kw)
     else:
         y = ops.conv3d(segs, wp, cout, ksize, groups=groups, **kw)
@@ -116,9 +114,8 @@ def _conv_backward(st, gy, need_w, need_b, need_shift, need_scale, need_res, nee
     if need_x:
         wp_t = st["wp_dgrad"] if st["wp_dgrad"] is not None else ops.pack_conv_weight(w, groups=groups, mode=1)
         if ksize == 3:     # the data gradient is a 3x3x3 convolution too (a plain input: no pass at all)
-            wino_ok = ops.config.winograd and ops.wino_conv_supported(cin, cout, ksize, groups)
-            weights = ops.ConvWeights(lambda: wp_t, (lambda: _wf_weights(w, groups, 3)) if wino_ok else None,
-                                      (lambda planes: ops.pack_conv_weight_wino(w, groups, mode=1, planes=planes)) if wino_ok else None)
+            weights = ops.ConvWeights(lambda: wp_t, lambda: _wf_weights(w, groups, 3),
+                                      lambda planes: ops.pack_conv_weight_wino(w, groups, mode=1, planes=planes))
             gp = ops.conv3d_auto([g], weights, cin, groups=groups)                # dL/dx'
         else:
             gp = ops.conv3d([g], wp_t, cin, ksize, groups=groups)

@@ -9,8 +9,6 @@ tests carry the `fallback` marker (and `gpu`: they run in the same GPU session).
 routing.conv3_family returns "wino4" / "wino2" for such shapes and ops.conv3d_auto dispatches here."""
 import ctypes as C
 
-import torch
-
 from . import ops
 from ._lib import check, lib
 
@@ -30,35 +28,20 @@ def conv3d_wino(segs, w_packed, cout, planes=None, emit=None, keep_y=True, group
     planes = planes or wino_planes(n)
     if planes not in (4, 6) or w % 4:
         raise ValueError(f"conv3d_wino: {n} bands x {w} columns not supported (even band count, W % 4 == 0)")
-    y = torch.empty(b, cout, n, h, w, device=dev, dtype=torch.float32) if keep_y else None
-    y2 = None
-    if emit is not None:
-        y2 = torch.empty(b, cout, n, h, w, device=dev, dtype=torch.float32)
-        kw = dict(kw, y2_act=emit.get("act", False), y2_shift=emit.get("shift"), y2_scale=emit.get("scale"),
-                  y2_shift_stride=emit.get("shift_stride", 0), y2_scale_stride=emit.get("scale_stride", 0))
-    elif y is None:
-        raise ValueError("conv3d_wino: keep_y=False needs emit=")
-    d = ops.make_conv_desc(segs, w_packed, cout, 3, y, y2=y2, groups=groups, **kw)
+    y, y2 = ops._outputs("conv3d_wino", dev, (b, cout, n, h, w), keep_y, emit, (b, cout, n, h, w))
+    d = ops.make_conv_desc(segs, w_packed, cout, 3, y, y2=y2, groups=groups, **kw, **ops._emit_kw(emit))
     if not lib.tmdiff_conv3d_wino_supported(C.byref(d)):
         raise ValueError("conv3d_wino: shape not supported")
     ws = ops._workspace(dev, lib.tmdiff_conv3d_wino_workspace_bytes(C.byref(d)), "wino").data_ptr()
-    ret = y if y2 is None else ((y, y2) if y is not None else y2)
-    if xp_out is not None and not (xp_out.is_cuda and xp_out.is_contiguous() and xp_out.numel() == b * d.Cin * n * h * w):
-        raise ValueError("conv3d_wino: xp_out must be a contiguous fp32 [B, Cin, N, H, W] tensor")
+    xp = ops._xp_target("conv3d_wino", xp_out, 4 * b * d.Cin * n * h * w, dev) if xp_out is not None else None
     mo = planes - 2                  # bands per tile
+    what = f"conv3d_wino{mo}_fwd"
     flops = 2.0 * b * cout * (d.Cin // groups) * (9.0 * planes / mo) * n * h * w      # EXECUTED: 9 * planes per tile of mo bands
-    ops._count(f"conv3d_wino{mo}_fwd", flops)
-    if ops.TIMER is None or xp_out is not None:
-        check(lib.tmdiff_conv3d_wino_fwd_planes(C.byref(d), ws, 0, xp_out.data_ptr() if xp_out is not None else None, planes,
-                                                ops.stream_ptr()), "conv3d_wino_fwd")
-        return ret
-    # timed: the input-transform pass (an HBM pass, recorded under ksize 0 with its bytes) and the convolution kernel apart
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    ev[0].record()
-    check(lib.tmdiff_conv3d_wino_fwd_planes(C.byref(d), ws, 1, None, planes, ops.stream_ptr()), "conv3d_wino_fwd (input transform)")
-    ev[1].record()
-    check(lib.tmdiff_conv3d_wino_fwd_planes(C.byref(d), ws, 2, None, planes, ops.stream_ptr()), "conv3d_wino_fwd")
-    ev[2].record()
-    ops.TIMER.records.append((ev[0], ev[1], (4.0 + 4.0 * planes / mo) * b * d.Cin * n * h * w, 0, "wino_input", ops._tag(d)))
-    ops.TIMER.records.append((ev[1], ev[2], flops, 3, f"conv3d_wino{mo}_fwd", ops._tag(d)))
-    return ret
+    if ops.TIMER is None or xp_out is not None:     # one launch: input transform + convolution
+        ops._count(what, flops)
+        check(lib.tmdiff_conv3d_wino_fwd_planes(C.byref(d), ws, 0, xp, planes, ops.stream_ptr()), what)
+    else:   # timed: the input-transform pass (an HBM pass, recorded under ksize 0 with its bytes) and the convolution apart
+        ops._launch(lib.tmdiff_conv3d_wino_fwd_planes, d, (ws, 1, None, planes), "wino_input", None,
+                    (4.0 + 4.0 * planes / mo) * b * d.Cin * n * h * w, 0)
+        ops._launch(lib.tmdiff_conv3d_wino_fwd_planes, d, (ws, 2, None, planes), what, what, flops)
+    return ops._result(y, y2)

@@ -433,7 +433,7 @@ class ConvTimer:
     object).  Events are recorded on the launch stream; ``summary()`` resolves them after a sync."""
 
     def __init__(self):
-        self.records = []        # (start_event, end_event, flops, ksize, entry point)
+        self.records = []        # (start_event, end_event, flops, ksize, entry point, _tag[, bytes])
 
     def summary(self, by_entry=False):
         """{ksize: (launches, ms, flops)}; with by_entry the key is (ksize, C entry point that served the launch)."""
@@ -505,6 +505,75 @@ def _workspace(device, nbytes, tag="x"):
     return ws
 
 
+# The launch steps every forward-convolution wrapper (conv3d, conv3d_wf, conv3d_ll, conv3d_wf_ll, fallback.conv3d_wino) shares.
+
+def _outputs(what, dev, y_shape, keep_y, emit, y2_shape, y2_dtype=torch.float32, out=None):
+    """(y, y2): y = `out`, else a fresh tensor unless keep_y=False; y2 when `emit` asks for it and y2_shape is given."""
+    y = out if out is not None else (torch.empty(*y_shape, device=dev, dtype=torch.float32) if keep_y else None)
+    if emit is None and y is None:
+        raise ValueError(f"{what}: keep_y=False needs emit=")
+    return y, (torch.empty(*y2_shape, device=dev, dtype=y2_dtype) if emit is not None and y2_shape is not None else None)
+
+
+def _emit_kw(emit):
+    """make_conv_desc keywords of the second output y2 = act(y + shift) * scale that `emit` describes."""
+    return {} if emit is None else dict(y2_act=emit.get("act", False), y2_shift=emit.get("shift"), y2_scale=emit.get("scale"),
+                                        y2_shift_stride=emit.get("shift_stride", 0), y2_scale_stride=emit.get("scale_stride", 0))
+
+
+def _result(y, y2):
+    """The return convention of the wrappers: y, (y, y2), or y2 alone (keep_y=False)."""
+    return y if y2 is None else ((y, y2) if y is not None else y2)
+
+
+def _plain(segs, kw):
+    """One input tensor that the kernel reads as it stands: no prologue, mask or dropout."""
+    return len(segs) == 1 and not (kw.get("in_act") or kw.get("in_shift") is not None or kw.get("in_scale") is not None or
+                                   kw.get("in_mask") is not None or kw.get("drop") is not None)
+
+
+def _lend_splitk(d, dev, nbytes):
+    """Lend the split-K workspace a small grid asks for (nbytes 0: the launch runs unsplit)."""
+    if nbytes:
+        d.splitk_ws, d.splitk_ws_bytes = _workspace(dev, nbytes, "splitk").data_ptr(), nbytes
+
+
+def _xp_target(what, xp_out, nbytes, dev):
+    """Address the prologue pass writes x' (nbytes) to: the caller's xp_out, else the shared scratch (None: no pass)."""
+    if not nbytes:
+        return None
+    if xp_out is None:
+        return _workspace(dev, nbytes).data_ptr()
+    if not (xp_out.is_cuda and xp_out.is_contiguous() and xp_out.numel() * 4 == nbytes):
+        raise ValueError(f"{what}: xp_out must be a contiguous fp32 [B, Cin, N, H, W] tensor")
+    return xp_out.data_ptr()
+
+
+def _launch(fn, d, args, what, key, flops, ksize=3, suffix="", bytes_of=None):
+    """Count the launch (COUNTS[key] unless key is None, FLOPS += flops), then run fn(&d, *args, stream), checked as `what`.
+    With TIMER set the launch is bracketed by HIP events and recorded as (e0, e1, flops, ksize, what, tag[, bytes_of(d)])."""
+    if key is not None:
+        _count(key, flops)
+    if TIMER is None:
+        check(fn(C.byref(d), *args, stream_ptr()), what)
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    check(fn(C.byref(d), *args, stream_ptr()), what)
+    e1.record()
+    rec = (e0, e1, flops, ksize, what, _tag(d) + suffix)
+    TIMER.records.append(rec if bytes_of is None else rec + (bytes_of(d),))
+
+
+def _conv3d_bytes(d):
+    """Algorithmic HBM bytes of a conv3d launch: input once (2 B per element for packed bf16 units, else 4), outputs and
+    residual once (+ the by-product x' of a side_xp launch: Cin more channels written)."""
+    y2_b = 0.0 if not d.y2 else (2.0 if d.y2_bf16 else 4.0)
+    return d.B * d.N * d.H * d.W * ((2.0 if d.x_bf16 else 4.0) * d.Cin +
+                                    d.Cout * (4.0 * ((1 if d.y else 0) + (1 if d.residual else 0)) + y2_b) +
+                                    (4.0 * d.Cin if d.xp_out else 0.0))
+
+
 def conv3d(segs, w_packed, cout, ksize, out=None, math="fp32", pack_input=None, staged=None, emit=None, keep_y=True,
            x_bf16_shape=None, xp_out=None, **kw):
     """math="fp32": exact-fp32 MFMA kernel (w_packed from pack_conv_weight); "bf16": bf16 operands / fp32
@@ -519,78 +588,42 @@ def conv3d(segs, w_packed, cout, ksize, out=None, math="fp32", pack_input=None, 
     prologue pass writes it there instead of the shared scratch) -- the training path keeps it for the weight gradient."""
     if kw.get("res_conv") is not None or kw.get("y_ll") is not None or (emit is not None and (emit.get("ll") or emit.get("dwt"))):
         raise ValueError("conv3d: only conv3d_wf folds a residual convolution into its epilogue / writes the LL band")
-    if x_bf16_shape is not None:
-        b, (n, h, w) = segs[0].shape[0], x_bf16_shape
-        kw = dict(kw, x_bf16_shape=x_bf16_shape)
-    else:
-        b, _, n, h, w = segs[0].shape
+    b, _, n, h, w = segs[0].shape if x_bf16_shape is None else (segs[0].shape[0], None, *x_bf16_shape)
     dev = segs[0].device
-    y = out if out is not None else (torch.empty(b, cout, n, h, w, device=dev, dtype=torch.float32) if keep_y else None)
-    y2 = None
-    if emit is not None:
-        y2 = (torch.empty(b, cout // 8, n * h * w, 8, device=dev, dtype=torch.int16) if math == "bf16"
-              else torch.empty(b, cout, n, h, w, device=dev, dtype=torch.float32))
-        kw = dict(kw, y2=y2, y2_act=emit.get("act", False), y2_shift=emit.get("shift"), y2_scale=emit.get("scale"),
-                  y2_shift_stride=emit.get("shift_stride", 0), y2_scale_stride=emit.get("scale_stride", 0))
-    elif y is None:
-        raise ValueError("conv3d: keep_y=False needs emit=")
-    d = make_conv_desc(segs, w_packed, cout, ksize, y, **kw)
+    bf16 = math == "bf16"
+    y, y2 = _outputs("conv3d", dev, (b, cout, n, h, w), keep_y, emit,
+                     (b, cout // 8, n * h * w, 8) if bf16 else (b, cout, n, h, w), torch.int16 if bf16 else torch.float32, out)
+    d = make_conv_desc(segs, w_packed, cout, ksize, y, y2=y2, x_bf16_shape=x_bf16_shape, **kw, **_emit_kw(emit))
     if d.xp_out and (math != "fp32" or not lib.tmdiff_conv3d_fwd_xp_supported(C.byref(d))):
         raise ValueError("conv3d: side_xp needs the 16-byte 1x1x1 bandwidth kernel (ask routing.k1_side_xp first)")
-    ret = y if y2 is None else ((y, y2) if y is not None else y2)
-    if math == "bf16":
+    if bf16:
         if w_packed.dtype != torch.int16:
             raise TypeError("conv3d(math='bf16') needs weights from pack_conv_weight_bf16")
         if pack_input is None:
             pack_input = {"0": False, "1": True}.get(config.bf16_pack, True)   # measured: the two-kernel variant wins on every production layer
         ws = (_workspace(dev, lib.tmdiff_conv3d_bf16_workspace_bytes(C.byref(d))).data_ptr()
               if pack_input and ksize == 3 and x_bf16_shape is None else None)
-        fwd, what = (lambda dd, st: lib.tmdiff_conv3d_fwd_bf16(dd, ws, st)), "conv3d_fwd_bf16"
+        fn, args, what = lib.tmdiff_conv3d_fwd_bf16, (ws,), "conv3d_fwd_bf16"
     elif math == "fp32":
         if not isinstance(w_packed, int) and w_packed.dtype != torch.float32:
             raise TypeError("conv3d(math='fp32') needs weights from pack_conv_weight")
-        if ksize == 3:      # lend the split-K workspace (small grids only: B = 1, the 8x8 / 16x16 levels at small batches)
-            nsk = lib.tmdiff_conv3d_fwd_splitk_workspace_bytes(C.byref(d))
-            if nsk:
-                d.splitk_ws, d.splitk_ws_bytes = _workspace(dev, nsk, "splitk").data_ptr(), nsk
+        if ksize == 3:      # (split-K: small grids only -- B = 1, the 8x8 / 16x16 levels at small batches)
+            _lend_splitk(d, dev, lib.tmdiff_conv3d_fwd_splitk_workspace_bytes(C.byref(d)))
         if staged is None:       # (the rule and its measurements: routing.direct_family)
-            plain = len(segs) == 1 and not (kw.get("in_act") or kw.get("in_shift") is not None or
-                                            kw.get("in_scale") is not None or kw.get("in_mask") is not None)
-            plain = plain and kw.get("drop") is None
-            staged = ksize == 3 and routing.direct_family(d.Cin, cout, d.groups, plain, kw.get("in_mask") is not None,
+            staged = ksize == 3 and routing.direct_family(d.Cin, cout, d.groups, _plain(segs, kw), kw.get("in_mask") is not None,
                                                           kw.get("drop") is not None) == "staged"
         if xp_out is not None:
             staged = True
         if staged and lib.tmdiff_conv3d_fwd_staged_supported(C.byref(d)):
             nb = lib.tmdiff_conv3d_fwd_staged_workspace_bytes(C.byref(d))
-            if xp_out is not None and nb:
-                if xp_out.numel() * 4 != nb or not (xp_out.is_cuda and xp_out.is_contiguous()):
-                    raise ValueError("conv3d: xp_out must be a contiguous fp32 [B, Cin, N, H, W] tensor")
-                ws32 = xp_out.data_ptr()
-            else:
-                ws32 = _workspace(dev, nb).data_ptr() if nb else None
-            fwd, what = (lambda dd, st: lib.tmdiff_conv3d_fwd_staged(dd, ws32, st)), "conv3d_fwd_staged"
+            fn, args, what = lib.tmdiff_conv3d_fwd_staged, (_xp_target("conv3d", xp_out, nb, dev),), "conv3d_fwd_staged"
         else:
-            fwd, what = lib.tmdiff_conv3d_fwd, "conv3d_fwd"
+            fn, args, what = lib.tmdiff_conv3d_fwd, (), "conv3d_fwd"
     else:
         raise ValueError(f"conv3d: unknown math {math!r}")
-    _count(what if ksize == 3 else what + "_k1", 2.0 * b * cout * (d.Cin // d.groups) * ksize ** 3 * n * h * w)
-    if TIMER is None:
-        check(fwd(C.byref(d), stream_ptr()), what)
-        return ret
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(fwd(C.byref(d), stream_ptr()), what)
-    e1.record()
-    # algorithmic HBM bytes of the launch: input once (2 B per element for packed bf16 units, else 4), outputs once
-    in_b = 2.0 if d.x_bf16 else 4.0
-    y2_b = 0.0 if y2 is None else (2.0 if d.y2_bf16 else 4.0)
-    # (+ the by-product x' of a side_xp launch: Cin more channels written)
-    nbytes = b * n * h * w * (in_b * d.Cin + cout * (4.0 * ((1 if y is not None else 0) + (1 if kw.get("residual") is not None else 0)) + y2_b) +
-                              (4.0 * d.Cin if d.xp_out else 0.0))
-    TIMER.records.append((e0, e1, 2.0 * b * cout * (d.Cin // d.groups) * ksize ** 3 * n * h * w, ksize, what,
-                          _tag(d) + (" +xp" if d.xp_out else ""), nbytes))
-    return ret
+    _launch(fn, d, args, what, what if ksize == 3 else what + "_k1",
+            2.0 * b * cout * (d.Cin // d.groups) * ksize ** 3 * n * h * w, ksize, " +xp" if d.xp_out else "", _conv3d_bytes)
+    return _result(y, y2)
 
 
 def conv3d_prologue(desc, shape):
@@ -617,8 +650,6 @@ def pack_conv_weight_wino(w, groups=1, mode=0, planes=6):
     return out
 
 
-
-
 # routing lives in tmdiff_amd/routing.py; these names stay importable from ops (tests, tools)
 wino_conv_supported = routing.wino_weight_ok
 wf_route = routing.wf_route
@@ -643,9 +674,7 @@ def conv3d_auto(segs, weights, cout, groups=1, math="fp32", emit=None, keep_y=Tr
                       x_bf16_shape=x_bf16_shape, **kw)
     b, _, n, h, w = segs[0].shape
     cin = sum(s_.shape[1] for s_ in segs)
-    masked, dropout = kw.get("in_mask") is not None, kw.get("drop") is not None
-    plain = len(segs) == 1 and not (kw.get("in_act") or kw.get("in_shift") is not None or kw.get("in_scale") is not None or
-                                    masked or dropout)
+    masked, dropout, plain = kw.get("in_mask") is not None, kw.get("drop") is not None, _plain(segs, kw)
     fam = routing.conv3_family(b, cin, cout, n, h, w, groups, plain=plain, masked=masked, dropout=dropout,
                                keep_xp=xp_out is not None)
     if fam in ("wf", "wf_pair") and weights.wf is not None:
@@ -658,9 +687,10 @@ def conv3d_auto(segs, weights, cout, groups=1, math="fp32", emit=None, keep_y=Tr
     if (emit is not None and (emit.get("s2d") or emit.get("ll") or emit.get("dwt"))) or kw.get("res_conv") is not None:
         raise ValueError("conv3d_auto: only conv3d_wf writes a space-to-depth second output / folds a residual convolution "
                          "(ask routing.wf_route first)")
-    staged = fam == "staged" or (fam not in ("staged", "fused") and
-                                 routing.direct_family(cin, cout, groups, plain, masked, dropout, xp_out is not None) == "staged")
-    return conv3d(segs, weights.direct(), cout, 3, groups=groups, staged=staged, emit=emit, keep_y=keep_y, xp_out=xp_out, **kw)
+    if fam not in ("staged", "fused"):      # (a direct family named by conv3_family is direct_family's answer already)
+        fam = routing.direct_family(cin, cout, groups, plain, masked, dropout, xp_out is not None)
+    return conv3d(segs, weights.direct(), cout, 3, groups=groups, staged=fam == "staged", emit=emit, keep_y=keep_y,
+                  xp_out=xp_out, **kw)
 
 
 def conv3d_wf(segs, w_packed, cout, emit=None, keep_y=True, groups=1, xp_out=None, **kw):
@@ -685,55 +715,26 @@ def conv3d_wf(segs, w_packed, cout, emit=None, keep_y=True, groups=1, xp_out=Non
             raise ValueError("conv3d_wf: this launch cannot write a space-to-depth / LL output (ask routing.wf_route first)")
     if want_ll and keep_y:
         raise ValueError("conv3d_wf: the LL output replaces y (keep_y=False)")
-    y = torch.empty(b, cout, n, h, w, device=dev, dtype=torch.float32) if keep_y else None
-    y2 = None
-    if want_ll:
-        kw = dict(kw, y_ll=torch.empty(b, cout, n, h // 2, w // 2, device=dev, dtype=torch.float32))
-    if want_dwt:
-        kw = dict(kw, y_hi=[torch.empty(b, cout, n, h // 2, w // 2, device=dev, dtype=torch.float32) for _ in range(3)])
-    if emit is not None and not want_dwt:
-        y2 = torch.empty((b, 4 * cout, n, h // 2, w // 2) if s2d else (b, cout, n, h, w), device=dev, dtype=torch.float32)
-    if emit is not None:
-        kw = dict(kw, y2_act=emit.get("act", False), y2_shift=emit.get("shift"), y2_scale=emit.get("scale"),
-                  y2_shift_stride=emit.get("shift_stride", 0), y2_scale_stride=emit.get("scale_stride", 0), y2_s2d=s2d)
-    elif y is None:
-        raise ValueError("conv3d_wf: keep_y=False needs emit=")
-    d = make_conv_desc(segs, w_packed, cout, 3, y, y2=y2, groups=groups, **kw)
+    q = (b, cout, n, h // 2, w // 2)       # (allocated before y and y2 -- y is None whenever y_ll is wanted)
+    y_ll = torch.empty(*q, device=dev, dtype=torch.float32) if want_ll else None
+    y_hi = [torch.empty(*q, device=dev, dtype=torch.float32) for _ in range(3)] if want_dwt else None
+    y, y2 = _outputs("conv3d_wf", dev, (b, cout, n, h, w), keep_y, emit,
+                     None if want_dwt else ((b, 4 * cout, n, h // 2, w // 2) if s2d else (b, cout, n, h, w)))
+    d = make_conv_desc(segs, w_packed, cout, 3, y, y2=y2, groups=groups, y2_s2d=s2d, y_ll=y_ll, y_hi=y_hi, **kw,
+                       **_emit_kw(emit))
     if not lib.tmdiff_conv3d_wf_supported(C.byref(d)):
         raise ValueError("conv3d_wf: shape not supported")
     # (a launch that writes an LL / Haar / space-to-depth output runs unsplit: no workspace is lent)
-    nsk = lib.tmdiff_conv3d_wf_splitk_workspace_bytes(C.byref(d)) if (config.wf_splitk and not want_ll) else 0
-    if nsk:
-        d.splitk_ws, d.splitk_ws_bytes = _workspace(dev, nsk, "splitk").data_ptr(), nsk
+    _lend_splitk(d, dev, lib.tmdiff_conv3d_wf_splitk_workspace_bytes(C.byref(d)) if (config.wf_splitk and not want_ll) else 0)
     nws = lib.tmdiff_conv3d_wf_workspace_bytes(C.byref(d))
-    ws = None
-    if nws:
-        if xp_out is not None:
-            if not (xp_out.is_cuda and xp_out.is_contiguous() and xp_out.numel() * 4 == nws):
-                raise ValueError("conv3d_wf: xp_out must be a contiguous fp32 [B, Cin, N, H, W] tensor")
-            ws = xp_out.data_ptr()
-        else:
-            ws = _workspace(dev, nws).data_ptr()
-    elif xp_out is not None:          # plain input: x' IS the input
+    ws = _xp_target("conv3d_wf", xp_out, nws, dev)
+    if xp_out is not None and not nws:          # plain input: x' IS the input
         xp_out.copy_(segs[0] if len(segs) == 1 else torch.cat(segs, 1))
-    ret = y if y2 is None else ((y, y2) if y is not None else y2)
-    if want_dwt:
-        ret = (kw["y_ll"], *kw["y_hi"])
-    elif want_ll:
-        ret = (y2, kw["y_ll"])
     # EXECUTED flops: 54 multiply-adds per (ci, co) and tile of four output bands (the direct kernel: 27 per band), plus the
     # folded res_conv's rc_cin multiply-adds per output
     flops = 2.0 * b * cout * ((d.Cin // groups) * 13.5 + d.rc_cin) * n * h * w
-    _count("conv3d_wf_fwd", flops)
-    if TIMER is None:
-        check(lib.tmdiff_conv3d_wf_fwd(C.byref(d), ws, stream_ptr()), "conv3d_wf_fwd")
-        return ret
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(lib.tmdiff_conv3d_wf_fwd(C.byref(d), ws, stream_ptr()), "conv3d_wf_fwd")
-    e1.record()
-    TIMER.records.append((e0, e1, flops, 3, "conv3d_wf_fwd", _tag(d) + (f" +rc{d.rc_cin}" if d.rc_cin else "")))
-    return ret
+    _launch(lib.tmdiff_conv3d_wf_fwd, d, (ws,), "conv3d_wf_fwd", "conv3d_wf_fwd", flops, 3, f" +rc{d.rc_cin}" if d.rc_cin else "")
+    return (y_ll, *y_hi) if want_dwt else (y2, y_ll) if want_ll else _result(y, y2)
 
 
 def ll_conv_supported(cout, cin, ksize=3, groups=1):
@@ -760,34 +761,15 @@ def conv3d_ll(x, w_packed, cout, ll_scale=0.5, emit=None, keep_y=True, **kw):
     b, _, n, h, w = x.shape
     dev = x.device
     oshape = (b, cout, n, h // 2, w // 2)
-    y = torch.empty(oshape, device=dev, dtype=torch.float32) if keep_y else None
-    y2 = None
-    if emit is not None:
-        y2 = torch.empty(oshape, device=dev, dtype=torch.float32)
-        kw = dict(kw, y2_act=emit.get("act", False), y2_shift=emit.get("shift"), y2_scale=emit.get("scale"),
-                  y2_shift_stride=emit.get("shift_stride", 0), y2_scale_stride=emit.get("scale_stride", 0))
-    elif y is None:
-        raise ValueError("conv3d_ll: keep_y=False needs emit=")
-    d = make_conv_desc([x], w_packed, cout, 3, y, y2=y2, out_div=2, **kw)
+    y, y2 = _outputs("conv3d_ll", dev, oshape, keep_y, emit, oshape)
+    d = make_conv_desc([x], w_packed, cout, 3, y, y2=y2, out_div=2, **kw, **_emit_kw(emit))
     if not lib.tmdiff_conv3d_ll_supported(C.byref(d)):
         raise ValueError("conv3d_ll: shape not supported (ll_conv_supported)")
-    nsk = lib.tmdiff_conv3d_ll_splitk_workspace_bytes(C.byref(d))      # small grids: lend the split-K workspace
-    if nsk:
-        d.splitk_ws, d.splitk_ws_bytes = _workspace(dev, nsk, "splitk").data_ptr(), nsk
-    ret = y if y2 is None else ((y, y2) if y is not None else y2)
-    _count("conv3d_ll_fwd", 2.0 * b * cout * d.Cin * 48 * n * (h // 2) * (w // 2))
-    if TIMER is None:
-        check(lib.tmdiff_conv3d_ll_fwd(C.byref(d), float(ll_scale), stream_ptr()), "conv3d_ll_fwd")
-        return ret
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(lib.tmdiff_conv3d_ll_fwd(C.byref(d), float(ll_scale), stream_ptr()), "conv3d_ll_fwd")
-    e1.record()
+    _lend_splitk(d, dev, lib.tmdiff_conv3d_ll_splitk_workspace_bytes(C.byref(d)))
     # EXECUTED flops: 48 multiply-adds per (ci, co, output position) -- the pair it replaces would execute 4 x 27
-    TIMER.records.append((e0, e1, 2.0 * b * cout * d.Cin * 48 * n * (h // 2) * (w // 2), 3, "conv3d_ll_fwd", _tag(d)))
-    return ret
-
-
+    _launch(lib.tmdiff_conv3d_ll_fwd, d, (float(ll_scale),), "conv3d_ll_fwd", "conv3d_ll_fwd",
+            2.0 * b * cout * d.Cin * 48 * n * (h // 2) * (w // 2))
+    return _result(y, y2)
 
 
 def pack_conv_weight_wfll(w, ll_scale=0.5):
@@ -807,33 +789,15 @@ def conv3d_wf_ll(x_s2d, w_packed, cout, ll_scale=0.5, emit=None, keep_y=True, **
     b, c4, n, h2, w2 = x_s2d.shape
     dev = x_s2d.device
     oshape = (b, cout, n, h2, w2)
-    y = torch.empty(oshape, device=dev, dtype=torch.float32) if keep_y else None
-    y2 = None
-    if emit is not None:
-        y2 = torch.empty(oshape, device=dev, dtype=torch.float32)
-        kw = dict(kw, y2_act=emit.get("act", False), y2_shift=emit.get("shift"), y2_scale=emit.get("scale"),
-                  y2_shift_stride=emit.get("shift_stride", 0), y2_scale_stride=emit.get("scale_stride", 0))
-    elif y is None:
-        raise ValueError("conv3d_wf_ll: keep_y=False needs emit=")
-    d = make_conv_desc([x_s2d], w_packed, cout, 3, y, y2=y2, out_div=2, x_s2d=True, **kw)
+    y, y2 = _outputs("conv3d_wf_ll", dev, oshape, keep_y, emit, oshape)
+    d = make_conv_desc([x_s2d], w_packed, cout, 3, y, y2=y2, out_div=2, x_s2d=True, **kw, **_emit_kw(emit))
     if not lib.tmdiff_conv3d_wfll_supported(C.byref(d)):
         raise ValueError("conv3d_wf_ll: shape not supported")
-    nsk = lib.tmdiff_conv3d_wfll_splitk_workspace_bytes(C.byref(d)) if config.wf_splitk else 0
-    if nsk:
-        d.splitk_ws, d.splitk_ws_bytes = _workspace(dev, nsk, "splitk").data_ptr(), nsk
-    ret = y if y2 is None else ((y, y2) if y is not None else y2)
+    _lend_splitk(d, dev, lib.tmdiff_conv3d_wfll_splitk_workspace_bytes(C.byref(d)) if config.wf_splitk else 0)
     # EXECUTED flops: 16 taps x 6 planes per tile of four bands = 24 multiply-adds per (ci, co, output position)
-    fl = 2.0 * b * cout * d.Cin * 24 * n * h2 * w2
-    _count("conv3d_wfll_fwd", fl)
-    if TIMER is None:
-        check(lib.tmdiff_conv3d_wfll_fwd(C.byref(d), float(ll_scale), stream_ptr()), "conv3d_wfll_fwd")
-        return ret
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(lib.tmdiff_conv3d_wfll_fwd(C.byref(d), float(ll_scale), stream_ptr()), "conv3d_wfll_fwd")
-    e1.record()
-    TIMER.records.append((e0, e1, fl, 3, "conv3d_wfll_fwd", _tag(d)))
-    return ret
+    _launch(lib.tmdiff_conv3d_wfll_fwd, d, (float(ll_scale),), "conv3d_wfll_fwd", "conv3d_wfll_fwd",
+            2.0 * b * cout * d.Cin * 24 * n * h2 * w2)
+    return _result(y, y2)
 
 
 def stem(w, bias, out_channels, xin=None, pan=None, ms=None, silu=True, out=None, out_scale=None, out_scale_stride=0,
