@@ -463,3 +463,173 @@ def test_side_prologue_rule_on_the_benchmark_workload():
     assert not routing.k1_side_xp(32, (32, 32, 32), 48, 8, 64, 64)          # Cout not a multiple of 32
     assert not routing.k1_side_xp(32, (32, 32, 32), 32, 3, 7, 9)            # a plane that is not a multiple of 4 positions
 
+
+
+
+# ---- descriptor validation of the convolution entry points --------------------------------------------------------------
+# Every case below is refused (or, for an empty batch, accepted) before the entry point makes a HIP call.  The child process
+# sees no GPU (HIP_VISIBLE_DEVICES=-1), so a case that wrongly got past validation fails on the missing device instead of
+# launching on placeholder pointers.  The pointers are placeholders only ("A": 16-byte aligned, "U": not) and are never
+# dereferenced.
+_VALIDATION_CHILD = r"""
+import ctypes as C, json, sys
+sys.path.insert(0, sys.argv[1])
+from tmdiff_amd import _lib
+L = _lib.lib
+PTR = {"A": 0x10000, "U": 0x10004}
+A = PTR["A"]
+dx, acc = (C.c_void_p * 3)(A, A, A), (C.c_int32 * 3)(0, 0, 0)
+ENTRIES = {
+    "conv3d_fwd": lambda p: L.tmdiff_conv3d_fwd(p, None),
+    "conv3d_fwd_xp_supported": lambda p: L.tmdiff_conv3d_fwd_xp_supported(p),
+    "conv3d_fwd_staged": lambda p: L.tmdiff_conv3d_fwd_staged(p, A, None),
+    "conv3d_fwd_bf16": lambda p: L.tmdiff_conv3d_fwd_bf16(p, None, None),
+    "conv3d_ll_fwd": lambda p: L.tmdiff_conv3d_ll_fwd(p, 0.5, None),
+    "conv3d_wf_fwd": lambda p: L.tmdiff_conv3d_wf_fwd(p, A, None),
+    "conv3d_wfll_fwd": lambda p: L.tmdiff_conv3d_wfll_fwd(p, 0.5, None),
+    "conv3d_wino_fwd": lambda p: L.tmdiff_conv3d_wino_fwd(p, A, None),
+    "conv3d_prologue_fwd": lambda p: L.tmdiff_conv3d_prologue_fwd(p, A, None),
+    "conv3d_wgrad": lambda p: L.tmdiff_conv3d_wgrad_bias(p, A, A, A, A, None),
+    "conv3d_wgrad_wino": lambda p: L.tmdiff_conv3d_wgrad_wino_bias(p, A, A, A, A, None),
+    "prologue_bwd": lambda p: L.tmdiff_conv3d_prologue_bwd_ws(p, A, dx, acc, None, None, None, None),
+}
+out = []
+for entry, fields in json.loads(sys.argv[2]):
+    d = None
+    if fields is not None:
+        d = _lib.Conv3dDesc()
+        d.bias_scale = d.out_scale = 1.0
+        for k, v in fields.items():
+            if isinstance(v, list):
+                for i, x in enumerate(v):
+                    getattr(d, k)[i] = PTR.get(x, x)
+            else:
+                setattr(d, k, PTR.get(v, v))
+    assert L.tmdiff_conv3d_pack_weights(None, None, 1, 1, 3, 1, 0, None) != 0   # a known message in the error buffer
+    rc = ENTRIES[entry](C.byref(d) if d is not None else None)
+    out.append([rc, L.tmdiff_last_error_string().decode()])
+print(json.dumps(out))
+"""
+
+_BASE_DESC = dict(B=2, N=8, H=16, W=16, Cin=64, Cout=64, groups=1, ksize=3, nseg=1, seg_c=[64], seg_x=["A"], w_packed="A", y="A")
+_BAD_DESC = {
+    "null": None,
+    "nseg0": dict(nseg=0), "nseg4": dict(nseg=4),
+    "seg_null": dict(seg_x=[0]),
+    "seg_empty": dict(nseg=2, seg_c=[64, 0], seg_x=["A", "A"]),
+    "csum": dict(nseg=2, seg_c=[32, 16], seg_x=["A", "A"]),
+    "groups3_unequal": dict(groups=3, Cin=96, Cout=96, nseg=3, seg_c=[16, 32, 48], seg_x=["A", "A", "A"]),
+    "mask_and_drop": dict(in_mask="A", drop_p=0.1), "drop1": dict(drop_p=1.0),
+    "no_weights": dict(w_packed=0), "no_output": dict(y=0),
+    "unaligned_x": dict(seg_x=["U"]), "unaligned_w": dict(w_packed="U"), "unaligned_y": dict(y="U"),
+    "bad_extents": dict(N=0), "ksize2": dict(ksize=2), "groups2": dict(groups=2), "indivisible": dict(groups=3),
+    "B0": dict(B=0), "B0_seg_null": dict(B=0, seg_x=[0]), "B0_drop1": dict(B=0, drop_p=1.0),
+}
+# entry -> {case: (return code, prefix of the message)}: -1 = TMDIFF_E_INVALID, -2 = TMDIFF_E_UNSUPPORTED, 0 = accepted.  Cases
+# an entry point lets through to its launch are not listed for it.
+_INVALID = ("null", "nseg0", "nseg4", "seg_null", "seg_empty", "csum", "no_weights", "no_output", "bad_extents")
+_SHAPE = ("nseg0", "nseg4", "mask_and_drop", "drop1", "bad_extents", "ksize2", "groups2", "indivisible")
+
+
+def _expect(name, invalid=(), unsupported=(), ok=(), **other):
+    t = {c: (-1, name) for c in invalid}
+    t.update({c: (-2, name) for c in unsupported})
+    t.update({c: (0, None) for c in ok})
+    t.update(other)
+    return t
+
+
+_VALIDATION = {
+    "conv3d_fwd": _expect("conv3d_fwd", _INVALID + ("groups3_unequal", "mask_and_drop", "drop1", "ksize2", "groups2", "indivisible"),
+                          ok=("B0", "B0_seg_null", "B0_drop1")),
+    "conv3d_fwd_staged": _expect("conv3d_fwd_staged", _INVALID + ("mask_and_drop", "drop1", "unaligned_w"),
+                                 ("ksize2", "groups2", "indivisible"), ("B0", "B0_seg_null", "B0_drop1")),
+    "conv3d_fwd_bf16": _expect("conv3d_fwd_bf16", _INVALID + ("groups3_unequal", "unaligned_w", "ksize2", "groups2", "indivisible"),
+                               ("mask_and_drop", "drop1", "B0_drop1"), ("B0", "B0_seg_null")),
+    "conv3d_ll_fwd": _expect("conv3d_ll_fwd", ("null", "seg_null", "no_weights", "no_output", "unaligned_w", "bad_extents"),
+                             ("nseg0", "nseg4", "mask_and_drop", "drop1", "ksize2", "groups2", "indivisible", "seg_empty", "csum",
+                              "groups3_unequal", "B0_drop1"),
+                             ("B0", "B0_seg_null")),
+    "conv3d_wf_fwd": _expect("conv3d_wf_fwd", ("null", "seg_null", "seg_empty", "csum", "no_weights", "no_output", "unaligned_x",
+                                               "unaligned_w"), _SHAPE + ("unaligned_y", "B0_drop1"), ("B0", "B0_seg_null")),
+    # (the composed Conv_0 + LL entry point translates its descriptor and hands it to the conv3d_wf_fwd checks)
+    "conv3d_wfll_fwd": _expect("conv3d_wf_fwd", ("seg_null", "no_weights", "no_output", "unaligned_x", "unaligned_w"), ("unaligned_y",),
+                               ("B0", "B0_seg_null"), **{c: (-2, "conv3d_wfll_fwd") for c in _SHAPE + (
+                                   "null", "seg_empty", "csum", "groups3_unequal", "B0_drop1")}),
+    "conv3d_wino_fwd": _expect("conv3d_wino_fwd", ("null", "seg_null", "seg_empty", "csum", "no_weights", "no_output", "unaligned_x",
+                                                   "unaligned_w"), _SHAPE + ("B0_drop1",), ("B0", "B0_seg_null")),
+    "conv3d_prologue_fwd": _expect("conv3d_prologue_fwd", ("null", "nseg0", "nseg4", "seg_null", "seg_empty", "csum", "bad_extents",
+                                                           "B0_seg_null"), ok=("B0", "B0_drop1")),
+    "conv3d_wgrad": _expect("conv3d_wgrad", ("null", "nseg0", "nseg4", "seg_null", "seg_empty", "csum", "mask_and_drop",
+                                             "bad_extents", "ksize2", "groups2", "indivisible", "B0")),
+    "conv3d_wgrad_wino": _expect("conv3d_wgrad_wino", ("null", "seg_null", "seg_empty", "csum", "mask_and_drop", "unaligned_x"),
+                                 ("nseg0", "nseg4", "bad_extents", "ksize2", "groups2", "indivisible", "B0")),
+    "prologue_bwd": _expect("prologue_bwd", ("null", "nseg0", "nseg4", "seg_null", "csum", "mask_and_drop", "B0")),
+}
+
+
+def _run_validation_child(calls):
+    import json, subprocess, sys
+    env = {k: v for k, v in os.environ.items() if k not in ("ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")}
+    env["HIP_VISIBLE_DEVICES"] = "-1"
+    p = subprocess.run([sys.executable, "-c", _VALIDATION_CHILD, ROOT, json.dumps(calls)], capture_output=True, text=True, env=env,
+                       timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    return json.loads(p.stdout.strip().splitlines()[-1])
+
+
+def _desc(case, **base):
+    bad = _BAD_DESC[case]
+    return None if bad is None else dict(_BASE_DESC, **base, **bad)
+
+
+def test_conv_entry_points_validate_descriptors():
+    """Return code and message prefix of every convolution entry point for a table of malformed descriptors (NULL descriptor,
+    nseg 0 / 4, NULL / empty segments, a channel sum other than Cin, unequal segments of a grouped convolution, a mask with
+    drop_p, drop_p = 1, no weights, no output, unaligned pointers where alignment is required, bad extents / ksize / groups) and
+    for an empty batch, which some entry points accept before their segment or dropout checks and others after them."""
+    table = [(entry, case, want) for entry, cases in _VALIDATION.items() for case, want in cases.items()]
+    got = _run_validation_child([[entry, _desc(case)] for entry, case, _ in table])
+    bad = [f"{entry} / {case}: want {rc} '{prefix}: ...', got {got_rc} '{msg}'"
+           for (entry, case, (rc, prefix)), (got_rc, msg) in zip(table, got)
+           if got_rc != rc or (rc != 0 and not msg.startswith(prefix + ":"))]
+    assert not bad, "\n".join(bad)
+
+
+def test_conv_fwd_xp_supported_refuses_malformed_descriptors():
+    """tmdiff_conv3d_fwd_xp_supported: 1 for a raw 1x1x1 input the small-grid bandwidth kernel takes, 0 for the malformed forms of
+    that descriptor and for an empty batch."""
+    xp = dict(ksize=1, Cin=128, seg_c=[128], xp_out="A")
+    bad = [None, dict(nseg=0), dict(nseg=4), dict(seg_x=[0]), dict(nseg=2, seg_c=[128, 0], seg_x=["A", "A"]),
+           dict(nseg=2, seg_c=[64, 16], seg_x=["A", "A"]), dict(w_packed=0), dict(groups=3), dict(B=0)]
+    got = _run_validation_child([["conv3d_fwd_xp_supported", dict(_BASE_DESC, **xp)]] +
+                                [["conv3d_fwd_xp_supported", None if b is None else dict(_BASE_DESC, **dict(xp, **b))] for b in bad])
+    assert [g[0] for g in got] == [1] + [0] * len(bad), got
+
+
+def test_splitk_workspace_queries():
+    """Bytes of split-K partial outputs the fp32 3x3x3, LL and Winograd entry points ask for: ksplit x B x Cout x output plane x 4
+    bytes on small grids, 0 where the grid fills the chip or the descriptor is not taken."""
+    import ctypes as C
+    from tmdiff_amd import _lib
+    L = _lib.lib
+
+    def desc(**f):
+        d = _lib.Conv3dDesc()
+        for k, v in dict(_BASE_DESC, seg_x=[0], w_packed=0, y=0, **f).items():
+            if isinstance(v, list):
+                for i, x in enumerate(v):
+                    getattr(d, k)[i] = x
+            else:
+                setattr(d, k, v)
+        return C.byref(d)
+
+    small = dict(B=1, H=8, W=8, Cin=256, Cout=256, seg_c=[256])   # 8x8x8: one image leaves most of the chip idle
+    out = 256 * 8 * 8 * 8 * 4                                        # B x Cout x output plane x 4 bytes
+    assert L.tmdiff_conv3d_fwd_splitk_workspace_bytes(desc(**small)) == 32 * out
+    assert L.tmdiff_conv3d_fwd_splitk_workspace_bytes(desc(**dict(small, ksize=1))) == 0
+    assert L.tmdiff_conv3d_fwd_splitk_workspace_bytes(desc(B=32, H=64, W=64)) == 0
+    assert L.tmdiff_conv3d_fwd_splitk_workspace_bytes(None) == 0
+    assert L.tmdiff_conv3d_ll_splitk_workspace_bytes(desc(**dict(small, H=16, W=16))) == 32 * out
+    assert L.tmdiff_conv3d_wf_splitk_workspace_bytes(desc(**dict(small, W=16))) == 32 * 2 * out
+    assert L.tmdiff_conv3d_wfll_splitk_workspace_bytes(desc(**dict(small, Cin=64, seg_c=[64], H=16, W=16))) == 32 * out

@@ -723,12 +723,10 @@ int tmdiff::launch_prologue_apply(const tmdiff_conv3d_desc* d, float* xp, hipStr
   const long plane = (long)d->N * d->H * d->W;
   ApplyArgs q;
   q.B = d->B; q.Cin = d->Cin; q.nseg = d->nseg;
-  for (int i = 0; i < 3; ++i) { q.seg_c[i] = i < d->nseg ? d->seg_c[i] : 0; q.seg_x[i] = i < d->nseg ? d->seg_x[i] : nullptr; }
-  q.in_shift = d->in_shift; q.in_scale = d->in_scale; q.in_mask = d->in_mask; q.in_act = d->in_act;
-  q.drop_seed = d->drop_seed; q.drop_seed_dev = d->drop_seed_dev; q.drop_thresh = drop_threshold(d->drop_p);
-  q.drop_inv = d->drop_p > 0.f ? 1.0f / (1.0f - d->drop_p) : 0.f;
-  q.shift_stride = bank_stride(d->in_shift_stride, d->Cin);
-  q.scale_stride = bank_stride(d->in_scale_stride, d->Cin);
+  set_segments(q, d, 0, nullptr);
+  set_input_prologue(q, d);
+  q.in_mask = d->in_mask; q.in_act = d->in_act;
+  set_dropout(q, d);
   q.xp = xp;
   q.plane = plane;
   long pb = (plane + 1023) / 1024;
@@ -742,12 +740,7 @@ extern "C" int tmdiff_conv3d_prologue_fwd(const tmdiff_conv3d_desc* d, float* xp
   TMDIFF_REQUIRE(d && xp, "conv3d_prologue_fwd: NULL pointer");
   TMDIFF_REQUIRE(d->B >= 0 && d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0, "conv3d_prologue_fwd: bad extents");
   TMDIFF_REQUIRE(d->nseg >= 1 && d->nseg <= 3, "conv3d_prologue_fwd: nseg=%d", d->nseg);
-  int csum = 0;
-  for (int i = 0; i < d->nseg; ++i) {
-    TMDIFF_REQUIRE(d->seg_x[i] && d->seg_c[i] > 0, "conv3d_prologue_fwd: segment %d is empty", i);
-    csum += d->seg_c[i];
-  }
-  TMDIFF_REQUIRE(csum == d->Cin, "conv3d_prologue_fwd: segments hold %d channels, Cin=%d", csum, d->Cin);
+  if (const int rc = check_segments(d, "conv3d_prologue_fwd")) return rc;
   if (d->B == 0) return TMDIFF_OK;
   return launch_prologue_apply(d, xp, as_stream(stream));
 }
@@ -767,20 +760,13 @@ extern "C" int tmdiff_conv3d_wgrad(const tmdiff_conv3d_desc* d, const float* g, 
 extern "C" int tmdiff_conv3d_wgrad_bias(const tmdiff_conv3d_desc* d, const float* g, float* dw, float* dbias,
                                         void* workspace, tmdiff_stream_t stream) {
   using namespace tmdiff;
+  const char* what = "conv3d_wgrad";
   TMDIFF_REQUIRE(d && g && dw, "conv3d_wgrad: NULL pointer");
-  TMDIFF_REQUIRE(d->ksize == 1 || d->ksize == 3, "conv3d_wgrad: ksize=%d", d->ksize);
-  TMDIFF_REQUIRE(d->groups == 1 || d->groups == 3, "conv3d_wgrad: groups=%d", d->groups);
-  TMDIFF_REQUIRE(d->B > 0 && d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 &&
-                     d->Cin % d->groups == 0 && d->Cout % d->groups == 0, "conv3d_wgrad: bad extents");
-  TMDIFF_REQUIRE(d->nseg >= 1 && d->nseg <= 3, "conv3d_wgrad: nseg=%d", d->nseg);
-  int csum = 0;
-  for (int i = 0; i < d->nseg; ++i) {
-    TMDIFF_REQUIRE(d->seg_x[i] && d->seg_c[i] > 0, "conv3d_wgrad: segment %d is empty", i);
-    csum += d->seg_c[i];
-  }
-  TMDIFF_REQUIRE(csum == d->Cin, "conv3d_wgrad: segments hold %d channels, Cin=%d", csum, d->Cin);
+  if (const int rc = check_head(d, what)) return rc;
+  TMDIFF_REQUIRE(d->B > 0, "conv3d_wgrad: empty batch");
+  if (const int rc = check_segments(d, what)) return rc;
   TMDIFF_REQUIRE(workspace != nullptr, "conv3d_wgrad: NULL workspace");
-  TMDIFF_REQUIRE(!(d->in_mask && d->drop_p > 0.f), "conv3d_wgrad: give either a mask tensor or drop_p, not both");
+  if (const int rc = check_mask_or_dropout(d, what)) return rc;
   const WgradPlan p = plan_wgrad(d);
   TMDIFF_REQUIRE(p.total_boxes < (1L << 31) && (long)d->N * d->H * d->W * 32 < (1L << 31),
                  "conv3d_wgrad: tensor too large for 32-bit box / offset arithmetic");
@@ -872,13 +858,12 @@ int prologue_bwd_impl(const tmdiff_conv3d_desc* d, const float* gp, float* const
   using namespace tmdiff;
   TMDIFF_REQUIRE(d && gp && dx_seg && accumulate, "prologue_bwd: NULL pointer");
   TMDIFF_REQUIRE(d->B > 0 && d->Cin > 0 && d->B <= 65535 && d->nseg >= 1 && d->nseg <= 3, "prologue_bwd: bad extents");
-  TMDIFF_REQUIRE(!(d->in_mask && d->drop_p > 0.f), "prologue_bwd: give either a mask tensor or drop_p, not both");
+  if (const int rc = check_mask_or_dropout(d, "prologue_bwd")) return rc;
   PrologueBwdArgs a;
   a.B = d->B; a.Cin = d->Cin; a.nseg = d->nseg;
+  set_segments(a, d, 0, nullptr);
   int csum = 0;
   for (int i = 0; i < 3; ++i) {
-    a.seg_c[i] = i < d->nseg ? d->seg_c[i] : 0;
-    a.seg_x[i] = i < d->nseg ? d->seg_x[i] : nullptr;
     a.dx[i] = i < d->nseg ? dx_seg[i] : nullptr;
     a.accumulate[i] = i < d->nseg ? accumulate[i] : 0;
     a.add[i] = (add_seg && i < d->nseg) ? add_seg[i] : nullptr;
@@ -888,11 +873,9 @@ int prologue_bwd_impl(const tmdiff_conv3d_desc* d, const float* gp, float* const
     }
   }
   TMDIFF_REQUIRE(csum == d->Cin, "prologue_bwd: segments hold %d channels, Cin=%d", csum, d->Cin);
-  a.in_shift = d->in_shift; a.in_scale = d->in_scale; a.in_mask = d->in_mask; a.in_act = d->in_act;
-  a.shift_stride = bank_stride(d->in_shift_stride, d->Cin);
-  a.scale_stride = bank_stride(d->in_scale_stride, d->Cin);
-  a.drop_seed = d->drop_seed; a.drop_seed_dev = d->drop_seed_dev; a.drop_thresh = drop_threshold(d->drop_p);
-  a.drop_inv = d->drop_p > 0.f ? 1.0f / (1.0f - d->drop_p) : 0.f;
+  set_input_prologue(a, d);
+  a.in_mask = d->in_mask; a.in_act = d->in_act;
+  set_dropout(a, d);
   a.gp = gp; a.d_shift = d_shift; a.d_scale = d_scale;
   a.plane = (long)d->N * d->H * d->W;
   a.slices = workspace ? prologue_bwd_slices(d) : 1;

@@ -23,6 +23,11 @@ inline int fail(int code, const char* fmt, ...) {
   return code;
 }
 
+#define TMDIFF_REQUIRE(cond, ...) \
+  do {                            \
+    if (!(cond)) return tmdiff::fail(TMDIFF_E_INVALID, __VA_ARGS__); \
+  } while (0)
+
 inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(TMDIFF_E_LAUNCH, "%s: %s", what, hipGetErrorString(e));
@@ -124,8 +129,13 @@ struct Conv3Plan {
   int ksplit;    // 1 = no split; else the chunks (4 input channels each) are divided into ksplit equal ranges
 };
 Conv3Plan plan_conv3(const tmdiff_conv3d_desc* d);
-// the dwordx4 epilogue (epilogue.h) applies: W % 4 == 0, 16-byte aligned outputs / residual (TMDIFF_EPILOGUE_VEC=0: never)
-bool epilogue_vec_ok(const tmdiff_conv3d_desc* d);
+// The shape rule of the dwordx4 epilogue (epilogue.h) for an output of W columns and `plane` positions: W % 4 == 0, 16-byte
+// aligned outputs / residual, planes of at most 2^23 positions (it addresses up to 128 channels of a sample through one
+// descriptor of 32-bit offsets).  epilogue_vec_ok: the same, unless TMDIFF_EPILOGUE_VEC=0 (conv3d.hip; experiments).
+inline bool epilogue_vec_shape(const tmdiff_conv3d_desc* d, int W, long plane) {
+  return W % 4 == 0 && aligned16(d->y) && aligned16(d->residual) && (d->y2_bf16 || aligned16(d->y2)) && plane <= (1L << 23);
+}
+bool epilogue_vec_ok(const tmdiff_conv3d_desc* d, int W, long plane);
 
 // sum of the split-K partials + epilogue (conv3d.hip)
 struct SplitKReduceArgs {
@@ -145,12 +155,114 @@ struct SplitKReduceArgs {
 };
 int launch_splitk_reduce(const SplitKReduceArgs& r, hipStream_t st);
 
+// Split-K over a lent workspace (tmdiff_conv3d_desc.splitk_ws): the bytes of partial outputs [ks][B][Cout][plane] a launch split
+// `ks` ways writes (0: no split), the workspace when it is lent, large enough and aligned (else NULL: the launch runs unsplit),
+// and the reduction that sums the partials and applies the epilogue (bias_scale: the caller's, factors included).
+inline size_t splitk_bytes(int ks, const tmdiff_conv3d_desc* d, long plane) {
+  return ks > 1 ? (size_t)ks * d->B * d->Cout * plane * sizeof(float) : 0;
+}
+inline float* lend_splitk(const tmdiff_conv3d_desc* d, int ks, long plane) {
+  const bool ok = ks > 1 && d->splitk_ws && (size_t)d->splitk_ws_bytes >= splitk_bytes(ks, d, plane) && aligned16(d->splitk_ws);
+  return ok ? static_cast<float*>(d->splitk_ws) : nullptr;
+}
+template <class Args>
+int finish_splitk(const Args& a, const tmdiff_conv3d_desc* d, long plane, float bias_scale, hipStream_t st) {
+  const SplitKReduceArgs r{a.part, a.ksplit, d->B, d->Cout, plane, d->bias, bias_scale, d->residual, d->out_scale, d->y, d->y2,
+                           d->y2_shift, d->y2_scale, a.y2_shift_stride, a.y2_scale_stride, d->y2_act};
+  return launch_splitk_reduce(r, st);
+}
+
+// ---- Descriptor checks of the convolution entry points.  Each returns TMDIFF_OK or fails with a message that begins with the
+// entry point's name `what`. -----------------------------------------------------------------------------------------------
+
+// extents (B may be 0), ksize 1 or 3, groups 1 or 3, Cin and Cout positive multiples of groups, 1..3 input segments
+inline int check_head(const tmdiff_conv3d_desc* d, const char* what) {
+  TMDIFF_REQUIRE(d->B >= 0 && d->N > 0 && d->H > 0 && d->W > 0, "%s: bad extents B=%d N=%d H=%d W=%d", what, d->B, d->N, d->H, d->W);
+  TMDIFF_REQUIRE(d->ksize == 1 || d->ksize == 3, "%s: ksize=%d (1 or 3)", what, d->ksize);
+  TMDIFF_REQUIRE(d->groups == 1 || d->groups == 3, "%s: groups=%d (1 or 3)", what, d->groups);
+  TMDIFF_REQUIRE(d->Cin > 0 && d->Cout > 0 && d->Cin % d->groups == 0 && d->Cout % d->groups == 0, "%s: Cin=%d Cout=%d groups=%d",
+                 what, d->Cin, d->Cout, d->groups);
+  TMDIFF_REQUIRE(d->nseg >= 1 && d->nseg <= 3, "%s: nseg=%d", what, d->nseg);
+  return TMDIFF_OK;
+}
+
+// the d->nseg segments: non-NULL, non-empty and, with `aligned`, 16-byte aligned; channels summing to Cin.  A segment whose
+// channel count is not a multiple of `unit` fails with TMDIFF_E_UNSUPPORTED.
+inline int check_segments(const tmdiff_conv3d_desc* d, const char* what, bool aligned = false, int unit = 1) {
+  int csum = 0;
+  for (int i = 0; i < d->nseg; ++i) {
+    TMDIFF_REQUIRE(d->seg_x[i] && d->seg_c[i] > 0 && (!aligned || aligned16(d->seg_x[i])), "%s: segment %d is empty%s", what, i,
+                   aligned ? " / unaligned" : "");
+    if (d->seg_c[i] % unit) return fail(TMDIFF_E_UNSUPPORTED, "%s: segment of %d channels", what, d->seg_c[i]);
+    csum += d->seg_c[i];
+  }
+  TMDIFF_REQUIRE(csum == d->Cin, "%s: segments hold %d channels, Cin=%d", what, csum, d->Cin);
+  return TMDIFF_OK;
+}
+// the same as a predicate (nseg included; support queries)
+inline bool segments_ok(const tmdiff_conv3d_desc* d) {
+  if (d->nseg < 1 || d->nseg > 3) return false;
+  int csum = 0;
+  for (int i = 0; i < d->nseg; ++i) {
+    if (!d->seg_x[i] || d->seg_c[i] <= 0) return false;
+    csum += d->seg_c[i];
+  }
+  return csum == d->Cin;
+}
+
+// groups = 3 takes one segment or three equal ones
+inline int check_group_segments(const tmdiff_conv3d_desc* d, const char* what) {
+  TMDIFF_REQUIRE(d->groups != 3 || d->nseg == 1 || (d->nseg == 3 && d->seg_c[0] == d->seg_c[1] && d->seg_c[1] == d->seg_c[2]),
+                 "%s: groups=3 wants 1 segment or 3 equal ones", what);
+  return TMDIFF_OK;
+}
+
+// a mask tensor or in-kernel dropout, not both; check_dropout: and 0 <= drop_p < 1
+inline int check_mask_or_dropout(const tmdiff_conv3d_desc* d, const char* what) {
+  TMDIFF_REQUIRE(!(d->in_mask && d->drop_p > 0.f), "%s: give either a mask tensor or drop_p, not both", what);
+  return TMDIFF_OK;
+}
+inline int check_dropout(const tmdiff_conv3d_desc* d, const char* what) {
+  if (const int rc = check_mask_or_dropout(d, what)) return rc;
+  TMDIFF_REQUIRE(d->drop_p >= 0.f && d->drop_p < 1.f, "%s: drop_p=%g (0 <= drop_p < 1)", what, (double)d->drop_p);
+  return TMDIFF_OK;
+}
+
+// ---- Descriptor fields of the kernels' argument structs (host side).  Each sets only the fields it names. ------------------
+
+// the input segments; the unused ones get (pad_c, pad_x)
+template <class Args>
+void set_segments(Args& a, const tmdiff_conv3d_desc* d, int pad_c, const float* pad_x) {
+  for (int i = 0; i < 3; ++i) {
+    a.seg_c[i] = i < d->nseg ? d->seg_c[i] : pad_c;
+    a.seg_x[i] = i < d->nseg ? d->seg_x[i] : pad_x;
+  }
+}
+// the input's shift / scale banks (in_act and in_mask are the caller's: not every kernel has them)
+template <class Args>
+void set_input_prologue(Args& a, const tmdiff_conv3d_desc* d) {
+  a.in_shift = d->in_shift; a.in_scale = d->in_scale;
+  a.shift_stride = bank_stride(d->in_shift_stride, d->Cin);
+  a.scale_stride = bank_stride(d->in_scale_stride, d->Cin);
+}
+// in-kernel dropout (drop_inv > 0): common.h drop_keep
+template <class Args>
+void set_dropout(Args& a, const tmdiff_conv3d_desc* d) {
+  a.drop_seed = d->drop_seed; a.drop_seed_dev = d->drop_seed_dev; a.drop_thresh = drop_threshold(d->drop_p);
+  a.drop_inv = d->drop_p > 0.f ? 1.0f / (1.0f - d->drop_p) : 0.f;
+}
+// bias and epilogue: out = (conv + bias * bias_scale + residual) * out_scale, the second output y2 = act2(out + shift2) * scale2
+// (a caller with a factor on the bias applies it to a.bias_scale afterwards)
+template <class Args>
+void set_outputs(Args& a, const tmdiff_conv3d_desc* d) {
+  a.bias = d->bias; a.bias_scale = d->bias_scale;
+  a.residual = d->residual; a.out_scale = d->out_scale; a.y = d->y;
+  a.y2 = reinterpret_cast<decltype(a.y2)>(d->y2); a.y2_shift = d->y2_shift; a.y2_scale = d->y2_scale; a.y2_act = d->y2_act;
+  a.y2_shift_stride = bank_stride(d->y2_shift_stride, d->Cout);
+  a.y2_scale_stride = bank_stride(d->y2_scale_stride, d->Cout);
+}
+
 // 1x1x1 forward through the LDS-free bandwidth kernel (conv1.hip); TMDIFF_E_UNSUPPORTED = shape not taken.
 int conv1_fp32_try(const tmdiff_conv3d_desc* d, hipStream_t st, bool dry = false);   // dry: no launch, TMDIFF_OK = the 16-byte kernel on a raw input
 
 }  // namespace tmdiff
-
-#define TMDIFF_REQUIRE(cond, ...) \
-  do {                            \
-    if (!(cond)) return tmdiff::fail(TMDIFF_E_INVALID, __VA_ARGS__); \
-  } while (0)

@@ -415,14 +415,9 @@ int tmdiff::conv1_fp32_try(const tmdiff_conv3d_desc* d, hipStream_t st, bool dry
   if (plane * 2 * G >= (1L << 31)) return TMDIFF_E_UNSUPPORTED;
   K1Args a;
   a.B = d->B; a.Cin = d->Cin; a.Cout = d->Cout; a.cin_g = cin_g; a.cout_g = cout_g; a.groups = d->groups;
-  for (int i = 0; i < 3; ++i) {
-    a.seg_c[i] = i < d->nseg ? d->seg_c[i] : (1 << 28);
-    a.seg_x[i] = i < d->nseg ? d->seg_x[i] : d->seg_x[0];
-  }
+  set_segments(a, d, 1 << 28, d->seg_x[0]);
   a.wp = d->w_packed; a.bias = d->bias; a.bias_scale = d->bias_scale;
-  a.in_shift = d->in_shift; a.in_scale = d->in_scale;
-  a.shift_stride = bank_stride(d->in_shift_stride, d->Cin);
-  a.scale_stride = bank_stride(d->in_scale_stride, d->Cin);
+  set_input_prologue(a, d);
   a.residual = d->residual; a.out_scale = d->out_scale; a.y = d->y;
   a.plane = plane;
   a.xp_out = d->xp_out; a.xp_shift = d->xp_shift; a.xp_act = d->xp_act;
@@ -449,12 +444,7 @@ int tmdiff::conv1_fp32_try(const tmdiff_conv3d_desc* d, hipStream_t st, bool dry
 // 1 when tmdiff_conv3d_fwd would write the by-product d->xp_out for this descriptor (the 16-byte bandwidth kernel takes it), else 0.
 extern "C" int tmdiff_conv3d_fwd_xp_supported(const tmdiff_conv3d_desc* d) {
   if (!d || !d->xp_out || d->x_bf16 || d->groups <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->Cin % d->groups || d->Cout % d->groups ||
-      d->nseg < 1 || d->nseg > 3 || d->B <= 0 || !d->w_packed)
+      d->B <= 0 || !d->w_packed)
     return 0;
-  int csum = 0;
-  for (int i = 0; i < d->nseg; ++i) {
-    if (!d->seg_x[i] || d->seg_c[i] <= 0) return 0;
-    csum += d->seg_c[i];
-  }
-  return csum == d->Cin && tmdiff::conv1_fp32_try(d, nullptr, true) == TMDIFF_OK ? 1 : 0;
+  return tmdiff::segments_ok(d) && tmdiff::conv1_fp32_try(d, nullptr, true) == TMDIFF_OK ? 1 : 0;
 }

@@ -622,11 +622,9 @@ static long splitk_target() {
   return t;
 }
 
-bool epilogue_vec_ok(const tmdiff_conv3d_desc* d) {
+bool epilogue_vec_ok(const tmdiff_conv3d_desc* d, int W, long plane) {
   static const bool on = !env_off("TMDIFF_EPILOGUE_VEC");   // experiments: "0" = the scalar epilogue everywhere
-  // (the dwordx4 epilogue addresses up to 128 channels of a sample through one descriptor of 32-bit offsets: planes <= 2^23)
-  return on && d->W % 4 == 0 && aligned16(d->y) && aligned16(d->residual) && (d->y2_bf16 || aligned16(d->y2)) &&
-         (long)d->N * d->H * d->W <= (1L << 23);
+  return on && epilogue_vec_shape(d, W, plane);
 }
 
 Conv3Plan plan_conv3(const tmdiff_conv3d_desc* d) {
@@ -672,8 +670,7 @@ Conv3Plan plan_conv3(const tmdiff_conv3d_desc* d) {
 
 extern "C" size_t tmdiff_conv3d_fwd_splitk_workspace_bytes(const tmdiff_conv3d_desc* d) {
   if (!d || d->ksize != 3 || d->B <= 0 || d->groups <= 0 || d->Cin % d->groups || d->Cout % d->groups) return 0;
-  const tmdiff::Conv3Plan p = tmdiff::plan_conv3(d);
-  return p.ksplit > 1 ? (size_t)p.ksplit * d->B * d->Cout * d->N * d->H * d->W * sizeof(float) : 0;
+  return tmdiff::splitk_bytes(tmdiff::plan_conv3(d).ksplit, d, (long)d->N * d->H * d->W);
 }
 
 extern "C" int tmdiff_conv3d_pack_weights(const float* w, float* packed, int32_t Cout, int32_t Cin, int32_t ksize,
@@ -714,27 +711,16 @@ extern "C" int tmdiff_conv3d_pack_weights_multi(const tmdiff_pack_entry* entries
 
 extern "C" int tmdiff_conv3d_fwd(const tmdiff_conv3d_desc* d, tmdiff_stream_t stream) {
   using namespace tmdiff;
+  const char* what = "conv3d_fwd";
   TMDIFF_REQUIRE(d != nullptr, "conv3d_fwd: NULL descriptor");
-  TMDIFF_REQUIRE(d->B >= 0 && d->N > 0 && d->H > 0 && d->W > 0, "conv3d_fwd: bad extents B=%d N=%d H=%d W=%d", d->B,
-                 d->N, d->H, d->W);
-  TMDIFF_REQUIRE(d->ksize == 1 || d->ksize == 3, "conv3d_fwd: ksize=%d (1 or 3)", d->ksize);
-  TMDIFF_REQUIRE(d->groups == 1 || d->groups == 3, "conv3d_fwd: groups=%d (1 or 3)", d->groups);
-  TMDIFF_REQUIRE(d->Cin > 0 && d->Cout > 0 && d->Cin % d->groups == 0 && d->Cout % d->groups == 0,
-                 "conv3d_fwd: Cin=%d Cout=%d groups=%d", d->Cin, d->Cout, d->groups);
-  TMDIFF_REQUIRE(d->nseg >= 1 && d->nseg <= 3, "conv3d_fwd: nseg=%d", d->nseg);
+  if (const int rc = check_head(d, what)) return rc;
   if (d->B == 0) return TMDIFF_OK;  // empty batch: nothing to read or write
-  int csum = 0;
-  for (int i = 0; i < d->nseg; ++i) {
-    TMDIFF_REQUIRE(d->seg_x[i] != nullptr && d->seg_c[i] > 0, "conv3d_fwd: segment %d is empty", i);
-    csum += d->seg_c[i];
-  }
-  TMDIFF_REQUIRE(csum == d->Cin, "conv3d_fwd: segments hold %d channels, Cin=%d", csum, d->Cin);
-  if (d->groups == 3)
-    TMDIFF_REQUIRE(d->nseg == 1 || (d->nseg == 3 && d->seg_c[0] == d->seg_c[1] && d->seg_c[1] == d->seg_c[2]),
-                   "conv3d_fwd: groups=3 wants 1 segment or 3 equal ones");
+  if (const int rc = check_segments(d, what)) return rc;
+  if (const int rc = check_group_segments(d, what)) return rc;
   TMDIFF_REQUIRE(d->w_packed && (d->y || d->y2), "conv3d_fwd: NULL weights/output");
   TMDIFF_REQUIRE(!d->y2 || !d->y2_bf16, "conv3d_fwd: a bf16-packed second output needs tmdiff_conv3d_fwd_bf16");
-  TMDIFF_REQUIRE((long)d->N * d->H * d->W < (1L << 31), "conv3d_fwd: plane too large for 32-bit offsets");
+  const long plane = (long)d->N * d->H * d->W;
+  TMDIFF_REQUIRE(plane < (1L << 31), "conv3d_fwd: plane too large for 32-bit offsets");
 
   if (d->ksize == 1) {  // bandwidth kernel for the shapes it takes (every production 1x1x1 layer)
     const int rc = conv1_fp32_try(d, as_stream(stream));
@@ -743,39 +729,28 @@ extern "C" int tmdiff_conv3d_fwd(const tmdiff_conv3d_desc* d, tmdiff_stream_t st
   if (d->xp_out)
     return fail(TMDIFF_E_UNSUPPORTED, "conv3d_fwd: only the 1x1x1 bandwidth kernel writes the by-product xp_out (fp32, ksize 1, no mask / "
                                       "dropout / second output, Cin/g and every segment %% 16 == 0, Cout/g %% 32 == 0)");
+  if (const int rc = check_dropout(d, what)) return rc;
 
   ConvArgs a;
   a.B = d->B; a.N = d->N; a.H = d->H; a.W = d->W;
   a.Cin = d->Cin; a.Cout = d->Cout; a.groups = d->groups;
   a.cin_g = d->Cin / d->groups; a.cout_g = d->Cout / d->groups;
   a.nseg = d->nseg;
-  for (int i = 0; i < 3; ++i) {  // unused segments: never selected (huge channel count), but with a valid pointer
-    a.seg_c[i] = i < d->nseg ? d->seg_c[i] : (1 << 28);
-    a.seg_x[i] = i < d->nseg ? d->seg_x[i] : d->seg_x[0];
-  }
-  a.wp = d->w_packed; a.bias = d->bias; a.bias_scale = d->bias_scale;
-  a.in_shift = d->in_shift; a.in_scale = d->in_scale; a.in_mask = d->in_mask; a.in_act = d->in_act;
-  TMDIFF_REQUIRE(!(d->in_mask && d->drop_p > 0.f), "conv3d_fwd: give either a mask tensor or drop_p, not both");
-  TMDIFF_REQUIRE(d->drop_p >= 0.f && d->drop_p < 1.f, "conv3d_fwd: drop_p=%g", (double)d->drop_p);
-  a.drop_seed = d->drop_seed; a.drop_seed_dev = d->drop_seed_dev; a.drop_thresh = drop_threshold(d->drop_p);
-  a.drop_inv = d->drop_p > 0.f ? 1.0f / (1.0f - d->drop_p) : 0.f;
-  a.shift_stride = bank_stride(d->in_shift_stride, d->Cin);
-  a.scale_stride = bank_stride(d->in_scale_stride, d->Cin);
-  a.residual = d->residual; a.out_scale = d->out_scale; a.y = d->y;
-  a.y2 = d->y2; a.y2_shift = d->y2_shift; a.y2_scale = d->y2_scale; a.y2_act = d->y2_act;
-  a.y2_shift_stride = bank_stride(d->y2_shift_stride, d->Cout);
-  a.y2_scale_stride = bank_stride(d->y2_scale_stride, d->Cout);
+  set_segments(a, d, 1 << 28, d->seg_x[0]);   // unused segments: never selected (huge channel count), but with a valid pointer
+  a.wp = d->w_packed;
+  set_input_prologue(a, d);
+  a.in_mask = d->in_mask; a.in_act = d->in_act;
+  set_dropout(a, d);
+  set_outputs(a, d);
   a.w_vec4 = (a.cout_g % 4 == 0) && aligned16(d->w_packed);
-  a.vec4 = epilogue_vec_ok(d);
+  a.vec4 = epilogue_vec_ok(d, d->W, plane);
   hipStream_t st = as_stream(stream);
 
   a.ksplit = 1; a.split_ch = a.cin_g; a.part = nullptr;
   if (d->ksize == 3) {  // tile configuration and split-K factor: plan_conv3 (shared with the staged kernel)
     Conv3Plan plan = plan_conv3(d);
-    const size_t need = (size_t)plan.ksplit * d->B * d->Cout * d->N * d->H * d->W * sizeof(float);
-    if (plan.ksplit > 1 && d->splitk_ws && (size_t)d->splitk_ws_bytes >= need && aligned16(d->splitk_ws)) {
-      a.ksplit = plan.ksplit; a.split_ch = a.cin_g / plan.ksplit; a.part = static_cast<float*>(d->splitk_ws);
-    }
+    a.part = lend_splitk(d, plan.ksplit, plane);
+    if (a.part) { a.ksplit = plan.ksplit; a.split_ch = a.cin_g / plan.ksplit; }
     int rc;
     switch (plan.tile) {
       case 0: rc = launch<3, 1, 2, 4, 2, 8, 8>(a, st); break;
@@ -784,9 +759,7 @@ extern "C" int tmdiff_conv3d_fwd(const tmdiff_conv3d_desc* d, tmdiff_stream_t st
       default: rc = launch<3, 2, 1, 4, 4, 8, 8>(a, st); break;
     }
     if (rc || !a.part) return rc;
-    SplitKReduceArgs r{a.part, a.ksplit, d->B, d->Cout, (long)d->N * d->H * d->W, d->bias, d->bias_scale, d->residual,
-                       d->out_scale, d->y, d->y2, d->y2_shift, d->y2_scale, a.y2_shift_stride, a.y2_scale_stride, d->y2_act};
-    return launch_splitk_reduce(r, st);
+    return finish_splitk(a, d, plane, d->bias_scale, st);
   }
   const bool c64 = a.cout_g % 64 == 0;
   if (c64) return launch<1, 2, 2, 8, 4, 8, 8>(a, st);

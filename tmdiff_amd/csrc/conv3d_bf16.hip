@@ -943,30 +943,17 @@ extern "C" int tmdiff_conv3d_pack_weights_bf16(const float* w, void* packed, int
 
 extern "C" int tmdiff_conv3d_fwd_bf16(const tmdiff_conv3d_desc* d, void* workspace, tmdiff_stream_t stream) {
   using namespace tmdiff;
+  const char* what = "conv3d_fwd_bf16";
   TMDIFF_REQUIRE(d != nullptr, "conv3d_fwd_bf16: NULL descriptor");
-  TMDIFF_REQUIRE(d->B >= 0 && d->N > 0 && d->H > 0 && d->W > 0, "conv3d_fwd_bf16: bad extents B=%d N=%d H=%d W=%d", d->B,
-                 d->N, d->H, d->W);
-  TMDIFF_REQUIRE(d->groups == 1 || d->groups == 3, "conv3d_fwd_bf16: groups=%d (1 or 3)", d->groups);
-  TMDIFF_REQUIRE(d->Cin > 0 && d->Cout > 0 && d->Cin % d->groups == 0 && d->Cout % d->groups == 0,
-                 "conv3d_fwd_bf16: Cin=%d Cout=%d groups=%d", d->Cin, d->Cout, d->groups);
-  TMDIFF_REQUIRE(d->nseg >= 1 && d->nseg <= 3, "conv3d_fwd_bf16: nseg=%d", d->nseg);
-  TMDIFF_REQUIRE(d->ksize == 1 || d->ksize == 3, "conv3d_fwd_bf16: ksize=%d (1 or 3)", d->ksize);
+  if (const int rc = check_head(d, what)) return rc;
   if (d->in_mask || d->drop_p > 0.f) return fail(TMDIFF_E_UNSUPPORTED, "conv3d_fwd_bf16: dropout (training) is fp32 only");
   const int cin_g = d->Cin / d->groups, cout_g = d->Cout / d->groups;
   if (cin_g % (d->ksize == 3 ? 8 : 16) || cout_g % 32)
     return fail(TMDIFF_E_UNSUPPORTED, "conv3d_fwd_bf16: Cin/g=%d (multiple of %d) Cout/g=%d (multiple of 32)", cin_g,
                 d->ksize == 3 ? 8 : 16, cout_g);
   if (d->B == 0) return TMDIFF_OK;
-  int csum = 0;
-  for (int i = 0; i < d->nseg; ++i) {
-    TMDIFF_REQUIRE(d->seg_x[i] != nullptr && d->seg_c[i] > 0, "conv3d_fwd_bf16: segment %d is empty", i);
-    if (d->seg_c[i] % 8) return fail(TMDIFF_E_UNSUPPORTED, "conv3d_fwd_bf16: segment of %d channels", d->seg_c[i]);
-    csum += d->seg_c[i];
-  }
-  TMDIFF_REQUIRE(csum == d->Cin, "conv3d_fwd_bf16: segments hold %d channels, Cin=%d", csum, d->Cin);
-  if (d->groups == 3)
-    TMDIFF_REQUIRE(d->nseg == 1 || (d->nseg == 3 && d->seg_c[0] == d->seg_c[1] && d->seg_c[1] == d->seg_c[2]),
-                   "conv3d_fwd_bf16: groups=3 wants 1 segment or 3 equal ones");
+  if (const int rc = check_segments(d, what, false, 8)) return rc;
+  if (const int rc = check_group_segments(d, what)) return rc;
   TMDIFF_REQUIRE(d->w_packed && (d->y || d->y2), "conv3d_fwd_bf16: NULL weights/output");
   if (d->y2) {
     if (!d->y2_bf16) return fail(TMDIFF_E_UNSUPPORTED, "conv3d_fwd_bf16: the second output is written as bf16 units (y2_bf16)");
@@ -983,21 +970,14 @@ extern "C" int tmdiff_conv3d_fwd_bf16(const tmdiff_conv3d_desc* d, void* workspa
   BfArgs a;
   a.B = d->B; a.N = d->N; a.H = d->H; a.W = d->W;
   a.Cin = d->Cin; a.Cout = d->Cout; a.groups = d->groups; a.cin_g = cin_g; a.cout_g = cout_g;
-  for (int i = 0; i < 3; ++i) {
-    a.seg_c[i] = i < d->nseg ? d->seg_c[i] : (1 << 28);
-    a.seg_x[i] = i < d->nseg ? d->seg_x[i] : d->seg_x[0];
-  }
+  set_segments(a, d, 1 << 28, d->seg_x[0]);
   a.wp = reinterpret_cast<const uint4*>(d->w_packed);
-  a.bias = d->bias; a.bias_scale = d->bias_scale;
-  a.in_shift = d->in_shift; a.in_scale = d->in_scale; a.in_act = d->in_act;
-  a.shift_stride = bank_stride(d->in_shift_stride, d->Cin);
-  a.scale_stride = bank_stride(d->in_scale_stride, d->Cin);
-  a.residual = d->residual; a.out_scale = d->out_scale; a.y = d->y;
-  a.y2 = reinterpret_cast<uint4*>(d->y2); a.y2_shift = d->y2_shift; a.y2_scale = d->y2_scale; a.y2_act = d->y2_act;
-  a.y2_shift_stride = bank_stride(d->y2_shift_stride, d->Cout);
-  a.y2_scale_stride = bank_stride(d->y2_scale_stride, d->Cout);
-  // (the dwordx4 epilogue addresses its tensors through descriptors of 32-bit offsets: planes of at most 2^24 positions)
-  a.vec4 = d->W % 4 == 0 && (!d->y || aligned16(d->y)) && (!d->residual || aligned16(d->residual)) && (long)d->N * d->H * d->W <= (1L << 24);
+  set_input_prologue(a, d);
+  a.in_act = d->in_act;
+  set_outputs(a, d);
+  // The dwordx4 epilogue (store_tile_v) addresses the MSUB x 32 channels of a tile through one descriptor of 32-bit offsets,
+  // MSUB * 32 * plane * 4 bytes: below 2^32 for MSUB = 2 (the 64-channel tiles) when the plane has fewer than 2^24 positions.
+  a.vec4 = d->W % 4 == 0 && aligned16(d->y) && aligned16(d->residual) && (long)d->N * d->H * d->W < (1L << 24);
   a.stamps = TMDIFF_BF16_STAMPS ? static_cast<unsigned long long*>(d->splitk_ws) : nullptr;
   hipStream_t st = as_stream(stream);
   if (d->x_bf16) {  // input already packed by its producer: straight to the staging-free kernel

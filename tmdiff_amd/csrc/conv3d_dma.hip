@@ -319,22 +319,17 @@ extern "C" size_t tmdiff_conv3d_fwd_staged_workspace_bytes(const tmdiff_conv3d_d
 
 extern "C" int tmdiff_conv3d_fwd_staged(const tmdiff_conv3d_desc* d, void* workspace, tmdiff_stream_t stream) {
   using namespace tmdiff;
+  const char* what = "conv3d_fwd_staged";
   TMDIFF_REQUIRE(d != nullptr, "conv3d_fwd_staged: NULL descriptor");
   if (!staged_ok(d)) return fail(TMDIFF_E_UNSUPPORTED, "conv3d_fwd_staged: shape not supported (use tmdiff_conv3d_fwd)");
-  TMDIFF_REQUIRE(d->B >= 0 && d->N > 0 && d->H > 0 && d->W > 0, "conv3d_fwd_staged: bad extents");
-  TMDIFF_REQUIRE(d->nseg >= 1 && d->nseg <= 3, "conv3d_fwd_staged: nseg=%d", d->nseg);
+  if (const int rc = check_head(d, what)) return rc;
   if (d->B == 0) return TMDIFF_OK;
-  int csum = 0;
-  for (int i = 0; i < d->nseg; ++i) {
-    TMDIFF_REQUIRE(d->seg_x[i] != nullptr && d->seg_c[i] > 0, "conv3d_fwd_staged: segment %d is empty", i);
-    csum += d->seg_c[i];
-  }
-  TMDIFF_REQUIRE(csum == d->Cin, "conv3d_fwd_staged: segments hold %d channels, Cin=%d", csum, d->Cin);
+  if (const int rc = check_segments(d, what)) return rc;
   TMDIFF_REQUIRE(d->w_packed && (d->y || d->y2) && aligned16(d->w_packed), "conv3d_fwd_staged: NULL / unaligned weights or output");
   TMDIFF_REQUIRE(!d->y2 || !d->y2_bf16, "conv3d_fwd_staged: a bf16-packed second output needs tmdiff_conv3d_fwd_bf16");
-  TMDIFF_REQUIRE(!(d->in_mask && d->drop_p > 0.f) && d->drop_p >= 0.f && d->drop_p < 1.f,
-                 "conv3d_fwd_staged: give either a mask tensor or 0 <= drop_p < 1");
-  TMDIFF_REQUIRE((long)d->N * d->H * d->W * 8 < (1L << 31), "conv3d_fwd_staged: plane too large");
+  if (const int rc = check_dropout(d, what)) return rc;
+  const long plane = (long)d->N * d->H * d->W;
+  TMDIFF_REQUIRE(plane * 8 < (1L << 31), "conv3d_fwd_staged: plane too large");
   hipStream_t st = as_stream(stream);
 
   DmaArgs a;
@@ -349,20 +344,15 @@ extern "C" int tmdiff_conv3d_fwd_staged(const tmdiff_conv3d_desc* d, void* works
     if (rc) return rc;
     a.xq = xp;
   }
-  a.wp = d->w_packed; a.bias = d->bias; a.bias_scale = d->bias_scale;
-  a.residual = d->residual; a.out_scale = d->out_scale; a.y = d->y;
-  a.y2 = d->y2; a.y2_shift = d->y2_shift; a.y2_scale = d->y2_scale; a.y2_act = d->y2_act;
-  a.y2_shift_stride = bank_stride(d->y2_shift_stride, d->Cout);
-  a.y2_scale_stride = bank_stride(d->y2_scale_stride, d->Cout);
-  a.vec4 = tmdiff::epilogue_vec_ok(d);
+  a.wp = d->w_packed;
+  set_outputs(a, d);
+  a.vec4 = epilogue_vec_ok(d, d->W, plane);
 
   // tile configuration and split-K factor: plan_conv3 (conv3d.hip), the same rule as tmdiff_conv3d_fwd
   Conv3Plan plan = plan_conv3(d);
-  a.ksplit = 1; a.split_chunks = a.cin_g / 4; a.part = nullptr;
-  const size_t need = (size_t)plan.ksplit * d->B * d->Cout * d->N * d->H * d->W * sizeof(float);
-  if (plan.ksplit > 1 && d->splitk_ws && (size_t)d->splitk_ws_bytes >= need && aligned16(d->splitk_ws)) {
-    a.ksplit = plan.ksplit; a.split_chunks = a.cin_g / 4 / plan.ksplit; a.part = static_cast<float*>(d->splitk_ws);
-  }
+  a.ksplit = 1; a.split_chunks = a.cin_g / 4;
+  a.part = lend_splitk(d, plan.ksplit, plane);
+  if (a.part) { a.ksplit = plan.ksplit; a.split_chunks = a.cin_g / 4 / plan.ksplit; }
   int rc;
   switch (plan.tile) {
     case 0: rc = launch<3, 1, 2, 4, 2, 8, 8>(a, st); break;
@@ -371,7 +361,5 @@ extern "C" int tmdiff_conv3d_fwd_staged(const tmdiff_conv3d_desc* d, void* works
     default: rc = launch<3, 2, 1, 4, 4, 8, 8>(a, st); break;
   }
   if (rc || !a.part) return rc;
-  SplitKReduceArgs r{a.part, a.ksplit, d->B, d->Cout, (long)d->N * d->H * d->W, d->bias, d->bias_scale, d->residual,
-                     d->out_scale, d->y, d->y2, d->y2_shift, d->y2_scale, a.y2_shift_stride, a.y2_scale_stride, d->y2_act};
-  return launch_splitk_reduce(r, st);
+  return finish_splitk(a, d, plane, d->bias_scale, st);
 }

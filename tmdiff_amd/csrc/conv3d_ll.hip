@@ -335,8 +335,7 @@ extern "C" int tmdiff_conv3d_ll_supported(const tmdiff_conv3d_desc* d) { return 
 
 extern "C" size_t tmdiff_conv3d_ll_splitk_workspace_bytes(const tmdiff_conv3d_desc* d) {
   if (!ll_ok(d) || d->B <= 0) return 0;
-  const LlPlan p = plan_ll(d);
-  return p.ksplit > 1 ? (size_t)p.ksplit * d->B * d->Cout * d->N * (d->H / 2) * (d->W / 2) * sizeof(float) : 0;
+  return splitk_bytes(plan_ll(d).ksplit, d, (long)d->N * (d->H / 2) * (d->W / 2));
 }
 
 extern "C" size_t tmdiff_conv3d_ll_packed_bytes(int32_t Cout, int32_t Cin) {
@@ -370,23 +369,16 @@ extern "C" int tmdiff_conv3d_ll_fwd(const tmdiff_conv3d_desc* d, float ll_scale,
   a.B = d->B; a.N = d->N; a.Hi = d->H; a.Wi = d->W; a.H = d->H / 2; a.W = d->W / 2;
   a.Cin = d->Cin; a.Cout = d->Cout; a.cout_g = d->Cout;
   a.xq = d->seg_x[0]; a.wp = d->w_packed;
-  a.bias = d->bias; a.bias_scale = d->bias_scale * 2.0f * ll_scale;   // the (scaled) LL band of a constant
-  a.residual = d->residual; a.out_scale = d->out_scale; a.y = d->y;
-  a.y2 = d->y2; a.y2_shift = d->y2_shift; a.y2_scale = d->y2_scale; a.y2_act = d->y2_act;
-  a.y2_shift_stride = bank_stride(d->y2_shift_stride, d->Cout);
-  a.y2_scale_stride = bank_stride(d->y2_scale_stride, d->Cout);
-  static const bool vec_on = !env_off("TMDIFF_EPILOGUE_VEC");
-  a.vec4 = vec_on && a.W % 4 == 0 && aligned16(d->y) && aligned16(d->y2) && aligned16(d->residual) && (long)a.N * a.H * a.W <= (1L << 23);
+  set_outputs(a, d);
+  a.bias_scale = d->bias_scale * 2.0f * ll_scale;   // the (scaled) LL band of a constant
+  const long plane = (long)a.N * a.H * a.W;
+  a.vec4 = epilogue_vec_ok(d, a.W, plane);
   hipStream_t st = as_stream(stream);
   const LlPlan plan = plan_ll(d);
-  a.ksplit = 1; a.split_chunks = a.Cin / 2; a.part = nullptr;
-  const size_t need = (size_t)plan.ksplit * d->B * d->Cout * a.N * a.H * a.W * sizeof(float);
-  if (plan.ksplit > 1 && d->splitk_ws && (size_t)d->splitk_ws_bytes >= need && aligned16(d->splitk_ws)) {
-    a.ksplit = plan.ksplit; a.split_chunks = a.Cin / 2 / plan.ksplit; a.part = static_cast<float*>(d->splitk_ws);
-  }
+  a.ksplit = 1; a.split_chunks = a.Cin / 2;
+  a.part = lend_splitk(d, plan.ksplit, plane);
+  if (a.part) { a.ksplit = plan.ksplit; a.split_chunks = a.Cin / 2 / plan.ksplit; }
   const int rc = plan.small ? launch<1, 2, 2, 2, 8, 8>(a, st) : launch<2, 2, 2, 4, 8, 8>(a, st);
   if (rc || !a.part) return rc;
-  SplitKReduceArgs r{a.part, a.ksplit, d->B, d->Cout, (long)a.N * a.H * a.W, d->bias, a.bias_scale, d->residual,
-                     d->out_scale, d->y, d->y2, d->y2_shift, d->y2_scale, a.y2_shift_stride, a.y2_scale_stride, d->y2_act};
-  return launch_splitk_reduce(r, st);
+  return finish_splitk(a, d, plane, a.bias_scale, st);
 }

@@ -750,8 +750,7 @@ extern "C" int64_t tmdiff_conv3d_wf_blocks(const tmdiff_conv3d_desc* d) {
 /* bytes of partial outputs a small grid splits its input channels into (lend them through d->splitk_ws; 0: no split) */
 extern "C" size_t tmdiff_conv3d_wf_splitk_workspace_bytes(const tmdiff_conv3d_desc* d) {
   if (!wf_shape_ok(d) || d->B <= 0) return 0;
-  const int ks = wf_ksplit(d);
-  return ks > 1 ? (size_t)ks * d->B * d->Cout * d->N * d->H * d->W * sizeof(float) : 0;
+  return splitk_bytes(wf_ksplit(d), d, (long)d->N * d->H * d->W);
 }
 
 /* bytes of the prologue output x' the entry point forms first when the input is not one plain tensor (0: plain input) */
@@ -771,13 +770,9 @@ int wf_forward(const tmdiff_conv3d_desc* d, void* workspace, tmdiff_stream_t str
   TMDIFF_REQUIRE(d->B >= 0, "conv3d_wf_fwd: bad extents");
   if (d->B == 0) return TMDIFF_OK;
   TMDIFF_REQUIRE(d->w_packed && (d->y || d->y2 || d->y_ll) && aligned16(d->w_packed), "conv3d_wf_fwd: NULL / unaligned weights or output");
-  TMDIFF_REQUIRE((long)d->N * d->H * d->W <= (1L << 24), "conv3d_wf_fwd: plane too large for 32-bit offsets (32 channels of a sample per descriptor)");
-  int csum = 0;
-  for (int i = 0; i < d->nseg; ++i) {
-    TMDIFF_REQUIRE(d->seg_x[i] != nullptr && d->seg_c[i] > 0 && aligned16(d->seg_x[i]), "conv3d_wf_fwd: segment %d is empty / unaligned", i);
-    csum += d->seg_c[i];
-  }
-  TMDIFF_REQUIRE(csum == d->Cin, "conv3d_wf_fwd: segments hold %d channels, Cin=%d", csum, d->Cin);
+  const long plane = (long)d->N * d->H * d->W;
+  TMDIFF_REQUIRE(plane <= (1L << 24), "conv3d_wf_fwd: plane too large for 32-bit offsets (32 channels of a sample per descriptor)");
+  if (const int rc = check_segments(d, "conv3d_wf_fwd", true)) return rc;
   if (!(aligned16(d->y) && aligned16(d->y2) && aligned16(d->residual)))
     return fail(TMDIFF_E_UNSUPPORTED, "conv3d_wf_fwd: 16-byte aligned outputs / residual");
   hipStream_t st = as_stream(stream);
@@ -794,25 +789,21 @@ int wf_forward(const tmdiff_conv3d_desc* d, void* workspace, tmdiff_stream_t str
   a.B = d->B; a.N = d->N; a.H = d->H; a.W = d->W;
   a.Cin = d->Cin; a.Cout = d->Cout; a.groups = d->groups; a.cin_g = d->Cin / d->groups; a.cout_g = d->Cout / d->groups;
   a.x = x; a.wp = d->w_packed;
-  a.bias = d->bias; a.bias_scale = d->bias_scale * bias_mul;
-  a.residual = d->residual; a.out_scale = d->out_scale; a.y = d->y;
-  a.y2 = d->y2; a.y2_shift = d->y2_shift; a.y2_scale = d->y2_scale; a.y2_act = d->y2_act;
+  set_outputs(a, d);
+  a.bias_scale *= bias_mul;
   a.y2_s2d = d->y2 && d->y2_s2d ? 1 : 0;
   if (a.y2_s2d) TMDIFF_REQUIRE(d->H % 2 == 0 && d->W % 4 == 0, "conv3d_wf_fwd: the space-to-depth second output needs even H and W %% 4 == 0");
-  a.y2_shift_stride = bank_stride(d->y2_shift_stride, d->Cout);
-  a.y2_scale_stride = bank_stride(d->y2_scale_stride, d->Cout);
   a.vec4 = 1;
   a.stamps = TMDIFF_WF_STAMPS ? static_cast<unsigned long long*>(d->splitk_ws) : nullptr;
   a.ksplit = 1; a.split_chunks = a.cin_g / 2; a.part = nullptr;
   if (!TMDIFF_WF_STAMPS) {
     const int ks = wf_ksplit(d, llm);
-    const size_t need = (size_t)ks * d->B * d->Cout * d->N * d->H * d->W * sizeof(float);
-    if (ks > 1 && d->splitk_ws && (size_t)d->splitk_ws_bytes >= need && aligned16(d->splitk_ws)) {
+    if (float* part = lend_splitk(d, ks, plane)) {
       // (only a launch that really splits is refused: without a lent workspace the grid runs unsplit and its own epilogue
       //  writes the second output -- ADVICE r3: TMDIFF_WF_SPLITK=0 used to raise here for shapes the host had routed)
       if (a.y2_s2d)
         return fail(TMDIFF_E_UNSUPPORTED, "conv3d_wf_fwd: a grid that splits its input channels cannot write the space-to-depth second output");
-      a.ksplit = ks; a.split_chunks = a.cin_g / 2 / ks; a.part = static_cast<float*>(d->splitk_ws);
+      a.ksplit = ks; a.split_chunks = a.cin_g / 2 / ks; a.part = part;
     }
   }
   a.yll = nullptr; a.yhi[0] = a.yhi[1] = a.yhi[2] = nullptr;
@@ -841,9 +832,7 @@ int wf_forward(const tmdiff_conv3d_desc* d, void* workspace, tmdiff_stream_t str
   if (llm) rc = wf_pair(d) ? launch<2, 8, 16, true, true>(a, st) : (d->N == 8 ? launch<2, 8, 16, false, true>(a, st) : launch<1, 16, 16, false, true>(a, st));
   else rc = wf_pair(d) ? launch<2, 8, 16, true>(a, st) : (d->N == 8 ? launch<2, 8, 16>(a, st) : launch<1, 16, 16>(a, st));
   if (rc || !a.part) return rc;
-  SplitKReduceArgs r{a.part, a.ksplit, d->B, d->Cout, (long)d->N * d->H * d->W, d->bias, d->bias_scale, d->residual,
-                     d->out_scale, d->y, d->y2, d->y2_shift, d->y2_scale, a.y2_shift_stride, a.y2_scale_stride, d->y2_act};
-  return launch_splitk_reduce(r, st);
+  return finish_splitk(a, d, plane, d->bias_scale, st);
 }
 
 // the descriptor of the composed-LL convolution as the kernel sees it: the space-to-depth input has 4 x the channels at half
@@ -930,8 +919,7 @@ extern "C" int tmdiff_conv3d_wfll_pack_weights(const float* w, float* packed, in
 extern "C" size_t tmdiff_conv3d_wfll_splitk_workspace_bytes(const tmdiff_conv3d_desc* d) {
   tmdiff_conv3d_desc e;
   if (!wfll_desc(d, &e) || d->B <= 0) return 0;
-  const int ks = wf_ksplit(&e, true);
-  return ks > 1 ? (size_t)ks * e.B * e.Cout * e.N * e.H * e.W * sizeof(float) : 0;
+  return splitk_bytes(wf_ksplit(&e, true), &e, (long)e.N * e.H * e.W);
 }
 
 extern "C" int tmdiff_conv3d_wfll_fwd(const tmdiff_conv3d_desc* d, float ll_scale, tmdiff_stream_t stream) {

@@ -611,24 +611,17 @@ extern "C" int tmdiff_conv3d_wino_fwd_planes(const tmdiff_conv3d_desc* d, void* 
   TMDIFF_REQUIRE(d->w_packed && (d->y || d->y2) && aligned16(d->w_packed), "conv3d_wino_fwd: NULL / unaligned weights or output");
   TMDIFF_REQUIRE((long)d->Cin * (d->N / mo) * np * (d->H + 2) * (d->W + 4) < (1L << 31) / 2, "conv3d_wino_fwd: input too large for 32-bit offsets");
   TMDIFF_REQUIRE((long)d->B * d->Cin <= 65535, "conv3d_wino_fwd: B*Cin = %ld exceeds the grid", (long)d->B * d->Cin);
-  int csum = 0;
-  for (int i = 0; i < d->nseg; ++i) {
-    TMDIFF_REQUIRE(d->seg_x[i] != nullptr && d->seg_c[i] > 0 && aligned16(d->seg_x[i]), "conv3d_wino_fwd: segment %d is empty / unaligned", i);
-    csum += d->seg_c[i];
-  }
-  TMDIFF_REQUIRE(csum == d->Cin, "conv3d_wino_fwd: segments hold %d channels, Cin=%d", csum, d->Cin);
+  if (const int rc = check_segments(d, "conv3d_wino_fwd", true)) return rc;
   hipStream_t st = as_stream(stream);
 
   WinoInArgs q;
   q.B = d->B; q.Cin = d->Cin; q.N = d->N; q.H = d->H; q.W = d->W; q.nseg = d->nseg;
-  for (int i = 0; i < 3; ++i) { q.seg_c[i] = i < d->nseg ? d->seg_c[i] : 0; q.seg_x[i] = i < d->nseg ? d->seg_x[i] : nullptr; }
-  q.in_shift = d->in_shift; q.in_scale = d->in_scale; q.in_act = d->in_act;
-  q.shift_stride = bank_stride(d->in_shift_stride, d->Cin);
-  q.scale_stride = bank_stride(d->in_scale_stride, d->Cin);
+  set_segments(q, d, 0, nullptr);
+  set_input_prologue(q, d);
+  q.in_act = d->in_act;
   q.v = static_cast<float*>(workspace);
   q.xp = xp_out;
-  q.drop_seed = d->drop_seed; q.drop_seed_dev = d->drop_seed_dev; q.drop_thresh = drop_threshold(d->drop_p);
-  q.drop_inv = d->drop_p > 0.f ? 1.0f / (1.0f - d->drop_p) : 0.f;
+  set_dropout(q, d);
   TMDIFF_REQUIRE(!xp_out || aligned16(xp_out), "conv3d_wino_fwd: xp_out must be 16-byte aligned");
   TMDIFF_REQUIRE(stage >= 0 && stage <= 2, "conv3d_wino_fwd: stage=%d", stage);
   if (stage != 2) {
@@ -645,14 +638,10 @@ extern "C" int tmdiff_conv3d_wino_fwd_planes(const tmdiff_conv3d_desc* d, void* 
   a.B = d->B; a.N = d->N; a.H = d->H; a.W = d->W;
   a.Cin = d->Cin; a.Cout = d->Cout; a.groups = d->groups; a.cin_g = d->Cin / d->groups; a.cout_g = d->Cout / d->groups;
   a.v = q.v; a.wp = d->w_packed;
-  a.bias = d->bias; a.bias_scale = d->bias_scale;
-  a.residual = d->residual; a.out_scale = d->out_scale; a.y = d->y;
-  a.y2 = d->y2; a.y2_shift = d->y2_shift; a.y2_scale = d->y2_scale; a.y2_act = d->y2_act;
-  a.y2_shift_stride = bank_stride(d->y2_shift_stride, d->Cout);
-  a.y2_scale_stride = bank_stride(d->y2_scale_stride, d->Cout);
-  a.vec4 = 1;
+  set_outputs(a, d);
+  a.vec4 = 1;   // (its only epilogue: the dwordx4 one, whatever TMDIFF_EPILOGUE_VEC says)
   a.stamps = TMDIFF_WINO_STAMPS ? static_cast<unsigned long long*>(d->splitk_ws) : nullptr;
-  if (!(d->W % 4 == 0 && aligned16(d->y) && aligned16(d->y2) && aligned16(d->residual) && (long)d->N * d->H * d->W <= (1L << 23)))
+  if (!epilogue_vec_shape(d, d->W, (long)d->N * d->H * d->W))
     return fail(TMDIFF_E_UNSUPPORTED, "conv3d_wino_fwd: W %% 4 == 0, 16-byte aligned outputs / residual, planes of at most 2^23 positions");
   if (np == 6) {
     if (a.cout_g % 64 == 0) return launch<2, 2, 2, 2, 8, 8, 6>(a, st);

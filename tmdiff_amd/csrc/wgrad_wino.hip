@@ -501,13 +501,8 @@ extern "C" int tmdiff_conv3d_wgrad_wino_bias(const tmdiff_conv3d_desc* d, const 
   const WwPlan p = ww_plan(d);
   if (!ww_fits(d, p)) return fail(TMDIFF_E_UNSUPPORTED, "conv3d_wgrad_wino: tensor too large for 32-bit offsets");
   TMDIFF_REQUIRE(aligned16(g) && aligned16(workspace), "conv3d_wgrad_wino: 16-byte aligned gradient / workspace");
-  TMDIFF_REQUIRE(!(d->in_mask && d->drop_p > 0.f), "conv3d_wgrad_wino: give either a mask tensor or drop_p, not both");
-  int csum = 0;
-  for (int i = 0; i < d->nseg; ++i) {
-    TMDIFF_REQUIRE(d->seg_x[i] && d->seg_c[i] > 0 && aligned16(d->seg_x[i]), "conv3d_wgrad_wino: segment %d is empty / unaligned", i);
-    csum += d->seg_c[i];
-  }
-  TMDIFF_REQUIRE(csum == d->Cin, "conv3d_wgrad_wino: segments hold %d channels, Cin=%d", csum, d->Cin);
+  if (const int rc = check_mask_or_dropout(d, "conv3d_wgrad_wino")) return rc;
+  if (const int rc = check_segments(d, "conv3d_wgrad_wino", true)) return rc;
   hipStream_t st = as_stream(stream);
   float* xh = static_cast<float*>(workspace);
   float* gh = xh + p.xh_floats;
