@@ -484,6 +484,7 @@ ENTRIES = {
     "conv3d_fwd_xp_supported": lambda p: L.tmdiff_conv3d_fwd_xp_supported(p),
     "conv3d_fwd_staged": lambda p: L.tmdiff_conv3d_fwd_staged(p, A, None),
     "conv3d_fwd_bf16": lambda p: L.tmdiff_conv3d_fwd_bf16(p, None, None),
+    "conv3d_fwd_bf16_ws": lambda p: L.tmdiff_conv3d_fwd_bf16(p, A, None),
     "conv3d_ll_fwd": lambda p: L.tmdiff_conv3d_ll_fwd(p, 0.5, None),
     "conv3d_wf_fwd": lambda p: L.tmdiff_conv3d_wf_fwd(p, A, None),
     "conv3d_wfll_fwd": lambda p: L.tmdiff_conv3d_wfll_fwd(p, 0.5, None),
@@ -633,3 +634,184 @@ def test_splitk_workspace_queries():
     assert L.tmdiff_conv3d_ll_splitk_workspace_bytes(desc(**dict(small, H=16, W=16))) == 32 * out
     assert L.tmdiff_conv3d_wf_splitk_workspace_bytes(desc(**dict(small, W=16))) == 32 * 2 * out
     assert L.tmdiff_conv3d_wfll_splitk_workspace_bytes(desc(**dict(small, Cin=64, seg_c=[64], H=16, W=16))) == 32 * out
+
+
+# ---- the 32-bit size limits of the convolution families ------------------------------------------------------------------
+# Each case is a descriptor just inside (True) or just past (False) one limit an entry point enforces for its 32-bit offsets
+# or its grid.  The support queries must answer 0 exactly where the entry point refuses; a refusal is TMDIFF_E_UNSUPPORTED with
+# the entry's message prefix, an accepted descriptor gets past validation and fails on the missing device only.
+_RC = dict(rc_x="A", rc_w="A", rc_cin=64)
+_SIZE_CASES = [
+    # (label, entry, prefix, fields over _BASE_DESC, accepted, support queries)
+    ("wf plane 4x2048x2048", "conv3d_wf_fwd", "conv3d_wf_fwd", dict(B=2, N=4, H=2048, W=2048, Cin=4, seg_c=[4]), True, "wf"),
+    ("wf plane 4x2048x2052", "conv3d_wf_fwd", "conv3d_wf_fwd", dict(B=2, N=4, H=2048, W=2052, Cin=4, seg_c=[4]), False, "wf"),
+    ("wf plane 8x1024x2048", "conv3d_wf_fwd", "conv3d_wf_fwd", dict(N=8, H=1024, W=2048, Cin=4, seg_c=[4]), True, "wf"),
+    ("wf plane 8x1024x2052", "conv3d_wf_fwd", "conv3d_wf_fwd", dict(N=8, H=1024, W=2052, Cin=4, seg_c=[4]), False, "wf"),
+    ("wf pair (Cin+2) plane < 2^29", "conv3d_wf_fwd", "conv3d_wf_fwd", dict(N=8, H=131071, W=8, Cin=62, seg_c=[62]), True, "wf"),
+    ("wf pair (Cin+2) plane = 2^29", "conv3d_wf_fwd", "conv3d_wf_fwd", dict(N=8, H=131072, W=8, Cin=62, seg_c=[62]), False, "wf"),
+    ("wf rc_cin plane < 2^30", "conv3d_wf_fwd", "conv3d_wf_fwd", dict(N=4, H=2048, W=2044, **_RC), True, "wf_opt"),
+    ("wf rc_cin plane = 2^30", "conv3d_wf_fwd", "conv3d_wf_fwd", dict(N=4, H=2048, W=2048, **_RC), False, "wf_opt"),
+    ("wf prologue B*Cin 65472", "conv3d_wf_fwd", "conv3d_wf_fwd", dict(B=1023, in_act=1), True, "wf_opt"),
+    ("wf prologue B*Cin 65536", "conv3d_wf_fwd", "conv3d_wf_fwd", dict(B=1024, in_act=1), False, "wf_opt"),
+    ("wfll plane 4x2048x2048 (s2d)", "conv3d_wfll_fwd", "conv3d_wf_fwd", dict(N=4, H=4096, W=4096, Cin=1, seg_c=[1]), True, "wfll"),
+    ("wfll plane 4x2052x2048 (s2d)", "conv3d_wfll_fwd", "conv3d_wfll_fwd", dict(N=4, H=4096, W=4104, Cin=1, seg_c=[1]), False, "wfll"),
+    ("bf16 plane 2^31 - 8", "conv3d_fwd_bf16", "conv3d_fwd_bf16", dict(N=8, H=16384, W=16383), True, "bf16"),
+    ("bf16 plane 2^31", "conv3d_fwd_bf16", "conv3d_fwd_bf16", dict(N=8, H=16384, W=16384), False, "bf16"),
+    ("bf16 pack B*Cin/8 65535", "conv3d_fwd_bf16_ws", "conv3d_fwd_bf16", dict(B=65535, Cin=8, seg_c=[8]), True, "bf16_ws"),
+    ("bf16 pack B*Cin/8 65536", "conv3d_fwd_bf16_ws", "conv3d_fwd_bf16", dict(B=65536, Cin=8, seg_c=[8]), False, "bf16_ws"),
+    ("fused plane 2^31 - 8", "conv3d_fwd", "conv3d_fwd", dict(N=8, H=16384, W=16383, Cin=1, Cout=1, seg_c=[1]), True, "fused"),
+    ("fused plane 2^31", "conv3d_fwd", "conv3d_fwd", dict(N=8, H=16384, W=16384, Cin=1, Cout=1, seg_c=[1]), False, "fused"),
+    ("staged plane 8 < 2^31", "conv3d_fwd_staged", "conv3d_fwd_staged", dict(N=8, H=4096, W=8191, Cin=4, Cout=32, seg_c=[4]), True, "staged"),
+    ("staged plane 8 = 2^31", "conv3d_fwd_staged", "conv3d_fwd_staged", dict(N=8, H=4096, W=8192, Cin=4, Cout=32, seg_c=[4]), False, "staged"),
+    ("staged prologue B*Cin 65472", "conv3d_fwd_staged", "conv3d_fwd_staged", dict(B=1023, in_act=1), True, "staged"),
+    ("staged prologue B*Cin 65536", "conv3d_fwd_staged", "conv3d_fwd_staged", dict(B=1024, in_act=1), False, "staged"),
+    ("staged plain B*Cin 65536", "conv3d_fwd_staged", "conv3d_fwd_staged", dict(B=1024), True, "staged"),
+    ("ll Cin plane < 2^30", "conv3d_ll_fwd", "conv3d_ll_fwd", dict(N=8, H=1024, W=2046), True, "ll"),
+    ("ll Cin plane = 2^30", "conv3d_ll_fwd", "conv3d_ll_fwd", dict(N=8, H=1024, W=2048), False, "ll"),
+    ("wino plane 2x2048x2048", "conv3d_wino_fwd", "conv3d_wino_fwd", dict(N=2, H=2048, W=2048, Cin=2, seg_c=[2]), True, "wino"),
+    ("wino plane 2x2048x2052", "conv3d_wino_fwd", "conv3d_wino_fwd", dict(N=2, H=2048, W=2052, Cin=2, seg_c=[2]), False, "wino"),
+    ("wino input < 2^30", "conv3d_wino_fwd", "conv3d_wino_fwd", dict(N=2, H=1022, W=4088), True, "wino"),
+    ("wino input = 2^30", "conv3d_wino_fwd", "conv3d_wino_fwd", dict(N=2, H=1022, W=4092), False, "wino"),
+    ("wino B*Cin 65472", "conv3d_wino_fwd", "conv3d_wino_fwd", dict(B=1023), True, "wino"),
+    ("wino B*Cin 65536", "conv3d_wino_fwd", "conv3d_wino_fwd", dict(B=1024), False, "wino"),
+    ("k1 x' Cin plane < 2^30", "conv3d_fwd", "conv3d_fwd", dict(ksize=1, B=1, N=4, H=2048, W=2047, xp_out="A"), True, "xp"),
+    ("k1 x' Cin plane = 2^30", "conv3d_fwd", "conv3d_fwd", dict(ksize=1, B=1, N=4, H=2048, W=2048, xp_out="A"), False, "xp"),
+    # (past plane * 16 < 2^31 the bandwidth kernel leaves a 1x1x1 convolution to the general kernel; x' is bounded sooner)
+    ("k1 plane 16 = 2^31", "conv3d_fwd", "conv3d_fwd", dict(ksize=1, B=1, N=8, H=4096, W=4096, Cin=16, seg_c=[16]), True, None),
+    ("wgrad plane 32 < 2^31", "conv3d_wgrad", "conv3d_wgrad", dict(B=1, N=4, H=4096, W=4095, Cin=4, Cout=32, seg_c=[4]), True, None),
+    ("wgrad plane 32 = 2^31", "conv3d_wgrad", "conv3d_wgrad", dict(B=1, N=4, H=4096, W=4096, Cin=4, Cout=32, seg_c=[4]), False, None),
+    ("wgrad_wino 2 B T 65534", "conv3d_wgrad_wino", "conv3d_wgrad_wino", dict(B=8191, N=16, H=8, W=8), True, "ww"),
+    ("wgrad_wino 2 B T 65536", "conv3d_wgrad_wino", "conv3d_wgrad_wino", dict(B=8192, N=16, H=8, W=8), False, "ww"),
+]
+_SIZE_QUERIES = {        # family -> the queries that answer 0 exactly where its entry point refuses
+    "wf": ("tmdiff_conv3d_wf_supported", "tmdiff_conv3d_wf_blocks", "tmdiff_conv3d_wf_plan"),
+    "wf_opt": ("tmdiff_conv3d_wf_supported", "tmdiff_conv3d_wf_blocks"),      # (limits of an optional input: not the plan's)
+    "wfll": ("tmdiff_conv3d_wfll_supported",),
+    "bf16_ws": ("tmdiff_conv3d_bf16_workspace_bytes",),
+    "staged": ("tmdiff_conv3d_fwd_staged_supported",),
+    "ll": ("tmdiff_conv3d_ll_supported",),
+    "wino": ("tmdiff_conv3d_wino_supported", "tmdiff_conv3d_wino_blocks", "tmdiff_conv3d_wino_workspace_bytes"),
+    "xp": ("tmdiff_conv3d_fwd_xp_supported",),
+    "ww": ("tmdiff_conv3d_wgrad_wino_supported",),
+}
+_SIZE_CHILD = r"""
+import ctypes as C, json, sys
+sys.path.insert(0, sys.argv[1])
+from tmdiff_amd import _lib
+L = _lib.lib
+PTR = {"A": 0x10000}
+out = []
+for fields, queries in json.loads(sys.argv[2]):
+    d = _lib.Conv3dDesc()
+    d.bias_scale = d.out_scale = 1.0
+    for k, v in fields.items():
+        if isinstance(v, list):
+            for i, x in enumerate(v):
+                getattr(d, k)[i] = PTR.get(x, x)
+        else:
+            setattr(d, k, PTR.get(v, v))
+    r = {}
+    for q in queries:
+        if q == "tmdiff_conv3d_wf_plan":
+            r[q] = L.tmdiff_conv3d_wf_plan(d.B, d.Cin, d.Cout, d.N, d.H, d.W, d.groups, 0, None)
+        else:
+            r[q] = int(getattr(L, q)(C.byref(d)))
+    out.append(r)
+print(json.dumps(out))
+"""
+
+
+def _size_desc(fields):
+    return dict(_BASE_DESC, **fields)
+
+
+def test_size_limits_agree_among_entry_points_support_queries_and_routing():
+    """Every 32-bit size limit of the convolution families, one descriptor just inside and one just past it: the entry point
+    accepts the one (and then fails on the missing device only) and refuses the other with TMDIFF_E_UNSUPPORTED and its own
+    message prefix; the support queries, the wf launch plan and the workspace queries answer 0 exactly where the entry point
+    refuses; the routing layer never names a family that refuses a shape, and past a limit it falls through to one that
+    takes it."""
+    import json, subprocess, sys
+    from tmdiff_amd import routing
+    got = _run_validation_child([[entry, _size_desc(f)] for _, entry, _, f, _, _ in _SIZE_CASES])
+    bad = []
+    for (label, entry, prefix, f, ok, _), (rc, msg) in zip(_SIZE_CASES, got):
+        if ok and rc in (0, -1, -2):
+            bad.append(f"{label}: accepted descriptor stopped at validation: {rc} '{msg}'")
+        if not ok and (rc != -2 or not msg.startswith(prefix + ":")):
+            bad.append(f"{label}: want -2 '{prefix}: ...', got {rc} '{msg}'")
+    env = {k: v for k, v in os.environ.items() if k not in ("ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")}
+    env["HIP_VISIBLE_DEVICES"] = "-1"
+    calls = [[_size_desc(f), _SIZE_QUERIES[q]] for _, _, _, f, _, q in _SIZE_CASES if q in _SIZE_QUERIES]
+    p = subprocess.run([sys.executable, "-c", _SIZE_CHILD, ROOT, json.dumps(calls)], capture_output=True, text=True, env=env,
+                       timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    answers = iter(json.loads(p.stdout.strip().splitlines()[-1]))
+    for label, _, _, f, ok, q in _SIZE_CASES:
+        if q in _SIZE_QUERIES:
+            for name, v in next(answers).items():
+                if (v != 0) != ok:
+                    bad.append(f"{label}: {name} answers {v}, the entry point {'accepts' if ok else 'refuses'}")
+    assert not bad, "\n".join(bad)
+
+    # routing: the family named for each case's extents takes them
+    def d(label):
+        return _size_desc(next(f for l_, _, _, f, _, _ in _SIZE_CASES if l_ == label))
+
+    for label, want in (("wf plane 4x2048x2048", "wf"), ("wf plane 8x1024x2048", "wf")):
+        e = d(label)
+        assert routing.conv3_family(e["B"], e["Cin"], e["Cout"], e["N"], e["H"], e["W"]) == want, label
+    for label in ("wf plane 4x2048x2052", "wf plane 8x1024x2052"):
+        e = d(label)
+        assert routing.wf_route(e["B"], e["Cin"], e["Cout"], e["N"], e["H"], e["W"]) == (False, 1), label
+        assert routing.conv3_family(e["B"], e["Cin"], e["Cout"], e["N"], e["H"], e["W"]) == "staged", label
+    # the issue's shapes: plane 2^25 at 32 -> 32 channels falls through to the staged kernel, which takes it
+    assert routing.wf_route(1, 32, 32, 8, 2048, 2048) == (False, 1)
+    assert routing.conv3_family(1, 32, 32, 8, 2048, 2048) == "staged"
+    e = d("wf pair (Cin+2) plane = 2^29")
+    assert not routing.wf_route(e["B"], 62, 64, 8, e["H"], 8)[0] and routing.wf_route(e["B"], 62, 64, 8, e["H"] - 1, 8)[0]
+    # a prologue pass of B * Cin > 65535 rows: conv3d_wf takes the plain input, not the one with a prologue
+    assert routing.conv3_family(1024, 64, 64, 8, 16, 16, plain=True) == "wf"
+    assert routing.conv3_family(1024, 64, 64, 8, 16, 16, plain=False) == "fused"
+    assert routing.conv3_family(1023, 64, 64, 8, 16, 16, plain=False) == "wf"
+    # staged: past its plane limit or prologue grid, the direct route is the fused kernel
+    assert routing.direct_family(4, 32, extents=(1, 8, 4096, 8191)) == "staged"
+    assert routing.direct_family(4, 32, extents=(1, 8, 4096, 8192)) == "fused"
+    assert routing.direct_family(64, 64, plain=False, keep_xp=True, extents=(1023, 8, 16, 16)) == "staged"
+    assert routing.direct_family(64, 64, plain=False, keep_xp=True, extents=(1024, 8, 16, 16)) == "fused"
+    assert routing.direct_family(64, 64, plain=True, extents=(1024, 8, 16, 16)) == "staged"
+    # composed Conv_0 + LL: the direct composed kernel up to its limit, then convolution + DWT; conv3d_wf's composed mode
+    assert routing.ll_family(2, 64, 64, 8, 1024, 2046, producer_s2d=False) == "ll" and routing.ll_fits(2, 64, 64, 8, 1024, 2046)
+    assert routing.ll_family(2, 64, 64, 8, 1024, 2048, producer_s2d=False) is None
+    assert routing.wfll_route(2, 1, 64, 4, 4096, 4096) and not routing.wfll_route(2, 1, 64, 4, 4096, 4104)
+    # the transform-pass Winograd kernel: planes 0 past any of its limits
+    for label, ok in (("wino plane 2x2048x2048", True), ("wino plane 2x2048x2052", False), ("wino input < 2^30", True),
+                      ("wino input = 2^30", False), ("wino B*Cin 65472", True), ("wino B*Cin 65536", False)):
+        e = d(label)
+        assert bool(routing.wino_plan(e["B"], e["Cout"], e["N"], e["H"], e["W"], cin=e["Cin"])[0]) == ok, label
+    assert routing.conv3_family(1024, 64, 64, 12, 64, 64) not in ("wino4", "wino2")      # B * Cin > 65535
+    assert routing.conv3_family(1023, 64, 64, 12, 64, 64) == "wino4"
+    # the side x' of the 1x1x1 bandwidth kernel: its two limits
+    assert routing.k1_side_xp(1, (64,), 64, 4, 2048, 2044) and not routing.k1_side_xp(1, (64,), 64, 4, 2048, 2048)
+    assert not routing.k1_side_xp(1, (16,), 64, 8, 4096, 4096)
+    # a folded res_conv: the limit of its rc_x offsets
+    assert routing.wf_fold_fits(2, 64, 64, 4, 2048, 2044, 64) and not routing.wf_fold_fits(2, 64, 64, 4, 2048, 2048, 64)
+    assert routing.wf_fold_fits(2, 64, 64, 4, 2048, 2048, 32)
+
+
+def test_network_routes_respect_size_limits():
+    """WavBEST's own decisions at a plane past the composed-LL and folded-res_conv limits: no LL composition (Conv_0 runs and
+    the DWT keeps the LL band) and no res_conv folded into conv3d_wf, while the same network folds / composes at a plane
+    inside the limits."""
+    from tmdiff_amd.Hyper_unet_general import WavBEST
+    net = WavBEST(channels=[64, 128, 128, 128])
+    P = {"bf16": set(), "w_wino": {"down1.conv20.conv21": object(), "down1.Conv_1": object()}, "w_wfll": {}}
+
+    class X:         # a stand-in with the extents of a tensor (nothing is allocated)
+        def __init__(self, *shape):
+            self.shape = shape
+
+    assert net._fold_res_conv(P, "down1.conv20", [X(1, 64, 4, 2048, 2044)]) is not None
+    assert net._fold_res_conv(P, "down1.conv20", [X(1, 64, 4, 2048, 2048)]) is None          # 64 x 2^24 = 2^30
+    assert net.down1.down.Conv_0.in_channels == 128           # 128 x 2^23 = 2^30
+    assert net._ll_fits("down1.down", X(1, 128, 8, 1024, 1022)) and not net._ll_fits("down1.down", X(1, 128, 8, 1024, 1024))

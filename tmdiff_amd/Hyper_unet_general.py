@@ -178,9 +178,11 @@ class WaveletUPorDown(nn.Module):
     def run(self, x, shift, scale, skipH=None, want_high=True):
         from . import autograd as A
         # down, high bands dropped: Conv_0 + halved LL band as one strided convolution (autograd._ConvLL)
+        from . import routing
         ll = (self.down and not want_high and ops.config.ll_compose and
               ops.ll_conv_supported(self.Conv_0.out_channels, self.Conv_0.in_channels, 3, 1) and
-              x.shape[3] % 2 == 0 and x.shape[4] % 2 == 0)
+              x.shape[3] % 2 == 0 and x.shape[4] % 2 == 0 and
+              routing.ll_fits(x.shape[0], self.Conv_0.in_channels, self.Conv_0.out_channels, *x.shape[2:]))
         hh = None if ll else A.conv3d([x], self.Conv_0.weight, self.Conv_0.bias, act=True)
         # down: Conv_2 commutes with the halved LL band (see WavBEST._down), so it runs after it, on a quarter of the positions
         xx = None if self.down and ops.config.conv2_after_ll else A.conv3d([x], self.Conv_2.weight, self.Conv_2.bias)
@@ -540,6 +542,8 @@ class WavBEST(nn.Module):
         from . import routing
         if routing.conv3_family(b, m3.in_channels, m3.out_channels, n, h, w, 1, plain=False) != "wf":
             return None
+        if not routing.wf_fold_fits(b, m3.in_channels, m3.out_channels, n, h, w, cx):
+            return None
         return x, self.get_submodule(name + k1).weight.detach(), cx
 
     def _ll_s2d(self, P, blk, h):
@@ -557,6 +561,12 @@ class WavBEST(nn.Module):
         return bool(takes and split == 1 and m21.out_channels == c0.in_channels and
                     ops.wfll_route(b, c0.in_channels, c0.out_channels, n, hh, ww))
 
+    def _ll_fits(self, name, x):
+        """True when conv3d_ll takes the down block `name`'s Conv_0 + LL on x (its size limit)."""
+        from . import routing
+        c0 = self.get_submodule(name + ".Conv_0")
+        return routing.ll_fits(x.shape[0], c0.in_channels, c0.out_channels, *x.shape[2:])
+
     def _conv0(self, P, name, x, pre):
         """Conv_0 of a wavelet block on SiLU(x): from the producer's second output when there is one."""
         if pre is None:
@@ -568,6 +578,8 @@ class WavBEST(nn.Module):
         caller drops the high bands.  Returns (out, out2, bands).  pre_s2d: `pre` is in space-to-depth form (_ll_s2d).
         xq: LL(x) / 2 as the producer already wrote it (_resblock(want_ll=True)); x itself may then be None."""
         w_ll = None if want_high or pre is None or pre.dtype != torch.float32 else P["w_wfll" if pre_s2d else "w_ll"].get(name + ".Conv_0")
+        if w_ll is not None and not pre_s2d and not self._ll_fits(name, pre):
+            w_ll = None
         assert not pre_s2d or w_ll is not None
         conv_ll = ops.conv3d_wf_ll if pre_s2d else ops.conv3d_ll
         # high bands kept (condition branch): where Conv_0 runs on conv3d_wf unsplit, its epilogue writes the Haar transform of its

@@ -768,8 +768,8 @@ extern "C" int tmdiff_conv3d_wgrad_bias(const tmdiff_conv3d_desc* d, const float
   TMDIFF_REQUIRE(workspace != nullptr, "conv3d_wgrad: NULL workspace");
   if (const int rc = check_mask_or_dropout(d, what)) return rc;
   const WgradPlan p = plan_wgrad(d);
-  TMDIFF_REQUIRE(p.total_boxes < (1L << 31) && (long)d->N * d->H * d->W * 32 < (1L << 31),
-                 "conv3d_wgrad: tensor too large for 32-bit box / offset arithmetic");
+  if (!(p.total_boxes < (1L << 31) && (long)d->N * d->H * d->W * 32 < (1L << 31)))
+    return fail(TMDIFF_E_UNSUPPORTED, "conv3d_wgrad: tensor too large for 32-bit box / offset arithmetic");
   hipStream_t st = as_stream(stream);
   WgradArgs a;
   a.B = d->B; a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout;

@@ -720,7 +720,7 @@ extern "C" int tmdiff_conv3d_fwd(const tmdiff_conv3d_desc* d, tmdiff_stream_t st
   TMDIFF_REQUIRE(d->w_packed && (d->y || d->y2), "conv3d_fwd: NULL weights/output");
   TMDIFF_REQUIRE(!d->y2 || !d->y2_bf16, "conv3d_fwd: a bf16-packed second output needs tmdiff_conv3d_fwd_bf16");
   const long plane = (long)d->N * d->H * d->W;
-  TMDIFF_REQUIRE(plane < (1L << 31), "conv3d_fwd: plane too large for 32-bit offsets");
+  if (plane >= (1L << 31)) return fail(TMDIFF_E_UNSUPPORTED, "conv3d_fwd: plane too large for 32-bit offsets");
 
   if (d->ksize == 1) {  // bandwidth kernel for the shapes it takes (every production 1x1x1 layer)
     const int rc = conv1_fp32_try(d, as_stream(stream));

@@ -914,7 +914,7 @@ int launch_dma(BfArgs& a, uint4* xp, hipStream_t st, bool do_pack = true) {
 }  // namespace
 
 extern "C" size_t tmdiff_conv3d_bf16_workspace_bytes(const tmdiff_conv3d_desc* d) {
-  if (!d || d->B <= 0 || d->Cin <= 0 || d->Cin % 8) return 0;
+  if (!d || d->B <= 0 || d->Cin <= 0 || d->Cin % 8 || d->B * (long)(d->Cin / 8) > 65535) return 0;   // (the pack pass's grid)
   return (size_t)d->B * d->Cin * d->N * d->H * d->W * 2;
 }
 
@@ -965,7 +965,7 @@ extern "C" int tmdiff_conv3d_fwd_bf16(const tmdiff_conv3d_desc* d, void* workspa
                    "conv3d_fwd_bf16: a bf16-packed input is one 16-byte aligned tensor without prologue, 3x3x3 only");
   }
   TMDIFF_REQUIRE(aligned16(d->w_packed), "conv3d_fwd_bf16: packed weights must be 16-byte aligned");
-  TMDIFF_REQUIRE((long)d->N * d->H * d->W < (1L << 31), "conv3d_fwd_bf16: plane too large for 32-bit offsets");
+  if ((long)d->N * d->H * d->W >= (1L << 31)) return fail(TMDIFF_E_UNSUPPORTED, "conv3d_fwd_bf16: plane too large for 32-bit offsets");
 
   BfArgs a;
   a.B = d->B; a.N = d->N; a.H = d->H; a.W = d->W;
@@ -992,7 +992,9 @@ extern "C" int tmdiff_conv3d_fwd_bf16(const tmdiff_conv3d_desc* d, void* workspa
   }
   if (workspace) {  // two-kernel variant: pack the prologue output once, then the staging-free kernel
     TMDIFF_REQUIRE(aligned16(workspace), "conv3d_fwd_bf16: workspace must be 16-byte aligned");
-    TMDIFF_REQUIRE(d->B * (long)(d->Cin / 8) <= 65535, "conv3d_fwd_bf16: B*Cin/8 = %ld exceeds the pack grid", d->B * (long)(d->Cin / 8));
+    if (d->B * (long)(d->Cin / 8) > 65535)
+      return fail(TMDIFF_E_UNSUPPORTED, "conv3d_fwd_bf16: B*Cin/8 = %ld exceeds the pack grid (tmdiff_conv3d_bf16_workspace_bytes is 0: "
+                                        "no workspace, one kernel)", d->B * (long)(d->Cin / 8));
     uint4* xp = static_cast<uint4*>(workspace);
     if (cout_g % 64 == 0) return launch_dma<2, 2, 8, 8>(a, xp, st);
     return d->W >= 16 ? launch_dma<4, 1, 8, 16>(a, xp, st) : launch_dma<2, 1, 8, 8>(a, xp, st);

@@ -300,12 +300,16 @@ bool needs_apply(const tmdiff_conv3d_desc* d) {
   return d->nseg > 1 || d->in_shift || d->in_scale || d->in_mask || d->in_act || d->drop_p > 0.f;
 }
 
-// shapes the staged kernel takes (every production layer); others stay on the fused kernel
-bool staged_ok(const tmdiff_conv3d_desc* d) {
+// shapes the staged kernel takes (every production layer); others stay on the fused kernel.  Its 32-bit offsets cover eight
+// channels of a plane (plane * 8 < 2^31); an input that needs the prologue pass adds that pass's grid of B * Cin rows.
+bool staged_form_ok(const tmdiff_conv3d_desc* d) {
   if (!d || d->ksize != 3 || (d->groups != 1 && d->groups != 3)) return false;  // 1x1x1 has its own kernel (conv1.hip)
   if (d->Cin <= 0 || d->Cout <= 0 || d->Cin % d->groups || d->Cout % d->groups) return false;
-  const int cin_g = d->Cin / d->groups, cout_g = d->Cout / d->groups;
-  return cin_g % 4 == 0 && cout_g % 32 == 0;
+  return (d->Cin / d->groups) % 4 == 0 && (d->Cout / d->groups) % 32 == 0;
+}
+
+bool staged_ok(const tmdiff_conv3d_desc* d) {
+  return staged_form_ok(d) && (long)d->N * d->H * d->W * 8 < (1L << 31) && (!needs_apply(d) || (long)d->B * d->Cin <= 65535);
 }
 
 }  // namespace
@@ -321,7 +325,13 @@ extern "C" int tmdiff_conv3d_fwd_staged(const tmdiff_conv3d_desc* d, void* works
   using namespace tmdiff;
   const char* what = "conv3d_fwd_staged";
   TMDIFF_REQUIRE(d != nullptr, "conv3d_fwd_staged: NULL descriptor");
-  if (!staged_ok(d)) return fail(TMDIFF_E_UNSUPPORTED, "conv3d_fwd_staged: shape not supported (use tmdiff_conv3d_fwd)");
+  if (!staged_ok(d)) {
+    if (staged_form_ok(d))
+      return fail(TMDIFF_E_UNSUPPORTED, (long)d->N * d->H * d->W * 8 >= (1L << 31)
+                                            ? "conv3d_fwd_staged: plane too large (plane * 8 < 2^31)"
+                                            : "conv3d_fwd_staged: B*Cin = %ld exceeds the prologue pass's grid", (long)d->B * d->Cin);
+    return fail(TMDIFF_E_UNSUPPORTED, "conv3d_fwd_staged: shape not supported (use tmdiff_conv3d_fwd)");
+  }
   if (const int rc = check_head(d, what)) return rc;
   if (d->B == 0) return TMDIFF_OK;
   if (const int rc = check_segments(d, what)) return rc;
@@ -329,7 +339,6 @@ extern "C" int tmdiff_conv3d_fwd_staged(const tmdiff_conv3d_desc* d, void* works
   TMDIFF_REQUIRE(!d->y2 || !d->y2_bf16, "conv3d_fwd_staged: a bf16-packed second output needs tmdiff_conv3d_fwd_bf16");
   if (const int rc = check_dropout(d, what)) return rc;
   const long plane = (long)d->N * d->H * d->W;
-  TMDIFF_REQUIRE(plane * 8 < (1L << 31), "conv3d_fwd_staged: plane too large");
   hipStream_t st = as_stream(stream);
 
   DmaArgs a;

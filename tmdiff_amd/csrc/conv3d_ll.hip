@@ -306,7 +306,9 @@ __global__ void __launch_bounds__(256) ll_pack_weights_kernel(const float* __res
 bool ll_ok(const tmdiff_conv3d_desc* d) {
   if (!d || d->ksize != 3 || d->groups != 1 || d->nseg != 1) return false;
   if (d->in_shift || d->in_scale || d->in_mask || d->in_act || d->drop_p > 0.f || d->x_bf16 || d->y2_bf16) return false;
-  return d->Cin > 0 && d->Cin % 2 == 0 && d->Cout > 0 && d->Cout % 64 == 0 && d->H > 0 && d->W > 0 && d->H % 2 == 0 && d->W % 2 == 0;
+  if (!(d->Cin > 0 && d->Cin % 2 == 0 && d->Cout > 0 && d->Cout % 64 == 0 && d->H > 0 && d->W > 0 && d->H % 2 == 0 && d->W % 2 == 0))
+    return false;
+  return (long)d->Cin * d->N * d->H * d->W < (1L << 30);    // a sample's input: 32-bit byte offsets
 }
 
 // tile choice and split-K factor (as plan_conv3 for the stride-1 kernels): 256-position tiles, 128-position ones (two
@@ -359,12 +361,13 @@ extern "C" int tmdiff_conv3d_ll_fwd(const tmdiff_conv3d_desc* d, float ll_scale,
   using namespace tmdiff;
   TMDIFF_REQUIRE(d != nullptr, "conv3d_ll_fwd: NULL descriptor");
   if (!ll_ok(d))
-    return fail(TMDIFF_E_UNSUPPORTED, "conv3d_ll_fwd: one plain fp32 input, 3x3x3, groups 1, even H and W, Cin %% 2 == 0, Cout %% 64 == 0");
+    return fail(TMDIFF_E_UNSUPPORTED, d->N > 0 && d->Cin > 0 && (long)d->Cin * d->N * d->H * d->W >= (1L << 30)
+                                          ? "conv3d_ll_fwd: input too large for 32-bit offsets (Cin * plane < 2^30)"
+                                          : "conv3d_ll_fwd: one plain fp32 input, 3x3x3, groups 1, even H and W, Cin %% 2 == 0, Cout %% 64 == 0");
   TMDIFF_REQUIRE(d->B >= 0 && d->N > 0, "conv3d_ll_fwd: bad extents");
   if (d->B == 0) return TMDIFF_OK;
   TMDIFF_REQUIRE(d->seg_x[0] && d->seg_c[0] == d->Cin, "conv3d_ll_fwd: the segment must hold all %d input channels", d->Cin);
   TMDIFF_REQUIRE(d->w_packed && (d->y || d->y2) && aligned16(d->w_packed), "conv3d_ll_fwd: NULL / unaligned weights or output");
-  TMDIFF_REQUIRE((long)d->Cin * d->N * d->H * d->W < (1L << 31) / 2, "conv3d_ll_fwd: input too large for 32-bit offsets");
   LlArgs a;
   a.B = d->B; a.N = d->N; a.Hi = d->H; a.Wi = d->W; a.H = d->H / 2; a.W = d->W / 2;
   a.Cin = d->Cin; a.Cout = d->Cout; a.cout_g = d->Cout;

@@ -668,7 +668,7 @@ int launch(WfArgs& a, hipStream_t st) {
   return tmdiff::check_launch("conv3d_wf_fwd");
 }
 
-bool wf_shape_ok(const tmdiff_conv3d_desc* d) {
+bool wf_form_ok(const tmdiff_conv3d_desc* d) {
   if (!d || d->ksize != 3 || (d->groups != 1 && d->groups != 3) || d->in_mask || d->x_bf16 || d->y2_bf16) return false;
   if (!(d->drop_p >= 0.f && d->drop_p < 1.f)) return false;
   if (d->nseg < 1 || d->nseg > 3 || d->Cin <= 0 || d->Cout <= 0 || d->Cin % d->groups || d->Cout % d->groups) return false;
@@ -684,6 +684,23 @@ bool wf_grouped_segs(const tmdiff_conv3d_desc* d) {
 
 // 8 bands x 8 columns (the 8x8 level): two images share a tile, see GeoF
 bool wf_pair(const tmdiff_conv3d_desc* d) { return d->N == 8 && d->W == 8; }
+
+bool wf_plain(const tmdiff_conv3d_desc* d) {
+  return (d->nseg == 1 || wf_grouped_segs(d)) && !d->in_shift && !d->in_scale && !d->in_act && !(d->drop_p > 0.f);
+}
+
+// the 32-bit offset limits of the kernel's extents: 32 channels of a sample per descriptor (pair mode: the Cin + 2 channel
+// planes of a sample); an input that is not one plain tensor goes through the prologue pass, whose grid holds B * Cin rows
+bool wf_fits(const tmdiff_conv3d_desc* d) {
+  const long plane = (long)d->N * d->H * d->W;
+  return plane <= (1L << 24) && (!wf_pair(d) || ((long)d->Cin + 2) * plane < (1L << 29)) &&
+         (wf_plain(d) || (long)d->B * d->Cin <= 65535);
+}
+
+// a folded residual convolution: its rc_cin input channels of a sample addressed by 32-bit byte offsets
+bool wf_rc_fits(const tmdiff_conv3d_desc* d) { return !d->rc_x || (long)d->rc_cin * d->N * d->H * d->W < (1L << 30); }
+
+bool wf_shape_ok(const tmdiff_conv3d_desc* d) { return wf_form_ok(d) && wf_fits(d) && wf_rc_fits(d); }
 
 long wf_tiles(const tmdiff_conv3d_desc* d) {
   const int th = d->N == 8 ? 8 : 16;
@@ -717,10 +734,6 @@ int wf_ksplit(const tmdiff_conv3d_desc* d, bool pairs = false) {
   static const long long_range = env_long("TMDIFF_SPLITK_LONG", 1700);
   if (tiles * best < 384 && ok(2 * best) && (long)(nchunks / (2 * best)) * ksteps >= long_range) best *= 2;
   return best;
-}
-
-bool wf_plain(const tmdiff_conv3d_desc* d) {
-  return (d->nseg == 1 || wf_grouped_segs(d)) && !d->in_shift && !d->in_scale && !d->in_act && !(d->drop_p > 0.f);
 }
 
 }  // namespace
@@ -765,13 +778,15 @@ namespace {
 int wf_forward(const tmdiff_conv3d_desc* d, void* workspace, tmdiff_stream_t stream, bool llm, float bias_mul) {
   using namespace tmdiff;
   TMDIFF_REQUIRE(d != nullptr, "conv3d_wf_fwd: NULL descriptor");
-  if (!wf_shape_ok(d))
+  if (!wf_form_ok(d))
     return fail(TMDIFF_E_UNSUPPORTED, "conv3d_wf_fwd: fp32 3x3x3, groups 1 or 3, N = 8 or 4, W %% 4 == 0, Cin/g %% 2 == 0, Cout/g %% 32 == 0, no mask");
+  if (!wf_fits(d))
+    return fail(TMDIFF_E_UNSUPPORTED, "conv3d_wf_fwd: plane too large for 32-bit offsets (32 channels of a sample per descriptor; pair "
+                                      "mode: (Cin + 2) x plane < 2^29; a prologue pass: B * Cin <= 65535)");
   TMDIFF_REQUIRE(d->B >= 0, "conv3d_wf_fwd: bad extents");
   if (d->B == 0) return TMDIFF_OK;
   TMDIFF_REQUIRE(d->w_packed && (d->y || d->y2 || d->y_ll) && aligned16(d->w_packed), "conv3d_wf_fwd: NULL / unaligned weights or output");
   const long plane = (long)d->N * d->H * d->W;
-  TMDIFF_REQUIRE(plane <= (1L << 24), "conv3d_wf_fwd: plane too large for 32-bit offsets (32 channels of a sample per descriptor)");
   if (const int rc = check_segments(d, "conv3d_wf_fwd", true)) return rc;
   if (!(aligned16(d->y) && aligned16(d->y2) && aligned16(d->residual)))
     return fail(TMDIFF_E_UNSUPPORTED, "conv3d_wf_fwd: 16-byte aligned outputs / residual");
@@ -823,11 +838,9 @@ int wf_forward(const tmdiff_conv3d_desc* d, void* workspace, tmdiff_stream_t str
         !aligned16(d->rc_x) || !aligned16(d->rc_w))
       return fail(TMDIFF_E_UNSUPPORTED, "conv3d_wf_fwd: a folded residual convolution needs groups 1, rc_cin %% 32 == 0 (at most 512), no residual "
                                         "tensor and planes wider than 8 columns");
-    TMDIFF_REQUIRE((long)d->rc_cin * d->N * d->H * d->W < (1L << 30), "conv3d_wf_fwd: rc_x sample too large for 32-bit byte offsets");
+    if (!wf_rc_fits(d)) return fail(TMDIFF_E_UNSUPPORTED, "conv3d_wf_fwd: rc_x sample too large for 32-bit byte offsets");
     a.rc_x = d->rc_x; a.rc_w = d->rc_w; a.rc_cin = d->rc_cin;
   }
-  if (wf_pair(d))
-    TMDIFF_REQUIRE(((long)d->Cin + 2) * d->N * d->H * d->W < (1L << 29), "conv3d_wf_fwd: sample too large for 32-bit offsets");
   int rc;
   if (llm) rc = wf_pair(d) ? launch<2, 8, 16, true, true>(a, st) : (d->N == 8 ? launch<2, 8, 16, false, true>(a, st) : launch<1, 16, 16, false, true>(a, st));
   else rc = wf_pair(d) ? launch<2, 8, 16, true>(a, st) : (d->N == 8 ? launch<2, 8, 16>(a, st) : launch<1, 16, 16>(a, st));

@@ -528,6 +528,18 @@ bool wino_ok(const tmdiff_conv3d_desc* d) {
          d->W % 4 == 0;
 }
 
+int planes_for(int N);
+
+// the 32-bit limits of the extents (transform planes_for(N)): the transformed input of a sample in 32-bit byte offsets, the
+// transform pass's grid of B * Cin rows, and the dwordx4 epilogue's planes of at most 2^23 positions
+bool wino_fits(const tmdiff_conv3d_desc* d, int np) {
+  const int mo = np - 2;
+  return (long)d->Cin * (d->N / mo) * np * (d->H + 2) * (d->W + 4) < (1L << 30) && (long)d->B * d->Cin <= 65535 &&
+         (long)d->N * d->H * d->W <= (1L << 23);
+}
+
+bool wino_shape_ok(const tmdiff_conv3d_desc* d) { return wino_ok(d) && wino_fits(d, planes_for(d->N)); }
+
 // F(4,3) when the band count is a multiple of four and its tiles fill the kernel's pairs of tiles at least as well as F(2,3)'s
 // would (a workgroup covers TT = 2 tiles along the bands: with N = 4 the second F(4,3) tile would be empty -- 2 x 13.5
 // multiply-adds per output against F(2,3)'s 18), else F(2,3); TMDIFF_WINO_F4=0 (experiments): always F(2,3)
@@ -541,7 +553,7 @@ int planes_for(int N) {
 
 }  // namespace
 
-extern "C" int tmdiff_conv3d_wino_supported(const tmdiff_conv3d_desc* d) { return wino_ok(d) ? 1 : 0; }
+extern "C" int tmdiff_conv3d_wino_supported(const tmdiff_conv3d_desc* d) { return wino_shape_ok(d) ? 1 : 0; }
 
 /* planes of the transform this library uses for N bands (6: F(4,3), 4: F(2,3)): the `planes` argument of the weight packing */
 extern "C" int32_t tmdiff_conv3d_wino_planes(int32_t N) { return N > 0 && N % 2 == 0 ? planes_for(N) : 0; }
@@ -549,14 +561,14 @@ extern "C" int32_t tmdiff_conv3d_wino_planes(int32_t N) { return N > 0 && N % 2 
 // workgroups the convolution kernel would launch (0 = shape not supported): callers keep small grids on tmdiff_conv3d_fwd,
 // whose split-K fills the chip
 extern "C" int64_t tmdiff_conv3d_wino_blocks(const tmdiff_conv3d_desc* d) {
-  if (!wino_ok(d) || d->B <= 0) return 0;
+  if (!wino_shape_ok(d) || d->B <= 0) return 0;
   const int T = d->N / (planes_for(d->N) - 2), cg = d->Cout / d->groups;
   if (cg % 64 == 0) return (int64_t)d->B * d->groups * ((T + 1) / 2) * ((d->H + 7) / 8) * ((d->W + 7) / 8) * (cg / 64);
   return (int64_t)d->B * d->groups * ((T + 1) / 2) * ((d->H + 7) / 8) * ((d->W + 15) / 16) * (cg / 32);
 }
 
 extern "C" size_t tmdiff_conv3d_wino_workspace_bytes(const tmdiff_conv3d_desc* d) {
-  if (!wino_ok(d) || d->B <= 0) return 0;
+  if (!wino_shape_ok(d) || d->B <= 0) return 0;
   return (size_t)d->B * d->Cin * (d->N / 2) * 4 * (d->H + 2) * (d->W + 4) * sizeof(float);   // (F(2,3): the larger of the two)
 }
 
@@ -609,8 +621,9 @@ extern "C" int tmdiff_conv3d_wino_fwd_planes(const tmdiff_conv3d_desc* d, void* 
   TMDIFF_REQUIRE((np == 6 && d->N % 4 == 0) || np == 4, "conv3d_wino_fwd: planes=%d with N=%d", planes, d->N);
   TMDIFF_REQUIRE(workspace && aligned16(workspace), "conv3d_wino_fwd: needs its workspace (tmdiff_conv3d_wino_workspace_bytes)");
   TMDIFF_REQUIRE(d->w_packed && (d->y || d->y2) && aligned16(d->w_packed), "conv3d_wino_fwd: NULL / unaligned weights or output");
-  TMDIFF_REQUIRE((long)d->Cin * (d->N / mo) * np * (d->H + 2) * (d->W + 4) < (1L << 31) / 2, "conv3d_wino_fwd: input too large for 32-bit offsets");
-  TMDIFF_REQUIRE((long)d->B * d->Cin <= 65535, "conv3d_wino_fwd: B*Cin = %ld exceeds the grid", (long)d->B * d->Cin);
+  if (!wino_fits(d, np))
+    return fail(TMDIFF_E_UNSUPPORTED, "conv3d_wino_fwd: input too large for 32-bit offsets (Cin x transformed plane < 2^30, "
+                                      "B*Cin = %ld at most 65535, planes of at most 2^23 positions)", (long)d->B * d->Cin);
   if (const int rc = check_segments(d, "conv3d_wino_fwd", true)) return rc;
   hipStream_t st = as_stream(stream);
 

@@ -601,8 +601,8 @@ def conv3d(segs, w_packed, cout, ksize, out=None, math="fp32", pack_input=None, 
             raise TypeError("conv3d(math='bf16') needs weights from pack_conv_weight_bf16")
         if pack_input is None:
             pack_input = {"0": False, "1": True}.get(config.bf16_pack, True)   # measured: the two-kernel variant wins on every production layer
-        ws = (_workspace(dev, lib.tmdiff_conv3d_bf16_workspace_bytes(C.byref(d))).data_ptr()
-              if pack_input and ksize == 3 and x_bf16_shape is None else None)
+        nb = lib.tmdiff_conv3d_bf16_workspace_bytes(C.byref(d))      # (0: the pack pass's grid cannot hold B * Cin / 8 rows)
+        ws = _workspace(dev, nb).data_ptr() if pack_input and ksize == 3 and x_bf16_shape is None and nb else None
         fn, args, what = lib.tmdiff_conv3d_fwd_bf16, (ws,), "conv3d_fwd_bf16"
     elif math == "fp32":
         if not isinstance(w_packed, int) and w_packed.dtype != torch.float32:
@@ -611,9 +611,11 @@ def conv3d(segs, w_packed, cout, ksize, out=None, math="fp32", pack_input=None, 
             _lend_splitk(d, dev, lib.tmdiff_conv3d_fwd_splitk_workspace_bytes(C.byref(d)))
         if staged is None:       # (the rule and its measurements: routing.direct_family)
             staged = ksize == 3 and routing.direct_family(d.Cin, cout, d.groups, _plain(segs, kw), kw.get("in_mask") is not None,
-                                                          kw.get("drop") is not None) == "staged"
+                                                          kw.get("drop") is not None, extents=(b, n, h, w)) == "staged"
         if xp_out is not None:
             staged = True
+            if not lib.tmdiff_conv3d_fwd_staged_supported(C.byref(d)):
+                raise ValueError("conv3d: xp_out needs the staged kernel, which does not take this shape")
         if staged and lib.tmdiff_conv3d_fwd_staged_supported(C.byref(d)):
             nb = lib.tmdiff_conv3d_fwd_staged_workspace_bytes(C.byref(d))
             fn, args, what = lib.tmdiff_conv3d_fwd_staged, (_xp_target("conv3d", xp_out, nb, dev),), "conv3d_fwd_staged"
@@ -688,7 +690,7 @@ def conv3d_auto(segs, weights, cout, groups=1, math="fp32", emit=None, keep_y=Tr
         raise ValueError("conv3d_auto: only conv3d_wf writes a space-to-depth second output / folds a residual convolution "
                          "(ask routing.wf_route first)")
     if fam not in ("staged", "fused"):      # (a direct family named by conv3_family is direct_family's answer already)
-        fam = routing.direct_family(cin, cout, groups, plain, masked, dropout, xp_out is not None)
+        fam = routing.direct_family(cin, cout, groups, plain, masked, dropout, xp_out is not None, extents=(b, n, h, w))
     return conv3d(segs, weights.direct(), cout, 3, groups=groups, staged=fam == "staged", emit=emit, keep_y=keep_y,
                   xp_out=xp_out, **kw)
 

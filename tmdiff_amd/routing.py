@@ -34,6 +34,7 @@ different fp32 summation orders; tests/test_gpu_configs.py bounds the difference
 import collections
 import ctypes as C
 
+from . import _lib
 from ._lib import lib
 
 PRODUCT_FAMILIES = ("wf", "wf_pair", "wfll", "ll", "staged", "fused", "bf16")
@@ -86,6 +87,29 @@ def _wf_route(cfg, b, cin, cout, n, h, w, groups, masked, llm):
     return bool(tiles.value * split >= cfg.wino_min_blocks and fill >= cfg.wf_min_fill), split
 
 
+_QUERIES = {}        # (the support queries below are pure functions of the extents and the fields set: one call per shape)
+
+
+def supported(query, b, cin, cout, n, h, w, groups=1, **fields):
+    """The library's support query `query` (e.g. "tmdiff_conv3d_ll_supported") for a 3x3x3 convolution of these extents on one
+    input tensor, with the descriptor fields `fields` set (in_act=1: an input that needs a prologue; rc_x=1, rc_cin=: a folded
+    residual convolution; pointers are placeholders, never dereferenced).  Where the size limits of the 32-bit offsets live.
+    The answers are cached per process: the library reads the switches they depend on (TMDIFF_WINO_F4 and the like) once
+    per process too."""
+    key = (query, b, cin, cout, n, h, w, groups, tuple(sorted(fields.items())))
+    r = _QUERIES.get(key)
+    if r is None:
+        if len(_QUERIES) > 4096:
+            _QUERIES.clear()
+        d = _lib.Conv3dDesc()
+        d.B, d.N, d.H, d.W, d.Cin, d.Cout, d.groups, d.ksize, d.nseg = b, n, h, w, cin, cout, groups, 3, 1
+        d.seg_c[0] = cin
+        for k, v in fields.items():
+            setattr(d, k, v)
+        r = _QUERIES[key] = bool(getattr(lib, query)(C.byref(d)))
+    return r
+
+
 def wfll_route(b, cin, cout, n, h, w):
     """True when conv3d_wf's composed-LL mode takes Conv_0 + LL of a [b, cin, n, h, w] input (h, w: full resolution)."""
     if not (_config().wfll and n in (4, 8) and h % 2 == 0 and w % 8 == 0 and cout % 32 == 0):
@@ -93,10 +117,13 @@ def wfll_route(b, cin, cout, n, h, w):
     return wf_route(b, 4 * cin, cout, n, h // 2, w // 2, llm=True)[0]
 
 
-def wino_plan(b, cout, n, h, w, groups=1):
-    """(planes, workgroups) of the transform-pass Winograd kernel for these extents; planes 0 = not taken."""
+def wino_plan(b, cout, n, h, w, groups=1, cin=None):
+    """(planes, workgroups) of the transform-pass Winograd kernel for these extents; planes 0 = not taken.  cin: also check the
+    kernel's size limits (tmdiff_conv3d_wino_supported)."""
     planes = lib.tmdiff_conv3d_wino_planes(int(n))
     if not planes or w % 4:
+        return 0, 0
+    if cin is not None and not supported("tmdiff_conv3d_wino_supported", b, cin, cout, n, h, w, groups):
         return 0, 0
     cg = cout // groups
     per_tile = b * groups * ((h + 7) // 8) * (((w + 7) // 8) * (cg // 64) if cg % 64 == 0 else ((w + 15) // 16) * (cg // 32))
@@ -115,22 +142,30 @@ def conv3_family(b, cin, cout, n, h, w, groups=1, plain=True, masked=False, drop
     if math == "bf16":
         return "bf16"
     if cfg.winograd and not masked and wino_weight_ok(cout, cin, 3, groups):
-        if wf_route(b, cin, cout, n, h, w, groups, masked)[0]:
+        # (an input that is not plain goes through conv3d_wf's prologue pass, which has size limits of its own; conservative
+        #  for a grouped convolution's three plain segments, which conv3d_wf reads in place: declined at B * Cin > 65535)
+        if wf_route(b, cin, cout, n, h, w, groups, masked)[0] and (
+                plain or supported("tmdiff_conv3d_wf_supported", b, cin, cout, n, h, w, groups, in_act=1)):
             return "wf_pair" if (n == 8 and w == 8) else "wf"
-        planes, _ = wino_plan(b, cout, n, h, w, groups)
+        planes, _ = wino_plan(b, cout, n, h, w, groups, cin=cin)
         if planes:
             return "wino4" if planes == 6 else "wino2"
-    return direct_family(cin, cout, groups, plain, masked, dropout, keep_xp)
+    return direct_family(cin, cout, groups, plain, masked, dropout, keep_xp, extents=(b, n, h, w))
 
 
-def direct_family(cin, cout, groups=1, plain=True, masked=False, dropout=False, keep_xp=False):
+def direct_family(cin, cout, groups=1, plain=True, masked=False, dropout=False, keep_xp=False, extents=None):
     """"staged" or "fused" for a 3x3x3 convolution on the direct kernels.  Measured (tools/bench_conv.py, B = 32): the staged
     kernel itself is 3-6 % faster than the fused one, but its prologue pass costs 8 B per input element -- a net win when the
     input needs no pass (one plain tensor: every data-gradient convolution), is shared by >= 2 channel tiles (Cout/g >= 128),
     is wide (Cin/g >= 384), or carries a dropout mask (the fused kernel reads the mask inside its MFMA stream); a kept x'
-    (finetune) forces it.  Both give the same bits (tests/test_gpu_kernels.py::test_conv3d_staged_equals_fused)."""
+    (finetune) forces it.  Both give the same bits (tests/test_gpu_kernels.py::test_conv3d_staged_equals_fused).
+    extents = (b, n, h, w): also check the staged kernel's size limits (tmdiff_conv3d_fwd_staged_supported)."""
     cin_g, cout_g = cin // groups, cout // groups
     staged_ok = groups in (1, 3) and cin % groups == 0 and cout % groups == 0 and cin_g % 4 == 0 and cout_g % 32 == 0
+    if staged_ok and extents is not None:
+        b, n, h, w = extents
+        staged_ok = supported("tmdiff_conv3d_fwd_staged_supported", b, cin, cout, n, h, w, groups,
+                              in_act=0 if plain and not masked and not dropout else 1)
     want = {"0": False, "1": True}.get(_config().fp32_staged, plain or cout_g >= 128 or cin_g >= 384 or masked or dropout)
     return "staged" if staged_ok and (want or keep_xp) else "fused"
 
@@ -159,7 +194,18 @@ def ll_family(b, cin, cout, n, h, w, producer_s2d=True):
         return None
     if cfg.winograd and producer_s2d and wfll_route(b, cin, cout, n, h, w):
         return "wfll"
-    return "ll"
+    return "ll" if ll_fits(b, cin, cout, n, h, w) else None
+
+
+def ll_fits(b, cin, cout, n, h, w):
+    """True when conv3d_ll takes Conv_0 + LL of a [b, cin, n, h, w] input (h, w: full resolution), its size limit included."""
+    return supported("tmdiff_conv3d_ll_supported", b, cin, cout, n, h, w)
+
+
+def wf_fold_fits(b, cin, cout, n, h, w, rc_cin):
+    """True when conv3d_wf can fold a residual 1x1x1 convolution of rc_cin input channels into its epilogue at these extents
+    (the size limit of its rc_x offsets; the other conditions: Hyper_unet_general.WavBEST._fold_res_conv)."""
+    return supported("tmdiff_conv3d_wf_supported", b, cin, cout, n, h, w, rc_x=16, rc_cin=rc_cin)
 
 
 # ---- the network's 3x3x3 convolutions ------------------------------------------------------------------------------------
