@@ -493,6 +493,20 @@ int tmdiff_ddpm_step(const float* x, const float* eps, const float* noise, const
                      float sigma, int32_t clip, tmdiff_stream_t stream);
 int tmdiff_axpby(const float* const in[4], const float coef[4], int32_t n_in, float* out, int64_t n,
                  tmdiff_stream_t stream);
+/* ddpm_step_dev: the same step with its scalars in DEVICE memory, so that a recorded launch can be replayed from a HIP
+ * graph for every timestep: t = *step; row t of coef [T][5] = (c_recip, c_recipm1, coef1, coef2, sigma), built from the
+ * same fp32 values tmdiff_ddpm_step is passed (sigma = 0 at t = 0).  x may equal out (in-place update).  noise is not
+ * read where sigma is 0.  If frames != NULL and t % frame_every == 0, out + ms is also written to slot
+ * tmdiff_ddpm_frame_slot(t, T, frame_every) of frames (slots of n floats: p_sample_loop's frame stack, slot 0 being
+ * x_T + ms).  A t outside [0, T) writes nothing.
+ * sampler_tick: *step = set_to if set_to >= 0, else *step - 1; then time_in[b] = *step + 1 (fp32) for b < B.  One
+ * workgroup; stream-ordered after the step it follows. */
+int tmdiff_ddpm_step_dev(const float* x, const float* eps, const float* noise, const float* ms, float* out, float* frames,
+                         int64_t n, const int32_t* step, const float* coef, int32_t T, int32_t frame_every, int32_t clip,
+                         tmdiff_stream_t stream);
+int tmdiff_sampler_tick(int32_t* step, float* time_in, int32_t B, int32_t set_to, tmdiff_stream_t stream);
+/* slot index of step t in p_sample_loop's frame stack (host function; -1 for arguments out of range) */
+int tmdiff_ddpm_frame_slot(int32_t t, int32_t T, int32_t frame_every);
 /* Multi-tensor form, ONE launch for a whole parameter list: out_t = ca * a_t + cb * b_t for every entry (the EMA update of
  * utils/EmaUpdater.py:23-38: out = a = EMA weights, b = live weights).  `tensors_dev` is a DEVICE array of entries;
  * the launch has one workgroup per chunk of tmdiff_multi_axpby_chunk() elements: chunk k works on elements

@@ -107,6 +107,9 @@ SIGNATURES = {
     "tmdiff_gamma_embedding": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, vp]),
     "tmdiff_ddpm_step": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_int32, vp]),
+    "tmdiff_ddpm_step_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp]),
+    "tmdiff_sampler_tick": (C.c_int, [vp, vp, C.c_int32, C.c_int32, vp]),
+    "tmdiff_ddpm_frame_slot": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "tmdiff_axpby": (C.c_int, [vp * 4, C.c_float * 4, C.c_int32, vp, C.c_int64, vp]),
     "tmdiff_multi_axpby_chunk": (C.c_int32, []),
     "tmdiff_multi_axpby": (C.c_int, [vp, vp, vp, C.c_int32, C.c_float, C.c_float, vp]),

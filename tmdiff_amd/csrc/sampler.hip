@@ -28,11 +28,13 @@ __device__ __forceinline__ float ddpm_one(float x, float e, float nz, const Ddpm
   return __fadd_rn(mean, __fmul_rn(nz, k.sigma));                            // + noise * exp(0.5 logvar)
 }
 
+// One grid-stride pass of the DDPM update (shared by the host-scalar and the device-scalar kernels, so both round
+// identically).  No __restrict__ on x / out: the device-scalar kernel updates x in place (element i is read before it
+// is written, by the same lane).
 template <int V>
-__global__ void __launch_bounds__(256) ddpm_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
-                                                        const float* __restrict__ noise, const float* __restrict__ ms,
-                                                        float* __restrict__ out, float* __restrict__ img, long nvec,
-                                                        DdpmCoef k) {
+__device__ __forceinline__ void ddpm_step_body(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
+                                               const float* __restrict__ ms, float* out, float* __restrict__ img, long nvec,
+                                               const DdpmCoef& k) {
   for (long i = blockIdx.x * 256L + threadIdx.x; i < nvec; i += 256L * gridDim.x) {
     float xv[V], ev[V], nv[V], mv[V], ov[V];
     if constexpr (V == 4) {
@@ -55,6 +57,46 @@ __global__ void __launch_bounds__(256) ddpm_step_kernel(const float* __restrict_
       if (img) img[i] = ov[0] + mv[0];
     }
   }
+}
+
+template <int V>
+__global__ void __launch_bounds__(256) ddpm_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                                        const float* __restrict__ noise, const float* __restrict__ ms,
+                                                        float* __restrict__ out, float* __restrict__ img, long nvec,
+                                                        DdpmCoef k) {
+  ddpm_step_body<V>(x, eps, noise, ms, out, img, nvec, k);
+}
+
+// Slot of p_sample_loop's frame stack that step t fills: slot 0 is the initial x_T + MS, then one slot per kept step
+// (t % every == 0) in the order the loop visits them (t = T-1 down to 0).
+__host__ __device__ __forceinline__ int ddpm_frame_slot(int t, int T, int every) { return 1 + (T - 1) / every - t / every; }
+
+// The same step with its scalars read from device memory: t = *step (one word every lane reads: a uniform load), then
+// row t of the coefficient table.  Every branch below depends on t only, so it is the same for the whole grid.
+template <int V>
+__global__ void __launch_bounds__(256) ddpm_step_dev_kernel(const float* x, const float* __restrict__ eps,
+                                                            const float* __restrict__ noise, const float* __restrict__ ms,
+                                                            float* out, float* __restrict__ frames, long nvec, long n,
+                                                            const int32_t* __restrict__ step, const float* __restrict__ coef,
+                                                            int T, int frame_every, int clip) {
+  const int t = *step;
+  if (t < 0 || t >= T) return;
+  const float* c = coef + 5L * t;
+  const DdpmCoef k{c[0], c[1], c[2], c[3], c[4], clip};
+  float* img = frames && t % frame_every == 0 ? frames + (long)ddpm_frame_slot(t, T, frame_every) * n : nullptr;
+  ddpm_step_body<V>(x, eps, k.sigma != 0.f ? noise : nullptr, ms, out, img, nvec, k);
+}
+
+// Advance the sampler's step word and write the [B, 1] time input the next network evaluation reads (t + 1, exact in
+// fp32).  One workgroup; launched after the step kernel in stream order.
+__global__ void __launch_bounds__(256) sampler_tick_kernel(int32_t* step, float* time_in, int B, int set_to) {
+  __shared__ int t_new;
+  if (threadIdx.x == 0) {
+    t_new = set_to >= 0 ? set_to : *step - 1;
+    *step = t_new;
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < B; b += 256) time_in[b] = (float)(t_new + 1);
 }
 
 struct AxpbyArgs {
@@ -390,6 +432,36 @@ extern "C" int tmdiff_ddpm_step(const float* x, const float* eps, const float* n
     ddpm_step_kernel<1><<<grid_for(n), 256, 0, as_stream(stream)>>>(x, eps, noise, ms, out, img_out, n, k);
   }
   return check_launch("ddpm_step");
+}
+
+extern "C" int tmdiff_ddpm_frame_slot(int32_t t, int32_t T, int32_t frame_every) {
+  return T > 0 && frame_every > 0 && t >= 0 && t < T ? ddpm_frame_slot(t, T, frame_every) : -1;
+}
+
+extern "C" int tmdiff_ddpm_step_dev(const float* x, const float* eps, const float* noise, const float* ms, float* out,
+                                    float* frames, int64_t n, const int32_t* step, const float* coef, int32_t T,
+                                    int32_t frame_every, int32_t clip, tmdiff_stream_t stream) {
+  using namespace tmdiff;
+  TMDIFF_REQUIRE(x && eps && noise && out && step && coef, "ddpm_step_dev: NULL pointer");
+  TMDIFF_REQUIRE(n >= 0 && T > 0, "ddpm_step_dev: n=%ld T=%d", (long)n, T);
+  TMDIFF_REQUIRE(!frames || (ms && frame_every > 0), "ddpm_step_dev: frames need ms and frame_every > 0 (got %d)", frame_every);
+  if (n == 0) return TMDIFF_OK;
+  hipStream_t st = as_stream(stream);
+  if (all_aligned({x, eps, noise, ms, out, frames}, n, 0)) {
+    ddpm_step_dev_kernel<4><<<grid_for(n / 4), 256, 0, st>>>(x, eps, noise, ms, out, frames, n / 4, n, step, coef, T,
+                                                            frame_every, clip);
+  } else {
+    ddpm_step_dev_kernel<1><<<grid_for(n), 256, 0, st>>>(x, eps, noise, ms, out, frames, n, n, step, coef, T, frame_every,
+                                                        clip);
+  }
+  return check_launch("ddpm_step_dev");
+}
+
+extern "C" int tmdiff_sampler_tick(int32_t* step, float* time_in, int32_t B, int32_t set_to, tmdiff_stream_t stream) {
+  using namespace tmdiff;
+  TMDIFF_REQUIRE(step && (time_in || B == 0) && B >= 0, "sampler_tick: bad arguments");
+  sampler_tick_kernel<<<1, 256, 0, as_stream(stream)>>>(step, time_in, B, set_to);
+  return check_launch("sampler_tick");
 }
 
 extern "C" int tmdiff_axpby(const float* const in[4], const float coef[4], int32_t n_in, float* out, int64_t n,

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import ops
+from . import ops, sample_graph
 from .dpm_solver import DPM_Solver, NoiseScheduleVP, model_wrapper
 from .util import res2img  # noqa: F401  (re-exported like the reference module does)
 
@@ -43,6 +43,10 @@ def betas_for_alpha_bar(num_diffusion_timesteps, alpha_bar, max_beta=0.999):
 
 
 class GeneralDiffusion(nn.Module):
+    sample_graphs = None           # captured-graph sampling for this object: True / False, None = ops.config.sample_graph
+    sample_graph_capacity = 2      # captured samplers kept per object (least recently used dropped first)
+    sample_graph_captures = 0      # samplers captured so far by this object
+
     def __init__(self, denoise_fn, loss_type="l1", noise_fn=None):
         super().__init__()
         self.denoise_fn = denoise_fn
@@ -168,10 +172,16 @@ class GeneralDiffusion(nn.Module):
 
         return _Ctx()
 
+    def release_sample_graphs(self):
+        """Drop every captured sampler of this object (graphs, static buffers and what they keep alive)."""
+        self.__dict__.pop("_sample_graph_cache", None)
+
     @torch.no_grad()
     def p_sample_loop(self, x_in, continous=False, prompt="QB", guidance=1.0):
         sample_inter = 1 | (self.num_timesteps // 10)
         x_in = self._prep_inputs(x_in)
+        if sample_graph.usable(self, x_in):
+            return sample_graph.ddpm(self, x_in, prompt, continous)
         img = self._noise(x_in["Res"])
         frames = [ops.add(img, x_in["MS"])]
         with self._cached(x_in, prompt):
@@ -203,10 +213,16 @@ class GeneralDiffusion(nn.Module):
             out[k] = x_in[k].float().contiguous()
         return out
 
-    def _solve(self, x_in, prompt, model_type, model_kwargs, steps, order, method, denoise_to_zero=True, **wrap_kw):
-        x_T = self._noise(x_in["Res"])
-        ns = NoiseScheduleVP(schedule="discrete", betas=self.betas)
+    def _dpm_schedule(self):
+        return NoiseScheduleVP(schedule="discrete", betas=self.betas)
+
+    def _solve(self, x_in, prompt, model_type, model_kwargs, steps, order, method, denoise_to_zero=True, x_T=None, ns=None,
+               time_table=None, **wrap_kw):
+        """x_T / ns: given by the graph runner (drawn / built outside its capture); time_table: see _WrappedModel."""
+        x_T = self._noise(x_in["Res"]) if x_T is None else x_T
+        ns = self._dpm_schedule() if ns is None else ns
         model_fn = model_wrapper(self.denoise_fn, ns, model_type=model_type, model_kwargs=model_kwargs, **wrap_kw)
+        model_fn.time_table = time_table
         solver = DPM_Solver(model_fn, ns, algorithm_type="dpmsolver++", correcting_x0_fn="dynamic_thresholding")
         x = solver.sample(x_T, steps=steps, order=order, skip_type="logSNR", method=method,
                           denoise_to_zero=denoise_to_zero)
@@ -218,6 +234,8 @@ class GeneralDiffusion(nn.Module):
         """ref :227-255: x_start-parameterised DPM-Solver++, singlestep order 3, logSNR grid, dynamic
         thresholding, denoise-to-zero => steps + 1 network evaluations (reference hard-codes steps=30)."""
         x_in = self._prep_inputs(x_in)
+        if sample_graph.usable(self, x_in):
+            return sample_graph.dpmsolver(self, x_in, prompt, steps)
         with self._cached(x_in, prompt):
             return self._solve(x_in, prompt, "x_start", {"PAN": x_in["PAN"], "MS": x_in["MS"], "prompt": prompt},
                                steps, 3, "singlestep")

@@ -105,12 +105,25 @@ class _WrappedModel:
         self.model, self.ns, self.model_type, self.model_kwargs = model, ns, model_type, model_kwargs
         self.guidance_type, self.condition, self.unconditional_condition = guidance_type, condition, unconditional_condition
         self.guidance_scale, self.classifier_fn, self.classifier_kwargs = guidance_scale, classifier_fn, classifier_kwargs
+        # (host [NFE, B], device [NFE, B]) time inputs of a recorded solve, in call order (tmdiff_amd.sample_graph): the
+        # k-th evaluation reads row k of the device table instead of copying its time to the device
+        self.time_table, self._calls = None, 0
 
-    def model_time(self, t, batch, device):
-        """continuous t (host scalar) -> the [B] time tensor the network expects (:285-294)."""
+    def host_time(self, t, batch):
+        """continuous t (host scalar) -> the [B] time tensor the network expects (:285-294), on the host."""
         t = NoiseScheduleVP._cpu(t)
         t_in = (t - 1.0 / self.ns.total_N) * 1000.0 if self.ns.schedule == "discrete" else t
-        return t_in.expand(batch).to(device)
+        return t_in.expand(batch)
+
+    def model_time(self, t, batch, device):
+        t_in = self.host_time(t, batch)
+        if self.time_table is None:
+            return t_in.to(device)
+        host, dev = self.time_table
+        k, self._calls = self._calls, self._calls + 1
+        if k >= host.shape[0] or not torch.equal(host[k], t_in):
+            raise RuntimeError(f"time table: evaluation {k} at t = {t_in[0].item()} was not recorded by the warm-up run")
+        return dev[k]
 
     def raw(self, x, t, cond=None):
         t_in = self.model_time(t, x.shape[0], x.device)

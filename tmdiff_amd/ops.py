@@ -55,6 +55,9 @@ class KernelConfig:
     train_two_streams  TMDIFF_TRAIN_STREAMS     True     forward_train runs the condition branch on a second stream beside the
                                                          main branch's down path (at a local batch of 8 most launches fill half
                                                          of the CU slots); autograd then runs their backward passes side by side too
+    sample_graph       TMDIFF_SAMPLE_GRAPH      False    (GeneralDiffusion) p_sample_loop / super_resolution / sample /
+                                                         sample_by_dpmsolver capture their steps into HIP graphs and replay them
+                                                         (tmdiff_amd.sample_graph; per object: GeneralDiffusion.sample_graphs)
 
     Library-side experiment variables (read by libtmdiff_hip.so itself, C getenv): TMDIFF_SPLITK, TMDIFF_SPLITK_LONG,
     TMDIFF_WF_STAGGER, TMDIFF_WINO_STAGGER, TMDIFF_WINO_F4, TMDIFF_EPILOGUE_VEC, TMDIFF_SMALLGRID, TMDIFF_WW_PHASES,
@@ -78,6 +81,7 @@ class KernelConfig:
         "train_fused_resblock": ("TMDIFF_TRAIN_FUSED_RESBLOCK", _FLAG(True), True),
         "train_graph": ("TMDIFF_TRAIN_GRAPH", _FLAG(False), False),
         "train_two_streams": ("TMDIFF_TRAIN_STREAMS", _FLAG(True), True),
+        "sample_graph": ("TMDIFF_SAMPLE_GRAPH", _FLAG(False), False),
     }
 
     def __init__(self, env=None):
@@ -929,6 +933,26 @@ def ddpm_step(x, eps, noise, c_recip, c_recipm1, coef1, coef2, sigma, clip=True,
                                _chk(img_out, "img_out"), x.numel(), c_recip, c_recipm1, coef1, coef2, sigma,
                                1 if clip else 0, stream_ptr()), "ddpm_step")
     return y
+
+
+def ddpm_step_dev(x, eps, noise, step, coef, ms=None, out=None, frames=None, frame_every=1, clip=True):
+    """ddpm_step with the timestep and its coefficients read on the device: t = step[0] (int32), coefficients = row t of
+    coef [T, 5] (fp32).  ``out`` may be ``x`` (in-place).  frames: [slots, *x.shape] stack written at t % frame_every == 0."""
+    y = out if out is not None else torch.empty_like(x)
+    if step.dtype != torch.int32 or not step.is_cuda or coef.dim() != 2 or coef.shape[1] != 5:
+        raise ValueError("ddpm_step_dev: step must be an int32 device word and coef a [T, 5] table")
+    check(lib.tmdiff_ddpm_step_dev(_chk(x, "x"), _chk(eps, "eps"), _chk(noise, "noise"), _chk(ms, "ms"), _chk(y, "out"),
+                                   _chk(frames, "frames"), x.numel(), step.data_ptr(), _chk(coef, "coef"), coef.shape[0],
+                                   frame_every, 1 if clip else 0, stream_ptr()), "ddpm_step_dev")
+    return y
+
+
+def sampler_tick(step, time_in, set_to=-1):
+    """step[0] = set_to (>= 0) or step[0] - 1; then time_in[:] = step[0] + 1 (fp32), on the device."""
+    if step.dtype != torch.int32 or not step.is_cuda:
+        raise ValueError("sampler_tick: step must be an int32 device word")
+    check(lib.tmdiff_sampler_tick(step.data_ptr(), _chk(time_in, "time_in"), time_in.numel(), int(set_to), stream_ptr()),
+          "sampler_tick")
 
 
 def axpby(tensors, coefs, out=None):
