@@ -93,6 +93,44 @@ __device__ __forceinline__ void stagger_start(int cycles, unsigned first_round) 
   while ((long long)(__builtin_amdgcn_s_memtime() - t0) < (long long)cycles) __builtin_amdgcn_s_sleep(32);
 }
 
+// One step of a tile-index decode: the index along an extent of n tiles, and the block id of the outer extents left in id.
+// (integer division runs on the VALU; readfirstlane moves the wave-uniform result back to an SGPR)
+__device__ __forceinline__ int take(unsigned& id, int n) {
+  const int i = __builtin_amdgcn_readfirstlane(id % n);
+  id /= n;
+  return i;
+}
+
+// Per-channel vectors of an MFMA epilogue: lane l (and l + 32) holds, for channel co0 + m*32 + (l & 31) of group g, the bias
+// times bias_scale and the second output's shift and scale of sample b (0 / 0 / 1 where absent).  CLAMPED: every load at a
+// valid address -- a channel past cout_g reads the group's last one, an absent bias reads a.wp (the fused kernel, whose
+// channel tiles may be ragged).  The fields are read into locals and the values gathered in local arrays: a store through
+// the caller's arrays could alias a field, and the loads and tests would then stay inside the loop.
+template <int MSUB, bool CLAMPED = false, class Args>
+__device__ __forceinline__ void load_channel_vectors(const Args& a, int b, int g, int co0, int l31, float (&bias_v)[MSUB],
+                                                     float (&sh2_v)[MSUB], float (&sc2_v)[MSUB]) {
+  const float* bias = a.bias;
+  const float bias_scale = a.bias_scale;
+  const int cout_g = a.cout_g;
+  const bool has_sh2 = a.y2 && a.y2_shift, has_sc2 = a.y2 && a.y2_scale;
+  float bv[MSUB], sv[MSUB], cv[MSUB];
+#pragma unroll
+  for (int m = 0; m < MSUB; ++m) {
+    if constexpr (CLAMPED) {
+      const float* bp = bias ? bias + g * cout_g + min(co0 + m * 32 + l31, cout_g - 1) : a.wp;
+      const float raw = *bp;
+      bv[m] = bias ? bias_scale * raw : 0.f;
+    } else {
+      bv[m] = bias ? bias[g * cout_g + co0 + m * 32 + l31] * bias_scale : 0.f;
+    }
+    const int col = CLAMPED ? g * cout_g + min(co0 + m * 32 + l31, cout_g - 1) : g * cout_g + co0 + m * 32 + l31;
+    sv[m] = has_sh2 ? a.y2_shift[(long)b * a.y2_shift_stride + col] : 0.f;
+    cv[m] = has_sc2 ? a.y2_scale[(long)b * a.y2_scale_stride + col] : 1.f;
+  }
+#pragma unroll
+  for (int m = 0; m < MSUB; ++m) bias_v[m] = bv[m], sh2_v[m] = sv[m], sc2_v[m] = cv[m];
+}
+
 // source of zero padding / filler lanes of the LDS-DMA staging (internal linkage: one copy per translation unit)
 static __device__ const float4 kZero4 = {0.f, 0.f, 0.f, 0.f};
 
@@ -225,6 +263,15 @@ inline int check_mask_or_dropout(const tmdiff_conv3d_desc* d, const char* what) 
 inline int check_dropout(const tmdiff_conv3d_desc* d, const char* what) {
   if (const int rc = check_mask_or_dropout(d, what)) return rc;
   TMDIFF_REQUIRE(d->drop_p >= 0.f && d->drop_p < 1.f, "%s: drop_p=%g (0 <= drop_p < 1)", what, (double)d->drop_p);
+  return TMDIFF_OK;
+}
+
+// Grid of a tiled launch: `blocks` workgroups, whose ids the kernels decode in 32 bits; sets a.total_blocks.  Fails with a
+// message that begins with the kernel's name `what`.
+template <class Args>
+int set_grid(Args& a, long blocks, const char* what) {
+  if (blocks <= 0 || blocks > 0x7fffffffL) return fail(TMDIFF_E_INVALID, "%s: grid of %ld blocks", what, blocks);
+  a.total_blocks = (unsigned)blocks;
   return TMDIFF_OK;
 }
 

@@ -79,8 +79,8 @@ __global__ void __launch_bounds__(256, 2) conv1_fp32_kernel(const K1Args a) {
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, khalf = lane >> 5;
   unsigned id = blockIdx.x;
-  const int co_tile = __builtin_amdgcn_readfirstlane(id % a.tiles_co); id /= a.tiles_co;
-  const int ptile = __builtin_amdgcn_readfirstlane(id % a.ptiles); id /= a.ptiles;
+  const int co_tile = take(id, a.tiles_co);
+  const int ptile = take(id, a.ptiles);
   const int g = __builtin_amdgcn_readfirstlane(id % a.groups);
   const int b = __builtin_amdgcn_readfirstlane(id / a.groups);
   const int co0 = co_tile * CO;
@@ -244,8 +244,8 @@ __global__ void __launch_bounds__(256, 2) conv1_fp32_vec_kernel(const K1Args a) 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int l31 = lane & 31, khalf = lane >> 5;
   unsigned id = blockIdx.x;
-  const int co_tile = __builtin_amdgcn_readfirstlane(id % a.tiles_co); id /= a.tiles_co;
-  const int ptile = __builtin_amdgcn_readfirstlane(id % a.ptiles); id /= a.ptiles;
+  const int co_tile = take(id, a.tiles_co);
+  const int ptile = take(id, a.ptiles);
   const int g = __builtin_amdgcn_readfirstlane(id % a.groups);
   const int b = __builtin_amdgcn_readfirstlane(id / a.groups);
   const int co0 = co_tile * CO;

@@ -109,13 +109,12 @@ __global__ void __launch_bounds__(256, 2) conv3d_mfma_kernel(const ConvArgs a) {
   const int l31 = lane & 31, khalf = lane >> 5;
 
   // ---- which tile -------------------------------------------------------------------------
-  // (integer division runs on the VALU; readfirstlane moves the wave-uniform results back to SGPRs)
   unsigned id = xcd_remap(blockIdx.x, a.total_blocks);
-  const int co_tile = __builtin_amdgcn_readfirstlane(id % a.tiles_co); id /= a.tiles_co;
-  const int tw_i = __builtin_amdgcn_readfirstlane(id % a.tiles_w); id /= a.tiles_w;
-  const int th_i = __builtin_amdgcn_readfirstlane(id % a.tiles_h); id /= a.tiles_h;
-  const int tn_i = __builtin_amdgcn_readfirstlane(id % a.tiles_n); id /= a.tiles_n;
-  const int g = __builtin_amdgcn_readfirstlane(id % a.groups); id /= a.groups;
+  const int co_tile = take(id, a.tiles_co);
+  const int tw_i = take(id, a.tiles_w);
+  const int th_i = take(id, a.tiles_h);
+  const int tn_i = take(id, a.tiles_n);
+  const int g = take(id, a.groups);
   const int b = __builtin_amdgcn_readfirstlane(id % a.B);
   const int split = __builtin_amdgcn_readfirstlane(id / a.B);   // split-K range of this workgroup (outermost index)
   const int c_begin = split * a.split_ch, c_end = c_begin + a.split_ch;
@@ -160,21 +159,9 @@ __global__ void __launch_bounds__(256, 2) conv3d_mfma_kernel(const ConvArgs a) {
 
   const float* wp_g = a.wp + (long)g * a.cin_g * G::TAPS * a.cout_g;
 
-  float bias_v[MSUB];  // epilogue bias, fetched now so that its latency is long gone when it is needed
-#pragma unroll
-  for (int m = 0; m < MSUB; ++m) {
-    const int col = min(co0 + m * 32 + l31, a.cout_g - 1);
-    const float* bp = a.bias ? a.bias + g * a.cout_g + col : a.wp;  // always a valid address
-    const float raw = *bp;
-    bias_v[m] = a.bias ? a.bias_scale * raw : 0.f;
-  }
-  float sh2_v[MSUB], sc2_v[MSUB];  // second-output shift / scale of channel co0 + m*32 + l31 (same readlane scheme)
-#pragma unroll
-  for (int m = 0; m < MSUB; ++m) {
-    const int col = g * a.cout_g + min(co0 + m * 32 + l31, a.cout_g - 1);
-    sh2_v[m] = (a.y2 && a.y2_shift) ? a.y2_shift[(long)b * a.y2_shift_stride + col] : 0.f;
-    sc2_v[m] = (a.y2 && a.y2_scale) ? a.y2_scale[(long)b * a.y2_scale_stride + col] : 1.f;
-  }
+  // epilogue bias, second-output shift / scale: fetched now so that their latency is long gone when they are needed
+  float bias_v[MSUB], sh2_v[MSUB], sc2_v[MSUB];
+  load_channel_vectors<MSUB, true>(a, b, g, co0, l31, bias_v, sh2_v, sc2_v);
 
   // prefetch registers of the chunk in flight
   float xr[KC][G::EPT];
@@ -348,19 +335,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_mfma_kernel(const ConvArgs a) {
   }
 
   if (a.part) {  // split-K: raw partial sums; splitk_reduce_kernel adds them up and applies the epilogue
-#pragma unroll
-    for (int m = 0; m < MSUB; ++m)
-#pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        const int p = (wv * NS + s) * 32 + l31;
-        const int n = n0 + p / (TW * TH), h = h0 + (p / TW) % TH, w = w0 + p % TW;
-        const bool pok = n < a.N && h < a.H && w < a.W;
-        const long sp = pok ? ((long)n * a.H + h) * a.W + w : 0;
-        float* dst = a.part + (((long)split * a.B + b) * a.Cout + g * a.cout_g + co0 + m * 32 + 4 * khalf) * plane + sp;
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (pok) dst[((r & 3) + 8 * (r >> 2)) * plane] = acc[s][m][r];
-      }
+    tmdiff::store_partials<NS, MSUB, TH, TW>(a, acc, split, b, g, co0, n0, h0, w0, wv, lane, plane);
     return;
   }
 
@@ -373,59 +348,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_mfma_kernel(const ConvArgs a) {
       return;
     }
   }
-  // ---- scalar epilogue: bias, residual, scale; D layout: col = lane&31 (position), row = channel --------
-  // Loads first (bias rows, then all residual elements of a sub-tile), then the stores: no load->store chains.
-#pragma unroll
-  for (int m = 0; m < MSUB; ++m) {
-    // lane l31 holds the bias of channel co0 + m*32 + l31 (one coalesced load, issued before the main loop);
-    // accumulator register r of a lane needs row (r&3) + 8*(r>>2) + 4*khalf of it -> v_readlane + select.
-    float bias_r[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2);
-      const float b0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bias_v[m]), row));
-      const float b1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bias_v[m]), row + 4));
-      bias_r[r] = khalf ? b1 : b0;
-    }
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      const int p = (wv * NS + s) * 32 + l31;
-      const int n = n0 + p / (TW * TH), h = h0 + (p / TW) % TH, w = w0 + p % TW;
-      const bool pok = n < a.N && h < a.H && w < a.W;
-      const long sp = pok ? ((long)n * a.H + h) * a.W + w : 0;
-      const long obase = ((long)b * a.Cout + g * a.cout_g + co0 + m * 32 + 4 * khalf) * plane + sp;
-      float res[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2);
-        const bool ok = pok && (FAST || co0 + m * 32 + 4 * khalf + row < a.cout_g);
-        res[r] = (a.residual && ok) ? a.residual[obase + row * plane] : 0.f;
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2);
-        const bool ok = pok && (FAST || co0 + m * 32 + 4 * khalf + row < a.cout_g);
-        const float v = (acc[s][m][r] + bias_r[r] + res[r]) * a.out_scale;
-        if (ok && a.y) a.y[obase + row * plane] = v;
-        acc[s][m][r] = v;
-      }
-      if (a.y2) {  // (wave-uniform) the consumer's prologue on the finished values
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = (r & 3) + 8 * (r >> 2);
-          const bool ok = pok && (FAST || co0 + m * 32 + 4 * khalf + row < a.cout_g);
-          const float s0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sh2_v[m]), row));
-          const float s1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sh2_v[m]), row + 4));
-          const float c0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sc2_v[m]), row));
-          const float c1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sc2_v[m]), row + 4));
-          float t = acc[s][m][r] + (khalf ? s1 : s0);
-          const float ta = tmdiff::silu_f(t);
-          t = (a.y2_act ? ta : t) * (khalf ? c1 : c0);
-          if (ok) a.y2[obase + row * plane] = t;
-        }
-      }
-    }
-  }
+  tmdiff::epilogue_scalar<NS, MSUB, TN, TH, TW, FAST>(a, acc, bias_v, sh2_v, sc2_v, b, g, co0, n0, h0, w0, wv, lane, plane);
 }
 
 // Column order inside a packed row.  When the (output) channel count is a multiple of 64 the forward kernel
@@ -585,8 +508,7 @@ int launch(ConvArgs& a, hipStream_t st) {
   a.tiles_w = (a.W + TW - 1) / TW;
   a.tiles_co = (a.cout_g + CO - 1) / CO;
   const long blocks = (long)a.ksplit * a.B * a.groups * a.tiles_n * a.tiles_h * a.tiles_w * a.tiles_co;
-  if (blocks <= 0 || blocks > 0x7fffffffL) return tmdiff::fail(TMDIFF_E_INVALID, "conv3d: grid of %ld blocks", blocks);
-  a.total_blocks = (unsigned)blocks;
+  if (const int rc = tmdiff::set_grid(a, blocks, "conv3d")) return rc;
   const bool fast = a.cin_g % KC == 0 && a.cout_g % CO == 0 && a.w_vec4;
   const bool masked = a.in_mask || a.drop_inv > 0.f;
   if (masked && fast)  // training (dropout) path

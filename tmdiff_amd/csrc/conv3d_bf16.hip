@@ -318,10 +318,10 @@ __global__ void __launch_bounds__(256, 2) conv3d_bf16_kernel(const BfArgs a) {
   const int l31 = lane & 31, kg = lane >> 5;
 
   unsigned id = xcd_remap(blockIdx.x, a.total_blocks);
-  const int co_tile = __builtin_amdgcn_readfirstlane(id % a.tiles_co); id /= a.tiles_co;
-  const int tw_i = __builtin_amdgcn_readfirstlane(id % a.tiles_w); id /= a.tiles_w;
-  const int th_i = __builtin_amdgcn_readfirstlane(id % a.tiles_h); id /= a.tiles_h;
-  const int tn_i = __builtin_amdgcn_readfirstlane(id % a.tiles_n); id /= a.tiles_n;
+  const int co_tile = take(id, a.tiles_co);
+  const int tw_i = take(id, a.tiles_w);
+  const int th_i = take(id, a.tiles_h);
+  const int tn_i = take(id, a.tiles_n);
   const int g = __builtin_amdgcn_readfirstlane(id % a.groups);
   const int b = __builtin_amdgcn_readfirstlane(id / a.groups);
   const int n0 = tn_i * TN, h0 = th_i * TH, w0 = tw_i * TW;
@@ -528,10 +528,10 @@ __global__ void __launch_bounds__(256, 2) conv3d_bf16_dma_kernel(const BfArgs a,
   const int l31 = lane & 31, kg = lane >> 5;
 
   unsigned id = xcd_remap(blockIdx.x, a.total_blocks);
-  const int co_tile = __builtin_amdgcn_readfirstlane(id % a.tiles_co); id /= a.tiles_co;
-  const int tw_i = __builtin_amdgcn_readfirstlane(id % a.tiles_w); id /= a.tiles_w;
-  const int th_i = __builtin_amdgcn_readfirstlane(id % a.tiles_h); id /= a.tiles_h;
-  const int tn_i = __builtin_amdgcn_readfirstlane(id % a.tiles_n); id /= a.tiles_n;
+  const int co_tile = take(id, a.tiles_co);
+  const int tw_i = take(id, a.tiles_w);
+  const int th_i = take(id, a.tiles_h);
+  const int tn_i = take(id, a.tiles_n);
   const int g = __builtin_amdgcn_readfirstlane(id % a.groups);
   const int b = __builtin_amdgcn_readfirstlane(id / a.groups);
   const int n0 = tn_i * TN, h0 = th_i * TH, w0 = tw_i * TW;
@@ -739,8 +739,8 @@ __global__ void __launch_bounds__(256, 2) conv1_bf16_kernel(const BfArgs a) {
   const int l31 = lane & 31, kg = lane >> 5;
   const long plane = (long)a.N * a.H * a.W;
   unsigned id = blockIdx.x;
-  const int co_tile = __builtin_amdgcn_readfirstlane(id % a.tiles_co); id /= a.tiles_co;
-  const int ptile = __builtin_amdgcn_readfirstlane(id % a.tiles_w); id /= a.tiles_w;   // tiles_w = position tiles here
+  const int co_tile = take(id, a.tiles_co);
+  const int ptile = take(id, a.tiles_w);   // tiles_w = position tiles here
   const int g = __builtin_amdgcn_readfirstlane(id % a.groups);
   const int b = __builtin_amdgcn_readfirstlane(id / a.groups);
   const int co0 = co_tile * CO;
@@ -880,8 +880,7 @@ int launch(BfArgs& a, hipStream_t st) {
   a.tiles_w = (a.W + TW - 1) / TW;
   a.tiles_co = a.cout_g / CO;
   const long blocks = (long)a.B * a.groups * a.tiles_n * a.tiles_h * a.tiles_w * a.tiles_co;
-  if (blocks <= 0 || blocks > 0x7fffffffL) return tmdiff::fail(TMDIFF_E_INVALID, "conv3d_bf16: grid of %ld blocks", blocks);
-  a.total_blocks = (unsigned)blocks;
+  if (const int rc = tmdiff::set_grid(a, blocks, "conv3d_bf16")) return rc;
   if (a.in_act)
     conv3d_bf16_kernel<NS, MSUB, TH, TW, true><<<(unsigned)blocks, 256, 0, st>>>(a);
   else
@@ -905,8 +904,7 @@ int launch_dma(BfArgs& a, uint4* xp, hipStream_t st, bool do_pack = true) {
   a.tiles_w = (a.W + TW - 1) / TW;
   a.tiles_co = a.cout_g / CO;
   const long blocks = (long)a.B * a.groups * a.tiles_n * a.tiles_h * a.tiles_w * a.tiles_co;
-  if (blocks <= 0 || blocks > 0x7fffffffL) return tmdiff::fail(TMDIFF_E_INVALID, "conv3d_bf16: grid of %ld blocks", blocks);
-  a.total_blocks = (unsigned)blocks;
+  if (const int rc = tmdiff::set_grid(a, blocks, "conv3d_bf16")) return rc;
   conv3d_bf16_dma_kernel<NS, MSUB, TH, TW><<<(unsigned)blocks, 256, 0, st>>>(a, xp);
   return tmdiff::check_launch("conv3d_fwd_bf16 (packed input)");
 }

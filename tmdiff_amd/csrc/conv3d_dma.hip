@@ -70,11 +70,11 @@ __global__ void __launch_bounds__(256, 2) conv3d_dma_kernel(const DmaArgs a) {
   const int l31 = lane & 31, khalf = lane >> 5;
 
   unsigned id = xcd_remap(blockIdx.x, a.total_blocks);
-  const int co_tile = __builtin_amdgcn_readfirstlane(id % a.tiles_co); id /= a.tiles_co;
-  const int tw_i = __builtin_amdgcn_readfirstlane(id % a.tiles_w); id /= a.tiles_w;
-  const int th_i = __builtin_amdgcn_readfirstlane(id % a.tiles_h); id /= a.tiles_h;
-  const int tn_i = __builtin_amdgcn_readfirstlane(id % a.tiles_n); id /= a.tiles_n;
-  const int g = __builtin_amdgcn_readfirstlane(id % a.groups); id /= a.groups;
+  const int co_tile = take(id, a.tiles_co);
+  const int tw_i = take(id, a.tiles_w);
+  const int th_i = take(id, a.tiles_h);
+  const int tn_i = take(id, a.tiles_n);
+  const int g = take(id, a.groups);
   const int b = __builtin_amdgcn_readfirstlane(id % a.B);
   const int split = __builtin_amdgcn_readfirstlane(id / a.B);   // split-K range of this workgroup (outermost index)
   const int n0 = tn_i * TN, h0 = th_i * TH, w0 = tw_i * TW;
@@ -132,16 +132,8 @@ __global__ void __launch_bounds__(256, 2) conv3d_dma_kernel(const DmaArgs a) {
   }
   const int aoff = G::X_FLOATS + khalf * G::TAPS * CO + l31 * MSUB;  // slab rows hold the tile's channels as [l31][m]
 
-  float bias_v[MSUB];
-#pragma unroll
-  for (int m = 0; m < MSUB; ++m) bias_v[m] = a.bias ? a.bias[g * a.cout_g + co0 + m * 32 + l31] * a.bias_scale : 0.f;
-  float sh2_v[MSUB], sc2_v[MSUB];
-#pragma unroll
-  for (int m = 0; m < MSUB; ++m) {
-    const int col = g * a.cout_g + co0 + m * 32 + l31;
-    sh2_v[m] = (a.y2 && a.y2_shift) ? a.y2_shift[(long)b * a.y2_shift_stride + col] : 0.f;
-    sc2_v[m] = (a.y2 && a.y2_scale) ? a.y2_scale[(long)b * a.y2_scale_stride + col] : 1.f;
-  }
+  float bias_v[MSUB], sh2_v[MSUB], sc2_v[MSUB];
+  load_channel_vectors<MSUB>(a, b, g, co0, l31, bias_v, sh2_v, sc2_v);
 
   f32x16 acc[NS][MSUB];
 #pragma unroll
@@ -211,19 +203,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_dma_kernel(const DmaArgs a) {
   }
 
   if (a.part) {  // split-K: raw partial sums; splitk_reduce_kernel (conv3d.hip) adds them up and applies the epilogue
-#pragma unroll
-    for (int m = 0; m < MSUB; ++m)
-#pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        const int p = (wv * NS + s) * 32 + l31;
-        const int n = n0 + p / (TW * TH), h = h0 + (p / TW) % TH, w = w0 + p % TW;
-        const bool pok = n < a.N && h < a.H && w < a.W;
-        const long sp = pok ? ((long)n * a.H + h) * a.W + w : 0;
-        float* dst = a.part + (((long)split * a.B + b) * a.Cout + g * a.cout_g + co0 + m * 32 + 4 * khalf) * plane + sp;
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (pok) dst[((r & 3) + 8 * (r >> 2)) * plane] = acc[s][m][r];
-      }
+    tmdiff::store_partials<NS, MSUB, TH, TW>(a, acc, split, b, g, co0, n0, h0, w0, wv, lane, plane);
     return;
   }
 
@@ -233,53 +213,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_dma_kernel(const DmaArgs a) {
                                                st0 + wv * 1024);
     return;
   }
-  // ---- scalar epilogue: bias, residual, scale; D layout: col = lane&31 (position), row = channel ---------------
-#pragma unroll
-  for (int m = 0; m < MSUB; ++m) {
-    float bias_r[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2);
-      const float b0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bias_v[m]), row));
-      const float b1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bias_v[m]), row + 4));
-      bias_r[r] = khalf ? b1 : b0;
-    }
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      const int p = (wv * NS + s) * 32 + l31;
-      const int n = n0 + p / (TW * TH), h = h0 + (p / TW) % TH, w = w0 + p % TW;
-      const bool pok = n < a.N && h < a.H && w < a.W;
-      const long sp = pok ? ((long)n * a.H + h) * a.W + w : 0;
-      const long obase = ((long)b * a.Cout + g * a.cout_g + co0 + m * 32 + 4 * khalf) * plane + sp;
-      float res[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2);
-        res[r] = (a.residual && pok) ? a.residual[obase + row * plane] : 0.f;
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2);
-        const float v = (acc[s][m][r] + bias_r[r] + res[r]) * a.out_scale;
-        if (pok && a.y) a.y[obase + row * plane] = v;
-        acc[s][m][r] = v;
-      }
-      if (a.y2) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = (r & 3) + 8 * (r >> 2);
-          const float s0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sh2_v[m]), row));
-          const float s1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sh2_v[m]), row + 4));
-          const float c0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sc2_v[m]), row));
-          const float c1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sc2_v[m]), row + 4));
-          float t = acc[s][m][r] + (khalf ? s1 : s0);
-          const float ta = tmdiff::silu_f(t);
-          t = (a.y2_act ? ta : t) * (khalf ? c1 : c0);
-          if (pok) a.y2[obase + row * plane] = t;
-        }
-      }
-    }
-  }
+  tmdiff::epilogue_scalar<NS, MSUB, TN, TH, TW, true>(a, acc, bias_v, sh2_v, sc2_v, b, g, co0, n0, h0, w0, wv, lane, plane);
 }
 
 template <int KS, int NS, int MSUB, int KC, int TN, int TH, int TW>
@@ -290,8 +224,7 @@ int launch(DmaArgs& a, hipStream_t st) {
   a.tiles_w = (a.W + TW - 1) / TW;
   a.tiles_co = a.cout_g / CO;
   const long blocks = (long)a.ksplit * a.B * a.groups * a.tiles_n * a.tiles_h * a.tiles_w * a.tiles_co;
-  if (blocks <= 0 || blocks > 0x7fffffffL) return tmdiff::fail(TMDIFF_E_INVALID, "conv3d_fwd_staged: grid of %ld blocks", blocks);
-  a.total_blocks = (unsigned)blocks;
+  if (const int rc = tmdiff::set_grid(a, blocks, "conv3d_fwd_staged")) return rc;
   conv3d_dma_kernel<KS, NS, MSUB, KC, TN, TH, TW><<<(unsigned)blocks, 256, 0, st>>>(a);
   return tmdiff::check_launch("conv3d_fwd_staged");
 }

@@ -333,10 +333,10 @@ __global__ void __launch_bounds__(256, 2) conv3d_wf_kernel(const WfArgs a) {
   WF_STAMP(1);
 
   unsigned id = xcd_remap(blockIdx.x, a.total_blocks);
-  const int split = __builtin_amdgcn_readfirstlane(id % a.ksplit); id /= a.ksplit;      // (1: no split-K)
-  const int co_tile = __builtin_amdgcn_readfirstlane(id % a.tiles_co); id /= a.tiles_co;
-  const int tw_i = __builtin_amdgcn_readfirstlane(id % a.tiles_w); id /= a.tiles_w;
-  const int th_i = __builtin_amdgcn_readfirstlane(id % a.tiles_h); id /= a.tiles_h;
+  const int split = take(id, a.ksplit);      // (1: no split-K)
+  const int co_tile = take(id, a.tiles_co);
+  const int tw_i = take(id, a.tiles_w);
+  const int th_i = take(id, a.tiles_h);
   const int g = __builtin_amdgcn_readfirstlane(id % a.groups);
   const int b = __builtin_amdgcn_readfirstlane(id / a.groups) * (PAIR ? 2 : 1);     // (PAIR: images b and b + 1)
   const bool pimg_ok = !PAIR || b + 1 < a.B;
@@ -658,8 +658,7 @@ int launch(WfArgs& a, hipStream_t st) {
   a.tiles_w = PAIR ? 1 : (a.W + TW - 1) / TW;
   a.tiles_co = a.cout_g / 32;
   const long blocks = (long)a.ksplit * (PAIR ? (a.B + 1) / 2 : a.B) * a.groups * a.tiles_h * a.tiles_w * a.tiles_co;
-  if (blocks <= 0 || blocks > 0x7fffffffL) return tmdiff::fail(TMDIFF_E_INVALID, "conv3d_wf_fwd: grid of %ld blocks", blocks);
-  a.total_blocks = (unsigned)blocks;
+  if (const int rc = tmdiff::set_grid(a, blocks, "conv3d_wf_fwd")) return rc;
   // experiments: delay of every CU's second resident workgroup, in chunk times
   static const double stagger_chunks = env_double("TMDIFF_WF_STAGGER", 0.0);
   a.first_round = 512;

@@ -229,10 +229,10 @@ __global__ void __launch_bounds__(256, 2) conv3d_wino_kernel(const WinoArgs a) {
   WINO_STAMP(1);
 
   unsigned id = xcd_remap(blockIdx.x, a.total_blocks);
-  const int co_tile = __builtin_amdgcn_readfirstlane(id % a.tiles_co); id /= a.tiles_co;
-  const int tw_i = __builtin_amdgcn_readfirstlane(id % a.tiles_w); id /= a.tiles_w;
-  const int th_i = __builtin_amdgcn_readfirstlane(id % a.tiles_h); id /= a.tiles_h;
-  const int tt_i = __builtin_amdgcn_readfirstlane(id % a.tiles_t); id /= a.tiles_t;
+  const int co_tile = take(id, a.tiles_co);
+  const int tw_i = take(id, a.tiles_w);
+  const int th_i = take(id, a.tiles_h);
+  const int tt_i = take(id, a.tiles_t);
   const int g = __builtin_amdgcn_readfirstlane(id % a.groups);
   const int b = __builtin_amdgcn_readfirstlane(id / a.groups);
   const int t0 = tt_i * TT, h0 = th_i * TH, w0 = tw_i * TW;
@@ -296,13 +296,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_wino_kernel(const WinoArgs a) {
   const int aoff = G::X_FLOATS + khalf * W_TAPS * CO + xi_base * CO + l31 * MSUB;  // slab rows hold the tile's channels as [l31][m]
 
   float bias_v[MSUB], sh2_v[MSUB], sc2_v[MSUB];
-#pragma unroll
-  for (int m = 0; m < MSUB; ++m) {
-    const int col = g * a.cout_g + co0 + m * 32 + l31;
-    bias_v[m] = a.bias ? a.bias[col] * a.bias_scale : 0.f;
-    sh2_v[m] = (a.y2 && a.y2_shift) ? a.y2_shift[(long)b * a.y2_shift_stride + col] : 0.f;
-    sc2_v[m] = (a.y2 && a.y2_scale) ? a.y2_scale[(long)b * a.y2_scale_stride + col] : 1.f;
-  }
+  load_channel_vectors<MSUB>(a, b, g, co0, l31, bias_v, sh2_v, sc2_v);
 
   f32x16 acc[NX * NS][MSUB];    // [(k - xi_base) * NS + s][m]
 #pragma unroll
@@ -448,8 +442,7 @@ int launch(WinoArgs& a, hipStream_t st) {
   a.tiles_w = (a.W + TW - 1) / TW;
   a.tiles_co = a.cout_g / CO;
   const long blocks = (long)a.B * a.groups * a.tiles_t * a.tiles_h * a.tiles_w * a.tiles_co;
-  if (blocks <= 0 || blocks > 0x7fffffffL) return tmdiff::fail(TMDIFF_E_INVALID, "conv3d_wino_fwd: grid of %ld blocks", blocks);
-  a.total_blocks = (unsigned)blocks;
+  if (const int rc = tmdiff::set_grid(a, blocks, "conv3d_wino_fwd")) return rc;
   // stagger (see stagger_start): TMDIFF_WINO_STAGGER = delay in units of one chunk's MFMA time of a workgroup pair
   // (2 x KSTEPS x MF x 64 cycles); only worth it when there are several rounds of workgroups
   static const double stagger_chunks = env_double("TMDIFF_WINO_STAGGER", 0.0);

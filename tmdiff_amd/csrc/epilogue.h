@@ -1,4 +1,6 @@
-// Vector epilogue of the fp32 3x3x3 / 1x1x1 MFMA convolution kernels (conv3d.hip, conv3d_dma.hip).
+// Epilogues of the fp32 MFMA convolution kernels: the fused and staged direct kernels (conv3d.hip, conv3d_dma.hip), the
+// composed-LL kernel (conv3d_ll.hip) and the fallback Winograd kernel (conv3d_wino.hip, vector form only);
+// conv3d_wf.hip takes lane_value for its own.
 //
 // The accumulators come out of v_mfma_f32_32x32x2_f32 as D[channel row][position column]: a lane holds ONE position and 16
 // channels, so written straight from that layout every register is one dword store of 32-byte (TW = 8) or 64-byte (TW = 16)
@@ -116,6 +118,91 @@ __device__ __forceinline__ void epilogue_vec(const Args& a, Acc (&acc)[NS][MSUB]
     if (a.residual) TMDIFF_EPI(false, true, true); else TMDIFF_EPI(false, false, true);
   }
 #undef TMDIFF_EPI
+}
+
+// ---- The scalar forms, straight from the D layout: lane (l31, khalf) = (lane & 31, lane >> 5) holds position l31 of a
+// sub-tile and channel rows (r & 3) + 8 (r >> 2) + 4 khalf of accumulator register r. ------------------------------------
+
+// position of lane l31 in sub-tile s of wave wv: its offset in the output plane, and whether it lies inside the image
+template <int NS, int TH, int TW, class Args>
+__device__ __forceinline__ long sub_tile_pos(const Args& a, int n0, int h0, int w0, int wv, int s, int l31, bool& pok) {
+  const int p = (wv * NS + s) * 32 + l31;
+  const int n = n0 + p / (TW * TH), h = h0 + (p / TW) % TH, w = w0 + p % TW;
+  pok = n < a.N && h < a.H && w < a.W;
+  return pok ? ((long)n * a.H + h) * a.W + w : 0;
+}
+
+// Split-K: the raw partial sums of range `split` into a.part [ksplit][B][Cout][plane]; splitk_reduce_kernel (conv3d.hip) adds
+// them up and applies the epilogue.
+template <int NS, int MSUB, int TH, int TW, class Args, class Acc>
+__device__ __forceinline__ void store_partials(const Args& a, const Acc (&acc)[NS][MSUB], int split, int b, int g, int co0, int n0,
+                                               int h0, int w0, int wv, int lane, long plane) {
+  const int l31 = lane & 31, khalf = lane >> 5;
+#pragma unroll
+  for (int m = 0; m < MSUB; ++m)
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      bool pok;
+      const long sp = sub_tile_pos<NS, TH, TW>(a, n0, h0, w0, wv, s, l31, pok);
+      float* dst = a.part + (((long)split * a.B + b) * a.Cout + g * a.cout_g + co0 + m * 32 + 4 * khalf) * plane + sp;
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        if (pok) dst[((r & 3) + 8 * (r >> 2)) * plane] = acc[s][m][r];
+    }
+}
+
+// Scalar epilogue (W % 4 != 0 or unaligned tensors): bias, residual, scale, second output -- the arithmetic of epilogue_vec.
+// A lane's bias / shift / scale comes from the lane of its channel by v_readlane and a select on khalf.  Loads first (all
+// residual elements of a sub-tile), then the stores: no load->store chains.  Without FAST the channels past cout_g of a ragged
+// channel tile are neither read nor written.
+template <int NS, int MSUB, int TN, int TH, int TW, bool FAST, class Args, class Acc>
+__device__ __forceinline__ void epilogue_scalar(const Args& a, Acc (&acc)[NS][MSUB], const float (&bias_v)[MSUB],
+                                                const float (&sh2_v)[MSUB], const float (&sc2_v)[MSUB], int b, int g, int co0,
+                                                int n0, int h0, int w0, int wv, int lane, long plane) {
+  const int l31 = lane & 31, khalf = lane >> 5;
+  auto row_value = [&](float v, int row) __attribute__((always_inline)) {   // channel row + 4 khalf of the sub-tile
+    const float v0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), row));
+    const float v1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), row + 4));
+    return khalf ? v1 : v0;
+  };
+#pragma unroll
+  for (int m = 0; m < MSUB; ++m) {
+    float bias_r[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) bias_r[r] = row_value(bias_v[m], (r & 3) + 8 * (r >> 2));
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      bool pok;
+      const long sp = sub_tile_pos<NS, TH, TW>(a, n0, h0, w0, wv, s, l31, pok);
+      const long obase = ((long)b * a.Cout + g * a.cout_g + co0 + m * 32 + 4 * khalf) * plane + sp;
+      float res[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2);
+        const bool ok = pok && (FAST || co0 + m * 32 + 4 * khalf + row < a.cout_g);
+        res[r] = (a.residual && ok) ? a.residual[obase + row * plane] : 0.f;
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2);
+        const bool ok = pok && (FAST || co0 + m * 32 + 4 * khalf + row < a.cout_g);
+        const float v = (acc[s][m][r] + bias_r[r] + res[r]) * a.out_scale;
+        if (ok && a.y) a.y[obase + row * plane] = v;
+        acc[s][m][r] = v;
+      }
+      if (a.y2) {  // (wave-uniform) the consumer's prologue on the finished values
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = (r & 3) + 8 * (r >> 2);
+          const bool ok = pok && (FAST || co0 + m * 32 + 4 * khalf + row < a.cout_g);
+          float t = acc[s][m][r] + row_value(sh2_v[m], row);
+          const float ta = silu_f(t);
+          t = (a.y2_act ? ta : t) * row_value(sc2_v[m], row);
+          if (ok) a.y2[obase + row * plane] = t;
+        }
+      }
+    }
+  }
 }
 
 }  // namespace tmdiff

@@ -200,9 +200,9 @@ __global__ void __launch_bounds__(256, 2) ww_gemm_kernel(const WwArgs a) {
 
   // tiles fastest: the workgroups that read the same boxes sit side by side (and, after the remap, on one XCD's L2)
   unsigned id = xcd_remap(blockIdx.x, a.total_blocks);
-  const int ci_t = __builtin_amdgcn_readfirstlane(id % a.tiles_ci); id /= a.tiles_ci;
-  const int co_t = __builtin_amdgcn_readfirstlane(id % a.tiles_co); id /= a.tiles_co;
-  const int split = __builtin_amdgcn_readfirstlane(id % a.splits); id /= a.splits;
+  const int ci_t = take(id, a.tiles_ci);
+  const int co_t = take(id, a.tiles_co);
+  const int split = take(id, a.splits);
   const int k = __builtin_amdgcn_readfirstlane(id % 6);
   const int g = __builtin_amdgcn_readfirstlane(id / 6);
   const int Hp = a.Hb + 2, Wp = a.Wb + 2;
