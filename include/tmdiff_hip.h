@@ -545,6 +545,30 @@ int tmdiff_q_sample(const float* x0, const float* noise, const float* a, float* 
                     tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Overlapped scene tiles (fused large-scene sampling; the reference only tiles without overlap, data/LRHR_dataset.py:17-53).
+ * One noisy scene [B, C, H, W] is kept; at every denoise step square tiles of edge `tile` that overlap by `overlap` pixels
+ * are cut out of it, the network runs on the tiles, and its outputs are blended back into one scene-sized prediction.
+ *  plan (per axis of length L): origins 0, s, 2s, ... with s = tile - overlap while origin + tile <= L, plus one tile pushed
+ *    inwards to L - tile when the last regular one does not end at L: origin(i) = min(i * s, L - tile).  Needs tile <= L and
+ *    0 <= overlap <= tile / 2.  tmdiff_tile_plan (host function) returns the number of origins and writes the first
+ *    `capacity` of them (origins may be NULL); -1 for arguments out of range.  (tile % 8 == 0, which the UNet's three
+ *    wavelet levels need, is the caller's rule -- tiling.plan_tiles -- and not checked here: the kernels only copy.)
+ *  tiles are [B * ny * nx, C, tile, tile], numbered row-major per scene sample.
+ *  tile_gather: tiles[(b, iy, ix), c, y, x] = scene[b, c, oy(iy) + y, ox(ix) + x]  (a copy).
+ *  tile_blend : scene[b, c, Y, X] = sum_t w_t v_t / sum_t w_t over the tiles t that cover (Y, X), in row-major tile order, with
+ *    w_t = w1(Y - oy) * w1(X - ox), w1(i) = min(i + 1, tile - i, overlap + 1); fp32, no atomics: deterministic.
+ * Both use 16-byte accesses when W, tile and tile - overlap are multiples of 4 and the tensors are 16-byte aligned, scalar ones
+ * otherwise.  Element offsets are 32-bit: tmdiff_tile_supported is 0 (and the entry points return TMDIFF_E_UNSUPPORTED
+ * without launching) when the scene or the tile stack holds more than 2^31 - 1 elements.
+ * ------------------------------------------------------------------------------------ */
+int32_t tmdiff_tile_plan(int32_t L, int32_t tile, int32_t overlap, int32_t* origins, int32_t capacity);
+int tmdiff_tile_supported(int32_t B, int32_t C, int32_t H, int32_t W, int32_t tile, int32_t overlap);
+int tmdiff_tile_gather(const float* scene, float* tiles, int32_t B, int32_t C, int32_t H, int32_t W, int32_t tile,
+                       int32_t overlap, tmdiff_stream_t stream);
+int tmdiff_tile_blend(const float* tiles, float* scene, int32_t B, int32_t C, int32_t H, int32_t W, int32_t tile,
+                      int32_t overlap, tmdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Standalone attention operators of core/Attention.py (imported by nothing in the reference; built because the
  * north star names them).  All fp32.
  *  attn_fwd : out = softmax(q k^T * scale [key mask]) v per (batch, head); fp32 MFMA, online softmax.

@@ -732,6 +732,18 @@ class WavBEST(nn.Module):
             self._cond = self._condition(self._prepare(), PAN, MS, prompt)
         self._cond["key"] = (self._tensor_key(PAN), self._tensor_key(MS), prompt)
 
+    def add_condition_cache(self, PAN, MS, prompt):
+        """One more cached condition beside the one ``begin_condition_cache`` opened (a run that feeds the network several
+        fixed batches per step: ``tiling.TiledDenoiser``'s chunks).  ``forward`` picks the one whose key matches;
+        ``end_condition_cache`` drops them all."""
+        P = self._prepare()                      # (drops an open cache when the parameters have changed)
+        if self._cond is None:
+            raise RuntimeError("add_condition_cache: no open condition cache (call begin_condition_cache first)")
+        with torch.no_grad():
+            cond = self._condition(P, PAN, MS, prompt)
+        cond["key"] = (self._tensor_key(PAN), self._tensor_key(MS), prompt)
+        self._cond.setdefault("more", []).append(cond)
+
     def end_condition_cache(self):
         self._cond = None
 
@@ -769,7 +781,10 @@ class WavBEST(nn.Module):
     def _forward_infer(self, x_t, t_input, PAN, MS, prompt):
         P = self._prepare()
         cond = self._cond
-        if not (cond is not None and cond.get("key") == (self._tensor_key(PAN), self._tensor_key(MS), prompt)):
+        key = (self._tensor_key(PAN), self._tensor_key(MS), prompt)
+        if cond is not None and cond.get("key") != key:
+            cond = next((c for c in cond.get("more", ()) if c["key"] == key), None)
+        if cond is None:
             cond = self._condition(P, PAN, MS, prompt)
         b = x_t.shape[0]
         t = t_input.reshape(-1).to(device=x_t.device, dtype=torch.float32)

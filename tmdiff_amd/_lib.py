@@ -161,6 +161,11 @@ SIGNATURES.update({
                                             C.c_int32, C.c_int32, vp]),
     "tmdiff_stem_fwd_scaled": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_int32, vp]),
+    # overlapped scene tiles (csrc/tiles.hip): (B, C, H, W, tile, overlap) after the two tensors
+    "tmdiff_tile_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "tmdiff_tile_supported": (C.c_int, [C.c_int32] * 6),
+    "tmdiff_tile_gather": (C.c_int, [vp, vp] + [C.c_int32] * 6 + [vp]),
+    "tmdiff_tile_blend": (C.c_int, [vp, vp] + [C.c_int32] * 6 + [vp]),
 })
 
 

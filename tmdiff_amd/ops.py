@@ -1029,6 +1029,50 @@ def q_sample(x0, noise, a, out=None):
     return y
 
 
+# ---- overlapped scene tiles (csrc/tiles.hip; plan and blend weights: tmdiff_amd/tiling.py) ---------------------------
+def _tile_grid(h, w, tile, overlap):
+    ny, nx = (lib.tmdiff_tile_plan(int(n), int(tile), int(overlap), None, 0) for n in (h, w))
+    if ny < 0 or nx < 0:
+        raise ValueError(f"no tile plan for a {h} x {w} scene with tile={tile}, overlap={overlap}: need tile <= extent and "
+                         f"0 <= overlap <= tile // 2")
+    return ny, nx
+
+
+def tile_supported(b, c, h, w, tile, overlap):
+    """True when tile_gather / tile_blend take these extents (a valid plan whose 32-bit element offsets fit)."""
+    return bool(lib.tmdiff_tile_supported(b, c, h, w, tile, overlap))
+
+
+def tile_gather(scene, tile, overlap, out=None):
+    """scene [B, C, H, W] -> tiles [B * ny * nx, C, tile, tile], row-major per sample."""
+    if scene.dim() != 4:
+        raise ValueError(f"scene: need [B, C, H, W], got {tuple(scene.shape)}")
+    b, c, h, w = scene.shape
+    ny, nx = _tile_grid(h, w, tile, overlap)
+    shape = (b * ny * nx, c, tile, tile)
+    y = out if out is not None else torch.empty(shape, device=scene.device, dtype=torch.float32)
+    if tuple(y.shape) != shape:
+        raise ValueError(f"tiles: need {shape}, got {tuple(y.shape)}")
+    check(lib.tmdiff_tile_gather(_chk(scene, "scene"), _chk(y, "tiles"), b, c, h, w, tile, overlap, stream_ptr()), "tile_gather")
+    return y
+
+
+def tile_blend(tiles, batch, h, w, overlap, out=None):
+    """tiles [batch * ny * nx, C, tile, tile] -> scene [batch, C, h, w]: the weighted mean over the covering tiles."""
+    if tiles.dim() != 4 or tiles.shape[2] != tiles.shape[3]:
+        raise ValueError(f"tiles: need [N, C, tile, tile], got {tuple(tiles.shape)}")
+    n, c, tile, _ = tiles.shape
+    ny, nx = _tile_grid(h, w, tile, overlap)
+    if n != batch * ny * nx:
+        raise ValueError(f"tiles: {n} tiles, the plan has {batch} x {ny} x {nx}")
+    shape = (batch, c, h, w)
+    y = out if out is not None else torch.empty(shape, device=tiles.device, dtype=torch.float32)
+    if tuple(y.shape) != shape:
+        raise ValueError(f"scene: need {shape}, got {tuple(y.shape)}")
+    check(lib.tmdiff_tile_blend(_chk(tiles, "tiles"), _chk(y, "scene"), batch, c, h, w, tile, overlap, stream_ptr()), "tile_blend")
+    return y
+
+
 # ---- backward-side wrappers (finetune path) -----------------------------------------------------------
 
 

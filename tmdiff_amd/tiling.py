@@ -5,10 +5,119 @@
 independent tiles that are sharded over the ranks of the process group (no collective during sampling, one
 all-gather at the end).  WavBEST is fully convolutional with zero padding, so tiled output differs from
 full-frame output within 3x3x3-receptive-field distance of the tile seams -- same as the reference's tiling.
+
+Fused mode (``sample_tiled(..., overlap=k)``, ``TiledDenoiser``): ONE noisy scene is kept; at every denoise step
+overlapping tiles are cut out of it (``ops.tile_gather``), the network runs on the tiles and its outputs are blended
+back into one scene-sized prediction (``ops.tile_blend``) that the sampler steps as a whole, so noise, clamp and
+dynamic thresholding act per scene and a tile's influence fades towards its border.  ``plan_tiles`` is the tile plan.
 """
 import torch
+from torch import nn
 
 from . import dist as tdist
+from . import ops
+
+
+def _plan_axis(length, tile, overlap):
+    step = tile - overlap
+    origins = list(range(0, length - tile + 1, step))
+    if origins[-1] != length - tile:
+        origins.append(length - tile)          # the last tile is pushed inwards: no tile leaves the scene, no padding
+    return origins
+
+
+def plan_tiles(h, w, tile, overlap):
+    """(row origins, column origins) of the overlapped tiles of an h x w scene: per axis 0, s, 2s, ... with
+    s = tile - overlap while origin + tile <= L, plus L - tile if the last one does not end at L.  Tiles are numbered
+    row-major per scene sample, as ``split_tiles`` does.  ``tile % 8 == 0`` (three wavelet levels)."""
+    if tile <= 0 or tile % 8:
+        raise ValueError(f"tile={tile}: need a positive multiple of 8 (three wavelet levels)")
+    if not 0 <= overlap <= tile // 2:
+        raise ValueError(f"overlap={overlap}: need 0 <= overlap <= tile // 2 = {tile // 2}")
+    if h < tile or w < tile:
+        raise ValueError(f"a {h} x {w} scene is smaller than one {tile} x {tile} tile")
+    return _plan_axis(h, tile, overlap), _plan_axis(w, tile, overlap)
+
+
+def tile_profile(tile, overlap):
+    """1-D blend weights w1(i) = min(i + 1, tile - i, overlap + 1), float64; a tile's 2-D weight is w1(y) * w1(x) and a scene
+    pixel is sum(w v) / sum(w) over the tiles that cover it."""
+    i = torch.arange(tile, dtype=torch.float64)
+    return torch.minimum(torch.minimum(i + 1, tile - i), torch.full_like(i, overlap + 1))
+
+
+class TiledDenoiser(nn.Module):
+    """Scene-shaped outside, tile-shaped inside: ``forward`` has ``WavBEST.forward``'s signature, takes scene tensors
+    [B, C, H, W] and returns the scene-sized blend of ``net``'s predictions on the overlapped tiles, run in chunks of at
+    most ``max_batch`` tiles.  Inside ``begin_condition_cache`` / ``end_condition_cache`` the PAN / MS tiles are gathered
+    once and ``net``'s condition branch runs once per chunk for the whole run."""
+
+    def __init__(self, net, tile=64, overlap=16, max_batch=32):
+        super().__init__()
+        plan_tiles(tile, tile, tile, overlap)             # argument check
+        if max_batch < 1:
+            raise ValueError(f"max_batch={max_batch}")
+        self.net, self.tile, self.overlap, self.max_batch = net, tile, overlap, max_batch
+        self._run = None
+
+    @staticmethod
+    def _key(PAN, MS, prompt):
+        k = lambda t: (t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()))
+        return k(PAN), k(MS), tuple(prompt) if isinstance(prompt, (list, tuple)) else prompt
+
+    def _chunks(self, PAN, MS, prompt):
+        """[(PAN tiles, MS tiles, prompt)] per chunk of at most max_batch tiles."""
+        b, _, h, w = MS.shape
+        rows, cols = plan_tiles(h, w, self.tile, self.overlap)
+        per = len(rows) * len(cols)
+        pan_t = ops.tile_gather(PAN.float().contiguous(), self.tile, self.overlap)
+        ms_t = ops.tile_gather(MS.float().contiguous(), self.tile, self.overlap)
+        if isinstance(prompt, (list, tuple)):
+            if len(prompt) != b:
+                raise ValueError("per-sample prompt list must have one entry per batch element")
+            prompts = [p for p in prompt for _ in range(per)]
+        out = []
+        for lo in range(0, b * per, self.max_batch):
+            hi = min(lo + self.max_batch, b * per)
+            out.append((pan_t[lo:hi], ms_t[lo:hi], prompts[lo:hi] if isinstance(prompt, (list, tuple)) else prompt))
+        return out
+
+    def begin_condition_cache(self, PAN, MS, prompt):
+        self.end_condition_cache()
+        chunks = self._chunks(PAN, MS, prompt)
+        self._run = (self._key(PAN, MS, prompt), chunks)
+        if hasattr(self.net, "add_condition_cache"):
+            try:
+                for i, (pan, ms, pr) in enumerate(chunks):
+                    (self.net.begin_condition_cache if i == 0 else self.net.add_condition_cache)(pan, ms, pr)
+            except BaseException:
+                self.end_condition_cache()        # nothing half-open is left behind
+                raise
+
+    def end_condition_cache(self):
+        if self._run is not None and hasattr(self.net, "end_condition_cache"):
+            self.net.end_condition_cache()
+        self._run = None
+
+    @torch.no_grad()
+    def forward(self, x_t, t_input, PAN=None, MS=None, prompt=None):
+        b, _, h, w = x_t.shape
+        rows, cols = plan_tiles(h, w, self.tile, self.overlap)
+        per = len(rows) * len(cols)
+        if self._run is not None and self._run[0] == self._key(PAN, MS, prompt):
+            chunks = self._run[1]
+        else:
+            chunks = self._chunks(PAN, MS, prompt)
+        x_tiles = ops.tile_gather(x_t.float().contiguous(), self.tile, self.overlap)
+        t = t_input.reshape(-1)
+        t = (t if t.numel() == b else t.expand(b)).repeat_interleave(per)
+        outs, lo = [], 0
+        for pan, ms, pr in chunks:
+            hi = lo + pan.shape[0]
+            outs.append(self.net(x_tiles[lo:hi], t[lo:hi].reshape(-1, 1), pan, ms, pr))
+            lo = hi
+        y = outs[0] if len(outs) == 1 else torch.cat(outs)
+        return ops.tile_blend(y.contiguous(), b, h, w, self.overlap)
 
 
 def split_tiles(img, th, tw):
@@ -44,10 +153,36 @@ def unpatch_16(patch):
 
 
 @torch.no_grad()
-def sample_tiled(diffusion, scene, prompt, tile=64, method="dpmsolver", steps=20, max_batch=32):
+def sample_tiled(diffusion, scene, prompt, tile=64, method="dpmsolver", steps=20, max_batch=32, overlap=None):
     """Fuse a large scene tile by tile.  ``scene`` = {'MS': [B,C,H,W], 'PAN': [B,1,H,W]} (Res optional).
-    Tiles are sharded over the ranks; each rank samples its share in batches of ``max_batch`` and the fused
-    tiles are gathered and stitched on every rank."""
+
+    ``overlap=None`` (independent mode): disjoint tiles, one diffusion chain per tile with its own noise and its own
+    dynamic threshold, outputs butted together.  Tiles are sharded over the ranks; each rank samples its share in
+    batches of ``max_batch`` and the fused tiles are gathered and stitched on every rank.  The scene must be a whole
+    number of tiles.
+
+    ``overlap=k >= 0`` (fused mode): the scene is sampled as ONE chain by ``diffusion.sample`` with a ``TiledDenoiser``
+    in place of ``diffusion.denoise_fn`` for the duration of the call: tiles that overlap by k pixels are cut out of the
+    noisy scene at every step and the network's outputs are blended, so clamp and dynamic thresholding act per scene
+    and no seam is left.  Scene extents need not be multiples of the tile.  The UNet work grows by about
+    (tile / (tile - k))^2.  Not covered: more than one rank (ValueError; use the independent mode -- sharding tiles per
+    step needs an all-gather per step), captured-graph sampling (the fused mode runs eagerly, with the same result, also
+    when ``sample_graph`` is on), the gather folded into the stem kernel, training."""
+    if overlap is not None:
+        if tdist.dist.is_initialized() and tdist.dist.get_world_size() > 1:
+            raise ValueError("sample_tiled: the fused mode (overlap=k) runs on one rank only; use the independent mode "
+                             "(overlap=None) under a process group")
+        ms = scene["MS"]
+        plan_tiles(ms.shape[2], ms.shape[3], tile, overlap)
+        x_in = {"MS": ms, "PAN": scene["PAN"], "Res": scene["Res"] if "Res" in scene else torch.zeros_like(ms)}
+        net = diffusion.denoise_fn
+        wrapped = TiledDenoiser(net, tile, overlap, max_batch)
+        diffusion.denoise_fn = wrapped
+        try:
+            return diffusion.sample(x_in, prompt, method=method, **({"steps": steps} if method == "dpmsolver" else {}))
+        finally:
+            diffusion.denoise_fn = net
+            wrapped.end_condition_cache()
     ms, pan = scene["MS"], scene["PAN"]
     rows, cols = ms.shape[2] // tile, ms.shape[3] // tile
     tiles = {"MS": split_tiles(ms, tile, tile), "PAN": split_tiles(pan, tile, tile)}
