@@ -575,7 +575,11 @@ int tmdiff_tile_blend(const float* tiles, float* scene, int32_t B, int32_t C, in
  *             q/k/v/out are addressed as base + b*strides[0] + head*strides[1] + row*strides[2] + d (elements),
  *             which covers both the '(b h) n d' split of CrossAttention (:186) and the channel-major
  *             [B, C, HW] tensors of SpatialSelfAttention (:143-153, via a transposed view prepared by the caller).
- *             key_mask [B, Nk] bytes (1 = keep) or NULL; head dim D even, <= 128.
+ *             key_mask [B, Nk] bytes (1 = keep) or NULL; head dim D even, <= 128.  A masked key scores -FLT_MAX (the
+ *             reference's masked_fill, :203-204): a sample whose keys are all masked yields the mean of v over its Nk keys.
+ *  attn_ctx_queries_per_workgroup (host function): the queries one workgroup of the small-context kernel walks over
+ *             (128 per pass of its four waves) when attn_fwd is called with these extents, D == 64, Nk <= 96 and 16-byte
+ *             aligned q / out rows; 0 when the extents rule that kernel out.
  *  gemm_nt  : C[M,N] = A[M,K] W[N,K]^T + bias[N] + residual[M,N]   (nn.Linear on token-major activations)
  *  group_norm (:108-109, eps 1e-6, affine), layer_norm (:279-281), geglu / gelu (:69-76, :84-87).
  * ------------------------------------------------------------------------------------ */
@@ -583,6 +587,7 @@ int tmdiff_attn_fwd(const float* q, const float* k, const float* v, float* out, 
                     int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t D, const int64_t q_strides[3],
                     const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], float scale,
                     tmdiff_stream_t stream);
+int32_t tmdiff_attn_ctx_queries_per_workgroup(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t D);
 int tmdiff_gemm_nt(const float* A, const float* Wt, const float* bias, const float* residual, float* C, int64_t M,
                    int32_t N, int32_t K, tmdiff_stream_t stream);
 int tmdiff_group_norm(const float* x, const float* gamma, const float* beta, float* y, int32_t B, int32_t C,

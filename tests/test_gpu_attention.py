@@ -39,7 +39,8 @@ def test_primitives():
     assert_close(ops.geglu(cu(u), gelu_only=True).cpu(), F.gelu(u), 1e-6, 1e-6, "gelu")
     # (head dims 64 / 128 take the pipelined LDS-DMA kernel, the others the simple one: ragged Nq / Nk for both)
     # (... and d_head 64 with at most 96 keys -- the CLIP context -- the small-context kernel: K / V resident in LDS, single-pass
-    #  softmax; 77 / 80 keys (80 key rows in LDS), 96 and 81 (96 rows), one key tile, several query blocks per wave, ragged Nq)
+    #  softmax; 77 / 80 keys (80 key rows in LDS), 96 and 81 (96 rows), one key tile, ragged Nq.  Every shape here gives that
+    #  kernel 128 queries per workgroup, i.e. ONE query block per wave: several blocks per wave are test_gpu_attention_edges.py's)
     for b, h, nq, nk, d in ((2, 8, 256, 77, 16), (1, 4, 64, 64, 32), (2, 1, 200, 200, 64), (1, 2, 33, 5, 128), (2, 4, 300, 77, 64),
                             (1, 1, 1024, 1024, 128), (3, 2, 129, 97, 64), (1, 2, 1200, 80, 64), (2, 2, 130, 96, 64),
                             (1, 1, 64, 13, 64), (1, 8, 4096, 77, 64), (1, 3, 1000, 81, 64), (2, 1, 31, 33, 64)):

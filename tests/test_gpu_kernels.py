@@ -357,6 +357,10 @@ def test_per_operator_abi_names(ops):
     assert_close(out, c[0] * v[0] + c[1] * v[1] + c[2] * v[2], 1e-6, 1e-6, "axpby3")
     assert L.tmdiff_dpm_axpby4(p(v[0]), c[0], p(v[1]), c[1], p(v[2]), c[2], p(v[3]), c[3], p(out), 1000, S) == 0
     assert_close(out, c[0] * v[0] + c[1] * v[1] + c[2] * v[2] + c[3] * v[3], 1e-6, 1e-6, "axpby4")
+    # host function: the small-context attention kernel's queries per workgroup (0: that kernel is ruled out)
+    assert L.tmdiff_attn_ctx_queries_per_workgroup(1, 8, 4096, 77, 64) == 128
+    assert L.tmdiff_attn_ctx_queries_per_workgroup(32, 8, 4096, 77, 64) == 1024
+    assert L.tmdiff_attn_ctx_queries_per_workgroup(32, 8, 4096, 97, 64) == 0
 
 
 def _bf16_round(t):

@@ -29,6 +29,23 @@ def test_library_exports_every_declared_symbol():
     assert ctypes.sizeof(_lib.Conv3dDesc) % 8 == 0
 
 
+def test_attn_ctx_queries_per_workgroup():
+    """The host function the attention launcher sizes the small-context kernel's workgroups with: 128 queries (one block per
+    wave) doubling up to 1024 while the grid still fills the chip twice over; 0 where that kernel cannot run."""
+    from tmdiff_amd import _lib
+    qpw = _lib.lib.tmdiff_attn_ctx_queries_per_workgroup
+    assert qpw(1, 1, 1, 1, 64) == 128 and qpw(1, 8, 4096, 77, 64) == 128
+    assert qpw(16, 8, 2048, 77, 64) == 256 and qpw(32, 8, 2100, 96, 64) == 512
+    assert qpw(32, 8, 4096, 77, 64) == 1024 and qpw(64, 8, 100000, 96, 64) == 1024
+    for b, h, nq, nk, d in ((32, 8, 4096, 97, 64), (32, 8, 4096, 77, 32), (32, 8, 4096, 77, 128), (0, 8, 4096, 77, 64),
+                            (32, 0, 4096, 77, 64), (32, 8, 0, 77, 64), (32, 8, 4096, 0, 64), (8192, 8, 4096, 77, 64)):
+        assert qpw(b, h, nq, nk, d) == 0, (b, h, nq, nk, d)
+    # whatever the heuristic picks, a workgroup's share is a whole number of 128-query passes, 1024 queries at the most
+    for args in ((3, 5, 777, 77, 64), (64, 8, 1025, 77, 64), (1, 1, 5000, 96, 64), (7, 16, 130, 80, 64)):
+        v = qpw(*args)
+        assert v in (128, 256, 512, 1024), (args, v)
+
+
 def test_state_dict_contract_and_clip_keys_ignored():
     from tmdiff_amd.Hyper_unet_general import WavBEST
     from tmdiff_amd.diffusion_general import GeneralDiffusion, GaussianDiffusion

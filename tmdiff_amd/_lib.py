@@ -120,6 +120,7 @@ SIGNATURES = {
     "tmdiff_add": (C.c_int, [vp, vp, vp, C.c_int64, C.c_float, vp]),
     "tmdiff_attn_fwd": (C.c_int, [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_int64 * 3, C.c_int64 * 3, C.c_int64 * 3, C.c_int64 * 3, C.c_float, vp]),
+    "tmdiff_attn_ctx_queries_per_workgroup": (C.c_int32, [C.c_int32] * 5),
     "tmdiff_gemm_nt": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]),
     "tmdiff_group_norm": (C.c_int, [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, vp]),
     "tmdiff_layer_norm": (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_float, vp]),

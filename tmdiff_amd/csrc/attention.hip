@@ -32,6 +32,20 @@ struct AttnArgs {
   float scale;
 };
 
+// Key mask (online-softmax kernels).  A masked key keeps its place in the softmax with the score the reference gives it,
+// masked_fill(-finfo.max) (ref :203-204): next to any kept key it weighs exp(-huge) = 0, and a sample whose keys are ALL masked
+// gets equal weights, i.e. the mean of V over its Nk keys, as the reference and attn_ctx_kernel compute it.  The running max
+// therefore starts AT the fill value, so that exp(fill - max) is 1 in that case.  The slots of the last 32-key tile at or
+// beyond Nk are no keys at all, but carry the fill value too: their V rows are zero, so they never reach the accumulator, and
+// they add exp(fill - max) each to the running sum -- 0 unless the final max IS the fill value, where every slot has added
+// exactly 1 (and every rescale was by exp(0) = 1).  softmax_denominator puts Nk in the place of that count after the key
+// loop, which keeps the loop itself as it was.
+constexpr float kMaskFill = -3.4028234e38f;
+
+__device__ __forceinline__ float softmax_denominator(float m_run, float l_run, int Nk) {
+  return m_run == kMaskFill ? (float)Nk : l_run;
+}
+
 template <int DT>  // DT = ceil(D / 32): 32-row tiles of the transposed output accumulator
 __global__ void __launch_bounds__(256) attn_fwd_kernel(const AttnArgs a) {
   constexpr int DP = DT * 32;       // padded head dim
@@ -55,7 +69,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const AttnArgs a) {
   for (int t = 0; t < DT; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) oacc[t][r] = 0.f;
-  float m_run = -3.0e38f, l_run = 0.f;  // running max / sum of this lane's query (both half-waves keep a copy)
+  float m_run = kMaskFill, l_run = 0.f;  // running max / sum of this lane's query (both half-waves keep a copy)
   const float* qrow = qs + (wv * 32 + l31) * KS;
 
   for (int k0 = 0; k0 < a.Nk; k0 += 32) {
@@ -73,14 +87,14 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const AttnArgs a) {
     for (int r = 0; r < 16; ++r) s[r] = 0.f;
     const float* krow = ks + l31 * KS;
     for (int d = 0; d < DP; d += 2) s = __builtin_amdgcn_mfma_f32_32x32x2f32(krow[d + h], qrow[d + h], s, 0, 0, 0);
-    // mask keys past Nk (and masked keys); register r of half h is key (r&3) + 8(r>>2) + 4h
-    float mx = -3.0e38f;
+    // mask keys past Nk (and masked keys: kMaskFill above); register r of half h is key (r&3) + 8(r>>2) + 4h
+    float mx = kMaskFill;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * h;
       bool keep = key < a.Nk;
       if (keep && a.mask) keep = a.mask[(long)b * a.Nk + key] != 0;
-      s[r] = keep ? s[r] : -3.4028234e38f;   // masked_fill(-finfo.max), ref :203-204
+      s[r] = keep ? s[r] : kMaskFill;   // masked_fill(-finfo.max), ref :203-204
       mx = fmaxf(mx, s[r]);
     }
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
@@ -109,7 +123,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const AttnArgs a) {
   }
   // out[query, d] = O^T[d, query] / l; transpose through LDS (reuse the query buffer) for coalesced stores
   __syncthreads();
-  const float inv = 1.f / l_run;
+  const float inv = 1.f / softmax_denominator(m_run, l_run, a.Nk);
   float* ot = qs + wv * 32 * KS;
 #pragma unroll
   for (int t = 0; t < DT; ++t)
@@ -188,7 +202,7 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_dma_kernel(const AttnArgs a) 
   for (int t = 0; t < DT; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) oacc[t][r] = 0.f;
-  float m_run = -3.0e38f, l_run = 0.f;
+  float m_run = kMaskFill, l_run = 0.f;
 
   issue(0, lds);
   int it = 0;
@@ -203,13 +217,13 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_dma_kernel(const AttnArgs a) 
     const float* krow = ks + l31 * KS + h;
 #pragma unroll
     for (int j = 0; j < D / 2; ++j) s = __builtin_amdgcn_mfma_f32_32x32x2f32(krow[2 * j], qreg[j], s, 0, 0, 0);
-    float mx = -3.0e38f;
+    float mx = kMaskFill;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * h;
       bool keep = key < a.Nk;
       if (keep && a.mask) keep = a.mask[(long)b * a.Nk + key] != 0;
-      s[r] = keep ? s[r] : -3.4028234e38f;   // masked_fill(-finfo.max), ref :203-204
+      s[r] = keep ? s[r] : kMaskFill;   // masked_fill(-finfo.max), ref :203-204
       mx = fmaxf(mx, s[r]);
     }
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
@@ -237,7 +251,7 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_dma_kernel(const AttnArgs a) 
   }
   // out[query, d] = O^T[d, query] / l; transpose through LDS for coalesced stores
   __syncthreads();
-  const float inv = 1.f / l_run;
+  const float inv = 1.f / softmax_denominator(m_run, l_run, a.Nk);
   float* ot = lds + wv * 32 * KS;
 #pragma unroll
   for (int t = 0; t < DT; ++t)
@@ -495,7 +509,20 @@ __global__ void __launch_bounds__(256) geglu_kernel(const float* __restrict__ u,
   y[i] = a * (0.5f * gte * (1.f + erff(gte * 0.70710678118654752440f)));
 }
 
+// Queries per workgroup of attn_ctx_kernel: blocks of 128 (4 waves x 32); enough workgroups to fill the chip twice over, at
+// most 1024 queries each.  0: the extents rule the small-context kernel out (it holds d_head 64 and at most 96 keys).
+int attn_ctx_qpw(int B, int H, int Nq, int Nk, int D) {
+  if (B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0 || D != 64 || Nk > 96) return 0;
+  int qpw = 128;
+  while (qpw < 1024 && (long)((Nq + 2 * qpw - 1) / (2 * qpw)) * B * H >= 1024) qpw *= 2;
+  return qpw;
+}
+
 }  // namespace
+
+extern "C" int32_t tmdiff_attn_ctx_queries_per_workgroup(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t D) {
+  return (long)B * H <= 65535 ? attn_ctx_qpw(B, H, Nq, Nk, D) : 0;
+}
 
 extern "C" int tmdiff_attn_fwd(const float* q, const float* k, const float* v, float* out, const unsigned char* key_mask,
                                int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t D, const int64_t q_strides[3],
@@ -518,11 +545,9 @@ extern "C" int tmdiff_attn_fwd(const float* q, const float* k, const float* v, f
   static const bool no_ctx = env_flag("TMDIFF_ATTN_NO_CTX");   // experiments: never the small-context kernel
   // a short context (the 77 CLIP tokens) with d_head 64: K / V resident in LDS, single-pass softmax.  Needs 16-byte aligned
   // query / output rows (float4 row pieces).
-  if (!no_dma && !no_ctx && D == 64 && Nk <= 96 && a.q_rs % 4 == 0 && a.o_rs % 4 == 0 && a.q_bs % 4 == 0 && a.q_hs % 4 == 0 &&
+  const int qpw = attn_ctx_qpw(B, H, Nq, Nk, D);
+  if (!no_dma && !no_ctx && qpw > 0 && a.q_rs % 4 == 0 && a.o_rs % 4 == 0 && a.q_bs % 4 == 0 && a.q_hs % 4 == 0 &&
       a.o_bs % 4 == 0 && a.o_hs % 4 == 0 && aligned16(q) && aligned16(out)) {
-    // queries per workgroup: blocks of 128 (4 waves x 32); enough workgroups to fill the chip twice over, at most 1024 queries each
-    int qpw = 128;
-    while (qpw < 1024 && (long)((Nq + 2 * qpw - 1) / (2 * qpw)) * B * H >= 1024) qpw *= 2;
     dim3 g((Nq + qpw - 1) / qpw, B * H);
     if (Nk <= 80) attn_ctx_kernel<80><<<g, 256, 0, st>>>(a, qpw);
     else attn_ctx_kernel<96><<<g, 256, 0, st>>>(a, qpw);
@@ -545,8 +570,9 @@ extern "C" int tmdiff_attn_fwd(const float* q, const float* k, const float* v, f
 extern "C" int tmdiff_gemm_nt(const float* A, const float* Wt, const float* bias, const float* residual, float* Cm,
                               int64_t M, int32_t N, int32_t K, tmdiff_stream_t stream) {
   using namespace tmdiff;
-  TMDIFF_REQUIRE(A && Wt && Cm && M >= 0 && N > 0 && K > 0 && M < (1L << 31), "gemm_nt: bad arguments");
-  if (M == 0) return TMDIFF_OK;
+  TMDIFF_REQUIRE(M >= 0 && N > 0 && K > 0 && M < (1L << 31), "gemm_nt: bad arguments (M=%ld N=%d K=%d)", (long)M, N, K);
+  if (M == 0) return TMDIFF_OK;   // (an empty A / C has no storage: NULL is fine)
+  TMDIFF_REQUIRE(A && Wt && Cm, "gemm_nt: NULL pointer");
   dim3 grid((N + 63) / 64, (unsigned)((M + 63) / 64));
   gemm_nt_kernel<<<grid, 256, 0, as_stream(stream)>>>(A, Wt, bias, residual, Cm, (int)M, N, K);
   return check_launch("gemm_nt");
@@ -564,8 +590,9 @@ extern "C" int tmdiff_group_norm(const float* x, const float* gamma, const float
 extern "C" int tmdiff_layer_norm(const float* x, const float* gamma, const float* beta, float* y, int64_t rows,
                                  int32_t D, float eps, tmdiff_stream_t stream) {
   using namespace tmdiff;
-  TMDIFF_REQUIRE(x && gamma && beta && y && rows >= 0 && D > 0, "layer_norm: bad arguments");
-  if (rows == 0) return TMDIFF_OK;
+  TMDIFF_REQUIRE(rows >= 0 && D > 0, "layer_norm: bad arguments (rows=%ld D=%d)", (long)rows, D);
+  if (rows == 0) return TMDIFF_OK;   // (an empty x / y has no storage: NULL is fine)
+  TMDIFF_REQUIRE(x && gamma && beta && y, "layer_norm: NULL pointer");
   layer_norm_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, as_stream(stream)>>>(x, gamma, beta, y, rows, D, eps);
   return check_launch("layer_norm");
 }
@@ -573,8 +600,9 @@ extern "C" int tmdiff_layer_norm(const float* x, const float* gamma, const float
 extern "C" int tmdiff_geglu(const float* u, float* y, int64_t rows, int32_t inner, int32_t gelu_only,
                             tmdiff_stream_t stream) {
   using namespace tmdiff;
-  TMDIFF_REQUIRE(u && y && rows >= 0 && inner > 0, "geglu: bad arguments");
-  if (rows == 0) return TMDIFF_OK;
+  TMDIFF_REQUIRE(rows >= 0 && inner > 0, "geglu: bad arguments (rows=%ld inner=%d)", (long)rows, inner);
+  if (rows == 0) return TMDIFF_OK;   // (an empty u / y has no storage: NULL is fine)
+  TMDIFF_REQUIRE(u && y, "geglu: NULL pointer");
   const long n = rows * inner;
   geglu_kernel<<<(unsigned)((n + 255) / 256), 256, 0, as_stream(stream)>>>(u, y, rows, inner, gelu_only);
   return check_launch("geglu");

@@ -1203,9 +1203,9 @@ def attention(q, k, v, scale, heads=1, key_mask=None, layout="bnd"):
 def gemm_nt(a, w, bias=None, residual=None):
     """a [..., K] @ w[N, K]^T + bias + residual -> [..., N]"""
     k = a.shape[-1]
-    m = a.numel() // k
     n = w.shape[0]
     out = torch.empty(*a.shape[:-1], n, device=a.device, dtype=torch.float32)
+    m = out[..., 0].numel() if n else 0                    # rows: the leading dims folded (K = 0 / N = 0 are the library's to refuse)
     check(lib.tmdiff_gemm_nt(_chk(a, "a"), _chk(w, "w"), _chk(bias, "bias"), _chk(residual, "residual"),
                              out.data_ptr(), m, n, k, stream_ptr()), "gemm_nt")
     return out
