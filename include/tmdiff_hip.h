@@ -569,6 +569,37 @@ int tmdiff_tile_blend(const float* tiles, float* scene, int32_t B, int32_t C, in
                       int32_t overlap, tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Pansharpening quality metrics on the device (csrc/metrics.hip; definitions: tmdiff_amd/metrics.py, reference core/metrics.py).
+ * Inputs are fp32 [B, C, H, W] with dense rows and planes; the batch and channel strides (in elements) are arguments, so a
+ * channel or batch slice of a larger tensor is scored in place.  Outputs are fp64 [B, K] on the device, one row per image.
+ *  metrics_pair : x_pred against x_true.  K = 9 columns: psnr, sam (degrees), ssim (7 x 7 uniform window, K1 = 0.01, K2 = 0.03,
+ *    sample covariance, 'valid' region), ergas (per-band MSE over the squared mean of x_pred), rmse (bands summed, divided by
+ *    H * W), cc, scc (Pearson correlation of the 'valid' 3 x 3 Laplacians), q (universal quality index, ddof = 1), q4 (NaN unless
+ *    C == 4); psnr, ssim, cc, scc and q are means over the bands.  The spectral angle is formed per pixel in fp64 as
+ *    acos(dot / |pred| / |true|), a non-finite angle counting as 0; every other non-finite value is left as IEEE gives it.
+ *    A band that is constant in an image (least value == greatest value) has variance and covariance exactly 0 there, so
+ *    cc and scc are NaN for it (and q, when it is constant in both images), as a two-pass evaluation gives.
+ *  metrics_noref: d_lambda, d_s, qnr = (1 - d_lambda)(1 - d_s) of ps [B, C, H, W] and pan [B, 1, H, W] against l_ms
+ *    [B, C, h, w] and l_pan [B, 1, h, w]; the quality index with population moments and 1e-8 added to its denominator.
+ * All sums are fp64 and no atomics are used: the workgroups store partial sums into `workspace` and one finalize launch adds
+ * them in a fixed order (16 runs of consecutive tiles, then the runs), so a call is reproducible bit for bit.  Nothing is allocated, synchronised or copied to the host: a call
+ * can be captured into a graph on `stream`.  workspace: 8-byte aligned, tmdiff_metrics_workspace_bytes(B, C, H, W) bytes (H, W:
+ * the full-resolution extents), enough for either entry point.
+ * Extents: 1 <= C <= 16, H >= 7, W >= 7, B * C * H * W <= 2^31 - 1 (32-bit element offsets inside a plane); for anything else
+ * tmdiff_metrics_supported is 0, the workspace size is 0 and the entry points return TMDIFF_E_UNSUPPORTED without launching.
+ * ------------------------------------------------------------------------------------ */
+int tmdiff_metrics_supported(int32_t B, int32_t C, int32_t H, int32_t W);
+size_t tmdiff_metrics_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int tmdiff_metrics_pair(const float* x_true, int64_t true_stride_b, int64_t true_stride_c, const float* x_pred,
+                        int64_t pred_stride_b, int64_t pred_stride_c, int32_t B, int32_t C, int32_t H, int32_t W,
+                        double data_range, double ratio, double* out, void* workspace, size_t workspace_bytes,
+                        tmdiff_stream_t stream);
+int tmdiff_metrics_noref(const float* l_ms, int64_t l_ms_stride_b, int64_t l_ms_stride_c, const float* pan,
+                         int64_t pan_stride_b, const float* l_pan, int64_t l_pan_stride_b, const float* ps,
+                         int64_t ps_stride_b, int64_t ps_stride_c, int32_t B, int32_t C, int32_t H, int32_t W, int32_t h,
+                         int32_t w, double* out, void* workspace, size_t workspace_bytes, tmdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Standalone attention operators of core/Attention.py (imported by nothing in the reference; built because the
  * north star names them).  All fp32.
  *  attn_fwd : out = softmax(q k^T * scale [key mask]) v per (batch, head); fp32 MFMA, online softmax.

@@ -167,6 +167,13 @@ SIGNATURES.update({
     "tmdiff_tile_supported": (C.c_int, [C.c_int32] * 6),
     "tmdiff_tile_gather": (C.c_int, [vp, vp] + [C.c_int32] * 6 + [vp]),
     "tmdiff_tile_blend": (C.c_int, [vp, vp] + [C.c_int32] * 6 + [vp]),
+    # quality metrics (csrc/metrics.hip): tensors come with their batch / channel strides in elements
+    "tmdiff_metrics_supported": (C.c_int, [C.c_int32] * 4),
+    "tmdiff_metrics_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "tmdiff_metrics_pair": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64] + [C.c_int32] * 4 +
+                            [C.c_double, C.c_double, vp, vp, C.c_size_t, vp]),
+    "tmdiff_metrics_noref": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int64] +
+                             [C.c_int32] * 6 + [vp, vp, C.c_size_t, vp]),
 })
 
 

@@ -1,0 +1,463 @@
+// Pansharpening quality metrics on the device (gfx950): PSNR, SAM, SSIM, ERGAS, RMSE, CC, SCC, Q, Q4 of a prediction against a
+// target, and D_lambda, D_s, QNR without a target -- the definitions of tmdiff_amd/metrics.py (reference core/metrics.py:56-284,
+// :411-503), on fp32 [B, C, H, W] tensors whose batch and channel strides are arguments (rows and planes are dense).
+//
+//  metrics_pair_kernel   one workgroup per 16 x 64 tile of one image.  It walks the bands with the tile and a 3-pixel halo of both
+//                        images in LDS, and forms per band 12 sums: a, b, a^2, b^2, ab, (a-b)^2 over the tile's pixels; the SSIM
+//                        values of the 7 x 7 windows centred in the tile (window sums separably: rows first, through LDS); and
+//                        the five moments of the two 3 x 3 Laplacians centred in the tile; and the least and greatest value of
+//                        either image (a band is constant exactly when they agree).  The spectral sums of each pixel (dot,
+//                        |a|^2, |b|^2) stay in registers across the band loop and become one angle per pixel after it; with four
+//                        bands the pixel's eight values stay too and give the 4 x 4 cross products of Q4.
+//  metrics_gram_kernel   channel sums and the upper triangle of sum x_i x_j over a list of up to 17 channels in two segments.
+//  *_finalize_kernel     one workgroup per image: adds the workgroups' partial sums in a fixed order, evaluates the formulas.
+//
+// Every sum is fp64 (products of two fp32 values are exact there): at sensor scale (mean 1000, sigma 5) a variance is a 4e4-th
+// of the raw second moment, which fp32 sums would lose entirely.  No atomics: each workgroup stores its partial sums with plain
+// vector stores and the finalize kernel adds them in a fixed order, so a call is reproducible bit for bit.  Nothing is allocated,
+// copied to the host or synchronised here: the caller lends the workspace and the launches go to its stream.
+#include <algorithm>
+
+#include "common.h"
+
+namespace {
+
+constexpr int TH = 16, TW = 64, HALO = 3;            // tile owned by a workgroup; 256 lanes: lane (x, q) owns rows 4q .. 4q+3 of column x
+constexpr int LH = TH + 2 * HALO, LW = TW + 2 * HALO;
+constexpr int LS = 72;                               // LDS row stride of the staged tile (floats)
+constexpr int NSUM = 12, NBAND = 16;                 // per band: 12 sums, then min a, max a, min b, max b
+constexpr int FIN_T = 1024, FIN_W = FIN_T / 64;      // finalize: 16 waves, each adds a fixed run of the tiles
+constexpr int MAXC = 16, MAXG = 17;                  // bands of a pair; channels of a gram
+constexpr int PAIR_K = 9, NOREF_K = 3;               // output columns
+constexpr int GRAM_PIX = 256, GRAM_WG = 64;          // pixels per staged chunk; workgroups per image at most
+constexpr int MAXENT = MAXG + MAXG * (MAXG + 1) / 2; // 170
+
+__host__ __device__ inline int pair_np(int C) { return NBAND * C + 17; }   // + the angle sum + 16 cross products
+inline int tiles_of(int H, int W) { return ((H + TH - 1) / TH) * ((W + TW - 1) / TW); }
+inline int gram_wgs(long n) { return (int)std::min<long>((n + GRAM_PIX - 1) / GRAM_PIX, GRAM_WG); }
+__host__ __device__ inline int gram_entries(int ch) { return ch + ch * (ch + 1) / 2; }
+
+struct PairArgs {
+  const float* a;   // x_true
+  const float* b;   // x_pred
+  long asB, asC, bsB, bsC;
+  int C, H, W, tiles_x, tiles;
+  double c1, c2;
+  double* part;     // [B][tiles][pair_np(C)]
+};
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = fminf(v, __shfl_xor(v, m, 64));
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+  return v;
+}
+
+// sum over the workgroup of N values per lane -> red[w][k] holds wave w's sum (the caller syncs and adds the four in order)
+template <int N>
+__device__ __forceinline__ void waves_to_lds(const double (&v)[N], double (*red)[NBAND + 5], int lane, int wave) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const double s = wave_sum(v[k]);
+    if (lane == 0) red[wave][k] = s;
+  }
+}
+
+__global__ void __launch_bounds__(256) metrics_pair_kernel(PairArgs p) {
+  __shared__ float sa[LH][LS], sb[LH][LS];
+  __shared__ double hs[5][LH][TW];        // row sums over 7 columns of a, b, a^2, b^2, ab
+  __shared__ double red[4][NBAND + 5];    // per-wave sums (17 columns: the band's 12, or the angle + 16 cross products)
+
+  const int t = threadIdx.x, x = t & 63, q = t >> 6;
+  const int img = blockIdx.x / p.tiles, tile = blockIdx.x - img * p.tiles;
+  const int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
+  const int y0 = ty * TH, x0 = tx * TW;
+  const int H = p.H, W = p.W, C = p.C;
+  const int gx = x0 + x;
+  double* part = p.part + ((long)img * p.tiles + tile) * pair_np(C);
+
+  double dot[4] = {0, 0, 0, 0}, na[4] = {0, 0, 0, 0}, nb[4] = {0, 0, 0, 0};
+  float av[4][4], bv[4][4];               // [band][row]: kept for C == 4 only
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) av[k][r] = bv[k][r] = 0.f;
+
+  for (int c = 0; c < C; ++c) {
+    const float* pa = p.a + (long)img * p.asB + (long)c * p.asC;
+    const float* pb = p.b + (long)img * p.bsB + (long)c * p.bsC;
+    for (int i = t; i < LH * LW; i += 256) {
+      const int ly = i / LW, lx = i - ly * LW;
+      const int yy = y0 - HALO + ly, xx = x0 - HALO + lx;
+      const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
+      const int off = in ? yy * W + xx : 0;
+      const float va = pa[off], vb = pb[off];   // (0, 0) is always a valid element
+      sa[ly][lx] = in ? va : 0.f;
+      sb[ly][lx] = in ? vb : 0.f;
+    }
+    __syncthreads();
+
+    double s[NSUM];
+#pragma unroll
+    for (int k = 0; k < NSUM; ++k) s[k] = 0.0;
+    float lo_a = INFINITY, hi_a = -INFINITY, lo_b = INFINITY, hi_b = -INFINITY;
+    // point moments, the pixel's spectral sums, the Laplacians
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int ly = q * 4 + r + HALO, lx = x + HALO, gy = y0 + q * 4 + r;
+      if (gy < H && gx < W) {
+        const float fa = sa[ly][lx], fb = sb[ly][lx];
+        const double a = fa, b = fb, d = a - b;
+        s[0] += a; s[1] += b; s[2] += a * a; s[3] += b * b; s[4] += a * b; s[5] += d * d;
+        dot[r] += a * b; na[r] += a * a; nb[r] += b * b;
+        lo_a = fminf(lo_a, fa); hi_a = fmaxf(hi_a, fa); lo_b = fminf(lo_b, fb); hi_b = fmaxf(hi_b, fb);
+        if (C == 4) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (c == k) av[k][r] = fa, bv[k][r] = fb;
+        }
+        if (gy >= 1 && gy <= H - 2 && gx >= 1 && gx <= W - 2) {
+          double ba = 0.0, bb = 0.0;
+#pragma unroll
+          for (int i = -1; i <= 1; ++i)
+#pragma unroll
+            for (int j = -1; j <= 1; ++j) ba += (double)sa[ly + i][lx + j], bb += (double)sb[ly + i][lx + j];
+          const double la = 9.0 * a - ba, lb = 9.0 * b - bb;
+          s[7] += la; s[8] += lb; s[9] += la * la; s[10] += lb * lb; s[11] += la * lb;
+        }
+      }
+    }
+    // 7-column sums of every staged row
+    for (int i = t; i < LH * TW; i += 256) {
+      const int ly = i >> 6, cx = i & 63;
+      double h0 = 0, h1 = 0, h2 = 0, h3 = 0, h4 = 0;
+#pragma unroll
+      for (int j = 0; j < 7; ++j) {
+        const double a = sa[ly][cx + j], b = sb[ly][cx + j];
+        h0 += a; h1 += b; h2 += a * a; h3 += b * b; h4 += a * b;
+      }
+      hs[0][ly][cx] = h0; hs[1][ly][cx] = h1; hs[2][ly][cx] = h2; hs[3][ly][cx] = h3; hs[4][ly][cx] = h4;
+    }
+    __syncthreads();
+    // 7-row sums of those -> the window moments of the four window centres this lane owns
+    {
+      double w[5][4];
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        double v[10];
+#pragma unroll
+        for (int j = 0; j < 10; ++j) v[j] = hs[k][q * 4 + j][x];
+        const double mid = (v[3] + v[4]) + (v[5] + v[6]);
+        w[k][0] = ((v[0] + v[1]) + v[2]) + mid;
+        w[k][1] = ((v[1] + v[2]) + v[7]) + mid;
+        w[k][2] = ((v[2] + v[7]) + v[8]) + mid;
+        w[k][3] = ((v[7] + v[8]) + v[9]) + mid;
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int gy = y0 + q * 4 + r;
+        if (gy >= HALO && gy <= H - 1 - HALO && gx >= HALO && gx <= W - 1 - HALO) {
+          const double ux = w[0][r] / 49.0, uy = w[1][r] / 49.0;
+          const double cn = 49.0 / 48.0;                                  // sample covariance
+          const double vx = cn * (w[2][r] / 49.0 - ux * ux), vy = cn * (w[3][r] / 49.0 - uy * uy);
+          const double vxy = cn * (w[4][r] / 49.0 - ux * uy);
+          s[6] += ((2.0 * ux * uy + p.c1) * (2.0 * vxy + p.c2)) / ((ux * ux + uy * uy + p.c1) * (vx + vy + p.c2));
+        }
+      }
+    }
+    waves_to_lds<NSUM>(s, red, x, q);
+    {
+      const float m0 = wave_min(lo_a), m1 = wave_max(hi_a), m2 = wave_min(lo_b), m3 = wave_max(hi_b);
+      if (x == 0) red[q][NSUM] = m0, red[q][NSUM + 1] = m1, red[q][NSUM + 2] = m2, red[q][NSUM + 3] = m3;
+    }
+    __syncthreads();
+    if (t < NSUM) part[c * NBAND + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+    else if (t < NBAND) {
+      const bool least = ((t - NSUM) & 1) == 0;   // a wave without a pixel of the image holds +inf / -inf
+      const double u = least ? fmin(red[0][t], red[1][t]) : fmax(red[0][t], red[1][t]);
+      const double v = least ? fmin(red[2][t], red[3][t]) : fmax(red[2][t], red[3][t]);
+      part[c * NBAND + t] = least ? fmin(u, v) : fmax(u, v);
+    }
+  }
+
+  // the spectral angle of each pixel: dot / |pred| / |true|, then acos; a non-finite angle (a zero spectrum, a ratio that rounds
+  // above 1) counts as 0
+  double e[17];
+#pragma unroll
+  for (int k = 0; k < 17; ++k) e[k] = 0.0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int gy = y0 + q * 4 + r;
+    if (gy < H && gx < W) {
+      const double ang = acos(dot[r] / sqrt(nb[r]) / sqrt(na[r]));
+      e[0] += isfinite(ang) ? ang : 0.0;
+      if (C == 4) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) e[1 + i * 4 + j] += (double)av[i][r] * (double)bv[j][r];
+      }
+    }
+  }
+  __syncthreads();   // the last band's readers of `red` are done
+  waves_to_lds<17>(e, red, x, q);
+  __syncthreads();
+  if (t < 17) part[C * NBAND + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+}
+
+struct PairFinalArgs {
+  const double* part;
+  int C, H, W, tiles;
+  double data_range, ratio;
+  double* out;   // [B][PAIR_K]
+};
+
+// entry e of a tile's partial sums: 0 = a sum, 1 = a least value, 2 = a greatest value
+__device__ __forceinline__ int entry_kind(int e, int C) {
+  const int k = e % NBAND;
+  return e < C * NBAND && k >= NSUM ? 1 + ((k - NSUM) & 1) : 0;
+}
+__device__ __forceinline__ double combine(int kind, double u, double v) { return kind == 0 ? u + v : kind == 1 ? fmin(u, v) : fmax(u, v); }
+
+// Wave g adds tiles [g * run, (g + 1) * run) in index order, lane l the entries l, l + 64, ...; then the 16 runs are added in
+// order: the order depends on the number of tiles alone.
+__global__ void __launch_bounds__(FIN_T) metrics_pair_finalize_kernel(PairFinalArgs p) {
+  __shared__ double runs[FIN_W][NBAND * MAXC + 17];
+  __shared__ double tot[NBAND * MAXC + 17];
+  const int np = pair_np(p.C), img = blockIdx.x, lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int run = (p.tiles + FIN_W - 1) / FIN_W, i0 = g * run, i1 = min(i0 + run, p.tiles);
+  for (int e = lane; e < np; e += 64) {
+    const int kind = entry_kind(e, p.C);
+    const double* src = p.part + (long)img * p.tiles * np + e;
+    double s = kind == 0 ? 0.0 : kind == 1 ? (double)INFINITY : -(double)INFINITY;
+    for (int i = i0; i < i1; ++i) s = combine(kind, s, src[(long)i * np]);
+    runs[g][e] = s;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < np; e += FIN_T) {
+    const int kind = entry_kind(e, p.C);
+    double s = runs[0][e];
+    for (int k = 1; k < FIN_W; ++k) s = combine(kind, s, runs[k][e]);
+    tot[e] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const int C = p.C;
+  const double n = (double)p.H * (double)p.W, nwin = (double)(p.H - 6) * (double)(p.W - 6);
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  double psnr = 0, ssim = 0, erg = 0, sq = 0, cc = 0, scc = 0, qq = 0;
+  for (int c = 0; c < C; ++c) {
+    const double* s = tot + c * NBAND;
+    const double ma = s[0] / n, mb = s[1] / n, mse = s[5] / n;
+    psnr += 10.0 * log10(p.data_range * p.data_range / mse);
+    ssim += s[6] / nwin;
+    erg += mse / (mb * mb);
+    sq += s[5];
+    // centred second moments.  A constant band (least value == greatest value) has variance and covariance exactly 0, which the
+    // raw moments only give up to rounding (n v^2 is not exact for most v): they are set, so that such a band gives 0 / 0 = NaN
+    // as the two-pass host evaluation does.  (Its Laplacian is exactly 0 at every pixel, so lc below needs no such care.)
+    const bool const_a = s[12] == s[13], const_b = s[14] == s[15];
+    const double va = const_a ? 0.0 : s[2] - s[0] * ma, vb = const_b ? 0.0 : s[3] - s[1] * mb;
+    const double cov = (const_a || const_b) ? 0.0 : s[4] - s[0] * mb;
+    cc += cov / sqrt(va) / sqrt(vb);
+    const double d1 = va / (n - 1.0), d2 = vb / (n - 1.0);
+    qq += 4.0 * (cov / (n - 1.0)) * ma * mb / (d1 + d2) / (ma * ma + mb * mb);
+    const double nl = (double)(p.H - 2) * (double)(p.W - 2);
+    const double la = s[9] - s[7] * (s[7] / nl), lb = s[10] - s[8] * (s[8] / nl);
+    const double lc = s[11] - s[7] * (s[8] / nl);
+    scc += lc / sqrt(la) / sqrt(lb);
+  }
+  double* o = p.out + (long)img * PAIR_K;
+  o[0] = psnr / C;
+  o[1] = tot[C * NBAND] / n * 180.0 / 3.14159265358979323846;
+  o[2] = ssim / C;
+  o[3] = 100.0 * p.ratio * sqrt(erg / C);
+  o[4] = sqrt(sq / n);
+  o[5] = cc / C;
+  o[6] = scc / C;
+  o[7] = qq / C;
+  double q4 = nan;
+  if (C == 4) {
+    // the mean quaternion product of the centred prediction with the conjugate of the centred target (metrics._q4_from_moments)
+    const double* X = tot + C * NBAND + 1;   // X[i * 4 + j] = sum a_i b_j
+    double m1[4], m2[4], s1 = 0, s2 = 0, e1 = 0, e2 = 0, r[4][4];
+    for (int i = 0; i < 4; ++i) {
+      m2[i] = tot[i * NBAND] / n; m1[i] = tot[i * NBAND + 1] / n;
+      s2 += tot[i * NBAND + 2] / n - m2[i] * m2[i]; s1 += tot[i * NBAND + 3] / n - m1[i] * m1[i];
+      e1 += m1[i] * m1[i]; e2 += m2[i] * m2[i];
+    }
+    for (int i = 0; i < 4; ++i)
+      for (int j = 0; j < 4; ++j) r[i][j] = (X[j * 4 + i] / n - m1[i] * m2[j]) * (j == 0 ? 1.0 : -1.0);
+    const double c0 = r[0][0] - r[1][1] - r[2][2] - r[3][3], c1 = r[0][1] + r[1][0] + r[2][3] - r[3][2];
+    const double c2 = r[0][2] - r[1][3] + r[2][0] + r[3][1], c3 = r[0][3] + r[1][2] - r[2][1] + r[3][0];
+    q4 = 4.0 * sqrt(e1 * e2 * (c0 * c0 + c1 * c1 + c2 * c2 + c3 * c3)) / (s1 + s2) / (e1 + e2);
+  }
+  o[8] = q4;
+}
+
+struct GramArgs {
+  const float* x0;   // c0 channels
+  const float* x1;   // c1 channels (may be 0)
+  long s0B, s0C, s1B, s1C;
+  int c0, c1, n, wgs;   // n = H * W pixels per image
+  double* part;         // [B][wgs][gram_entries(c0 + c1)]: the channel sums, then the rows of the upper triangle
+};
+
+__global__ void __launch_bounds__(256) metrics_gram_kernel(GramArgs p) {
+  __shared__ float xs[GRAM_PIX][MAXG];
+  __shared__ double red[256];
+  const int t = threadIdx.x, ch = p.c0 + p.c1, nent = gram_entries(ch), ng = 256 / nent;
+  const int img = blockIdx.x / p.wgs, wg = blockIdx.x - img * p.wgs;
+  const int e = t % nent, g = t / nent;
+  int ei = e, ej = -1;                       // entry e: the sum of channel ei (ej < 0) or of x_ei x_ej
+  if (e >= ch) {
+    int k = e - ch;
+    ei = 0;
+    while (k >= ch - ei) k -= ch - ei, ++ei;
+    ej = ei + k;
+  }
+  double acc = 0.0;
+  const int chunks = (p.n + GRAM_PIX - 1) / GRAM_PIX;
+  for (int chunk = wg; chunk < chunks; chunk += p.wgs) {
+    const int px = chunk * GRAM_PIX + t, cnt = min(GRAM_PIX, p.n - chunk * GRAM_PIX);
+    __syncthreads();
+    for (int c = 0; c < ch; ++c) {
+      const float* src = c < p.c0 ? p.x0 + (long)img * p.s0B + (long)c * p.s0C : p.x1 + (long)img * p.s1B + (long)(c - p.c0) * p.s1C;
+      xs[t][c] = t < cnt ? src[px] : 0.f;
+    }
+    __syncthreads();
+    if (g < ng)
+      for (int i = g; i < cnt; i += ng) acc += ej < 0 ? (double)xs[i][ei] : (double)xs[i][ei] * (double)xs[i][ej];
+  }
+  red[t] = acc;
+  __syncthreads();
+  if (t < nent) {
+    double s = 0.0;
+    for (int k = 0; k < ng; ++k) s += red[k * nent + t];
+    p.part[((long)img * p.wgs + wg) * nent + t] = s;
+  }
+}
+
+struct NorefFinalArgs {
+  const double* hi;   // gram partials of (ps, pan) over H x W
+  const double* lo;   // ... of (l_ms, l_pan) over h x w
+  int C, wgs_hi, wgs_lo;
+  double n_hi, n_lo;
+  double* out;        // [B][NOREF_K]
+};
+
+// QIndex of channels i < j from the totals: population moments, eps = 1e-8 in the denominator (core/metrics.py:442-461)
+__device__ double q_pop(const double* tot, int ch, double n, int i, int j) {
+  auto g = [&](int a, int b) { return tot[ch + a * ch - a * (a - 1) / 2 + (b - a)]; };
+  const double ea = tot[i] / n, eb = tot[j] / n;
+  const double va = g(i, i) / n - ea * ea, vb = g(j, j) / n - eb * eb, cab = g(i, j) / n - ea * eb;
+  return 4.0 * cab * ea * eb / ((va + vb) * (ea * ea + eb * eb) + 1e-8);
+}
+
+__global__ void __launch_bounds__(256) metrics_noref_finalize_kernel(NorefFinalArgs p) {
+  __shared__ double tot[2][MAXENT];
+  const int ch = p.C + 1, nent = gram_entries(ch), img = blockIdx.x;
+  for (int e = threadIdx.x; e < 2 * nent; e += 256) {
+    const int which = e / nent, k = e - which * nent, wgs = which ? p.wgs_lo : p.wgs_hi;
+    const double* src = (which ? p.lo : p.hi) + (long)img * wgs * nent + k;
+    double s = 0.0;
+    for (int i = 0; i < wgs; ++i) s += src[(long)i * nent];
+    tot[which][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const int L = p.C;
+  double dl = 0.0, ds = 0.0;
+  for (int i = 0; i < L; ++i) {
+    for (int j = i + 1; j < L; ++j) dl += 2.0 * fabs(q_pop(tot[0], ch, p.n_hi, i, j) - q_pop(tot[1], ch, p.n_lo, i, j));
+    ds += fabs(q_pop(tot[0], ch, p.n_hi, i, L) - q_pop(tot[1], ch, p.n_lo, i, L));
+  }
+  dl = dl / L / (double)(L - 1);   // one band: 0 / 0
+  ds = ds / L;
+  double* o = p.out + (long)img * NOREF_K;
+  o[0] = dl; o[1] = ds; o[2] = (1.0 - dl) * (1.0 - ds);
+}
+
+bool extents_ok(int B, int C, int H, int W) {
+  return B >= 0 && C >= 1 && C <= MAXC && H >= 7 && W >= 7 && (double)B * C * H * W <= 2147483647.0;
+}
+
+size_t pair_bytes(int B, int C, int H, int W) { return (size_t)B * tiles_of(H, W) * pair_np(C) * sizeof(double); }
+size_t noref_bytes(int B, int C) { return (size_t)B * 2 * GRAM_WG * gram_entries(C + 1) * sizeof(double); }
+
+}  // namespace
+
+extern "C" {
+
+int tmdiff_metrics_supported(int32_t B, int32_t C, int32_t H, int32_t W) {
+  return extents_ok(B, C, H, W);   // a predicate: it leaves the last-error string alone
+}
+
+size_t tmdiff_metrics_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
+  if (!extents_ok(B, C, H, W)) return 0;
+  return std::max(pair_bytes(B, C, H, W), noref_bytes(B, C));
+}
+
+int tmdiff_metrics_pair(const float* x_true, int64_t true_stride_b, int64_t true_stride_c, const float* x_pred, int64_t pred_stride_b,
+                        int64_t pred_stride_c, int32_t B, int32_t C, int32_t H, int32_t W, double data_range, double ratio, double* out,
+                        void* workspace, size_t workspace_bytes, tmdiff_stream_t stream) {
+  if (!extents_ok(B, C, H, W))
+    return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "metrics_pair: B=%d C=%d H=%d W=%d (1 <= C <= 16, H, W >= 7, fewer than 2^31 elements)", B, C,
+                        H, W);
+  if (B == 0) return TMDIFF_OK;
+  TMDIFF_REQUIRE(x_true && x_pred && out && workspace, "metrics_pair: null tensor");
+  TMDIFF_REQUIRE(true_stride_b >= 0 && true_stride_c >= (int64_t)H * W && pred_stride_b >= 0 && pred_stride_c >= (int64_t)H * W,
+                 "metrics_pair: channel strides below a plane of %d x %d", H, W);
+  TMDIFF_REQUIRE(workspace_bytes >= pair_bytes(B, C, H, W) && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0,
+                 "metrics_pair: workspace of %zu bytes, %zu needed (8-byte aligned)", workspace_bytes, pair_bytes(B, C, H, W));
+  const hipStream_t st = tmdiff::as_stream(stream);
+  const int tiles_x = (W + TW - 1) / TW, tiles = tiles_of(H, W);
+  const long blocks = (long)B * tiles;
+  if (blocks > 0x7fffffffL) return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "metrics_pair: grid of %ld blocks", blocks);
+  const PairArgs a{x_true, x_pred, true_stride_b, true_stride_c, pred_stride_b, pred_stride_c, C, H, W, tiles_x, tiles,
+                   (0.01 * data_range) * (0.01 * data_range), (0.03 * data_range) * (0.03 * data_range), static_cast<double*>(workspace)};
+  metrics_pair_kernel<<<(unsigned)blocks, 256, 0, st>>>(a);
+  if (const int rc = tmdiff::check_launch("metrics_pair")) return rc;
+  const PairFinalArgs f{a.part, C, H, W, tiles, data_range, ratio, out};
+  metrics_pair_finalize_kernel<<<B, FIN_T, 0, st>>>(f);
+  return tmdiff::check_launch("metrics_pair (finalize)");
+}
+
+int tmdiff_metrics_noref(const float* l_ms, int64_t l_ms_stride_b, int64_t l_ms_stride_c, const float* pan, int64_t pan_stride_b,
+                         const float* l_pan, int64_t l_pan_stride_b, const float* ps, int64_t ps_stride_b, int64_t ps_stride_c, int32_t B,
+                         int32_t C, int32_t H, int32_t W, int32_t h, int32_t w, double* out, void* workspace, size_t workspace_bytes,
+                         tmdiff_stream_t stream) {
+  if (!extents_ok(B, C, H, W) || h < 1 || w < 1 || (double)B * C * h * w > 2147483647.0)
+    return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "metrics_noref: B=%d C=%d H=%d W=%d h=%d w=%d (1 <= C <= 16, H, W >= 7, h, w >= 1, fewer than "
+                        "2^31 elements)", B, C, H, W, h, w);
+  if (B == 0) return TMDIFF_OK;
+  TMDIFF_REQUIRE(l_ms && pan && l_pan && ps && out && workspace, "metrics_noref: null tensor");
+  TMDIFF_REQUIRE(ps_stride_b >= 0 && pan_stride_b >= 0 && l_ms_stride_b >= 0 && l_pan_stride_b >= 0 && ps_stride_c >= (int64_t)H * W &&
+                     l_ms_stride_c >= (int64_t)h * w, "metrics_noref: channel strides below a plane");
+  TMDIFF_REQUIRE(workspace_bytes >= noref_bytes(B, C) && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0,
+                 "metrics_noref: workspace of %zu bytes, %zu needed (8-byte aligned)", workspace_bytes, noref_bytes(B, C));
+  const hipStream_t st = tmdiff::as_stream(stream);
+  const int nent = gram_entries(C + 1);
+  double* hi = static_cast<double*>(workspace);
+  const GramArgs gh{ps, pan, ps_stride_b, ps_stride_c, pan_stride_b, 0, C, 1, H * W, gram_wgs((long)H * W), hi};
+  double* lo = hi + (size_t)B * gh.wgs * nent;
+  const GramArgs gl{l_ms, l_pan, l_ms_stride_b, l_ms_stride_c, l_pan_stride_b, 0, C, 1, h * w, gram_wgs((long)h * w), lo};
+  metrics_gram_kernel<<<(unsigned)(B * gh.wgs), 256, 0, st>>>(gh);
+  if (const int rc = tmdiff::check_launch("metrics_noref (gram of ps, pan)")) return rc;
+  metrics_gram_kernel<<<(unsigned)(B * gl.wgs), 256, 0, st>>>(gl);
+  if (const int rc = tmdiff::check_launch("metrics_noref (gram of l_ms, l_pan)")) return rc;
+  const NorefFinalArgs f{hi, lo, C, gh.wgs, gl.wgs, (double)H * W, (double)h * w, out};
+  metrics_noref_finalize_kernel<<<B, 256, 0, st>>>(f);
+  return tmdiff::check_launch("metrics_noref (finalize)");
+}
+
+}  // extern "C"

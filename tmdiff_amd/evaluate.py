@@ -20,14 +20,28 @@ def to_hwc01(img, min_max=(0.0, 1.0)):
     return np.transpose((data - lo) / (hi - lo), (1, 2, 0))
 
 
-def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=print):
+def _to_nchw01(img, min_max=(0.0, 1.0)):
+    """The clamp and rescale of ``to_hwc01`` on the device: [1,C,H,W] or [C,H,W] tensor -> float32 [1,C,H,W] on the GPU."""
+    lo, hi = min_max
+    t = img.detach().float()
+    t = t if t.is_cuda else t.cuda()
+    t = t.reshape(1, *t.shape[-3:])
+    return ((t.clamp(lo, hi) - lo) / (hi - lo)).contiguous()
+
+
+def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=print, device_metrics=False):
     """``trainer`` is a ``tmdiff_amd.model.DDPM`` (or the reference's); ``dataset`` is the prompt name.
-    Returns ``{"ssim_<dataset>": ..., "sam_<dataset>": ..., "sec_per_item": ...}``."""
+    Returns ``{"ssim_<dataset>": ..., "sam_<dataset>": ..., "sec_per_item": ...}``.
+
+    ``device_metrics=True`` scores on the GPU instead (``ops.metrics_pair``: one pass per item over the two images, sums kept
+    on the device, one synchronising read of the scores after the last item) and adds ``psnr_``, ``ergas_``, ``scc_``, ``cc_``
+    and ``q_<dataset>``.  The ``.mat`` files are the same in both modes (writing them is what still brings SR to the host)."""
     result_path = os.path.join(result_root, dataset)
     os.makedirs(result_path, exist_ok=True)
     scale = IMG_SCALE.get(dataset, 2047.0)
     ssim_sum = sam_sum = 0.0
     n = 0
+    dev_sum, dev_ws = None, {}
     t0 = time.time()
     for idx, val_data in enumerate(val_loader):
         trainer.feed_data(val_data)
@@ -35,12 +49,24 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
         vis = trainer.get_current_visuals()
         sr = to_hwc01(vis["SR"][-1])                       # last image of the returned stack (ref :136)
         scio.savemat(os.path.join(result_path, f"output_mulExm_{idx}.mat"), {"sr": sr * scale})
-        if "HR" in vis:
+        if "HR" in vis and device_metrics:
+            from . import ops
+            hr_d, sr_d = _to_nchw01(vis["HR"]), _to_nchw01(vis["SR"][-1])
+            if hr_d.shape not in dev_ws:
+                dev_ws[hr_d.shape] = ops.metrics_workspace(*hr_d.shape, hr_d.device)
+            row = ops.metrics_pair(hr_d, sr_d, 1.0, workspace=dev_ws[hr_d.shape])[0]
+            dev_sum = row if dev_sum is None else dev_sum + row
+        elif "HR" in vis:
             hr = to_hwc01(vis["HR"])
             ssim_sum += metrics.ssim(hr, sr, 1)
             sam_sum += metrics.sam(hr, sr)
         n += 1
+    extra = {}
+    if dev_sum is not None:
+        total = dict(zip(metrics.PAIR_FIELDS, dev_sum.tolist()))                     # the one synchronising read
+        ssim_sum, sam_sum = total["ssim"], total["sam"]
+        extra = {f"{k}_{dataset}": total[k] / max(n, 1) for k in ("psnr", "ergas", "scc", "cc", "q")}
     score = {f"ssim_{dataset}": ssim_sum / max(n, 1), f"sam_{dataset}": sam_sum / max(n, 1),
-             "sec_per_item": (time.time() - t0) / max(n, 1)}
+             "sec_per_item": (time.time() - t0) / max(n, 1), **extra}
     log(dataset, score)
     return score

@@ -1073,6 +1073,74 @@ def tile_blend(tiles, batch, h, w, overlap, out=None):
     return y
 
 
+# ---- quality metrics (csrc/metrics.hip; definitions and column order: tmdiff_amd/metrics.py) -------------------------
+def metrics_supported(b, c, h, w):
+    """True when metrics_pair / metrics_noref take a [b, c, h, w] image batch: 1 <= c <= 16, h, w >= 7, 32-bit offsets."""
+    return bool(lib.tmdiff_metrics_supported(int(b), int(c), int(h), int(w)))
+
+
+def metrics_workspace(b, c, h, w, device):
+    """A workspace either metrics entry point accepts for [b, c, h, w] images (reusable; captured calls must keep it alive)."""
+    return torch.empty(max(1, lib.tmdiff_metrics_workspace_bytes(b, c, h, w) // 8), device=device, dtype=torch.float64)
+
+
+def _planes(t, name, c=None):
+    """(pointer, batch stride, channel stride) of a float32 GPU tensor [B, C, H, W] whose rows and planes are dense."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4):
+        raise ValueError(f"{name}: need a float32 [B, C, H, W] tensor on the GPU")
+    _, ch, h, w = t.shape
+    sb, sc, sh, sw = t.stride()
+    if c is not None and ch != c:
+        raise ValueError(f"{name}: {ch} channels, need {c}")
+    if (w > 1 and sw != 1) or (h > 1 and sh != w) or (ch > 1 and sc < h * w):
+        raise ValueError(f"{name}: rows and planes must be dense (strides {t.stride()} for shape {tuple(t.shape)})")
+    return t.data_ptr(), (sb if t.shape[0] > 1 else 0), (sc if ch > 1 else h * w)
+
+
+def _metrics_buffers(name, k, b, c, h, w, device, out, workspace):
+    if not metrics_supported(b, c, h, w):
+        raise ValueError(f"{name}: B={b} C={c} H={h} W={w} is not supported (1 <= C <= 16, H, W >= 7, fewer than 2^31 elements)")
+    y = out if out is not None else torch.empty(b, k, device=device, dtype=torch.float64)
+    if not (y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and tuple(y.shape) == (b, k)):
+        raise ValueError(f"{name}: out must be a contiguous float64 [{b}, {k}] tensor on the GPU")
+    ws = workspace if workspace is not None else metrics_workspace(b, c, h, w, device)
+    nbytes = ws.numel() * ws.element_size()
+    if not (ws.is_cuda and ws.is_contiguous() and nbytes >= lib.tmdiff_metrics_workspace_bytes(b, c, h, w)):
+        raise ValueError(f"{name}: workspace of {nbytes} bytes, need {lib.tmdiff_metrics_workspace_bytes(b, c, h, w)}")
+    return y, ws, nbytes
+
+
+def metrics_pair(x_true, x_pred, data_range=1.0, ratio=0.25, out=None, workspace=None):
+    """x_pred against x_true, both float32 [B, C, H, W]: float64 [B, 9] in the column order of metrics.PAIR_FIELDS."""
+    if x_true.shape != x_pred.shape:
+        raise ValueError(f"metrics_pair: shapes {tuple(x_true.shape)} and {tuple(x_pred.shape)} differ")
+    pa, asb, asc = _planes(x_true, "x_true")
+    pb, bsb, bsc = _planes(x_pred, "x_pred")
+    b, c, h, w = x_true.shape
+    y, ws, nbytes = _metrics_buffers("metrics_pair", 9, b, c, h, w, x_true.device, out, workspace)
+    check(lib.tmdiff_metrics_pair(pa, asb, asc, pb, bsb, bsc, b, c, h, w, float(data_range), float(ratio), y.data_ptr(),
+                                  ws.data_ptr(), nbytes, stream_ptr()), "metrics_pair")
+    return y
+
+
+def metrics_noref(l_ms, pan, l_pan, ps, out=None, workspace=None):
+    """Full-resolution set of ps [B, C, H, W] and pan [B, 1, H, W] against l_ms [B, C, h, w] and l_pan [B, 1, h, w]: float64
+    [B, 3] in the column order of metrics.NOREF_FIELDS."""
+    pp, psb, psc = _planes(ps, "ps")
+    b, c, h, w = ps.shape
+    pl, lsb, lsc = _planes(l_ms, "l_ms", c)
+    lh, lw = l_ms.shape[2:]
+    pn, nsb, _ = _planes(pan, "pan", 1)
+    pq, qsb, _ = _planes(l_pan, "l_pan", 1)
+    if tuple(pan.shape) != (b, 1, h, w) or tuple(l_pan.shape) != (b, 1, lh, lw) or l_ms.shape[0] != b or lh < 1 or lw < 1:
+        raise ValueError(f"metrics_noref: ps {tuple(ps.shape)}, pan {tuple(pan.shape)}, l_ms {tuple(l_ms.shape)}, "
+                         f"l_pan {tuple(l_pan.shape)} do not belong together")
+    y, ws, nbytes = _metrics_buffers("metrics_noref", 3, b, c, h, w, ps.device, out, workspace)
+    check(lib.tmdiff_metrics_noref(pl, lsb, lsc, pn, nsb, pq, qsb, pp, psb, psc, b, c, h, w, lh, lw, y.data_ptr(), ws.data_ptr(),
+                                   nbytes, stream_ptr()), "metrics_noref")
+    return y
+
+
 # ---- backward-side wrappers (finetune path) -----------------------------------------------------------
 
 
