@@ -393,7 +393,10 @@ int tmdiff_head_fwd(const float* x, const float* w, const float* scale, int32_t 
 /* stem backward: with u = w[co]*x + bias[co], y = SiLU(u): dwb[b, co, 0] = sum_p gy*SiLU'(u)*x and
  * dwb[b, co, 1] = sum_p gy*SiLU'(u) (per-sample partials [B, Cout, 2]; the caller sums over b).
  * head backward: dx[b,c,p] = gy[b,p]*w[c]*scale[b,c]*SiLU'(x); dws[b,c] = sum_p gy[b,p]*SiLU(x[b,c,p])
- * (dL/d(w[c]*scale[b,c])); scale rows dense [B,C] or NULL (= 1). */
+ * (dL/d(w[c]*scale[b,c])); scale rows dense [B,C] or NULL (= 1).
+ * B == 0 is a no-op for every stem / head / linear entry point, forward and backward: nothing is read or written and the
+ * per-sample pointers may be NULL (an empty tensor has no storage).  The sums over no samples are the caller's to zero
+ * (dw / db of tmdiff_linear_bwd; dwb and dws have no rows). */
 int tmdiff_stem_bwd(const float* xin, const float* pan, const float* ms, const float* w, const float* bias,
                     const float* gy, float* dwb, int32_t B, int32_t Cout, int32_t N, int32_t H, int32_t W,
                     tmdiff_stream_t stream);
@@ -416,8 +419,8 @@ int tmdiff_head_bwd(const float* x, const float* w, const float* scale, const fl
  *        high bands (the two iwt calls with 2*h and 2*x at :383-386 are one launch).  The high
  *        bands may be channel slices of one [B, 3C, N, h, w] tensor (the convH_0 output, :381-384):
  *        hi_planes_per_batch = C*N planes per sample, hi_batch_stride = floats between samples
- *        (0 = dense [planes, h, w] bands).  lh/hl/hh may all be NULL = zero high bands (the adjoint of an
- *        LL-only dwt).
+ *        (0 = dense [planes, h, w] bands; a stride that is no multiple of 4 floats is served by the 4-byte
+ *        kernel).  lh/hl/hh may all be NULL = zero high bands (the adjoint of an LL-only dwt).
  * The adjoint of dwt is idwt and vice versa (orthonormal transform), which is how the
  * backward passes are served.
  * ------------------------------------------------------------------------------------ */
@@ -440,7 +443,9 @@ int tmdiff_haar_idwt2d_pro(const float* const ll[2], int32_t n_ll, const float* 
                            tmdiff_stream_t stream);
 /* bf16-mode producers: the LL band / first reconstruction (x, ll0, ll1: [B, C, N, ., .] fp32; stacked_bands [B, 3C, N, h, w])
  * written as the packed bf16 units [B][C/8][N*h*w] of 8 channels (16 bytes) that tmdiff_conv3d_fwd_bf16 reads with x_bf16 = 1,
- * prologue applied in fp32 and rounded to nearest even exactly as that entry point's own pack pass does.  C % 8 == 0. */
+ * prologue applied in fp32 and rounded to nearest even exactly as that entry point's own pack pass does.  C % 8 == 0.
+ * The kernels move fp32 pairs as 8 bytes: x (dwt) and out1 (idwt) must be 8-byte aligned, the units 16-byte aligned; any other
+ * base is TMDIFF_E_INVALID without a launch ("... must be 8-byte aligned" in tmdiff_last_error_string()). */
 int tmdiff_haar_dwt2d_pack_bf16(const float* x, void* ll_units, float* lh, float* hl, float* hh, int32_t B, int32_t C,
                                 int32_t N, int32_t H, int32_t W, float ll_scale, float hi_scale,
                                 const tmdiff_plane_prologue* ll_prologue, tmdiff_stream_t stream);
@@ -467,7 +472,7 @@ int tmdiff_gamma_embedding(const float* t, const float* freqs, float* emb, int32
                            tmdiff_stream_t stream);
 /* backward of y = act(x @ w^T + bias): gu = gy * act'(u) with the pre-activation u recomputed into gu_scratch
  * [B, O] (only needed when act != 0); dx[b,i] = sum_o gu[b,o] w[o,i]; dw[o,i] = sum_b gu[b,o] x[b,i];
- * db[o] = sum_b gu[b,o].  Any of dx / dw / db may be NULL. */
+ * db[o] = sum_b gu[b,o].  Any of dx / dw / db may be NULL.  B == 0: a no-op (dw / db are NOT zeroed; see above). */
 int tmdiff_linear_bwd(const float* x, const float* w, const float* bias, const float* gy, float* gu_scratch,
                       float* dx, float* dw, float* db, int32_t B, int32_t I, int32_t O, int32_t act,
                       tmdiff_stream_t stream);

@@ -803,7 +803,7 @@ extern "C" int tmdiff_conv3d_wgrad_bias(const tmdiff_conv3d_desc* d, const float
 extern "C" int tmdiff_channel_sum(const float* x, float* out, int32_t B, int32_t C, int64_t P, float scale,
                                   tmdiff_stream_t stream) {
   using namespace tmdiff;
-  TMDIFF_REQUIRE(x && out && B >= 0 && C > 0 && P > 0, "channel_sum: bad arguments");
+  TMDIFF_REQUIRE((x || B == 0) && out && B >= 0 && C > 0 && P > 0, "channel_sum: bad arguments");   // B == 0: out = 0
   // ~2048 workgroups in total, at least 2048 elements per slice and sample
   long slices = (2048 + C - 1) / C;
   if (slices > (P + 2047) / 2048) slices = (P + 2047) / 2048;
@@ -905,9 +905,10 @@ extern "C" int tmdiff_stem_bwd(const float* xin, const float* pan, const float* 
                                const float* gy, float* dwb, int32_t B, int32_t Cout, int32_t N, int32_t H, int32_t W,
                                tmdiff_stream_t stream) {
   using namespace tmdiff;
+  TMDIFF_REQUIRE(B >= 0 && B <= 65535 && Cout > 0 && N > 0 && H > 0 && W > 0, "stem_bwd: bad extents");
+  if (B == 0) return TMDIFF_OK;   // no samples, no partials (an empty tensor has no storage: NULL is fine)
   TMDIFF_REQUIRE(w && gy && dwb, "stem_bwd: NULL pointer");
   TMDIFF_REQUIRE((ms && pan) || (!ms && xin), "stem_bwd: give either (pan, ms) or xin");
-  TMDIFF_REQUIRE(B > 0 && B <= 65535 && Cout > 0 && N > 0 && H > 0 && W > 0, "stem_bwd: bad extents");
   const long HW = (long)H * W;
   stem_bwd_kernel<<<dim3(Cout, B), 256, 0, as_stream(stream)>>>(xin, pan, ms, w, bias, gy, dwb, Cout, HW * N, HW);
   return check_launch("stem_bwd");
@@ -917,10 +918,11 @@ extern "C" int tmdiff_stem_bwd_input(const float* xin, const float* pan, const f
                                      const float* bias, const float* gy, float* dx, float* dpan, int32_t B, int32_t Cout,
                                      int32_t N, int32_t H, int32_t W, tmdiff_stream_t stream) {
   using namespace tmdiff;
+  TMDIFF_REQUIRE(B >= 0 && B <= 65535 && Cout > 0 && N > 0 && H > 0 && W > 0, "stem_bwd_input: bad extents");
+  if (B == 0) return TMDIFF_OK;
   TMDIFF_REQUIRE(w && gy && (dx || dpan), "stem_bwd_input: NULL pointer");
   TMDIFF_REQUIRE((ms && pan) || (!ms && xin), "stem_bwd_input: give either (pan, ms) or xin");
   TMDIFF_REQUIRE(ms || !dpan, "stem_bwd_input: d_pan only exists in the (pan, ms) form");
-  TMDIFF_REQUIRE(B > 0 && B <= 65535 && Cout > 0 && N > 0 && H > 0 && W > 0, "stem_bwd_input: bad extents");
   const long HW = (long)H * W;
   stem_bwd_input_kernel<<<dim3((unsigned)((HW + 255) / 256), B), 256, 0, as_stream(stream)>>>(xin, pan, ms, w, bias, gy, dx,
                                                                                             dpan, Cout, N, HW);
@@ -930,8 +932,9 @@ extern "C" int tmdiff_stem_bwd_input(const float* xin, const float* pan, const f
 extern "C" int tmdiff_head_bwd(const float* x, const float* w, const float* scale, const float* gy, float* dx,
                                float* dws, int32_t B, int32_t C, int64_t P, tmdiff_stream_t stream) {
   using namespace tmdiff;
+  TMDIFF_REQUIRE(B >= 0 && B <= 65535 && C > 0 && P > 0, "head_bwd: bad extents");
+  if (B == 0) return TMDIFF_OK;
   TMDIFF_REQUIRE(x && w && gy, "head_bwd: NULL pointer");
-  TMDIFF_REQUIRE(B > 0 && B <= 65535 && C > 0 && P > 0, "head_bwd: bad extents");
   head_bwd_kernel<<<dim3(C, B), 256, 0, as_stream(stream)>>>(x, w, scale, gy, dx, dws, C, P);
   return check_launch("head_bwd");
 }
@@ -940,8 +943,9 @@ extern "C" int tmdiff_linear_bwd(const float* x, const float* w, const float* bi
                                  float* dx, float* dw, float* db, int32_t B, int32_t I, int32_t O, int32_t act,
                                  tmdiff_stream_t stream) {
   using namespace tmdiff;
+  TMDIFF_REQUIRE(B >= 0 && I > 0 && O > 0, "linear_bwd: bad extents");
+  if (B == 0) return TMDIFF_OK;   // nothing is written: the sums over no rows (dw, db = 0) are the caller's
   TMDIFF_REQUIRE(x && w && gy, "linear_bwd: NULL pointer");
-  TMDIFF_REQUIRE(B > 0 && I > 0 && O > 0, "linear_bwd: bad extents");
   TMDIFF_REQUIRE(!act || gu_scratch, "linear_bwd: act != 0 needs a [B, O] scratch buffer");
   hipStream_t st = as_stream(stream);
   const float* gu = gy;

@@ -274,6 +274,8 @@ __global__ void __launch_bounds__(256) idwt2d_pack_bf16_kernel(const float* __re
   }
 }
 
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
 inline int grid_for(long total) {
   long blocks = (total + 255) / 256;
   return (int)(blocks < 1 ? 1 : (blocks > 256 * 8 ? 256 * 8 : blocks));  // <= 8 blocks per CU, grid-stride beyond
@@ -305,10 +307,10 @@ extern "C" int tmdiff_haar_dwt2d_pro(const float* x, float* ll, float* lh, float
   using namespace tmdiff;
   PlanePrologue pro;
   if (int rc = make_prologue(ll_prologue, planes, pro)) return rc;
-  TMDIFF_REQUIRE(x && ll, "haar_dwt2d: x and ll must not be NULL");
   TMDIFF_REQUIRE(planes >= 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "haar_dwt2d: H=%d W=%d must be positive and even",
                  H, W);
   if (planes == 0) return TMDIFF_OK;
+  TMDIFF_REQUIRE(x && ll, "haar_dwt2d: x and ll must not be NULL");
   const int h = H / 2, w = W / 2;
   const bool vec = (w % 4 == 0) && aligned16(x) && aligned16(ll) && aligned16(lh) && aligned16(hl) && aligned16(hh);
   if (vec) {
@@ -330,6 +332,8 @@ extern "C" int tmdiff_haar_dwt2d_pack_bf16(const float* x, void* ll_units, float
   TMDIFF_REQUIRE(B >= 0 && C > 0 && C % 8 == 0 && N > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0,
                  "haar_dwt2d_pack_bf16: C=%d (multiple of 8) H=%d W=%d (even)", C, H, W);
   if (B == 0) return TMDIFF_OK;
+  // the kernel reads x in 8-byte pairs (rows and pair offsets are even: only the base can be odd)
+  TMDIFF_REQUIRE(aligned8(x), "haar_dwt2d_pack_bf16: x must be 8-byte aligned");
   PlanePrologue pro = PlanePrologue{nullptr, nullptr, 0, 0, C, N, 0, 1};
   if (ll_prologue) {
     TMDIFF_REQUIRE(ll_prologue->C == C && ll_prologue->n_per_channel == N, "haar_dwt2d_pack_bf16: prologue C / n mismatch");
@@ -350,6 +354,8 @@ extern "C" int tmdiff_haar_idwt2d_pack_bf16(const float* ll0, const float* ll1, 
                  "haar_idwt2d_pack_bf16: NULL / unaligned pointer");
   TMDIFF_REQUIRE(B >= 0 && C > 0 && C % 8 == 0 && N > 0 && h > 0 && w > 0, "haar_idwt2d_pack_bf16: C=%d (multiple of 8)", C);
   if (B == 0) return TMDIFF_OK;
+  // the kernel writes out1 in 8-byte pairs
+  TMDIFF_REQUIRE(aligned8(out1), "haar_idwt2d_pack_bf16: out1 must be 8-byte aligned");
   PlanePrologue pro = PlanePrologue{nullptr, nullptr, 0, 0, C, N, 0, 1};
   if (out0_prologue) {
     TMDIFF_REQUIRE(out0_prologue->C == C && out0_prologue->n_per_channel == N, "haar_idwt2d_pack_bf16: prologue C / n mismatch");
@@ -382,14 +388,14 @@ extern "C" int tmdiff_haar_idwt2d_pro(const float* const ll[2], int32_t n_ll, co
   TMDIFF_REQUIRE(n_ll == 1 || (ll[1] && out[1]), "haar_idwt2d: second low band / output is NULL");
   TMDIFF_REQUIRE(planes >= 0 && h > 0 && w > 0, "haar_idwt2d: bad sizes");
   TMDIFF_REQUIRE(hi_batch_stride == 0 || (hi_planes_per_batch > 0 && planes % hi_planes_per_batch == 0 &&
-                                          hi_batch_stride >= hi_planes_per_batch * h * w && hi_batch_stride % 4 == 0),
+                                          hi_batch_stride >= hi_planes_per_batch * h * w),
                  "haar_idwt2d: bad high-band slicing (planes_per_batch=%ld stride=%ld)", (long)hi_planes_per_batch,
                  (long)hi_batch_stride);
   if (planes == 0) return TMDIFF_OK;
   const float* ll1 = n_ll == 2 ? ll[1] : nullptr;
   float* out1 = n_ll == 2 ? out[1] : nullptr;
-  const bool vec = (w % 4 == 0) && aligned16(ll[0]) && aligned16(ll1) && aligned16(lh) && aligned16(hl) &&
-                   aligned16(hh) && aligned16(out[0]) && aligned16(out1);
+  const bool vec = (w % 4 == 0) && hi_batch_stride % 4 == 0 && aligned16(ll[0]) && aligned16(ll1) && aligned16(lh) &&
+                   aligned16(hl) && aligned16(hh) && aligned16(out[0]) && aligned16(out1);
   if (vec) {
     const long total = planes * h * (w / 4);
     idwt2d_kernel<4><<<grid_for(total), 256, 0, as_stream(stream)>>>(ll[0], ll1, lh, hl, hh, out[0], out1, total, h, w, in_scale,

@@ -100,16 +100,26 @@ __global__ void __launch_bounds__(256) head_kernel(const float* __restrict__ x, 
 #pragma unroll
   for (int k = 0; k < V; ++k) acc[k] = 0.f;
   const float* src = x + (long)b * C * P + pv;
-  for (int c = 0; c < C; ++c) {
-    float v[V];
-    if constexpr (V == 4) {
-      const float4 t = *reinterpret_cast<const float4*>(src + c * P);
-      v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    } else {
-      v[0] = src[c * P];
+  // One fma chain per 256 channels, the chains added in order.  C <= 256 is one chain; a single chain of 4096 terms carries
+  // ~C/2.4 roundings of a partial sum each and misses the 2e-6 the suite holds the head to (measured 2.2e-6).
+  for (int c0 = 0; c0 < C; c0 += 256) {
+    const int c1 = min(c0 + 256, C);
+    float part[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) part[k] = 0.f;
+    for (int c = c0; c < c1; ++c) {
+      float v[V];
+      if constexpr (V == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(src + c * P);
+        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+      } else {
+        v[0] = src[c * P];
+      }
+#pragma unroll
+      for (int k = 0; k < V; ++k) part[k] = fmaf(ws[c], tmdiff::silu_f(v[k]), part[k]);
     }
 #pragma unroll
-    for (int k = 0; k < V; ++k) acc[k] = fmaf(ws[c], tmdiff::silu_f(v[k]), acc[k]);
+    for (int k = 0; k < V; ++k) acc[k] = c0 ? acc[k] + part[k] : part[k];
   }
   float* dst = y + (long)b * P + pv;
   if constexpr (V == 4)
@@ -189,10 +199,10 @@ extern "C" int tmdiff_stem_fwd_scaled(const float* xin, const float* pan, const 
                                       int32_t N, int32_t H, int32_t W, int32_t apply_silu, tmdiff_stream_t stream) {
   using namespace tmdiff;
   const int oss = bank_stride(out_scale_stride, Cout);
+  TMDIFF_REQUIRE(B >= 0 && Cout > 0 && N > 0 && H > 0 && W > 0 && B <= 65535, "stem_fwd: bad extents");
+  if (B == 0) return TMDIFF_OK;   // (an empty input / output has no storage: NULL is fine)
   TMDIFF_REQUIRE(w && y, "stem_fwd: NULL weights/output");
   TMDIFF_REQUIRE((ms && pan) || (!ms && xin), "stem_fwd: give either (pan, ms) or xin");
-  TMDIFF_REQUIRE(B >= 0 && Cout > 0 && N > 0 && H > 0 && W > 0 && B <= 65535, "stem_fwd: bad extents");
-  if (B == 0) return TMDIFF_OK;
   const long HW = (long)H * W, P = HW * N;
   const bool vec = HW % 4 == 0 && aligned16(xin) && aligned16(pan) && aligned16(ms) && aligned16(y);
   if (vec) {
@@ -210,10 +220,10 @@ extern "C" int tmdiff_stem_fwd_pack_bf16(const float* xin, const float* pan, con
                                          int32_t B, int32_t Cout, int32_t N, int32_t H, int32_t W, int32_t apply_silu,
                                          tmdiff_stream_t stream) {
   using namespace tmdiff;
-  TMDIFF_REQUIRE(w && units && aligned16(units), "stem_fwd_pack_bf16: NULL / unaligned weights / output");
-  TMDIFF_REQUIRE((ms && pan) || (!ms && xin), "stem_fwd_pack_bf16: give either (pan, ms) or xin");
   TMDIFF_REQUIRE(B >= 0 && Cout > 0 && Cout % 8 == 0 && N > 0 && H > 0 && W > 0 && B <= 65535, "stem_fwd_pack_bf16: bad extents");
   if (B == 0) return TMDIFF_OK;
+  TMDIFF_REQUIRE(w && units && aligned16(units), "stem_fwd_pack_bf16: NULL / unaligned weights / output");
+  TMDIFF_REQUIRE((ms && pan) || (!ms && xin), "stem_fwd_pack_bf16: give either (pan, ms) or xin");
   const int oss = bank_stride(out_scale_stride, Cout);
   const long HW = (long)H * W, P = HW * N;
   stem_pack_bf16_kernel<<<dim3((unsigned)((P + 255) / 256), B), 256, 0, as_stream(stream)>>>(
@@ -224,9 +234,9 @@ extern "C" int tmdiff_stem_fwd_pack_bf16(const float* xin, const float* pan, con
 extern "C" int tmdiff_head_fwd(const float* x, const float* w, const float* scale, int32_t scale_stride, float* y,
                                int32_t B, int32_t C, int64_t P, tmdiff_stream_t stream) {
   using namespace tmdiff;
-  TMDIFF_REQUIRE(x && w && y, "head_fwd: NULL pointer");
   TMDIFF_REQUIRE(B >= 0 && C > 0 && C <= 4096 && P > 0 && B <= 65535, "head_fwd: bad extents B=%d C=%d", B, C);
-  if (B == 0) return TMDIFF_OK;
+  if (B == 0) return TMDIFF_OK;   // (an empty x / y has no storage: NULL is fine)
+  TMDIFF_REQUIRE(x && w && y, "head_fwd: NULL pointer");
   const int ss = bank_stride(scale_stride, C);
   const bool vec = P % 4 == 0 && aligned16(x) && aligned16(y);
   if (vec) {
@@ -242,9 +252,9 @@ extern "C" int tmdiff_head_fwd(const float* x, const float* w, const float* scal
 extern "C" int tmdiff_linear_fwd(const float* x, const float* w, const float* bias, float* y, int32_t B, int32_t I,
                                  int32_t O, int32_t act, tmdiff_stream_t stream) {
   using namespace tmdiff;
-  TMDIFF_REQUIRE(x && w && y, "linear_fwd: NULL pointer");
   TMDIFF_REQUIRE(B >= 0 && I > 0 && I <= 1024 && O > 0, "linear_fwd: B=%d I=%d (<=1024) O=%d", B, I, O);
-  if (B == 0) return TMDIFF_OK;
+  if (B == 0) return TMDIFF_OK;   // (an empty x / y has no storage: NULL is fine)
+  TMDIFF_REQUIRE(x && w && y, "linear_fwd: NULL pointer");
   linear_kernel<<<(O + 3) / 4, 256, 0, as_stream(stream)>>>(x, w, bias, y, B, I, O, act);
   return check_launch("linear_fwd");
 }
@@ -252,9 +262,9 @@ extern "C" int tmdiff_linear_fwd(const float* x, const float* w, const float* bi
 extern "C" int tmdiff_gamma_embedding(const float* t, const float* freqs, float* emb, int32_t B, int32_t dim,
                                       tmdiff_stream_t stream) {
   using namespace tmdiff;
-  TMDIFF_REQUIRE(t && freqs && emb, "gamma_embedding: NULL pointer");
   TMDIFF_REQUIRE(B >= 0 && dim >= 2, "gamma_embedding: B=%d dim=%d", B, dim);
   if (B == 0) return TMDIFF_OK;
+  TMDIFF_REQUIRE(t && freqs && emb, "gamma_embedding: NULL pointer");
   gamma_kernel<<<(B * dim + 255) / 256, 256, 0, as_stream(stream)>>>(t, freqs, emb, B, dim);
   return check_launch("gamma_embedding");
 }

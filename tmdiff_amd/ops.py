@@ -5,6 +5,7 @@ these ops runs in libtmdiff_hip.so.  All wrappers require CUDA(HIP) fp32 contigu
 tensors and raise otherwise -- there is no eager fallback.
 """
 import ctypes as C
+import math
 import os
 
 import torch
@@ -1180,7 +1181,7 @@ def channel_sum(x, scale=1.0):
     """x [B, C, ...] -> [C]: scale * sum over batch and positions."""
     b, c = x.shape[:2]
     out = torch.empty(c, device=x.device, dtype=torch.float32)
-    check(lib.tmdiff_channel_sum(_chk(x, "x"), out.data_ptr(), b, c, x.numel() // (b * c), scale, stream_ptr()),
+    check(lib.tmdiff_channel_sum(_chk(x, "x"), out.data_ptr(), b, c, math.prod(x.shape[2:]), scale, stream_ptr()),
           "channel_sum")
     return out
 
@@ -1240,8 +1241,9 @@ def linear_bwd(x, w, bias, gy, act=False, need_dx=True, need_dw=True, need_db=Tr
     b, i = x.shape
     o = w.shape[0]
     dx = torch.empty(b, i, device=x.device, dtype=torch.float32) if need_dx else None
-    dw = torch.empty(o, i, device=x.device, dtype=torch.float32) if need_dw else None
-    db = torch.empty(o, device=x.device, dtype=torch.float32) if need_db else None
+    new = torch.zeros if b == 0 else torch.empty       # (no rows: the kernels do not run, the sums over them are 0)
+    dw = new(o, i, device=x.device, dtype=torch.float32) if need_dw else None
+    db = new(o, device=x.device, dtype=torch.float32) if need_db else None
     gu = torch.empty(b, o, device=x.device, dtype=torch.float32) if act else None
     check(lib.tmdiff_linear_bwd(_chk(x, "x"), _chk(w, "w"), _chk(bias, "bias"), _chk(gy, "gy"), _chk(gu, "gu"),
                                 _chk(dx, "dx"), _chk(dw, "dw"), _chk(db, "db"), b, i, o, 1 if act else 0,
