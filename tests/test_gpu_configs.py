@@ -98,6 +98,48 @@ def test_config2_batch32_epilogue_fusions_switched_off(switch, what):
         assert c_off == c_on
 
 
+_FUSION_CASE_COUNTS = {"conv3d_fwd_k1": 9, "conv3d_ll_fwd": 2, "conv3d_wf_fwd": 48, "conv3d_wfll_fwd": 1}
+
+
+def test_small_network_takes_and_declines_every_epilogue_fusion():
+    """The smallest case in which each of the five fusions tmdiff_amd.routing decides (fold_k1, side_xp, emit_ll, its emit_dwt
+    form, s2d_handover) is taken by some block and declined by another, chosen on the CPU from routing.unet_fusions under
+    wino_min_blocks=1: widths [32, 64, 128, 128], B = 4, 8 bands, 64x64 (smaller batches and 32x32 planes split every grid that
+    could emit an LL band; the 8x8 level is the pair mode, where folding and emitting decline).  One fp32 inference forward:
+    (a) the launches per C entry point are those recorded from the same forward before the fusion rules moved into
+    tmdiff_amd.routing (the literals below: a moved rule that decided differently would change them); (b) the output equals
+    the forward's with the five fusions switched off, within the bound of test_config2_batch32_epilogue_fusions_switched_off
+    (another summation order where a convolution is folded)."""
+    import collections
+    from tmdiff_amd import ops, routing
+    channels, b, n, size = [32, 64, 128, 128], 4, 8, 64
+    with ops.config.override(wino_min_blocks=1):
+        rows = routing.unet_fusions(channels, b, n, size, size)
+    for fusion, kind in (("fold", "resblock"), ("fold", "down"), ("side_xp", "resblock"), ("emit_ll", "resblock"),
+                         ("s2d", "resblock"), ("dwt", "down"), ("wfll", "down")):
+        mine = [fusion in r.taken for r in rows if r.kind == kind]
+        assert any(mine) and not all(mine), (fusion, kind)
+    net = _hip_net(channels)
+    d = {k: cu(v) for k, v in case_inputs(41, b, n, size).items()}
+    t = torch.tensor([[650.0], [12.0], [333.0], [901.0]]).cuda()
+
+    def run():
+        ops.COUNTS = collections.Counter()
+        try:
+            with torch.no_grad():
+                return net(d["x_t"], t, d["PAN"], d["MS"], "WV3"), dict(ops.COUNTS)
+        finally:
+            ops.COUNTS = None
+
+    with ops.config.override(wino_min_blocks=1):
+        y_on, c_on = run()
+        with ops.config.override(fuse_res_conv=False, side_xp=False, emit_ll=False, emit_dwt=False, wfll=False):
+            y_off, c_off = run()
+    print("fused:", sorted(c_on.items()), "unfused:", sorted(c_off.items()))
+    assert c_on == _FUSION_CASE_COUNTS
+    assert_close(y_off, y_on, 1e-5, 2e-6, "the five fusions off vs on")
+
+
 # ---- configs[2]: the WorldView-3 network of config/general.json ---------------------------------------------------------
 @pytest.fixture(scope="module")
 def wide_net():

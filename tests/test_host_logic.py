@@ -832,3 +832,107 @@ def test_network_routes_respect_size_limits():
     assert net._fold_res_conv(P, "down1.conv20", [X(1, 64, 4, 2048, 2048)]) is None          # 64 x 2^24 = 2^30
     assert net.down1.down.Conv_0.in_channels == 128           # 128 x 2^23 = 2^30
     assert net._ll_fits("down1.down", X(1, 128, 8, 1024, 1022)) and not net._ll_fits("down1.down", X(1, 128, 8, 1024, 1024))
+    # the same four facts asked of the rules themselves: functions of the extents, no network
+    from tmdiff_amd import routing
+    assert routing.fold_k1(1, 64, 128, 128, 4, 2048, 2044) and not routing.fold_k1(1, 64, 128, 128, 4, 2048, 2048)
+    assert routing.ll_fits(1, 128, 128, 8, 1024, 1022) and not routing.ll_fits(1, 128, 128, 8, 1024, 1024)
+
+
+def test_fusion_table_of_the_baseline_configs():
+    """What the epilogues of the inference graph additionally do (tmdiff_amd.routing.unet_fusions), tabulated like the
+    families: the table committed as profiles/fusion_table.txt is this code's (tools/routing_table.py --fusions), and the
+    benchmark workload (B = 32, 8 bands, 64x64, widths 32-256) has no prologue pass left, its four three-segment res_conv
+    launches write conv20's prologue output on the side, its three main-branch Conv_0 run composed with the LL band on
+    conv3d_wf's composed mode from a space-to-depth second output, and 9 of its 19 1x1x1 launches remain (DESIGN.md section 1:
+    "per step 19 -> 9 1x1x1 launches")."""
+    import subprocess, sys
+    from tmdiff_amd import ops, routing
+    assert ops.config.as_dict() == ops.KernelConfig(env={}).as_dict(), "this table is that of the default switches"
+    rows = {r.block: r for r in routing.unet_fusions(routing.FULL, 32, 8, 64, 64)}
+    assert len(rows) == 25 and sum(r.passes for r in rows.values()) == 0
+    for blk in ("up1.conv20", "up2.conv20", "up3.conv20", "final.conv20"):
+        assert rows[blk].taken == ("side_xp",) and rows[blk].k1 == 1, rows[blk]
+    for blk in ("down1", "down2", "down3"):
+        assert "wfll" in rows[blk + ".down"].taken and "s2d" in rows[blk + ".conv20"].taken, (rows[blk + ".down"], rows[blk + ".conv20"])
+    assert sum(r.k1 for r in rows.values()) == 9
+    # every fusion is taken by some BASELINE case and declined by some
+    seen = [set(t for r in routing.unet_fusions(ch, b, n, size, size, math) for t in r.taken)
+            for _, ch, b, n, size, math in routing.BASELINE_CASES if math == "fp32"]
+    every = {"fold", "side_xp", "emit_ll", "s2d", "wfll", "ll", "dwt"}
+    assert set().union(*seen) == every and set.intersection(*seen) < every, seen
+    path = os.path.join(ROOT, "profiles", "fusion_table.txt")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "routing_table.py"), "--fusions"], capture_output=True, text=True,
+                         timeout=300)
+    assert out.returncode == 0, out.stderr[-1000:]
+    assert out.stdout == open(path).read(), "profiles/fusion_table.txt is stale: python tools/routing_table.py --fusions > " + path
+
+
+def _model_fusions(net, b, n, size):
+    """{block: fusions taken} as WavBEST's own methods decide them on stand-ins with the extents of the tensors of one fp32
+    inference forward, asked in _resblock's / _down's order (a CPU module: no _prepare, nothing allocated)."""
+    from tmdiff_amd import ops
+
+    class X:
+        def __init__(self, ch, k):
+            self.shape = (b, ch, n, size >> k, size >> k)
+
+    P, c, got = {"bf16": set()}, net.channels, {}
+    fuse_c, fuse = net._producer_fuse(P)
+
+    def resblock(name, seg_c, k, pre, emit, want_ll=False, to_conv0=False):
+        segs, taken = [X(ch, k) for ch in seg_c], []
+        if isinstance(net.get_submodule(name).res_conv, torch.nn.Conv3d):
+            if net._fold_res_conv(P, name, segs) is not None:
+                taken.append("fold")
+            elif not pre and net._side_xp(P, name, segs):
+                taken.append("side_xp")
+        if want_ll and emit and ops.config.epilogue_fuse and net._emit_ll(P, name, segs[0]):
+            taken.append("emit_ll")
+        s2d = bool(to_conv0 and emit and net._ll_s2d(P, name[:-len(".conv20")], segs[0]))
+        got[name] = tuple(taken + ["s2d"] * s2d)
+        return s2d
+
+    def down(name, k, main, pre, s2d):
+        ch, conv0 = c[k + 1], None
+        if main and pre:
+            if s2d:
+                conv0 = "wfll"
+            elif ops.config.ll_compose and ops.ll_conv_supported(ch, ch) and net._ll_fits(name, X(ch, k)):
+                conv0 = "ll"
+        elif fuse and pre and net._emit_ll(P, name, X(ch, k), conv=".Conv_0", switch="emit_dwt"):
+            conv0 = "dwt"
+        fold = ops.config.conv2_after_ll and net._fold_res_conv(P, name, [X(ch, k + 1)], k1=".Conv_2", k3=".Conv_1") is not None
+        got[name] = tuple(t for t in (conv0, "fold" if fold else None) if t)
+
+    for branch in ("_1", ""):
+        for k in range(3):
+            blk = f"down{k + 1}{branch}"
+            s2d = resblock(blk + ".conv20", [c[k]], k, fuse_c, fuse_c, want_ll=True, to_conv0=not branch)
+            down(blk + ".down", k, not branch, fuse_c, s2d)
+    resblock("middle1", [c[3]], 3, fuse_c, False)
+    for k, upn in ((3, "up1"), (2, "up2"), (1, "up3")):
+        resblock(upn + ".conv20", [c[k]] * 3, k, False, fuse_c)
+    resblock("final.conv20", [c[0]] * 3, 0, False, fuse_c)
+    for k in (1, 2, 3):
+        resblock(f"final.conv2{k}", [c[0]], 0, fuse_c, fuse_c and k < 3)
+    return got
+
+
+@pytest.mark.parametrize("channels,b,n,size,switches", [
+    ([32, 64, 128, 256], 32, 8, 64, {}),                          # the benchmark workload (a BASELINE width)
+    ([16, 32, 64, 128], 32, 8, 64, {}),                           # the reference's default widths: 16 channels fold / emit nothing
+    ([32, 64, 128, 128], 4, 8, 64, {"wino_min_blocks": 1}),       # the small case of tests/test_gpu_configs.py's fusion test
+    ([32, 64, 128, 256], 32, 4, 64, {"emit_dwt": False, "wfll": False}),
+])
+def test_model_decisions_equal_the_fusion_rows(channels, b, n, size, switches):
+    """The block walk and the channel bookkeeping of routing.unet_fusions against the real module tree: what a CPU WavBEST
+    decides for every ResBlock and every down block (its own methods, which read the channel counts off its modules) is that
+    block's row."""
+    from tmdiff_amd import ops, routing
+    from tmdiff_amd.Hyper_unet_general import WavBEST
+    net = WavBEST(channels=channels)
+    with ops.config.override(**switches):
+        got = _model_fusions(net, b, n, size)
+        rows = {r.block: r.taken for r in routing.unet_fusions(channels, b, n, size, size) if r.kind in ("resblock", "down")}
+    assert got == rows
+    assert any(got.values())

@@ -26,7 +26,7 @@ import math
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, routing
 
 PROMPTS = ("QB", "WV3", "GF2", "WV2", "WV4")
 # (behaviour switches: ops.config)
@@ -338,6 +338,23 @@ class WavBEST(nn.Module):
             self._cond = None
         return self
 
+    def _projection_layers(self):
+        """([(name, Linear)] of the time-embedding shifts, ... of the prompt-embedding scales), in module order: the layers one
+        bank launch evaluates (_Bank in inference, autograd's `bank` in forward_train)."""
+        shift, scale = [], []
+        for name, m in self.named_modules():
+            if isinstance(m, ResBlockModulateBEST):
+                scale.append((name + ".dense2", m.dense2.dense))
+                if not m.flag:
+                    shift.append((name + ".dense1", m.dense1.dense))
+            elif isinstance(m, WaveletUPorDown):
+                scale.append((name + ".dense1", m.dense1.dense))
+                if not m.flag:
+                    shift.append((name + ".Dense_0", m.Dense_0))
+            elif isinstance(m, (AdaptionModulateBEST, FinalBlockModulateBEST)):
+                scale.append((name + ".dense2", m.dense2.dense))
+        return shift, scale
+
     # ---- weight-dependent preparation (redone when any parameter changes) --------------------------
     def _prepare(self):
         params = list(self.parameters())
@@ -374,18 +391,7 @@ class WavBEST(nn.Module):
                     # can hand over its second output in space-to-depth form (_ll_s2d)
                     if ops.config.winograd and ops.config.wfll and m.out_channels % 32 == 0:
                         prep["w_wfll"][blk + ".down.Conv_0"] = ops.pack_conv_weight_wfll(m.weight.detach().float().contiguous(), 0.5)
-        shift, scale = [], []
-        for name, m in self.named_modules():
-            if isinstance(m, ResBlockModulateBEST):
-                scale.append((name + ".dense2", m.dense2.dense))
-                if not m.flag:
-                    shift.append((name + ".dense1", m.dense1.dense))
-            elif isinstance(m, WaveletUPorDown):
-                scale.append((name + ".dense1", m.dense1.dense))
-                if not m.flag:
-                    shift.append((name + ".Dense_0", m.Dense_0))
-            elif isinstance(m, (AdaptionModulateBEST, FinalBlockModulateBEST)):
-                scale.append((name + ".dense2", m.dense2.dense))
+        shift, scale = self._projection_layers()
         prep["shift_bank"] = _Bank(shift, dev)
         prep["scale_bank"] = _Bank(scale, dev)
         self._prep = prep
@@ -451,9 +457,9 @@ class WavBEST(nn.Module):
         (None, y2, y_ll); else (y, y2, None)."""
         rb = self.get_submodule(name)
         sh = {} if flag else self._shift(P, S, name + ".dense1")
-        # res_conv (1x1x1, where the channel count changes) folded into conv21's epilogue where conv21 runs on conv3d_wf unsplit:
+        # res_conv (1x1x1, where the channel count changes) folded into conv21's epilogue where conv21 runs on conv3d_wf:
         # W1^T x is accumulated by the matrix pipe into conv21's output blocks -- no launch of its own, no residual tensor
-        # written and read back (19 -> 13 1x1x1 launches per step at the benchmark batch)
+        # written and read back (with the down blocks' Conv_2: 19 -> 9 1x1x1 launches per step at the benchmark batch)
         rc = side = None
         if isinstance(rb.res_conv, nn.Conv3d):
             rc = self._fold_res_conv(P, name, segs)
@@ -496,74 +502,45 @@ class WavBEST(nn.Module):
         out = out if emit is not None else (out, None)
         return (*out, None) if want_ll else out
 
+    # Which launches take which epilogue form is decided in tmdiff_amd.routing (fold_k1, side_xp, emit_ll, s2d_handover, ll_fits:
+    # functions of extents, switches and math).  What is the model's: the channel counts and the set of bf16 convolutions.
+    @staticmethod
+    def _math(P, *names):
+        return "bf16" if any(n_ in P["bf16"] for n_ in names) else "fp32"
+
     def _emit_ll(self, P, name, x, conv=".conv21", switch="emit_ll"):
-        """True when the convolution `name + conv` (a ResBlock's conv21; a down block's Conv_0 for the whole Haar transform) can
-        write the halved LL band / the Haar transform of its output instead of the output itself (desc.y_ll / y_hi): fp32,
-        8 bands, even H, planes of at least 16 columns, the convolution on conv3d_wf without splitting its input channels, and
-        the down block's Conv_2 after the LL band (ops.config.conv2_after_ll).  x: a tensor of the convolution's input extents."""
-        cfg = ops.config
-        if not (getattr(cfg, switch) and cfg.conv2_after_ll and cfg.epilogue_fuse) or (name + conv) in P["bf16"]:
-            return False
+        """True when the convolution `name + conv` (a ResBlock's conv21; a down block's Conv_0 with switch="emit_dwt") writes the
+        halved LL band / the Haar transform of its output instead of the output.  x: a tensor of its input extents."""
         m = self.get_submodule(name + conv)
         b, _, n, h, w = x.shape
-        if P["w_wino"].get(name + conv) is None or n != 8 or w == 8 or h % 2 or w % 4 or m.groups != 1:
-            return False
-        from . import routing
-        return (routing.conv3_family(b, m.in_channels, m.out_channels, n, h, w, 1, plain=False) == "wf" and
-                routing.wf_route(b, m.in_channels, m.out_channels, n, h, w)[1] == 1)
+        return routing.emit_ll(b, m.in_channels, m.out_channels, n, h, w, m.groups, self._math(P, name + conv), switch)
 
     def _side_xp(self, P, name, segs):
-        """True when res_conv of the ResBlock `name` can write conv20's prologue output on the side (make_conv_desc side_xp=):
-        fp32 inference with the conv20 -> conv21 epilogue fusion, a segmented input, conv20 on conv3d_wf (whose prologue would
-        otherwise be a pass of its own), res_conv on the 16-byte bandwidth kernel."""
-        cfg = ops.config
-        if not (cfg.side_xp and cfg.epilogue_fuse) or len(segs) < 2 or any((name + k) in P["bf16"] for k in (".conv20", ".conv21", ".res_conv")):
-            return False
+        """True when res_conv of the ResBlock `name` also writes conv20's prologue output (make_conv_desc side_xp=)."""
         m = self.get_submodule(name + ".conv20")
         b, _, n, h, w = segs[0].shape
-        from . import routing
-        if P["w_wino"].get(name + ".conv20") is None or m.groups != 1:
-            return False
-        if routing.conv3_family(b, m.in_channels, m.out_channels, n, h, w, 1, plain=False) not in ("wf", "wf_pair"):
-            return False
-        return routing.k1_side_xp(b, [s.shape[1] for s in segs], self.get_submodule(name + ".res_conv").out_channels, n, h, w)
+        return routing.side_xp(b, tuple(s.shape[1] for s in segs), m.out_channels, n, h, w, m.groups,
+                               self._math(P, name + ".conv20", name + ".conv21", name + ".res_conv"))
 
     def _fold_res_conv(self, P, name, segs, k1=".res_conv", k3=".conv21"):
         """(x, the 1x1x1 weight, Cx) when the 1x1x1 convolution `name + k1` -- a ResBlock's res_conv, a down block's Conv_2 --
-        whose result is only ever the residual of the 3x3x3 convolution `name + k3` can ride in that convolution's epilogue
-        (make_conv_desc res_conv=), else None: fp32, one input tensor x of a multiple of 32 channels at the consumer's plane
-        size, the consumer on conv3d_wf (not its pair mode; a split-K grid adds it to the partial sums of its first range)."""
-        if not ops.config.fuse_res_conv or len(segs) != 1 or (name + k3) in P["bf16"] or (name + k1) in P["bf16"]:
-            return None
+        rides in the epilogue of the 3x3x3 convolution `name + k3` (make_conv_desc res_conv=), else None."""
         m3, x = self.get_submodule(name + k3), segs[0]
         b, cx, n, h, w = x.shape
-        if P["w_wino"].get(name + k3) is None or cx % 32 or cx > 512 or m3.groups != 1 or (n == 8 and w == 8):
-            return None
-        from . import routing
-        if routing.conv3_family(b, m3.in_channels, m3.out_channels, n, h, w, 1, plain=False) != "wf":
-            return None
-        if not routing.wf_fold_fits(b, m3.in_channels, m3.out_channels, n, h, w, cx):
+        if not routing.fold_k1(b, cx, m3.in_channels, m3.out_channels, n, h, w, m3.groups, self._math(P, name + k3, name + k1), len(segs)):
             return None
         return x, self.get_submodule(name + k1).weight.detach(), cx
 
     def _ll_s2d(self, P, blk, h):
-        """True when the main branch's down block `blk` runs Conv_0 + LL as conv3d_wf_ll: its weights exist, the ResBlock in
-        front ends in a conv3d_wf launch that does not split its input channels (only that epilogue writes the space-to-depth
-        form), and the composed convolution's own grid is taken by the kernel.  h: the ResBlock's input."""
-        if not ops.config.epilogue_fuse or P["w_wfll"].get(blk + ".down.Conv_0") is None:
-            return False
-        c21, c0 = blk + ".conv20.conv21", self.get_submodule(blk + ".down.Conv_0")
-        if P["w_wino"].get(c21) is None or c21 in P["bf16"] or (blk + ".conv20.conv20") in P["bf16"]:
-            return False
-        m21 = self.get_submodule(c21)
+        """True when the main branch's down block `blk` runs Conv_0 + LL as conv3d_wf_ll, on the space-to-depth second output
+        of the ResBlock in front.  h: the ResBlock's input."""
+        m21, c0 = self.get_submodule(blk + ".conv20.conv21"), self.get_submodule(blk + ".down.Conv_0")
         b, _, n, hh, ww = h.shape
-        takes, split = ops.wf_route(b, m21.in_channels, m21.out_channels, n, hh, ww, m21.groups)
-        return bool(takes and split == 1 and m21.out_channels == c0.in_channels and
-                    ops.wfll_route(b, c0.in_channels, c0.out_channels, n, hh, ww))
+        math = "bf16" if self.compute_dtype == "bf16" else self._math(P, blk + ".conv20.conv20", blk + ".conv20.conv21")
+        return routing.s2d_handover(b, (m21.in_channels, m21.out_channels), (c0.in_channels, c0.out_channels), n, hh, ww, m21.groups, math)
 
     def _ll_fits(self, name, x):
         """True when conv3d_ll takes the down block `name`'s Conv_0 + LL on x (its size limit)."""
-        from . import routing
         c0 = self.get_submodule(name + ".Conv_0")
         return routing.ll_fits(x.shape[0], c0.in_channels, c0.out_channels, *x.shape[2:])
 
@@ -598,7 +575,7 @@ class WavBEST(nn.Module):
         if ops.config.conv2_after_ll:
             if xq is None:
                 xq = ops.haar_dwt2d(x, want_high=False, ll_scale=0.5)[0]
-            # ... and where Conv_1 runs on conv3d_wf unsplit, Conv_2 rides in its epilogue like a ResBlock's res_conv
+            # ... and where Conv_1 runs on conv3d_wf, Conv_2 rides in its epilogue like a ResBlock's res_conv
             rc = self._fold_res_conv(P, name, [xq], k1=".Conv_2", k3=".Conv_1")
             if rc is not None:
                 xll, rc2 = None, {"res_conv": rc, "bias": self.get_submodule(name + ".Conv_2").bias.detach()}
@@ -862,18 +839,7 @@ class WavBEST(nn.Module):
         g = ops.gamma_embedding(t, fr, self.inter_dim)
         temb = lin(self.embed, 2, lin(self.embed, 0, g, True), True)
 
-        shift_layers, scale_layers = [], []
-        for name, m in self.named_modules():
-            if isinstance(m, ResBlockModulateBEST):
-                scale_layers.append((name + ".dense2", m.dense2.dense))
-                if not m.flag:
-                    shift_layers.append((name + ".dense1", m.dense1.dense))
-            elif isinstance(m, WaveletUPorDown):
-                scale_layers.append((name + ".dense1", m.dense1.dense))
-                if not m.flag:
-                    shift_layers.append((name + ".Dense_0", m.Dense_0))
-            elif isinstance(m, (AdaptionModulateBEST, FinalBlockModulateBEST)):
-                scale_layers.append((name + ".dense2", m.dense2.dense))
+        shift_layers, scale_layers = self._projection_layers()
 
         def bank(x, layers):     # one launch for all projections of x; autograd splits the gradient back
             out = A.linear(x, torch.cat([l.weight for _, l in layers]), torch.cat([l.bias for _, l in layers]))

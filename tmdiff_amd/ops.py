@@ -659,6 +659,7 @@ def pack_conv_weight_wino(w, groups=1, mode=0, planes=6):
 
 # routing lives in tmdiff_amd/routing.py; these names stay importable from ops (tests, tools)
 wino_conv_supported = routing.wino_weight_ok
+ll_conv_supported = routing.ll_weight_ok       # (shapes tmdiff_conv3d_ll_fwd takes)
 wf_route = routing.wf_route
 wfll_route = routing.wfll_route
 
@@ -718,8 +719,8 @@ def conv3d_wf(segs, w_packed, cout, emit=None, keep_y=True, groups=1, xp_out=Non
     want_ll = want_ll or want_dwt
     if s2d or want_ll:
         cin = sum(s_.shape[1] for s_ in segs)
-        if routing.wf_route(b, cin, cout, n, h, w, groups)[1] > 1 or h % 2 or w % 4:
-            raise ValueError("conv3d_wf: this launch cannot write a space-to-depth / LL output (ask routing.wf_route first)")
+        if not routing.wf_quarter_ok(b, cin, cout, n, h, w, groups):
+            raise ValueError("conv3d_wf: this launch cannot write a space-to-depth / LL output (ask routing.wf_quarter_ok first)")
     if want_ll and keep_y:
         raise ValueError("conv3d_wf: the LL output replaces y (keep_y=False)")
     q = (b, cout, n, h // 2, w // 2)       # (allocated before y and y2 -- y is None whenever y_ll is wanted)
@@ -742,11 +743,6 @@ def conv3d_wf(segs, w_packed, cout, emit=None, keep_y=True, groups=1, xp_out=Non
     flops = 2.0 * b * cout * ((d.Cin // groups) * 13.5 + d.rc_cin) * n * h * w
     _launch(lib.tmdiff_conv3d_wf_fwd, d, (ws,), "conv3d_wf_fwd", "conv3d_wf_fwd", flops, 3, f" +rc{d.rc_cin}" if d.rc_cin else "")
     return (y_ll, *y_hi) if want_dwt else (y2, y_ll) if want_ll else _result(y, y2)
-
-
-def ll_conv_supported(cout, cin, ksize=3, groups=1):
-    """Shapes tmdiff_conv3d_ll_fwd takes (conv3d_ll_halved below)."""
-    return ksize == 3 and groups == 1 and cin % 2 == 0 and cout % 64 == 0
 
 
 def pack_conv_weight_ll(w, ll_scale=0.5):

@@ -1,4 +1,5 @@
-"""Which kernel family runs each 3x3x3 convolution: the ONE place the decision is taken (host logic only, no GPU work).
+"""Which kernel family runs each 3x3x3 convolution, and what its epilogue additionally does: the ONE place both decisions are
+taken (host logic only, no GPU work).
 
 A *family* is a C entry point of libtmdiff_hip.so with the kernel behind it:
 
@@ -28,6 +29,24 @@ The rules, in order (fp32):
   3. the direct kernels, whose split-K fills the chip on small grids: staged (operands by LDS-DMA; needs Cin/g % 4 == 0 and
      Cout/g % 32 == 0) where the input is plain or the prologue pass is amortised (Cout/g >= 128, Cin/g >= 384, dropout / mask,
      a kept x'), else fused.
+What a launch's epilogue additionally does in the fp32 inference graph is decided here too (WavBEST reads the channel counts
+and its set of bf16 convolutions off its modules and asks); `unet_fusions` tabulates it per block, `tools/routing_table.py
+--fusions` writes profiles/fusion_table.txt:
+
+  fusion                        descriptor fields            rule
+  ----------------------------  ---------------------------  ------------------------------------------------------------------
+  fold a 1x1x1 conv (res_conv,  rc_x, rc_w, rc_cin           fold_k1: one input tensor of 32 .. 512 channels (% 32), consumer on
+    Conv_2) into its consumer                                conv3d_wf outside the pair mode (split-K allowed), rc_x size limit
+  side x' of a segmented        xp_out, xp_shift, xp_act     side_xp: conv20 on conv3d_wf (pair mode, split-K allowed), res_conv
+    res_conv launch                                          on a bandwidth kernel that can (k1_side_xp)
+  conv21 writes LL(y) / 2       y_ll                         emit_ll: 8 bands, unsplit conv3d_wf launch outside the pair mode,
+  Conv_0 writes the Haar bands  y_ll, y_hi                   even H, W % 4 == 0 (wf_launch and wf_quarter_ok); switch emit_dwt
+  second output space-to-depth  y2_s2d                       s2d_handover: conv21 an unsplit conv3d_wf launch, composed weights
+    (Conv_0 + LL on "wfll")                                  exist, wfll_route takes the composed convolution
+  Conv_0 + LL on "ll"           (tmdiff_conv3d_ll_fwd)       ll_fits: the direct composed kernel's size limit
+Each rule also reads its switches (fuse_res_conv, side_xp, emit_ll / emit_dwt, conv2_after_ll, epilogue_fuse, wfll, ll_compose,
+winograd) and declines as soon as a convolution involved runs on the bf16 kernels.
+
 Batch-size note (README): the same sample can take different families at B = 1 and B = 32 (rule 1's grid threshold), hence
 different fp32 summation orders; tests/test_gpu_configs.py bounds the difference at 1e-5.
 """
@@ -50,6 +69,11 @@ def wino_weight_ok(cout, cin, ksize=3, groups=1):
     """Weight shapes the Winograd kernels (conv3d_wf, fallback.conv3d_wino) take."""
     return (ksize == 3 and groups in (1, 3) and cin % groups == 0 and cout % groups == 0 and (cin // groups) % 2 == 0 and
             (cout // groups) % 32 == 0)
+
+
+def ll_weight_ok(cout, cin, ksize=3, groups=1):
+    """Weight shapes that have the composed Conv_0 + LL forms (conv3d_ll; conv3d_wf's composed-LL mode: Cout % 32, implied)."""
+    return ksize == 3 and groups == 1 and cin % 2 == 0 and cout % 64 == 0
 
 
 _WF_ROUTES = {}      # (the plan is a pure function of the extents and the switches: one library call per distinct shape)
@@ -204,8 +228,94 @@ def ll_fits(b, cin, cout, n, h, w):
 
 def wf_fold_fits(b, cin, cout, n, h, w, rc_cin):
     """True when conv3d_wf can fold a residual 1x1x1 convolution of rc_cin input channels into its epilogue at these extents
-    (the size limit of its rc_x offsets; the other conditions: Hyper_unet_general.WavBEST._fold_res_conv)."""
+    (the size limit of its rc_x offsets; the whole rule: fold_k1)."""
     return supported("tmdiff_conv3d_wf_supported", b, cin, cout, n, h, w, rc_x=16, rc_cin=rc_cin)
+
+
+# ---- what a launch's epilogue additionally does: the fusions of the fp32 inference graph -------------------------------------
+# Functions of the extents, ops.config and a math string ("bf16" as soon as one of the convolutions involved runs on the bf16
+# kernels); WavBEST asks them once per block per forward, so the answers are kept per (arguments, config.key()) like wf_route's.
+_FUSIONS = {}
+
+
+def _cached(fn):
+    def ask(*args):
+        key = (fn.__name__, args, _config().key())
+        r = _FUSIONS.get(key)
+        if r is None:
+            if len(_FUSIONS) > 4096:
+                _FUSIONS.clear()
+            r = _FUSIONS[key] = bool(fn(*args))
+        return r
+    ask.__name__, ask.__doc__ = fn.__name__, fn.__doc__
+    return ask
+
+
+def wf_launch(b, cin, cout, n, h, w, groups=1, pair_ok=False):
+    """The shared core, part 1: the convolution is a conv3d_wf launch ("wf"; its pair mode too with pair_ok) whatever its input
+    looks like -- the rules are asked before the input's form is settled, hence plain=False: the prologue pass's size limit
+    counts even where the launch ends up reading a plain tensor.  (conv3_family names these families only for a weight with a
+    Winograd form: config.winograd and wino_weight_ok.)"""
+    return conv3_family(b, cin, cout, n, h, w, groups, plain=False) in (("wf", "wf_pair") if pair_ok else ("wf",))
+
+
+def wf_quarter_ok(b, cin, cout, n, h, w, groups=1):
+    """The shared core, part 2: a conv3d_wf launch of these extents can write at quarter resolution -- its second output in
+    space-to-depth form, LL(y) / 2, the Haar transform of y: it does not split its input channels (a split-K launch's epilogue
+    sees partial sums), H is even and W a multiple of 4.  ops.conv3d_wf raises where this is False."""
+    return wf_route(b, cin, cout, n, h, w, groups)[1] == 1 and h % 2 == 0 and w % 4 == 0
+
+
+@_cached
+def fold_k1(b, cx, cin, cout, n, h, w, groups=1, math="fp32", segments=1):
+    """A 1x1x1 convolution of cx input channels (a ResBlock's res_conv, a down block's Conv_2), whose result is only ever the
+    residual of the 3x3x3 convolution cin -> cout, rides in that convolution's epilogue (desc.rc_x / rc_w / rc_cin): fp32, ONE
+    input tensor of a multiple of 32 channels (at most 512) at the consumer's plane size, the consumer on conv3d_wf but not in
+    its pair mode.  A split-K grid is fine: it adds W1^T x to the partial sums of its first range."""
+    if not _config().fuse_res_conv or segments != 1 or math == "bf16" or groups != 1 or cx % 32 or cx > 512:
+        return False
+    return wf_launch(b, cin, cout, n, h, w) and wf_fold_fits(b, cin, cout, n, h, w, cx)
+
+
+@_cached
+def side_xp(b, seg_c, cout, n, h, w, groups=1, math="fp32"):
+    """The 1x1x1 res_conv launch of a ResBlock on the segments seg_c (a tuple of channel counts) also writes conv20's prologue
+    output (desc.xp_out / xp_shift / xp_act): fp32 with the conv20 -> conv21 epilogue fusion, a segmented input, conv20 on
+    conv3d_wf (pair mode and split-K included: its prologue would otherwise be a pass of its own), res_conv on a form of the
+    bandwidth kernel that can (k1_side_xp)."""
+    cfg = _config()
+    if not (cfg.side_xp and cfg.epilogue_fuse) or len(seg_c) < 2 or math == "bf16" or groups != 1:
+        return False
+    return wf_launch(b, sum(seg_c), cout, n, h, w, pair_ok=True) and k1_side_xp(b, seg_c, cout, n, h, w)
+
+
+@_cached
+def emit_ll(b, cin, cout, n, h, w, groups=1, math="fp32", switch="emit_ll"):
+    """The convolution writes the halved LL band of its output instead of the output (desc.y_ll: a ResBlock's conv21 in front
+    of a down block) or, switch="emit_dwt", its whole Haar transform (desc.y_ll + y_hi: Conv_0 of a down block whose high bands
+    are kept): fp32, 8 bands, the convolution an unsplit conv3d_wf launch outside the pair mode, the conv20 -> conv21 fusion on
+    and the down block's Conv_2 after the LL band (config.conv2_after_ll: nothing else reads the full-resolution tensor)."""
+    cfg = _config()
+    if not (getattr(cfg, switch) and cfg.conv2_after_ll and cfg.epilogue_fuse) or math == "bf16" or n != 8 or groups != 1:
+        return False
+    return wf_quarter_ok(b, cin, cout, n, h, w) and wf_launch(b, cin, cout, n, h, w)
+
+
+@_cached
+def s2d_handover(b, c21, c0, n, h, w, groups=1, math="fp32"):
+    """The ResBlock in front of a main-branch down block hands its second output over in space-to-depth form (desc.y2_s2d), so
+    that Conv_0 + LL runs on conv3d_wf's composed-LL mode ("wfll").  c21 = (cin, cout) of the ResBlock's conv21 (groups: its
+    groups), c0 = (cin, cout) of Conv_0, math: "bf16" when the network computes in bf16 at all.  The composed weights exist
+    (ll_weight_ok), conv21 is an unsplit conv3d_wf launch -- asked of wf_route, not of conv3_family: pair mode is not excluded
+    and the prologue pass's size limit not applied (conv21 reads conv20's plain second output here) --, it produces Conv_0's
+    input channels, and the composed convolution's own grid is taken by the kernel (wfll_route)."""
+    cfg = _config()
+    if not (cfg.epilogue_fuse and cfg.ll_compose and cfg.winograd and cfg.wfll) or math == "bf16":
+        return False
+    if not (ll_weight_ok(c0[1], c0[0]) and wino_weight_ok(c21[1], c21[0], 3, groups)) or c21[1] != c0[0]:
+        return False
+    return (wf_route(b, c21[0], c21[1], n, h, w, groups)[0] and wf_quarter_ok(b, c21[0], c21[1], n, h, w, groups) and
+            wfll_route(b, c0[0], c0[1], n, h, w))
 
 
 # ---- the network's 3x3x3 convolutions ------------------------------------------------------------------------------------
@@ -252,13 +362,96 @@ def unet_table(channels, b, n, h, w, math="fp32"):
     for L in unet_conv3_layers(channels, h, w):
         if L.kind == "conv0_ll" and math == "fp32":
             # (the producer -- the ResBlock's conv21 in front -- writes the space-to-depth form only from an unsplit wf launch)
-            takes, split = wf_route(b, L.cin, L.cin, n, L.h, L.w)
-            fam = ll_family(b, L.cin, L.cout, n, L.h, L.w, producer_s2d=takes and split == 1)
+            fam = ll_family(b, L.cin, L.cout, n, L.h, L.w, producer_s2d=s2d_handover(b, (L.cin, L.cin), (L.cin, L.cout), n, L.h, L.w))
             if fam is not None:
                 rows.append((L, fam))
                 continue
         bf = math == "bf16" and L.cin // L.groups % 8 == 0 and L.cout // L.groups % 32 == 0 and (L.plain or L.cin // 3 % 8 == 0)
         rows.append((L, conv3_family(b, L.cin, L.cout, n, L.h, L.w, L.groups, plain=L.plain, math="bf16" if bf else "fp32")))
+    return rows
+
+
+# ---- the network's fusions ---------------------------------------------------------------------------------------------------
+Fusion = collections.namedtuple("Fusion", "block kind taken k1 passes")
+# kind: "stem" | "resblock" | "down" | "up"; taken: the fusions of this block, of "fold" (res_conv / Conv_2 folded), "side_xp",
+# "emit_ll", "s2d" (ResBlocks) and "wfll" | "ll" | "dwt" (what a down block's Conv_0 launch is, beyond a convolution);
+# k1: the 1x1x1 launches the block still makes; passes: the prologue (bf16: pack) passes in front of its 3x3x3 convolutions
+
+
+def unet_fusions(channels, b, n, h, w, math="fp32", fuse=None):
+    """[Fusion] of one inference forward (condition branch, then main branch) of a batch of b tiles with n bands: which
+    fusions each ResBlock and each wavelet block takes -- the block walk of WavBEST._condition / _forward_infer with the
+    decisions of _resblock / _down, on extents alone.  math: the network's compute mode; fuse: what WavBEST._producer_fuse
+    returns (the default: what it returns in fp32).  tests/test_host_logic.py holds WavBEST's own decisions to these rows."""
+    from . import ops
+    cfg = _config()
+    fuse_c, fuse_p = (cfg.producer_fuse and cfg.epilogue_fuse,) * 2 if fuse is None else fuse
+    c = list(channels)
+    lv = [(h >> k, w >> k) for k in range(4)]
+    rows = []
+
+    def m16(cout, cin, ksize=3):          # the math of one convolution (WavBEST._prepare's rule, its segment check included)
+        seg = [cin // 3] if cin % 3 == 0 else None
+        return "bf16" if math == "bf16" and ops.bf16_conv_supported(cout, cin, ksize, 1, seg) else "fp32"
+
+    def any16(*maths):
+        return "bf16" if "bf16" in maths else "fp32"
+
+    def passes(convs):                    # convs: (cin, cout, level, plain) -- a pass in front of every input that is not plain
+        return sum(1 for ci, co, k, plain in convs if not plain and conv3_family(
+            b, ci, co, n, *lv[k], plain=False, math=m16(co, ci)) in ("wf", "wf_pair", "staged", "bf16"))
+
+    def resblock(name, seg_c, cout, k, pre, emit, want_ll=False, to_conv0=False):
+        cin, (hh, ww) = sum(seg_c), lv[k]
+        m20, m21, mrc = m16(cout, cin), m16(cout, cout), m16(cout, cin, 1)
+        pair_fused = cfg.epilogue_fuse and m20 == m21
+        taken = []
+        if cin != cout:                   # (a res_conv exists)
+            if fold_k1(b, seg_c[0], cout, cout, n, hh, ww, 1, any16(m21, mrc), len(seg_c)):
+                taken.append("fold")
+            elif not pre and side_xp(b, tuple(seg_c), cout, n, hh, ww, 1, any16(m20, m21, mrc)):
+                taken.append("side_xp")
+        if want_ll and emit and pair_fused and emit_ll(b, cout, cout, n, hh, ww, 1, m21):
+            taken.append("emit_ll")
+        s2d = to_conv0 and emit and s2d_handover(b, (cout, cout), (cout, cout), n, hh, ww, 1, any16(math, m20, m21))
+        if s2d:
+            taken.append("s2d")
+        plain20 = (pre and pair_fused) or "side_xp" in taken
+        rows.append(Fusion(name, "resblock", tuple(taken), int(cin != cout and "fold" not in taken),
+                           passes([(cin, cout, k, plain20), (cout, cout, k, pair_fused)])))
+        return s2d
+
+    def down(name, k, main, pre, s2d):
+        ch, (hh, ww) = c[k + 1], lv[k]
+        pre32 = pre and math == "fp32"
+        conv0 = None
+        if main and pre32:
+            if s2d:
+                conv0 = "wfll"
+            elif cfg.ll_compose and ll_weight_ok(ch, ch) and ll_fits(b, ch, ch, n, hh, ww):
+                conv0 = "ll"
+        elif fuse_p and pre32 and emit_ll(b, ch, ch, n, hh, ww, 1, m16(ch, ch), "emit_dwt"):
+            conv0 = "dwt"
+        fold = cfg.conv2_after_ll and fold_k1(b, ch, ch, ch, n, hh // 2, ww // 2, 1, any16(m16(ch, ch), m16(ch, ch, 1)), 1)
+        convs = [(ch, ch, k + 1, bool(fuse_p))] + ([(ch, ch, k, pre)] if conv0 in (None, "dwt") else [])
+        rows.append(Fusion(name, "down", tuple(t for t in (conv0, "fold" if fold else None) if t), int(not fold), passes(convs)))
+
+    def stem(name):                       # (the stem writes conv21's modulated input where the producers fuse)
+        rows.append(Fusion(name, "stem", (), 0, passes([(c[0], c[0], 0, bool(fuse_p))])))
+
+    for branch in ("_1", ""):
+        stem("conv2" if not branch else "conv1")
+        for k in range(3):
+            blk = f"down{k + 1}{branch}"
+            s2d = resblock(blk + ".conv20", [c[k]], c[k + 1], k, fuse_c, fuse_c, want_ll=True, to_conv0=not branch)
+            down(blk + ".down", k, not branch, fuse_c, s2d)
+    resblock("middle1", [c[3]], c[3], 3, fuse_c, False)
+    for k, upn in ((3, "up1"), (2, "up2"), (1, "up3")):
+        resblock(upn + ".conv20", [c[k]] * 3, c[k - 1], k, False, fuse_c)
+        rows.append(Fusion(upn + ".up1", "up", (), 1, passes([(c[k - 1], c[k - 1], k, fuse_c), (c[k - 1], c[k - 1], k - 1, bool(fuse_p))])))
+    resblock("final.conv20", [c[0]] * 3, c[0], 0, False, fuse_c)
+    for k in (1, 2, 3):
+        resblock(f"final.conv2{k}", [c[0]], c[0], 0, fuse_c, fuse_c and k < 3)
     return rows
 
 

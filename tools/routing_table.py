@@ -5,7 +5,12 @@
 
 One block per case of tmdiff_amd.routing.BASELINE_CASES (BASELINE.json configs[0..4]; B in {1, 8, 32}, 4 and 8 bands, 64^2 and
 256^2 planes), one line per convolution of one inference forward (reference GeneralModel/Hyper_unet_general.py:600-636), then the
-families each case reaches and -- last -- which families NO case reaches.  tests/test_host_logic.py asserts the same."""
+families each case reaches and -- last -- which families NO case reaches.  tests/test_host_logic.py asserts the same.
+
+    python tools/routing_table.py --fusions > profiles/fusion_table.txt
+
+What the epilogues of the same forwards additionally do (tmdiff_amd.routing.unet_fusions): one line per ResBlock / wavelet block
+with the fusions it takes, and per case the 1x1x1 launches and prologue passes that remain."""
 import collections
 import os
 import sys
@@ -40,5 +45,24 @@ def main():
           + (", ".join(f for f in never if f not in other) or "none"))
 
 
+def fusions():
+    print("# fusions per block of one inference forward (tmdiff_amd/routing.py unet_fusions; switches: defaults of ops.config)")
+    print("# fold = res_conv / Conv_2 in the consumer's epilogue, side_xp = res_conv also writes conv20's prologue output,")
+    print("# emit_ll = conv21 writes LL(y) / 2, s2d = second output in space-to-depth form, wfll / ll = Conv_0 + LL composed,")
+    print("# dwt = Conv_0 writes the Haar transform; k1 = 1x1x1 launches left, passes = prologue passes left")
+    for label, ch, b, n, size, math in routing.BASELINE_CASES + routing.OTHER_CASES:
+        fuse = None
+        if math == "bf16":      # (WavBEST._producer_fuse: only if every convolution runs on the bf16 kernels)
+            all16 = all(c % 16 == 0 for c in ch) and all(
+                ops.bf16_conv_supported(L.cout, L.cin, 3, L.groups, [L.cin // 3] if L.cin % 3 == 0 else None)
+                for L in routing.unet_conv3_layers(ch, size, size))
+            fuse = (all16 and ops.config.producer_fuse and ops.config.epilogue_fuse,) * 2
+        rows = routing.unet_fusions(ch, b, n, size, size, math, fuse)
+        print(f"\n== {label}: channels {ch}, B = {b}, {n} bands, {size}x{size}, {math} -- 1x1x1 launches left: "
+              f"{sum(r.k1 for r in rows)} of 19, prologue passes left: {sum(r.passes for r in rows)}")
+        for r in rows:
+            print(f"  {r.block:16s} {r.kind:9s} k1 {r.k1} passes {r.passes}  {' '.join(r.taken) or '-'}")
+
+
 if __name__ == "__main__":
-    main()
+    fusions() if sys.argv[1:] == ["--fusions"] else main()
