@@ -605,6 +605,24 @@ int tmdiff_metrics_noref(const float* l_ms, int64_t l_ms_stride_b, int64_t l_ms_
                          int32_t w, double* out, void* workspace, size_t workspace_bytes, tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Resampling of full-resolution scenes (csrc/resample.hip; host definitions: tmdiff_amd/metrics.py).  Dense fp32 planes
+ * [planes, H, W]; nothing is allocated or synchronised, so a call can be captured into a graph on `stream`.
+ *  pyr_down: `levels` (1 or 2) steps of OpenCV's pyrDown with its defaults -- separable [1 4 6 4 1] / 16, horizontal pass then
+ *    vertical pass, border reflect-101, output extent (L + 1) / 2 per axis and level, sampled at the even coordinates.  Each
+ *    5-tap sum is (a + e) / 16 + (b + d) / 4 + c * 3 / 8 with fixed roundings; two levels run as one kernel that keeps level 1
+ *    in LDS, and equal two one-level calls bit for bit.  y is [planes, H', W'] with L' = (L + 1) / 2 applied `levels` times.
+ *    Every level's input extent must be >= 3: H, W >= 3 for one level, >= 5 for two.
+ *  upsample_bilinear: y [planes, ratio * h, ratio * w], ratio 2 or 4, half-pixel centres with the edge clamped:
+ *    src = (dst + 0.5) / ratio - 0.5 in [0, L - 1] (cv2.resize(INTER_LINEAR); F.interpolate(mode="bilinear",
+ *    align_corners=False)).  16-byte stores when ratio * w is a multiple of 4 and y is 16-byte aligned, with the same values.
+ * Element offsets are 32-bit: more than 2^31 - 1 input (pyr_down) or output (upsample_bilinear) elements, other `levels` /
+ * `ratio` or smaller extents return TMDIFF_E_UNSUPPORTED without launching.
+ * ------------------------------------------------------------------------------------ */
+int tmdiff_pyr_down(const float* x, float* y, int32_t planes, int32_t H, int32_t W, int32_t levels, tmdiff_stream_t stream);
+int tmdiff_upsample_bilinear(const float* x, float* y, int32_t planes, int32_t h, int32_t w, int32_t ratio,
+                             tmdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Standalone attention operators of core/Attention.py (imported by nothing in the reference; built because the
  * north star names them).  All fp32.
  *  attn_fwd : out = softmax(q k^T * scale [key mask]) v per (batch, head); fp32 MFMA, online softmax.

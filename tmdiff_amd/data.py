@@ -34,7 +34,8 @@ class LRHRDataset(Dataset):
         self.img_scale, self.phase = img_scale, phase
         keys = set(data.keys())
         arr = lambda k: torch.from_numpy(np.array(data[k][...], dtype=np.float32) / img_scale)
-        self.gt = arr("gt") if "gt" in keys else arr("lms")
+        self.has_gt = "gt" in keys          # False: a full-resolution file, to be scored without a reference (evaluate.val_dataset)
+        self.gt = arr("gt") if self.has_gt else arr("lms")
         self.ms, self.lms, self.pan = arr("ms"), arr("lms"), arr("pan")
         n = self.ms.shape[0]
         self.data_len = n if data_len is None or data_len <= 0 else min(data_len, n)

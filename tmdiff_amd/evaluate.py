@@ -7,6 +7,7 @@ import time
 
 import numpy as np
 import scipy.io as scio
+import torch
 
 from . import metrics
 
@@ -29,27 +30,48 @@ def _to_nchw01(img, min_max=(0.0, 1.0)):
     return ((t.clamp(lo, hi) - lo) / (hi - lo)).contiguous()
 
 
-def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=print, device_metrics=False):
+def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=print, device_metrics=False,
+                full_resolution=False):
     """``trainer`` is a ``tmdiff_amd.model.DDPM`` (or the reference's); ``dataset`` is the prompt name.
     Returns ``{"ssim_<dataset>": ..., "sam_<dataset>": ..., "sec_per_item": ...}``.
 
     ``device_metrics=True`` scores on the GPU instead (``ops.metrics_pair``: one pass per item over the two images, sums kept
     on the device, one synchronising read of the scores after the last item) and adds ``psnr_``, ``ergas_``, ``scc_``, ``cc_``
-    and ``q_<dataset>``.  The ``.mat`` files are the same in both modes (writing them is what still brings SR to the host)."""
+    and ``q_<dataset>``.  The ``.mat`` files are the same in both modes (writing them is what still brings SR to the host).
+
+    ``full_resolution=True`` is for files without ground truth (``LRHRDataset.has_gt`` is False: ``HR`` is only ``lms`` standing
+    in, and SSIM / SAM against it mean nothing).  Each item is scored without a reference on the GPU instead:
+    ``ops.metrics_noref(LR, PAN, ops.pyr_down(PAN), SR)``, with the low-resolution PAN and the workspace allocated once per
+    shape, sums kept on the device and one synchronising read at the end.  Returns ``{"d_lambda_<dataset>": ...,
+    "d_s_<dataset>": ..., "qnr_<dataset>": ..., "sec_per_item": ...}`` and no ``ssim_`` / ``sam_`` keys; the ``.mat`` files
+    are written as in the other modes.  ValueError when the visuals carry no ``LR`` or ``PAN``."""
     result_path = os.path.join(result_root, dataset)
     os.makedirs(result_path, exist_ok=True)
     scale = IMG_SCALE.get(dataset, 2047.0)
     ssim_sum = sam_sum = 0.0
     n = 0
     dev_sum, dev_ws = None, {}
+    full_sum, full_ws = None, {}
     t0 = time.time()
     for idx, val_data in enumerate(val_loader):
         trainer.feed_data(val_data)
         trainer.test(continous=continous, prompt=dataset)
         vis = trainer.get_current_visuals()
+        if full_resolution and not ("LR" in vis and "PAN" in vis):
+            raise ValueError(f"val_dataset(full_resolution=True): the visuals need 'LR' and 'PAN', got {sorted(vis)}")
         sr = to_hwc01(vis["SR"][-1])                       # last image of the returned stack (ref :136)
         scio.savemat(os.path.join(result_path, f"output_mulExm_{idx}.mat"), {"sr": sr * scale})
-        if "HR" in vis and device_metrics:
+        if full_resolution:
+            from . import ops
+            lr_d, pan_d, sr_d = _to_nchw01(vis["LR"]), _to_nchw01(vis["PAN"]), _to_nchw01(vis["SR"][-1])
+            key = (lr_d.shape, sr_d.shape)
+            if key not in full_ws:
+                full_ws[key] = (torch.empty(1, 1, *ops.pyr_down_shape(*pan_d.shape[2:]), device=pan_d.device),
+                                ops.metrics_workspace(*sr_d.shape, sr_d.device))
+            l_pan, ws = full_ws[key]
+            row = ops.metrics_noref(lr_d, pan_d, ops.pyr_down(pan_d, 2, out=l_pan), sr_d, workspace=ws)[0]
+            full_sum = row if full_sum is None else full_sum + row
+        elif "HR" in vis and device_metrics:
             from . import ops
             hr_d, sr_d = _to_nchw01(vis["HR"]), _to_nchw01(vis["SR"][-1])
             if hr_d.shape not in dev_ws:
@@ -61,6 +83,12 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
             ssim_sum += metrics.ssim(hr, sr, 1)
             sam_sum += metrics.sam(hr, sr)
         n += 1
+    if full_resolution:
+        total = full_sum.tolist() if full_sum is not None else [0.0] * len(metrics.NOREF_FIELDS)   # the one synchronising read
+        score = {**{f"{k}_{dataset}": v / max(n, 1) for k, v in zip(metrics.NOREF_FIELDS, total)},
+                 "sec_per_item": (time.time() - t0) / max(n, 1)}
+        log(dataset, score)
+        return score
     extra = {}
     if dev_sum is not None:
         total = dict(zip(metrics.PAIR_FIELDS, dev_sum.tolist()))                     # the one synchronising read

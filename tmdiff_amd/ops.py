@@ -1138,6 +1138,57 @@ def metrics_noref(l_ms, pan, l_pan, ps, out=None, workspace=None):
     return y
 
 
+# ---- resampling of full-resolution scenes (csrc/resample.hip; definitions: tmdiff_amd/metrics.py) --------------------
+def _resample_args(name, x, shape_of, out, limits):
+    """(x pointer, y, y pointer) of a resampling call: x float32 [B, C, H, W] on the GPU, contiguous, fewer than 2^31 elements
+    either side; ``shape_of(h, w)`` is the output's (H', W') or None when the extents are not taken."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
+        raise ValueError(f"{name}: need a contiguous float32 [B, C, H, W] tensor on the GPU ({limits})")
+    b, c, h, w = x.shape
+    hw = shape_of(h, w)
+    if hw is None or max(x.numel(), b * c * hw[0] * hw[1]) > 2 ** 31 - 1:
+        raise ValueError(f"{name}: shape {tuple(x.shape)} is not supported ({limits})")
+    shape = (b, c, *hw)
+    y = out if out is not None else torch.empty(shape, device=x.device, dtype=torch.float32)
+    if tuple(y.shape) != shape:
+        raise ValueError(f"{name}: out must be {shape}, got {tuple(y.shape)}")
+    return x.data_ptr(), y, _chk(y, "out")
+
+
+def pyr_down_shape(h, w, levels=2):
+    """(H', W') of ``pyr_down``: (L + 1) // 2 per axis and level."""
+    for _ in range(levels):
+        h, w = (h + 1) // 2, (w + 1) // 2
+    return h, w
+
+
+def pyr_down(x, levels=2, out=None):
+    """``levels`` (1 or 2) steps of OpenCV's pyrDown on x [B, C, H, W]: [1 4 6 4 1] / 16 along both axes, reflect-101 border,
+    every second pixel -> [B, C, H', W'] with L' = (L + 1) // 2 per level.  Two levels are one kernel and equal two one-level
+    calls bit for bit.  With ``out=`` nothing is allocated or synchronised (graph capture)."""
+    limits = "levels 1 or 2; H, W >= 3 for one level, >= 5 for two; fewer than 2^31 elements"
+    if levels not in (1, 2):
+        raise ValueError(f"pyr_down: levels={levels} ({limits})")
+    least = 5 if levels == 2 else 3
+    px, y, py = _resample_args("pyr_down", x, lambda h, w: pyr_down_shape(h, w, levels) if min(h, w) >= least else None, out, limits)
+    b, c, h, w = x.shape
+    check(lib.tmdiff_pyr_down(px, py, b * c, h, w, levels, stream_ptr()), "pyr_down")
+    return y
+
+
+def upsample_bilinear(x, ratio=4, out=None):
+    """x [B, C, h, w] -> [B, C, ratio * h, ratio * w], ratio 2 or 4: bilinear with half-pixel centres and a clamped edge
+    (cv2.resize(INTER_LINEAR), F.interpolate(mode="bilinear", align_corners=False)).  With ``out=`` nothing is allocated or
+    synchronised (graph capture)."""
+    limits = "ratio 2 or 4; fewer than 2^31 output elements"
+    if ratio not in (2, 4):
+        raise ValueError(f"upsample_bilinear: ratio={ratio} ({limits})")
+    px, y, py = _resample_args("upsample_bilinear", x, lambda h, w: (ratio * h, ratio * w) if min(h, w) >= 1 else None, out, limits)
+    b, c, h, w = x.shape
+    check(lib.tmdiff_upsample_bilinear(px, py, b * c, h, w, ratio, stream_ptr()), "upsample_bilinear")
+    return y
+
+
 # ---- backward-side wrappers (finetune path) -----------------------------------------------------------
 
 

@@ -135,7 +135,9 @@ def main(argv=None):
         if rank == 0:                       # (validation items are few; the other ranks wait at the barrier)
             for name, prompt in VAL_SETS:
                 if name in loaders:
-                    scores.update(evaluate.val_dataset(diffusion, prompt, loaders[name], results, log=logger.info))
+                    # a validation dataset's optional "full_resolution": score without ground truth (QNR) instead of SSIM / SAM
+                    kw = {"full_resolution": True} if opt["datasets"][name].get("full_resolution") else {}
+                    scores.update(evaluate.val_dataset(diffusion, prompt, loaders[name], results, log=logger.info, **kw))
         if world > 1:
             torch.distributed.barrier()
         return scores

@@ -1,0 +1,88 @@
+#!/usr/bin/env python3
+"""Achieved bytes per second of the resampling kernels (csrc/resample.hip): algorithmic bytes (input read once + output written
+once) over device time, each beside a device-to-device copy that moves the same number of bytes in the same run.
+
+Cases: the fused two-level pyramid step and a single level on PAN [8, 1, 512, 512] and [1, 1, 2048, 2048], the x4 upsampling of MS
+[8, 8, 128, 128].  Every working set is far below the 256 MiB Infinity Cache, so these are rates of cache-resident data and of
+launches a few microseconds long, not HBM streaming rates: the copy of equal size is the yardstick, and the 6.29 TB/s streaming
+copy that bench_hbm_kernels.py quotes is printed for scale only.
+
+Timing: device events around `--reps` back-to-back launches after a warm-up of the same length, repeated `--rounds` times with
+the cases interleaved; the median round is reported with the least and the greatest."""
+import argparse
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from tmdiff_amd import ops  # noqa: E402
+
+STREAM_COPY_GBS = 6290.0          # the copy rate tools/bench_hbm_kernels.py measures its kernels against
+
+
+def time_us(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--rounds", type=int, default=7)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_resample.py needs the GPU: a rate cannot be measured without one")
+    p = torch.cuda.get_device_properties(0)
+    print(f"device: {p.name} ({getattr(p, 'gcnArchName', '?')}), {p.multi_processor_count} CUs, {p.total_memory / 2 ** 30:.0f} GiB; "
+          f"torch {torch.__version__}, HIP {torch.version.hip}; reps {args.reps}, rounds {args.rounds}", flush=True)
+
+    cases = []          # (name, kernel call, bytes, copy call of the same bytes)
+
+    def add(name, x, fn):
+        y = fn(x, None)
+        nbytes = (x.numel() + y.numel()) * 4
+        src = torch.empty(nbytes // 8, device="cuda").normal_()
+        dst = torch.empty_like(src)
+        cases.append((name, lambda: fn(x, y), nbytes, lambda: dst.copy_(src)))
+
+    for shape in ((8, 1, 512, 512), (1, 1, 2048, 2048)):
+        pan = torch.rand(*shape, device="cuda")
+        add(f"pyr_down 2 levels (fused) {list(shape)}", pan, lambda x, o: ops.pyr_down(x, 2, out=o))
+        add(f"pyr_down 1 level          {list(shape)}", pan, lambda x, o: ops.pyr_down(x, 1, out=o))
+        # what the fused kernel replaces: two launches with level 1 written and read back
+        half = ops.pyr_down(pan, 1)
+        quarter = ops.pyr_down(half, 1)
+        nbytes = (pan.numel() + quarter.numel()) * 4
+        src = torch.empty(nbytes // 8, device="cuda").normal_()
+        dst = torch.empty_like(src)
+        cases.append((f"pyr_down 1 + 1 levels     {list(shape)}",
+                      lambda pan=pan, half=half, quarter=quarter: ops.pyr_down(ops.pyr_down(pan, 1, out=half), 1, out=quarter),
+                      nbytes, lambda dst=dst, src=src: dst.copy_(src)))
+    ms = torch.rand(8, 8, 128, 128, device="cuda")
+    add("upsample_bilinear x4      [8, 8, 128, 128]", ms, lambda x, o: ops.upsample_bilinear(x, 4, out=o))
+
+    times = [([], []) for _ in cases]
+    for _ in range(args.rounds):
+        for (name, fn, nbytes, copy), (tk, tc) in zip(cases, times):
+            time_us(fn, args.reps)                         # warm-up of this case
+            tk.append(time_us(fn, args.reps))
+            time_us(copy, args.reps)
+            tc.append(time_us(copy, args.reps))
+    print(f"{'case':50s} {'MiB':>6s} {'us (min..max)':>22s} {'GB/s':>8s} | {'copy us':>8s} {'copy GB/s':>9s} | "
+          f"{'of copy':>7s} {'of 6.29 TB/s':>12s}")
+    for (name, _, nbytes, _), (tk, tc) in zip(cases, times):
+        k, c = statistics.median(tk), statistics.median(tc)
+        gbs, cgbs = nbytes / k / 1e3, nbytes / c / 1e3
+        print(f"{name:50s} {nbytes / 2 ** 20:6.1f} {k:8.2f} ({min(tk):5.2f}..{max(tk):5.2f}) {gbs:8.1f} | {c:8.2f} {cgbs:9.1f} | "
+              f"{100 * gbs / cgbs:6.1f}% {100 * gbs / STREAM_COPY_GBS:11.1f}%", flush=True)
+
+
+if __name__ == "__main__":
+    main()
