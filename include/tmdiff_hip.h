@@ -615,12 +615,22 @@ int tmdiff_metrics_noref(const float* l_ms, int64_t l_ms_stride_b, int64_t l_ms_
  *  upsample_bilinear: y [planes, ratio * h, ratio * w], ratio 2 or 4, half-pixel centres with the edge clamped:
  *    src = (dst + 0.5) / ratio - 0.5 in [0, L - 1] (cv2.resize(INTER_LINEAR); F.interpolate(mode="bilinear",
  *    align_corners=False)).  16-byte stores when ratio * w is a multiple of 4 and y is 16-byte aligned, with the same values.
- * Element offsets are 32-bit: more than 2^31 - 1 input (pyr_down) or output (upsample_bilinear) elements, other `levels` /
- * `ratio` or smaller extents return TMDIFF_E_UNSUPPORTED without launching.
+ *  upsample_poly23: y [planes, ratio * h, ratio * w], ratio 2 or 4: the Pansharpening Toolbox's interp23tap (the `lms` of the
+ *    PanCollection files).  Per x2 stage and axis, H then W, with circular borders: the samples go to the outputs of parity
+ *    `phase` (u[2k + phase] = x[k], a plain copy) and the outputs between become sum_j a_j (x[lo - j] + x[lo + 1 + j]), j = 0..5,
+ *    over the six samples either side, a = {0.61066818237, -0.145397186478, 0.043619155884, -0.010385513306, 0.001615524292,
+ *    -0.000120162964} (twice the odd taps of the 23-tap half-band kernel): pair sums first, then fused multiply-adds from j = 5
+ *    down to 0.  ratio 4 is a phase-1 stage followed by a phase-0 stage in one kernel that keeps the x2 image in LDS, and equals
+ *    the two calls bit for bit: y[4i + 2, 4j + 2] = x[i, j].  `phase` (0 or 1) selects the stage at ratio 2 and must be 1 at
+ *    ratio 4.  16-byte stores when ratio * w is a multiple of 4 and y is 16-byte aligned, with the same values.
+ * Element offsets are 32-bit: more than 2^31 - 1 input (pyr_down) or output (upsample_*) elements, other `levels` / `ratio` /
+ * `phase` or smaller extents return TMDIFF_E_UNSUPPORTED without launching (upsample_poly23: negative `planes` too).
  * ------------------------------------------------------------------------------------ */
 int tmdiff_pyr_down(const float* x, float* y, int32_t planes, int32_t H, int32_t W, int32_t levels, tmdiff_stream_t stream);
 int tmdiff_upsample_bilinear(const float* x, float* y, int32_t planes, int32_t h, int32_t w, int32_t ratio,
                              tmdiff_stream_t stream);
+int tmdiff_upsample_poly23(const float* x, float* y, int32_t planes, int32_t h, int32_t w, int32_t ratio, int32_t phase,
+                           tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Standalone attention operators of core/Attention.py (imported by nothing in the reference; built because the

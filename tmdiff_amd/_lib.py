@@ -177,6 +177,7 @@ SIGNATURES.update({
     # resampling (csrc/resample.hip): (planes, H, W, levels | ratio) after the two tensors
     "tmdiff_pyr_down": (C.c_int, [vp, vp] + [C.c_int32] * 4 + [vp]),
     "tmdiff_upsample_bilinear": (C.c_int, [vp, vp] + [C.c_int32] * 4 + [vp]),
+    "tmdiff_upsample_poly23": (C.c_int, [vp, vp] + [C.c_int32] * 5 + [vp]),      # ... ratio, phase
 })
 
 

@@ -4,7 +4,8 @@
 ``pan`` ([N, C, h, w] digital numbers) from an ``.h5`` file (needs h5py, which this image does not ship), an ``.npz`` file
 or any mapping of arrays, divides by the sensor range (1023 for GaoFen-2 files -- "gf2" in the path -- else 2047) and
 serves the dictionaries the trainer consumes: ``LR`` (ms), ``PAN``, ``MS`` (the upsampled lms), ``HR`` (gt),
-``Res`` = HR - MS.
+``Res`` = HR - MS.  A raw file that has ``ms`` and ``pan`` but no ``lms`` gets it once, at construction, from
+``metrics.upsample_poly23(ms, pan width // ms width)``: the interpolator that made the ``lms`` of the PanCollection files.
 """
 import numpy as np
 import torch
@@ -35,8 +36,13 @@ class LRHRDataset(Dataset):
         keys = set(data.keys())
         arr = lambda k: torch.from_numpy(np.array(data[k][...], dtype=np.float32) / img_scale)
         self.has_gt = "gt" in keys          # False: a full-resolution file, to be scored without a reference (evaluate.val_dataset)
-        self.gt = arr("gt") if self.has_gt else arr("lms")
-        self.ms, self.lms, self.pan = arr("ms"), arr("lms"), arr("pan")
+        self.ms, self.pan = arr("ms"), arr("pan")
+        if "lms" in keys:
+            self.lms = arr("lms")
+        else:                               # a raw (ms, pan) file: lms as PanCollection makes it
+            from .metrics import upsample_poly23
+            self.lms = torch.from_numpy(upsample_poly23(self.ms, self.pan.shape[-1] // self.ms.shape[-1])).float()
+        self.gt = arr("gt") if self.has_gt else self.lms
         n = self.ms.shape[0]
         self.data_len = n if data_len is None or data_len <= 0 else min(data_len, n)
 

@@ -1189,6 +1189,21 @@ def upsample_bilinear(x, ratio=4, out=None):
     return y
 
 
+def upsample_poly23(x, ratio=4, out=None, phase=1):
+    """x [B, C, h, w] -> [B, C, ratio * h, ratio * w], ratio 2 or 4: the Pansharpening Toolbox's interp23tap, which makes the
+    ``lms`` of the PanCollection files (definition: ``metrics.upsample_poly23``).  Per x2 stage the 23-tap half-band polynomial
+    kernel with circular borders, along H then W; ``phase`` 1 puts the samples at the odd outputs, 0 at the even ones.  Ratio 4
+    is a phase-1 stage followed by a phase-0 stage in one kernel, bit for bit the two calls: ``y[..., 2::4, 2::4] == x``;
+    ``phase`` must be 1 there.  With ``out=`` nothing is allocated or synchronised (graph capture)."""
+    limits = "ratio 2 or 4; phase 0 or 1, 1 at ratio 4; fewer than 2^31 output elements"
+    if ratio not in (2, 4) or phase not in (0, 1) or (ratio == 4 and phase != 1):
+        raise ValueError(f"upsample_poly23: ratio={ratio} phase={phase} ({limits})")
+    px, y, py = _resample_args("upsample_poly23", x, lambda h, w: (ratio * h, ratio * w) if min(h, w) >= 1 else None, out, limits)
+    b, c, h, w = x.shape
+    check(lib.tmdiff_upsample_poly23(px, py, b * c, h, w, ratio, phase, stream_ptr()), "upsample_poly23")
+    return y
+
+
 # ---- backward-side wrappers (finetune path) -----------------------------------------------------------
 
 

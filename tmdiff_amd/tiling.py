@@ -203,17 +203,21 @@ def sample_tiled(diffusion, scene, prompt, tile=64, method="dpmsolver", steps=20
 
 
 @torch.no_grad()
-def fuse_scene(diffusion, lr_ms, pan, prompt, ratio=4, score=False, **sample_tiled_kwargs):
-    """From the raw pair to the fused scene: lr_ms [B, C, h, w] is upsampled by ``ratio`` (2 or 4) on the device
-    (``ops.upsample_bilinear``, the reference's cv2.resize(INTER_LINEAR)) into the ``MS`` the network is conditioned on, and
-    ``sample_tiled`` fuses {"MS", "PAN"} with pan [B, 1, ratio * h, ratio * w]; the keyword arguments are ``sample_tiled``'s.
+def fuse_scene(diffusion, lr_ms, pan, prompt, ratio=4, score=False, interp="bilinear", **sample_tiled_kwargs):
+    """From the raw pair to the fused scene: lr_ms [B, C, h, w] is upsampled by ``ratio`` (2 or 4) on the device into the ``MS``
+    the network is conditioned on -- ``interp="bilinear"``: ``ops.upsample_bilinear``, the reference's cv2.resize(INTER_LINEAR);
+    ``interp="poly23"``: ``ops.upsample_poly23``, the interpolator that made the ``lms`` of the PanCollection files, for any
+    checkpoint trained on them -- and ``sample_tiled`` fuses {"MS", "PAN"} with pan [B, 1, ratio * h, ratio * w]; the other
+    keyword arguments are ``sample_tiled``'s.
     ``score=True`` returns (scene, ``metrics.quality_fullres(lr_ms, pan, scene)``): D_lambda, D_s and QNR, which takes ratio 4
     (the low-resolution PAN is two pyramid levels of pan)."""
+    if interp not in ("bilinear", "poly23"):
+        raise ValueError(f"fuse_scene: interp={interp!r} ('bilinear' or 'poly23')")
     if lr_ms.dim() != 4 or pan.dim() != 4 or pan.shape[0] != lr_ms.shape[0] or pan.shape[1] != 1 or \
             tuple(pan.shape[2:]) != (ratio * lr_ms.shape[2], ratio * lr_ms.shape[3]):
         raise ValueError(f"fuse_scene: pan {tuple(pan.shape)} is not [B, 1, {ratio} h, {ratio} w] of lr_ms {tuple(lr_ms.shape)}")
     lr_ms, pan = lr_ms.float().contiguous(), pan.float().contiguous()
-    ms = ops.upsample_bilinear(lr_ms, ratio)
+    ms = ops.upsample_poly23(lr_ms, ratio) if interp == "poly23" else ops.upsample_bilinear(lr_ms, ratio)
     scene = sample_tiled(diffusion, {"MS": ms, "PAN": pan}, prompt, **sample_tiled_kwargs)
     if not score:
         return scene

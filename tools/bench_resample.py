@@ -3,7 +3,10 @@
 once) over device time, each beside a device-to-device copy that moves the same number of bytes in the same run.
 
 Cases: the fused two-level pyramid step and a single level on PAN [8, 1, 512, 512] and [1, 1, 2048, 2048], the x4 upsampling of MS
-[8, 8, 128, 128].  Every working set is far below the 256 MiB Infinity Cache, so these are rates of cache-resident data and of
+[8, 8, 128, 128], and the 23-tap polynomial upsampling (`upsample_poly23`) of MS [8, 8, 128, 128] and [1, 8, 512, 512]: x2, fused x4,
+and the two x2 launches the fused kernel replaces, each beside a copy that writes the same number of output bytes (the kernel
+reads 1/4 or 1/16 of what it writes, the copy reads as much as it writes; "of copy" is copy time over kernel time either way).
+Every working set is far below the 256 MiB Infinity Cache, so these are rates of cache-resident data and of
 launches a few microseconds long, not HBM streaming rates: the copy of equal size is the yardstick, and the 6.29 TB/s streaming
 copy that bench_hbm_kernels.py quotes is printed for scale only.
 
@@ -43,14 +46,19 @@ def main():
     print(f"device: {p.name} ({getattr(p, 'gcnArchName', '?')}), {p.multi_processor_count} CUs, {p.total_memory / 2 ** 30:.0f} GiB; "
           f"torch {torch.__version__}, HIP {torch.version.hip}; reps {args.reps}, rounds {args.rounds}", flush=True)
 
-    cases = []          # (name, kernel call, bytes, copy call of the same bytes)
+    cases = []          # (name, kernel call, bytes, copy call, bytes the copy moves)
 
     def add(name, x, fn):
         y = fn(x, None)
         nbytes = (x.numel() + y.numel()) * 4
         src = torch.empty(nbytes // 8, device="cuda").normal_()
         dst = torch.empty_like(src)
-        cases.append((name, lambda: fn(x, y), nbytes, lambda: dst.copy_(src)))
+        cases.append((name, lambda: fn(x, y), nbytes, lambda: dst.copy_(src), nbytes))
+
+    def add_poly23(name, x, y, fn):          # the copy writes y's bytes
+        src = torch.empty_like(y).normal_()
+        dst = torch.empty_like(y)
+        cases.append((name, fn, (x.numel() + y.numel()) * 4, lambda: dst.copy_(src), 2 * y.numel() * 4))
 
     for shape in ((8, 1, 512, 512), (1, 1, 2048, 2048)):
         pan = torch.rand(*shape, device="cuda")
@@ -64,24 +72,33 @@ def main():
         dst = torch.empty_like(src)
         cases.append((f"pyr_down 1 + 1 levels     {list(shape)}",
                       lambda pan=pan, half=half, quarter=quarter: ops.pyr_down(ops.pyr_down(pan, 1, out=half), 1, out=quarter),
-                      nbytes, lambda dst=dst, src=src: dst.copy_(src)))
+                      nbytes, lambda dst=dst, src=src: dst.copy_(src), nbytes))
     ms = torch.rand(8, 8, 128, 128, device="cuda")
     add("upsample_bilinear x4      [8, 8, 128, 128]", ms, lambda x, o: ops.upsample_bilinear(x, 4, out=o))
 
+    for shape in ((8, 8, 128, 128), (1, 8, 512, 512)):
+        ms = torch.randn(*shape, device="cuda")
+        half, full = ops.upsample_poly23(ms, 2), ops.upsample_poly23(ms, 4)
+        add_poly23(f"upsample_poly23 x2        {list(shape)}", ms, half, lambda ms=ms, half=half: ops.upsample_poly23(ms, 2, out=half))
+        add_poly23(f"upsample_poly23 x4 (fused) {list(shape)}", ms, full, lambda ms=ms, full=full: ops.upsample_poly23(ms, 4, out=full))
+        # what the fused kernel replaces: two launches with the x2 image written and read back
+        add_poly23(f"upsample_poly23 x2 + x2   {list(shape)}", ms, full, lambda ms=ms, half=half, full=full: ops.upsample_poly23(
+            ops.upsample_poly23(ms, 2, out=half), 2, out=full, phase=0))
+
     times = [([], []) for _ in cases]
     for _ in range(args.rounds):
-        for (name, fn, nbytes, copy), (tk, tc) in zip(cases, times):
+        for (name, fn, nbytes, copy, cbytes), (tk, tc) in zip(cases, times):
             time_us(fn, args.reps)                         # warm-up of this case
             tk.append(time_us(fn, args.reps))
             time_us(copy, args.reps)
             tc.append(time_us(copy, args.reps))
     print(f"{'case':50s} {'MiB':>6s} {'us (min..max)':>22s} {'GB/s':>8s} | {'copy us':>8s} {'copy GB/s':>9s} | "
           f"{'of copy':>7s} {'of 6.29 TB/s':>12s}")
-    for (name, _, nbytes, _), (tk, tc) in zip(cases, times):
+    for (name, _, nbytes, _, cbytes), (tk, tc) in zip(cases, times):
         k, c = statistics.median(tk), statistics.median(tc)
-        gbs, cgbs = nbytes / k / 1e3, nbytes / c / 1e3
+        gbs, cgbs = nbytes / k / 1e3, cbytes / c / 1e3
         print(f"{name:50s} {nbytes / 2 ** 20:6.1f} {k:8.2f} ({min(tk):5.2f}..{max(tk):5.2f}) {gbs:8.1f} | {c:8.2f} {cgbs:9.1f} | "
-              f"{100 * gbs / cgbs:6.1f}% {100 * gbs / STREAM_COPY_GBS:11.1f}%", flush=True)
+              f"{100 * c / k:6.1f}% {100 * gbs / STREAM_COPY_GBS:11.1f}%", flush=True)
 
 
 if __name__ == "__main__":
