@@ -109,7 +109,9 @@ def test_small_network_takes_and_declines_every_epilogue_fusion():
     (a) the launches per C entry point are those recorded from the same forward before the fusion rules moved into
     tmdiff_amd.routing (the literals below: a moved rule that decided differently would change them); (b) the output equals
     the forward's with the five fusions switched off, within the bound of test_config2_batch32_epilogue_fusions_switched_off
-    (another summation order where a convolution is folded)."""
+    (another summation order where a convolution is folded); (c) the plans the model executed are the tables': in both switch
+    settings the recorded launches agree with routing.unet_fusions / unet_table of the same case (1x1x1 launches left, composed
+    Conv_0 + LL launches per kernel, conv3d_wf launches)."""
     import collections
     from tmdiff_amd import ops, routing
     channels, b, n, size = [32, 64, 128, 128], 4, 8, 64
@@ -123,20 +125,26 @@ def test_small_network_takes_and_declines_every_epilogue_fusion():
     d = {k: cu(v) for k, v in case_inputs(41, b, n, size).items()}
     t = torch.tensor([[650.0], [12.0], [333.0], [901.0]]).cuda()
 
-    def run():
+    def run():          # (output, launches per entry point, the same launches as the tables of the current switches give them)
+        rows, fams = routing.unet_fusions(channels, b, n, size, size), [f for _, f in routing.unet_table(channels, b, n, size, size)]
+        table = {"conv3d_fwd_k1": sum(r.k1 for r in rows), "conv3d_ll_fwd": sum("ll" in r.taken for r in rows),
+                 "conv3d_wfll_fwd": sum("wfll" in r.taken for r in rows), "conv3d_wf_fwd": fams.count("wf") + fams.count("wf_pair")}
         ops.COUNTS = collections.Counter()
         try:
             with torch.no_grad():
-                return net(d["x_t"], t, d["PAN"], d["MS"], "WV3"), dict(ops.COUNTS)
+                return net(d["x_t"], t, d["PAN"], d["MS"], "WV3"), dict(ops.COUNTS), table
         finally:
             ops.COUNTS = None
 
     with ops.config.override(wino_min_blocks=1):
-        y_on, c_on = run()
+        y_on, c_on, t_on = run()
         with ops.config.override(fuse_res_conv=False, side_xp=False, emit_ll=False, emit_dwt=False, wfll=False):
-            y_off, c_off = run()
-    print("fused:", sorted(c_on.items()), "unfused:", sorted(c_off.items()))
+            y_off, c_off, t_off = run()
+    print("fused:", sorted(c_on.items()), "tables:", sorted(t_on.items()))
+    print("unfused:", sorted(c_off.items()), "tables:", sorted(t_off.items()))
     assert c_on == _FUSION_CASE_COUNTS
+    assert {k: c_on.get(k, 0) for k in t_on} == t_on
+    assert {k: c_off.get(k, 0) for k in t_off} == t_off
     assert_close(y_off, y_on, 1e-5, 2e-6, "the five fusions off vs on")
 
 

@@ -822,16 +822,17 @@ def test_network_routes_respect_size_limits():
     inside the limits."""
     from tmdiff_amd.Hyper_unet_general import WavBEST
     net = WavBEST(channels=[64, 128, 128, 128])
-    P = {"bf16": set(), "w_wino": {"down1.conv20.conv21": object(), "down1.Conv_1": object()}, "w_wfll": {}}
+    P = {"bf16": set()}
 
     class X:         # a stand-in with the extents of a tensor (nothing is allocated)
         def __init__(self, *shape):
             self.shape = shape
 
-    assert net._fold_res_conv(P, "down1.conv20", [X(1, 64, 4, 2048, 2044)]) is not None
-    assert net._fold_res_conv(P, "down1.conv20", [X(1, 64, 4, 2048, 2048)]) is None          # 64 x 2^24 = 2^30
+    fold = lambda *shape: net._resblock_plan(P, "down1.conv20", [X(*shape)], True, True, want_ll=True, to_conv0=True).fold
+    assert fold(1, 64, 4, 2048, 2044) and not fold(1, 64, 4, 2048, 2048)           # 64 x 2^24 = 2^30
     assert net.down1.down.Conv_0.in_channels == 128           # 128 x 2^23 = 2^30
-    assert net._ll_fits("down1.down", X(1, 128, 8, 1024, 1022)) and not net._ll_fits("down1.down", X(1, 128, 8, 1024, 1024))
+    conv0 = lambda *shape: net._down_plan(P, "down1.down", shape, True, True, False, True).conv0
+    assert conv0(1, 128, 8, 1024, 1022) == "ll" and conv0(1, 128, 8, 1024, 1024) is None
     # the same four facts asked of the rules themselves: functions of the extents, no network
     from tmdiff_amd import routing
     assert routing.fold_k1(1, 64, 128, 128, 4, 2048, 2044) and not routing.fold_k1(1, 64, 128, 128, 4, 2048, 2048)
@@ -868,10 +869,8 @@ def test_fusion_table_of_the_baseline_configs():
 
 
 def _model_fusions(net, b, n, size):
-    """{block: fusions taken} as WavBEST's own methods decide them on stand-ins with the extents of the tensors of one fp32
-    inference forward, asked in _resblock's / _down's order (a CPU module: no _prepare, nothing allocated)."""
-    from tmdiff_amd import ops
-
+    """{block: fusions taken} of the plans a CPU WavBEST asks for (_resblock_plan / _down_plan: what _resblock / _down execute),
+    on stand-ins with the extents of the tensors of one fp32 inference forward (no _prepare, nothing allocated)."""
     class X:
         def __init__(self, ch, k):
             self.shape = (b, ch, n, size >> k, size >> k)
@@ -879,36 +878,17 @@ def _model_fusions(net, b, n, size):
     P, c, got = {"bf16": set()}, net.channels, {}
     fuse_c, fuse = net._producer_fuse(P)
 
-    def resblock(name, seg_c, k, pre, emit, want_ll=False, to_conv0=False):
-        segs, taken = [X(ch, k) for ch in seg_c], []
-        if isinstance(net.get_submodule(name).res_conv, torch.nn.Conv3d):
-            if net._fold_res_conv(P, name, segs) is not None:
-                taken.append("fold")
-            elif not pre and net._side_xp(P, name, segs):
-                taken.append("side_xp")
-        if want_ll and emit and ops.config.epilogue_fuse and net._emit_ll(P, name, segs[0]):
-            taken.append("emit_ll")
-        s2d = bool(to_conv0 and emit and net._ll_s2d(P, name[:-len(".conv20")], segs[0]))
-        got[name] = tuple(taken + ["s2d"] * s2d)
-        return s2d
-
-    def down(name, k, main, pre, s2d):
-        ch, conv0 = c[k + 1], None
-        if main and pre:
-            if s2d:
-                conv0 = "wfll"
-            elif ops.config.ll_compose and ops.ll_conv_supported(ch, ch) and net._ll_fits(name, X(ch, k)):
-                conv0 = "ll"
-        elif fuse and pre and net._emit_ll(P, name, X(ch, k), conv=".Conv_0", switch="emit_dwt"):
-            conv0 = "dwt"
-        fold = ops.config.conv2_after_ll and net._fold_res_conv(P, name, [X(ch, k + 1)], k1=".Conv_2", k3=".Conv_1") is not None
-        got[name] = tuple(t for t in (conv0, "fold" if fold else None) if t)
+    def resblock(name, seg_c, k, pre, emit, **kw):
+        p = net._resblock_plan(P, name, [X(ch, k) for ch in seg_c], bool(pre), bool(emit), **kw)
+        got[name] = tuple(f for f in ("fold", "side_xp", "emit_ll", "s2d") if getattr(p, f))
+        return p.s2d
 
     for branch in ("_1", ""):
         for k in range(3):
             blk = f"down{k + 1}{branch}"
             s2d = resblock(blk + ".conv20", [c[k]], k, fuse_c, fuse_c, want_ll=True, to_conv0=not branch)
-            down(blk + ".down", k, not branch, fuse_c, s2d)
+            p = net._down_plan(P, blk + ".down", X(c[k + 1], k).shape, not branch, bool(fuse_c), s2d, fuse)
+            got[blk + ".down"] = tuple(t for t in (p.conv0, "fold" if p.fold else None) if t)
     resblock("middle1", [c[3]], 3, fuse_c, False)
     for k, upn in ((3, "up1"), (2, "up2"), (1, "up3")):
         resblock(upn + ".conv20", [c[k]] * 3, k, False, fuse_c)
@@ -926,8 +906,8 @@ def _model_fusions(net, b, n, size):
 ])
 def test_model_decisions_equal_the_fusion_rows(channels, b, n, size, switches):
     """The block walk and the channel bookkeeping of routing.unet_fusions against the real module tree: what a CPU WavBEST
-    decides for every ResBlock and every down block (its own methods, which read the channel counts off its modules) is that
-    block's row."""
+    plans for every ResBlock and every down block (through the entry _resblock / _down use, which reads the channel counts off
+    its modules) is that block's row."""
     from tmdiff_amd import ops, routing
     from tmdiff_amd.Hyper_unet_general import WavBEST
     net = WavBEST(channels=channels)

@@ -388,7 +388,7 @@ class WavBEST(nn.Module):
                 if ops.ll_conv_supported(m.out_channels, m.in_channels, m.kernel_size[0], m.groups):
                     prep["w_ll"][blk + ".down.Conv_0"] = ops.pack_conv_weight_ll(m.weight.detach().float().contiguous(), 0.5)
                     # ... and with Winograd along the bands on top (conv3d_wf's composed-LL mode), for the launches whose producer
-                    # can hand over its second output in space-to-depth form (_ll_s2d)
+                    # can hand over its second output in space-to-depth form (routing.resblock_plan: s2d)
                     if ops.config.winograd and ops.config.wfll and m.out_channels % 32 == 0:
                         prep["w_wfll"][blk + ".down.Conv_0"] = ops.pack_conv_weight_wfll(m.weight.detach().float().contiguous(), 0.5)
         shift, scale = self._projection_layers()
@@ -399,16 +399,21 @@ class WavBEST(nn.Module):
         return prep
 
     # ---- fused building blocks -------------------------------------------------------------------
-    def _conv(self, P, name, segs, use_bias=True, bias_scale=1.0, bias=None, **kw):
+    def _conv(self, P, name, segs, use_bias=True, bias_scale=1.0, bias=None, emit=False, **kw):
         """One convolution of the fused inference graph on the kernel family tmdiff_amd.routing picks for its extents.
-        bias: another module's bias instead of this one's (a folded res_conv's)."""
+        bias: another module's bias instead of this one's (a folded res_conv's).  emit: the consumer's prologue spec, as in
+        ops.conv3d; given as None (a consumer that turns out to want no second output) the result is (y, None), so such a
+        call site unpacks (y, y2) either way."""
         m = self.get_submodule(name)
         if bias is None:
             bias = m.bias.detach() if (use_bias and m.bias is not None) else None
+        if emit:
+            kw["emit"] = emit
         math = "bf16" if name in P["bf16"] else "fp32"
         if m.kernel_size[0] != 3:
-            return ops.conv3d(segs, P["w"][name], m.out_channels, m.kernel_size[0], groups=m.groups, math=math, bias=bias,
-                              bias_scale=bias_scale, **kw)
+            out = ops.conv3d(segs, P["w"][name], m.out_channels, m.kernel_size[0], groups=m.groups, math=math, bias=bias,
+                             bias_scale=bias_scale, **kw)
+            return (out, None) if emit is None else out
         ww = P["w_wino"].get(name)        # the Winograd forms of this weight, packed on first use (None: shape not taken)
 
         def packed(planes):               # transform-pass kernels (tmdiff_amd.fallback): per plane count of the transform
@@ -422,17 +427,8 @@ class WavBEST(nn.Module):
             return ww["wf"]
 
         weights = ops.ConvWeights(lambda: P["w"][name], packed_wf if ww is not None else None, packed if ww is not None else None)
-        return ops.conv3d_auto(segs, weights, m.out_channels, groups=m.groups, math=math, bias=bias, bias_scale=bias_scale, **kw)
-
-    @staticmethod
-    def _shift(P, S, name):
-        ptr, stride = P["shift_bank"].slot(S["shift"], name)
-        return {"in_shift": ptr, "shift_stride": stride}
-
-    @staticmethod
-    def _scale(P, S, name):
-        ptr, stride = P["scale_bank"].slot(S["scale"], name)
-        return {"in_scale": ptr, "scale_stride": stride}
+        out = ops.conv3d_auto(segs, weights, m.out_channels, groups=m.groups, math=math, bias=bias, bias_scale=bias_scale, **kw)
+        return (out, None) if emit is None else out
 
     # Producer-side prologues (fp32 inference): wherever a tensor has ONE convolution as its consumer, the kernel that
     # produces it also writes the consumer's prologue output act(y + shift) * scale (a second output of a convolution's
@@ -442,6 +438,8 @@ class WavBEST(nn.Module):
     # as the consumer-side prologue.  `pre` = such a tensor for a block's first convolution; `emit` = the prologue spec
     # of the block's consumer.  Multi-segment consumers (the up path's conv20) keep their own prologue pass.
     def _spec(self, P, S, shift=None, scale=None, act=True):
+        """The prologue act(x + shift) * scale of a convolution (shift, scale: names of projection layers), as its producer
+        takes it (emit=, ll_prologue=, out0_prologue=, side_xp=)."""
         d = {"act": act}
         if shift is not None:
             d["shift"], d["shift_stride"] = P["shift_bank"].slot(S["shift"], shift)
@@ -449,100 +447,76 @@ class WavBEST(nn.Module):
             d["scale"], d["scale_stride"] = P["scale_bank"].slot(S["scale"], scale)
         return d
 
-    def _resblock(self, P, S, name, segs, flag, pre=None, emit=None, want_ll=False):
+    @staticmethod
+    def _own(spec):
+        """The same prologue as the keywords of the convolution itself, where no producer applied it."""
+        return dict(in_act=spec["act"], in_shift=spec.get("shift"), shift_stride=spec.get("shift_stride", 0),
+                    in_scale=spec.get("scale"), scale_stride=spec.get("scale_stride", 0))
+
+    # Which launches take which epilogue form is decided in tmdiff_amd.routing: resblock_plan / down_plan compose its rules
+    # (functions of extents, switches and math) per block.  What is the model's: the channel counts and the set of bf16
+    # convolutions, gathered here -- from tensors or from stand-ins with a .shape (tests/test_host_logic.py, on a CPU module).
+    @staticmethod
+    def _math(P, name):
+        return "bf16" if name in P["bf16"] else "fp32"
+
+    def _resblock_plan(self, P, name, segs, pre, emit, want_ll=False, to_conv0=False):
+        b, _, n, h, w = segs[0].shape
+        maths = (*(self._math(P, name + k) for k in (".conv20", ".conv21", ".res_conv")), self.compute_dtype)
+        return routing.resblock_plan(b, tuple(s.shape[1] for s in segs), self.get_submodule(name + ".conv20").out_channels, n, h, w,
+                                     maths, pre, emit, want_ll, to_conv0)
+
+    def _down_plan(self, P, name, shape, main, pre, s2d, fuse):
+        b, ch, n, h, w = shape
+        return routing.down_plan(b, ch, n, h, w, tuple(self._math(P, name + k) for k in (".Conv_0", ".Conv_1", ".Conv_2")),
+                                 main, pre, s2d, fuse)
+
+    def _resblock(self, P, S, name, segs, flag, pre=None, emit=None, want_ll=False, to_conv0=False):
         """ResBlockModulateBEST (ref :237-249): conv20 with fused (shift,) SiLU; optional 1x1x1
         res_conv; conv21 with fused SiLU + text modulation + residual add.  Returns (y, y2): y2 = `emit` applied to y
         (None without emit).  want_ll (the block in front of a down block, whose raw output is read by nothing but the LL
-        band of the Conv_2 path): where conv21's launch can (`_emit_ll`), it writes LL(y) / 2 instead of y -- returns
-        (None, y2, y_ll); else (y, y2, None)."""
+        band of the Conv_2 path; to_conv0: the main branch's): returns (y, y2, y_ll, s2d) for _down -- where conv21's launch
+        can (the plan's emit_ll), it writes y_ll = LL(y) / 2 instead of y; s2d: y2 is in space-to-depth form."""
         rb = self.get_submodule(name)
-        sh = {} if flag else self._shift(P, S, name + ".dense1")
-        # res_conv (1x1x1, where the channel count changes) folded into conv21's epilogue where conv21 runs on conv3d_wf:
-        # W1^T x is accumulated by the matrix pipe into conv21's output blocks -- no launch of its own, no residual tensor
-        # written and read back (with the down blocks' Conv_2: 19 -> 9 1x1x1 launches per step at the benchmark batch)
-        rc = side = None
-        if isinstance(rb.res_conv, nn.Conv3d):
-            rc = self._fold_res_conv(P, name, segs)
-            if rc is None and pre is None and self._side_xp(P, name, segs):
-                # a segmented input (an up block's concat): res_conv's launch reads every element anyway and also writes
-                # conv20's prologue output SiLU(x + shift) -- conv20 then reads one plain tensor, no prologue pass
-                side = ops.scratch_like(segs, "side_xp")
-                res = self._conv(P, name + ".res_conv", segs, side_xp=dict(
-                    out=side, shift=sh.get("in_shift"), shift_stride=sh.get("shift_stride", 0), act=True))
-            else:
-                res = None if rc is not None else self._conv(P, name + ".res_conv", segs)
-        else:
-            res = segs[0]
-        rckw = {} if rc is None else {"res_conv": rc, "bias": rb.res_conv.bias.detach()}
-        sc = self._scale(P, S, name + ".dense2")
+        plan = self._resblock_plan(P, name, segs, pre is not None, emit is not None, want_ll, to_conv0)
+        pro20 = self._spec(P, S, shift=None if flag else name + ".dense1")
+        pro21 = self._spec(P, S, scale=name + ".dense2")
+        res, side, rckw = segs[0], None, {}
+        if plan.fold:
+            # res_conv (1x1x1, where the channel count changes) folded into conv21's epilogue where conv21 runs on conv3d_wf:
+            # W1^T x is accumulated by the matrix pipe into conv21's output blocks -- no launch of its own, no residual tensor
+            # written and read back (with the down blocks' Conv_2: 19 -> 9 1x1x1 launches per step at the benchmark batch)
+            res, rckw = None, {"res_conv": (segs[0], rb.res_conv.weight.detach(), segs[0].shape[1]), "bias": rb.res_conv.bias.detach()}
+        elif plan.side_xp:
+            # a segmented input (an up block's concat): res_conv's launch reads every element anyway and also writes
+            # conv20's prologue output SiLU(x + shift) -- conv20 then reads one plain tensor, no prologue pass
+            side = ops.scratch_like(segs, "side_xp")
+            res = self._conv(P, name + ".res_conv", segs, side_xp=dict(pro20, out=side))
+        elif isinstance(rb.res_conv, nn.Conv3d):
+            res = self._conv(P, name + ".res_conv", segs)
+        if plan.s2d:        # Conv_0 + LL of the down block behind with Winograd on top: it reads the second output in this form
+            emit = dict(emit, s2d=True)
+        shape = tuple(segs[0].shape[2:])
+        if not plan.pair_fused:
+            assert pre is None
+            t1 = self._conv(P, name + ".conv20", segs, **self._own(pro20))
+            y, y2 = self._conv(P, name + ".conv21", [t1], use_bias=False, residual=res, emit=emit, **self._own(pro21), **rckw)
+            return (y, y2, None, plan.s2d) if want_ll else (y, y2)
         # conv20's result feeds conv21 only: its epilogue applies conv21's prologue (SiLU, text modulation) and conv21
         # reads that directly -- a plain fp32 tensor for the staged kernel, or the packed bf16 units in the bf16 mode
         # (no prologue / pack pass in between; same bits either way)
-        both16 = name + ".conv20" in P["bf16"] and name + ".conv21" in P["bf16"]
-        kw = {} if emit is None else {"emit": emit}
-        if ops.config.epilogue_fuse and (both16 or (name + ".conv20" not in P["bf16"] and name + ".conv21" not in P["bf16"])):
-            mid = dict(act=True, scale=sc["in_scale"], scale_stride=sc["scale_stride"])
-            if side is not None:    # (res_conv's launch wrote conv20's prologue output: a plain-input convolution)
-                t1p = self._conv(P, name + ".conv20", [side], keep_y=False, emit=mid)
-            elif pre is not None:   # (bf16 mode: `pre` is the packed bf16 form a bf16 producer wrote)
-                t1p = self._conv(P, name + ".conv20", [pre], keep_y=False, emit=mid,
-                                 x_bf16_shape=tuple(segs[0].shape[2:]) if pre.dtype == torch.int16 else None)
-            else:
-                t1p = self._conv(P, name + ".conv20", segs, in_act=True, keep_y=False, emit=mid, **sh)
-            shape = tuple(segs[0].shape[2:]) if both16 else None
-            if want_ll and emit is not None and self._emit_ll(P, name, segs[0]):
-                y2, yll = self._conv(P, name + ".conv21", [t1p], use_bias=False, residual=res, keep_y=False,
-                                     emit=dict(emit, ll=True), **rckw)
-                return None, y2, yll
-            out = self._conv(P, name + ".conv21", [t1p], use_bias=False, residual=res, x_bf16_shape=shape, **rckw, **kw)
+        if side is not None:    # (res_conv's launch wrote conv20's prologue output: a plain-input convolution)
+            t1p = self._conv(P, name + ".conv20", [side], keep_y=False, emit=pro21)
+        elif pre is not None:   # (bf16 mode: `pre` is the packed bf16 form a bf16 producer wrote)
+            t1p = self._conv(P, name + ".conv20", [pre], keep_y=False, emit=pro21, x_bf16_shape=shape if pre.dtype == torch.int16 else None)
         else:
-            assert pre is None
-            t1 = self._conv(P, name + ".conv20", segs, in_act=True, **sh)
-            out = self._conv(P, name + ".conv21", [t1], use_bias=False, in_act=True, residual=res, **sc, **rckw, **kw)
-        out = out if emit is not None else (out, None)
-        return (*out, None) if want_ll else out
-
-    # Which launches take which epilogue form is decided in tmdiff_amd.routing (fold_k1, side_xp, emit_ll, s2d_handover, ll_fits:
-    # functions of extents, switches and math).  What is the model's: the channel counts and the set of bf16 convolutions.
-    @staticmethod
-    def _math(P, *names):
-        return "bf16" if any(n_ in P["bf16"] for n_ in names) else "fp32"
-
-    def _emit_ll(self, P, name, x, conv=".conv21", switch="emit_ll"):
-        """True when the convolution `name + conv` (a ResBlock's conv21; a down block's Conv_0 with switch="emit_dwt") writes the
-        halved LL band / the Haar transform of its output instead of the output.  x: a tensor of its input extents."""
-        m = self.get_submodule(name + conv)
-        b, _, n, h, w = x.shape
-        return routing.emit_ll(b, m.in_channels, m.out_channels, n, h, w, m.groups, self._math(P, name + conv), switch)
-
-    def _side_xp(self, P, name, segs):
-        """True when res_conv of the ResBlock `name` also writes conv20's prologue output (make_conv_desc side_xp=)."""
-        m = self.get_submodule(name + ".conv20")
-        b, _, n, h, w = segs[0].shape
-        return routing.side_xp(b, tuple(s.shape[1] for s in segs), m.out_channels, n, h, w, m.groups,
-                               self._math(P, name + ".conv20", name + ".conv21", name + ".res_conv"))
-
-    def _fold_res_conv(self, P, name, segs, k1=".res_conv", k3=".conv21"):
-        """(x, the 1x1x1 weight, Cx) when the 1x1x1 convolution `name + k1` -- a ResBlock's res_conv, a down block's Conv_2 --
-        rides in the epilogue of the 3x3x3 convolution `name + k3` (make_conv_desc res_conv=), else None."""
-        m3, x = self.get_submodule(name + k3), segs[0]
-        b, cx, n, h, w = x.shape
-        if not routing.fold_k1(b, cx, m3.in_channels, m3.out_channels, n, h, w, m3.groups, self._math(P, name + k3, name + k1), len(segs)):
-            return None
-        return x, self.get_submodule(name + k1).weight.detach(), cx
-
-    def _ll_s2d(self, P, blk, h):
-        """True when the main branch's down block `blk` runs Conv_0 + LL as conv3d_wf_ll, on the space-to-depth second output
-        of the ResBlock in front.  h: the ResBlock's input."""
-        m21, c0 = self.get_submodule(blk + ".conv20.conv21"), self.get_submodule(blk + ".down.Conv_0")
-        b, _, n, hh, ww = h.shape
-        math = "bf16" if self.compute_dtype == "bf16" else self._math(P, blk + ".conv20.conv20", blk + ".conv20.conv21")
-        return routing.s2d_handover(b, (m21.in_channels, m21.out_channels), (c0.in_channels, c0.out_channels), n, hh, ww, m21.groups, math)
-
-    def _ll_fits(self, name, x):
-        """True when conv3d_ll takes the down block `name`'s Conv_0 + LL on x (its size limit)."""
-        c0 = self.get_submodule(name + ".Conv_0")
-        return routing.ll_fits(x.shape[0], c0.in_channels, c0.out_channels, *x.shape[2:])
+            t1p = self._conv(P, name + ".conv20", segs, keep_y=False, emit=pro21, **self._own(pro20))
+        if plan.emit_ll:
+            y2, yll = self._conv(P, name + ".conv21", [t1p], use_bias=False, residual=res, keep_y=False, emit=dict(emit, ll=True), **rckw)
+            return None, y2, yll, plan.s2d
+        y, y2 = self._conv(P, name + ".conv21", [t1p], use_bias=False, residual=res, emit=emit,
+                           x_bf16_shape=shape if name + ".conv21" in P["bf16"] else None, **rckw)
+        return (y, y2, None, plan.s2d) if want_ll else (y, y2)
 
     def _conv0(self, P, name, x, pre):
         """Conv_0 of a wavelet block on SiLU(x): from the producer's second output when there is one."""
@@ -550,87 +524,74 @@ class WavBEST(nn.Module):
             return self._conv(P, name + ".Conv_0", [x], in_act=True)
         return self._conv(P, name + ".Conv_0", [pre], x_bf16_shape=tuple(x.shape[2:]) if pre.dtype == torch.int16 else None)
 
-    def _down(self, P, S, name, x, flag, want_high, pre=None, emit=None, fuse=False, pre_s2d=False, xq=None):
+    def _down(self, P, S, name, x, flag, want_high, pre=None, emit=None, fuse=False, xq=None, s2d=False):
         """WaveletUPorDown(down=True) (ref :369-414); /2 folded into the DWT, LL-only when the
-        caller drops the high bands.  Returns (out, out2, bands).  pre_s2d: `pre` is in space-to-depth form (_ll_s2d).
-        xq: LL(x) / 2 as the producer already wrote it (_resblock(want_ll=True)); x itself may then be None."""
-        w_ll = None if want_high or pre is None or pre.dtype != torch.float32 else P["w_wfll" if pre_s2d else "w_ll"].get(name + ".Conv_0")
-        if w_ll is not None and not pre_s2d and not self._ll_fits(name, pre):
-            w_ll = None
-        assert not pre_s2d or w_ll is not None
-        conv_ll = ops.conv3d_wf_ll if pre_s2d else ops.conv3d_ll
+        caller drops the high bands.  Returns (out, out2, bands).  xq, s2d: what _resblock(want_ll=True) returned with x
+        and pre -- LL(x) / 2 as the producer already wrote it (x itself may then be None); `pre` is in space-to-depth form."""
+        shape = x.shape if x is not None else (*xq.shape[:3], 2 * xq.shape[3], 2 * xq.shape[4])
+        plan = self._down_plan(P, name, shape, not want_high, pre is not None and pre.dtype == torch.float32, s2d, fuse)
+        pro = self._spec(P, S, shift=None if flag else name + ".Dense_0", scale=name + ".dense1")      # Conv_1's prologue
         # high bands kept (condition branch): where Conv_0 runs on conv3d_wf unsplit, its epilogue writes the Haar transform of its
         # output -- LL through Conv_1's prologue, LH, HL, HH -- instead of the output: no full-resolution tensor, no DWT pass
-        dwt4 = None
-        if (w_ll is None and fuse and want_high and pre is not None and pre.dtype == torch.float32 and
-                self._emit_ll(P, name, pre, conv=".Conv_0", switch="emit_dwt")):
-            pro = self._spec(P, S, shift=None if flag else name + ".Dense_0", scale=name + ".dense1")
-            dwt4 = self._conv(P, name + ".Conv_0", [pre], keep_y=False, emit=dict(pro, dwt=True))
-        hh = None if (w_ll is not None or dwt4 is not None) else self._conv0(P, name, x, pre)
+        if plan.conv0 == "dwt":
+            hll, *bands = self._conv(P, name + ".Conv_0", [pre], keep_y=False, emit=dict(pro, dwt=True))
+        elif plan.conv0 is None:
+            hh = self._conv0(P, name, x, pre)
         # The reference runs the 1x1x1 Conv_2 at full resolution and keeps the halved LL band of its output (:390, :396).
         # Both are linear and act on different axes (channels / the 2x2 pixel block), and the halved LL band of a
         # constant is that constant, so LL(Conv_2(x)) / 2 == Conv_2(LL(x) / 2): the convolution runs on a quarter of
         # the positions and the full-resolution intermediate is never written (same value up to fp32 summation order).
         rc2 = {}
-        if ops.config.conv2_after_ll:
+        if not ops.config.conv2_after_ll:
+            xll = ops.haar_dwt2d(self._conv(P, name + ".Conv_2", [x]), want_high=False, ll_scale=0.5)[0]
+        else:
             if xq is None:
                 xq = ops.haar_dwt2d(x, want_high=False, ll_scale=0.5)[0]
-            # ... and where Conv_1 runs on conv3d_wf, Conv_2 rides in its epilogue like a ResBlock's res_conv
-            rc = self._fold_res_conv(P, name, [xq], k1=".Conv_2", k3=".Conv_1")
-            if rc is not None:
-                xll, rc2 = None, {"res_conv": rc, "bias": self.get_submodule(name + ".Conv_2").bias.detach()}
+            if plan.fold:   # ... and where Conv_1 runs on conv3d_wf, Conv_2 rides in its epilogue like a ResBlock's res_conv
+                c2 = self.get_submodule(name + ".Conv_2")
+                xll, rc2 = None, {"res_conv": (xq, c2.weight.detach(), xq.shape[1]), "bias": c2.bias.detach()}
             else:
                 xll = self._conv(P, name + ".Conv_2", [xq])
-        else:
-            xll = ops.haar_dwt2d(self._conv(P, name + ".Conv_2", [x]), want_high=False, ll_scale=0.5)[0]
-        kw = dict(rc2) if emit is None else dict(rc2, emit=emit)
-        if w_ll is not None:
-            # Conv_0 and the halved LL band of its output as ONE strided convolution (only the LL band is used here); with
-            # `fuse` its epilogue applies Conv_1's prologue, as the DWT does below
-            c0 = self.get_submodule(name + ".Conv_0")
-            if fuse:
-                pro = self._spec(P, S, shift=None if flag else name + ".Dense_0", scale=name + ".dense1")
-                hll = conv_ll(pre, w_ll, c0.out_channels, 0.5, bias=c0.bias.detach(), emit=pro, keep_y=False)
-                out = self._conv(P, name + ".Conv_1", [hll], use_bias=False, residual=xll, **kw)
-            else:
-                hll = conv_ll(pre, w_ll, c0.out_channels, 0.5, bias=c0.bias.detach())
-                sh = {} if flag else self._shift(P, S, name + ".Dense_0")
-                out = self._conv(P, name + ".Conv_1", [hll], use_bias=False, in_act=True, residual=xll,
-                                 **self._scale(P, S, name + ".dense1"), **sh, **kw)
-            out, out2 = out if emit is not None else (out, None)
-            return out, out2, (None, None, None)
-        if dwt4 is not None:
-            hll, lh, hl, hhh = dwt4
-            out = self._conv(P, name + ".Conv_1", [hll], use_bias=False, residual=xll, **kw)
-        elif fuse:   # Conv_1's prologue (shift, SiLU, text modulation) is applied to the LL band where the DWT writes it
-            pro = self._spec(P, S, shift=None if flag else name + ".Dense_0", scale=name + ".dense1")
-            p16 = name + ".Conv_1" in P["bf16"]          # bf16 mode: ... as the packed bf16 units the convolution reads
-            hll, lh, hl, hhh = ops.haar_dwt2d(hh, want_high=want_high, ll_scale=0.5, ll_prologue=pro, pack_bf16=p16)
-            out = self._conv(P, name + ".Conv_1", [hll], use_bias=False, residual=xll,
-                             x_bf16_shape=tuple(xll.shape[2:]) if p16 else None, **kw)
-        else:
-            hll, lh, hl, hhh = ops.haar_dwt2d(hh, want_high=want_high, ll_scale=0.5)
-            sh = {} if flag else self._shift(P, S, name + ".Dense_0")
-            out = self._conv(P, name + ".Conv_1", [hll], use_bias=False, in_act=True, residual=xll,
-                             **self._scale(P, S, name + ".dense1"), **sh, **kw)
-        out, out2 = out if emit is not None else (out, None)
-        return out, out2, (lh, hl, hhh)
+        # hll = the halved LL band of Conv_0's output, through Conv_1's prologue where the kernel that writes it applies it (`fuse`)
+        p16 = False
+        if plan.conv0 in ("ll", "wfll"):
+            # Conv_0 and the halved LL band of its output as ONE strided convolution (only the LL band is used here)
+            c0, wfll = self.get_submodule(name + ".Conv_0"), plan.conv0 == "wfll"
+            hll = (ops.conv3d_wf_ll if wfll else ops.conv3d_ll)(pre, P["w_wfll" if wfll else "w_ll"][name + ".Conv_0"], c0.out_channels, 0.5,
+                                                                bias=c0.bias.detach(), **(dict(emit=pro, keep_y=False) if fuse else {}))
+            bands = [None, None, None]
+        elif plan.conv0 is None:
+            p16 = fuse and name + ".Conv_1" in P["bf16"]      # bf16 mode: ... as the packed bf16 units the convolution reads
+            hll, *bands = ops.haar_dwt2d(hh, want_high=want_high, ll_scale=0.5, ll_prologue=pro if fuse else None, pack_bf16=p16)
+        out, out2 = self._conv(P, name + ".Conv_1", [hll], use_bias=False, residual=xll, emit=emit,
+                               x_bf16_shape=tuple(xll.shape[2:]) if p16 else None, **({} if fuse else self._own(pro)), **rc2)
+        return out, out2, tuple(bands)
 
     def _up(self, P, S, name, x, bands, pre=None, fuse=False):
         """WaveletUPorDown(up=True) (ref :379-386, :398-408); ``bands`` = convH_0 output
         [B, 3C, N, h, w], step-invariant and cached with the condition branch."""
         hh = self._conv0(P, name, x, pre)
         xx = self._conv(P, name + ".Conv_2", [x])
-        if fuse:   # Conv_1's prologue applied to the h reconstruction where the IDWT writes it
-            pro = self._spec(P, S, shift=name + ".Dense_0", scale=name + ".dense1")
-            p16 = name + ".Conv_1" in P["bf16"]
-            h_up, x_up = ops.haar_idwt2d([hh, xx], None, None, None, in_scale=2.0, stacked_bands=bands, out0_prologue=pro,
-                                         pack_bf16=p16)
-            return self._conv(P, name + ".Conv_1", [h_up], use_bias=False, residual=x_up,
-                              x_bf16_shape=tuple(x_up.shape[2:]) if p16 else None)
-        h_up, x_up = ops.haar_idwt2d([hh, xx], None, None, None, in_scale=2.0, stacked_bands=bands)
-        return self._conv(P, name + ".Conv_1", [h_up], use_bias=False, in_act=True, residual=x_up,
-                          **self._shift(P, S, name + ".Dense_0"), **self._scale(P, S, name + ".dense1"))
+        # with `fuse`, Conv_1's prologue is applied to the h reconstruction where the IDWT writes it
+        pro = self._spec(P, S, shift=name + ".Dense_0", scale=name + ".dense1")
+        p16 = fuse and name + ".Conv_1" in P["bf16"]
+        h_up, x_up = ops.haar_idwt2d([hh, xx], None, None, None, in_scale=2.0, stacked_bands=bands, out0_prologue=pro if fuse else None,
+                                     pack_bf16=p16)
+        return self._conv(P, name + ".Conv_1", [h_up], use_bias=False, residual=x_up,
+                          x_bf16_shape=tuple(x_up.shape[2:]) if p16 else None, **({} if fuse else self._own(pro)))
+
+    def _stem(self, P, S, block, shift, **inputs):
+        """AdaptionModulateBEST `block` (conv1 on pan=, ms=; conv2 on xin=): the pointwise conv20 and conv21.  Returns (h, hp):
+        hp = h through the prologue of its consumer, the ResBlock whose time shift is `shift` (None: a flag block's), where the
+        producers fuse (else None)."""
+        fuse_c, fuse = self._producer_fuse(P)
+        m, x = self.get_submodule(block), inputs["ms" if "ms" in inputs else "xin"]
+        pro = self._spec(P, S, scale=block + ".dense2", act=False)       # conv21's prologue: with `fuse` the stem applies it
+        p16 = fuse and block + ".conv21" in P["bf16"]
+        a0 = ops.stem(m.conv20.weight.detach().reshape(-1), m.conv20.bias.detach(), self.channels[0], pack_bf16=p16,
+                      **(dict(out_scale=pro["scale"], out_scale_stride=pro["scale_stride"]) if fuse else {}), **inputs)
+        return self._conv(P, block + ".conv21", [a0], use_bias=False, emit=self._spec(P, S, shift=shift) if fuse_c else None,
+                          x_bf16_shape=tuple(x.shape[1:]) if p16 else None, **({} if fuse else self._own(pro)))
 
     def _producer_fuse(self, P):
         """(conv -> conv edges, wavelet / stem producers): the first in both compute modes (in the bf16 mode the second
@@ -670,25 +631,13 @@ class WavBEST(nn.Module):
         lin = lambda i, x: ops.linear(x, self.embed2[i].weight.detach(), self.embed2[i].bias.detach(), act=True)
         pemb = lin(4, lin(2, lin(0, pe)))                 # act(embed2(prompt)) -- one row per distinct prompt row
         S = {"scale": P["scale_bank"].run(pemb)}
-        c0 = self.channels[0]
         fuse_c, fuse = self._producer_fuse(P)
         spec = lambda **k: self._spec(P, S, **k) if fuse_c else None
-        w0, b0 = self.conv1.conv20.weight.detach().reshape(-1), self.conv1.conv20.bias.detach()
-        if fuse:    # the stem writes conv21's modulated input; conv21's epilogue writes SiLU(h) for down1_1.conv20 (flag: no shift)
-            osc, oss = P["scale_bank"].slot(S["scale"], "conv1.dense2")
-            p16 = "conv1.conv21" in P["bf16"]
-            a0 = ops.stem(w0, b0, c0, pan=PAN.contiguous(), ms=MS.contiguous(), out_scale=osc, out_scale_stride=oss,
-                          pack_bf16=p16)
-            h, hp = self._conv(P, "conv1.conv21", [a0], use_bias=False, emit=spec(),
-                               x_bf16_shape=(MS.shape[1], MS.shape[2], MS.shape[3]) if p16 else None)
-        else:
-            a0 = ops.stem(w0, b0, c0, pan=PAN.contiguous(), ms=MS.contiguous())
-            out = self._conv(P, "conv1.conv21", [a0], use_bias=False, **self._scale(P, S, "conv1.dense2"),
-                             **({"emit": spec()} if fuse_c else {}))
-            h, hp = out if fuse_c else (out, None)
+        # (with the producers fused the stem writes conv21's modulated input, and conv21's epilogue SiLU(h) for down1_1.conv20 -- flag: no shift)
+        h, hp = self._stem(P, S, "conv1", None, pan=PAN.contiguous(), ms=MS.contiguous())
         cond = {"h0": h, "pan": PAN, "ms": MS, "prompt": prompt, "scale": S["scale"]}
         for lvl, (dn, upn) in enumerate((("down1_1", "up3"), ("down2_1", "up2"), ("down3_1", "up1")), start=1):
-            h, ha, hq = self._resblock(P, S, dn + ".conv20", [h], flag=True, pre=hp, emit=spec(), want_ll=True)
+            h, ha, hq, _ = self._resblock(P, S, dn + ".conv20", [h], flag=True, pre=hp, emit=spec(), want_ll=True)
             # (the last level's output only feeds the up path's three-segment conv20: nothing to emit)
             h, hp, skip = self._down(P, S, dn + ".down", h, flag=True, want_high=True, pre=ha,
                                      emit=spec() if lvl < 3 else None, fuse=fuse, xq=hq)
@@ -773,27 +722,13 @@ class WavBEST(nn.Module):
 
         fuse_c, fuse = self._producer_fuse(P)
         spec = lambda **k: self._spec(P, S, **k) if fuse_c else None
-        w0, b0 = self.conv2.conv20.weight.detach().reshape(-1), self.conv2.conv20.bias.detach()
-        if fuse:
-            osc, oss = P["scale_bank"].slot(S["scale"], "conv2.dense2")
-            p16 = "conv2.conv21" in P["bf16"]
-            a0 = ops.stem(w0, b0, self.channels[0], xin=x_t.contiguous(), out_scale=osc, out_scale_stride=oss, pack_bf16=p16)
-            h, hp = self._conv(P, "conv2.conv21", [a0], use_bias=False, emit=spec(shift="down1.conv20.dense1"),
-                               x_bf16_shape=tuple(x_t.shape[1:]) if p16 else None)
-        else:
-            a0 = ops.stem(w0, b0, self.channels[0], xin=x_t.contiguous())
-            out = self._conv(P, "conv2.conv21", [a0], use_bias=False, **self._scale(P, S, "conv2.dense2"),
-                             **({"emit": spec(shift="down1.conv20.dense1")} if fuse_c else {}))
-            h, hp = out if fuse_c else (out, None)
+        h, hp = self._stem(P, S, "conv2", "down1.conv20.dense1", xin=x_t.contiguous())
         hs = [h]
         for dn, nxt in (("down1", "down2.conv20"), ("down2", "down3.conv20"), ("down3", "middle1")):
-            # Conv_0 + LL with Winograd on top: the ResBlock hands its second output over in space-to-depth form
-            sp = spec()
-            s2d = sp is not None and self._ll_s2d(P, dn, h)
-            h, ha, hq = self._resblock(P, S, dn + ".conv20", [h], flag=False, pre=hp, emit=dict(sp, s2d=True) if s2d else sp,
-                                       want_ll=True)
+            # (to_conv0: Conv_0 + LL with Winograd on top where the ResBlock can hand its second output over in space-to-depth form)
+            h, ha, hq, s2d = self._resblock(P, S, dn + ".conv20", [h], flag=False, pre=hp, emit=spec(), want_ll=True, to_conv0=True)
             h, hp, _ = self._down(P, S, dn + ".down", h, flag=False, want_high=False, pre=ha,
-                                  emit=spec(shift=nxt + ".dense1"), fuse=fuse, pre_s2d=s2d, xq=hq)
+                                  emit=spec(shift=nxt + ".dense1"), fuse=fuse, xq=hq, s2d=s2d)
             hs.append(h)
         h, _ = self._resblock(P, S, "middle1", [hs[3]], flag=False, pre=hp)
         for lvl, upn in ((3, "up1"), (2, "up2"), (1, "up3")):
@@ -803,8 +738,8 @@ class WavBEST(nn.Module):
         for k in (1, 2, 3):
             h, hp = self._resblock(P, S, f"final.conv2{k}", [h], flag=False, pre=hp,
                                    emit=spec(shift=f"final.conv2{k + 1}.dense1") if k < 3 else None)
-        sc = self._scale(P, S, "final.dense2")
-        return ops.head(h, self.final.conv24.weight.detach().reshape(-1), sc["in_scale"], sc["scale_stride"])
+        sc = self._spec(P, S, scale="final.dense2")
+        return ops.head(h, self.final.conv24.weight.detach().reshape(-1), sc["scale"], sc["scale_stride"])
 
     # ---- training path (finetune): same graph through the autograd-wrapped HIP ops ----------------------------
     def forward_train(self, x_t, t_input, PAN=None, MS=None, prompt=None):

@@ -29,9 +29,10 @@ The rules, in order (fp32):
   3. the direct kernels, whose split-K fills the chip on small grids: staged (operands by LDS-DMA; needs Cin/g % 4 == 0 and
      Cout/g % 32 == 0) where the input is plain or the prologue pass is amortised (Cout/g >= 128, Cin/g >= 384, dropout / mask,
      a kept x'), else fused.
-What a launch's epilogue additionally does in the fp32 inference graph is decided here too (WavBEST reads the channel counts
-and its set of bf16 convolutions off its modules and asks); `unet_fusions` tabulates it per block, `tools/routing_table.py
---fusions` writes profiles/fusion_table.txt:
+What a launch's epilogue additionally does in the fp32 inference graph is decided here too: the rules below, composed per block
+by `resblock_plan` / `down_plan` (WavBEST reads the channel counts and its set of bf16 convolutions off its modules, asks for
+the plan and executes it); `unet_fusions` tabulates the plans per block, `tools/routing_table.py --fusions` writes
+profiles/fusion_table.txt:
 
   fusion                        descriptor fields            rule
   ----------------------------  ---------------------------  ------------------------------------------------------------------
@@ -234,7 +235,8 @@ def wf_fold_fits(b, cin, cout, n, h, w, rc_cin):
 
 # ---- what a launch's epilogue additionally does: the fusions of the fp32 inference graph -------------------------------------
 # Functions of the extents, ops.config and a math string ("bf16" as soon as one of the convolutions involved runs on the bf16
-# kernels); WavBEST asks them once per block per forward, so the answers are kept per (arguments, config.key()) like wf_route's.
+# kernels); WavBEST asks once per block per forward (through the plans below), so the answers are kept per (arguments,
+# config.key()) like wf_route's.
 _FUSIONS = {}
 
 
@@ -245,7 +247,7 @@ def _cached(fn):
         if r is None:
             if len(_FUSIONS) > 4096:
                 _FUSIONS.clear()
-            r = _FUSIONS[key] = bool(fn(*args))
+            r = _FUSIONS[key] = fn(*args)
         return r
     ask.__name__, ask.__doc__ = fn.__name__, fn.__doc__
     return ask
@@ -318,6 +320,54 @@ def s2d_handover(b, c21, c0, n, h, w, groups=1, math="fp32"):
             wfll_route(b, c0[0], c0[1], n, h, w))
 
 
+# ---- the rules composed: one plan per block ----------------------------------------------------------------------------------
+# Which of the fusions above a ResBlock and a down block take TOGETHER, and in which order they exclude each other: what
+# WavBEST._resblock / _down execute and unet_fusions tabulates.  Functions of the same things as the rules (extents, channel
+# counts, ops.config, math strings) plus what the caller knows of the block's neighbours; cached like them.
+ResBlockPlan = collections.namedtuple("ResBlockPlan", "fold side_xp pair_fused emit_ll s2d")
+DownPlan = collections.namedtuple("DownPlan", "conv0 fold")
+
+
+def _any16(*maths):
+    return "bf16" if "bf16" in maths else "fp32"
+
+
+@_cached
+def resblock_plan(b, seg_c, cout, n, h, w, maths, pre, emit, want_ll, to_conv0):
+    """A ResBlock on input segments of seg_c channels (a tuple) -> cout at [b, ., n, h, w].  maths = the math of (conv20, conv21,
+    res_conv, the network's compute mode); pre: conv20 reads a second output its producer wrote; emit: the block's consumer wants
+    a second output; want_ll: nothing but a down block's Conv_2 path reads the raw output; to_conv0: that down block is the main
+    branch's, whose Conv_0 + LL can run composed.  fold: res_conv rides in conv21's epilogue; side_xp: else, without `pre`,
+    its launch writes conv20's prologue output; pair_fused: conv20's epilogue applies conv21's prologue (one math); emit_ll:
+    conv21 writes LL(y) / 2 instead of y; s2d: its second output is in space-to-depth form."""
+    m20, m21, mrc, net = maths
+    cin, pair_fused = sum(seg_c), bool(_config().epilogue_fuse) and m20 == m21
+    fold = cin != cout and fold_k1(b, seg_c[0], cout, cout, n, h, w, 1, _any16(m21, mrc), len(seg_c))      # (cin != cout: a res_conv exists)
+    side = cin != cout and not fold and not pre and side_xp(b, seg_c, cout, n, h, w, 1, _any16(m20, m21, mrc))
+    return ResBlockPlan(fold, side, pair_fused,
+                        bool(want_ll and emit and pair_fused and emit_ll(b, cout, cout, n, h, w, 1, m21)),
+                        bool(to_conv0 and emit and s2d_handover(b, (cout, cout), (cout, cout), n, h, w, 1, _any16(net, m20, m21))))
+
+
+@_cached
+def down_plan(b, ch, n, h, w, maths, main, pre, s2d, fuse):
+    """A down block of ch channels on a [b, ch, n, h, w] input.  maths = the math of (Conv_0, Conv_1, Conv_2); main: the main
+    branch (high bands dropped); pre: a producer-written fp32 second output exists; s2d: in space-to-depth form
+    (resblock_plan's s2d); fuse: the wavelet producers apply their consumer's prologue.  conv0: what the Conv_0 launch is --
+    "wfll" / "ll" (composed with the LL band, main branch), "dwt" (writes its own Haar transform, high bands kept) or None (a
+    convolution, then a DWT pass); fold: Conv_2, after the LL band, rides in Conv_1's epilogue."""
+    m0, m1, m2 = maths
+    cfg, conv0 = _config(), None
+    if main and pre:
+        if s2d:
+            conv0 = "wfll"
+        elif cfg.ll_compose and ll_weight_ok(ch, ch) and ll_fits(b, ch, ch, n, h, w):
+            conv0 = "ll"
+    elif fuse and pre and emit_ll(b, ch, ch, n, h, w, 1, m0, "emit_dwt"):
+        conv0 = "dwt"
+    return DownPlan(conv0, bool(cfg.conv2_after_ll and fold_k1(b, ch, ch, ch, n, h // 2, w // 2, 1, _any16(m1, m2), 1)))
+
+
 # ---- the network's 3x3x3 convolutions ------------------------------------------------------------------------------------
 Layer = collections.namedtuple("Layer", "name cin cout groups h w plain kind")      # kind: "conv" | "conv0_ll"
 
@@ -361,8 +411,9 @@ def unet_table(channels, b, n, h, w, math="fp32"):
     rows = []
     for L in unet_conv3_layers(channels, h, w):
         if L.kind == "conv0_ll" and math == "fp32":
-            # (the producer -- the ResBlock's conv21 in front -- writes the space-to-depth form only from an unsplit wf launch)
-            fam = ll_family(b, L.cin, L.cout, n, L.h, L.w, producer_s2d=s2d_handover(b, (L.cin, L.cin), (L.cin, L.cout), n, L.h, L.w))
+            # (the plans of the fused fp32 graph; the ResBlock's s2d does not depend on its input channels)
+            s2d = resblock_plan(b, (L.cin,), L.cin, n, L.h, L.w, ("fp32",) * 4, True, True, True, True).s2d
+            fam = down_plan(b, L.cout, n, L.h, L.w, ("fp32",) * 3, True, True, s2d, True).conv0
             if fam is not None:
                 rows.append((L, fam))
                 continue
@@ -380,9 +431,10 @@ Fusion = collections.namedtuple("Fusion", "block kind taken k1 passes")
 
 def unet_fusions(channels, b, n, h, w, math="fp32", fuse=None):
     """[Fusion] of one inference forward (condition branch, then main branch) of a batch of b tiles with n bands: which
-    fusions each ResBlock and each wavelet block takes -- the block walk of WavBEST._condition / _forward_infer with the
-    decisions of _resblock / _down, on extents alone.  math: the network's compute mode; fuse: what WavBEST._producer_fuse
-    returns (the default: what it returns in fp32).  tests/test_host_logic.py holds WavBEST's own decisions to these rows."""
+    fusions each ResBlock and each wavelet block takes -- the block walk of WavBEST._condition / _forward_infer over the plans
+    WavBEST._resblock / _down execute (resblock_plan, down_plan), on extents alone.  math: the network's compute mode; fuse: what
+    WavBEST._producer_fuse returns (the default: what it returns in fp32).  tests/test_host_logic.py holds the plans WavBEST
+    asks for, from its own module tree, to these rows."""
     from . import ops
     cfg = _config()
     fuse_c, fuse_p = (cfg.producer_fuse and cfg.epilogue_fuse,) * 2 if fuse is None else fuse
@@ -394,47 +446,24 @@ def unet_fusions(channels, b, n, h, w, math="fp32", fuse=None):
         seg = [cin // 3] if cin % 3 == 0 else None
         return "bf16" if math == "bf16" and ops.bf16_conv_supported(cout, cin, ksize, 1, seg) else "fp32"
 
-    def any16(*maths):
-        return "bf16" if "bf16" in maths else "fp32"
-
     def passes(convs):                    # convs: (cin, cout, level, plain) -- a pass in front of every input that is not plain
         return sum(1 for ci, co, k, plain in convs if not plain and conv3_family(
             b, ci, co, n, *lv[k], plain=False, math=m16(co, ci)) in ("wf", "wf_pair", "staged", "bf16"))
 
     def resblock(name, seg_c, cout, k, pre, emit, want_ll=False, to_conv0=False):
-        cin, (hh, ww) = sum(seg_c), lv[k]
-        m20, m21, mrc = m16(cout, cin), m16(cout, cout), m16(cout, cin, 1)
-        pair_fused = cfg.epilogue_fuse and m20 == m21
-        taken = []
-        if cin != cout:                   # (a res_conv exists)
-            if fold_k1(b, seg_c[0], cout, cout, n, hh, ww, 1, any16(m21, mrc), len(seg_c)):
-                taken.append("fold")
-            elif not pre and side_xp(b, tuple(seg_c), cout, n, hh, ww, 1, any16(m20, m21, mrc)):
-                taken.append("side_xp")
-        if want_ll and emit and pair_fused and emit_ll(b, cout, cout, n, hh, ww, 1, m21):
-            taken.append("emit_ll")
-        s2d = to_conv0 and emit and s2d_handover(b, (cout, cout), (cout, cout), n, hh, ww, 1, any16(math, m20, m21))
-        if s2d:
-            taken.append("s2d")
-        plain20 = (pre and pair_fused) or "side_xp" in taken
-        rows.append(Fusion(name, "resblock", tuple(taken), int(cin != cout and "fold" not in taken),
-                           passes([(cin, cout, k, plain20), (cout, cout, k, pair_fused)])))
-        return s2d
+        cin = sum(seg_c)
+        p = resblock_plan(b, tuple(seg_c), cout, n, *lv[k], (m16(cout, cin), m16(cout, cout), m16(cout, cin, 1), math),
+                          bool(pre), bool(emit), want_ll, to_conv0)
+        rows.append(Fusion(name, "resblock", tuple(f for f in ("fold", "side_xp", "emit_ll", "s2d") if getattr(p, f)),
+                           int(cin != cout and not p.fold),
+                           passes([(cin, cout, k, (pre and p.pair_fused) or p.side_xp), (cout, cout, k, p.pair_fused)])))
+        return p.s2d
 
     def down(name, k, main, pre, s2d):
-        ch, (hh, ww) = c[k + 1], lv[k]
-        pre32 = pre and math == "fp32"
-        conv0 = None
-        if main and pre32:
-            if s2d:
-                conv0 = "wfll"
-            elif cfg.ll_compose and ll_weight_ok(ch, ch) and ll_fits(b, ch, ch, n, hh, ww):
-                conv0 = "ll"
-        elif fuse_p and pre32 and emit_ll(b, ch, ch, n, hh, ww, 1, m16(ch, ch), "emit_dwt"):
-            conv0 = "dwt"
-        fold = cfg.conv2_after_ll and fold_k1(b, ch, ch, ch, n, hh // 2, ww // 2, 1, any16(m16(ch, ch), m16(ch, ch, 1)), 1)
-        convs = [(ch, ch, k + 1, bool(fuse_p))] + ([(ch, ch, k, pre)] if conv0 in (None, "dwt") else [])
-        rows.append(Fusion(name, "down", tuple(t for t in (conv0, "fold" if fold else None) if t), int(not fold), passes(convs)))
+        ch = c[k + 1]
+        p = down_plan(b, ch, n, *lv[k], (m16(ch, ch), m16(ch, ch), m16(ch, ch, 1)), main, bool(pre and math == "fp32"), s2d, bool(fuse_p))
+        convs = [(ch, ch, k + 1, bool(fuse_p))] + ([(ch, ch, k, pre)] if p.conv0 in (None, "dwt") else [])
+        rows.append(Fusion(name, "down", tuple(t for t in (p.conv0, "fold" if p.fold else None) if t), int(not p.fold), passes(convs)))
 
     def stem(name):                       # (the stem writes conv21's modulated input where the producers fuse)
         rows.append(Fusion(name, "stem", (), 0, passes([(c[0], c[0], 0, bool(fuse_p))])))
