@@ -605,6 +605,24 @@ int tmdiff_metrics_noref(const float* l_ms, int64_t l_ms_stride_b, int64_t l_ms_
                          int32_t w, double* out, void* workspace, size_t workspace_bytes, tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Q2n on the device (csrc/metrics.hip; definition: tmdiff_amd/metrics.py q2n): the hypercomplex quality index of Garzelli and
+ * Nencini (2009) -- Q4 for four bands, Q8 for eight -- of x_pred against x_true on windows of block x block pixels every `shift`
+ * pixels, averaged per image.  ny = ceil(H / shift), nx = ceil(W / shift) windows; the images are mirrored at the bottom and
+ * the right (edge sample included) up to (ny - 1) * shift + block, and zero bands are appended up to the next power of two.
+ * Tensors, strides, sums, reproducibility and graph capture as for tmdiff_metrics_pair.  out: fp64 [B]; map_out: fp64
+ * [B, ny, nx] of the windows' values, or NULL; workspace: 8-byte aligned, tmdiff_metrics_q2n_workspace_bytes(...) bytes.
+ * Extents: 1 <= C <= 16, block 8, 16 or 32, 1 <= shift <= block, mirrored rows / columns no more than H / W,
+ * B * C * H * W <= 2^31 - 1; for anything else tmdiff_metrics_q2n_supported is 0, the workspace size is 0 and the entry point
+ * returns TMDIFF_E_UNSUPPORTED without launching.
+ * ------------------------------------------------------------------------------------ */
+int tmdiff_metrics_q2n_supported(int32_t B, int32_t C, int32_t H, int32_t W, int32_t block, int32_t shift);
+size_t tmdiff_metrics_q2n_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t block, int32_t shift);
+int tmdiff_metrics_q2n(const float* x_true, int64_t true_stride_b, int64_t true_stride_c, const float* x_pred,
+                       int64_t pred_stride_b, int64_t pred_stride_c, int32_t B, int32_t C, int32_t H, int32_t W, int32_t block,
+                       int32_t shift, double* out, double* map_out, void* workspace, size_t workspace_bytes,
+                       tmdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Resampling of full-resolution scenes (csrc/resample.hip; host definitions: tmdiff_amd/metrics.py).  Dense fp32 planes
  * [planes, H, W]; nothing is allocated or synchronised, so a call can be captured into a graph on `stream`.
  *  pyr_down: `levels` (1 or 2) steps of OpenCV's pyrDown with its defaults -- separable [1 4 6 4 1] / 16, horizontal pass then

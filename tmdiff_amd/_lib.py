@@ -174,6 +174,10 @@ SIGNATURES.update({
                             [C.c_double, C.c_double, vp, vp, C.c_size_t, vp]),
     "tmdiff_metrics_noref": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int64] +
                              [C.c_int32] * 6 + [vp, vp, C.c_size_t, vp]),
+    "tmdiff_metrics_q2n_supported": (C.c_int, [C.c_int32] * 6),
+    "tmdiff_metrics_q2n_workspace_bytes": (C.c_size_t, [C.c_int32] * 6),
+    "tmdiff_metrics_q2n": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64] + [C.c_int32] * 6 +
+                           [vp, vp, vp, C.c_size_t, vp]),                    # ... block, shift, out, map_out, workspace
     # resampling (csrc/resample.hip): (planes, H, W, levels | ratio) after the two tensors
     "tmdiff_pyr_down": (C.c_int, [vp, vp] + [C.c_int32] * 4 + [vp]),
     "tmdiff_upsample_bilinear": (C.c_int, [vp, vp] + [C.c_int32] * 4 + [vp]),

@@ -11,6 +11,13 @@
 //                        bands the pixel's eight values stay too and give the 4 x 4 cross products of Q4.
 //  metrics_gram_kernel   channel sums and the upper triangle of sum x_i x_j over a list of up to 17 channels in two segments.
 //  *_finalize_kernel     one workgroup per image: adds the workgroups' partial sums in a fixed order, evaluates the formulas.
+//  metrics_q2n_kernel    Q2n (Q4 / Q8, metrics.q2n): one workgroup per block x block window of one image, both images' window in
+//                        LDS as fp32 (mirrored at the bottom and the right while staging, zero bands up to a power of two).  Pass
+//                        one: per band the mean and the centred sums of the ground truth and of the fused image about that mean.
+//                        Pass two: the C x C matrix of centred cross products, each lane a T x T tile of band pairs over a slice
+//                        of the pixels.  The normalised moments the definition asks for are affine in these, so no lane divides
+//                        per pixel.  The workgroup then evaluates the hypercomplex product through the sign table and stores the
+//                        block's value; metrics_q2n_finalize_kernel averages them per image in a fixed order.
 //
 // Every sum is fp64 (products of two fp32 values are exact there): at sensor scale (mean 1000, sigma 5) a variance is a 4e4-th
 // of the raw second moment, which fp32 sums would lose entirely.  No atomics: each workgroup stores its partial sums with plain
@@ -387,6 +394,230 @@ __global__ void __launch_bounds__(256) metrics_noref_finalize_kernel(NorefFinalA
   o[0] = dl; o[1] = ds; o[2] = (1.0 - dl) * (1.0 - ds);
 }
 
+// ---- Q2n --------------------------------------------------------------------------------------------------------------------
+constexpr int Q2N_PAD = 4;   // floats after each staged band: the four band tiles a wave reads then fall on different LDS banks
+
+struct Q2nArgs {
+  const float* a;   // ground truth
+  const float* b;   // fused
+  long asB, asC, bsB, bsC;
+  int C, Cp, H, W, block, shift, nx, nblk;   // Cp: C padded to a power of two; nblk = ny * nx
+  unsigned long long neg[4];                 // bit i * 16 + j: e_i e_j = -e_(i xor j)
+  double* vals;     // [B][nblk]
+  double* map;      // [B][nblk] or null
+};
+
+__host__ __device__ inline int q2n_tile(int Cp) { return Cp < 4 ? Cp : 4; }   // a lane owns a T x T tile of band pairs
+
+// Sum of N values per lane over groups of G consecutive lanes (G a power of two, 16 <= G <= 256, the same for the whole
+// workgroup): every lane of a group gets the group's sum.  Butterflies inside a wave, then the group's waves in order through
+// red[4][16]: a fixed order.
+template <int N>
+__device__ __forceinline__ void group_sum(double (&v)[N], int G, double (*red)[16], int t) {
+  const int gw = G < 64 ? G : 64;
+#pragma unroll
+  for (int k = 0; k < N; ++k)
+    for (int m = gw >> 1; m >= 1; m >>= 1) v[k] += __shfl_xor(v[k], m, 64);
+  if (G > 64) {
+    const int wave = t >> 6, wpg = G >> 6, w0 = (wave / wpg) * wpg;
+    __syncthreads();   // earlier readers of red are done
+    if ((t & 63) == 0)
+#pragma unroll
+      for (int k = 0; k < N; ++k) red[wave][k] = v[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      double s = red[w0][k];
+      for (int i = 1; i < wpg; ++i) s += red[w0 + i][k];
+      v[k] = s;
+    }
+  }
+}
+
+template <int T>
+__device__ __forceinline__ void q2n_gram(const float* sg, const float* sf, int bs, int n, int Cp, const double* mean, double (*gram)[16],
+                                         double (*red)[16], int t) {
+  const int tpr = Cp / T, tiles = tpr * tpr, slices = 256 / tiles;   // 16 / 64 / 256 / 256 / 256 slices for Cp = 16 / 8 / 4 / 2 / 1
+  const int tile = t / slices, s = t - tile * slices, i0 = (tile / tpr) * T, j0 = (tile % tpr) * T;
+  double mi[T], mj[T], acc[T * T];
+#pragma unroll
+  for (int u = 0; u < T; ++u) mi[u] = mean[i0 + u], mj[u] = mean[j0 + u];
+#pragma unroll
+  for (int u = 0; u < T * T; ++u) acc[u] = 0.0;
+  for (int p = s; p < n; p += slices) {
+    double dg[T], df[T];
+#pragma unroll
+    for (int u = 0; u < T; ++u) dg[u] = (double)sg[(i0 + u) * bs + p] - mi[u], df[u] = (double)sf[(j0 + u) * bs + p] - mj[u];
+#pragma unroll
+    for (int u = 0; u < T; ++u)
+#pragma unroll
+      for (int v = 0; v < T; ++v) acc[u * T + v] += dg[u] * df[v];
+  }
+  group_sum<T * T>(acc, slices, red, t);
+  if (s == 0)
+#pragma unroll
+    for (int u = 0; u < T; ++u)
+#pragma unroll
+      for (int v = 0; v < T; ++v) gram[i0 + u][j0 + v] = acc[u * T + v];
+}
+
+__global__ void __launch_bounds__(256) metrics_q2n_kernel(Q2nArgs p) {
+  extern __shared__ float q2n_lds[];         // [2][Cp][n + Q2N_PAD]: the window of a, then of b
+  __shared__ double st[7][16];               // per band: mean a, divisor of x, divisor of y, sum dg, sum dg^2, sum df, sum df^2
+  __shared__ double gram[16][16];            // sum over pixels of dg_i df_j
+  __shared__ double red[4][16];
+  __shared__ double qv[16];
+
+  const int t = threadIdx.x, Cp = p.Cp, block = p.block, n = block * block, bs = n + Q2N_PAD;
+  const int img = blockIdx.x / p.nblk, blk = blockIdx.x - img * p.nblk;
+  const int by = blk / p.nx, bx = blk - by * p.nx, y0 = by * p.shift, x0 = bx * p.shift;
+  float* sg = q2n_lds;
+  float* sf = q2n_lds + Cp * bs;
+
+  const int lb = block == 8 ? 3 : block == 16 ? 4 : 5;
+  // staging: row H + k is row H - 1 - k (the host checked that the mirror stays inside the image); bands past C are zero
+  for (int i = t; i < Cp * n; i += 256) {
+    const int c = i >> (2 * lb), px = i & (n - 1), ly = px >> lb, lx = px & (block - 1);
+    int yy = y0 + ly, xx = x0 + lx;
+    yy = yy < p.H ? yy : 2 * p.H - 1 - yy;
+    xx = xx < p.W ? xx : 2 * p.W - 1 - xx;
+    const bool in = c < p.C;
+    const int cc = in ? c : 0, off = yy * p.W + xx;
+    const float va = p.a[(long)img * p.asB + (long)cc * p.asC + off], vb = p.b[(long)img * p.bsB + (long)cc * p.bsC + off];
+    sg[c * bs + px] = in ? va : 0.f;
+    sf[c * bs + px] = in ? vb : 0.f;
+  }
+  __syncthreads();
+
+  // pass one: 256 / Cp lanes per band
+  {
+    const int G = 256 / Cp, c = t / G, l = t - c * G;
+    double m[1] = {0.0};
+    for (int px = l; px < n; px += G) m[0] += (double)sg[c * bs + px];
+    group_sum<1>(m, G, red, t);
+    const double mean = m[0] / (double)n;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int px = l; px < n; px += G) {
+      const double dg = (double)sg[c * bs + px] - mean, df = (double)sf[c * bs + px] - mean;
+      s[0] += dg; s[1] += dg * dg; s[2] += df; s[3] += df * df;
+    }
+    group_sum<4>(s, G, red, t);
+    if (l == 0) {
+      double sd = sqrt(s[1] / (double)(n - 1));
+      if (sd == 0.0) sd = 0x1p-52;
+      st[0][c] = mean; st[1][c] = sd; st[2][c] = mean == 0.0 ? 1.0 : sd;
+      st[3][c] = s[0]; st[4][c] = s[1]; st[5][c] = s[2]; st[6][c] = s[3];
+    }
+  }
+  __syncthreads();
+
+  // pass two: the cross products
+  if (Cp >= 4) q2n_gram<4>(sg, sf, bs, n, Cp, st[0], gram, red, t);
+  else if (Cp == 2) q2n_gram<2>(sg, sf, bs, n, Cp, st[0], gram, red, t);
+  else q2n_gram<1>(sg, sf, bs, n, Cp, st[0], gram, red, t);
+  __syncthreads();
+
+  // the block's value.  With u_i = sum dg_i / sx_i and w_j = sum df_j / sy_j:  sum x_i = u_i + n,  sum y_j = w_j + n,
+  // sum x_i y_j = gram_ij / (sx_i sy_j) + u_i + w_j + n,  sum x_i^2 = sum dg_i^2 / sx_i^2 + 2 u_i + n, and y likewise.
+  // No contraction here: t3 == 0 is an exact test that the host makes with separately rounded products.
+  {
+#pragma clang fp contract(off)
+    const double nn = (double)n, k = nn / (nn - 1.0);
+    double e1 = 0.0, e2 = 0.0, sxx = 0.0, syy = 0.0;
+    for (int c = 0; c < Cp; ++c) {
+      const double u = st[3][c] / st[1][c], w = st[5][c] / st[2][c];
+      const double m1 = u / nn + 1.0, m2 = w / nn + 1.0;
+      e1 += m1 * m1; e2 += m2 * m2;
+      sxx += (st[4][c] / st[1][c] / st[1][c] + 2.0 * u + nn) / nn;
+      syy += (st[6][c] / st[2][c] / st[2][c] + 2.0 * w + nn) / nn;
+    }
+    const double bias = 2.0 * sqrt(e1 * e2) / (e1 + e2);
+    const double t3 = (k * sxx + k * syy) - k * (e1 + e2);
+    if (t < Cp) {
+      double q = 0.0;
+      if (t3 == 0.0) {
+        q = t == Cp - 1 ? bias : 0.0;
+      } else {
+        double ex = 0.0, mm = 0.0;   // component t of mean(x * y) and of m1 * m2: the pairs (i, i xor t)
+        for (int i = 0; i < Cp; ++i) {
+          const int j = i ^ t, bit = i * 16 + j;
+          const double sgn = (((p.neg[bit >> 6] >> (bit & 63)) & 1ull) != 0) == (j != 0) ? 1.0 : -1.0;   // times y's conjugation
+          const double u = st[3][i] / st[1][i], w = st[5][j] / st[2][j];
+          const double xy = gram[i][j] / st[1][i] / st[2][j] + u + w + nn;
+          ex += sgn * (xy / nn);
+          mm += sgn * ((u / nn + 1.0) * (w / nn + 1.0));
+        }
+        q = (k * ex - k * mm) * bias * 2.0 / t3;
+      }
+      qv[t] = q * q;
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    double s = 0.0;
+    for (int c = 0; c < Cp; ++c) s += qv[c];
+    const double v = sqrt(s);
+    p.vals[(long)img * p.nblk + blk] = v;
+    if (p.map) p.map[(long)img * p.nblk + blk] = v;
+  }
+}
+
+// Lane t adds the blocks t, t + 256, ... in order; then the waves' butterflies and the four waves in order: the order depends on
+// the number of blocks alone.
+__global__ void __launch_bounds__(256) metrics_q2n_finalize_kernel(const double* vals, int nblk, double* out) {
+  __shared__ double red[4];
+  const int t = threadIdx.x, img = blockIdx.x;
+  double s = 0.0;
+  for (int i = t; i < nblk; i += 256) s += vals[(long)img * nblk + i];
+  s = wave_sum(s);
+  if ((t & 63) == 0) red[t >> 6] = s;
+  __syncthreads();
+  if (t == 0) out[img] = (((red[0] + red[1]) + red[2]) + red[3]) / (double)nblk;
+}
+
+// Cayley-Dickson product of two n-vectors (n a power of two; metrics.cd_mul): with p = (a, b), r = (c, d),
+// p r = (a c - d conj(b), conj(a) d + c b)
+void cd_mul(const double* p, const double* r, double* out, int n) {
+  if (n == 1) { out[0] = p[0] * r[0]; return; }
+  const int h = n / 2;
+  double cb[8], ca[8], u[8], v[8];
+  for (int i = 0; i < h; ++i) cb[i] = i ? -p[h + i] : p[h + i], ca[i] = i ? -p[i] : p[i];
+  cd_mul(p, r, u, h); cd_mul(r + h, cb, v, h);
+  for (int i = 0; i < h; ++i) out[i] = u[i] - v[i];
+  cd_mul(ca, r + h, u, h); cd_mul(r, p + h, v, h);
+  for (int i = 0; i < h; ++i) out[h + i] = u[i] + v[i];
+}
+
+// the signs of e_i e_j = +-e_(i xor j) for 16 components (the tables of 1, 2, 4 and 8 components are its leading blocks)
+void q2n_signs(unsigned long long (&neg)[4]) {
+  neg[0] = neg[1] = neg[2] = neg[3] = 0;
+  for (int i = 0; i < 16; ++i)
+    for (int j = 0; j < 16; ++j) {
+      double ei[16] = {0}, ej[16] = {0}, o[16];
+      ei[i] = ej[j] = 1.0;
+      cd_mul(ei, ej, o, 16);
+      if (o[i ^ j] < 0.0) neg[(i * 16 + j) >> 6] |= 1ull << ((i * 16 + j) & 63);
+    }
+}
+
+int q2n_bands(int C) {
+  int cp = 1;
+  while (cp < C) cp *= 2;
+  return cp;
+}
+
+struct Q2nGrid { int ny, nx; };
+bool q2n_ok(int B, int C, int H, int W, int block, int shift, Q2nGrid* g = nullptr) {
+  if (!(B >= 0 && C >= 1 && C <= MAXC && H >= 1 && W >= 1 && (double)B * C * H * W <= 2147483647.0)) return false;
+  if (!(block == 8 || block == 16 || block == 32) || shift < 1 || shift > block) return false;
+  const long ny = ((long)H + shift - 1) / shift, nx = ((long)W + shift - 1) / shift;
+  if ((ny - 1) * shift + block - H > H || (nx - 1) * shift + block - W > W) return false;   // the mirror stays inside the image
+  if ((double)B * ny * nx > 2147483647.0) return false;
+  if (g) g->ny = (int)ny, g->nx = (int)nx;
+  return true;
+}
+size_t q2n_lds_bytes(int Cp, int block) { return (size_t)2 * Cp * (block * block + Q2N_PAD) * sizeof(float); }
+
 bool extents_ok(int B, int C, int H, int W) {
   return B >= 0 && C >= 1 && C <= MAXC && H >= 7 && W >= 7 && (double)B * C * H * W <= 2147483647.0;
 }
@@ -458,6 +689,58 @@ int tmdiff_metrics_noref(const float* l_ms, int64_t l_ms_stride_b, int64_t l_ms_
   const NorefFinalArgs f{hi, lo, C, gh.wgs, gl.wgs, (double)H * W, (double)h * w, out};
   metrics_noref_finalize_kernel<<<B, 256, 0, st>>>(f);
   return tmdiff::check_launch("metrics_noref (finalize)");
+}
+
+int tmdiff_metrics_q2n_supported(int32_t B, int32_t C, int32_t H, int32_t W, int32_t block, int32_t shift) {
+  return q2n_ok(B, C, H, W, block, shift);
+}
+
+size_t tmdiff_metrics_q2n_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t block, int32_t shift) {
+  Q2nGrid g;
+  if (!q2n_ok(B, C, H, W, block, shift, &g)) return 0;
+  return (size_t)B * g.ny * g.nx * sizeof(double);
+}
+
+int tmdiff_metrics_q2n(const float* x_true, int64_t true_stride_b, int64_t true_stride_c, const float* x_pred, int64_t pred_stride_b,
+                       int64_t pred_stride_c, int32_t B, int32_t C, int32_t H, int32_t W, int32_t block, int32_t shift, double* out,
+                       double* map_out, void* workspace, size_t workspace_bytes, tmdiff_stream_t stream) {
+  Q2nGrid g;
+  if (!q2n_ok(B, C, H, W, block, shift, &g))
+    return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "metrics_q2n: B=%d C=%d H=%d W=%d block=%d shift=%d (1 <= C <= 16, block 8, 16 or 32, 1 <= "
+                        "shift <= block, mirror padding no longer than the axis, fewer than 2^31 elements)", B, C, H, W, block, shift);
+  if (B == 0) return TMDIFF_OK;
+  const size_t need = (size_t)B * g.ny * g.nx * sizeof(double);
+  TMDIFF_REQUIRE(x_true && x_pred && out && workspace, "metrics_q2n: null tensor");
+  TMDIFF_REQUIRE(true_stride_b >= 0 && true_stride_c >= (int64_t)H * W && pred_stride_b >= 0 && pred_stride_c >= (int64_t)H * W,
+                 "metrics_q2n: channel strides below a plane of %d x %d", H, W);
+  TMDIFF_REQUIRE(workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0,
+                 "metrics_q2n: workspace of %zu bytes, %zu needed (8-byte aligned)", workspace_bytes, need);
+  const hipStream_t st = tmdiff::as_stream(stream);
+  const int Cp = q2n_bands(C);
+  const size_t lds = q2n_lds_bytes(Cp, block);
+  if (lds > 48 * 1024) {
+    // more dynamic LDS than a launch gets by default: raise the kernel's limit once per device (131,584 bytes at the most)
+    static size_t raised[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return tmdiff::fail(TMDIFF_E_LAUNCH, "metrics_q2n: no current device");
+    if (raised[dev] < lds) {
+      const size_t most = q2n_lds_bytes(MAXC, 32);
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(metrics_q2n_kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)most);
+      if (e != hipSuccess) return tmdiff::fail(TMDIFF_E_LAUNCH, "metrics_q2n: %zu bytes of LDS: %s", most, hipGetErrorString(e));
+      raised[dev] = most;
+    }
+  }
+  Q2nArgs a{x_true, x_pred, true_stride_b, true_stride_c, pred_stride_b, pred_stride_c, C, Cp, H, W, block, shift, g.nx, g.ny * g.nx,
+            {0, 0, 0, 0}, static_cast<double*>(workspace), map_out};
+  static unsigned long long signs[4];
+  static const bool signs_made = (q2n_signs(signs), true);
+  (void)signs_made;
+  for (int i = 0; i < 4; ++i) a.neg[i] = signs[i];
+  metrics_q2n_kernel<<<(unsigned)((long)B * a.nblk), 256, lds, st>>>(a);
+  if (const int rc = tmdiff::check_launch("metrics_q2n")) return rc;
+  metrics_q2n_finalize_kernel<<<B, 256, 0, st>>>(a.vals, a.nblk, out);
+  return tmdiff::check_launch("metrics_q2n (finalize)");
 }
 
 }  // extern "C"

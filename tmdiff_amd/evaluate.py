@@ -31,7 +31,7 @@ def _to_nchw01(img, min_max=(0.0, 1.0)):
 
 
 def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=print, device_metrics=False,
-                full_resolution=False):
+                full_resolution=False, q2n=False):
     """``trainer`` is a ``tmdiff_amd.model.DDPM`` (or the reference's); ``dataset`` is the prompt name.
     Returns ``{"ssim_<dataset>": ..., "sam_<dataset>": ..., "sec_per_item": ...}``.
 
@@ -44,13 +44,20 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
     ``ops.metrics_noref(LR, PAN, ops.pyr_down(PAN), SR)``, with the low-resolution PAN and the workspace allocated once per
     shape, sums kept on the device and one synchronising read at the end.  Returns ``{"d_lambda_<dataset>": ...,
     "d_s_<dataset>": ..., "qnr_<dataset>": ..., "sec_per_item": ...}`` and no ``ssim_`` / ``sam_`` keys; the ``.mat`` files
-    are written as in the other modes.  ValueError when the visuals carry no ``LR`` or ``PAN``."""
+    are written as in the other modes.  ValueError when the visuals carry no ``LR`` or ``PAN``.
+
+    ``q2n=True`` (with ``device_metrics=True`` only, and not with ``full_resolution=True``: ValueError otherwise) adds
+    ``q2n_<dataset>``: the mean over the items of ``ops.metrics_q2n`` (Q4 / Q8 on 32 x 32 blocks), accumulated on the device with
+    its workspace allocated once per shape and read in the same synchronising read."""
+    if q2n and (full_resolution or not device_metrics):
+        raise ValueError("val_dataset(q2n=True) scores on the GPU against ground truth: it needs device_metrics=True and "
+                         "full_resolution=False")
     result_path = os.path.join(result_root, dataset)
     os.makedirs(result_path, exist_ok=True)
     scale = IMG_SCALE.get(dataset, 2047.0)
     ssim_sum = sam_sum = 0.0
     n = 0
-    dev_sum, dev_ws = None, {}
+    dev_sum, dev_ws, q2n_ws = None, {}, {}
     full_sum, full_ws = None, {}
     t0 = time.time()
     for idx, val_data in enumerate(val_loader):
@@ -77,6 +84,10 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
             if hr_d.shape not in dev_ws:
                 dev_ws[hr_d.shape] = ops.metrics_workspace(*hr_d.shape, hr_d.device)
             row = ops.metrics_pair(hr_d, sr_d, 1.0, workspace=dev_ws[hr_d.shape])[0]
+            if q2n:
+                if hr_d.shape not in q2n_ws:
+                    q2n_ws[hr_d.shape] = ops.metrics_q2n_workspace(*hr_d.shape, hr_d.device)
+                row = torch.cat([row, ops.metrics_q2n(hr_d, sr_d, workspace=q2n_ws[hr_d.shape])])
             dev_sum = row if dev_sum is None else dev_sum + row
         elif "HR" in vis:
             hr = to_hwc01(vis["HR"])
@@ -91,9 +102,9 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
         return score
     extra = {}
     if dev_sum is not None:
-        total = dict(zip(metrics.PAIR_FIELDS, dev_sum.tolist()))                     # the one synchronising read
+        total = dict(zip(metrics.PAIR_FIELDS + ("q2n",), dev_sum.tolist()))          # the one synchronising read
         ssim_sum, sam_sum = total["ssim"], total["sam"]
-        extra = {f"{k}_{dataset}": total[k] / max(n, 1) for k in ("psnr", "ergas", "scc", "cc", "q")}
+        extra = {f"{k}_{dataset}": total[k] / max(n, 1) for k in ("psnr", "ergas", "scc", "cc", "q") + (("q2n",) if q2n else ())}
     score = {f"ssim_{dataset}": ssim_sum / max(n, 1), f"sam_{dataset}": sam_sum / max(n, 1),
              "sec_per_item": (time.time() - t0) / max(n, 1), **extra}
     log(dataset, score)

@@ -1138,6 +1138,56 @@ def metrics_noref(l_ms, pan, l_pan, ps, out=None, workspace=None):
     return y
 
 
+_Q2N_LIMITS = "1 <= C <= 16, block 8, 16 or 32, 1 <= shift <= block, mirror padding no longer than the axis, fewer than 2^31 elements"
+
+
+def q2n_grid(h, w, block=32, shift=32):
+    """(ny, nx) of the windows of metrics_q2n: ceil(h / shift), ceil(w / shift)."""
+    if shift < 1:
+        raise ValueError(f"q2n_grid: shift={shift} ({_Q2N_LIMITS})")
+    return -(-int(h) // int(shift)), -(-int(w) // int(shift))
+
+
+def metrics_q2n_supported(b, c, h, w, block=32, shift=32):
+    """True when metrics_q2n takes a [b, c, h, w] image batch with these windows."""
+    return bool(lib.tmdiff_metrics_q2n_supported(int(b), int(c), int(h), int(w), int(block), int(shift)))
+
+
+def metrics_q2n_workspace(b, c, h, w, device, block=32, shift=32):
+    """A workspace metrics_q2n accepts for [b, c, h, w] images (reusable; captured calls must keep it alive)."""
+    nbytes = lib.tmdiff_metrics_q2n_workspace_bytes(int(b), int(c), int(h), int(w), int(block), int(shift))
+    return torch.empty(max(1, nbytes // 8), device=device, dtype=torch.float64)
+
+
+def metrics_q2n(x_true, x_pred, block=32, shift=32, out=None, map_out=None, workspace=None):
+    """Q2n (Q4 / Q8; definition: ``metrics.q2n``) of x_pred against x_true, both float32 [B, C, H, W]: float64 [B].  ``map_out``,
+    a float64 [B, ny, nx] tensor (``q2n_grid``), receives the windows' values."""
+    if x_true.shape != x_pred.shape:
+        raise ValueError(f"metrics_q2n: shapes {tuple(x_true.shape)} and {tuple(x_pred.shape)} differ")
+    pa, asb, asc = _planes(x_true, "x_true")
+    pb, bsb, bsc = _planes(x_pred, "x_pred")
+    b, c, h, w = x_true.shape
+    block, shift = int(block), int(shift)
+    if not metrics_q2n_supported(b, c, h, w, block, shift):
+        raise ValueError(f"metrics_q2n: B={b} C={c} H={h} W={w} block={block} shift={shift} is not supported ({_Q2N_LIMITS})")
+    ny, nx = q2n_grid(h, w, block, shift)
+    dev = x_true.device
+    y = out if out is not None else torch.empty(b, device=dev, dtype=torch.float64)
+    if not (y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and tuple(y.shape) == (b,)):
+        raise ValueError(f"metrics_q2n: out must be a contiguous float64 [{b}] tensor on the GPU")
+    if map_out is not None and not (map_out.is_cuda and map_out.dtype == torch.float64 and map_out.is_contiguous()
+                                    and tuple(map_out.shape) == (b, ny, nx)):
+        raise ValueError(f"metrics_q2n: map_out must be a contiguous float64 [{b}, {ny}, {nx}] tensor on the GPU")
+    ws = workspace if workspace is not None else metrics_q2n_workspace(b, c, h, w, dev, block, shift)
+    nbytes, need = ws.numel() * ws.element_size(), lib.tmdiff_metrics_q2n_workspace_bytes(b, c, h, w, block, shift)
+    if not (ws.is_cuda and ws.is_contiguous() and nbytes >= need):
+        raise ValueError(f"metrics_q2n: workspace of {nbytes} bytes, need {need}")
+    check(lib.tmdiff_metrics_q2n(pa, asb, asc, pb, bsb, bsc, b, c, h, w, block, shift, y.data_ptr(),
+                                 map_out.data_ptr() if map_out is not None else None, ws.data_ptr(), nbytes, stream_ptr()),
+          "metrics_q2n")
+    return y
+
+
 # ---- resampling of full-resolution scenes (csrc/resample.hip; definitions: tmdiff_amd/metrics.py) --------------------
 def _resample_args(name, x, shape_of, out, limits):
     """(x pointer, y, y pointer) of a resampling call: x float32 [B, C, H, W] on the GPU, contiguous, fewer than 2^31 elements
