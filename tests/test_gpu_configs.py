@@ -528,19 +528,19 @@ def test_config4_finetune_step_vs_oracle_autograd(switches):
         np.random.randint = orig
     for lt, (lo, lh, _) in res.items():
         assert abs(lo - lh) <= 1e-5 * abs(lo), (lt, lo, lh)
+    # the launches of the step are the tabulated ones, family by family, and the switch really selected the other path
+    from tmdiff_amd import routing
     cnt = res["l2"][2]
-    if ops.config.winograd and ops.config.ll_compose:   # (experiment switches off)
-        assert (cnt.get("conv3d_wf_fwd", 0) + cnt.get("conv3d_wino4_fwd", 0) + cnt.get("conv3d_wino2_fwd", 0) >= 40 and
-                cnt.get("conv3d_ll_fwd", 0) + cnt.get("conv3d_wfll_fwd", 0) == 3), cnt
-    # the switch really selected the other path
+    with ops.config.override(**switches):
+        assert cnt == routing.unet_train_launches(FULL, 8, 8, 64, 64).counts, cnt
     if switches.get("wgrad_wino") is False:
-        assert cnt.get("conv3d_wgrad_wino", 0) == 0 and cnt.get("conv3d_wgrad", 0) > 40, cnt
+        assert "conv3d_wgrad_wino" not in cnt and cnt["conv3d_wgrad"] == 70, cnt
     elif not switches:
-        assert cnt.get("conv3d_wgrad_wino", 0) > 40, cnt
+        assert cnt["conv3d_wgrad_wino"] == 51 and cnt["conv3d_wf_fwd"] == 99, cnt
     if switches.get("train_ll_wino") is False:
-        assert cnt.get("conv3d_wfll_fwd", 0) == 0 and cnt.get("conv3d_ll_fwd", 0) == 3, cnt
+        assert "conv3d_wfll_fwd" not in cnt and cnt["conv3d_ll_fwd"] == 3, cnt
     elif not switches:
-        assert cnt.get("conv3d_wfll_fwd", 0) == 3, cnt
+        assert cnt["conv3d_wfll_fwd"] == 3, cnt
     ref_g = _C4_ORACLE["grads"]
     hip_g = dict(net.named_parameters())
     report = []
@@ -561,6 +561,47 @@ def test_config4_finetune_step_vs_oracle_autograd(switches):
         m, l2 = rel_err(p.grad, ref_g[k])
         assert l2 <= 1e-4, (k, m, l2)
     assert n == 272 - 56
+
+
+@pytest.mark.parametrize("channels,b,n,size,switches", [
+    ([16, 32, 64, 64], 2, 8, 64, {"wino_min_blocks": 1}),
+    ([16, 32, 64, 64], 2, 4, 128, {"wino_min_blocks": 1}),
+    ([16, 32, 64, 64], 2, 8, 64, {"wino_min_blocks": 1, "train_ll_wino": False}),
+    ([4, 8, 16, 32], 2, 8, 16, {}),
+], ids=["8-band", "4-band", "8-band-conv3d_ll", "tiny-direct"])
+def test_finetune_step_launches_equal_the_train_table(channels, b, n, size, switches):
+    """One GeneralDiffusion L2 step, forward plus backward, of the small networks of routing.TRAIN_CASES (conv3d_wf with its
+    pair mode, the general-shape direct kernel, Conv_0 + LL composed both ways, both weight-gradient kernels; the last case:
+    everything on the direct kernels under the default switches) under ops.COUNTS: the launches are EXACTLY
+    routing.unet_train_launches' -- with dropout off (net.eval()) and with in-kernel dropout (net.train(): kept x', the staged
+    kernel's pass) -- and the loss and every gradient are finite."""
+    import collections
+    from tmdiff_amd import ops, routing
+    from tmdiff_amd.diffusion_general import GeneralDiffusion
+    assert (channels, b, n, size, switches) in [c[1:] for c in routing.TRAIN_CASES]       # (the committed table has this case)
+    net = _hip_net(channels)
+    diff = GeneralDiffusion(net, "l2").cuda()
+    diff.set_loss("cuda")
+    diff.set_new_noise_schedule({"schedule": "cosine", "n_timestep": 1000}, "cuda")
+    d = {k: cu(v) for k, v in case_inputs(3450, b, n, size).items()}
+    with ops.config.override(**switches):
+        for training in (False, True):
+            net.train(training)
+            np.random.seed(3); torch.manual_seed(4)
+            net.zero_grad(set_to_none=True)
+            counts = ops.COUNTS = collections.Counter()
+            try:
+                loss = diff(d, "WV3" if n == 8 else "GF2")
+                loss.backward()
+            finally:
+                ops.COUNTS = None
+            want = routing.unet_train_launches(channels, b, n, size, size, dropout=training).counts
+            print("training" if training else "eval", dict(counts))
+            assert dict(counts) == want, (training, dict(counts), want)
+            grads = [p.grad for p in net.parameters()]       # (56 tensors the reference's forward never uses, whatever the widths)
+            assert np.isfinite(float(loss)) and sum(g is None for g in grads) == 56
+            assert all(bool(torch.isfinite(g).all()) for g in grads if g is not None)
+    net.eval()
 
 
 def test_round3_kernels_at_full_size_properties():

@@ -916,3 +916,164 @@ def test_model_decisions_equal_the_fusion_rows(channels, b, n, size, switches):
         rows = {r.block: r.taken for r in routing.unet_fusions(channels, b, n, size, size) if r.kind in ("resblock", "down")}
     assert got == rows
     assert any(got.values())
+
+
+# ---- the finetune graph: plans, launches, table ------------------------------------------------------------------------
+def test_train_routing_table_is_the_committed_one():
+    """The launches of the finetune step (tmdiff_amd.routing.unet_train_launches), tabulated without a GPU: the table
+    committed as profiles/train_routing_table.txt is this code's (tools/routing_table.py --train).  The configs[3] step
+    (B = 8, 8 bands, 64x64, widths 32-256) runs its three main-branch Conv_0 composed with the LL band on conv3d_wf, every 3x3x3
+    weight gradient (51) in the Winograd domain and the 19 1x1x1 ones on the direct kernel; the small 8-band network that
+    tests/test_gpu_configs.py counts launch by launch still reaches every family (conv3d_wf with a pair-mode layer at its 8x8
+    level, a direct forward family, a composed Conv_0 + LL, both weight-gradient kernels)."""
+    import subprocess, sys
+    from tmdiff_amd import ops, routing
+    assert ops.config.as_dict() == ops.KernelConfig(env={}).as_dict(), "this table is that of the default switches"
+    c3 = routing.unet_train_launches(routing.FULL, 8, 8, 64, 64)
+    assert len(c3.convs) == 51 + 19 and sum(c3.counts.values()) == 3 * 70
+    assert c3.counts["conv3d_wfll_fwd"] == 3 and c3.counts["conv3d_wgrad_wino"] == 51 and c3.counts["conv3d_wgrad"] == 19
+    assert c3.counts["conv3d_fwd_k1"] == 2 * 19
+    label, ch, b, n, size, switches = routing.TRAIN_CASES[2]
+    assert n == 8 and "train_ll_wino" not in switches, label
+    with ops.config.override(**switches):
+        for dropout in (False, True):
+            r = routing.unet_train_launches(ch, b, n, size, size, dropout)
+            assert r.counts["conv3d_wf_fwd"] and r.counts["conv3d_wgrad_wino"] and r.counts["conv3d_wgrad"], r.counts
+            assert r.counts.get("conv3d_fwd_staged") or r.counts.get("conv3d_fwd"), r.counts
+            assert r.counts.get("conv3d_wfll_fwd") or r.counts.get("conv3d_ll_fwd"), r.counts
+            assert any("wf_pair" in (c.fwd, c.dgrad) and (c.h, c.w) == (8, 8) for c in r.convs)
+        assert any(c.keep_xp and c.fwd in ("wf", "wf_pair") for c in r.convs)
+    # (x' kept by the staged kernel's pass: the narrow networks, on the direct kernels under the default switches)
+    assert any(c.keep_xp and c.fwd == "staged" for c in routing.unet_train_launches([4, 8, 16, 32], 2, 8, 16, 16, True).convs)
+    # the inference table's configs[3] row says what it is
+    assert "inference graph" in [c[0] for c in routing.BASELINE_CASES if c[0].startswith("configs[3]")][0]
+    path = os.path.join(ROOT, "profiles", "train_routing_table.txt")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "routing_table.py"), "--train"], capture_output=True, text=True,
+                         timeout=300)
+    assert out.returncode == 0, out.stderr[-1000:]
+    assert out.stdout == open(path).read(), "profiles/train_routing_table.txt is stale: python tools/routing_table.py --train > " + path
+
+
+def _model_train_plans(net, b, n, size, dropout):
+    """({convolution: plan}, {block: plan}) a CPU WavBEST asks for in one forward_train: its blocks' train_plan (what their `run`
+    executes) and autograd.conv_plan / routing.train_ll_plan (what _conv_forward / _ConvLL execute) with the weight shapes and
+    groups of its own modules, on stand-ins with the extents of the tensors (nothing allocated)."""
+    from torch import nn
+    from tmdiff_amd import autograd as A, routing
+
+    class X:
+        def __init__(self, ch, k):
+            self.shape = (b, ch, n, size >> k, size >> k)
+
+    c, convs, blocks = net.channels, {}, {}
+    drop = A.DropSpec(1, 0.2) if dropout else None
+
+    def conv(name, segs, prologue=False, mask=None):
+        m = net.get_submodule(name)
+        convs[name] = tuple(A.conv_plan(segs, m.weight.shape, m.groups, prologue, mask, True))
+
+    def resblock(name, seg_c, k):
+        rb, segs = net.get_submodule(name), [X(ch, k) for ch in seg_c]
+        blocks[name] = rb.train_plan(segs)
+        conv(name + ".conv20", segs, True, drop)
+        if isinstance(rb.res_conv, nn.Conv3d):
+            conv(name + ".res_conv", segs)
+        conv(name + ".conv21", [X(rb.conv20.out_channels, k)], True, drop)
+
+    def wavelet(name, k, want_high=True):
+        m = net.get_submodule(name)
+        x = X(m.in_ch, k)
+        p = m.train_plan(x, want_high)
+        if m.down:
+            blocks[name] = p
+        if p.conv0:
+            ll = routing.train_ll_plan(b, m.Conv_0.in_channels, m.Conv_0.out_channels, *x.shape[2:])
+            convs[name + ".Conv_0"] = (ll.fwd, True, ll.dgrad, ll.wgrad, False)
+        else:
+            conv(name + ".Conv_0", [x], True)
+        conv(name + ".Conv_2", [X(m.in_ch, k + 1 if p.conv2_after_ll else k)])
+        if m.up:
+            conv(name + ".convH_0.0", [X(m.convH_0[0].in_channels // 3, k)] * 3)
+        conv(name + ".Conv_1", [X(m.in_ch, k + 1 if m.down else k - 1)], True, drop)
+
+    for branch in ("_1", ""):
+        conv(("conv1" if branch else "conv2") + ".conv21", [X(c[0], 0)], True)
+        for k in range(3):
+            resblock(f"down{k + 1}{branch}.conv20", [c[k]], k)
+            wavelet(f"down{k + 1}{branch}.down", k, want_high=bool(branch))
+    resblock("middle1", [c[3]], 3)
+    for k, upn in ((3, "up1"), (2, "up2"), (1, "up3")):
+        resblock(upn + ".conv20", [c[k]] * 3, k)
+        wavelet(upn + ".up1", k)
+    resblock("final.conv20", [c[0]] * 3, 0)
+    for k in (1, 2, 3):
+        resblock(f"final.conv2{k}", [c[0]], 0)
+    return convs, blocks
+
+
+@pytest.mark.parametrize("channels,b,n,size,switches", [
+    ([32, 64, 128, 256], 8, 8, 64, {}),                                       # configs[3]
+    ([16, 32, 64, 128], 8, 8, 64, {}),                                        # the reference's default widths
+    ([16, 32, 64, 64], 2, 8, 64, {"wino_min_blocks": 1}),                     # the small cases of tests/test_gpu_configs.py
+    ([16, 32, 64, 64], 2, 4, 128, {"wino_min_blocks": 1}),
+    ([16, 32, 64, 64], 2, 8, 64, {"wino_min_blocks": 1, "train_ll_wino": False}),
+    ([4, 8, 16, 32], 2, 8, 16, {}),
+    ([32, 64, 128, 256], 8, 8, 64, {"wgrad_wino": False}),
+    ([32, 64, 128, 256], 8, 8, 64, {"train_fused_resblock": False}),
+    ([32, 64, 128, 256], 8, 8, 64, {"conv2_after_ll": False}),
+    ([32, 64, 128, 256], 8, 8, 64, {"wgrad_bias": True, "ll_compose": False}),
+])
+def test_model_train_plans_equal_the_train_rows(channels, b, n, size, switches):
+    """The block walk and the channel bookkeeping of routing.unet_train_launches against the real module tree, dropout off and
+    on: every convolution's plan and every block's plan, asked through the entries the finetune graph itself uses, is that
+    convolution's / block's row."""
+    from tmdiff_amd import ops, routing
+    from tmdiff_amd.Hyper_unet_general import WavBEST
+    net = WavBEST(channels=channels)
+    with ops.config.override(**switches):
+        for dropout in (False, True):
+            convs, blocks = _model_train_plans(net, b, n, size, dropout)
+            r = routing.unet_train_launches(channels, b, n, size, size, dropout)
+            assert convs == {c.name: tuple(c[7:]) for c in r.convs}
+            assert blocks == dict(r.blocks)
+            for c in r.convs:           # ... and the module tree's own extents
+                m = net.get_submodule(c.name)
+                assert (m.in_channels, m.out_channels, m.groups, m.kernel_size[0]) == (c.cin, c.cout, c.groups, c.ksize), c
+        nodes = set(p for p in blocks.values() if isinstance(p, str))
+    assert nodes == ({"separate"} if switches.get("train_fused_resblock") is False else {"rc", "id"})
+    assert all(p.conv2_after_ll == switches.get("conv2_after_ll", True) for p in blocks.values() if not isinstance(p, str))
+
+
+def test_train_predicates_agree_with_the_rules_they_came_from():
+    """One statement per rule: routing.staged_weight_ok is the shape half of direct_family's "staged" on every (cin, cout, groups)
+    of every layer of the tabulated cases (a plain input always wants the staged kernel, so the family IS the predicate), and
+    ops.wgrad_wino_takes / ops.conv3d_wgrad answer from routing.wgrad_family, which is the library's own query."""
+    import ctypes as C
+    from tmdiff_amd import _lib, ops, routing
+    seen = set()
+    for _, ch, b, n, size, _ in routing.BASELINE_CASES + routing.OTHER_CASES:
+        for L in routing.unet_conv3_layers(ch, size, size):
+            seen.add((L.cin, L.cout, L.groups))
+            assert (routing.direct_family(L.cin, L.cout, L.groups) == "staged") == routing.staged_weight_ok(L.cout, L.cin, L.groups), L
+            assert (routing.direct_family(L.cin, L.cout, L.groups, plain=False, keep_xp=True) == "staged") == \
+                routing.staged_weight_ok(L.cout, L.cin, L.groups), L
+    assert {routing.staged_weight_ok(co, ci, g) for ci, co, g in seen} == {True, False}
+    d = _lib.Conv3dDesc()
+    d.B, d.N, d.H, d.W, d.Cin, d.Cout, d.groups, d.ksize, d.nseg = 8, 8, 64, 64, 64, 64, 1, 3, 1
+    d.seg_c[0] = 64
+    cases = [d]
+    for field, bad in (("N", 6), ("W", 62), ("ksize", 1), ("groups", 2), ("in_act", 1)):
+        e = _lib.Conv3dDesc.from_buffer_copy(d)
+        setattr(e, field, bad)
+        cases.append(e)
+    e = _lib.Conv3dDesc.from_buffer_copy(d)         # three segments, as the up path's conv20
+    e.Cin, e.nseg = 192, 3
+    e.seg_c[0] = e.seg_c[1] = e.seg_c[2] = 64
+    cases.append(e)
+    for e in cases:
+        fam = routing.wgrad_family(e.B, tuple(e.seg_c[:e.nseg]), e.Cout, e.N, e.H, e.W, e.groups, e.ksize, bool(e.in_act))
+        lib_says = bool(e.ksize == 3 and _lib.lib.tmdiff_conv3d_wgrad_wino_supported(C.byref(e)))
+        assert ops.wgrad_wino_takes(e) == (fam == "wino") == lib_says, (e.N, e.W, e.ksize, e.groups, e.nseg)
+    assert ops.wgrad_wino_takes(d) and [ops.wgrad_wino_takes(e) for e in cases[1:5]] == [False] * 4
+    with ops.config.override(wgrad_wino=False):
+        assert not ops.wgrad_wino_takes(d) and routing.wgrad_family(8, (64,), 64, 8, 64, 64) == "direct"

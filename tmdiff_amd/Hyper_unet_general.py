@@ -128,6 +128,10 @@ class ResBlockModulateBEST(nn.Module):
         self.act = Swish()
         self.flag = flag
 
+    def train_plan(self, segs):
+        """routing.train_resblock_plan of this block on `segs` (tensors, or stand-ins with a .shape)."""
+        return routing.train_resblock_plan(tuple(s.shape[1] for s in segs), self.conv20.out_channels)
+
     def run(self, segs, shift, scale):
         """segs: the channel segments of the input (a torch.cat the reference materialises, :631-634)."""
         from . import autograd as A
@@ -135,11 +139,12 @@ class ResBlockModulateBEST(nn.Module):
         cin = sum(s.shape[1] for s in segs)
         dev = segs[0].device
         m20 = _drop_mask(self, (b, cin, n, h, w), self.dropout.p, dev)
-        if isinstance(self.res_conv, nn.Conv3d) and ops.config.train_fused_resblock:      # one autograd node: the two gradients of every input segment meet in a kernel
+        node = self.train_plan(segs)
+        if node == "rc":      # one autograd node: the two gradients of every input segment meet in a kernel
             m21 = _drop_mask(self, (b, self.conv20.out_channels, n, h, w), self.dropout.p, dev)
             return A.resblock_rc(segs, self.conv20.weight, self.conv20.bias, self.conv21.weight, self.res_conv.weight,
                                  self.res_conv.bias, None if self.flag else shift, scale, m20, m21)
-        if not isinstance(self.res_conv, nn.Conv3d) and len(segs) == 1 and ops.config.train_fused_resblock:
+        if node == "id":
             m21 = _drop_mask(self, (b, self.conv20.out_channels, n, h, w), self.dropout.p, dev)
             return A.resblock_id(segs[0], self.conv20.weight, self.conv20.bias, self.conv21.weight, None if self.flag else shift, scale, m20, m21)
         t1 = A.conv3d(segs, self.conv20.weight, self.conv20.bias, shift=None if self.flag else shift, act=True, mask=m20)
@@ -175,17 +180,21 @@ class WaveletUPorDown(nn.Module):
         self.dense1 = Dense(zemb_dim, in_ch)
         self.dense2 = Dense(zemb_dim, in_ch)      # exists in the reference (:366), unused by its forward
 
+    def train_plan(self, x, want_high=True):
+        """routing.train_down_plan of this block on x (a tensor, or a stand-in with a .shape); an up block composes nothing."""
+        if not self.down:
+            return routing.TrainDownPlan(None, False)
+        b, _, n, h, w = x.shape
+        return routing.train_down_plan(b, self.Conv_0.in_channels, n, h, w, not want_high)
+
     def run(self, x, shift, scale, skipH=None, want_high=True):
         from . import autograd as A
-        # down, high bands dropped: Conv_0 + halved LL band as one strided convolution (autograd._ConvLL)
-        from . import routing
-        ll = (self.down and not want_high and ops.config.ll_compose and
-              ops.ll_conv_supported(self.Conv_0.out_channels, self.Conv_0.in_channels, 3, 1) and
-              x.shape[3] % 2 == 0 and x.shape[4] % 2 == 0 and
-              routing.ll_fits(x.shape[0], self.Conv_0.in_channels, self.Conv_0.out_channels, *x.shape[2:]))
+        # down, high bands dropped: Conv_0 + halved LL band as one strided convolution (autograd._ConvLL) where the plan says so
+        plan = self.train_plan(x, want_high)
+        ll = plan.conv0 is not None
         hh = None if ll else A.conv3d([x], self.Conv_0.weight, self.Conv_0.bias, act=True)
         # down: Conv_2 commutes with the halved LL band (see WavBEST._down), so it runs after it, on a quarter of the positions
-        xx = None if self.down and ops.config.conv2_after_ll else A.conv3d([x], self.Conv_2.weight, self.Conv_2.bias)
+        xx = None if plan.conv2_after_ll else A.conv3d([x], self.Conv_2.weight, self.Conv_2.bias)
         hH = None
         if self.up:
             ch = self.convH_0[0]

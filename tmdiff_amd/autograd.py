@@ -9,13 +9,13 @@ import ctypes as C
 
 import torch
 
-from . import ops
-from ._lib import check, lib
+from . import ops, routing
 
 
-# (switches: ops.config -- winograd, wgrad_bias (43.4 vs 43.2 ms per finetune step with the bias gradient inside the direct
-#  weight-gradient kernel: the saved pass is paid back inside the MFMA stream, so the separate pass stays the default),
-#  train_ll_wino, wgrad_wino_bias)
+# Which kernel runs what is decided in tmdiff_amd.routing (train_conv_plan, train_ll_plan: one look-up per convolution per
+# step, in the forward); this module executes the plans.  (Measured: 43.4 vs 43.2 ms per finetune step with the bias
+# gradient inside the direct weight-gradient kernel -- the saved pass is paid back inside the MFMA stream, so the separate
+# pass stays the default, config.wgrad_bias.)
 
 
 class DropSpec(tuple):
@@ -45,9 +45,18 @@ def _rows(t, what):
     return {"in_" + what: t.data_ptr(), what + "_stride": t.stride(0)}
 
 
+def conv_plan(segs, wshape, groups, prologue, mask, need_w):
+    """routing.train_conv_plan of a convolution of `segs` (tensors, or stand-ins with a .shape) by a weight of shape wshape;
+    prologue: SiLU / shift / scale on the input; mask: None, a mask tensor or a DropSpec."""
+    b, _, n, h, w = segs[0].shape
+    drop = isinstance(mask, DropSpec)
+    return routing.train_conv_plan(b, tuple(s.shape[1] for s in segs), wshape[0], n, h, w, groups, wshape[2], bool(prologue),
+                                   mask is not None and not drop, drop, bool(need_w))
+
+
 def _conv_forward(meta, weight, bias, shift, scale, residual, mask, segs, need_w):
     """y = (conv3d(act(cat(segs) + shift) * scale * mask, w) + bias_scale*bias + residual) * out_scale, and what its backward needs:
-    (y, state) with state = dict(meta, drop, w, shift, scale, mask, xp, segs, wp_dgrad, has_bias, has_res)."""
+    (y, state) with state = dict(meta, plan, drop, w, shift, scale, mask, xp, segs, wp_dgrad, has_bias, has_res)."""
     act, groups, bias_scale, out_scale = meta
     segs = [s.contiguous() for s in segs]
     w = weight.contiguous()
@@ -57,25 +66,22 @@ def _conv_forward(meta, weight, bias, shift, scale, residual, mask, segs, need_w
     # mask: None, a tensor (caller-supplied dropout mask, parity runs) or a DropSpec (seed, p): in-kernel dropout
     drop = mask if isinstance(mask, DropSpec) else None
     mask = None if drop is not None else mask
-    # a 3x3x3 convolution with dropout runs as prologue pass + staged kernel anyway: let the pass write x' into a
-    # tensor of its own and keep it -- the weight gradient then needs no prologue pass of its own
-    xp = None
-    if ksize == 3 and (drop is not None or mask is not None) and need_w:
+    plan = conv_plan(segs, w.shape, groups, act or shift is not None or scale is not None, drop or mask, need_w)
+    xp = None       # (plan.keep_xp: the prologue pass writes x' into a tensor of its own, which the weight gradient reads)
+    if plan.keep_xp:
         b, _, n, h, wd = segs[0].shape
-        cin = sum(s.shape[1] for s in segs)
-        if cin % groups == 0 and (cin // groups) % 4 == 0 and (cout // groups) % 32 == 0:   # shapes the staged kernel takes
-            xp = torch.empty(b, cin, n, h, wd, device=segs[0].device, dtype=torch.float32)
+        xp = torch.empty(b, sum(s.shape[1] for s in segs), n, h, wd, device=segs[0].device, dtype=torch.float32)
     kw = dict(bias=bias, bias_scale=bias_scale, in_act=act, in_mask=mask, drop=drop, residual=residual, out_scale=out_scale,
               xp_out=xp, **_rows(shift, "shift"), **_rows(scale, "scale"))
-    # 3x3x3 convolutions (in-kernel dropout included): the family tmdiff_amd.routing picks -- Winograd along the bands where
-    # its grid fills the chip (conv3d_wf's prologue pass writes x' where the weight gradient will read it), else direct
+    # 3x3x3 convolutions (in-kernel dropout included): the family of the plan -- Winograd along the bands where its grid
+    # fills the chip (conv3d_wf's prologue pass writes x' where the weight gradient will read it), else direct
     if ksize == 3:
         weights = ops.ConvWeights(lambda: wp, lambda: _wf_weights(w, groups, 2),
                                   lambda planes: ops.pack_conv_weight_wino(w, groups, planes=planes))
-        y = ops.conv3d_auto(segs, weights, cout, groups=groups, **kw)
+        y = ops.conv3d_auto(segs, weights, cout, groups=groups, family=plan.fwd, **kw)
     else:
         y = ops.conv3d(segs, wp, cout, ksize, groups=groups, **kw)
-    state = dict(meta=meta, drop=drop, w=w, shift=shift, scale=scale, mask=mask, xp=xp, segs=segs,
+    state = dict(meta=meta, plan=plan, drop=drop, w=w, shift=shift, scale=scale, mask=mask, xp=xp, segs=segs,
                  wp_dgrad=pre[1] if pre is not None else None, has_bias=bias is not None, has_res=residual is not None)
     return y, state
 
@@ -99,7 +105,7 @@ def _conv_backward(st, gy, need_w, need_b, need_shift, need_scale, need_res, nee
                               **_rows(shift, "shift"), **_rows(scale, "scale"))
     if need_w:   # x' kept by the forward: a plain single-tensor input, no prologue pass inside the weight gradient
         desc_w = ops.make_conv_desc([xp], 0, cout, ksize, g, groups=groups) if xp is not None else desc
-        if has_bias and need_b and (ops.config.wgrad_bias or (ops.config.wgrad_wino_bias and ops.wgrad_wino_takes(desc_w))):   # the bias gradient rides along in the weight-gradient kernel
+        if has_bias and need_b and st["plan"].bias_in_wgrad:   # the bias gradient rides along in the weight-gradient kernel
             desc_w.bias_scale = bias_scale
             d_w, d_bias = ops.conv3d_wgrad(desc_w, g, tuple(w.shape), want_bias=True)
         else:
@@ -116,7 +122,7 @@ def _conv_backward(st, gy, need_w, need_b, need_shift, need_scale, need_res, nee
         if ksize == 3:     # the data gradient is a 3x3x3 convolution too (a plain input: no pass at all)
             weights = ops.ConvWeights(lambda: wp_t, lambda: _wf_weights(w, groups, 3),
                                       lambda planes: ops.pack_conv_weight_wino(w, groups, mode=1, planes=planes))
-            gp = ops.conv3d_auto([g], weights, cin, groups=groups)                # dL/dx'
+            gp = ops.conv3d_auto([g], weights, cin, groups=groups, family=st["plan"].dgrad)                # dL/dx'
         else:
             gp = ops.conv3d([g], wp_t, cin, ksize, groups=groups)
         plain = not (act or has_shift or has_scale or mask is not None or st["drop"] is not None)
@@ -285,19 +291,17 @@ class _ConvLL(torch.autograd.Function):
     def forward(ctx, ll_scale, weight, bias, x):
         w, x = weight.contiguous(), x.contiguous()
         cout = w.shape[0]
-        d = ops.Conv3dDesc()
         b, cin, n, h, wd = x.shape
-        d.B, d.N, d.H, d.W, d.Cin, d.Cout, d.groups, d.ksize, d.nseg = b, n, h, wd, cin, cout, 1, 3, 1
-        d.seg_c[0], d.seg_x[0], d.in_act = cin, x.data_ptr(), 1
-        xp = ops.conv3d_prologue(d, tuple(x.shape))
-        if ops.config.train_ll_wino and ops.wfll_route(b, cin, cout, n, h, wd):
+        plan = routing.train_ll_plan(b, cin, cout, n, h, wd)
+        xp = ops.conv3d_prologue([x], in_act=True)
+        if plan.fwd == "wfll":
             # with Winograd along the bands on top (conv3d_wf's composed-LL mode): x' once more in space-to-depth form (a copy:
             # the weight gradient keeps reading the plain x'; 28.37 -> 28.19 ms per finetune step)
             xs = xp.view(b, cin, n, h // 2, 2, wd // 2, 2).permute(0, 1, 4, 6, 2, 3, 5).reshape(b, 4 * cin, n, h // 2, wd // 2)
             y = ops.conv3d_wf_ll(xs, ops.pack_conv_weight_wfll(w, ll_scale), cout, ll_scale, bias=bias)
         else:
             y = ops.conv3d_ll(xp, ops.pack_conv_weight_ll(w, ll_scale), cout, ll_scale, bias=bias)
-        ctx.ll_scale = ll_scale
+        ctx.ll_scale, ctx.plan = ll_scale, plan
         ctx.has_bias = bias is not None
         ctx.save_for_backward(w, x, xp)
         return y
@@ -317,8 +321,7 @@ class _ConvLL(torch.autograd.Function):
             wp_t = pre[1] if pre is not None else ops.pack_conv_weight(w, mode=1)
             # dL/dx': a 3x3x3 convolution of the up-sampled gradient -- Winograd along the bands (13.5 multiply-adds per
             # element; the transposed form of the composed strided convolution would take 12)
-            gp = ops.conv3d_auto([g], ops.ConvWeights(lambda: wp_t, (lambda: _wf_weights(w, 1, 3)) if ops.config.winograd else None),
-                                 cin)
+            gp = ops.conv3d_auto([g], ops.ConvWeights(lambda: wp_t, lambda: _wf_weights(w, 1, 3)), cin, family=ctx.plan.dgrad)
             d_x = torch.empty_like(x)
             ops.conv3d_prologue_bwd(ops.make_conv_desc([x], 0, cout, 3, g, in_act=True), gp, [d_x], [False], False, False)
         return None, d_w, d_b, d_x

@@ -633,10 +633,14 @@ def conv3d(segs, w_packed, cout, ksize, out=None, math="fp32", pack_input=None, 
     return _result(y, y2)
 
 
-def conv3d_prologue(desc, shape):
-    """x' = the prologue output of the convolution `desc` describes (shape [B, Cin, N, H, W]), as a tensor of its own."""
-    xp = torch.empty(shape, device=torch.device("cuda", torch.cuda.current_device()), dtype=torch.float32)
-    check(lib.tmdiff_conv3d_prologue_fwd(C.byref(desc), xp.data_ptr(), stream_ptr()), "conv3d_prologue_fwd")
+def conv3d_prologue(segs, **kw):
+    """x' = the prologue output of a convolution of `segs` (kw: make_conv_desc's in_act / in_shift / in_scale / in_mask / drop),
+    [B, Cin, N, H, W], as a tensor of its own."""
+    b, _, n, h, w = segs[0].shape
+    cin = sum(s.shape[1] for s in segs)
+    xp = torch.empty(b, cin, n, h, w, device=segs[0].device, dtype=torch.float32)
+    d = make_conv_desc(segs, 0, cin, 1, xp, **kw)      # (the pass reads the extents, the segments and the prologue fields)
+    check(lib.tmdiff_conv3d_prologue_fwd(C.byref(d), xp.data_ptr(), stream_ptr()), "conv3d_prologue_fwd")
     return xp
 
 
@@ -673,18 +677,20 @@ class ConvWeights:
         self.direct, self.wf, self.wino = direct, wf, wino
 
 
-def conv3d_auto(segs, weights, cout, groups=1, math="fp32", emit=None, keep_y=True, xp_out=None, x_bf16_shape=None, **kw):
+def conv3d_auto(segs, weights, cout, groups=1, math="fp32", emit=None, keep_y=True, xp_out=None, x_bf16_shape=None, family=None,
+                **kw):
     """A 3x3x3 convolution on the kernel family routing.conv3_family picks for its extents (same keyword arguments and
     return convention as conv3d): conv3d_wf, the direct kernels (staged / fused), the bf16 kernel, or -- band counts other
-    than 4 / 8 -- tmdiff_amd.fallback.conv3d_wino."""
+    than 4 / 8 -- tmdiff_amd.fallback.conv3d_wino.  family: that answer, where the caller holds it already (the finetune
+    graph's plans, routing.train_conv_plan)."""
     if math == "bf16" or x_bf16_shape is not None:
         return conv3d(segs, weights.direct(), cout, 3, groups=groups, math=math, emit=emit, keep_y=keep_y,
                       x_bf16_shape=x_bf16_shape, **kw)
     b, _, n, h, w = segs[0].shape
     cin = sum(s_.shape[1] for s_ in segs)
     masked, dropout, plain = kw.get("in_mask") is not None, kw.get("drop") is not None, _plain(segs, kw)
-    fam = routing.conv3_family(b, cin, cout, n, h, w, groups, plain=plain, masked=masked, dropout=dropout,
-                               keep_xp=xp_out is not None)
+    fam = family or routing.conv3_family(b, cin, cout, n, h, w, groups, plain=plain, masked=masked, dropout=dropout,
+                                         keep_xp=xp_out is not None)
     if fam in ("wf", "wf_pair") and weights.wf is not None:
         return conv3d_wf(segs, weights.wf(), cout, emit=emit, keep_y=keep_y, groups=groups, xp_out=xp_out, **kw)
     if fam in ("wino4", "wino2") and weights.wino is not None:
@@ -1259,15 +1265,17 @@ def upsample_poly23(x, ratio=4, out=None, phase=1):
 
 def wgrad_wino_takes(desc):
     """True when conv3d_wgrad runs this weight gradient in the Winograd domain (its g pass then sums the bias gradient on
-    the side for free)."""
-    return bool(config.wgrad_wino and desc.ksize == 3 and lib.tmdiff_conv3d_wgrad_wino_supported(C.byref(desc)))
+    the side for free): routing.wgrad_family's answer for the descriptor's extents, segments and prologue."""
+    pro = bool(desc.in_act or desc.in_shift or desc.in_scale or desc.in_mask or desc.drop_p > 0.0)
+    return routing.wgrad_family(desc.B, tuple(desc.seg_c[:desc.nseg]), desc.Cout, desc.N, desc.H, desc.W, desc.groups, desc.ksize, pro,
+                                **({"x_bf16": 1} if desc.x_bf16 else {})) == "wino"
 
 
 def conv3d_wgrad(desc, g, weight_shape, want_bias=False):
     """dL/dw [Cout, Cin/g, k,k,k] for the convolution described by `desc` (a filled Conv3dDesc) given g = dL/dy; with
     want_bias also dL/dbias = desc.bias_scale * sum_{b,pos} g, accumulated inside the same kernel: returns (dw, dbias)."""
     dw = torch.empty(weight_shape, device=g.device, dtype=torch.float32)
-    if config.wgrad_wino and desc.ksize == 3 and lib.tmdiff_conv3d_wgrad_wino_supported(C.byref(desc)):
+    if wgrad_wino_takes(desc):
         # Winograd F(3,4) along the bands (csrc/wgrad_wino.hip): 13.5 executed multiply-adds per element instead of 27
         _count("conv3d_wgrad_wino", 2.0 * desc.B * desc.Cout * (desc.Cin // desc.groups) * 13.5 * desc.N * desc.H * desc.W)
         nbytes = lib.tmdiff_conv3d_wgrad_wino_workspace_bytes(C.byref(desc))

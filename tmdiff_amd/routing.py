@@ -48,6 +48,22 @@ profiles/fusion_table.txt:
 Each rule also reads its switches (fuse_res_conv, side_xp, emit_ll / emit_dwt, conv2_after_ll, epilogue_fuse, wfll, ll_compose,
 winograd) and declines as soon as a convolution involved runs on the bf16 kernels.
 
+The finetune graph (WavBEST.forward_train + backward) takes its decisions here as well: one plan per differentiable convolution
+(train_conv_plan, train_ll_plan) and per block (train_down_plan, train_resblock_plan), which tmdiff_amd.autograd and the block
+classes' `run` execute; `unet_train_launches` walks forward_train's blocks over the plans and gives the step's launches in the
+keys of ops.COUNTS, `tools/routing_table.py --train` writes profiles/train_routing_table.txt.  The rules:
+  4. forward and data gradient (a plain-input convolution Cout -> Cin): rules 1-3; 1x1x1 convolutions on the bandwidth kernel.
+  5. x' is kept for the weight gradient where dropout (or a mask) forces a prologue pass anyway, the weight wants a gradient
+     and the staged kernel takes the weight shape (staged_weight_ok: rule 3's shape test); a kept x' forces a kernel with a pass.
+  6. weight gradient (wgrad_family): Winograd F(3,4) along the bands where config.wgrad_wino, 3x3x3 and
+     tmdiff_conv3d_wgrad_wino_supported, else direct; the bias gradient rides in it with config.wgrad_bias, or in the
+     Winograd kernel's g pass with config.wgrad_wino_bias, else a channel sum of its own.
+  7. Conv_0 + LL of a main-branch down block is one node where the composed form exists (ll_composable) and ll_fits: on
+     conv3d_wf's composed mode with config.train_ll_wino where wfll_route takes it, else on conv3d_ll; Conv_2 after the LL
+     band with config.conv2_after_ll.
+  8. a ResBlock is one autograd node (config.train_fused_resblock) with its res_conv inside, or, without one, on a
+     one-tensor input; else a node per convolution.
+
 Batch-size note (README): the same sample can take different families at B = 1 and B = 32 (rule 1's grid threshold), hence
 different fp32 summation orders; tests/test_gpu_configs.py bounds the difference at 1e-5.
 """
@@ -69,6 +85,12 @@ def _config():
 def wino_weight_ok(cout, cin, ksize=3, groups=1):
     """Weight shapes the Winograd kernels (conv3d_wf, fallback.conv3d_wino) take."""
     return (ksize == 3 and groups in (1, 3) and cin % groups == 0 and cout % groups == 0 and (cin // groups) % 2 == 0 and
+            (cout // groups) % 32 == 0)
+
+
+def staged_weight_ok(cout, cin, groups=1):
+    """Weight shapes the staged direct kernel (conv3d_dma: operands by LDS-DMA) takes; its prologue pass is what keeps x'."""
+    return (groups in (1, 3) and cin % groups == 0 and cout % groups == 0 and (cin // groups) % 4 == 0 and
             (cout // groups) % 32 == 0)
 
 
@@ -117,8 +139,9 @@ _QUERIES = {}        # (the support queries below are pure functions of the exte
 
 def supported(query, b, cin, cout, n, h, w, groups=1, **fields):
     """The library's support query `query` (e.g. "tmdiff_conv3d_ll_supported") for a 3x3x3 convolution of these extents on one
-    input tensor, with the descriptor fields `fields` set (in_act=1: an input that needs a prologue; rc_x=1, rc_cin=: a folded
-    residual convolution; pointers are placeholders, never dereferenced).  Where the size limits of the 32-bit offsets live.
+    input tensor of cin channels -- or, cin a tuple, on segments of that many channels each --, with the descriptor fields
+    `fields` set (in_act=1: an input that needs a prologue; rc_x=1, rc_cin=: a folded residual convolution; pointers are
+    placeholders, never dereferenced).  Where the size limits of the 32-bit offsets live.
     The answers are cached per process: the library reads the switches they depend on (TMDIFF_WINO_F4 and the like) once
     per process too."""
     key = (query, b, cin, cout, n, h, w, groups, tuple(sorted(fields.items())))
@@ -126,9 +149,11 @@ def supported(query, b, cin, cout, n, h, w, groups=1, **fields):
     if r is None:
         if len(_QUERIES) > 4096:
             _QUERIES.clear()
+        seg_c = cin if isinstance(cin, tuple) else (cin,)
         d = _lib.Conv3dDesc()
-        d.B, d.N, d.H, d.W, d.Cin, d.Cout, d.groups, d.ksize, d.nseg = b, n, h, w, cin, cout, groups, 3, 1
-        d.seg_c[0] = cin
+        d.B, d.N, d.H, d.W, d.Cin, d.Cout, d.groups, d.ksize, d.nseg = b, n, h, w, sum(seg_c), cout, groups, 3, len(seg_c)
+        for i, c in enumerate(seg_c):
+            d.seg_c[i] = c
         for k, v in fields.items():
             setattr(d, k, v)
         r = _QUERIES[key] = bool(getattr(lib, query)(C.byref(d)))
@@ -186,7 +211,7 @@ def direct_family(cin, cout, groups=1, plain=True, masked=False, dropout=False, 
     (finetune) forces it.  Both give the same bits (tests/test_gpu_kernels.py::test_conv3d_staged_equals_fused).
     extents = (b, n, h, w): also check the staged kernel's size limits (tmdiff_conv3d_fwd_staged_supported)."""
     cin_g, cout_g = cin // groups, cout // groups
-    staged_ok = groups in (1, 3) and cin % groups == 0 and cout % groups == 0 and cin_g % 4 == 0 and cout_g % 32 == 0
+    staged_ok = staged_weight_ok(cout, cin, groups)
     if staged_ok and extents is not None:
         b, n, h, w = extents
         staged_ok = supported("tmdiff_conv3d_fwd_staged_supported", b, cin, cout, n, h, w, groups,
@@ -211,13 +236,17 @@ def k1_side_xp(b, seg_c, cout, n, h, w, groups=1):
     return (vec or small) and plane * 16 < (1 << 31) and cin * plane < (1 << 30)
 
 
+def ll_composable(cin, cout, h, w):
+    """Conv_0 + LL of a cin -> cout down block on h x w planes has a composed form at all (switch, weight shape, even planes)."""
+    return bool(_config().ll_compose and ll_weight_ok(cout, cin) and h % 2 == 0 and w % 2 == 0)
+
+
 def ll_family(b, cin, cout, n, h, w, producer_s2d=True):
     """Conv_0 + halved LL band of a main-branch down block on a [b, cin, n, h, w] input: "wfll" (the producer hands over its
     second output in space-to-depth form), "ll" (composed, direct), or None (convolution + LL-only DWT)."""
-    cfg = _config()
-    if not (cfg.ll_compose and cin % 2 == 0 and cout % 64 == 0 and h % 2 == 0 and w % 2 == 0):
+    if not ll_composable(cin, cout, h, w):
         return None
-    if cfg.winograd and producer_s2d and wfll_route(b, cin, cout, n, h, w):
+    if _config().winograd and producer_s2d and wfll_route(b, cin, cout, n, h, w):
         return "wfll"
     return "ll" if ll_fits(b, cin, cout, n, h, w) else None
 
@@ -368,6 +397,82 @@ def down_plan(b, ch, n, h, w, maths, main, pre, s2d, fuse):
     return DownPlan(conv0, bool(cfg.conv2_after_ll and fold_k1(b, ch, ch, ch, n, h // 2, w // 2, 1, _any16(m1, m2), 1)))
 
 
+# ---- the finetune graph: one plan per differentiable convolution and per block -------------------------------------------------
+# What autograd._conv_forward / _conv_backward / _ConvLL and the block classes' `run` execute and unet_train_launches tabulates;
+# functions of extents, channel counts, what the input looks like and ops.config, asked once per convolution per step.
+TrainConvPlan = collections.namedtuple("TrainConvPlan", "fwd keep_xp dgrad wgrad bias_in_wgrad")
+TrainLLPlan = collections.namedtuple("TrainLLPlan", "fwd dgrad wgrad")
+TrainDownPlan = collections.namedtuple("TrainDownPlan", "conv0 conv2_after_ll")
+
+
+def wgrad_family(b, seg_c, cout, n, h, w, groups=1, ksize=3, prologue=False, **fields):
+    """"wino" (Winograd F(3,4) along the bands, csrc/wgrad_wino.hip) or "direct": the kernel of the weight gradient of a
+    convolution of the segments seg_c (a tuple of channel counts) -> cout.  prologue: the kernel applies the forward's prologue to
+    its input itself (no kept x'); fields: further descriptor fields the library's query reads."""
+    if not (_config().wgrad_wino and ksize == 3):
+        return "direct"
+    if prologue:
+        fields["in_act"] = 1
+    return "wino" if supported("tmdiff_conv3d_wgrad_wino_supported", b, tuple(seg_c), cout, n, h, w, groups, **fields) else "direct"
+
+
+@_cached
+def train_conv_plan(b, seg_c, cout, n, h, w, groups=1, ksize=3, prologue=False, masked=False, dropout=False, need_w=True):
+    """One differentiable convolution of the segments seg_c -> cout at [b, ., n, h, w].  prologue: SiLU / shift / scale on the
+    input; masked / dropout: as for conv3_family; need_w: the weight wants a gradient.  fwd: the forward family ("k1": a 1x1x1
+    convolution, the bandwidth kernel); keep_xp: a 3x3x3 convolution with dropout runs as prologue pass + kernel anyway, so the
+    pass writes x' into a tensor of its own and the weight gradient reads that (staged_weight_ok: the direct kernel that has
+    such a pass); dgrad: the family of the data gradient, a plain-input convolution cout -> cin; wgrad: wgrad_family on what
+    the weight gradient reads; bias_in_wgrad: the bias gradient rides in the weight-gradient kernel (config.wgrad_bias: the
+    direct kernel accumulates it; config.wgrad_wino_bias: the Winograd kernel's g pass sums it on the side)."""
+    cfg, cin = _config(), sum(seg_c)
+    pro = bool(prologue or masked or dropout)
+    keep_xp = bool(ksize == 3 and (masked or dropout) and need_w and staged_weight_ok(cout, cin, groups))
+    if ksize == 3:
+        fwd = conv3_family(b, cin, cout, n, h, w, groups, len(seg_c) == 1 and not pro, masked, dropout, keep_xp)
+        dgrad = conv3_family(b, cout, cin, n, h, w, groups)
+    else:
+        fwd = dgrad = "k1"
+    wgrad = wgrad_family(b, (cin,) if keep_xp else seg_c, cout, n, h, w, groups, ksize, pro and not keep_xp)
+    return TrainConvPlan(fwd, keep_xp, dgrad, wgrad, bool(cfg.wgrad_bias or (cfg.wgrad_wino_bias and wgrad == "wino")))
+
+
+@_cached
+def train_ll_plan(b, cin, cout, n, h, w):
+    """Conv_0 + halved LL band as one differentiable node (autograd._ConvLL) on a [b, cin, n, h, w] input.  fwd: "wfll" (x' once
+    more in space-to-depth form for conv3d_wf's composed-LL mode) or "ll"; dgrad / wgrad: the families of the full-resolution
+    data gradient (the node offers no transform-pass weights: a fallback family's shape stays direct) and of the weight
+    gradient on the kept x'."""
+    fwd = "wfll" if _config().train_ll_wino and wfll_route(b, cin, cout, n, h, w) else "ll"
+    dgrad = conv3_family(b, cout, cin, n, h, w)
+    if dgrad in FALLBACK_FAMILIES:
+        dgrad = direct_family(cout, cin, extents=(b, n, h, w))
+    return TrainLLPlan(fwd, dgrad, wgrad_family(b, (cin,), cout, n, h, w))
+
+
+@_cached
+def train_down_plan(b, ch, n, h, w, main):
+    """A down block of ch channels on a [b, ch, n, h, w] input in the finetune graph; main: the high bands are dropped.  conv0:
+    what Conv_0 is -- "wfll" / "ll" (train_ll_plan's node; main branch, composable and within conv3d_ll's size limit whichever
+    of the two runs) or None (a convolution, then a DWT); conv2_after_ll: Conv_2 runs on the LL band of the input."""
+    conv0 = None
+    if main and ll_composable(ch, ch, h, w) and ll_fits(b, ch, ch, n, h, w):
+        conv0 = train_ll_plan(b, ch, ch, n, h, w).fwd
+    return TrainDownPlan(conv0, bool(_config().conv2_after_ll))
+
+
+def train_resblock_plan(seg_c, cout):
+    """Which autograd node(s) a ResBlock of the segments seg_c -> cout is: "rc" (one node, res_conv inside: conv20's input
+    gradients are added to res_conv's), "id" (one node, the input is the residual: one tensor) or "separate" (a node per
+    convolution; config.train_fused_resblock off, or a segmented input without a res_conv)."""
+    if _config().train_fused_resblock:
+        if sum(seg_c) != cout:
+            return "rc"
+        if len(seg_c) == 1:
+            return "id"
+    return "separate"
+
+
 # ---- the network's 3x3x3 convolutions ------------------------------------------------------------------------------------
 Layer = collections.namedtuple("Layer", "name cin cout groups h w plain kind")      # kind: "conv" | "conv0_ll"
 
@@ -484,6 +589,75 @@ def unet_fusions(channels, b, n, h, w, math="fp32", fuse=None):
     return rows
 
 
+# ---- the finetune step's launches --------------------------------------------------------------------------------------------
+TrainRow = collections.namedtuple("TrainRow", "name cin cout groups ksize h w fwd keep_xp dgrad wgrad bias_in_wgrad")
+TrainLaunches = collections.namedtuple("TrainLaunches", "counts convs blocks")
+# counts: {key of ops.COUNTS: launches}; convs: [TrainRow], the plan of every convolution; blocks: [(name, plan)] of every
+# ResBlock (train_resblock_plan) and down block (train_down_plan)
+LAUNCH_KEY = {"wf": "conv3d_wf_fwd", "wf_pair": "conv3d_wf_fwd", "wfll": "conv3d_wfll_fwd", "ll": "conv3d_ll_fwd",
+              "staged": "conv3d_fwd_staged", "fused": "conv3d_fwd", "k1": "conv3d_fwd_k1", "wino4": "conv3d_wino4_fwd",
+              "wino2": "conv3d_wino2_fwd", "wino": "conv3d_wgrad_wino", "direct": "conv3d_wgrad"}
+
+
+def unet_train_launches(channels, b, n, h, w, dropout=False):
+    """TrainLaunches of one WavBEST.forward_train plus its backward on a batch of b tiles with n bands, every parameter wanting
+    a gradient: the block walk of forward_train over the plans the block classes and tmdiff_amd.autograd execute, on extents
+    alone.  dropout: the network is in training mode (in-kernel dropout in front of every ResBlock convolution and every
+    Conv_1).  Each convolution is three counted launches: forward, data gradient, weight gradient.  tests/test_host_logic.py
+    holds the plans a WavBEST asks for, from its own module tree, to these rows; tests/test_gpu_configs.py ops.COUNTS of a
+    step to the counts."""
+    c = list(channels)
+    lv = [(h >> k, w >> k) for k in range(4)]
+    counts, convs, blocks = collections.Counter(), [], []
+
+    def add(name, cin, cout, k, groups, ksize, fwd, keep_xp, dgrad, wgrad, bias):
+        convs.append(TrainRow(name, cin, cout, groups, ksize, *lv[k], fwd, keep_xp, dgrad, wgrad, bias))
+        counts.update(LAUNCH_KEY[f] for f in (fwd, dgrad, wgrad))
+
+    def conv(name, seg_c, cout, k, ksize=3, groups=1, prologue=False, drop=False):
+        p = train_conv_plan(b, tuple(seg_c), cout, n, *lv[k], groups, ksize, prologue, False, bool(drop and dropout), True)
+        add(name, sum(seg_c), cout, k, groups, ksize, *p)
+
+    def resblock(name, seg_c, cout, k):
+        blocks.append((name, train_resblock_plan(tuple(seg_c), cout)))
+        conv(name + ".conv20", seg_c, cout, k, prologue=True, drop=True)
+        if sum(seg_c) != cout:
+            conv(name + ".res_conv", seg_c, cout, k, ksize=1)
+        conv(name + ".conv21", [cout], cout, k, prologue=True, drop=True)
+
+    def down(name, ch, k, main):
+        p = train_down_plan(b, ch, n, *lv[k], main)
+        blocks.append((name, p))
+        if p.conv0:         # (autograd._ConvLL: x' always kept, the bias gradient a pass of its own)
+            add(name + ".Conv_0", ch, ch, k, 1, 3, p.conv0, True, *train_ll_plan(b, ch, ch, n, *lv[k])[1:], False)
+        else:
+            conv(name + ".Conv_0", [ch], ch, k, prologue=True)
+        conv(name + ".Conv_2", [ch], ch, k + 1 if p.conv2_after_ll else k, ksize=1)
+        conv(name + ".Conv_1", [ch], ch, k + 1, prologue=True, drop=True)
+
+    def up(name, k):
+        ch = c[k - 1]
+        conv(name + ".Conv_0", [ch], ch, k, prologue=True)
+        conv(name + ".Conv_2", [ch], ch, k, ksize=1)
+        conv(name + ".convH_0.0", [c[k]] * 3, 3 * ch, k, groups=3)
+        conv(name + ".Conv_1", [ch], ch, k - 1, prologue=True, drop=True)
+
+    for branch in ("_1", ""):
+        conv(("conv1" if branch else "conv2") + ".conv21", [c[0]], c[0], 0, prologue=True)
+        for k in range(3):
+            blk = f"down{k + 1}{branch}"
+            resblock(blk + ".conv20", [c[k]], c[k + 1], k)
+            down(blk + ".down", c[k + 1], k, not branch)
+    resblock("middle1", [c[3]], c[3], 3)
+    for k, upn in ((3, "up1"), (2, "up2"), (1, "up3")):
+        resblock(upn + ".conv20", [c[k]] * 3, c[k - 1], k)
+        up(upn + ".up1", k)
+    resblock("final.conv20", [c[0]] * 3, c[0], 0)
+    for k in (1, 2, 3):
+        resblock(f"final.conv2{k}", [c[0]], c[0], 0)
+    return TrainLaunches(dict(counts), convs, blocks)
+
+
 # BASELINE.json configs (SURVEY 8d) as (label, channels, batch per GPU, bands, plane) -- B in {1, 8, 32}, N in {4, 8}, 64^2 / 256^2
 FULL, WIDE = [32, 64, 128, 256], [64, 128, 256, 512]
 BASELINE_CASES = (
@@ -491,7 +665,7 @@ BASELINE_CASES = (
     ("configs[1] batch 32 (benchmark)", FULL, 32, 8, 64, "fp32"),
     ("configs[2] WV-3 256x256, ch 64-512, fp32", WIDE, 1, 8, 256, "fp32"),
     ("configs[2] WV-3 256x256, ch 64-512, bf16", WIDE, 1, 8, 256, "bf16"),
-    ("configs[3] finetune local batch 8 (forward graph)", FULL, 8, 8, 64, "fp32"),
+    ("configs[3] finetune local batch 8 (the inference graph at that batch)", FULL, 8, 8, 64, "fp32"),
     ("configs[4] GF-2 tiles, batch 32", FULL, 32, 4, 64, "fp32"),
     ("configs[4] WV-3 tiles, batch 32", FULL, 32, 8, 64, "fp32"),
     ("configs[4] GF-2 tiles, batch 8", FULL, 8, 4, 64, "fp32"),
@@ -503,4 +677,15 @@ BASELINE_CASES = (
 OTHER_CASES = (
     ("reference default widths, batch 32", [16, 32, 64, 128], 32, 8, 64, "fp32"),
     ("TINY fixture widths, batch 2", [4, 8, 16, 32], 2, 8, 16, "fp32"),
+)
+# The finetune step itself (unet_train_launches; tools/routing_table.py --train) as (label, channels, batch, bands, plane, switches):
+# configs[3], and the small networks whose step tests/test_gpu_configs.py counts launch by launch
+SMALL = [16, 32, 64, 64]        # (16 channels: the general-shape direct kernel; planes down to 8x8 / 16x16: no fallback family)
+TRAIN_CASES = (
+    ("configs[3] finetune local batch 8", FULL, 8, 8, 64, {}),
+    ("reference default widths, batch 8", [16, 32, 64, 128], 8, 8, 64, {}),
+    ("small network, 8 bands", SMALL, 2, 8, 64, {"wino_min_blocks": 1}),
+    ("small network, 4 bands", SMALL, 2, 4, 128, {"wino_min_blocks": 1}),
+    ("small network, 8 bands, Conv_0 + LL on conv3d_ll", SMALL, 2, 8, 64, {"wino_min_blocks": 1, "train_ll_wino": False}),
+    ("TINY fixture widths, batch 2", [4, 8, 16, 32], 2, 8, 16, {}),
 )

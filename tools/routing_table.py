@@ -10,7 +10,13 @@ families each case reaches and -- last -- which families NO case reaches.  tests
     python tools/routing_table.py --fusions > profiles/fusion_table.txt
 
 What the epilogues of the same forwards additionally do (tmdiff_amd.routing.unet_fusions): one line per ResBlock / wavelet block
-with the fusions it takes, and per case the 1x1x1 launches and prologue passes that remain."""
+with the fusions it takes, and per case the 1x1x1 launches and prologue passes that remain.
+
+    python tools/routing_table.py --train > profiles/train_routing_table.txt
+
+The finetune step itself (tmdiff_amd.routing.unet_train_launches over TRAIN_CASES): per case and per dropout setting the counted
+launches of one forward_train plus backward, then one line per convolution with its forward, data-gradient and weight-gradient
+families, and one per block with its plan."""
 import collections
 import os
 import sys
@@ -64,5 +70,26 @@ def fusions():
             print(f"  {r.block:16s} {r.kind:9s} k1 {r.k1} passes {r.passes}  {' '.join(r.taken) or '-'}")
 
 
+def train():
+    print("# launches of one finetune step, forward_train + backward (tmdiff_amd/routing.py unet_train_launches; switches: defaults of")
+    print("# ops.config plus the ones named per case).  Per convolution: forward family / data-gradient family / weight-gradient")
+    print("# kernel; +xp = the forward keeps x' for the weight gradient, +db = the bias gradient rides in the weight gradient (where")
+    print("# there is a bias).  eval = dropout off (net.eval()), train = in-kernel dropout (net.train()).")
+    for label, ch, b, n, size, switches in routing.TRAIN_CASES:
+        with ops.config.override(**switches):
+            runs = [(mode, routing.unet_train_launches(ch, b, n, size, size, mode == "train")) for mode in ("eval", "train")]
+        print(f"\n== {label}: channels {ch}, B = {b}, {n} bands, {size}x{size}"
+              + "".join(f", {k}={v}" for k, v in sorted(switches.items())))
+        for mode, r in runs:
+            print(f"  {mode:5s} " + ", ".join(f"{k} x{v}" for k, v in sorted(r.counts.items())))
+        for name, plan in runs[0][1].blocks:
+            what = plan if isinstance(plan, str) else f"Conv_0 {plan.conv0 or 'conv'}, Conv_2 {'after' if plan.conv2_after_ll else 'before'} LL"
+            print(f"  {name:24s} {what}")
+        for e, t in zip(runs[0][1].convs, runs[1][1].convs):
+            cell = lambda r: f"{r.fwd}/{r.dgrad}/{r.wgrad}" + ("+xp" if r.keep_xp else "") + ("+db" if r.bias_in_wgrad else "")
+            print((f"  {e.name:24s} {e.cin:4d}->{e.cout:<4d} g{e.groups} k{e.ksize} {n}x{e.h}x{e.w:<4d} {cell(e):24s}"
+                   + ("" if cell(t) == cell(e) else f" train: {cell(t)}")).rstrip())
+
+
 if __name__ == "__main__":
-    fusions() if sys.argv[1:] == ["--fusions"] else main()
+    {"--fusions": fusions, "--train": train}[sys.argv[1]]() if sys.argv[1:] else main()
