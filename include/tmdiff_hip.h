@@ -662,6 +662,20 @@ int tmdiff_upsample_poly23(const float* x, float* y, int32_t planes, int32_t h, 
  *  attn_ctx_queries_per_workgroup (host function): the queries one workgroup of the small-context kernel walks over
  *             (128 per pass of its four waves) when attn_fwd is called with these extents, D == 64, Nk <= 96 and 16-byte
  *             aligned q / out rows; 0 when the extents rule that kernel out.
+ *  attn_fwd_lse : attn_fwd, and LSE[b, h, query] = max + log(sum exp) of the scaled (and masked) scores into lse [B, H, Nq].
+ *             The forward of the differentiable path: the same kernels on the same extents, each instantiated once more with
+ *             the store, so `out` equals attn_fwd's bit for bit.  A sample whose keys are all masked gets LSE = -FLT_MAX.
+ *  attn_bwd : dq, dk, dv of attn_fwd_lse from dout (addressed with out's strides; dq / dk / dv with those of q / k / v), `out`
+ *             and `lse`; any of dq / dk / dv may be NULL (not wanted).  Three launches on `stream`, no atomics (bitwise
+ *             reproducible): Delta = rowsum(dout * out) into `workspace` (attn_bwd_workspace_bytes, never NULL), then one
+ *             kernel that walks the key tiles per 128 queries (dq) and one that walks the query tiles per 128 keys (dk, dv);
+ *             both re-form P = exp(S - LSE).  Masked keys get dk = dv = 0 exactly; a sample whose keys are all masked gets
+ *             dq = dk = 0 and dv = (1 / Nk) * sum over the queries of dout.
+ *             Extents (attn_bwd_supported, a host function: 1 / 0): those of attn_fwd (positive, B * H <= 65535, D even and
+ *             <= 128), and q / out and k / v hold at most 2^31 - 1 elements each (B * H * Nq * D, B * H * Nk * D): row and
+ *             statistics indices are 32-bit, element offsets 64-bit.  Larger extents return TMDIFF_E_UNSUPPORTED without
+ *             launching, and the workspace size is 0 for anything refused.
+ *             (attn_fwd_lse, attn_bwd, attn_bwd_supported and attn_bwd_workspace_bytes were added within version 6.)
  *  gemm_nt  : C[M,N] = A[M,K] W[N,K]^T + bias[N] + residual[M,N]   (nn.Linear on token-major activations)
  *  group_norm (:108-109, eps 1e-6, affine), layer_norm (:279-281), geglu / gelu (:69-76, :84-87).
  * ------------------------------------------------------------------------------------ */
@@ -670,6 +684,16 @@ int tmdiff_attn_fwd(const float* q, const float* k, const float* v, float* out, 
                     const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], float scale,
                     tmdiff_stream_t stream);
 int32_t tmdiff_attn_ctx_queries_per_workgroup(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t D);
+int tmdiff_attn_fwd_lse(const float* q, const float* k, const float* v, float* out, const unsigned char* key_mask,
+                        int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t D, const int64_t q_strides[3],
+                        const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], float scale,
+                        float* lse, tmdiff_stream_t stream);
+int tmdiff_attn_bwd_supported(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t D);
+size_t tmdiff_attn_bwd_workspace_bytes(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t D);
+int tmdiff_attn_bwd(const float* q, const float* k, const float* v, const float* out, const float* dout, const float* lse,
+                    const unsigned char* key_mask, float* dq, float* dk, float* dv, void* workspace, int32_t B, int32_t H,
+                    int32_t Nq, int32_t Nk, int32_t D, const int64_t q_strides[3], const int64_t k_strides[3],
+                    const int64_t v_strides[3], const int64_t o_strides[3], float scale, tmdiff_stream_t stream);
 int tmdiff_gemm_nt(const float* A, const float* Wt, const float* bias, const float* residual, float* C, int64_t M,
                    int32_t N, int32_t K, tmdiff_stream_t stream);
 int tmdiff_group_norm(const float* x, const float* gamma, const float* beta, float* y, int32_t B, int32_t C,

@@ -1,4 +1,12 @@
-"""The attention operators of the reference's core/Attention.py on the HIP kernels (inference forward).
+"""The attention operators of the reference's core/Attention.py on the HIP kernels.
+
+Trainable: ``CrossAttention`` (with ``mask``, ``context=None`` and ``residual``).  With grad mode on and a parameter, ``x``,
+``context`` or ``residual`` requiring grad, its forward takes the differentiable path: the projections through
+``autograd.gemm_nt``, the attention core through ``autograd.AttentionFn`` (tmdiff_attn_fwd_lse / tmdiff_attn_bwd); its output
+equals the inference path's bit for bit.  Inference only, each forward under ``torch.no_grad()``: ``GEGLU``, ``FeedForward``,
+``SpatialSelfAttention``, ``BasicTransformerBlock``, ``SpatialTransformer``, ``AttnBlockpp`` -- they wait for the backward of
+GroupNorm, LayerNorm, GEGLU and the 1x1 convolution.  (``BasicTransformerBlock`` calls its ``CrossAttention`` layers under its
+own ``no_grad``, so they run the inference path there.)
 
 ``core/Attention.py`` is imported by nothing in TMDiff and WavBEST contains no attention layer;
 these classes exist because BASELINE's north star names them.  Module tree and parameter names follow the
@@ -12,7 +20,7 @@ tmdiff_group_norm, tmdiff_layer_norm, tmdiff_geglu.
 import torch
 from torch import nn
 
-from . import ops
+from . import autograd, ops
 
 
 def _conv1x1(conv, x, residual=None):
@@ -92,14 +100,36 @@ class CrossAttention(nn.Module):
         self.to_v = nn.Linear(context_dim, inner, bias=False)
         self.to_out = nn.Sequential(nn.Linear(inner, query_dim), nn.Dropout(dropout))
 
-    @torch.no_grad()
     def forward(self, x, context=None, mask=None, residual=None):
+        """Under ``torch.no_grad()`` (or with nothing that requires grad) the inference path; with grad mode on and a
+        parameter or an input that requires grad the differentiable path, as ``WavBEST.forward`` dispatches."""
+        if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or any(
+                torch.is_tensor(t) and t.requires_grad for t in (x, context, residual))):
+            return self.forward_train(x, context, mask, residual)
+        with torch.no_grad():
+            return self._forward_infer(x, context, mask, residual)
+
+    def _forward_infer(self, x, context, mask, residual):
         ctx = x if context is None else context
         q, k, v = _linear(self.to_q, x), _linear(self.to_k, ctx), _linear(self.to_v, ctx)
         if mask is not None:
             mask = mask.reshape(mask.shape[0], -1)
         o = ops.attention(q, k, v, float(self.scale), heads=self.heads, key_mask=mask)
         return _linear(self.to_out[0], o, residual)
+
+    def forward_train(self, x, context=None, mask=None, residual=None):
+        """The same arithmetic as the inference path, with an autograd graph."""
+        drop = self.to_out[1]
+        if self.training and drop.p > 0:
+            raise NotImplementedError("CrossAttention: dropout (p > 0) has no differentiable path; the reference "
+                                      "configurations all use p = 0")
+        ctx = x if context is None else context
+        lin = lambda m, t, res=None: autograd.gemm_nt(t, m.weight, m.bias, res)
+        q, k, v = lin(self.to_q, x), lin(self.to_k, ctx), lin(self.to_v, ctx)
+        if mask is not None:
+            mask = mask.reshape(mask.shape[0], -1)
+        o = autograd.attention(q, k, v, float(self.scale), heads=self.heads, key_mask=mask)
+        return lin(self.to_out[0], o, residual)
 
 
 class BasicTransformerBlock(nn.Module):

@@ -121,6 +121,11 @@ SIGNATURES = {
     "tmdiff_attn_fwd": (C.c_int, [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_int64 * 3, C.c_int64 * 3, C.c_int64 * 3, C.c_int64 * 3, C.c_float, vp]),
     "tmdiff_attn_ctx_queries_per_workgroup": (C.c_int32, [C.c_int32] * 5),
+    "tmdiff_attn_fwd_lse": (C.c_int, [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int64 * 3, C.c_int64 * 3, C.c_int64 * 3, C.c_int64 * 3, C.c_float, vp, vp]),
+    "tmdiff_attn_bwd_supported": (C.c_int, [C.c_int32] * 5),
+    "tmdiff_attn_bwd_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "tmdiff_attn_bwd": (C.c_int, [vp] * 11 + [C.c_int32] * 5 + [C.c_int64 * 3] * 4 + [C.c_float, vp]),
     "tmdiff_gemm_nt": (C.c_int, [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]),
     "tmdiff_group_norm": (C.c_int, [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, vp]),
     "tmdiff_layer_norm": (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_float, vp]),

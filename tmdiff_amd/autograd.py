@@ -470,3 +470,60 @@ class _SplitCols(torch.autograd.Function):
 
 def split_cols(out, sizes):
     return _SplitCols.apply(out, tuple(int(s) for s in sizes))
+
+
+class AttentionFn(torch.autograd.Function):
+    """softmax(q k^T * scale [key mask]) v, layout 'bnd' (ops.attention): forward through ops.attention_lse (the inference
+    kernels, which also store the softmax statistics), backward through ops.attention_bwd, which re-forms P from them."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale, heads, key_mask):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        out, lse = ops.attention_lse(q, k, v, scale, heads=heads, key_mask=key_mask)
+        ctx.scale, ctx.heads, ctx.key_mask = scale, heads, key_mask
+        ctx.save_for_backward(q, k, v, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        dq, dk, dv = ops.attention_bwd(q, k, v, out, dout.contiguous(), lse, ctx.scale, heads=ctx.heads, key_mask=ctx.key_mask,
+                                       need=tuple(ctx.needs_input_grad[:3]))
+        return dq, dk, dv, None, None, None
+
+
+def attention(q, k, v, scale, heads=1, key_mask=None):
+    return AttentionFn.apply(q, k, v, float(scale), heads, key_mask)
+
+
+class _GemmNT(torch.autograd.Function):
+    """ops.gemm_nt (a [..., K] @ w[N, K]^T + bias + residual) with its gradients: the input and weight gradients are gemm_nt
+    calls on transposed operands (the transposes are torch copies), the bias gradient is ops.channel_sum over the rows."""
+
+    @staticmethod
+    def forward(ctx, a, w, bias, residual):
+        a, w = a.contiguous(), w.contiguous()
+        ctx.save_for_backward(a, w)
+        ctx.has_bias = bias is not None
+        return ops.gemm_nt(a, w, bias, None if residual is None else residual.contiguous())
+
+    @staticmethod
+    def backward(ctx, gy):
+        a, w = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        n, k = w.shape
+        g2 = gy.contiguous().reshape(-1, n)                                   # [M, N]
+        da = dw = db = None
+        if need[0]:
+            da = ops.gemm_nt(g2, w.t().contiguous()).reshape(a.shape)        # [M, N] @ [N, K]
+        if need[1] or (need[2] and ctx.has_bias):
+            gt = g2.t().contiguous()                                         # [N, M]
+            if need[1]:
+                dw = ops.gemm_nt(gt, a.reshape(-1, k).t().contiguous())      # [N, M] @ [M, K]
+            if need[2] and ctx.has_bias:
+                db = ops.channel_sum(gt.reshape(1, n, -1))
+        return da, dw, db, (gy if need[3] else None)
+
+
+def gemm_nt(a, w, bias=None, residual=None):
+    return _GemmNT.apply(a, w, bias, residual)

@@ -32,6 +32,15 @@ struct AttnArgs {
   float scale;
 };
 
+// The forward used under grad mode (tmdiff_attn_fwd_lse) also writes LSE = m + log l per query, which the backward kernels
+// (attention_bwd.hip) re-form P from.  It is a compile-time variant of each kernel, selected by the argument type: the
+// instantiations on AttnArgs, which inference runs, carry neither the pointer nor the store.
+struct AttnLseArgs : AttnArgs {
+  float* lse;   // [B, H, Nq]
+};
+template <class Args>
+constexpr bool kWritesLse = std::is_same_v<Args, AttnLseArgs>;
+
 // Key mask (online-softmax kernels).  A masked key keeps its place in the softmax with the score the reference gives it,
 // masked_fill(-finfo.max) (ref :203-204): next to any kept key it weighs exp(-huge) = 0, and a sample whose keys are ALL masked
 // gets equal weights, i.e. the mean of V over its Nk keys, as the reference and attn_ctx_kernel compute it.  The running max
@@ -46,8 +55,8 @@ __device__ __forceinline__ float softmax_denominator(float m_run, float l_run, i
   return m_run == kMaskFill ? (float)Nk : l_run;
 }
 
-template <int DT>  // DT = ceil(D / 32): 32-row tiles of the transposed output accumulator
-__global__ void __launch_bounds__(256) attn_fwd_kernel(const AttnArgs a) {
+template <int DT, class Args = AttnArgs>  // DT = ceil(D / 32): 32-row tiles of the transposed output accumulator
+__global__ void __launch_bounds__(256) attn_fwd_kernel(const Args a) {
   constexpr int DP = DT * 32;       // padded head dim
   constexpr int KS = DP + 1;        // odd LDS row stride: lanes read one row each without bank conflicts
   __shared__ float qs[128 * KS];    // this workgroup's queries   [128][DP]
@@ -124,6 +133,10 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const AttnArgs a) {
   // out[query, d] = O^T[d, query] / l; transpose through LDS (reuse the query buffer) for coalesced stores
   __syncthreads();
   const float inv = 1.f / softmax_denominator(m_run, l_run, a.Nk);
+  if constexpr (kWritesLse<Args>) {   // both half-waves hold the statistics of query wv*32 + l31: the lower one stores
+    const int qi = q0 + wv * 32 + l31;
+    if (h == 0 && qi < a.Nq) a.lse[(long)bh * a.Nq + qi] = m_run + logf(softmax_denominator(m_run, l_run, a.Nk));
+  }
   float* ot = qs + wv * 32 * KS;
 #pragma unroll
   for (int t = 0; t < DT; ++t)
@@ -149,8 +162,8 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const AttnArgs a) {
 // ---------------------------------------------------------------------------------------------------------
 __device__ __attribute__((unused)) const float kZeroRow[128] = {};
 
-template <int DT>  // D == 32 * DT, DT = 2 or 4
-__global__ void __launch_bounds__(256, 2) attn_fwd_dma_kernel(const AttnArgs a) {
+template <int DT, class Args = AttnArgs>  // D == 32 * DT, DT = 2 or 4
+__global__ void __launch_bounds__(256, 2) attn_fwd_dma_kernel(const Args a) {
   constexpr int D = DT * 32, KS = D + 1, TILE = 32 * KS, RP = D / 64;   // RP = 256-byte pieces per row
   static_assert(DT == 2 || DT == 4, "head dim 64 or 128");
   static_assert(4 * TILE == 128 * KS, "two double-buffered K/V stages alias the 128-row Q / O buffer");
@@ -252,6 +265,10 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_dma_kernel(const AttnArgs a) 
   // out[query, d] = O^T[d, query] / l; transpose through LDS for coalesced stores
   __syncthreads();
   const float inv = 1.f / softmax_denominator(m_run, l_run, a.Nk);
+  if constexpr (kWritesLse<Args>) {   // both half-waves hold the statistics of query wv*32 + l31: the lower one stores
+    const int qi = q0 + wv * 32 + l31;
+    if (h == 0 && qi < a.Nq) a.lse[(long)bh * a.Nq + qi] = m_run + logf(softmax_denominator(m_run, l_run, a.Nk));
+  }
   float* ot = lds + wv * 32 * KS;
 #pragma unroll
   for (int t = 0; t < DT; ++t)
@@ -276,8 +293,8 @@ __global__ void __launch_bounds__(256, 2) attn_fwd_dma_kernel(const AttnArgs a) 
 // in flight while the MFMAs of the current one run.  LDS: K 20.8 KB (odd row stride) + V 20.5 KB + 4 x 8.3 KB staging = 74.5
 // KB at NKR = 80: two workgroups per CU.
 // ---------------------------------------------------------------------------------------------------------
-template <int NKR>   // key rows held in LDS: 80 (Nk <= 80) or 96
-__global__ void __launch_bounds__(256, NKR <= 80 ? 2 : 1) attn_ctx_kernel(const AttnArgs a, const int qpw) {
+template <int NKR, class Args = AttnArgs>   // key rows held in LDS: 80 (Nk <= 80) or 96
+__global__ void __launch_bounds__(256, NKR <= 80 ? 2 : 1) attn_ctx_kernel(const Args a, const int qpw) {
   constexpr int D = 64, KS = D + 1, NT = (NKR + 31) / 32;
   __shared__ float ks[NKR * KS];
   __shared__ __attribute__((aligned(16))) float vs[NKR * D];
@@ -380,6 +397,9 @@ __global__ void __launch_bounds__(256, NKR <= 80 ? 2 : 1) attn_ctx_kernel(const 
     }
     // ---- out[query, d] = O^T[d, query] / l: transpose through the staging tile, coalesced float4 rows out -----------------
     const float inv = 1.f / psum;
+    if constexpr (kWritesLse<Args>) {
+      if (h == 0 && q0 + l31 < a.Nq) a.lse[(long)bh * a.Nq + q0 + l31] = mx + logf(psum);
+    }
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt)
@@ -524,15 +544,19 @@ extern "C" int32_t tmdiff_attn_ctx_queries_per_workgroup(int32_t B, int32_t H, i
   return (long)B * H <= 65535 ? attn_ctx_qpw(B, H, Nq, Nk, D) : 0;
 }
 
-extern "C" int tmdiff_attn_fwd(const float* q, const float* k, const float* v, float* out, const unsigned char* key_mask,
-                               int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t D, const int64_t q_strides[3],
-                               const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],
-                               float scale, tmdiff_stream_t stream) {
+namespace {
+
+// The forward launch behind tmdiff_attn_fwd (Args = AttnArgs) and tmdiff_attn_fwd_lse (AttnLseArgs): one dispatch between the
+// three kernels for both, so that the two entry points run the same arithmetic on the same extents.
+template <class Args>
+int attn_forward(Args& a, const char* what, const float* q, const float* k, const float* v, float* out,
+                 const unsigned char* key_mask, int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t D, const int64_t q_strides[3],
+                 const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3], float scale,
+                 tmdiff_stream_t stream) {
   using namespace tmdiff;
-  TMDIFF_REQUIRE(q && k && v && out && q_strides && k_strides && v_strides && o_strides, "attn_fwd: NULL pointer");
-  TMDIFF_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0 && (long)B * H <= 65535, "attn_fwd: bad extents");
-  TMDIFF_REQUIRE(D >= 2 && D <= 128 && D % 2 == 0, "attn_fwd: head dim %d (even, <= 128)", D);
-  AttnArgs a;
+  TMDIFF_REQUIRE(q && k && v && out && q_strides && k_strides && v_strides && o_strides, "%s: NULL pointer", what);
+  TMDIFF_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0 && (long)B * H <= 65535, "%s: bad extents", what);
+  TMDIFF_REQUIRE(D >= 2 && D <= 128 && D % 2 == 0, "%s: head dim %d (even, <= 128)", what, D);
   a.q = q; a.k = k; a.v = v; a.o = out; a.mask = key_mask;
   a.q_bs = q_strides[0]; a.q_hs = q_strides[1]; a.q_rs = q_strides[2];
   a.k_bs = k_strides[0]; a.k_hs = k_strides[1]; a.k_rs = k_strides[2];
@@ -549,22 +573,44 @@ extern "C" int tmdiff_attn_fwd(const float* q, const float* k, const float* v, f
   if (!no_dma && !no_ctx && qpw > 0 && a.q_rs % 4 == 0 && a.o_rs % 4 == 0 && a.q_bs % 4 == 0 && a.q_hs % 4 == 0 &&
       a.o_bs % 4 == 0 && a.o_hs % 4 == 0 && aligned16(q) && aligned16(out)) {
     dim3 g((Nq + qpw - 1) / qpw, B * H);
-    if (Nk <= 80) attn_ctx_kernel<80><<<g, 256, 0, st>>>(a, qpw);
-    else attn_ctx_kernel<96><<<g, 256, 0, st>>>(a, qpw);
-    return check_launch("attn_fwd");
+    if (Nk <= 80) attn_ctx_kernel<80, Args><<<g, 256, 0, st>>>(a, qpw);
+    else attn_ctx_kernel<96, Args><<<g, 256, 0, st>>>(a, qpw);
+    return check_launch(what);
   }
   if (!no_dma && (D == 64 || D == 128)) {
-    if (D == 64) attn_fwd_dma_kernel<2><<<grid, 256, 0, st>>>(a);
-    else attn_fwd_dma_kernel<4><<<grid, 256, 0, st>>>(a);
-    return check_launch("attn_fwd");
+    if (D == 64) attn_fwd_dma_kernel<2, Args><<<grid, 256, 0, st>>>(a);
+    else attn_fwd_dma_kernel<4, Args><<<grid, 256, 0, st>>>(a);
+    return check_launch(what);
   }
   switch ((D + 31) / 32) {
-    case 1: attn_fwd_kernel<1><<<grid, 256, 0, st>>>(a); break;
-    case 2: attn_fwd_kernel<2><<<grid, 256, 0, st>>>(a); break;
-    case 3: attn_fwd_kernel<3><<<grid, 256, 0, st>>>(a); break;
-    default: attn_fwd_kernel<4><<<grid, 256, 0, st>>>(a); break;
+    case 1: attn_fwd_kernel<1, Args><<<grid, 256, 0, st>>>(a); break;
+    case 2: attn_fwd_kernel<2, Args><<<grid, 256, 0, st>>>(a); break;
+    case 3: attn_fwd_kernel<3, Args><<<grid, 256, 0, st>>>(a); break;
+    default: attn_fwd_kernel<4, Args><<<grid, 256, 0, st>>>(a); break;
   }
-  return check_launch("attn_fwd");
+  return check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int tmdiff_attn_fwd(const float* q, const float* k, const float* v, float* out, const unsigned char* key_mask,
+                               int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t D, const int64_t q_strides[3],
+                               const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],
+                               float scale, tmdiff_stream_t stream) {
+  AttnArgs a;
+  return attn_forward(a, "attn_fwd", q, k, v, out, key_mask, B, H, Nq, Nk, D, q_strides, k_strides, v_strides, o_strides, scale,
+                      stream);
+}
+
+extern "C" int tmdiff_attn_fwd_lse(const float* q, const float* k, const float* v, float* out, const unsigned char* key_mask,
+                                   int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t D, const int64_t q_strides[3],
+                                   const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],
+                                   float scale, float* lse, tmdiff_stream_t stream) {
+  TMDIFF_REQUIRE(lse, "attn_fwd_lse: NULL pointer");
+  AttnLseArgs a;
+  a.lse = lse;
+  return attn_forward(a, "attn_fwd_lse", q, k, v, out, key_mask, B, H, Nq, Nk, D, q_strides, k_strides, v_strides, o_strides,
+                      scale, stream);
 }
 
 extern "C" int tmdiff_gemm_nt(const float* A, const float* Wt, const float* bias, const float* residual, float* Cm,

@@ -1390,6 +1390,46 @@ def attention(q, k, v, scale, heads=1, key_mask=None, layout="bnd"):
     return out
 
 
+def _attn_extents(q, k, heads):
+    b, nq, hd = q.shape
+    nk, d = k.shape[1], hd // heads
+    st = lambda n: (C.c_int64 * 3)(n * hd, d, hd)          # batch, head, row strides in elements
+    return b, nq, nk, d, st(nq), st(nk)
+
+
+def _key_mask(key_mask, device):
+    return None if key_mask is None else key_mask.to(device=device, dtype=torch.uint8).contiguous()
+
+
+def attention_lse(q, k, v, scale, heads=1, key_mask=None):
+    """attention() for the differentiable path: (out, lse), lse [B, heads, Nq] = logsumexp of the scaled (masked) scores.
+    `out` equals attention()'s bit for bit (the same kernels, instantiated once more with the store of lse)."""
+    b, nq, nk, d, sq, sk = _attn_extents(q, k, heads)
+    out = torch.empty_like(q)
+    lse = torch.empty(b, heads, nq, device=q.device, dtype=torch.float32)
+    m = _key_mask(key_mask, q.device)
+    check(lib.tmdiff_attn_fwd_lse(_chk(q, "q"), _chk(k, "k"), _chk(v, "v"), out.data_ptr(),
+                                  m.data_ptr() if m is not None else None, b, heads, nq, nk, d, sq, sk, sk, sq, scale,
+                                  lse.data_ptr(), stream_ptr()), "attn_fwd_lse")
+    return out, lse
+
+
+def attention_bwd(q, k, v, out, dout, lse, scale, heads=1, key_mask=None, need=(True, True, True)):
+    """(dq, dk, dv) of attention_lse from dout; None where `need` is False.  No atomics: bitwise reproducible."""
+    b, nq, nk, d, sq, sk = _attn_extents(q, k, heads)
+    if not lib.tmdiff_attn_bwd_supported(b, heads, nq, nk, d):
+        raise ValueError(f"attention_bwd: extents B={b} H={heads} Nq={nq} Nk={nk} D={d} are not supported")
+    dq = torch.empty_like(q) if need[0] else None
+    dk = torch.empty_like(k) if need[1] else None
+    dv = torch.empty_like(v) if need[2] else None
+    ws = _workspace(q.device, lib.tmdiff_attn_bwd_workspace_bytes(b, heads, nq, nk, d), "attn_bwd")
+    m = _key_mask(key_mask, q.device)
+    check(lib.tmdiff_attn_bwd(_chk(q, "q"), _chk(k, "k"), _chk(v, "v"), _chk(out, "out"), _chk(dout, "dout"), _chk(lse, "lse"),
+                              m.data_ptr() if m is not None else None, _chk(dq, "dq"), _chk(dk, "dk"), _chk(dv, "dv"),
+                              ws.data_ptr(), b, heads, nq, nk, d, sq, sk, sk, sq, scale, stream_ptr()), "attn_bwd")
+    return dq, dk, dv
+
+
 def gemm_nt(a, w, bias=None, residual=None):
     """a [..., K] @ w[N, K]^T + bias + residual -> [..., N]"""
     k = a.shape[-1]
