@@ -322,7 +322,8 @@ int tmdiff_conv3d_prologue_fwd(const tmdiff_conv3d_desc* d, float* xp, tmdiff_st
 
 /* dw [Cout, Cin/groups, k,k,k] (PyTorch layout) = sum_{b,pos} g[b,co,pos] * x'[b,ci,pos+tap]; x' is formed from
  * the segments / shift / scale / mask / act of `d` exactly as in the forward (d->y, residual, bias, w_packed are
- * ignored).  `g` is [B, Cout, N, H, W].  workspace: tmdiff_conv3d_wgrad_workspace_bytes(d) bytes (partial sums). */
+ * ignored).  `g` is [B, Cout, N, H, W].  workspace: tmdiff_conv3d_wgrad_workspace_bytes(d) bytes (partial sums).
+ * Unlike the forward entry points it takes any group count that divides Cin and Cout. */
 size_t tmdiff_conv3d_wgrad_workspace_bytes(const tmdiff_conv3d_desc* d);
 int tmdiff_conv3d_wgrad(const tmdiff_conv3d_desc* d, const float* g, float* dw, void* workspace,
                         tmdiff_stream_t stream);

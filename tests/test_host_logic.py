@@ -540,7 +540,7 @@ _BAD_DESC = {
     "mask_and_drop": dict(in_mask="A", drop_p=0.1), "drop1": dict(drop_p=1.0),
     "no_weights": dict(w_packed=0), "no_output": dict(y=0),
     "unaligned_x": dict(seg_x=["U"]), "unaligned_w": dict(w_packed="U"), "unaligned_y": dict(y="U"),
-    "bad_extents": dict(N=0), "ksize2": dict(ksize=2), "groups2": dict(groups=2), "indivisible": dict(groups=3),
+    "bad_extents": dict(N=0), "ksize2": dict(ksize=2), "groups2": dict(groups=2), "groups0": dict(groups=0), "indivisible": dict(groups=3),
     "B0": dict(B=0), "B0_seg_null": dict(B=0, seg_x=[0]), "B0_drop1": dict(B=0, drop_p=1.0),
 }
 # entry -> {case: (return code, prefix of the message)}: -1 = TMDIFF_E_INVALID, -2 = TMDIFF_E_UNSUPPORTED, 0 = accepted.  Cases
@@ -578,8 +578,9 @@ _VALIDATION = {
                                                    "unaligned_w"), _SHAPE + ("B0_drop1",), ("B0", "B0_seg_null")),
     "conv3d_prologue_fwd": _expect("conv3d_prologue_fwd", ("null", "nseg0", "nseg4", "seg_null", "seg_empty", "csum", "bad_extents",
                                                            "B0_seg_null"), ok=("B0", "B0_drop1")),
+    # (the direct weight gradient takes any group count that divides the channels: groups = 2 goes through to its launch)
     "conv3d_wgrad": _expect("conv3d_wgrad", ("null", "nseg0", "nseg4", "seg_null", "seg_empty", "csum", "mask_and_drop",
-                                             "bad_extents", "ksize2", "groups2", "indivisible", "B0")),
+                                             "bad_extents", "ksize2", "groups0", "indivisible", "B0")),
     "conv3d_wgrad_wino": _expect("conv3d_wgrad_wino", ("null", "seg_null", "seg_empty", "csum", "mask_and_drop", "unaligned_x"),
                                  ("nseg0", "nseg4", "bad_extents", "ksize2", "groups2", "indivisible", "B0")),
     "prologue_bwd": _expect("prologue_bwd", ("null", "nseg0", "nseg4", "seg_null", "csum", "mask_and_drop", "B0")),

@@ -762,7 +762,14 @@ extern "C" int tmdiff_conv3d_wgrad_bias(const tmdiff_conv3d_desc* d, const float
   using namespace tmdiff;
   const char* what = "conv3d_wgrad";
   TMDIFF_REQUIRE(d && g && dw, "conv3d_wgrad: NULL pointer");
-  if (const int rc = check_head(d, what)) return rc;
+  // Any group count: the (co, ci) tiles are cut per group and x' is one dense tensor, so nothing here depends on the forward
+  // kernels' "groups 1 or 3" (this is the kernel every shape the Winograd weight gradient declines falls to).
+  TMDIFF_REQUIRE(d->groups >= 1, "%s: groups=%d", what, d->groups);
+  TMDIFF_REQUIRE(d->Cin > 0 && d->Cout > 0 && d->Cin % d->groups == 0 && d->Cout % d->groups == 0, "%s: Cin=%d Cout=%d groups=%d",
+                 what, d->Cin, d->Cout, d->groups);
+  tmdiff_conv3d_desc head = *d;
+  head.groups = 1;   // (the remaining checks of check_head: extents, ksize, nseg)
+  if (const int rc = check_head(&head, what)) return rc;
   TMDIFF_REQUIRE(d->B > 0, "conv3d_wgrad: empty batch");
   if (const int rc = check_segments(d, what)) return rc;
   TMDIFF_REQUIRE(workspace != nullptr, "conv3d_wgrad: NULL workspace");
