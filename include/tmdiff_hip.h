@@ -679,6 +679,26 @@ int tmdiff_upsample_poly23(const float* x, float* y, int32_t planes, int32_t h, 
  *             (attn_fwd_lse, attn_bwd, attn_bwd_supported and attn_bwd_workspace_bytes were added within version 6.)
  *  gemm_nt  : C[M,N] = A[M,K] W[N,K]^T + bias[N] + residual[M,N]   (nn.Linear on token-major activations)
  *  group_norm (:108-109, eps 1e-6, affine), layer_norm (:279-281), geglu / gelu (:69-76, :84-87).
+ *  layer_norm_stats / group_norm_stats : the forwards of the differentiable path -- layer_norm / group_norm, and the statistics
+ *             mean, rstd = 1 / sqrt(var + eps) into mean / rstd ([rows] and [B, groups]).  The same kernels instantiated once
+ *             more with the store, so `y` equals the plain entry point's bit for bit.
+ *  layer_norm_bwd : with g = dy * gamma and xhat = (x - mean) * rstd, dx = rstd * (g - mean_D(g) - xhat * mean_D(g * xhat)),
+ *             dgamma[j] = sum_r dy[r, j] * xhat[r, j], dbeta[j] = sum_r dy[r, j]; any of dx / dgamma / dbeta may be NULL (not
+ *             wanted).  One wave per row; each workgroup writes the column sums of its fixed block of rows into `workspace`
+ *             (layer_norm_bwd_workspace_bytes; may be NULL when neither dgamma nor dbeta is wanted), a second launch adds
+ *             the partials in block order.  No atomics: bitwise reproducible.  Extents (layer_norm_bwd_supported, a host
+ *             function: 1 / 0): 1 <= D <= 4096, rows >= 0 and rows * D < 2^31.  Anything else returns TMDIFF_E_UNSUPPORTED
+ *             without launching, and its workspace size is 0.
+ *  group_norm_bwd : the same for x [B, C, P] normalised per (b, group), gamma / dgamma / dbeta [C] (gamma NULL = 1).  One
+ *             workgroup per (b, group): a first pass forms the per-channel sums of dy and dy * xhat -- the [B, C] partials of
+ *             dbeta / dgamma in `workspace` (group_norm_bwd_workspace_bytes), and, weighted by gamma, the two group sums --
+ *             a second pass writes dx, a tail launch sums the partials over b in order.  Extents (group_norm_bwd_supported):
+ *             those of group_norm (groups divides C, B <= 65535) and B * C * P < 2^31; refusals as for layer_norm_bwd.
+ *  geglu_bwd : u [rows, 2 * inner] = (a | gate), dy [rows, inner] -> du[:, :inner] = dy * gelu(gate), du[:, inner:] =
+ *             dy * a * (Phi(gate) + gate * phi(gate)), the exact erf GELU of the forward; gelu_only = 1: u, dy, du
+ *             [rows, inner], du = dy * (Phi(u) + u * phi(u)).  float4 accesses where inner % 4 == 0 (and 16-byte bases).
+ *             (layer_norm_stats, group_norm_stats, layer_norm_bwd, group_norm_bwd, geglu_bwd and the *_supported /
+ *             *_workspace_bytes functions of the two norms were added within version 6.)
  * ------------------------------------------------------------------------------------ */
 int tmdiff_attn_fwd(const float* q, const float* k, const float* v, float* out, const unsigned char* key_mask,
                     int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t D, const int64_t q_strides[3],
@@ -702,6 +722,21 @@ int tmdiff_group_norm(const float* x, const float* gamma, const float* beta, flo
 int tmdiff_layer_norm(const float* x, const float* gamma, const float* beta, float* y, int64_t rows, int32_t D,
                       float eps, tmdiff_stream_t stream);
 int tmdiff_geglu(const float* u, float* y, int64_t rows, int32_t inner, int32_t gelu_only, tmdiff_stream_t stream);
+int tmdiff_layer_norm_stats(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
+                            int64_t rows, int32_t D, float eps, tmdiff_stream_t stream);
+int tmdiff_group_norm_stats(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
+                            int32_t B, int32_t C, int64_t P, int32_t groups, float eps, tmdiff_stream_t stream);
+int tmdiff_layer_norm_bwd_supported(int64_t rows, int32_t D);
+size_t tmdiff_layer_norm_bwd_workspace_bytes(int64_t rows, int32_t D);
+int tmdiff_layer_norm_bwd(const float* x, const float* gamma, const float* dy, const float* mean, const float* rstd, float* dx,
+                          float* dgamma, float* dbeta, void* workspace, int64_t rows, int32_t D, tmdiff_stream_t stream);
+int tmdiff_group_norm_bwd_supported(int32_t B, int32_t C, int64_t P, int32_t groups);
+size_t tmdiff_group_norm_bwd_workspace_bytes(int32_t B, int32_t C, int64_t P, int32_t groups);
+int tmdiff_group_norm_bwd(const float* x, const float* gamma, const float* dy, const float* mean, const float* rstd, float* dx,
+                          float* dgamma, float* dbeta, void* workspace, int32_t B, int32_t C, int64_t P, int32_t groups,
+                          tmdiff_stream_t stream);
+int tmdiff_geglu_bwd(const float* u, const float* dy, float* du, int64_t rows, int32_t inner, int32_t gelu_only,
+                     tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Per-operator names (SURVEY 8b "minimum exports").  Thin, argument-checked fronts of the entry points above for

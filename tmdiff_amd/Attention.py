@@ -1,12 +1,16 @@
 """The attention operators of the reference's core/Attention.py on the HIP kernels.
 
-Trainable: ``CrossAttention`` (with ``mask``, ``context=None`` and ``residual``).  With grad mode on and a parameter, ``x``,
-``context`` or ``residual`` requiring grad, its forward takes the differentiable path: the projections through
-``autograd.gemm_nt``, the attention core through ``autograd.AttentionFn`` (tmdiff_attn_fwd_lse / tmdiff_attn_bwd); its output
-equals the inference path's bit for bit.  Inference only, each forward under ``torch.no_grad()``: ``GEGLU``, ``FeedForward``,
-``SpatialSelfAttention``, ``BasicTransformerBlock``, ``SpatialTransformer``, ``AttnBlockpp`` -- they wait for the backward of
-GroupNorm, LayerNorm, GEGLU and the 1x1 convolution.  (``BasicTransformerBlock`` calls its ``CrossAttention`` layers under its
-own ``no_grad``, so they run the inference path there.)
+Every module here is trainable: ``CrossAttention`` (with ``mask``, ``context=None`` and ``residual``), ``GEGLU``, ``FeedForward``,
+``SpatialSelfAttention``, ``BasicTransformerBlock``, ``SpatialTransformer`` and ``AttnBlockpp``.  Each ``forward`` dispatches as
+``CrossAttention.forward`` does: under ``torch.no_grad()``, or when neither a parameter nor an input requires grad, the
+inference path; otherwise the differentiable path -- the same kernels in the same order, wrapped in the autograd Functions of
+``autograd`` (``gemm_nt``, ``AttentionFn``: tmdiff_attn_fwd_lse / tmdiff_attn_bwd, ``layer_norm`` / ``group_norm``: the *_stats
+forwards and tmdiff_layer_norm_bwd / tmdiff_group_norm_bwd, ``geglu``: tmdiff_geglu_bwd, ``conv1x1``: the 1x1 convolution's
+data and weight gradients), with differentiable torch views / copies for the reshapes and transposes between them.  Its output
+equals the inference path's bit for bit.  ``BasicTransformerBlock`` hands its inputs to its ``CrossAttention`` layers, which
+dispatch themselves.  Dropout inside the blocks has no differentiable path: ``nn.Dropout`` with ``p > 0`` in training mode raises
+``NotImplementedError`` (the reference configurations all use ``p = 0``); the reference's ``checkpoint=True`` is ignored (no
+recomputation).
 
 ``core/Attention.py`` is imported by nothing in TMDiff and WavBEST contains no attention layer;
 these classes exist because BASELINE's north star names them.  Module tree and parameter names follow the
@@ -39,6 +43,33 @@ def _linear(lin, x, residual=None):
                        residual)
 
 
+def _wants_grad(module, *tensors):
+    """The dispatch of every forward here: grad mode on, and a parameter of `module` or one of `tensors` requires grad."""
+    return torch.is_grad_enabled() and (any(p.requires_grad for p in module.parameters()) or any(
+        torch.is_tensor(t) and t.requires_grad for t in tensors))
+
+
+def _refuse_dropout(module):
+    """The differentiable paths have no dropout: refused before anything is launched."""
+    if module.training and any(isinstance(m, nn.Dropout) and m.p > 0 for m in module.modules()):
+        raise NotImplementedError(f"{type(module).__name__}: dropout (p > 0) has no differentiable path; the reference "
+                                  "configurations all use p = 0")
+
+
+def _lin(m, t, residual=None):
+    """nn.Linear on the differentiable path (the kernel of _linear)."""
+    return autograd.gemm_nt(t, m.weight, m.bias, residual)
+
+
+def _conv(m, t, residual=None):
+    """nn.Conv2d(kernel 1) on the differentiable path (the kernel of _conv1x1)."""
+    return autograd.conv1x1(t, m.weight, m.bias, residual)
+
+
+def _gn(m, t):
+    return autograd.group_norm(t, m.weight, m.bias, m.num_groups, m.eps)
+
+
 def Normalize(in_channels):
     return nn.GroupNorm(num_groups=32, num_channels=in_channels, eps=1e-6, affine=True)
 
@@ -48,9 +79,11 @@ class GEGLU(nn.Module):
         super().__init__()
         self.proj = nn.Linear(dim_in, dim_out * 2)
 
-    @torch.no_grad()
     def forward(self, x):
-        return ops.geglu(_linear(self.proj, x))
+        if _wants_grad(self, x):
+            return autograd.geglu(_lin(self.proj, x))
+        with torch.no_grad():
+            return ops.geglu(_linear(self.proj, x))
 
 
 class FeedForward(nn.Module):
@@ -60,11 +93,15 @@ class FeedForward(nn.Module):
         first = GEGLU(dim, inner) if glu else nn.Sequential(nn.Linear(dim, inner), nn.GELU())
         self.net = nn.Sequential(first, nn.Dropout(dropout), nn.Linear(inner, dim_out or dim))
 
-    @torch.no_grad()
     def forward(self, x, residual=None):
         first = self.net[0]
-        h = first(x) if isinstance(first, GEGLU) else ops.geglu(_linear(first[0], x), gelu_only=True)
-        return _linear(self.net[2], h, residual)
+        if _wants_grad(self, x, residual):
+            _refuse_dropout(self)
+            h = first(x) if isinstance(first, GEGLU) else autograd.geglu(_lin(first[0], x), gelu_only=True)
+            return _lin(self.net[2], h, residual)
+        with torch.no_grad():
+            h = first(x) if isinstance(first, GEGLU) else ops.geglu(_linear(first[0], x), gelu_only=True)
+            return _linear(self.net[2], h, residual)
 
 
 class SpatialSelfAttention(nn.Module):
@@ -77,8 +114,13 @@ class SpatialSelfAttention(nn.Module):
         self.v = nn.Conv2d(in_channels, in_channels, 1)
         self.proj_out = nn.Conv2d(in_channels, in_channels, 1)
 
-    @torch.no_grad()
     def forward(self, x):
+        if _wants_grad(self, x):
+            return self.forward_train(x)
+        with torch.no_grad():
+            return self._forward_infer(x)
+
+    def _forward_infer(self, x):
         b, c, h, w = x.shape
         x = x.contiguous()
         y = ops.group_norm(x, self.norm.weight.detach(), self.norm.bias.detach(), 32, self.norm.eps)
@@ -87,6 +129,17 @@ class SpatialSelfAttention(nn.Module):
         o = ops.attention(q, k, v, float(int(c) ** -0.5), heads=1)                  # [B, HW, C]
         o = o.transpose(1, 2).reshape(b, c, h, w).contiguous()
         return _conv1x1(self.proj_out, o, residual=x)
+
+    def forward_train(self, x):
+        """The same arithmetic as the inference path, with an autograd graph."""
+        b, c, h, w = x.shape
+        x = x.contiguous()
+        y = _gn(self.norm, x)
+        tok = lambda t: t.reshape(b, c, h * w).transpose(1, 2).contiguous()
+        q, k, v = tok(_conv(self.q, y)), tok(_conv(self.k, y)), tok(_conv(self.v, y))
+        o = autograd.attention(q, k, v, float(int(c) ** -0.5), heads=1)
+        o = o.transpose(1, 2).reshape(b, c, h, w).contiguous()
+        return _conv(self.proj_out, o, residual=x)
 
 
 class CrossAttention(nn.Module):
@@ -103,8 +156,7 @@ class CrossAttention(nn.Module):
     def forward(self, x, context=None, mask=None, residual=None):
         """Under ``torch.no_grad()`` (or with nothing that requires grad) the inference path; with grad mode on and a
         parameter or an input that requires grad the differentiable path, as ``WavBEST.forward`` dispatches."""
-        if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or any(
-                torch.is_tensor(t) and t.requires_grad for t in (x, context, residual))):
+        if _wants_grad(self, x, context, residual):
             return self.forward_train(x, context, mask, residual)
         with torch.no_grad():
             return self._forward_infer(x, context, mask, residual)
@@ -142,9 +194,16 @@ class BasicTransformerBlock(nn.Module):
         self.attn2 = CrossAttention(dim, context_dim, n_heads, d_head, dropout)
         self.norm1, self.norm2, self.norm3 = nn.LayerNorm(dim), nn.LayerNorm(dim), nn.LayerNorm(dim)
 
-    @torch.no_grad()
     def forward(self, x, context=None):
-        ln = lambda m, t: ops.layer_norm(t, m.weight.detach(), m.bias.detach(), m.eps)
+        if _wants_grad(self, x, context):
+            _refuse_dropout(self)
+            ln = lambda m, t: autograd.layer_norm(t, m.weight, m.bias, m.eps)
+            return self._blocks(ln, x, context)
+        with torch.no_grad():
+            return self._blocks(lambda m, t: ops.layer_norm(t, m.weight.detach(), m.bias.detach(), m.eps), x, context)
+
+    def _blocks(self, ln, x, context):
+        """Both paths: the attention and feed-forward layers dispatch on grad mode themselves."""
         x = x.contiguous()
         x = self.attn1(ln(self.norm1, x), context=context if self.disable_self_attn else None, residual=x)
         x = self.attn2(ln(self.norm2, x), context=context, residual=x)
@@ -168,9 +227,34 @@ class SpatialTransformer(nn.Module):
         for p in self.proj_out.parameters():        # zero_module (:99-105)
             p.detach().zero_()
 
-    @torch.no_grad()
     def forward(self, x, context=None):
         ctx = context if isinstance(context, list) else [context]
+        if _wants_grad(self, x, *ctx):
+            return self.forward_train(x, ctx)
+        with torch.no_grad():
+            return self._forward_infer(x, ctx)
+
+    def forward_train(self, x, ctx):
+        """The same arithmetic as the inference path, with an autograd graph."""
+        _refuse_dropout(self)
+        b, c, h, w = x.shape
+        x = x.contiguous()
+        y = _gn(self.norm, x)
+        if not self.use_linear:
+            y = _conv(self.proj_in, y)
+        y = y.reshape(b, y.shape[1], h * w).transpose(1, 2).contiguous()
+        if self.use_linear:
+            y = _lin(self.proj_in, y)
+        for i, blk in enumerate(self.transformer_blocks):
+            y = blk(y, context=ctx[i])
+        if self.use_linear:
+            y = _lin(self.proj_out, y)
+        y = y.transpose(1, 2).reshape(b, -1, h, w).contiguous()
+        if not self.use_linear:
+            return _conv(self.proj_out, y, residual=x)
+        return autograd.add(y, x)
+
+    def _forward_infer(self, x, ctx):
         b, c, h, w = x.shape
         x = x.contiguous()
         y = ops.group_norm(x, self.norm.weight.detach(), self.norm.bias.detach(), 32, self.norm.eps)
@@ -214,8 +298,29 @@ class AttnBlockpp(nn.Module):
         self.NIN_3 = NIN(channels, channels, init_scale=init_scale)
         self.skip_rescale = skip_rescale
 
-    @torch.no_grad()
     def forward(self, x):
+        if _wants_grad(self, x):
+            return self.forward_train(x)
+        with torch.no_grad():
+            return self._forward_infer(x)
+
+    def forward_train(self, x):
+        """The same arithmetic as the inference path, with an autograd graph (the NIN weights through gemm_nt on W.t())."""
+        b, c, n, h, w = x.shape
+        cf = c * n
+        xf = x.contiguous().reshape(b, cf, h, w)
+        t = _gn(self.GroupNorm_0, xf)
+        tok = t.reshape(b, cf, h * w).transpose(1, 2).contiguous()
+        nin = lambda m, a, res=None: autograd.gemm_nt(a, m.W.t(), m.b, res)
+        q, k, v = nin(self.NIN_0, tok), nin(self.NIN_1, tok), nin(self.NIN_2, tok)
+        o = autograd.attention(q, k, v, float(int(c) ** -0.5), heads=1)
+        x_tok = xf.reshape(b, cf, h * w).transpose(1, 2).contiguous()
+        y = nin(self.NIN_3, o, x_tok)
+        if self.skip_rescale:
+            y = autograd.scale(y, 2.0 ** -0.5)
+        return y.transpose(1, 2).reshape(b, c, n, h, w).contiguous()
+
+    def _forward_infer(self, x):
         b, c, n, h, w = x.shape
         cf = c * n
         xf = x.contiguous().reshape(b, cf, h, w)

@@ -130,6 +130,15 @@ SIGNATURES = {
     "tmdiff_group_norm": (C.c_int, [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, vp]),
     "tmdiff_layer_norm": (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_float, vp]),
     "tmdiff_geglu": (C.c_int, [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]),
+    "tmdiff_layer_norm_stats": (C.c_int, [vp] * 6 + [C.c_int64, C.c_int32, C.c_float, vp]),
+    "tmdiff_group_norm_stats": (C.c_int, [vp] * 6 + [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, vp]),
+    "tmdiff_layer_norm_bwd_supported": (C.c_int, [C.c_int64, C.c_int32]),
+    "tmdiff_layer_norm_bwd_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "tmdiff_layer_norm_bwd": (C.c_int, [vp] * 9 + [C.c_int64, C.c_int32, vp]),
+    "tmdiff_group_norm_bwd_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "tmdiff_group_norm_bwd_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "tmdiff_group_norm_bwd": (C.c_int, [vp] * 9 + [C.c_int32, C.c_int32, C.c_int64, C.c_int32, vp]),
+    "tmdiff_geglu_bwd": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]),
     "tmdiff_q_sample": (C.c_int, [vp, vp, vp, vp, C.c_int32, C.c_int64, vp]),
     # per-operator names (thin fronts of the entry points above)
     "tmdiff_conv3d_k3_fwd": (C.c_int, [C.POINTER(Conv3dDesc), vp]),

@@ -527,3 +527,112 @@ class _GemmNT(torch.autograd.Function):
 
 def gemm_nt(a, w, bias=None, residual=None):
     return _GemmNT.apply(a, w, bias, residual)
+
+
+class _LayerNorm(torch.autograd.Function):
+    """ops.layer_norm over the last dim: forward through ops.layer_norm_stats (the inference kernel, which also stores mean and
+    rstd per row), backward through ops.layer_norm_bwd."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        x = x.contiguous()
+        y, mean, rstd = ops.layer_norm_stats(x, gamma, beta, eps)
+        ctx.save_for_backward(x, gamma, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, gamma, mean, rstd = ctx.saved_tensors
+        dx, dgamma, dbeta = ops.layer_norm_bwd(x, gamma, gy.contiguous(), mean, rstd, need=tuple(ctx.needs_input_grad[:3]))
+        return dx, dgamma, dbeta, None
+
+
+def layer_norm(x, gamma, beta, eps=1e-5):
+    return _LayerNorm.apply(x, gamma, beta, float(eps))
+
+
+class _GroupNorm(torch.autograd.Function):
+    """ops.group_norm of [B, C, ...]: forward through ops.group_norm_stats, backward through ops.group_norm_bwd."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, groups, eps):
+        x = x.contiguous()
+        y, mean, rstd = ops.group_norm_stats(x, gamma, beta, groups, eps)
+        ctx.groups = groups
+        ctx.save_for_backward(x, gamma, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, gamma, mean, rstd = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dgamma, dbeta = ops.group_norm_bwd(x, gamma, gy.contiguous(), mean, rstd, ctx.groups, need=tuple(need[:3]))
+        return dx, dgamma, dbeta, None, None
+
+
+def group_norm(x, gamma, beta, groups=32, eps=1e-6):
+    return _GroupNorm.apply(x, gamma, beta, int(groups), float(eps))
+
+
+class _Geglu(torch.autograd.Function):
+    """ops.geglu (u = (a | gate) -> a * gelu(gate); gelu_only: gelu(u)) with ops.geglu_bwd as its backward."""
+
+    @staticmethod
+    def forward(ctx, u, gelu_only):
+        u = u.contiguous()
+        ctx.gelu_only = gelu_only
+        ctx.save_for_backward(u)
+        return ops.geglu(u, gelu_only=gelu_only)
+
+    @staticmethod
+    def backward(ctx, gy):
+        u, = ctx.saved_tensors
+        return ops.geglu_bwd(u, gy.contiguous(), gelu_only=ctx.gelu_only), None
+
+
+def geglu(u, gelu_only=False):
+    return _Geglu.apply(u, bool(gelu_only))
+
+
+def conv1x1(x, weight, bias=None, residual=None):
+    """nn.Conv2d(kernel 1) on [B, C, H, W], differentiable: conv3d() with N = 1 -- the same kernel on the same packed weight, bias
+    and residual fused, as the inference path launches it; its backward is tmdiff_conv3d_k1_dgrad / _k1_wgrad's kernels,
+    ops.channel_sum for the bias, and dL/dresidual = gy."""
+    b, c, h, w = x.shape
+    cout = weight.shape[0]
+    res = None if residual is None else residual.reshape(b, cout, 1, h, w)
+    y = conv3d([x.reshape(b, c, 1, h, w)], weight.reshape(cout, c, 1, 1, 1), bias, residual=res)
+    return y.reshape(b, cout, h, w)
+
+
+class _Add(torch.autograd.Function):
+    """ops.add(a, b); both gradients are the incoming one."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        return ops.add(a.contiguous(), b.contiguous())
+
+    @staticmethod
+    def backward(ctx, gy):
+        return gy, gy
+
+
+def add(a, b):
+    return _Add.apply(a, b)
+
+
+class _Scale(torch.autograd.Function):
+    """s * y through ops.axpby, forward and backward."""
+
+    @staticmethod
+    def forward(ctx, y, s):
+        ctx.s = s
+        return ops.axpby([y.contiguous()], [s])
+
+    @staticmethod
+    def backward(ctx, gy):
+        return ops.axpby([gy.contiguous()], [ctx.s]), None
+
+
+def scale(y, s):
+    return _Scale.apply(y, float(s))

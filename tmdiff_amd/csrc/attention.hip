@@ -461,24 +461,14 @@ __global__ void __launch_bounds__(256) gemm_nt_kernel(const float* __restrict__ 
   }
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
-// GroupNorm over [B, C, P]: one workgroup per (b, group); two passes (mean, then centred variance).
+// GroupNorm over [B, C, P]: one workgroup per (b, group); two passes (mean, then centred variance).  STATS: the forward of the
+// differentiable path -- the same kernel instantiated once more with the store of mean / rstd [B, groups] (the instantiation
+// inference runs carries neither the pointers' use nor the store, so y is the same bit for bit).
+template <bool STATS>
 __global__ void __launch_bounds__(256) group_norm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, float* __restrict__ y, int C,
-                                                         long P, int groups, float eps) {
+                                                         long P, int groups, float eps, float* __restrict__ mean_out,
+                                                         float* __restrict__ rstd_out) {
   __shared__ float red[4];
   const int g = blockIdx.x, b = blockIdx.y, cpg = C / groups;
   const long n = (long)cpg * P;
@@ -490,16 +480,21 @@ __global__ void __launch_bounds__(256) group_norm_kernel(const float* __restrict
   float v = 0.f;
   for (long i = threadIdx.x; i < n; i += 256) { const float d = xs[i] - mean; v += d * d; }
   const float rstd = rsqrtf(block_sum(v, red) / (float)n + eps);
+  if constexpr (STATS) {
+    if (threadIdx.x == 0) mean_out[(long)b * groups + g] = mean, rstd_out[(long)b * groups + g] = rstd;
+  }
   for (long i = threadIdx.x; i < n; i += 256) {
     const int c = g * cpg + (int)(i / P);
     ys[i] = (xs[i] - mean) * rstd * (gamma ? gamma[c] : 1.f) + (beta ? beta[c] : 0.f);
   }
 }
 
-// LayerNorm over the last dim of [rows, D]: one wave per row.
+// LayerNorm over the last dim of [rows, D]: one wave per row.  STATS: as for group_norm_kernel, mean / rstd [rows].
+template <bool STATS>
 __global__ void __launch_bounds__(256) layer_norm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, float* __restrict__ y,
-                                                         long rows, int D, float eps) {
+                                                         long rows, int D, float eps, float* __restrict__ mean_out,
+                                                         float* __restrict__ rstd_out) {
   const long row = blockIdx.x * 4L + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
@@ -510,6 +505,9 @@ __global__ void __launch_bounds__(256) layer_norm_kernel(const float* __restrict
   float v = 0.f;
   for (int i = lane; i < D; i += 64) { const float d = xs[i] - mean; v += d * d; }
   const float rstd = rsqrtf(wave_sum(v) / D + eps);
+  if constexpr (STATS) {
+    if (lane == 0) mean_out[row] = mean, rstd_out[row] = rstd;
+  }
   for (int i = lane; i < D; i += 64) y[row * D + i] = (xs[i] - mean) * rstd * gamma[i] + beta[i];
 }
 
@@ -624,23 +622,53 @@ extern "C" int tmdiff_gemm_nt(const float* A, const float* Wt, const float* bias
   return check_launch("gemm_nt");
 }
 
-extern "C" int tmdiff_group_norm(const float* x, const float* gamma, const float* beta, float* y, int32_t B, int32_t C,
-                                 int64_t P, int32_t groups, float eps, tmdiff_stream_t stream) {
+namespace {
+
+// The launches behind tmdiff_group_norm / tmdiff_layer_norm (STATS = false) and their *_stats forms: one argument check and
+// one grid for both, so that the two entry points run the same arithmetic on the same extents.
+template <bool STATS>
+int group_norm_forward(const char* what, const float* x, const float* gamma, const float* beta, float* y, int32_t B, int32_t C,
+                       int64_t P, int32_t groups, float eps, float* mean, float* rstd, tmdiff_stream_t stream) {
   using namespace tmdiff;
   TMDIFF_REQUIRE(x && y && B > 0 && B <= 65535 && C > 0 && P > 0 && groups > 0 && C % groups == 0,
-                 "group_norm: bad arguments (C=%d groups=%d)", C, groups);
-  group_norm_kernel<<<dim3(groups, B), 256, 0, as_stream(stream)>>>(x, gamma, beta, y, C, P, groups, eps);
-  return check_launch("group_norm");
+                 "%s: bad arguments (C=%d groups=%d)", what, C, groups);
+  group_norm_kernel<STATS><<<dim3(groups, B), 256, 0, as_stream(stream)>>>(x, gamma, beta, y, C, P, groups, eps, mean, rstd);
+  return check_launch(what);
+}
+
+template <bool STATS>
+int layer_norm_forward(const char* what, const float* x, const float* gamma, const float* beta, float* y, int64_t rows,
+                       int32_t D, float eps, float* mean, float* rstd, tmdiff_stream_t stream) {
+  using namespace tmdiff;
+  TMDIFF_REQUIRE(rows >= 0 && D > 0, "%s: bad arguments (rows=%ld D=%d)", what, (long)rows, D);
+  if (rows == 0) return TMDIFF_OK;   // (an empty x / y has no storage: NULL is fine)
+  TMDIFF_REQUIRE(x && gamma && beta && y, "%s: NULL pointer", what);
+  layer_norm_kernel<STATS><<<(unsigned)((rows + 3) / 4), 256, 0, as_stream(stream)>>>(x, gamma, beta, y, rows, D, eps, mean, rstd);
+  return check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int tmdiff_group_norm(const float* x, const float* gamma, const float* beta, float* y, int32_t B, int32_t C,
+                                 int64_t P, int32_t groups, float eps, tmdiff_stream_t stream) {
+  return group_norm_forward<false>("group_norm", x, gamma, beta, y, B, C, P, groups, eps, nullptr, nullptr, stream);
+}
+
+extern "C" int tmdiff_group_norm_stats(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
+                                       int32_t B, int32_t C, int64_t P, int32_t groups, float eps, tmdiff_stream_t stream) {
+  TMDIFF_REQUIRE(mean && rstd, "group_norm_stats: NULL pointer");
+  return group_norm_forward<true>("group_norm_stats", x, gamma, beta, y, B, C, P, groups, eps, mean, rstd, stream);
 }
 
 extern "C" int tmdiff_layer_norm(const float* x, const float* gamma, const float* beta, float* y, int64_t rows,
                                  int32_t D, float eps, tmdiff_stream_t stream) {
-  using namespace tmdiff;
-  TMDIFF_REQUIRE(rows >= 0 && D > 0, "layer_norm: bad arguments (rows=%ld D=%d)", (long)rows, D);
-  if (rows == 0) return TMDIFF_OK;   // (an empty x / y has no storage: NULL is fine)
-  TMDIFF_REQUIRE(x && gamma && beta && y, "layer_norm: NULL pointer");
-  layer_norm_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, as_stream(stream)>>>(x, gamma, beta, y, rows, D, eps);
-  return check_launch("layer_norm");
+  return layer_norm_forward<false>("layer_norm", x, gamma, beta, y, rows, D, eps, nullptr, nullptr, stream);
+}
+
+extern "C" int tmdiff_layer_norm_stats(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
+                                       int64_t rows, int32_t D, float eps, tmdiff_stream_t stream) {
+  TMDIFF_REQUIRE(rows == 0 || (mean && rstd), "layer_norm_stats: NULL pointer");
+  return layer_norm_forward<true>("layer_norm_stats", x, gamma, beta, y, rows, D, eps, mean, rstd, stream);
 }
 
 extern "C" int tmdiff_geglu(const float* u, float* y, int64_t rows, int32_t inner, int32_t gelu_only,

@@ -139,6 +139,22 @@ __device__ __forceinline__ float silu_f(float v) {
   return v / (1.0f + __expf(-v));
 }
 
+// Sums over a wave (every lane gets the total; fixed butterfly order) and over a workgroup of 256 threads (red: 4 floats of
+// LDS; the leading barrier lets consecutive calls share it).  The norm kernels and their backward (attention.hip, norm_bwd.hip).
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
 // Dropout keep factor of element `idx` under `seed`: 1/(1-p) with probability 1-p, else 0.  Counter-based (splitmix64
 // finaliser of idx + seed * golden ratio): every kernel that needs the mask recomputes it.  thresh = p * 2^32.
 __device__ __forceinline__ float drop_keep(uint64_t seed, uint64_t idx, uint32_t thresh, float inv_keep) {

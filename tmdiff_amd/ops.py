@@ -1463,3 +1463,71 @@ def geglu(u, gelu_only=False):
     check(lib.tmdiff_geglu(_chk(u, "u"), y.data_ptr(), u.numel() // u.shape[-1], inner, 1 if gelu_only else 0,
                            stream_ptr()), "geglu")
     return y
+
+
+# ---- the differentiable path of the norm / GEGLU operators (csrc/norm_bwd.hip) ---------------------------------
+def layer_norm_stats(x, gamma, beta, eps=1e-5):
+    """layer_norm() for the differentiable path: (y, mean, rstd), the statistics per row.  `y` equals layer_norm()'s bit for
+    bit (the same kernel, instantiated once more with the store of the statistics)."""
+    d = x.shape[-1]
+    rows = x.numel() // d
+    y = torch.empty_like(x)
+    mean = torch.empty(rows, device=x.device, dtype=torch.float32)
+    rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
+    check(lib.tmdiff_layer_norm_stats(_chk(x, "x"), _chk(gamma, "gamma"), _chk(beta, "beta"), y.data_ptr(), mean.data_ptr(),
+                                      rstd.data_ptr(), rows, d, eps, stream_ptr()), "layer_norm_stats")
+    return y, mean, rstd
+
+
+def group_norm_stats(x, gamma, beta, groups=32, eps=1e-6):
+    """group_norm() for the differentiable path: (y, mean, rstd), the statistics [B, groups]; `y` as group_norm()'s."""
+    b, c = x.shape[:2]
+    y = torch.empty_like(x)
+    mean = torch.empty(b, groups, device=x.device, dtype=torch.float32)
+    rstd = torch.empty(b, groups, device=x.device, dtype=torch.float32)
+    check(lib.tmdiff_group_norm_stats(_chk(x, "x"), _chk(gamma, "gamma"), _chk(beta, "beta"), y.data_ptr(), mean.data_ptr(),
+                                      rstd.data_ptr(), b, c, x.numel() // (b * c), groups, eps, stream_ptr()), "group_norm_stats")
+    return y, mean, rstd
+
+
+def layer_norm_bwd(x, gamma, dy, mean, rstd, need=(True, True, True)):
+    """(dx, dgamma, dbeta) of layer_norm_stats from dy; None where `need` is False.  No atomics: bitwise reproducible."""
+    d = x.shape[-1]
+    rows = x.numel() // d
+    if not lib.tmdiff_layer_norm_bwd_supported(rows, d):
+        raise ValueError(f"layer_norm_bwd: extents rows={rows} D={d} are not supported")
+    dx = torch.empty_like(x) if need[0] else None
+    dgamma = torch.empty(d, device=x.device, dtype=torch.float32) if need[1] else None
+    dbeta = torch.empty(d, device=x.device, dtype=torch.float32) if need[2] else None
+    nws = lib.tmdiff_layer_norm_bwd_workspace_bytes(rows, d) if (need[1] or need[2]) else 0
+    ws = _workspace(x.device, nws, "norm_bwd").data_ptr() if nws else None
+    check(lib.tmdiff_layer_norm_bwd(_chk(x, "x"), _chk(gamma, "gamma"), _chk(dy, "dy"), _chk(mean, "mean"), _chk(rstd, "rstd"),
+                                    _chk(dx, "dx"), _chk(dgamma, "dgamma"), _chk(dbeta, "dbeta"), ws, rows, d, stream_ptr()),
+          "layer_norm_bwd")
+    return dx, dgamma, dbeta
+
+
+def group_norm_bwd(x, gamma, dy, mean, rstd, groups=32, need=(True, True, True)):
+    """(dx, dgamma, dbeta) of group_norm_stats from dy (gamma None = 1); None where `need` is False.  No atomics."""
+    b, c = x.shape[:2]
+    p = x.numel() // (b * c) if b * c else 0
+    if not lib.tmdiff_group_norm_bwd_supported(b, c, p, groups):
+        raise ValueError(f"group_norm_bwd: extents B={b} C={c} P={p} groups={groups} are not supported")
+    dx = torch.empty_like(x) if need[0] else None
+    dgamma = torch.empty(c, device=x.device, dtype=torch.float32) if need[1] else None
+    dbeta = torch.empty(c, device=x.device, dtype=torch.float32) if need[2] else None
+    nws = lib.tmdiff_group_norm_bwd_workspace_bytes(b, c, p, groups) if (need[1] or need[2]) else 0
+    ws = _workspace(x.device, nws, "norm_bwd").data_ptr() if nws else None
+    check(lib.tmdiff_group_norm_bwd(_chk(x, "x"), _chk(gamma, "gamma"), _chk(dy, "dy"), _chk(mean, "mean"), _chk(rstd, "rstd"),
+                                    _chk(dx, "dx"), _chk(dgamma, "dgamma"), _chk(dbeta, "dbeta"), ws, b, c, p, groups,
+                                    stream_ptr()), "group_norm_bwd")
+    return dx, dgamma, dbeta
+
+
+def geglu_bwd(u, dy, gelu_only=False):
+    """du of geglu(u, gelu_only) from dy: [..., 2 * inner] (or [..., inner] with gelu_only)."""
+    inner = u.shape[-1] if gelu_only else u.shape[-1] // 2
+    du = torch.empty_like(u)
+    check(lib.tmdiff_geglu_bwd(_chk(u, "u"), _chk(dy, "dy"), du.data_ptr(), u.numel() // u.shape[-1], inner,
+                               1 if gelu_only else 0, stream_ptr()), "geglu_bwd")
+    return du
