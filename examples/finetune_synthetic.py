@@ -13,6 +13,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--local-batch", type=int, default=8)
 ap.add_argument("--channels", type=int, nargs=4, default=[32, 64, 128, 256])
+ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm inside the AdamW step")
 args = ap.parse_args()
 world = tdist.init_from_env()
 rank = int(os.environ.get("RANK", "0"))
@@ -20,6 +21,8 @@ torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
 opt = {"phase": "train", "gpu_ids": [0], "distributed": world > 1, "path": {"resume": None, "checkpoint": "/tmp/tmdiff_ckpt"},
        "model": {"unet": {"channel_multiplier": args.channels}, "diffusion": {"loss_type": "l1"}, "init_type": "orthogonal"},
        "train": {"optimizer": {"lr": 1e-4}, "max_iter": 150000}}
+if args.max_grad_norm is not None:
+    opt["train"]["max_grad_norm"] = args.max_grad_norm
 torch.manual_seed(3407)                     # identical initial weights on every rank
 model = DDPM(opt)
 ema = EmaUpdater(model, copy.deepcopy(model))
@@ -32,4 +35,5 @@ for it in range(args.iters):
     torch.cuda.synchronize()
     if rank == 0:
         log = model.get_current_log()
-        print(f"iter {it}: l_pix {float(log['l_pix']):.4f} lr {log['lr']:.2e} {1e3 * (time.perf_counter() - t0):.1f} ms", flush=True)
+        clip = f" grad_norm {log['grad_norm']:.3f} skipped {log['skipped']:.0f}" if "grad_norm" in log else ""
+        print(f"iter {it}: l_pix {float(log['l_pix']):.4f} lr {log['lr']:.2e}{clip} {1e3 * (time.perf_counter() - t0):.1f} ms", flush=True)

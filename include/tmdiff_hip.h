@@ -540,6 +540,25 @@ typedef struct tmdiff_adamw_entry {
 int tmdiff_multi_adamw(const tmdiff_adamw_entry* tensors_dev, const int32_t* chunk_tensor_dev, const int32_t* chunk_index_dev,
                        int32_t n_chunks, const float* lr_dev, const float* step_dev, float beta1, float beta2, float eps,
                        float weight_decay, tmdiff_stream_t stream);
+/* Global-norm gradient clipping inside that step (torch.nn.utils.clip_grad_norm_, norm_type 2), with no host read and no write
+ * to the gradients.  All three take the tables of tmdiff_multi_adamw and want n_chunks > 0.
+ *  multi_sqnorm_partial: partials_dev[k] = sum of g^2 over chunk k, accumulated in double; one workgroup per chunk, no atomics.
+ *    partials_dev holds tmdiff_multi_sqnorm_workspace_bytes(n_chunks) bytes.  Several parameter groups write at their own
+ *    offsets of one buffer.
+ *  multi_sqnorm_finish (one workgroup, fixed summation order: the same bits on every run and in a graph replay):
+ *    *norm_dev = (float)sqrt(sum of the n_partials partials), *ok_dev = 1 if that is finite, else 0,
+ *    *coef_dev = min(1, max_norm / (*norm_dev + 1e-6f)) in fp32, or 0 where *ok_dev is 0.  max_norm > 0.
+ *  multi_adamw_scaled: tmdiff_multi_adamw on g * *coef_dev (rounded once, kept in registers: g is only read).  With
+ *    *ok_dev == 0 the launch touches nothing: p, m and v keep their bits. */
+size_t tmdiff_multi_sqnorm_workspace_bytes(int32_t n_chunks);
+int tmdiff_multi_sqnorm_partial(const tmdiff_adamw_entry* tensors_dev, const int32_t* chunk_tensor_dev,
+                                const int32_t* chunk_index_dev, int32_t n_chunks, double* partials_dev, tmdiff_stream_t stream);
+int tmdiff_multi_sqnorm_finish(const double* partials_dev, int32_t n_partials, float max_norm, float* norm_dev, float* coef_dev,
+                               float* ok_dev, tmdiff_stream_t stream);
+int tmdiff_multi_adamw_scaled(const tmdiff_adamw_entry* tensors_dev, const int32_t* chunk_tensor_dev,
+                              const int32_t* chunk_index_dev, int32_t n_chunks, const float* lr_dev, const float* step_dev,
+                              float beta1, float beta2, float eps, float weight_decay, const float* coef_dev, const float* ok_dev,
+                              tmdiff_stream_t stream);
 int tmdiff_x0_from_model(const float* x, const float* model_out, float* x0, int64_t n, float alpha, float sigma,
                          int32_t model_is_x_start, tmdiff_stream_t stream);
 size_t tmdiff_abs_quantile_workspace_bytes(int32_t B, int64_t n_per_sample);

@@ -159,26 +159,42 @@ __global__ void __launch_bounds__(256) multi_axpby_kernel(const tmdiff_mt_entry*
 // multi-tensor / elementwise launches for the same update: 3 ms per step of this network against 0.15 ms here).  Operation order
 // as torch's _multi_tensor_adamw: p *= 1 - lr * wd; m = lerp(m, g, 1 - b1); v = b2 v + (1 - b2) g^2;
 // p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps), with bc1 = 1 - b1^t, bc2 = 1 - b2^t evaluated in double as the eager optimizer does.
-__global__ void __launch_bounds__(256) multi_adamw_kernel(const tmdiff_adamw_entry* __restrict__ tensors,
-                                                          const int32_t* __restrict__ chunk_tensor,
-                                                          const int32_t* __restrict__ chunk_index, const float* __restrict__ lr_dev,
-                                                          const float* __restrict__ step_dev, float beta1, float beta2, float eps,
-                                                          float weight_decay) {
-  const tmdiff_adamw_entry e = tensors[chunk_tensor[blockIdx.x]];
-  const long lo = (long)chunk_index[blockIdx.x] * MT_CHUNK;
-  const long hi = min(lo + MT_CHUNK, (long)e.n);
+struct AdamwCoef {
+  float decay, w1, w2, beta2, step_size, bc2_sqrt, eps;
+};
+
+__device__ __forceinline__ AdamwCoef adamw_coef(const float* __restrict__ lr_dev, const float* __restrict__ step_dev, float beta1,
+                                                float beta2, float eps, float weight_decay) {
   const float lr = *lr_dev;
   const double t = (double)*step_dev;
   const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
-  const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
-  const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
-  const float w1 = 1.f - beta1, w2 = 1.f - beta2;
+  return AdamwCoef{(float)(1.0 - (double)lr * (double)weight_decay), 1.f - beta1, 1.f - beta2, beta2, (float)((double)lr / bc1),
+                   (float)sqrt(bc2), eps};
+}
+
+// the update of ONE element (the only copy: the plain and the gradient-scaled kernel both run it)
+__device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v, const AdamwCoef& k) {
+  p = __fmul_rn(p, k.decay);
+  m = __fadd_rn(m, __fmul_rn(k.w1, __fsub_rn(g, m)));
+  v = __fadd_rn(__fmul_rn(v, k.beta2), __fmul_rn(__fmul_rn(k.w2, g), g));
+  const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), k.bc2_sqrt), k.eps);
+  p = __fsub_rn(p, __fmul_rn(k.step_size, __fdiv_rn(m, denom)));
+}
+
+// a * b rounded to fp32 on its own: without the pragma the compiler may contract the product into the subtraction that consumes
+// it (__fmul_rn is a plain product to it), and the scaled step would no longer be the plain step on g * coef bit for bit
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// One chunk of one tensor.  SCALED: the gradient is multiplied by `coef` (one rounding) on its way from memory to the update;
+// the product lives in registers only, the gradient tensor is never written.
+template <bool SCALED>
+__device__ __forceinline__ void adamw_chunk(const tmdiff_adamw_entry& e, long lo, const AdamwCoef& k, float coef) {
+  const long hi = min(lo + MT_CHUNK, (long)e.n);
   auto one = [&](float& p, float g, float& m, float& v) __attribute__((always_inline)) {
-    p = __fmul_rn(p, decay);
-    m = __fadd_rn(m, __fmul_rn(w1, __fsub_rn(g, m)));
-    v = __fadd_rn(__fmul_rn(v, beta2), __fmul_rn(__fmul_rn(w2, g), g));
-    const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), bc2_sqrt), eps);
-    p = __fsub_rn(p, __fmul_rn(step_size, __fdiv_rn(m, denom)));
+    adamw_one(p, SCALED ? mul_rounded(g, coef) : g, m, v, k);
   };
   const bool vec = ((reinterpret_cast<uintptr_t>(e.p) | reinterpret_cast<uintptr_t>(e.g) | reinterpret_cast<uintptr_t>(e.m) |
                      reinterpret_cast<uintptr_t>(e.v)) & 15u) == 0;
@@ -196,6 +212,88 @@ __global__ void __launch_bounds__(256) multi_adamw_kernel(const tmdiff_adamw_ent
     i0 = hi4;
   }
   for (long i = i0 + threadIdx.x; i < hi; i += 256) one(e.p[i], e.g[i], e.m[i], e.v[i]);
+}
+
+__global__ void __launch_bounds__(256) multi_adamw_kernel(const tmdiff_adamw_entry* __restrict__ tensors,
+                                                          const int32_t* __restrict__ chunk_tensor,
+                                                          const int32_t* __restrict__ chunk_index, const float* __restrict__ lr_dev,
+                                                          const float* __restrict__ step_dev, float beta1, float beta2, float eps,
+                                                          float weight_decay) {
+  const tmdiff_adamw_entry e = tensors[chunk_tensor[blockIdx.x]];
+  adamw_chunk<false>(e, (long)chunk_index[blockIdx.x] * MT_CHUNK, adamw_coef(lr_dev, step_dev, beta1, beta2, eps, weight_decay), 1.f);
+}
+
+// The same step on gradients scaled by *coef_dev (global-norm clipping: multi_sqnorm_finish_kernel below wrote it).  *ok_dev == 0
+// (a non-finite norm) skips the step: nothing is read or written, p / m / v keep their bits.
+__global__ void __launch_bounds__(256) multi_adamw_scaled_kernel(const tmdiff_adamw_entry* __restrict__ tensors,
+                                                                 const int32_t* __restrict__ chunk_tensor,
+                                                                 const int32_t* __restrict__ chunk_index,
+                                                                 const float* __restrict__ lr_dev, const float* __restrict__ step_dev,
+                                                                 float beta1, float beta2, float eps, float weight_decay,
+                                                                 const float* __restrict__ coef_dev, const float* __restrict__ ok_dev) {
+  if (*ok_dev == 0.f) return;
+  const tmdiff_adamw_entry e = tensors[chunk_tensor[blockIdx.x]];
+  adamw_chunk<true>(e, (long)chunk_index[blockIdx.x] * MT_CHUNK, adamw_coef(lr_dev, step_dev, beta1, beta2, eps, weight_decay),
+                    *coef_dev);
+}
+
+// Global gradient norm in two stages, both without atomics and with a fixed summation order, so the norm has the same bits
+// from run to run and from an eager launch to a graph replay.
+// Sum over a workgroup of 256 lanes in double: xor-butterfly inside each wave, then the four wave totals in index order.
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// Stage 1: workgroup k sums g^2 over chunk k of the AdamW tables (same entries, same chunks) into partials[k].  Each lane adds
+// the squares of its strided elements in double (the square of a float is exact there), 16 bytes per load where the
+// gradient is 16-byte aligned.
+__global__ void __launch_bounds__(256) multi_sqnorm_partial_kernel(const tmdiff_adamw_entry* __restrict__ tensors,
+                                                                   const int32_t* __restrict__ chunk_tensor,
+                                                                   const int32_t* __restrict__ chunk_index,
+                                                                   double* __restrict__ partials) {
+  __shared__ double red[4];
+  const tmdiff_adamw_entry e = tensors[chunk_tensor[blockIdx.x]];
+  const long lo = (long)chunk_index[blockIdx.x] * MT_CHUNK;
+  const long hi = min(lo + MT_CHUNK, (long)e.n);
+  double acc = 0.0;
+  long i0 = lo;
+  if ((reinterpret_cast<uintptr_t>(e.g) & 15u) == 0) {
+    const long hi4 = lo + ((hi - lo) & ~3L);
+    for (long i = lo + threadIdx.x * 4L; i < hi4; i += 1024) {
+      const float4 g = *reinterpret_cast<const float4*>(e.g + i);
+      acc += (double)g.x * (double)g.x;
+      acc += (double)g.y * (double)g.y;
+      acc += (double)g.z * (double)g.z;
+      acc += (double)g.w * (double)g.w;
+    }
+    i0 = hi4;
+  }
+  for (long i = i0 + threadIdx.x; i < hi; i += 256) acc += (double)e.g[i] * (double)e.g[i];
+  const double total = block_sum_f64(acc, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
+// Stage 2, one workgroup: the partials of every parameter group (the norm is global, as in clip_grad_norm_), strided over the
+// lanes and then the same tree; norm, clip coefficient and the finite flag as three device scalars.
+__global__ void __launch_bounds__(256) multi_sqnorm_finish_kernel(const double* __restrict__ partials, int n_partials, float max_norm,
+                                                                  float* __restrict__ norm_dev, float* __restrict__ coef_dev,
+                                                                  float* __restrict__ ok_dev) {
+  __shared__ double red[4];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n_partials; i += 256) acc += partials[i];
+  const double total = block_sum_f64(acc, red);
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(total);
+    const bool ok = isfinite(norm);
+    const float c = __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f));     // clip_grad_norm_'s coefficient, its 1e-6 included
+    *norm_dev = norm;
+    *coef_dev = ok ? fminf(c, 1.f) : 0.f;
+    *ok_dev = ok ? 1.f : 0.f;
+  }
 }
 
 template <int V>
@@ -511,6 +609,45 @@ extern "C" int tmdiff_multi_adamw(const tmdiff_adamw_entry* tensors_dev, const i
   multi_adamw_kernel<<<(unsigned)n_chunks, 256, 0, as_stream(stream)>>>(tensors_dev, chunk_tensor_dev, chunk_index_dev, lr_dev,
                                                                          step_dev, beta1, beta2, eps, weight_decay);
   return check_launch("multi_adamw");
+}
+
+extern "C" int tmdiff_multi_adamw_scaled(const tmdiff_adamw_entry* tensors_dev, const int32_t* chunk_tensor_dev,
+                                         const int32_t* chunk_index_dev, int32_t n_chunks, const float* lr_dev,
+                                         const float* step_dev, float beta1, float beta2, float eps, float weight_decay,
+                                         const float* coef_dev, const float* ok_dev, tmdiff_stream_t stream) {
+  using namespace tmdiff;
+  TMDIFF_REQUIRE(tensors_dev && chunk_tensor_dev && chunk_index_dev && lr_dev && step_dev && coef_dev && ok_dev && n_chunks > 0,
+                 "multi_adamw_scaled: bad arguments");
+  TMDIFF_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f && weight_decay >= 0.f,
+                 "multi_adamw_scaled: betas (%g, %g) eps %g weight_decay %g", (double)beta1, (double)beta2, (double)eps,
+                 (double)weight_decay);
+  multi_adamw_scaled_kernel<<<(unsigned)n_chunks, 256, 0, as_stream(stream)>>>(
+      tensors_dev, chunk_tensor_dev, chunk_index_dev, lr_dev, step_dev, beta1, beta2, eps, weight_decay, coef_dev, ok_dev);
+  return check_launch("multi_adamw_scaled");
+}
+
+extern "C" size_t tmdiff_multi_sqnorm_workspace_bytes(int32_t n_chunks) {
+  return n_chunks > 0 ? (size_t)n_chunks * sizeof(double) : 0;
+}
+
+extern "C" int tmdiff_multi_sqnorm_partial(const tmdiff_adamw_entry* tensors_dev, const int32_t* chunk_tensor_dev,
+                                           const int32_t* chunk_index_dev, int32_t n_chunks, double* partials_dev,
+                                           tmdiff_stream_t stream) {
+  using namespace tmdiff;
+  TMDIFF_REQUIRE(tensors_dev && chunk_tensor_dev && chunk_index_dev && partials_dev && n_chunks > 0,
+                 "multi_sqnorm_partial: bad arguments");
+  multi_sqnorm_partial_kernel<<<(unsigned)n_chunks, 256, 0, as_stream(stream)>>>(tensors_dev, chunk_tensor_dev, chunk_index_dev,
+                                                                                 partials_dev);
+  return check_launch("multi_sqnorm_partial");
+}
+
+extern "C" int tmdiff_multi_sqnorm_finish(const double* partials_dev, int32_t n_partials, float max_norm, float* norm_dev,
+                                          float* coef_dev, float* ok_dev, tmdiff_stream_t stream) {
+  using namespace tmdiff;
+  TMDIFF_REQUIRE(partials_dev && norm_dev && coef_dev && ok_dev && n_partials > 0, "multi_sqnorm_finish: bad arguments");
+  TMDIFF_REQUIRE(max_norm > 0.f, "multi_sqnorm_finish: max_norm %g (must be > 0)", (double)max_norm);
+  multi_sqnorm_finish_kernel<<<1, 256, 0, as_stream(stream)>>>(partials_dev, n_partials, max_norm, norm_dev, coef_dev, ok_dev);
+  return check_launch("multi_sqnorm_finish");
 }
 
 extern "C" int tmdiff_x0_from_model(const float* x, const float* model_out, float* x0, int64_t n, float alpha,

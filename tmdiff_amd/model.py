@@ -136,6 +136,10 @@ class DDPM(BaseModel):
         self.grad_reduce = train_opt.get("grad_reduce", "sum")
         # train.hip_graph (default: ops.config.train_graph / TMDIFF_TRAIN_GRAPH): record the finetune step into a HIP graph
         self.use_graph = bool(train_opt.get("hip_graph", ops.config.train_graph)) and self.device.type == "cuda"
+        # train.max_grad_norm (optional; absent: no clipping): bound on the global gradient norm, applied after the gradient
+        # all-reduce (every rank clips the same reduced gradients by the same norm)
+        self.max_grad_norm = train_opt.get("max_grad_norm")
+        self._grad_norm = None          # last norm of the torch.optim.AdamW path
         self.split_graph = False
         self._captured, self._eager_steps, self._drop_word = {}, {}, None
         self.reducer = None
@@ -146,11 +150,14 @@ class DDPM(BaseModel):
             lr = opt["train"]["optimizer"]["lr"]
             if self.device.type == "cuda":
                 # torch.optim.AdamW as ONE multi-tensor HIP launch (tmdiff_amd.optim; same state layout and checkpoint
-                # files); the learning rate is a device scalar the scheduler fills, so the step can live in a HIP graph
+                # files); the learning rate is a device scalar the scheduler fills, so the step can live in a HIP graph.
+                # It clips inside its step (device-side norm, no host read: the step stays capturable)
                 from .optim import FusedAdamW
-                self.optG = FusedAdamW(optim_params, lr=torch.tensor(float(lr), device=self.device), weight_decay=1e-4)
+                self.optG = FusedAdamW(optim_params, lr=torch.tensor(float(lr), device=self.device), weight_decay=1e-4,
+                                       max_grad_norm=self.max_grad_norm)
             else:
                 self.optG = torch.optim.AdamW(optim_params, lr=lr, weight_decay=1e-4)
+            self._optim_params = optim_params
             self.scheduler = linear_warmup_decay(self.optG, 100, opt["train"]["max_iter"])
             self.log_dict = OrderedDict()
         self.load_network()
@@ -163,6 +170,13 @@ class DDPM(BaseModel):
         lr = self.optG.param_groups[0]["lr"]
         return lr            # (a device tensor in graph mode: formatting it is the only host read, done by whoever logs)
 
+    def _optimizer_step(self):
+        """optG.step() on the reduced gradients; an optimizer that does not clip inside its step (torch.optim.AdamW) gets
+        clip_grad_norm_ in front of it, so train.max_grad_norm means the same on every path."""
+        if self.max_grad_norm is not None and getattr(self.optG, "max_grad_norm", None) is None:
+            self._grad_norm = torch.nn.utils.clip_grad_norm_(self._optim_params, self.max_grad_norm)
+        self.optG.step()
+
     def optimize_parameters(self, prompt=None):
         if self.reducer is None:       # created here: the process group exists by the first step
             self.reducer = tdist.GradReducer(self.netG, op=self.grad_reduce)
@@ -172,7 +186,7 @@ class DDPM(BaseModel):
         l_pix = self.netG(self.data, prompt).sum()
         l_pix.backward()                # bucket all-reduces start from hooks while backward is still running
         self.reducer.finish()           # no-op in a single process
-        self.optG.step()
+        self._optimizer_step()
         self.scheduler.step()
         self.reducer.zero_grad()
         self.log_dict["l_pix"] = l_pix.detach()
@@ -201,7 +215,7 @@ class DDPM(BaseModel):
                     self.reducer.active = keep
                 if self.split_graph:
                     tdist.allreduce_gradients(self.netG, op=self.grad_reduce)
-                self.optG.step()
+                self._optimizer_step()
                 self.scheduler.step()
                 self.log_dict["l_pix"], self.log_dict["lr"] = l_pix.detach(), self._lr()
                 return
@@ -234,6 +248,13 @@ class DDPM(BaseModel):
             self.netG.set_new_noise_schedule(schedule_opt, self.device)
 
     def get_current_log(self):
+        if self.optG is not None and self.max_grad_norm is not None:
+            # read here, when somebody prints the log, never inside the step
+            norm = self._grad_norm if self._grad_norm is not None else getattr(self.optG, "last_grad_norm", None)
+            ok = getattr(self.optG, "last_step_ok", None)
+            if norm is not None:
+                self.log_dict["grad_norm"] = float(norm)
+                self.log_dict["skipped"] = 0.0 if ok is None else 1.0 - float(ok)
         return self.log_dict
 
     def get_current_visuals(self):

@@ -6,7 +6,12 @@ same constructor arguments, same ``param_groups`` / ``state`` layout (``step``, 
 schedulers drive it unchanged.  Only ``step()`` differs: every parameter that has a gradient is updated by one multi-tensor kernel
 that reads the learning rate and the step count from device scalars -- no host read anywhere, so the step can be recorded into a
 HIP graph (torch's capturable AdamW does the same update in ~25 multi-tensor / elementwise launches: 3 ms per step of WavBEST's
-272 tensors against 0.15 ms).  amsgrad / maximize / fp16 parameters are not supported (the reference uses none of them)."""
+272 tensors against 0.15 ms).  amsgrad / maximize / fp16 parameters are not supported (the reference uses none of them).
+
+``max_grad_norm`` clips the global gradient norm inside that step (``torch.nn.utils.clip_grad_norm_``): one read pass over the
+gradients for the norm (tmdiff_multi_sqnorm_partial / _finish), then an AdamW launch that multiplies each gradient by the clip
+coefficient in registers (tmdiff_multi_adamw_scaled) -- the gradients are never rewritten and nothing is read on the host.  With
+``skip_nonfinite`` a step whose norm is inf / NaN changes nothing at all, the step counters included."""
 import ctypes as C
 import struct
 
@@ -17,11 +22,21 @@ from ._lib import check, lib
 
 
 class FusedAdamW(torch.optim.AdamW):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, **kw):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, skip_nonfinite=True,
+                 **kw):
         for bad in ("amsgrad", "maximize"):
             if kw.get(bad):
                 raise ValueError(f"FusedAdamW: {bad} is not supported")
+        if max_grad_norm is not None and not (float(max_grad_norm) > 0.0):          # (a NaN fails the comparison too)
+            raise ValueError(f"FusedAdamW: max_grad_norm must be positive, got {max_grad_norm}")
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **kw)
+        # constructor arguments, not part of state_dict()
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.last_grad_norm = None   # device scalars of the last clipped step: the norm before clipping, and 1 / 0 for
+        self.last_step_ok = None     # applied / skipped (float(...) them when logging; step() never reads them)
+        self.last_clip_coef = None   # ... and the factor the gradients were multiplied by (0 on a skipped step)
+        self._clip = None            # partial sums, the scalars, group offsets (see _clip_buffers)
         self._tables = {}        # group index -> dict(key, entries, chunk_tensor, chunk_index, n_chunks, pinned host copies)
         self._lr_dev = {}        # group index -> (device scalar, last host value) when the group's lr is a Python float
 
@@ -90,6 +105,25 @@ class FusedAdamW(torch.optim.AdamW):
             cur[1] = float(lr)
         return cur[0]
 
+    def _clip_buffers(self, work):
+        """The partial sums of every group in one buffer (group gi writes n_chunks doubles at its own offset) and the three
+        scalars norm / coef / ok, kept like the tables: alive with the optimizer, hence with a graph that recorded them."""
+        key = tuple((gi, tb["n_chunks"]) for gi, _, _, tb, _ in work)
+        cb = self._clip
+        if cb is not None and cb["key"] == key:
+            return cb
+        dev = work[0][2][0].device
+        offsets, total = {}, 0
+        for gi, n in key:
+            offsets[gi] = total
+            total += n
+        assert lib.tmdiff_multi_sqnorm_workspace_bytes(total) == 8 * total
+        cb = self._clip = {"key": key, "offsets": offsets, "total": total,
+                           "partials": torch.zeros(total, dtype=torch.float64, device=dev),
+                           "scalars": torch.zeros(3, dtype=torch.float32, device=dev),
+                           "one": torch.ones((), dtype=torch.float32, device=dev)}
+        return cb
+
     def state_dict(self):
         """torch's layout, with a step scalar OF ITS OWN per parameter (here they share one device counter; torch.optim.AdamW,
         which a reference-side run may load this checkpoint into, increments every entry and must not find them aliased)."""
@@ -111,6 +145,7 @@ class FusedAdamW(torch.optim.AdamW):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        work = []
         for gi, group in enumerate(self.param_groups):
             params = [p for p in group["params"] if p.grad is not None]
             if not params:
@@ -120,11 +155,41 @@ class FusedAdamW(torch.optim.AdamW):
                         p.grad.dtype == torch.float32 and not p.grad.is_sparse):
                     raise RuntimeError("FusedAdamW: parameters and gradients must be dense contiguous float32 tensors on the GPU")
             step = self._init_state(group, params)
-            step.add_(1.0)
-            tb = self._table(gi, params)
-            b1, b2 = group["betas"]
-            check(lib.tmdiff_multi_adamw(tb["entries"].data_ptr(), tb["chunk_tensor"].data_ptr(), tb["chunk_index"].data_ptr(),
-                                         tb["n_chunks"], self._lr_scalar(gi, group, params[0].device).data_ptr(), step.data_ptr(),
-                                         float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), ops.stream_ptr()),
-                  "multi_adamw")
+            if self.max_grad_norm is None:
+                step.add_(1.0)
+                self._launch(gi, group, params, step, self._table(gi, params))
+            else:
+                work.append((gi, group, params, self._table(gi, params), step))
+        if work:
+            self._clipped_step(work)
         return loss
+
+    def _launch(self, gi, group, params, step, tb, coef=None, ok=None):
+        b1, b2 = group["betas"]
+        args = (tb["entries"].data_ptr(), tb["chunk_tensor"].data_ptr(), tb["chunk_index"].data_ptr(), tb["n_chunks"],
+                self._lr_scalar(gi, group, params[0].device).data_ptr(), step.data_ptr(), float(b1), float(b2), float(group["eps"]),
+                float(group["weight_decay"]))
+        if coef is None:
+            check(lib.tmdiff_multi_adamw(*args, ops.stream_ptr()), "multi_adamw")
+        else:
+            check(lib.tmdiff_multi_adamw_scaled(*args, coef.data_ptr(), ok.data_ptr(), ops.stream_ptr()), "multi_adamw_scaled")
+
+    def _clipped_step(self, work):
+        """Norm over ALL groups (one stage-1 launch per group, one finish), then per group: counter += ok, scaled AdamW."""
+        cb = self._clip_buffers(work)
+        st = ops.stream_ptr()
+        for gi, _, _, tb, _ in work:
+            check(lib.tmdiff_multi_sqnorm_partial(tb["entries"].data_ptr(), tb["chunk_tensor"].data_ptr(), tb["chunk_index"].data_ptr(),
+                                                  tb["n_chunks"], cb["partials"].data_ptr() + 8 * cb["offsets"][gi], st),
+                  "multi_sqnorm_partial")
+        norm, coef, ok = cb["scalars"][0], cb["scalars"][1], cb["scalars"][2]
+        check(lib.tmdiff_multi_sqnorm_finish(cb["partials"].data_ptr(), cb["total"], self.max_grad_norm, norm.data_ptr(),
+                                             coef.data_ptr(), ok.data_ptr(), st), "multi_sqnorm_finish")
+        if not self.skip_nonfinite:
+            # every step is taken, and a NaN norm poisons every parameter as torch's clip_grad_norm_(error_if_nonfinite=False)
+            # does (the kernel's coefficient is 0 there; for an infinite norm 0 is torch's value too)
+            coef, ok = torch.where(torch.isnan(norm), norm, coef), cb["one"]
+        self.last_grad_norm, self.last_clip_coef, self.last_step_ok = norm, coef, ok
+        for gi, group, params, tb, step in work:
+            step.add_(ok)                  # (a skipped step does not advance the bias corrections)
+            self._launch(gi, group, params, step, tb, coef, ok)
