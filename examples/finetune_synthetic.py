@@ -14,6 +14,7 @@ ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--local-batch", type=int, default=8)
 ap.add_argument("--channels", type=int, nargs=4, default=[32, 64, 128, 256])
 ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm inside the AdamW step")
+ap.add_argument("--grad-bf16", action="store_true", help="gradients of the 3x3x3 convolutions from bf16-rounded operands (fp32 sums)")
 args = ap.parse_args()
 world = tdist.init_from_env()
 rank = int(os.environ.get("RANK", "0"))
@@ -23,6 +24,8 @@ opt = {"phase": "train", "gpu_ids": [0], "distributed": world > 1, "path": {"res
        "train": {"optimizer": {"lr": 1e-4}, "max_iter": 150000}}
 if args.max_grad_norm is not None:
     opt["train"]["max_grad_norm"] = args.max_grad_norm
+if args.grad_bf16:
+    opt["train"]["grad_compute"] = "bf16"
 torch.manual_seed(3407)                     # identical initial weights on every rank
 model = DDPM(opt)
 ema = EmaUpdater(model, copy.deepcopy(model))

@@ -294,7 +294,9 @@ int tmdiff_conv3d_wfll_fwd(const tmdiff_conv3d_desc* d, float ll_scale, tmdiff_s
  * (tmdiff_conv3d_packed_bf16_bytes bytes; 0 = shape not supported).
  * Supported: Cin/groups a multiple of 8 (ksize 3) or 16 (ksize 1), every segment a multiple of 8 channels,
  * Cout/groups a multiple of 32, no in_mask; anything else returns TMDIFF_E_UNSUPPORTED and the caller keeps using tmdiff_conv3d_fwd (forward only:
- * training runs in fp32).
+ * the training FORWARD runs in fp32 -- this entry point takes no dropout; the opt-in bf16 gradient arithmetic of the finetune step
+ * runs its data gradients, plain convolutions of g, through it with weights from tmdiff_conv3d_pack_weights_bf16_dgrad;
+ * tmdiff_conv3d_wgrad_bf16 below is the bf16 weight gradient).
  * workspace NULL: one fused kernel (prologue evaluated while staging, per channel tile).  workspace of
  * tmdiff_conv3d_bf16_workspace_bytes(d) bytes: two kernels -- the prologue output is packed to bf16 once
  * ([B][Cin/8][N*H*W] units of 8 channels), then a convolution whose operands go HBM -> LDS directly
@@ -303,6 +305,12 @@ int tmdiff_conv3d_wfll_fwd(const tmdiff_conv3d_desc* d, float ll_scale, tmdiff_s
 size_t tmdiff_conv3d_packed_bf16_bytes(int32_t Cout, int32_t Cin, int32_t ksize, int32_t groups);
 int tmdiff_conv3d_pack_weights_bf16(const float* w, void* packed, int32_t Cout, int32_t Cin, int32_t ksize,
                                     int32_t groups, tmdiff_stream_t stream);
+/* The bf16 counterpart of tmdiff_conv3d_pack_weights(..., mode 1): w = [Cout, Cin/groups, 3,3,3] of the FORWARD convolution ->
+ * the layout above for its data-gradient convolution (Cout -> Cin channels), taps mirrored and the two channel axes swapped per
+ * group, so that tmdiff_conv3d_fwd_bf16(g, packed) == dL/dx' from bf16-rounded g and w.  ksize 3, Cout/groups a multiple of 8;
+ * tmdiff_conv3d_packed_bf16_bytes(Cin, Cout, 3, groups) bytes (the convolution itself also wants Cin/groups % 32 == 0). */
+int tmdiff_conv3d_pack_weights_bf16_dgrad(const float* w, void* packed, int32_t Cout, int32_t Cin, int32_t ksize,
+                                          int32_t groups, tmdiff_stream_t stream);
 size_t tmdiff_conv3d_bf16_workspace_bytes(const tmdiff_conv3d_desc* d);
 int tmdiff_conv3d_fwd_bf16(const tmdiff_conv3d_desc* d, void* workspace, tmdiff_stream_t stream);
 
@@ -346,6 +354,19 @@ int tmdiff_conv3d_wgrad_wino(const tmdiff_conv3d_desc* d, const float* g, float*
  * summation order).  dbias NULL = tmdiff_conv3d_wgrad_wino. */
 int tmdiff_conv3d_wgrad_wino_bias(const tmdiff_conv3d_desc* d, const float* g, float* dw, float* dbias, void* workspace,
                                   tmdiff_stream_t stream);
+
+/* The weight gradient of a 3x3x3 convolution with bf16 operands (csrc/wgrad_bf16.hip): g and x' -- formed from the descriptor exactly as in the forward, in-kernel dropout included -- are each rounded
+ * to bf16 (round to nearest even) when staged, the products are summed in fp32 on v_mfma_f32_32x32x16_bf16; the sum over batch
+ * and positions is split over workgroups whose fp32 partials a second kernel adds in a fixed order (no atomics: the same bits on
+ * every run and in a graph replay).  Same arguments and result layout as tmdiff_conv3d_wgrad_bias; dbias (optional) =
+ * bias_scale * sum g of the UNROUNDED g, in a fixed order.  Takes ksize 3, groups 1 or 3, Cin/groups % 8 == 0, Cout/groups % 32 ==
+ * 0, any extents tmdiff_conv3d_wgrad takes; _supported() says so, anything else returns TMDIFF_E_UNSUPPORTED without a launch and
+ * the caller keeps the fp32 weight gradient.  _slots(): the number of partial sums per element the second kernel adds. */
+int tmdiff_conv3d_wgrad_bf16_supported(const tmdiff_conv3d_desc* d);
+size_t tmdiff_conv3d_wgrad_bf16_workspace_bytes(const tmdiff_conv3d_desc* d);
+int32_t tmdiff_conv3d_wgrad_bf16_slots(const tmdiff_conv3d_desc* d);
+int tmdiff_conv3d_wgrad_bf16(const tmdiff_conv3d_desc* d, const float* g, float* dw, float* dbias, void* workspace,
+                             tmdiff_stream_t stream);
 
 /* out[c] = scale * sum_{b, p} x[b, c, p]   (x is [B, C, P]); bias gradients. */
 int tmdiff_channel_sum(const float* x, float* out, int32_t B, int32_t C, int64_t P, float scale,

@@ -317,7 +317,7 @@ class WavBEST(nn.Module):
         # fp32 frequency table of gamma_embedding (ref :89-92), computed on the host exactly like the reference
         half = inter_dim // 2
         self._freqs_cpu = torch.exp(-math.log(10000) * torch.arange(half, dtype=torch.float32) / half)
-        self.compute_dtype = "fp32"   # "bf16": bf16 operands / fp32 accumulation in the 3x3x3 convs (inference only)
+        self.compute_dtype = "fp32"   # "bf16": bf16 operands / fp32 accumulation in the 3x3x3 convs (inference only; training: ops.config.grad_bf16 for the gradient passes)
         self._prep = None        # packed weights / banks, keyed on parameter versions
         self._cond = None        # pinned step-invariant tensors of the current image set
 
@@ -690,8 +690,9 @@ class WavBEST(nn.Module):
         self._cond = None
         self.__dict__.pop("_train_pack", None)       # the training path's packed weights (ops.PackedWeights)
         self.__dict__.pop("_train_pack_wino", None)
+        self.__dict__.pop("_train_pack_bf16", None)
 
-    _DERIVED = ("_train_pack", "_train_pack_wino", "_emb_dev", "_freqs_dev", "_side_stream")
+    _DERIVED = ("_train_pack", "_train_pack_wino", "_train_pack_bf16", "_emb_dev", "_freqs_dev", "_side_stream")
 
     def __getstate__(self):
         """copy.deepcopy / pickle: everything derived from the parameters' ADDRESSES stays behind (packed weights and their
@@ -763,6 +764,7 @@ class WavBEST(nn.Module):
         # version changed, i.e. after the optimizer step)
         pk = self.__dict__.get("_train_pack")
         if pk is None or pk.convs[0][0].device != dev:
+            self.__dict__.pop("_train_pack_bf16", None)      # (its owner set is this pack's weights)
             pk = self.__dict__["_train_pack"] = ops.PackedWeights(
                 [(m.weight, m.groups) for m in self.modules()
                  if isinstance(m, nn.Conv3d) and m.in_channels > 1 and m.out_channels > 1])
@@ -772,6 +774,10 @@ class WavBEST(nn.Module):
         if wk is None:     # (owner = this network's weights: a foreign weight is packed on the spot, never registered)
             wk = self.__dict__["_train_pack_wino"] = ops.WinoPackedWeights(owner=[w for w, _ in pk.convs])
         ops.WINO_PACKED = wk.refresh() if ops.config.wino_multipack else None
+        # ... and, with config.grad_bf16, the bf16 data-gradient packings, re-made per weight when its version changed
+        if ops.config.grad_bf16 and "_train_pack_bf16" not in self.__dict__:
+            self.__dict__["_train_pack_bf16"] = ops.Bf16DgradWeights(owner=[w for w, _ in pk.convs])
+        ops.BF16_DGRAD = self.__dict__["_train_pack_bf16"] if ops.config.grad_bf16 else None
         lin = lambda seq, i, x, act: A.linear(x, seq[i].weight, seq[i].bias, act=act)
         pe = self._prompt_rows(prompt, b, dev)
         pemb = lin(self.embed2, 4, lin(self.embed2, 2, lin(self.embed2, 0, pe, True), True), True)

@@ -87,6 +87,11 @@ SIGNATURES = {
     "tmdiff_conv3d_wgrad_wino_workspace_bytes": (C.c_size_t, [C.POINTER(Conv3dDesc)]),
     "tmdiff_conv3d_wgrad_wino": (C.c_int, [C.POINTER(Conv3dDesc), vp, vp, vp, vp]),
     "tmdiff_conv3d_wgrad_wino_bias": (C.c_int, [C.POINTER(Conv3dDesc), vp, vp, vp, vp, vp]),
+    "tmdiff_conv3d_pack_weights_bf16_dgrad": (C.c_int, [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
+    "tmdiff_conv3d_wgrad_bf16_supported": (C.c_int, [C.POINTER(Conv3dDesc)]),
+    "tmdiff_conv3d_wgrad_bf16_workspace_bytes": (C.c_size_t, [C.POINTER(Conv3dDesc)]),
+    "tmdiff_conv3d_wgrad_bf16_slots": (C.c_int32, [C.POINTER(Conv3dDesc)]),
+    "tmdiff_conv3d_wgrad_bf16": (C.c_int, [C.POINTER(Conv3dDesc), vp, vp, vp, vp, vp]),
     "tmdiff_channel_sum": (C.c_int, [vp, vp, C.c_int32, C.c_int32, C.c_int64, C.c_float, vp]),
     "tmdiff_conv3d_prologue_bwd": (C.c_int, [C.POINTER(Conv3dDesc), vp, vp * 3, C.c_int32 * 3, vp, vp, vp]),
     "tmdiff_conv3d_prologue_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(Conv3dDesc)]),

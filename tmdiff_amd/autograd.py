@@ -35,6 +35,14 @@ def _wf_weights(w, groups, mode):
     return ops.pack_conv_weight_wino(w, groups, mode=mode, planes=6)
 
 
+def _bf16_dgrad_weights(w, groups):
+    """The bf16 data-gradient packing of w (config.grad_bf16): from the network's cache by parameter version (one launch per
+    weight and step, WavBEST.forward_train), else packed on the spot."""
+    if ops.BF16_DGRAD is not None:
+        return ops.BF16_DGRAD.get(w, groups)
+    return ops.pack_conv_weight_bf16_dgrad(w, groups)
+
+
 def _rows(t, what):
     """make_conv_desc arguments for a per-(sample, channel) prologue table [B, C] that may be a column block of a projection
     bank (rows `stride(0)` floats apart, as _SplitCols hands them out): pointer + row stride, no contiguous copy."""
@@ -118,13 +126,15 @@ def _conv_backward(st, gy, need_w, need_b, need_shift, need_scale, need_res, nee
     d_shift = d_scale = None
     d_segs = [None] * len(segs)
     if need_x:
-        wp_t = st["wp_dgrad"] if st["wp_dgrad"] is not None else ops.pack_conv_weight(w, groups=groups, mode=1)
-        if ksize == 3:     # the data gradient is a 3x3x3 convolution too (a plain input: no pass at all)
-            weights = ops.ConvWeights(lambda: wp_t, lambda: _wf_weights(w, groups, 3),
+        dgrad_packed = lambda: st["wp_dgrad"] if st["wp_dgrad"] is not None else ops.pack_conv_weight(w, groups=groups, mode=1)
+        if st["plan"].dgrad == "bf16":     # a 3x3x3 convolution of bf16-rounded g and w, on the inference mode's kernel
+            gp = ops.conv3d([g], _bf16_dgrad_weights(w, groups), cin, 3, groups=groups, math="bf16")
+        elif ksize == 3:     # the data gradient is a 3x3x3 convolution too (a plain input: no pass at all)
+            weights = ops.ConvWeights(dgrad_packed, lambda: _wf_weights(w, groups, 3),
                                       lambda planes: ops.pack_conv_weight_wino(w, groups, mode=1, planes=planes))
             gp = ops.conv3d_auto([g], weights, cin, groups=groups, family=st["plan"].dgrad)                # dL/dx'
         else:
-            gp = ops.conv3d([g], wp_t, cin, ksize, groups=groups)
+            gp = ops.conv3d([g], dgrad_packed(), cin, ksize, groups=groups)
         plain = not (act or has_shift or has_scale or mask is not None or st["drop"] is not None)
         if plain and len(segs) == 1 and outs is None:      # x' IS x: dL/dx' is the input gradient (no pass to copy it)
             return d_w, d_bias, None, None, d_res, [gp]
@@ -317,11 +327,14 @@ class _ConvLL(torch.autograd.Function):
         d_b = ops.channel_sum(go, 2.0 * ctx.ll_scale) if (ctx.has_bias and need[2]) else None
         d_x = None
         if need[3]:
-            pre = ops.PACKED.lookup(w) if ops.PACKED is not None else None
-            wp_t = pre[1] if pre is not None else ops.pack_conv_weight(w, mode=1)
             # dL/dx': a 3x3x3 convolution of the up-sampled gradient -- Winograd along the bands (13.5 multiply-adds per
             # element; the transposed form of the composed strided convolution would take 12)
-            gp = ops.conv3d_auto([g], ops.ConvWeights(lambda: wp_t, lambda: _wf_weights(w, 1, 3)), cin, family=ctx.plan.dgrad)
+            if ctx.plan.dgrad == "bf16":
+                gp = ops.conv3d([g], _bf16_dgrad_weights(w, 1), cin, 3, math="bf16")
+            else:
+                pre = ops.PACKED.lookup(w) if ops.PACKED is not None else None
+                wp_t = pre[1] if pre is not None else ops.pack_conv_weight(w, mode=1)
+                gp = ops.conv3d_auto([g], ops.ConvWeights(lambda: wp_t, lambda: _wf_weights(w, 1, 3)), cin, family=ctx.plan.dgrad)
             d_x = torch.empty_like(x)
             ops.conv3d_prologue_bwd(ops.make_conv_desc([x], 0, cout, 3, g, in_act=True), gp, [d_x], [False], False, False)
         return None, d_w, d_b, d_x

@@ -54,6 +54,9 @@ def parse(config, phase, gpu_ids=None, debug=False, root="experiments", make_dir
             if make_dirs:
                 os.makedirs(opt["path"][key], exist_ok=True)
     opt["phase"] = phase
+    grad_compute = (opt.get("train") or {}).get("grad_compute")      # optional: "bf16" = bf16 gradient arithmetic (model.DDPM)
+    if grad_compute not in (None, "fp32", "bf16"):
+        raise ValueError(f"train.grad_compute must be 'fp32' or 'bf16', got {grad_compute!r}")
     if gpu_ids is not None:
         opt["gpu_ids"] = [int(i) for i in str(gpu_ids).split(",")]
     opt["distributed"] = len(opt.get("gpu_ids") or []) > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1

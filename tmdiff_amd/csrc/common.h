@@ -60,6 +60,16 @@ inline double env_double(const char* name, double dflt) {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;   // one 32x32 MFMA accumulator (16 registers per lane)
 
+// bf16 operands of v_mfma_f32_32x32x16_bf16: eight values per lane.  pack_bf16x2 is THE fp32 -> bf16 rounding of the library
+// (round to nearest even, the conversion of the __bf16 type): two values as one dword, `lo` in the low half.  conv3d_bf16.hip
+// and wgrad_bf16.hip stage their operands through it.
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
+  union { __attribute__((ext_vector_type(2))) __bf16 h; unsigned u; } p;
+  p.h[0] = (__bf16)lo, p.h[1] = (__bf16)hi;
+  return p.u;
+}
+
 // compile-time loop: f(std::integral_constant<int, I>) for I in [B, E) -- indices must be constants so that
 // register arrays indexed by them are addressed statically (a runtime index would send them to scratch).
 template <int B, int E, class F>

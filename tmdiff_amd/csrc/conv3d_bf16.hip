@@ -42,8 +42,6 @@ namespace {
 
 using namespace tmdiff;
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-
 struct BfArgs {
   int B, N, H, W;
   int Cin, Cout, cin_g, cout_g, groups;
@@ -94,12 +92,6 @@ __device__ __forceinline__ void swap_halves(unsigned& x, unsigned& y) {
   const auto r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
   x = r[0], y = r[1];
 #endif
-}
-
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-  union { __attribute__((ext_vector_type(2))) __bf16 h; unsigned u; } p;
-  p.h[0] = (__bf16)lo, p.h[1] = (__bf16)hi;
-  return p.u;
 }
 
 // SiLU of the bf16 mode: the quotient by v_rcp_f32 (1 ulp) instead of the IEEE division sequence (a dozen instructions
@@ -872,6 +864,25 @@ __global__ void __launch_bounds__(256) pack_weights_bf16_kernel(const float* __r
   }
 }
 
+// The same layout for the DATA-GRADIENT convolution (Cout -> Cin channels) of a 3x3x3 convolution with weights w: taps mirrored,
+// the roles of the two channel axes swapped per group:
+// packed[g][chunk][tap][ci][8 co] (bf16, RNE) <- w[g*cout_g + chunk*8 + co][ci][26 - tap], slot 27 = 0.
+__global__ void __launch_bounds__(256) pack_weights_bf16_dgrad_kernel(const float* __restrict__ w, uint16_t* __restrict__ packed,
+                                                                      int cout_g, int cin_g, long total) {
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += 256L * gridDim.x) {
+    const int co8 = (int)(i % 8);
+    long r = i / 8;
+    const int ci = (int)(r % cin_g); r /= cin_g;
+    const int tap = (int)(r % TAPS2); r /= TAPS2;
+    const int chunk = (int)(r % (cout_g / 8));
+    const int g = (int)(r / (cout_g / 8));
+    float v = 0.f;
+    if (tap < 27) v = w[(((long)g * cout_g + chunk * 8 + co8) * cin_g + ci) * 27 + (26 - tap)];
+    const __bf16 h = (__bf16)v;
+    packed[i] = *reinterpret_cast<const uint16_t*>(&h);
+  }
+}
+
 template <int NS, int MSUB, int TH, int TW>
 int launch(BfArgs& a, hipStream_t st) {
   constexpr int CO = 32 * MSUB;
@@ -937,6 +948,22 @@ extern "C" int tmdiff_conv3d_pack_weights_bf16(const float* w, void* packed, int
   pack_weights_bf16_kernel<<<(int)blocks, 256, 0, as_stream(stream)>>>(w, static_cast<uint16_t*>(packed), Cout / groups,
                                                                       Cin / groups, groups, taps, slots, total);
   return check_launch("conv3d_pack_weights_bf16");
+}
+
+extern "C" int tmdiff_conv3d_pack_weights_bf16_dgrad(const float* w, void* packed, int32_t Cout, int32_t Cin, int32_t ksize,
+                                                     int32_t groups, tmdiff_stream_t stream) {
+  using namespace tmdiff;
+  TMDIFF_REQUIRE(w && packed, "pack_weights_bf16_dgrad: NULL pointer");
+  TMDIFF_REQUIRE(ksize == 3, "pack_weights_bf16_dgrad: ksize=%d (3)", ksize);
+  TMDIFF_REQUIRE(groups >= 1 && Cout > 0 && Cin > 0 && Cout % groups == 0 && Cin % groups == 0,
+                 "pack_weights_bf16_dgrad: Cout=%d Cin=%d groups=%d", Cout, Cin, groups);
+  TMDIFF_REQUIRE((Cout / groups) % 8 == 0, "pack_weights_bf16_dgrad: Cout/groups=%d is not a multiple of 8", Cout / groups);
+  const long total = (long)(Cout / 8) * TAPS2 * (Cin / groups) * 8;
+  long blocks = (total + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  pack_weights_bf16_dgrad_kernel<<<(int)blocks, 256, 0, as_stream(stream)>>>(w, static_cast<uint16_t*>(packed), Cout / groups,
+                                                                            Cin / groups, total);
+  return check_launch("conv3d_pack_weights_bf16_dgrad");
 }
 
 extern "C" int tmdiff_conv3d_fwd_bf16(const tmdiff_conv3d_desc* d, void* workspace, tmdiff_stream_t stream) {

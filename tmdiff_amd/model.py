@@ -139,6 +139,11 @@ class DDPM(BaseModel):
         # train.max_grad_norm (optional; absent: no clipping): bound on the global gradient norm, applied after the gradient
         # all-reduce (every rank clips the same reduced gradients by the same norm)
         self.max_grad_norm = train_opt.get("max_grad_norm")
+        # train.grad_compute (optional; absent: ops.config.grad_bf16 / TMDIFF_GRAD_BF16 as it stands): "bf16" forms the gradients
+        # of the eligible 3x3x3 convolutions from bf16-rounded operands (fp32 sums; forward, loss, parameters, AdamW unchanged)
+        self.grad_compute = train_opt.get("grad_compute")
+        if self.grad_compute not in (None, "fp32", "bf16"):
+            raise ValueError(f"train.grad_compute must be 'fp32' or 'bf16', got {self.grad_compute!r}")
         self._grad_norm = None          # last norm of the torch.optim.AdamW path
         self.split_graph = False
         self._captured, self._eager_steps, self._drop_word = {}, {}, None
@@ -178,6 +183,12 @@ class DDPM(BaseModel):
         self.optG.step()
 
     def optimize_parameters(self, prompt=None):
+        if self.grad_compute is None:
+            return self._optimize_parameters(prompt)
+        with ops.config.override(grad_bf16=self.grad_compute == "bf16"):
+            return self._optimize_parameters(prompt)
+
+    def _optimize_parameters(self, prompt=None):
         if self.reducer is None:       # created here: the process group exists by the first step
             self.reducer = tdist.GradReducer(self.netG, op=self.grad_reduce)
             self.split_graph = self.use_graph and self.reducer.active

@@ -56,6 +56,9 @@ class KernelConfig:
     train_two_streams  TMDIFF_TRAIN_STREAMS     True     forward_train runs the condition branch on a second stream beside the
                                                          main branch's down path (at a local batch of 8 most launches fill half
                                                          of the CU slots); autograd then runs their backward passes side by side too
+    grad_bf16          TMDIFF_GRAD_BF16         False    finetune: the data gradients of the eligible 3x3x3 convolutions from bf16-rounded
+                                                         operands with fp32 accumulation (routing.train_conv_plan rule 6b; the forward,
+                                                         the loss, the weight gradients, parameters and the optimizer stay fp32)
     sample_graph       TMDIFF_SAMPLE_GRAPH      False    (GeneralDiffusion) p_sample_loop / super_resolution / sample /
                                                          sample_by_dpmsolver capture their steps into HIP graphs and replay them
                                                          (tmdiff_amd.sample_graph; per object: GeneralDiffusion.sample_graphs)
@@ -83,6 +86,7 @@ class KernelConfig:
         "train_graph": ("TMDIFF_TRAIN_GRAPH", _FLAG(False), False),
         "train_two_streams": ("TMDIFF_TRAIN_STREAMS", _FLAG(True), True),
         "sample_graph": ("TMDIFF_SAMPLE_GRAPH", _FLAG(False), False),
+        "grad_bf16": ("TMDIFF_GRAD_BF16", _FLAG(False), False),
     }
 
     def __init__(self, env=None):
@@ -321,6 +325,56 @@ def pack_conv_weight_bf16(w, groups=1):
     check(lib.tmdiff_conv3d_pack_weights_bf16(_chk(w.detach(), "w"), out.data_ptr(), cout, cin_g * groups, k, groups,
                                               stream_ptr()), "conv3d_pack_weights_bf16")
     return out
+
+
+def pack_conv_weight_bf16_dgrad(w, groups=1):
+    """[Cout, Cin/g, 3,3,3] fp32 of a FORWARD convolution -> the bf16 packing of its data-gradient convolution (Cout -> Cin
+    channels, taps mirrored, channel axes swapped per group; int16 storage): conv3d([g], packed, Cin, 3, math="bf16") == dL/dx'."""
+    cout, cin_g = w.shape[0], w.shape[1]
+    nbytes = lib.tmdiff_conv3d_packed_bf16_bytes(cin_g * groups, cout, 3, groups) if tuple(w.shape[2:]) == (3, 3, 3) else 0
+    if nbytes == 0:
+        raise ValueError(f"conv weight {tuple(w.shape)} (groups={groups}) has no bf16 data-gradient packing")
+    out = torch.empty(nbytes // 2, device=w.device, dtype=torch.int16)
+    check(lib.tmdiff_conv3d_pack_weights_bf16_dgrad(_chk(w.detach(), "w"), out.data_ptr(), cout, cin_g * groups, 3, groups,
+                                                    stream_ptr()), "conv3d_pack_weights_bf16_dgrad")
+    return out
+
+
+class Bf16DgradWeights:
+    """The bf16 data-gradient packings of the weights a finetune step with config.grad_bf16 runs through conv3d(math="bf16"),
+    cached by the parameter's ``_version`` like PackedWeights: ``get`` re-packs a weight (one launch) only when it has changed
+    since its packing was made -- once per weight and step after an optimizer update (optim.FusedAdamW bumps the versions of the
+    parameters its kernel writes), never per layer call.  The packed tensor of a weight keeps its address across re-packs (a
+    captured step replays on it).  ``owner`` = the weights of the network this cache belongs to, as for WinoPackedWeights: a
+    weight that is not among them is packed on the spot and not kept."""
+
+    def __init__(self, owner=None):
+        self.items = {}          # weight address -> [weight, groups, packed, version]
+        self.owner = None if owner is None else {w.data_ptr() for w in owner}
+
+    def get(self, w, groups):
+        if self.owner is not None and w.data_ptr() not in self.owner:
+            return pack_conv_weight_bf16_dgrad(w, groups)
+        it = self.items.get(w.data_ptr())
+        if it is not None and (it[0].shape != w.shape or it[1] != groups or it[2].device != w.device):
+            it = None
+        if it is not None and it[3] == w._version:
+            return it[2]
+        if it is None:
+            out = pack_conv_weight_bf16_dgrad(w, groups)
+        else:
+            out = it[2]
+            check(lib.tmdiff_conv3d_pack_weights_bf16_dgrad(_chk(w.detach(), "w"), out.data_ptr(), w.shape[0], w.shape[1] * groups, 3,
+                                                            groups, stream_ptr()), "conv3d_pack_weights_bf16_dgrad")
+        _count("conv3d_pack_weights_bf16_dgrad")
+        self.items[w.data_ptr()] = [w, groups, out, w._version]
+        return out
+
+    def __deepcopy__(self, memo):
+        return Bf16DgradWeights()
+
+
+BF16_DGRAD = None  # the Bf16DgradWeights of the network being trained with config.grad_bf16 (WavBEST.forward_train)
 
 
 def make_conv_desc(segs, w_packed, cout, ksize, y, groups=1, bias=None, bias_scale=1.0, in_shift=None, in_scale=None,
@@ -1295,6 +1349,25 @@ def conv3d_wgrad(desc, g, weight_shape, want_bias=False):
     check(lib.tmdiff_conv3d_wgrad_bias(C.byref(desc), _chk(g, "g"), dw.data_ptr(), db.data_ptr(), ws.data_ptr(),
                                        stream_ptr()), "conv3d_wgrad_bias")
     return dw, db
+
+
+def wgrad_bf16_supported(desc):
+    """True when tmdiff_conv3d_wgrad_bf16 takes the descriptor (3x3x3, groups 1 or 3, Cin/groups % 8 == 0, Cout/groups % 32 == 0)."""
+    return bool(lib.tmdiff_conv3d_wgrad_bf16_supported(C.byref(desc)))
+
+
+def conv3d_wgrad_bf16(desc, g, weight_shape, want_bias=False):
+    """conv3d_wgrad with bf16 operands: g and the prologue output x' of `desc` rounded to bf16 (nearest even), products summed
+    in fp32 (csrc/wgrad_bf16.hip; deterministic).  want_bias: also dL/dbias = desc.bias_scale * sum g of the unrounded g.
+    A descriptor the kernel does not take raises (TMDIFF_E_UNSUPPORTED): ask wgrad_bf16_supported / routing first."""
+    dw = torch.empty(weight_shape, device=g.device, dtype=torch.float32)
+    _count("conv3d_wgrad_bf16", 2.0 * desc.B * desc.Cout * (desc.Cin // max(desc.groups, 1)) * 27 * desc.N * desc.H * desc.W)
+    nbytes = lib.tmdiff_conv3d_wgrad_bf16_workspace_bytes(C.byref(desc))
+    ws = _workspace(g.device, max(16, nbytes), "wgrad")
+    db = torch.empty(weight_shape[0], device=g.device, dtype=torch.float32) if want_bias else None
+    check(lib.tmdiff_conv3d_wgrad_bf16(C.byref(desc), _chk(g, "g"), dw.data_ptr(), _chk(db, "db"), ws.data_ptr(), stream_ptr()),
+          "conv3d_wgrad_bf16")
+    return (dw, db) if want_bias else dw
 
 
 def channel_sum(x, scale=1.0):

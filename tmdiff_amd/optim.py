@@ -173,6 +173,9 @@ class FusedAdamW(torch.optim.AdamW):
             check(lib.tmdiff_multi_adamw(*args, ops.stream_ptr()), "multi_adamw")
         else:
             check(lib.tmdiff_multi_adamw_scaled(*args, coef.data_ptr(), ok.data_ptr(), ops.stream_ptr()), "multi_adamw_scaled")
+        # the kernel writes the parameters through raw pointers: tell autograd's version counters, which the packed convolution
+        # weights and projection banks are keyed on (ops.PackedWeights, WavBEST._prepare), as an in-place torch update would
+        torch.autograd.graph.increment_version(params)
 
     def _clipped_step(self, work):
         """Norm over ALL groups (one stage-1 launch per group, one finish), then per group: counter += ok, scaled AdamW."""

@@ -58,6 +58,11 @@ keys of ops.COUNTS, `tools/routing_table.py --train` writes profiles/train_routi
   6. weight gradient (wgrad_family): Winograd F(3,4) along the bands where config.wgrad_wino, 3x3x3 and
      tmdiff_conv3d_wgrad_wino_supported, else direct; the bias gradient rides in it with config.wgrad_bias, or in the
      Winograd kernel's g pass with config.wgrad_wino_bias, else a channel sum of its own.
+  6b. config.grad_bf16 (opt-in; the forward is untouched): the data gradient of a 3x3x3 convolution on conv3d_bf16 where
+     dgrad_bf16_ok (Cin/g % 32 == 0, Cout/g % 8 == 0): family "bf16" in the plan, whose dgrad_math / wgrad_math name the
+     arithmetic.  The weight gradient stays on rule 6's fp32 families in EVERY layer class: measured at local batch 8
+     (profiles/train_bf16_grad.txt), the bf16 weight-gradient kernel (csrc/wgrad_bf16.hip, ops.conv3d_wgrad_bf16) is 2.0 - 3.7x
+     slower than tmdiff_conv3d_wgrad_wino in all 20 classes of the 32-256 network, so no class is routed to it.
   7. Conv_0 + LL of a main-branch down block is one node where the composed form exists (ll_composable) and ll_fits: on
      conv3d_wf's composed mode with config.train_ll_wino where wfll_route takes it, else on conv3d_ll; Conv_2 after the LL
      band with config.conv2_after_ll.
@@ -80,6 +85,11 @@ FALLBACK_FAMILIES = ("wino4", "wino2")
 def _config():
     from . import ops
     return ops.config
+
+
+def _grad_bf16():
+    """config.grad_bf16 (a configuration without the field: off)"""
+    return bool(getattr(_config(), "grad_bf16", False))
 
 
 def wino_weight_ok(cout, cin, ksize=3, groups=1):
@@ -400,13 +410,35 @@ def down_plan(b, ch, n, h, w, maths, main, pre, s2d, fuse):
 # ---- the finetune graph: one plan per differentiable convolution and per block -------------------------------------------------
 # What autograd._conv_forward / _conv_backward / _ConvLL and the block classes' `run` execute and unet_train_launches tabulates;
 # functions of extents, channel counts, what the input looks like and ops.config, asked once per convolution per step.
-TrainConvPlan = collections.namedtuple("TrainConvPlan", "fwd keep_xp dgrad wgrad bias_in_wgrad")
-TrainLLPlan = collections.namedtuple("TrainLLPlan", "fwd dgrad wgrad")
+class _GradMath:
+    """The arithmetic of a plan's two gradient passes, "fp32" or "bf16" (config.grad_bf16): read off their families -- "bf16" is
+    the family of a data gradient on conv3d_bf16 (no weight gradient is routed to a bf16 kernel: rule 6b)."""
+    __slots__ = ()
+    dgrad_math = property(lambda self: "bf16" if self.dgrad == "bf16" else "fp32")
+    wgrad_math = property(lambda self: "bf16" if self.wgrad == "bf16" else "fp32")
+
+
+class TrainConvPlan(_GradMath, collections.namedtuple("TrainConvPlan", "fwd keep_xp dgrad wgrad bias_in_wgrad")):
+    __slots__ = ()
+
+
+class TrainLLPlan(_GradMath, collections.namedtuple("TrainLLPlan", "fwd dgrad wgrad")):
+    __slots__ = ()
+
+
 TrainDownPlan = collections.namedtuple("TrainDownPlan", "conv0 conv2_after_ll")
 
 
+def dgrad_bf16_ok(b, cin, cout, n, h, w, groups=1, ksize=3):
+    """True when the data gradient of a convolution cin -> cout runs on conv3d_bf16 (config.grad_bf16): a plain 3x3x3 convolution
+    of g, cout -> cin channels, on weights from tmdiff_conv3d_pack_weights_bf16_dgrad -- the forward kernel's shape rule with the
+    two channel counts swapped (Cin/groups % 32 == 0, Cout/groups % 8 == 0) and its 32-bit plane offsets."""
+    return bool(_grad_bf16() and ksize == 3 and groups in (1, 3) and cin % groups == 0 and cout % groups == 0 and
+                (cin // groups) % 32 == 0 and (cout // groups) % 8 == 0 and n * h * w < (1 << 31))
+
+
 def wgrad_family(b, seg_c, cout, n, h, w, groups=1, ksize=3, prologue=False, **fields):
-    """"wino" (Winograd F(3,4) along the bands, csrc/wgrad_wino.hip) or "direct": the kernel of the weight gradient of a
+    """"wino" (Winograd F(3,4) along the bands, csrc/wgrad_wino.hip) or "direct": the kernel of the fp32 weight gradient of a
     convolution of the segments seg_c (a tuple of channel counts) -> cout.  prologue: the kernel applies the forward's prologue to
     its input itself (no kept x'); fields: further descriptor fields the library's query reads."""
     if not (_config().wgrad_wino and ksize == 3):
@@ -424,13 +456,15 @@ def train_conv_plan(b, seg_c, cout, n, h, w, groups=1, ksize=3, prologue=False, 
     pass writes x' into a tensor of its own and the weight gradient reads that (staged_weight_ok: the direct kernel that has
     such a pass); dgrad: the family of the data gradient, a plain-input convolution cout -> cin; wgrad: wgrad_family on what
     the weight gradient reads; bias_in_wgrad: the bias gradient rides in the weight-gradient kernel (config.wgrad_bias: the
-    direct kernel accumulates it; config.wgrad_wino_bias: the Winograd kernel's g pass sums it on the side)."""
+    direct kernel accumulates it; config.wgrad_wino_bias: the Winograd kernel's g pass sums it on the side).  config.grad_bf16:
+    dgrad is "bf16" where dgrad_bf16_ok takes the shape (plan.dgrad_math / plan.wgrad_math name the arithmetic of the two gradient
+    passes); fwd, keep_xp and wgrad never change."""
     cfg, cin = _config(), sum(seg_c)
     pro = bool(prologue or masked or dropout)
     keep_xp = bool(ksize == 3 and (masked or dropout) and need_w and staged_weight_ok(cout, cin, groups))
     if ksize == 3:
         fwd = conv3_family(b, cin, cout, n, h, w, groups, len(seg_c) == 1 and not pro, masked, dropout, keep_xp)
-        dgrad = conv3_family(b, cout, cin, n, h, w, groups)
+        dgrad = "bf16" if dgrad_bf16_ok(b, cin, cout, n, h, w, groups) else conv3_family(b, cout, cin, n, h, w, groups)
     else:
         fwd = dgrad = "k1"
     wgrad = wgrad_family(b, (cin,) if keep_xp else seg_c, cout, n, h, w, groups, ksize, pro and not keep_xp)
@@ -444,7 +478,7 @@ def train_ll_plan(b, cin, cout, n, h, w):
     data gradient (the node offers no transform-pass weights: a fallback family's shape stays direct) and of the weight
     gradient on the kept x'."""
     fwd = "wfll" if _config().train_ll_wino and wfll_route(b, cin, cout, n, h, w) else "ll"
-    dgrad = conv3_family(b, cout, cin, n, h, w)
+    dgrad = "bf16" if dgrad_bf16_ok(b, cin, cout, n, h, w) else conv3_family(b, cout, cin, n, h, w)
     if dgrad in FALLBACK_FAMILIES:
         dgrad = direct_family(cout, cin, extents=(b, n, h, w))
     return TrainLLPlan(fwd, dgrad, wgrad_family(b, (cin,), cout, n, h, w))
@@ -596,7 +630,7 @@ TrainLaunches = collections.namedtuple("TrainLaunches", "counts convs blocks")
 # ResBlock (train_resblock_plan) and down block (train_down_plan)
 LAUNCH_KEY = {"wf": "conv3d_wf_fwd", "wf_pair": "conv3d_wf_fwd", "wfll": "conv3d_wfll_fwd", "ll": "conv3d_ll_fwd",
               "staged": "conv3d_fwd_staged", "fused": "conv3d_fwd", "k1": "conv3d_fwd_k1", "wino4": "conv3d_wino4_fwd",
-              "wino2": "conv3d_wino2_fwd", "wino": "conv3d_wgrad_wino", "direct": "conv3d_wgrad"}
+              "wino2": "conv3d_wino2_fwd", "wino": "conv3d_wgrad_wino", "direct": "conv3d_wgrad", "bf16": "conv3d_fwd_bf16"}
 
 
 def unet_train_launches(channels, b, n, h, w, dropout=False):

@@ -97,6 +97,7 @@ def main(argv=None):
     ap.add_argument("-debug", "-d", action="store_true")
     ap.add_argument("--root", type=str, default="experiments", help="where the run directory is created")
     ap.add_argument("--max-iter", type=int, default=None, help="override opt['train']['max_iter']")
+    ap.add_argument("--grad-compute", type=str, choices=["fp32", "bf16"], default=None, help="override opt['train']['grad_compute']")
     args = ap.parse_args(argv)
 
     world = tdist.init_from_env()
@@ -104,6 +105,8 @@ def main(argv=None):
     if torch.cuda.is_available():
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())
     opt = Config.parse(args.config, args.phase, args.gpu_ids, args.debug, root=args.root, make_dirs=rank == 0)
+    if args.grad_compute is not None:
+        opt["train"]["grad_compute"] = args.grad_compute
     logging.basicConfig(level=logging.INFO if rank == 0 else logging.WARNING, format="%(asctime)s %(message)s")
     logger = logging.getLogger("base")
     logger.info(Config.dict2str(opt))
