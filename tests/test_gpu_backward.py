@@ -434,6 +434,47 @@ def test_weight_gradient_in_the_winograd_domain(case):
     assert_close(db.cpu(), (2.0 * g.double().sum(dim=(0, 2, 3, 4))).float(), 1e-5, 1e-5, "dbias beside the Winograd weight gradient")
 
 
+@pytest.mark.parametrize("case", [
+    (2, (32,), 64, 8, 16, 16, 1, False),       # the first shape of test_weight_gradient_in_the_winograd_domain
+    (2, (16, 8, 8), 32, 4, 16, 32, 1, True),   # ... and its three segments + prologue (the x' pass inside either kernel)
+])
+def test_wgrad_family_argument_launches_what_routing_would(case):
+    """ops.conv3d_wgrad(family="wino" / "direct") -- what autograd passes from the plan -- is bit for bit what family=None gives
+    when routing picks that kernel (config.wgrad_wino on / off), with and without the bias gradient, and launches that kernel
+    alone; a 1x1x1 weight gradient with family="direct" likewise."""
+    import collections
+    from tmdiff_amd import ops
+    B, segc, cout, N, H, W, groups, pro = case
+    cin = sum(segc)
+    xd, gd = [cu(randn(41 + i, B, c, N, H, W)) for i, c in enumerate(segc)], cu(randn(40, B, cout, N, H, W))
+    sh, sc = cu(0.3 * randn(38, B, cin)), cu(torch.rand(B, cin) + 0.5)
+    kw = dict(in_shift=sh, in_scale=sc, in_act=True) if pro else {}
+    d = ops.make_conv_desc(xd, 0, cout, 3, gd, groups=groups, bias_scale=2.0, **kw)
+    wshape = (cout, cin // groups, 3, 3, 3)
+    counts, ops.COUNTS = ops.COUNTS, collections.Counter()
+    try:
+        for family, key, other in (("wino", "conv3d_wgrad_wino", "conv3d_wgrad"), ("direct", "conv3d_wgrad", "conv3d_wgrad_wino")):
+            with ops.config.override(wgrad_wino=family == "wino"):
+                want, (want_w, want_b) = ops.conv3d_wgrad(d, gd, wshape), ops.conv3d_wgrad(d, gd, wshape, want_bias=True)
+                assert ops.wgrad_wino_takes(d) == (family == "wino")
+            ops.COUNTS.clear()
+            with ops.config.override(wgrad_wino=family != "wino"):      # (what routing would say is not asked)
+                got, (got_w, got_b) = ops.conv3d_wgrad(d, gd, wshape, family=family), ops.conv3d_wgrad(d, gd, wshape, True, family=family)
+            assert ops.COUNTS[key] == 2 and ops.COUNTS[other] == 0, (family, dict(ops.COUNTS))
+            assert torch.equal(got, want) and torch.equal(got_w, want_w) and torch.equal(got_b, want_b), family
+        # 1x1x1: routing's answer is "direct" whatever the switch says
+        d1 = ops.make_conv_desc(xd, 0, cout, 1, gd, groups=groups, bias_scale=2.0, **kw)
+        w1 = (cout, cin // groups, 1, 1, 1)
+        want, (want_w, want_b) = ops.conv3d_wgrad(d1, gd, w1), ops.conv3d_wgrad(d1, gd, w1, want_bias=True)
+        got, (got_w, got_b) = ops.conv3d_wgrad(d1, gd, w1, family="direct"), ops.conv3d_wgrad(d1, gd, w1, True, family="direct")
+        assert torch.equal(got, want) and torch.equal(got_w, want_w) and torch.equal(got_b, want_b)
+        assert ops.COUNTS["conv3d_wgrad"] == 6 and ops.COUNTS["conv3d_wgrad_wino"] == 0, dict(ops.COUNTS)
+    finally:
+        ops.COUNTS = counts
+    with pytest.raises(ValueError):
+        ops.conv3d_wgrad(d, gd, wshape, family="bf16")
+
+
 @pytest.mark.parametrize("shape", [(2, 8, 64, 4, 16, 16), (1, 6, 128, 3, 12, 20), (8, 16, 64, 8, 32, 64)])
 def test_composed_conv_ll_gradients_vs_cpu_autograd(shape):
     """autograd.conv3d_ll = LL(conv3d(SiLU(x), w) + b) / 2 with the forward as ONE strided convolution on composed weights

@@ -339,7 +339,7 @@ def bwd_slices(b, cin, plane):
 def bwd_depth(plane, slices):
     """Longest chain of dependent additions behind one d_shift / d_scale element, read from prologue_bwd_kernel: a slice is
     ceil(units / slices) units (float4 branch: unit = 4 elements) over 256 lanes, each lane adding its elements one by one;
-    block_sum_256 adds 6 shuffle steps and red[0] + red[1] + red[2] + red[3] (3); rowsum_kernel adds the slices one by one."""
+    block_sum adds 6 shuffle steps and red[0] + red[1] + red[2] + red[3] (3); rowsum_kernel adds the slices one by one."""
     unit = 4 if plane % 4 == 0 else 1
     lane = unit * cdiv(cdiv(plane // unit, slices), 256)
     return lane + 6 + 3 + (slices if slices > 1 else 0)
@@ -522,7 +522,7 @@ def test_channel_sum_vs_fp64(ops, b, c, p):
     """out[c] = scale * sum_{b, p} x: one slice (P = 1, 2047), two slices of 1025 (P = 2049), three of 1667 with a last one of
     1666 (P = 5000), no sample at all (zeros).  The output starts as NaN: the kernel zeroes it, then every slice adds its part
     atomically.  Bound D * 2^-24 * |scale| * sum|x| with D from channel_sum_kernel: a lane adds at most ceil(slice / 256) values
-    per sample (the unrolled trips add pairs first, which only shortens the chain), B samples; block_sum_256 adds 6 shuffle steps
+    per sample (the unrolled trips add pairs first, which only shortens the chain), B samples; block_sum adds 6 shuffle steps
     and 3 additions of the waves' sums; one rounding of scale * s; the slices meet in `slices` atomic additions."""
     from tmdiff_amd import _lib
     slices = max(1, min(cdiv(2048, c), cdiv(p, 2048)))

@@ -1078,3 +1078,93 @@ def test_train_predicates_agree_with_the_rules_they_came_from():
     assert ops.wgrad_wino_takes(d) and [ops.wgrad_wino_takes(e) for e in cases[1:5]] == [False] * 4
     with ops.config.override(wgrad_wino=False):
         assert not ops.wgrad_wino_takes(d) and routing.wgrad_family(8, (64,), 64, 8, 64, 64) == "direct"
+
+
+@pytest.mark.parametrize("channels,b,n,size,switches", [
+    ([32, 64, 128, 256], 8, 8, 64, {}),                                       # configs[3]
+    ([16, 32, 64, 128], 8, 8, 64, {}),                                        # the reference's default widths
+    ([16, 32, 64, 64], 2, 4, 128, {"wino_min_blocks": 1}),                    # a small case of tests/test_gpu_configs.py
+])
+@pytest.mark.parametrize("wgrad_wino", [True, False])
+def test_plan_wgrad_family_is_what_conv3d_wgrad_would_ask_for(channels, b, n, size, switches, wgrad_wino):
+    """autograd passes plan.wgrad to ops.conv3d_wgrad(family=) instead of letting it ask routing again: on every row of
+    routing.unet_train_launches' convolution table the two answers are the same.  The descriptor is the one _conv_backward /
+    _ConvLL.backward hand to ops.conv3d_wgrad: the forward's segments with its prologue, or -- plan.keep_xp, _ConvLL -- the kept x'
+    as one plain segment.  (Pointers are placeholders: routing reads which fields are set, nothing is dereferenced.)"""
+    import collections
+    from tmdiff_amd import _lib, ops, routing
+
+    def desc(seg_c, cout, h, w, groups, ksize, prologue=False, dropout=False):
+        d = _lib.Conv3dDesc()
+        d.B, d.N, d.H, d.W, d.Cin, d.Cout, d.groups, d.ksize, d.nseg = b, n, h, w, sum(seg_c), cout, groups, ksize, len(seg_c)
+        for i, c in enumerate(seg_c):
+            d.seg_c[i], d.seg_x[i] = c, 64
+        if prologue:
+            d.in_act, d.in_shift = 1, 64
+        if dropout:
+            d.drop_seed, d.drop_p = 1, 0.2
+        return d
+
+    asked = []          # (plan.wgrad, the weight gradient's descriptor) of every plan the table asks for
+    conv_plan, ll_plan = routing.train_conv_plan, routing.train_ll_plan
+
+    def train_conv_plan(b_, seg_c, cout, n_, h, w, groups=1, ksize=3, prologue=False, masked=False, dropout=False, need_w=True):
+        p = conv_plan(b_, seg_c, cout, n_, h, w, groups, ksize, prologue, masked, dropout, need_w)
+        kept = desc((sum(seg_c),), cout, h, w, groups, ksize)
+        asked.append((p.wgrad, kept if p.keep_xp else desc(seg_c, cout, h, w, groups, ksize, prologue, dropout)))
+        return p
+
+    def train_ll_plan(b_, cin, cout, n_, h, w):
+        p = ll_plan(b_, cin, cout, n_, h, w)
+        asked.append((p.wgrad, desc((cin,), cout, h, w, 1, 3)))
+        return p
+
+    with ops.config.override(wgrad_wino=wgrad_wino, **switches):
+        for dropout in (False, True):
+            del asked[:]
+            routing.train_conv_plan, routing.train_ll_plan = train_conv_plan, train_ll_plan
+            try:
+                rows = routing.unet_train_launches(channels, b, n, size, size, dropout).convs
+            finally:
+                routing.train_conv_plan, routing.train_ll_plan = conv_plan, ll_plan
+            lls = sum(r.fwd in ("ll", "wfll") for r in rows)
+            # every row has asked for its plan here (a down block may ask for its Conv_0 + LL plan twice: block and row)
+            assert len(asked) >= len(rows) and lls > 0 and collections.Counter(r.wgrad for r in rows) <= collections.Counter(f for f, _ in asked)
+            for fam, d in asked:
+                assert fam == ("wino" if ops.wgrad_wino_takes(d) else "direct"), (fam, d.Cin, d.Cout, d.H, d.W, d.ksize, d.nseg)
+            if wgrad_wino:
+                assert {f for f, _ in asked} == {"wino", "direct"}      # both kernels are in the table (1x1x1 rows are direct)
+            else:
+                assert {f for f, _ in asked} == {"direct"}
+
+
+def test_wgrad_split_choice_through_the_workspace_queries():
+    """choose_splits (csrc/common.h) behind plan_wgrad and ww_plan, seen through tmdiff_conv3d_wgrad_workspace_bytes and
+    tmdiff_conv3d_wgrad_wino_workspace_bytes: the partial-sum area is `splits` slots, so the byte counts pin the split count.
+    One box in all, a prime number of boxes (7, 13), more than 256 (co, ci) tiles, more boxes than the split maximum, groups 3,
+    ragged extents, a 1x1x1 weight and a prologue (x' in the workspace).  The integers are those of the build before the split
+    search became one function; 0 = the Winograd kernel does not take the shape."""
+    import ctypes as C
+    from tmdiff_amd import _lib
+    L = _lib.lib
+    want = {    # (B, Cin, Cout, N, H, W, groups, ksize, in_act): (direct bytes, Winograd bytes)
+        (1, 8, 8, 2, 8, 8, 1, 3, 0): (6944, 0),
+        (1, 8, 8, 4, 8, 8, 1, 3, 0): (13888, 348160),
+        (1, 32, 32, 2, 8, 56, 1, 3, 0): (775040, 0),
+        (1, 32, 32, 4, 8, 104, 1, 3, 0): (2878720, 3113984),
+        (13, 16, 16, 4, 8, 8, 1, 3, 0): (720512, 4526080),
+        (1, 544, 544, 4, 8, 8, 1, 3, 0): (63926528, 66080768),
+        (2, 544, 544, 2, 16, 16, 1, 1, 0): (4743680, 0),
+        (8, 64, 64, 8, 64, 64, 1, 3, 0): (28327936, 226557952),
+        (2, 96, 96, 8, 16, 16, 3, 3, 0): (10629120, 10678272),
+        (3, 24, 40, 5, 12, 20, 1, 3, 0): (5607360, 0),
+        (32, 32, 32, 8, 64, 64, 1, 3, 0): (28344320, 434094080),
+        (1, 64, 64, 4, 8, 16, 1, 3, 1): (1901568, 1490944),
+        (4, 256, 256, 8, 8, 8, 1, 3, 0): (28315648, 22282240),
+    }
+    for case, bytes_ in want.items():
+        d = _lib.Conv3dDesc()
+        d.B, d.Cin, d.Cout, d.N, d.H, d.W, d.groups, d.ksize, d.in_act = case
+        d.nseg, d.seg_c[0] = 1, case[1]
+        got = (L.tmdiff_conv3d_wgrad_workspace_bytes(C.byref(d)), L.tmdiff_conv3d_wgrad_wino_workspace_bytes(C.byref(d)))
+        assert got == bytes_, (case, got, bytes_)

@@ -13,7 +13,8 @@ from . import ops, routing
 
 
 # Which kernel runs what is decided in tmdiff_amd.routing (train_conv_plan, train_ll_plan: one look-up per convolution per
-# step, in the forward); this module executes the plans.  (Measured: 43.4 vs 43.2 ms per finetune step with the bias
+# step, in the forward); this module executes the plans: the forward, the data gradient (_data_grad) and the weight gradient
+# (ops.conv3d_wgrad(family=plan.wgrad)) all take their family from the plan the forward kept.  (Measured: 43.4 vs 43.2 ms per finetune step with the bias
 # gradient inside the direct weight-gradient kernel -- the saved pass is paid back inside the MFMA stream, so the separate
 # pass stays the default, config.wgrad_bias.)
 
@@ -60,6 +61,22 @@ def conv_plan(segs, wshape, groups, prologue, mask, need_w):
     drop = isinstance(mask, DropSpec)
     return routing.train_conv_plan(b, tuple(s.shape[1] for s in segs), wshape[0], n, h, w, groups, wshape[2], bool(prologue),
                                    mask is not None and not drop, drop, bool(need_w))
+
+
+def _data_grad(plan_dgrad, w, groups, g, cin, ksize, wp_dgrad, offer_wino_pass):
+    """dL/dx' of a convolution by w: a convolution of g, cout -> cin channels, on the family the plan names.  plan_dgrad "bf16":
+    a 3x3x3 convolution of bf16-rounded g and w on the inference mode's kernel.  wp_dgrad: the step's packed data-gradient
+    weights (ops.PACKED), or None: packed here when a direct kernel runs.  offer_wino_pass: the weights of the transform-pass
+    Winograd kernels are on offer (a node that does not offer them has a plan that never names those families)."""
+    if plan_dgrad == "bf16":
+        return ops.conv3d([g], _bf16_dgrad_weights(w, groups), cin, 3, groups=groups, math="bf16")
+    packed = lambda: wp_dgrad if wp_dgrad is not None else ops.pack_conv_weight(w, groups=groups, mode=1)
+    if ksize != 3:
+        return ops.conv3d([g], packed(), cin, ksize, groups=groups)
+    # the data gradient is a 3x3x3 convolution too (a plain input: no pass at all)
+    wino_pass = (lambda planes: ops.pack_conv_weight_wino(w, groups, mode=1, planes=planes)) if offer_wino_pass else None
+    return ops.conv3d_auto([g], ops.ConvWeights(packed, lambda: _wf_weights(w, groups, 3), wino_pass), cin, groups=groups,
+                           family=plan_dgrad)
 
 
 def _conv_forward(meta, weight, bias, shift, scale, residual, mask, segs, need_w):
@@ -115,9 +132,9 @@ def _conv_backward(st, gy, need_w, need_b, need_shift, need_scale, need_res, nee
         desc_w = ops.make_conv_desc([xp], 0, cout, ksize, g, groups=groups) if xp is not None else desc
         if has_bias and need_b and st["plan"].bias_in_wgrad:   # the bias gradient rides along in the weight-gradient kernel
             desc_w.bias_scale = bias_scale
-            d_w, d_bias = ops.conv3d_wgrad(desc_w, g, tuple(w.shape), want_bias=True)
+            d_w, d_bias = ops.conv3d_wgrad(desc_w, g, tuple(w.shape), want_bias=True, family=st["plan"].wgrad)
         else:
-            d_w = ops.conv3d_wgrad(desc_w, g, tuple(w.shape))
+            d_w = ops.conv3d_wgrad(desc_w, g, tuple(w.shape), family=st["plan"].wgrad)
     else:
         d_w = None
     if has_bias and need_b and d_bias is None:
@@ -126,15 +143,7 @@ def _conv_backward(st, gy, need_w, need_b, need_shift, need_scale, need_res, nee
     d_shift = d_scale = None
     d_segs = [None] * len(segs)
     if need_x:
-        dgrad_packed = lambda: st["wp_dgrad"] if st["wp_dgrad"] is not None else ops.pack_conv_weight(w, groups=groups, mode=1)
-        if st["plan"].dgrad == "bf16":     # a 3x3x3 convolution of bf16-rounded g and w, on the inference mode's kernel
-            gp = ops.conv3d([g], _bf16_dgrad_weights(w, groups), cin, 3, groups=groups, math="bf16")
-        elif ksize == 3:     # the data gradient is a 3x3x3 convolution too (a plain input: no pass at all)
-            weights = ops.ConvWeights(dgrad_packed, lambda: _wf_weights(w, groups, 3),
-                                      lambda planes: ops.pack_conv_weight_wino(w, groups, mode=1, planes=planes))
-            gp = ops.conv3d_auto([g], weights, cin, groups=groups, family=st["plan"].dgrad)                # dL/dx'
-        else:
-            gp = ops.conv3d([g], dgrad_packed(), cin, ksize, groups=groups)
+        gp = _data_grad(st["plan"].dgrad, w, groups, g, cin, ksize, st["wp_dgrad"], True)                 # dL/dx'
         plain = not (act or has_shift or has_scale or mask is not None or st["drop"] is not None)
         if plain and len(segs) == 1 and outs is None:      # x' IS x: dL/dx' is the input gradient (no pass to copy it)
             return d_w, d_bias, None, None, d_res, [gp]
@@ -323,18 +332,15 @@ class _ConvLL(torch.autograd.Function):
         go = go.contiguous()
         cout, cin = w.shape[0], w.shape[1]
         g = ops.haar_idwt2d([go], None, None, None, in_scale=ctx.ll_scale)[0]      # adjoint of the scaled LL band
-        d_w = ops.conv3d_wgrad(ops.make_conv_desc([xp], 0, cout, 3, g), g, tuple(w.shape)) if need[1] else None
+        d_w = ops.conv3d_wgrad(ops.make_conv_desc([xp], 0, cout, 3, g), g, tuple(w.shape), family=ctx.plan.wgrad) if need[1] else None
         d_b = ops.channel_sum(go, 2.0 * ctx.ll_scale) if (ctx.has_bias and need[2]) else None
         d_x = None
         if need[3]:
             # dL/dx': a 3x3x3 convolution of the up-sampled gradient -- Winograd along the bands (13.5 multiply-adds per
-            # element; the transposed form of the composed strided convolution would take 12)
-            if ctx.plan.dgrad == "bf16":
-                gp = ops.conv3d([g], _bf16_dgrad_weights(w, 1), cin, 3, math="bf16")
-            else:
-                pre = ops.PACKED.lookup(w) if ops.PACKED is not None else None
-                wp_t = pre[1] if pre is not None else ops.pack_conv_weight(w, mode=1)
-                gp = ops.conv3d_auto([g], ops.ConvWeights(lambda: wp_t, lambda: _wf_weights(w, 1, 3)), cin, family=ctx.plan.dgrad)
+            # element; the transposed form of the composed strided convolution would take 12).  No transform-pass weights on
+            # offer: routing.train_ll_plan turns a fallback family into a direct one
+            pre = ops.PACKED.lookup(w) if ops.PACKED is not None else None
+            gp = _data_grad(ctx.plan.dgrad, w, 1, g, cin, 3, pre[1] if pre is not None else None, False)
             d_x = torch.empty_like(x)
             ops.conv3d_prologue_bwd(ops.make_conv_desc([x], 0, cout, 3, g, in_act=True), gp, [d_x], [False], False, False)
         return None, d_w, d_b, d_x

@@ -25,21 +25,9 @@ namespace {
 
 using namespace tmdiff;
 
-__device__ __forceinline__ bool tmdiff_aligned16_dev(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 __device__ __forceinline__ float silu_grad(float t) {  // d/dt [t * sigmoid(t)]
   const float s = 1.0f / (1.0f + __expf(-t));
   return s * (1.0f + t * (1.0f - s));
-}
-
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -92,10 +80,7 @@ struct ApplyArgs {
 // x'[b, c, :] = act(x[b, c, :] + shift[b,c]) * scale[b,c] * mask[b,c,:]  -- one (b, c) plane per blockIdx.y
 __global__ void __launch_bounds__(256) prologue_apply_kernel(const ApplyArgs a) {
   const int bc = blockIdx.y, b = bc / a.Cin, c = bc % a.Cin;
-  int cs = c, seg = 0;
-  if (a.nseg > 1 && cs >= a.seg_c[0]) { cs -= a.seg_c[0]; seg = 1; }
-  if (seg == 1 && a.nseg > 2 && cs >= a.seg_c[1]) { cs -= a.seg_c[1]; seg = 2; }
-  const int segc = seg == 0 ? a.seg_c[0] : (seg == 1 ? a.seg_c[1] : a.seg_c[2]);
+  TMDIFF_SEGMENT_OF(a, c, seg, cs, segc);
   const float* xs = (seg == 0 ? a.seg_x[0] : (seg == 1 ? a.seg_x[1] : a.seg_x[2])) + ((long)b * segc + cs) * a.plane;
   const float* msk = a.in_mask ? a.in_mask + (long)bc * a.plane : nullptr;
   const float sh = a.in_shift ? a.in_shift[(long)b * a.shift_stride + c] : 0.f;
@@ -104,7 +89,7 @@ __global__ void __launch_bounds__(256) prologue_apply_kernel(const ApplyArgs a) 
   const bool drop = a.drop_inv > 0.f;
   const uint64_t dseed = a.drop_seed + (drop && a.drop_seed_dev ? *a.drop_seed_dev : 0ull);
   const uint64_t ebase = (uint64_t)bc * (uint64_t)a.plane;
-  if ((a.plane & 3) == 0 && tmdiff_aligned16_dev(xs) && tmdiff_aligned16_dev(dst) && (!msk || tmdiff_aligned16_dev(msk))) {
+  if ((a.plane & 3) == 0 && aligned16(xs) && aligned16(dst) && (!msk || aligned16(msk))) {
     for (long i = (blockIdx.x * 256L + threadIdx.x) * 4; i < a.plane; i += 1024L * gridDim.x) {
       const float4 x4 = *reinterpret_cast<const float4*>(xs + i);
       float v[4] = {x4.x, x4.y, x4.z, x4.w};
@@ -372,14 +357,8 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restri
                                                            long total, const float* __restrict__ bias_ws,
                                                            float* __restrict__ dbias, float bias_scale) {
   __shared__ float part[4][64];
-  if (dbias && blockIdx.x == gridDim.x - 1) {   // bias gradient: sum of the per-workgroup partials, slot order
-    const int cout = groups * cout_g;
-    for (int c = threadIdx.x; c < cout; c += 256) {
-      float t = 0.f;
-      for (int k = 0; k < slots; ++k) t += bias_ws[(long)k * cout + c];
-      dbias[c] = bias_scale * t;
-    }
-  }
+  // bias gradient: sum of the per-workgroup partials, slot order
+  if (dbias && blockIdx.x == gridDim.x - 1) finish_bias_grad(bias_ws, slots, groups * cout_g, dbias, bias_scale);
   const long per_slot = (long)groups * taps * cout_g * cin_g;
   const int col = threadIdx.x & 63, row = threadIdx.x >> 6;
   for (long base = blockIdx.x * 64L; base < total; base += 64L * gridDim.x) {
@@ -434,7 +413,7 @@ __global__ void __launch_bounds__(256) channel_sum_kernel(const float* __restric
     }
     for (; i < hi; i += 256) s += p[i];
   }
-  s = block_sum_256(s, red);
+  s = block_sum(s, red);
   if (threadIdx.x == 0) atomicAdd(&out[c], scale * s);
 }
 
@@ -468,10 +447,7 @@ __global__ void __launch_bounds__(256) prologue_bwd_kernel(const PrologueBwdArgs
   const int c = blockIdx.x, b = blockIdx.y, sl = blockIdx.z;
   const float sh = a.in_shift ? a.in_shift[(long)b * a.shift_stride + c] : 0.f;
   const float sc = a.in_scale ? a.in_scale[(long)b * a.scale_stride + c] : 1.f;
-  int cs = c, seg = 0;
-  if (a.nseg > 1 && cs >= a.seg_c[0]) { cs -= a.seg_c[0]; seg = 1; }
-  if (seg == 1 && a.nseg > 2 && cs >= a.seg_c[1]) { cs -= a.seg_c[1]; seg = 2; }
-  const int segc = seg == 0 ? a.seg_c[0] : (seg == 1 ? a.seg_c[1] : a.seg_c[2]);
+  TMDIFF_SEGMENT_OF(a, c, seg, cs, segc);
   const float* xs = (seg == 0 ? a.seg_x[0] : (seg == 1 ? a.seg_x[1] : a.seg_x[2])) + ((long)b * segc + cs) * a.plane;
   float* dxs = seg == 0 ? a.dx[0] : (seg == 1 ? a.dx[1] : a.dx[2]);
   const int accum = seg == 0 ? a.accumulate[0] : (seg == 1 ? a.accumulate[1] : a.accumulate[2]);
@@ -484,8 +460,8 @@ __global__ void __launch_bounds__(256) prologue_bwd_kernel(const PrologueBwdArgs
   const uint64_t dseed = a.drop_seed + (drop && a.drop_seed_dev ? *a.drop_seed_dev : 0ull);
   const uint64_t ebase = ((uint64_t)b * a.Cin + c) * (uint64_t)a.plane;
   // this slice's element range (multiples of 4 when vectorised)
-  const bool vec = (a.plane & 3) == 0 && tmdiff_aligned16_dev(xs) && tmdiff_aligned16_dev(gp) &&
-                   (!dxs || tmdiff_aligned16_dev(dxs)) && (!msk || tmdiff_aligned16_dev(msk)) && (!adds || tmdiff_aligned16_dev(adds));
+  const bool vec = (a.plane & 3) == 0 && aligned16(xs) && aligned16(gp) &&
+                   (!dxs || aligned16(dxs)) && (!msk || aligned16(msk)) && (!adds || aligned16(adds));
   const long unit = vec ? 4 : 1;
   const long units = a.plane / unit;
   const long per = (units + a.slices - 1) / a.slices;
@@ -524,11 +500,11 @@ __global__ void __launch_bounds__(256) prologue_bwd_kernel(const PrologueBwdArgs
   }
   const long oidx = ((long)b * a.Cin + c) * a.slices + sl;
   if (a.d_shift) {
-    const float v = block_sum_256(s_sh, red);
+    const float v = block_sum(s_sh, red);
     if (threadIdx.x == 0) a.d_shift[oidx] = v;
   }
   if (a.d_scale) {
-    const float v = block_sum_256(s_sc, red);
+    const float v = block_sum(s_sc, red);
     if (threadIdx.x == 0) a.d_scale[oidx] = v;
   }
 }
@@ -559,8 +535,8 @@ __global__ void __launch_bounds__(256) stem_bwd_kernel(const float* __restrict__
     sw += gu * x;
     sb += gu;
   }
-  const float tw = block_sum_256(sw, red);
-  const float tb = block_sum_256(sb, red);
+  const float tw = block_sum(sw, red);
+  const float tb = block_sum(sb, red);
   if (threadIdx.x == 0) {
     dwb[((long)b * Cout + co) * 2 + 0] = tw;
     dwb[((long)b * Cout + co) * 2 + 1] = tb;
@@ -610,7 +586,7 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(const float* __restrict__
     s += gp * tmdiff::silu_f(v);
     if (dxs) dxs[p] = gp * wsv * silu_grad(v);
   }
-  const float tot = block_sum_256(s, red);
+  const float tot = block_sum(s, red);
   if (threadIdx.x == 0 && dws) dws[(long)b * C + c] = tot;
 }
 
@@ -681,8 +657,7 @@ __global__ void __launch_bounds__(256) linear_dx_kernel(const float* __restrict_
 struct WgradPlan {
   int taps, nbn, nbh, nbw, tiles_co, tiles_ci, splits, boxes_per_split, slots;
   long total_boxes;
-  bool needs_xp;        // the prologue output (or the concatenation of the segments) is materialised in the workspace
-  size_t partial_floats, bias_floats;
+  WgradWorkspace ws;    // x' in it: the prologue output (or the concatenation of the segments) is materialised
 };
 
 inline WgradPlan plan_wgrad(const tmdiff_conv3d_desc* d) {
@@ -697,22 +672,11 @@ inline WgradPlan plan_wgrad(const tmdiff_conv3d_desc* d) {
   // of K-splits that minimises  rounds x (boxes per workgroup + ~half a box of prologue / partial-sum stores);
   // ties go to the smaller split count (less to reduce).  E.g. 64 tiles x 32 boxes: 4 splits = one round of 8 boxes,
   // where the old "512 workgroups" rule gave 576 workgroups = three rounds of 4.
-  long best_s = 1;
-  double best_cost = 1e30;
-  const long smax = p.total_boxes < 512 ? p.total_boxes : 512;
-  for (long s = 1; s <= smax; ++s) {
-    const long bps = (p.total_boxes + s - 1) / s;
-    const long s_eff = (p.total_boxes + bps - 1) / bps;
-    const long rounds = (tiles * s_eff + 255) / 256;
-    const double cost = (double)rounds * ((double)bps + 0.5);
-    if (cost < best_cost - 1e-9) { best_cost = cost; best_s = s_eff; }
-  }
-  p.boxes_per_split = (int)((p.total_boxes + best_s - 1) / best_s);
-  p.splits = (int)((p.total_boxes + p.boxes_per_split - 1) / p.boxes_per_split);
+  const Splits sp = choose_splits(p.total_boxes, tiles, 256, 0.5, 512);
+  p.boxes_per_split = sp.boxes_per_split;
+  p.splits = sp.splits;
   p.slots = p.splits;          // the waves of a workgroup combine their partials in LDS
-  p.needs_xp = d->nseg > 1 || d->in_shift || d->in_scale || d->in_mask || d->in_act || d->drop_p > 0.f;
-  p.partial_floats = ((size_t)p.slots * d->Cout * cin_g * p.taps + 3) / 4 * 4;
-  p.bias_floats = ((size_t)p.slots * d->Cout + 3) / 4 * 4;
+  p.ws = wgrad_workspace((size_t)p.slots * d->Cout * cin_g * p.taps, (size_t)p.slots * d->Cout, d->nseg > 1 || input_prologue(d), d);
   return p;
 }
 
@@ -747,9 +711,7 @@ extern "C" int tmdiff_conv3d_prologue_fwd(const tmdiff_conv3d_desc* d, float* xp
 
 extern "C" size_t tmdiff_conv3d_wgrad_workspace_bytes(const tmdiff_conv3d_desc* d) {
   if (!d || d->B <= 0 || d->groups <= 0 || (d->ksize != 1 && d->ksize != 3)) return 0;
-  const WgradPlan p = plan_wgrad(d);
-  const size_t xp = p.needs_xp ? (size_t)d->B * d->Cin * d->N * d->H * d->W : 0;
-  return (p.partial_floats + p.bias_floats + xp) * sizeof(float);
+  return plan_wgrad(d).ws.bytes();
 }
 
 extern "C" int tmdiff_conv3d_wgrad(const tmdiff_conv3d_desc* d, const float* g, float* dw, void* workspace,
@@ -781,15 +743,9 @@ extern "C" int tmdiff_conv3d_wgrad_bias(const tmdiff_conv3d_desc* d, const float
   WgradArgs a;
   a.B = d->B; a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout;
   a.groups = d->groups; a.cin_g = d->Cin / d->groups; a.cout_g = d->Cout / d->groups;
-  a.g = g; a.ws = reinterpret_cast<float*>(workspace);
-  a.bias_ws = dbias ? a.ws + p.partial_floats : nullptr;
-  a.xp = d->seg_x[0];
-  if (p.needs_xp) {
-    float* xp = a.ws + p.partial_floats + p.bias_floats;
-    const int rc = launch_prologue_apply(d, xp, st);
-    if (rc) return rc;
-    a.xp = xp;
-  }
+  a.g = g; a.ws = p.ws.partials(workspace);
+  a.bias_ws = dbias ? p.ws.bias(workspace) : nullptr;
+  if (const int rc = p.ws.stage_input(d, workspace, st, &a.xp)) return rc;
   a.nbn = p.nbn; a.nbh = p.nbh; a.nbw = p.nbw; a.tiles_co = p.tiles_co; a.tiles_ci = p.tiles_ci;
   a.splits = p.splits; a.boxes_per_split = p.boxes_per_split; a.total_boxes = p.total_boxes;
   const long blocks = (long)d->groups * p.tiles_co * p.tiles_ci * p.splits;

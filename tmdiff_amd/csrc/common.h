@@ -36,7 +36,7 @@ inline int check_launch(const char* what) {
 
 inline hipStream_t as_stream(tmdiff_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+__host__ __device__ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // Row stride of a per-(sample, channel) shift / scale bank (tmdiff_hip.h): a stride > 0 is used as it is, 0 means dense rows
 // of c channels, a negative stride means one row broadcast over the batch (stride 0).
@@ -165,6 +165,28 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
+// dbias[c] = bias_scale * sum_k part[k * cout + c], k ascending (deterministic): one workgroup of 256 threads finishes the bias
+// gradient from the [slot][cout] partial sums a weight-gradient kernel left in its workspace (backward.hip, wgrad_bf16.hip).
+__device__ __forceinline__ void finish_bias_grad(const float* __restrict__ part, int slots, int cout, float* __restrict__ dbias,
+                                                 float bias_scale) {
+  for (int c = threadIdx.x; c < cout; c += 256) {
+    float t = 0.f;
+    for (int k = 0; k < slots; ++k) t += part[(long)k * cout + c];
+    dbias[c] = bias_scale * t;
+  }
+}
+
+// Channel c of an input that is the concatenation of a.nseg (1..3) segments of a.seg_c[] channels (the kernels that read NCDHW
+// segments plane by plane): declares seg (the segment), cs (the channel inside it) and segc (the segment's channel count).
+// A macro on purpose: every function form tried (reference outputs, a returned struct, scalar arguments) changed the ISA of the
+// kernels that use it (prologue_apply_kernel: 529 - 564 instructions where this text gives 563; branches and single-dword scalar
+// loads in place of selects); expanded as text, the four kernels compile to the instructions they had with the decode written out.
+#define TMDIFF_SEGMENT_OF(a, c, seg, cs, segc)                                     \
+  int cs = (c), seg = 0;                                                           \
+  if ((a).nseg > 1 && cs >= (a).seg_c[0]) { cs -= (a).seg_c[0]; seg = 1; }         \
+  if (seg == 1 && (a).nseg > 2 && cs >= (a).seg_c[1]) { cs -= (a).seg_c[1]; seg = 2; } \
+  const int segc = seg == 0 ? (a).seg_c[0] : (seg == 1 ? (a).seg_c[1] : (a).seg_c[2])
+
 // Dropout keep factor of element `idx` under `seed`: 1/(1-p) with probability 1-p, else 0.  Counter-based (splitmix64
 // finaliser of idx + seed * golden ratio): every kernel that needs the mask recomputes it.  thresh = p * 2^32.
 __device__ __forceinline__ float drop_keep(uint64_t seed, uint64_t idx, uint32_t thresh, float inv_keep) {
@@ -182,6 +204,57 @@ inline uint32_t drop_threshold(float p) {
 // x' = act(x + shift[b,c]) * scale[b,c] * mask of the descriptor's (possibly segmented) input, written densely as
 // [B, Cin, N, H, W] (backward.hip).  Used by the weight-gradient kernel and the staged forward convolution.
 int launch_prologue_apply(const tmdiff_conv3d_desc* d, float* xp, hipStream_t st);
+
+// The input carries a prologue (shift / scale / mask / activation / dropout): x' is not the raw input.  A kernel that reads one
+// dense tensor has x' materialised when this holds -- or, where it cannot walk segments itself, when nseg > 1 (the caller's term).
+inline bool input_prologue(const tmdiff_conv3d_desc* d) {
+  return d->in_shift || d->in_scale || d->in_mask || d->in_act || d->drop_p > 0.f;
+}
+
+// ---- Host path shared by the weight-gradient entry points (backward.hip, wgrad_wino.hip, wgrad_bf16.hip) --------------------
+
+// Split-K over the position boxes of a weight gradient.  `units` workgroups per split, `per_round` of them resident at a time:
+// the split count that minimises  rounds x (boxes per workgroup + overhead)  -- overhead: a workgroup's prologue and
+// partial-sum stores, in boxes -- among 1 .. smax; ties go to the smaller count (less to reduce), and no split is empty.
+struct Splits {
+  int splits, boxes_per_split;
+};
+inline Splits choose_splits(long total_boxes, long units, long per_round, double overhead, long smax) {
+  long best_s = 1;
+  double best_cost = 1e30;
+  if (smax > total_boxes) smax = total_boxes;
+  for (long s = 1; s <= smax; ++s) {
+    const long bps = (total_boxes + s - 1) / s;
+    const long s_eff = (total_boxes + bps - 1) / bps;
+    const long rounds = (units * s_eff + per_round - 1) / per_round;
+    const double cost = (double)rounds * ((double)bps + overhead);
+    if (cost < best_cost - 1e-9) { best_cost = cost; best_s = s_eff; }
+  }
+  Splits r;
+  r.boxes_per_split = (int)((total_boxes + best_s - 1) / best_s);
+  r.splits = (int)((total_boxes + r.boxes_per_split - 1) / r.boxes_per_split);
+  return r;
+}
+
+// Workspace of a weight gradient: [split-K partial sums | bias partials | x'], the first two areas rounded up to 16 bytes; x'
+// [B, Cin, N, H, W] only where the kernel cannot read the first segment as it stands (needs_xp).
+struct WgradWorkspace {
+  size_t partial_floats, bias_floats, xp_floats;
+  size_t bytes() const { return (partial_floats + bias_floats + xp_floats) * sizeof(float); }
+  float* partials(void* ws) const { return static_cast<float*>(ws); }
+  float* bias(void* ws) const { return partials(ws) + partial_floats; }
+  // *src = the dense tensor the kernel reads: the first segment, or x' written into the workspace by the prologue pass
+  int stage_input(const tmdiff_conv3d_desc* d, void* ws, hipStream_t st, const float** src) const {
+    *src = d->seg_x[0];
+    if (!xp_floats) return TMDIFF_OK;
+    float* xp = bias(ws) + bias_floats;
+    *src = xp;
+    return launch_prologue_apply(d, xp, st);
+  }
+};
+inline WgradWorkspace wgrad_workspace(size_t partial_floats, size_t bias_floats, bool needs_xp, const tmdiff_conv3d_desc* d) {
+  return {(partial_floats + 3) / 4 * 4, (bias_floats + 3) / 4 * 4, needs_xp ? (size_t)d->B * d->Cin * d->N * d->H * d->W : 0};
+}
 
 // Tile configuration and split-K factor of a fp32 3x3x3 launch -- one rule for the fused kernel (conv3d.hip), the staged
 // kernel (conv3d_dma.hip) and the workspace query, so that the two kernels always split identically.

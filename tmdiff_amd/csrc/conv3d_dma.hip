@@ -229,9 +229,7 @@ int launch(DmaArgs& a, hipStream_t st) {
   return tmdiff::check_launch("conv3d_fwd_staged");
 }
 
-bool needs_apply(const tmdiff_conv3d_desc* d) {
-  return d->nseg > 1 || d->in_shift || d->in_scale || d->in_mask || d->in_act || d->drop_p > 0.f;
-}
+bool needs_apply(const tmdiff_conv3d_desc* d) { return d->nseg > 1 || tmdiff::input_prologue(d); }
 
 // shapes the staged kernel takes (every production layer); others stay on the fused kernel.  Its 32-bit offsets cover eight
 // channels of a plane (plane * 8 < 2^31); an input that needs the prologue pass adds that pass's grid of B * Cin rows.

@@ -98,10 +98,7 @@ __global__ void __launch_bounds__(256) wino_input_kernel(const WinoInArgs a) {
   using M = WM<NP>;
   constexpr int MO = M::MO;
   const int bc = blockIdx.y, b = bc / a.Cin, c = bc % a.Cin;
-  int cs = c, seg = 0;
-  if (a.nseg > 1 && cs >= a.seg_c[0]) { cs -= a.seg_c[0]; seg = 1; }
-  if (seg == 1 && a.nseg > 2 && cs >= a.seg_c[1]) { cs -= a.seg_c[1]; seg = 2; }
-  const int segc = seg == 0 ? a.seg_c[0] : (seg == 1 ? a.seg_c[1] : a.seg_c[2]);
+  TMDIFF_SEGMENT_OF(a, c, seg, cs, segc);
   const long hw = (long)a.H * a.W;
   const float* xs = (seg == 0 ? a.seg_x[0] : (seg == 1 ? a.seg_x[1] : a.seg_x[2])) + ((long)b * segc + cs) * a.N * hw;
   const float sh = a.in_shift ? a.in_shift[(long)b * a.shift_stride + c] : 0.f;

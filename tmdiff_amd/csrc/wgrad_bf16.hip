@@ -47,8 +47,7 @@ struct WbArgs {
 struct WbPlan {
   int nbh, nbw, tiles_co, tiles_ci, splits, boxes_per_split, slots, bias_slices;
   long total_boxes;
-  bool needs_xp;
-  size_t partial_floats, bias_floats;
+  WgradWorkspace ws;
 };
 
 // eight consecutive columns w0 .. w0 + 7 of a row (NULL row: all zero), columns outside [0, W) zero, as one unit of 8 bf16
@@ -167,13 +166,7 @@ __global__ void __launch_bounds__(256) wgrad_bf16_reduce_kernel(const float* __r
                                                                 int cout_g, int cin_g, long total, const float* __restrict__ bias_part,
                                                                 int bias_slices, int cout, float* __restrict__ dbias,
                                                                 float bias_scale) {
-  if (dbias && blockIdx.x == gridDim.x - 1) {
-    for (int c = threadIdx.x; c < cout; c += 256) {
-      float t = 0.f;
-      for (int k = 0; k < bias_slices; ++k) t += bias_part[(long)k * cout + c];
-      dbias[c] = bias_scale * t;
-    }
-  }
+  if (dbias && blockIdx.x == gridDim.x - 1) finish_bias_grad(bias_part, bias_slices, cout, dbias, bias_scale);
   for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += 256L * gridDim.x) {
     float t = 0.f;
     for (int k = 0; k < slots; ++k) t += ws[(long)k * total + i];
@@ -187,9 +180,7 @@ __global__ void __launch_bounds__(256) wgrad_bf16_reduce_kernel(const float* __r
 }
 
 // x' is not the first segment as it stands: the prologue pass writes it into the workspace first
-bool needs_prologue(const tmdiff_conv3d_desc* d) {
-  return d->nseg > 1 || d->in_shift || d->in_scale || d->in_mask || d->in_act || d->drop_p > 0.f;
-}
+bool needs_xp(const tmdiff_conv3d_desc* d) { return d->nseg > 1 || input_prologue(d); }
 
 // the descriptors the kernel takes (what _supported() answers; the workspace and slot queries give 0 for any other)
 bool shape_ok(const tmdiff_conv3d_desc* d) {
@@ -201,7 +192,7 @@ bool shape_ok(const tmdiff_conv3d_desc* d) {
   const long boxes = (long)d->B * d->N * ((d->H + TH - 1) / TH) * ((d->W + WT - 1) / WT);
   if (boxes >= (1L << 31) || (long)d->N * d->H * d->W * 32 >= (1L << 31)) return false;
   // the prologue pass (launch_prologue_apply) has one grid row per (sample, channel): at most 65535
-  return !(needs_prologue(d) && (long)d->B * d->Cin > 65535);
+  return !(needs_xp(d) && (long)d->B * d->Cin > 65535);
 }
 
 WbPlan plan_wgrad_bf16(const tmdiff_conv3d_desc* d) {
@@ -222,9 +213,7 @@ WbPlan plan_wgrad_bf16(const tmdiff_conv3d_desc* d) {
   const long plane = (long)d->N * d->H * d->W;
   long bs = (plane + 4095) / 4096;
   p.bias_slices = (int)(bs > BIAS_SLICES_MAX ? BIAS_SLICES_MAX : bs);
-  p.needs_xp = needs_prologue(d);
-  p.partial_floats = ((size_t)p.slots * d->Cout * cin_g * 27 + 3) / 4 * 4;
-  p.bias_floats = ((size_t)p.bias_slices * d->Cout + 3) / 4 * 4;
+  p.ws = wgrad_workspace((size_t)p.slots * d->Cout * cin_g * 27, (size_t)p.bias_slices * d->Cout, needs_xp(d), d);
   return p;
 }
 
@@ -236,9 +225,7 @@ extern "C" int tmdiff_conv3d_wgrad_bf16_supported(const tmdiff_conv3d_desc* d) {
 
 extern "C" size_t tmdiff_conv3d_wgrad_bf16_workspace_bytes(const tmdiff_conv3d_desc* d) {
   if (!shape_ok(d)) return 0;
-  const WbPlan p = plan_wgrad_bf16(d);
-  const size_t xp = p.needs_xp ? (size_t)d->B * d->Cin * d->N * d->H * d->W : 0;
-  return (p.partial_floats + p.bias_floats + xp) * sizeof(float);
+  return plan_wgrad_bf16(d).ws.bytes();
 }
 
 extern "C" int32_t tmdiff_conv3d_wgrad_bf16_slots(const tmdiff_conv3d_desc* d) {
@@ -266,14 +253,10 @@ extern "C" int tmdiff_conv3d_wgrad_bf16(const tmdiff_conv3d_desc* d, const float
   WbArgs a;
   a.B = d->B; a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout;
   a.groups = d->groups; a.cin_g = d->Cin / d->groups; a.cout_g = d->Cout / d->groups;
-  a.g = g; a.ws = static_cast<float*>(workspace);
-  float* bias_part = a.ws + p.partial_floats;
-  a.xp = d->seg_x[0];
-  if (p.needs_xp) {   // the pass tmdiff_conv3d_wgrad runs: x' (and the concatenation of the segments) as one dense tensor
-    float* xp = a.ws + p.partial_floats + p.bias_floats;
-    if (const int rc = launch_prologue_apply(d, xp, st)) return rc;
-    a.xp = xp;
-  }
+  a.g = g; a.ws = p.ws.partials(workspace);
+  float* bias_part = p.ws.bias(workspace);
+  // (the pass tmdiff_conv3d_wgrad runs: x', and the concatenation of the segments, as one dense tensor)
+  if (const int rc = p.ws.stage_input(d, workspace, st, &a.xp)) return rc;
   a.nbh = p.nbh; a.nbw = p.nbw; a.tiles_co = p.tiles_co; a.tiles_ci = p.tiles_ci;
   a.splits = p.splits; a.boxes_per_split = p.boxes_per_split; a.total_boxes = p.total_boxes;
   const long blocks = (long)d->groups * p.tiles_co * p.tiles_ci * p.splits;

@@ -79,10 +79,7 @@ __global__ void __launch_bounds__(256) ww_transform_kernel(const WwTransformPair
   {
     const int c = tid >> 3, wq = tid & 7;
     const int cl = cc * 32 + c;                         // channel inside the group
-    int cs = g * a.cg + cl, seg = 0;
-    if (a.nseg > 1 && cs >= a.seg_c[0]) { cs -= a.seg_c[0]; seg = 1; }
-    if (seg == 1 && a.nseg > 2 && cs >= a.seg_c[1]) { cs -= a.seg_c[1]; seg = 2; }
-    const int segc = seg == 0 ? a.seg_c[0] : (seg == 1 ? a.seg_c[1] : a.seg_c[2]);
+    TMDIFF_SEGMENT_OF(a, g * a.cg + cl, seg, cs, segc);
     const float* src = (seg == 0 ? a.seg_x[0] : (seg == 1 ? a.seg_x[1] : a.seg_x[2])) + ((long)b * segc + cs) * a.N * hw + (long)h * a.W;
     const bool c_ok = row_ok && cl < a.cg;
     float bsum = 0.f;        // (bias gradient on the side: this pass reads every element of g exactly once)
@@ -397,8 +394,8 @@ struct WwPlan {
   int T, bw;                 // band tiles; box width (16, or 8 for planes of at most 8 columns)
   int Hb, Wb, CiP, CoP, Q;
   int tiles_co, tiles_ci, nbh, nbw, nboxes, splits, bps;
-  bool needs_xp;
-  size_t xh_floats, gh_floats, part_floats, bias_floats, xp_floats;
+  size_t xh_floats, gh_floats;
+  WgradWorkspace tail;       // behind x^ and g^: partial sums | the g^ pass's bias sums | x' (prologue / mask / dropout)
   int nbias;                 // workgroups of the g^ pass per channel chunk
 };
 
@@ -423,26 +420,15 @@ WwPlan ww_plan(const tmdiff_conv3d_desc* d) {
   p.nboxes = p.Q * p.nbh * p.nbw;
   // two workgroups per CU are resident: rounds of 512.  The split count that minimises rounds x (boxes per workgroup + one
   // box's worth of prologue and partial-sum stores); ties go to fewer splits (less to reduce).
-  const long units = (long)d->groups * p.tiles_co * p.tiles_ci * 6;
-  long best_s = 1;
-  double best_cost = 1e30;
-  const long smax = p.nboxes < 256 ? p.nboxes : 256;
-  for (long s = 1; s <= smax; ++s) {
-    const long bps = (p.nboxes + s - 1) / s;
-    const long s_eff = (p.nboxes + bps - 1) / bps;
-    const long rounds = (units * s_eff + 511) / 512;
-    const double cost = (double)rounds * ((double)bps + 1.0);
-    if (cost < best_cost - 1e-9) { best_cost = cost; best_s = s_eff; }
-  }
-  p.bps = (int)((p.nboxes + best_s - 1) / best_s);
-  p.splits = (p.nboxes + p.bps - 1) / p.bps;
-  p.needs_xp = d->in_shift || d->in_scale || d->in_mask || d->in_act || d->drop_p > 0.f;
+  const Splits sp = choose_splits(p.nboxes, (long)d->groups * p.tiles_co * p.tiles_ci * 6, 512, 1.0, 256);
+  p.bps = sp.boxes_per_split;
+  p.splits = sp.splits;
   p.xh_floats = (size_t)d->groups * 6 * p.Q * (p.Hb + 2) * (p.Wb + 2) * p.CiP;
   p.gh_floats = (size_t)d->groups * 6 * p.Q * p.Hb * p.Wb * p.CoP;
-  p.part_floats = (size_t)p.splits * d->groups * 54 * p.CoP * p.CiP;
   p.nbias = p.Hb * d->B * p.T * ((d->W + TR_W - 1) / TR_W);
-  p.bias_floats = (size_t)p.nbias * d->groups * p.CoP;
-  p.xp_floats = p.needs_xp ? ((size_t)d->B * d->Cin * d->N * d->H * d->W + 3) / 4 * 4 : 0;
+  // (the transform pass walks the segments itself: x' only for a prologue.  Every area is a whole number of 16-byte units:
+  //  CoP, CiP are multiples of 32 and W is one of 4)
+  p.tail = wgrad_workspace((size_t)p.splits * d->groups * 54 * p.CoP * p.CiP, (size_t)p.nbias * d->groups * p.CoP, input_prologue(d), d);
   return p;
 }
 
@@ -484,7 +470,7 @@ extern "C" int tmdiff_conv3d_wgrad_wino_supported(const tmdiff_conv3d_desc* d) {
 extern "C" size_t tmdiff_conv3d_wgrad_wino_workspace_bytes(const tmdiff_conv3d_desc* d) {
   if (!ww_shape_ok(d)) return 0;
   const WwPlan p = ww_plan(d);
-  return (p.xh_floats + p.gh_floats + p.part_floats + p.bias_floats + p.xp_floats) * sizeof(float);
+  return (p.xh_floats + p.gh_floats) * sizeof(float) + p.tail.bytes();
 }
 
 extern "C" int tmdiff_conv3d_wgrad_wino(const tmdiff_conv3d_desc* d, const float* g, float* dw, void* workspace,
@@ -507,16 +493,14 @@ extern "C" int tmdiff_conv3d_wgrad_wino_bias(const tmdiff_conv3d_desc* d, const 
   float* xh = static_cast<float*>(workspace);
   float* gh = xh + p.xh_floats;
   float* part = gh + p.gh_floats;
-  float* bias_part = part + p.part_floats;
-  float* xp = bias_part + p.bias_floats;
+  float* bias_part = p.tail.bias(part);
 
   const float* segs[3] = {d->seg_x[0], d->seg_x[1], d->seg_x[2]};
   int segc[3] = {d->seg_c[0], d->seg_c[1], d->seg_c[2]};
   int nseg = d->nseg;
-  if (p.needs_xp) {       // prologue / mask / dropout: x' first (the finetune path keeps x' from the forward and never gets here)
-    const int rc = launch_prologue_apply(d, xp, st);
-    if (rc) return rc;
-    segs[0] = xp; segc[0] = d->Cin; nseg = 1;
+  if (p.tail.xp_floats) {   // prologue / mask / dropout: x' first (the finetune path keeps x' from the forward and never gets here)
+    if (const int rc = p.tail.stage_input(d, part, st, &segs[0])) return rc;
+    segc[0] = d->Cin; nseg = 1;
   }
   // (timing experiments: TMDIFF_WW_PHASES = bit mask of the phases that run -- 1 transform passes, 2 accumulation, 4 reduction;
   //  anything but 7 leaves dw wrong or stale)

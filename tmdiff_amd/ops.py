@@ -1325,30 +1325,32 @@ def wgrad_wino_takes(desc):
                                 **({"x_bf16": 1} if desc.x_bf16 else {})) == "wino"
 
 
-def conv3d_wgrad(desc, g, weight_shape, want_bias=False):
-    """dL/dw [Cout, Cin/g, k,k,k] for the convolution described by `desc` (a filled Conv3dDesc) given g = dL/dy; with
-    want_bias also dL/dbias = desc.bias_scale * sum_{b,pos} g, accumulated inside the same kernel: returns (dw, dbias)."""
+def _wgrad(entry, workspace_query, desc, g, weight_shape, want_bias, count_key, flops):
+    """The host path of every weight-gradient kernel: dw (with want_bias: (dw, db)) from lib.<entry>(desc, g, dw, db or NULL,
+    workspace, stream) on a workspace of lib.<workspace_query>(desc) bytes; counted as count_key with `flops` executed FLOPs."""
     dw = torch.empty(weight_shape, device=g.device, dtype=torch.float32)
-    if wgrad_wino_takes(desc):
+    _count(count_key, flops)
+    ws = _workspace(g.device, max(16, getattr(lib, workspace_query)(C.byref(desc))), "wgrad")
+    db = torch.empty(weight_shape[0], device=g.device, dtype=torch.float32) if want_bias else None
+    check(getattr(lib, entry)(C.byref(desc), _chk(g, "g"), dw.data_ptr(), _chk(db, "db"), ws.data_ptr(), stream_ptr()), count_key)
+    return (dw, db) if want_bias else dw
+
+
+def conv3d_wgrad(desc, g, weight_shape, want_bias=False, family=None):
+    """dL/dw [Cout, Cin/g, k,k,k] for the convolution described by `desc` (a filled Conv3dDesc) given g = dL/dy; with
+    want_bias also dL/dbias = desc.bias_scale * sum_{b,pos} g, accumulated inside the same kernel: returns (dw, dbias).
+    family: "wino" / "direct", the kernel a routing plan has chosen (plan.wgrad); None asks routing here (wgrad_wino_takes)."""
+    if family is None:
+        family = "wino" if wgrad_wino_takes(desc) else "direct"
+    macs = desc.B * desc.Cout * (desc.Cin // desc.groups) * desc.N * desc.H * desc.W
+    if family == "wino":
         # Winograd F(3,4) along the bands (csrc/wgrad_wino.hip): 13.5 executed multiply-adds per element instead of 27
-        _count("conv3d_wgrad_wino", 2.0 * desc.B * desc.Cout * (desc.Cin // desc.groups) * 13.5 * desc.N * desc.H * desc.W)
-        nbytes = lib.tmdiff_conv3d_wgrad_wino_workspace_bytes(C.byref(desc))
-        ws = _workspace(g.device, max(16, nbytes), "wgrad")
-        db = torch.empty(weight_shape[0], device=g.device, dtype=torch.float32) if want_bias else None
-        check(lib.tmdiff_conv3d_wgrad_wino_bias(C.byref(desc), _chk(g, "g"), dw.data_ptr(), _chk(db, "db"), ws.data_ptr(),
-                                                stream_ptr()), "conv3d_wgrad_wino")
-        return (dw, db) if want_bias else dw
-    _count("conv3d_wgrad", 2.0 * desc.B * desc.Cout * (desc.Cin // desc.groups) * desc.ksize ** 3 * desc.N * desc.H * desc.W)
-    nbytes = lib.tmdiff_conv3d_wgrad_workspace_bytes(C.byref(desc))
-    ws = _workspace(g.device, max(4, nbytes), "wgrad")
-    if not want_bias:
-        check(lib.tmdiff_conv3d_wgrad(C.byref(desc), _chk(g, "g"), dw.data_ptr(), ws.data_ptr(), stream_ptr()),
-              "conv3d_wgrad")
-        return dw
-    db = torch.empty(weight_shape[0], device=g.device, dtype=torch.float32)
-    check(lib.tmdiff_conv3d_wgrad_bias(C.byref(desc), _chk(g, "g"), dw.data_ptr(), db.data_ptr(), ws.data_ptr(),
-                                       stream_ptr()), "conv3d_wgrad_bias")
-    return dw, db
+        return _wgrad("tmdiff_conv3d_wgrad_wino_bias", "tmdiff_conv3d_wgrad_wino_workspace_bytes", desc, g, weight_shape, want_bias,
+                      "conv3d_wgrad_wino", 2.0 * macs * 13.5)
+    if family != "direct":
+        raise ValueError(f"conv3d_wgrad: family={family!r} (wino, direct or None)")
+    return _wgrad("tmdiff_conv3d_wgrad_bias", "tmdiff_conv3d_wgrad_workspace_bytes", desc, g, weight_shape, want_bias,
+                  "conv3d_wgrad", 2.0 * macs * desc.ksize ** 3)
 
 
 def wgrad_bf16_supported(desc):
@@ -1360,14 +1362,8 @@ def conv3d_wgrad_bf16(desc, g, weight_shape, want_bias=False):
     """conv3d_wgrad with bf16 operands: g and the prologue output x' of `desc` rounded to bf16 (nearest even), products summed
     in fp32 (csrc/wgrad_bf16.hip; deterministic).  want_bias: also dL/dbias = desc.bias_scale * sum g of the unrounded g.
     A descriptor the kernel does not take raises (TMDIFF_E_UNSUPPORTED): ask wgrad_bf16_supported / routing first."""
-    dw = torch.empty(weight_shape, device=g.device, dtype=torch.float32)
-    _count("conv3d_wgrad_bf16", 2.0 * desc.B * desc.Cout * (desc.Cin // max(desc.groups, 1)) * 27 * desc.N * desc.H * desc.W)
-    nbytes = lib.tmdiff_conv3d_wgrad_bf16_workspace_bytes(C.byref(desc))
-    ws = _workspace(g.device, max(16, nbytes), "wgrad")
-    db = torch.empty(weight_shape[0], device=g.device, dtype=torch.float32) if want_bias else None
-    check(lib.tmdiff_conv3d_wgrad_bf16(C.byref(desc), _chk(g, "g"), dw.data_ptr(), _chk(db, "db"), ws.data_ptr(), stream_ptr()),
-          "conv3d_wgrad_bf16")
-    return (dw, db) if want_bias else dw
+    return _wgrad("tmdiff_conv3d_wgrad_bf16", "tmdiff_conv3d_wgrad_bf16_workspace_bytes", desc, g, weight_shape, want_bias,
+                  "conv3d_wgrad_bf16", 2.0 * desc.B * desc.Cout * (desc.Cin // max(desc.groups, 1)) * 27 * desc.N * desc.H * desc.W)
 
 
 def channel_sum(x, scale=1.0):
