@@ -664,6 +664,39 @@ int tmdiff_metrics_q2n(const float* x_true, int64_t true_stride_b, int64_t true_
                        tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * The composite finetune loss with its gradient, one pass (csrc/loss.hip; host definition: tmdiff_amd/losses.py):
+ *     L = base(xhat, x0) + w_sam * SAM(x0 + ms, xhat + ms) + w_lap * LAP(xhat - x0)
+ * on dense fp32 [B, C, H, W] tensors.
+ *  base : the mean over B C H W of rho(xhat - x0); base_kind 0 = l1 (|d|), 1 = l2 (d^2), 2 = smooth l1 with beta = 1.
+ *  SAM  : the mean over the B H W pixels of the angle in radians between the band vectors u = x0 + ms and v = xhat + ms,
+ *    formed as atan2(|cross|, dot) with |cross|^2 = |u|^2 |v|^2 - dot^2.  Its gradient with respect to v is
+ *    -(u - (dot / |v|^2) v) / |cross|, a vector of norm 1 / |v|.  A pixel with |u| = 0, |v| = 0 or |cross|^2 <= 0 (u parallel
+ *    to v; every pixel when C == 1) contributes its angle (0; pi for antiparallel vectors) and an exactly zero gradient.
+ *  LAP  : the mean over the B C (H - 2)(W - 2) interior ('valid') pixels of |Lap d|, d = xhat - x0, Lap the 3 x 3 kernel with
+ *    -8 at the centre and 1 on the eight neighbours; its gradient is Lap^T applied to sign(Lap d), sign(0) = 0, taken as 0
+ *    outside the interior.
+ * g (fp32 [B, C, H, W]) receives dL/dxhat, already weighted by w_sam and w_lap and divided by the counts; g == NULL selects
+ * the value-only mode, which writes no gradient.  out64: fp64 [4] = total, base, sam, lap (the unweighted means of the terms,
+ * the weighted total; a term whose weight is 0 is not evaluated and reports 0); out32: the total as one float.  ms may be
+ * NULL only when w_sam == 0.  Weights must be finite and not negative (else TMDIFF_E_INVALID, as for another base_kind).
+ * Every operation after the fp32 loads is fp64 and the gradient is rounded once, at its store (a magnitude past the fp32
+ * range saturates at FLT_MAX: nothing non-finite is stored for finite inputs).  No atomics: each workgroup (one per 16 x 32
+ * tile of one image) stores three fp64 partial sums into `workspace` and one finalize launch adds them in a fixed order, so a
+ * call is reproducible bit for bit.  Nothing is allocated, synchronised or copied: a call can be captured into a graph on
+ * `stream`.  16-byte accesses when W % 4 == 0 and the tensors are 16-byte aligned, scalar ones otherwise, with the same values.
+ * workspace: 8-byte aligned, tmdiff_loss_workspace_bytes(B, C, H, W, lap) = 24 * B * ceil(H / 16) * ceil(W / 32) bytes.
+ * Extents (`lap`: w_lap != 0): B >= 1, 1 <= C <= 16, H, W >= 3 with lap and >= 1 without, B * C * H * W <= 2^31 - 1; for
+ * anything else tmdiff_loss_supported is 0, the workspace size is 0 and the entry point returns TMDIFF_E_UNSUPPORTED without
+ * launching.  (Added within version 6.)
+ * ------------------------------------------------------------------------------------ */
+int tmdiff_loss_supported(int32_t B, int32_t C, int32_t H, int32_t W, int32_t lap);
+size_t tmdiff_loss_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t lap);
+int tmdiff_spectral_spatial_loss(const float* x0, const float* xhat, const float* ms, float* g, int32_t base_kind,
+                                 double w_sam, double w_lap, double* out64, float* out32, void* workspace,
+                                 size_t workspace_bytes, int32_t B, int32_t C, int32_t H, int32_t W,
+                                 tmdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Resampling of full-resolution scenes (csrc/resample.hip; host definitions: tmdiff_amd/metrics.py).  Dense fp32 planes
  * [planes, H, W]; nothing is allocated or synchronised, so a call can be captured into a graph on `stream`.
  *  pyr_down: `levels` (1 or 2) steps of OpenCV's pyrDown with its defaults -- separable [1 4 6 4 1] / 16, horizontal pass then

@@ -202,6 +202,11 @@ SIGNATURES.update({
     "tmdiff_metrics_q2n_workspace_bytes": (C.c_size_t, [C.c_int32] * 6),
     "tmdiff_metrics_q2n": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64] + [C.c_int32] * 6 +
                            [vp, vp, vp, C.c_size_t, vp]),                    # ... block, shift, out, map_out, workspace
+    # composite finetune loss (csrc/loss.hip): x0, xhat, ms, g | base_kind, w_sam, w_lap | out64, out32, workspace, bytes | B, C, H, W
+    "tmdiff_loss_supported": (C.c_int, [C.c_int32] * 5),
+    "tmdiff_loss_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "tmdiff_spectral_spatial_loss": (C.c_int, [vp] * 4 + [C.c_int32, C.c_double, C.c_double, vp, vp, vp, C.c_size_t] +
+                                     [C.c_int32] * 4 + [vp]),
     # resampling (csrc/resample.hip): (planes, H, W, levels | ratio) after the two tensors
     "tmdiff_pyr_down": (C.c_int, [vp, vp] + [C.c_int32] * 4 + [vp]),
     "tmdiff_upsample_bilinear": (C.c_int, [vp, vp] + [C.c_int32] * 4 + [vp]),

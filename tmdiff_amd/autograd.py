@@ -655,3 +655,28 @@ class _Scale(torch.autograd.Function):
 
 def scale(y, s):
     return _Scale.apply(y, float(s))
+
+
+class SpectralSpatialLossFn(torch.autograd.Function):
+    """ops.spectral_spatial_loss as a scalar loss: the forward's one kernel pair writes the value and g = dL/dxhat, which is
+    saved; backward is g * grad_out for xhat alone (x0 and ms get no gradient).  When xhat needs no gradient the forward runs
+    in the value-only mode.  Returns (total float32 [], terms float64 [4]); terms is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, x0, xhat, ms, base, w_sam, w_lap):
+        want = ctx.needs_input_grad[1]
+        terms, total, g = ops.spectral_spatial_loss(x0.contiguous(), xhat.contiguous(), None if ms is None else ms.contiguous(),
+                                                    base, w_sam, w_lap, grad=want)
+        if want:
+            ctx.save_for_backward(g)
+        ctx.mark_non_differentiable(terms)
+        return total, terms
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_terms):
+        g, = ctx.saved_tensors
+        return None, g * grad_out, None, None, None, None
+
+
+def spectral_spatial_loss(x0, xhat, ms, base="l1", w_sam=0.0, w_lap=0.0):
+    return SpectralSpatialLossFn.apply(x0, xhat, ms, base, float(w_sam), float(w_lap))

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import ops, sample_graph
+from . import losses, ops, sample_graph
 from .dpm_solver import DPM_Solver, NoiseScheduleVP, model_wrapper
 from .util import res2img  # noqa: F401  (re-exported like the reference module does)
 
@@ -47,15 +47,25 @@ class GeneralDiffusion(nn.Module):
     sample_graph_capacity = 2      # captured samplers kept per object (least recently used dropped first)
     sample_graph_captures = 0      # samplers captured so far by this object
 
-    def __init__(self, denoise_fn, loss_type="l1", noise_fn=None):
+    def __init__(self, denoise_fn, loss_type="l1", noise_fn=None, loss_terms=None):
+        """``loss_terms`` (ours, optional): ``{"sam": w, "lap": w}`` adds a spectral-angle and / or a Laplacian term to
+        ``loss_type`` (tmdiff_amd.losses); None or {} keeps the reference's torch loss modules."""
         super().__init__()
         self.denoise_fn = denoise_fn
         self.loss_type = loss_type
         self.noise_fn = noise_fn
+        self.loss_terms = dict(loss_terms) if loss_terms else None
+        if self.loss_terms is not None:
+            losses.parse_loss_terms(self.loss_terms)       # ValueError for an unknown key or a negative weight
 
     # ---- configuration ------------------------------------------------------------------------------
     def set_loss(self, device):
-        if self.loss_type == "l1":
+        if self.loss_terms is not None:
+            if self.loss_type not in losses.BASE_KINDS:
+                raise NotImplementedError()
+            w_sam, w_lap = losses.parse_loss_terms(self.loss_terms)
+            self.loss_func = losses.SpectralSpatialLoss(self.loss_type, w_sam, w_lap).to(device)
+        elif self.loss_type == "l1":
             self.loss_func = nn.L1Loss().to(device)
         elif self.loss_type == "l2":
             self.loss_func = nn.MSELoss().to(device)
@@ -309,8 +319,11 @@ class GeneralDiffusion(nn.Module):
         if a.numel() == 1 and x_start.shape[0] > 1:
             a = a.expand(x_start.shape[0])
         x_noisy = ops.q_sample(x_start, noise.contiguous(), a.contiguous())
+        ms = x_in["MS"].float().contiguous()
         x_recon = self.denoise_fn.forward_train(x_noisy, t_dev.view(x_start.shape[0], -1), x_in["PAN"].float().contiguous(),
-                                                x_in["MS"].float().contiguous(), prompt)
+                                                ms, prompt)
+        if self.loss_terms is not None:                  # the composite loss scores the images x_start + MS, x_recon + MS
+            return self.loss_func(x_start, x_recon, ms)
         return self.loss_func(x_start, x_recon)
 
     def forward(self, x, *args, **kwargs):

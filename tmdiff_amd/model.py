@@ -107,6 +107,7 @@ class CapturedStep:
             if not tr.split_graph:
                 tr.optG.step()
         self.loss = loss.detach()
+        self.terms = getattr(tr.netG.loss_func, "last_terms", None)      # the composite loss's four values: refilled per replay
         self.opt_graph = None
         if tr.split_graph:       # > 1 rank: the gradient exchange runs between two graphs (see DDPM.optimize_parameters)
             self.opt_graph = torch.cuda.CUDAGraph()
@@ -201,7 +202,14 @@ class DDPM(BaseModel):
         self.scheduler.step()
         self.reducer.zero_grad()
         self.log_dict["l_pix"] = l_pix.detach()
+        self._log_loss_terms(getattr(self.netG.loss_func, "last_terms", None))
         self.log_dict["lr"] = self._lr()
+
+    def _log_loss_terms(self, terms):
+        """l_base, l_sam, l_lap beside l_pix when the composite loss is on (losses.SpectralSpatialLoss.last_terms: a float64 [4]
+        device tensor; its entries are logged as device scalars, read by whoever prints the log)."""
+        if terms is not None:
+            self.log_dict["l_base"], self.log_dict["l_sam"], self.log_dict["l_lap"] = terms[1], terms[2], terms[3]
 
     def _optimize_captured(self, prompt):
         """The same step from a HIP graph (CapturedStep).  The first GRAPH_WARMUP steps of every (prompt, batch shape) run
@@ -229,6 +237,7 @@ class DDPM(BaseModel):
                 self._optimizer_step()
                 self.scheduler.step()
                 self.log_dict["l_pix"], self.log_dict["lr"] = l_pix.detach(), self._lr()
+                self._log_loss_terms(getattr(self.netG.loss_func, "last_terms", None))
                 return
             step = CapturedStep(self, self.data, prompt)
             step.load(self.data)
@@ -243,6 +252,7 @@ class DDPM(BaseModel):
         step.replay()
         self.scheduler.step()             # (fills the device learning-rate tensor for the next step)
         self.log_dict["l_pix"], self.log_dict["lr"] = step.loss, self._lr()
+        self._log_loss_terms(step.terms)
 
     def test(self, continous=False, prompt="QB", guidance=3.0):
         self.netG.eval()

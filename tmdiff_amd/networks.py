@@ -2,10 +2,12 @@
 
 Reads the same option keys as the reference -- ``opt['model']['unet']['channel_multiplier']``,
 ``opt['model']['diffusion']['loss_type']``, ``opt['model']['init_type']``, ``opt['phase']``,
-``opt['gpu_ids']``, ``opt['distributed']`` -- plus two optional keys of ours,
+``opt['gpu_ids']``, ``opt['distributed']`` -- plus three optional keys of ours,
 ``opt['model']['text_embeddings']`` (dict or path; default: fixed synthetic vectors, because the CLIP
 weights are not shipped) and ``opt['model']['compute_dtype']`` ("fp32" default | "bf16": bf16-operand convs for
-inference).  Missing keys behave like the reference's ``NoneDict`` (-> None).
+inference), and ``opt['model']['diffusion']['loss_terms']`` (``{"sam": w, "lap": w}``: the opt-in
+composite loss of tmdiff_amd.losses; absent: the reference's loss modules).  Missing keys behave like the reference's
+``NoneDict`` (-> None).
 
 Multi-GPU: the reference wraps the module in single-process ``nn.DataParallel`` (:88-91).  Here the
 unit of parallelism is one process per GPU (``tmdiff_amd.dist``), so with ``distributed`` set the
@@ -88,7 +90,9 @@ def define_General(opt):
                          text_embeddings=_get(model_opt, "text_embeddings"))
     if _get(model_opt, "compute_dtype") is not None:      # ours, optional: "fp32" (default) | "bf16" (inference convs)
         model.set_compute_dtype(_get(model_opt, "compute_dtype"))
-    netG = diffusion.GeneralDiffusion(denoise_fn=model, loss_type=_get(model_opt, "diffusion", "loss_type"))
+    # ours, optional: model.diffusion.loss_terms = {"sam": w, "lap": w} adds the spectral-angle / Laplacian terms (tmdiff_amd.losses)
+    netG = diffusion.GeneralDiffusion(denoise_fn=model, loss_type=_get(model_opt, "diffusion", "loss_type"),
+                                      loss_terms=_get(model_opt, "diffusion", "loss_terms"))
     if _get(opt, "phase") == "train":
         init_weights(netG, init_type=_get(model_opt, "init_type"))
     if _get(opt, "gpu_ids") and _get(opt, "distributed"):

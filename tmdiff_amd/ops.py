@@ -1198,6 +1198,60 @@ def metrics_noref(l_ms, pan, l_pan, ps, out=None, workspace=None):
     return y
 
 
+# ---- composite finetune loss (csrc/loss.hip; definition: tmdiff_amd/losses.py) ---------------------------------------
+LOSS_BASE_KINDS = {"l1": 0, "l2": 1, "smooth_l1": 2}
+_LOSS_LIMITS = "B >= 1, 1 <= C <= 16, H, W >= 3 with a Laplacian term and >= 1 without, fewer than 2^31 elements"
+
+
+def loss_supported(b, c, h, w, lap=True):
+    """True when spectral_spatial_loss takes [b, c, h, w] tensors (`lap`: with a Laplacian term)."""
+    return bool(lib.tmdiff_loss_supported(int(b), int(c), int(h), int(w), int(bool(lap))))
+
+
+def spectral_spatial_loss(x0, xhat, ms=None, base="l1", w_sam=0.0, w_lap=0.0, grad=True, terms=None, total=None, workspace=None):
+    """base(xhat, x0) + w_sam * SAM(x0 + ms, xhat + ms) + w_lap * LAP(xhat - x0) of float32 [B, C, H, W] tensors, two launches.
+    Returns (terms, total, g): terms float64 [4] = total, base, sam, lap (unweighted means; a term of weight 0 reports 0), total
+    float32 [], and g = dL/dxhat (float32, the shape of xhat).  `grad`: True allocates g, a tensor receives it, False selects the
+    value-only mode (g is None, nothing is written).  ms may be None only when w_sam == 0."""
+    if base not in LOSS_BASE_KINDS:
+        raise ValueError(f"spectral_spatial_loss: base {base!r}, need one of {sorted(LOSS_BASE_KINDS)}")
+    w_sam, w_lap = float(w_sam), float(w_lap)
+    if not (0.0 <= w_sam < float("inf") and 0.0 <= w_lap < float("inf")):
+        raise ValueError(f"spectral_spatial_loss: weights must be finite and not negative, got w_sam={w_sam}, w_lap={w_lap}")
+    if ms is None and w_sam != 0.0:
+        raise ValueError("spectral_spatial_loss: ms is needed when w_sam != 0")
+    if x0.dim() != 4 or x0.shape != xhat.shape or (ms is not None and ms.shape != x0.shape):
+        raise ValueError(f"spectral_spatial_loss: need three [B, C, H, W] tensors of one shape, got {tuple(x0.shape)}, "
+                         f"{tuple(xhat.shape)}, {None if ms is None else tuple(ms.shape)}")
+    b, c, h, w = x0.shape
+    lap = w_lap != 0.0
+    if not loss_supported(b, c, h, w, lap):
+        raise ValueError(f"spectral_spatial_loss: B={b} C={c} H={h} W={w} is not supported ({_LOSS_LIMITS})")
+    px, ph, pm = _chk(x0, "x0"), _chk(xhat, "xhat"), _chk(ms, "ms")
+    dev = x0.device
+    g = None
+    if grad is not False and grad is not None:
+        g = torch.empty_like(xhat) if grad is True else grad
+        if g.shape != xhat.shape:
+            raise ValueError(f"spectral_spatial_loss: g {tuple(g.shape)}, need {tuple(xhat.shape)}")
+    y = terms if terms is not None else torch.empty(4, device=dev, dtype=torch.float64)
+    if not (y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and y.numel() == 4):
+        raise ValueError("spectral_spatial_loss: terms must be a contiguous float64 [4] tensor on the GPU")
+    y32 = total if total is not None else torch.empty((), device=dev, dtype=torch.float32)
+    if y32.numel() != 1:
+        raise ValueError("spectral_spatial_loss: total must hold one float32")
+    need = lib.tmdiff_loss_workspace_bytes(b, c, h, w, int(lap))
+    ws = workspace if workspace is not None else _workspace(dev, need, "loss")
+    nbytes = ws.numel() * ws.element_size()
+    if not (ws.is_cuda and ws.is_contiguous() and nbytes >= need):
+        raise ValueError(f"spectral_spatial_loss: workspace of {nbytes} bytes, need {need}")
+    check(lib.tmdiff_spectral_spatial_loss(px, ph, pm, _chk(g, "g"), LOSS_BASE_KINDS[base], w_sam, w_lap, y.data_ptr(),
+                                           _chk(y32, "total"), ws.data_ptr(), nbytes, b, c, h, w, stream_ptr()),
+          "spectral_spatial_loss")
+    _count("spectral_spatial_loss")
+    return y, y32, g
+
+
 _Q2N_LIMITS = "1 <= C <= 16, block 8, 16 or 32, 1 <= shift <= block, mirror padding no longer than the axis, fewer than 2^31 elements"
 
 

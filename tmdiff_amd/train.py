@@ -98,6 +98,8 @@ def main(argv=None):
     ap.add_argument("--root", type=str, default="experiments", help="where the run directory is created")
     ap.add_argument("--max-iter", type=int, default=None, help="override opt['train']['max_iter']")
     ap.add_argument("--grad-compute", type=str, choices=["fp32", "bf16"], default=None, help="override opt['train']['grad_compute']")
+    ap.add_argument("--sam-weight", type=float, default=None, help="override opt['model']['diffusion']['loss_terms']['sam']")
+    ap.add_argument("--lap-weight", type=float, default=None, help="override opt['model']['diffusion']['loss_terms']['lap']")
     args = ap.parse_args(argv)
 
     world = tdist.init_from_env()
@@ -107,6 +109,11 @@ def main(argv=None):
     opt = Config.parse(args.config, args.phase, args.gpu_ids, args.debug, root=args.root, make_dirs=rank == 0)
     if args.grad_compute is not None:
         opt["train"]["grad_compute"] = args.grad_compute
+    for key, weight in (("sam", args.sam_weight), ("lap", args.lap_weight)):
+        if weight is not None:           # (GeneralDiffusion refuses a negative weight)
+            terms = dict(opt["model"]["diffusion"]["loss_terms"] or {})
+            terms[key] = weight
+            opt["model"]["diffusion"]["loss_terms"] = terms
     logging.basicConfig(level=logging.INFO if rank == 0 else logging.WARNING, format="%(asctime)s %(message)s")
     logger = logging.getLogger("base")
     logger.info(Config.dict2str(opt))
