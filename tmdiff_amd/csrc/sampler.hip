@@ -3,8 +3,9 @@
 //   (per-sample |x| quantile by radix select), q_sample, add.
 // Reference: GeneralModel/diffusion_general.py:134-138, :192-208, :341-347, :376-378;
 //            core/dpm_solver_pytorch.py:302-306, :430-456, :563-927; utils/util.py:135-142.
-// Arithmetic uses explicit round-to-nearest mul/add (no FMA contraction) in the reference's
-// evaluation order, so a step differs from the PyTorch CPU path only through eps itself.
+// Arithmetic is in the reference's evaluation order with every product rounded on its own (mul_rounded below: no FMA
+// contraction), so a step differs from the PyTorch CPU path only through eps itself.  The one exception is axpby, whose
+// accumulation is an explicit fma per term (see axpby_kernel).
 #include <initializer_list>
 
 #include "common.h"
@@ -16,16 +17,26 @@ inline int grid_for(long nvec) {
   return (int)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks));
 }
 
+// a * b rounded to fp32 on its own.  __fmul_rn is a plain product to the compiler, which contracts it into the add or subtract
+// that consumes it (v_fma_f32 / v_pk_fma_f32) -- and not alike in the 16-byte and the scalar loop of one kernel.  A product
+// formed under this pragma stays a product.  Every product of the elementwise kernels (axpby's fma apart) and of the AdamW
+// update below goes through here: each expression is mul, mul, add as PyTorch evaluates the reference's, an aligned and an
+// unaligned tensor get the same bits, and the gradient-scaled AdamW step is the plain step on g * coef bit for bit.
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 struct DdpmCoef {
   float c_recip, c_recipm1, coef1, coef2, sigma;
   int clip;
 };
 
 __device__ __forceinline__ float ddpm_one(float x, float e, float nz, const DdpmCoef& k) {
-  float x0 = __fsub_rn(__fmul_rn(k.c_recip, x), __fmul_rn(k.c_recipm1, e));  // predict_start_from_noise
-  if (k.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);                              // clamp_(-1, 1)
-  const float mean = __fadd_rn(__fmul_rn(k.coef1, x0), __fmul_rn(k.coef2, x));  // q_posterior
-  return __fadd_rn(mean, __fmul_rn(nz, k.sigma));                            // + noise * exp(0.5 logvar)
+  float x0 = __fsub_rn(mul_rounded(k.c_recip, x), mul_rounded(k.c_recipm1, e));     // predict_start_from_noise
+  if (k.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);                                     // clamp_(-1, 1)
+  const float mean = __fadd_rn(mul_rounded(k.coef1, x0), mul_rounded(k.coef2, x));  // q_posterior
+  return __fadd_rn(mean, mul_rounded(nz, k.sigma));                                 // + noise * exp(0.5 logvar)
 }
 
 // One grid-stride pass of the DDPM update (shared by the host-scalar and the device-scalar kernels, so both round
@@ -117,8 +128,11 @@ __global__ void __launch_bounds__(256) axpby_kernel(AxpbyArgs a, float* __restri
         *reinterpret_cast<float4*>(v) = reinterpret_cast<const float4*>(a.in[k])[i];
       else
         v[0] = a.in[k][i];
+      // acc = fma(c_k, v_k, acc): one rounding per term, written out so that it depends on no contraction mode.  The
+      // DPM-Solver updates are built from this kernel, and their ill-conditioned fixtures sit closer to the reference with the
+      // fused sum than with a product rounded on its own.
 #pragma unroll
-      for (int j = 0; j < V; ++j) acc[j] = k == 0 ? __fmul_rn(a.coef[0], v[j]) : __fadd_rn(acc[j], __fmul_rn(a.coef[k], v[j]));
+      for (int j = 0; j < V; ++j) acc[j] = k == 0 ? mul_rounded(a.coef[0], v[j]) : __fmaf_rn(a.coef[k], v[j], acc[j]);
     }
     if constexpr (V == 4)
       reinterpret_cast<float4*>(out)[i] = *reinterpret_cast<float4*>(acc);
@@ -143,12 +157,12 @@ __global__ void __launch_bounds__(256) multi_axpby_kernel(const tmdiff_mt_entry*
     for (long i = lo + threadIdx.x * 4L; i < hi4; i += 1024) {
       const float4 x = *reinterpret_cast<const float4*>(e.a + i), y = *reinterpret_cast<const float4*>(e.b + i);
       *reinterpret_cast<float4*>(e.out + i) =
-          make_float4(__fadd_rn(__fmul_rn(ca, x.x), __fmul_rn(cb, y.x)), __fadd_rn(__fmul_rn(ca, x.y), __fmul_rn(cb, y.y)),
-                      __fadd_rn(__fmul_rn(ca, x.z), __fmul_rn(cb, y.z)), __fadd_rn(__fmul_rn(ca, x.w), __fmul_rn(cb, y.w)));
+          make_float4(__fadd_rn(mul_rounded(ca, x.x), mul_rounded(cb, y.x)), __fadd_rn(mul_rounded(ca, x.y), mul_rounded(cb, y.y)),
+                      __fadd_rn(mul_rounded(ca, x.z), mul_rounded(cb, y.z)), __fadd_rn(mul_rounded(ca, x.w), mul_rounded(cb, y.w)));
     }
-    for (long i = hi4 + threadIdx.x; i < hi; i += 256) e.out[i] = __fadd_rn(__fmul_rn(ca, e.a[i]), __fmul_rn(cb, e.b[i]));
+    for (long i = hi4 + threadIdx.x; i < hi; i += 256) e.out[i] = __fadd_rn(mul_rounded(ca, e.a[i]), mul_rounded(cb, e.b[i]));
   } else {
-    for (long i = lo + threadIdx.x; i < hi; i += 256) e.out[i] = __fadd_rn(__fmul_rn(ca, e.a[i]), __fmul_rn(cb, e.b[i]));
+    for (long i = lo + threadIdx.x; i < hi; i += 256) e.out[i] = __fadd_rn(mul_rounded(ca, e.a[i]), mul_rounded(cb, e.b[i]));
   }
 }
 
@@ -174,18 +188,11 @@ __device__ __forceinline__ AdamwCoef adamw_coef(const float* __restrict__ lr_dev
 
 // the update of ONE element (the only copy: the plain and the gradient-scaled kernel both run it)
 __device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v, const AdamwCoef& k) {
-  p = __fmul_rn(p, k.decay);
-  m = __fadd_rn(m, __fmul_rn(k.w1, __fsub_rn(g, m)));
-  v = __fadd_rn(__fmul_rn(v, k.beta2), __fmul_rn(__fmul_rn(k.w2, g), g));
+  p = mul_rounded(p, k.decay);
+  m = __fadd_rn(m, mul_rounded(k.w1, __fsub_rn(g, m)));
+  v = __fadd_rn(mul_rounded(v, k.beta2), mul_rounded(mul_rounded(k.w2, g), g));
   const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), k.bc2_sqrt), k.eps);
-  p = __fsub_rn(p, __fmul_rn(k.step_size, __fdiv_rn(m, denom)));
-}
-
-// a * b rounded to fp32 on its own: without the pragma the compiler may contract the product into the subtraction that consumes
-// it (__fmul_rn is a plain product to it), and the scaled step would no longer be the plain step on g * coef bit for bit
-__device__ __forceinline__ float mul_rounded(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
+  p = __fsub_rn(p, mul_rounded(k.step_size, __fdiv_rn(m, denom)));
 }
 
 // One chunk of one tensor.  SCALED: the gradient is multiplied by `coef` (one rounding) on its way from memory to the update;
@@ -311,9 +318,9 @@ __global__ void __launch_bounds__(256) x0_kernel(const float* __restrict__ x, co
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       // model_wrapper: x_start output -> noise  (dpm_solver_pytorch.py:304-306)
-      const float eps = is_x_start ? __fdiv_rn(__fsub_rn(xv[j], __fmul_rn(alpha, mv[j])), sigma) : mv[j];
+      const float eps = is_x_start ? __fdiv_rn(__fsub_rn(xv[j], mul_rounded(alpha, mv[j])), sigma) : mv[j];
       // data_prediction_fn: noise -> x0          (:451-453)
-      ov[j] = __fdiv_rn(__fsub_rn(xv[j], __fmul_rn(sigma, eps)), alpha);
+      ov[j] = __fdiv_rn(__fsub_rn(xv[j], mul_rounded(sigma, eps)), alpha);
     }
     if constexpr (V == 4)
       reinterpret_cast<float4*>(x0)[i] = *reinterpret_cast<float4*>(ov);
@@ -328,9 +335,10 @@ __global__ void __launch_bounds__(256) add_kernel(const float* __restrict__ a, c
   for (long i = blockIdx.x * 256L + threadIdx.x; i < nvec; i += 256L * gridDim.x) {
     if constexpr (V == 4) {
       const float4 u = reinterpret_cast<const float4*>(a)[i], v = reinterpret_cast<const float4*>(b)[i];
-      reinterpret_cast<float4*>(out)[i] = make_float4(u.x + sign_b * v.x, u.y + sign_b * v.y, u.z + sign_b * v.z, u.w + sign_b * v.w);
+      reinterpret_cast<float4*>(out)[i] = make_float4(u.x + mul_rounded(sign_b, v.x), u.y + mul_rounded(sign_b, v.y),
+                                                      u.z + mul_rounded(sign_b, v.z), u.w + mul_rounded(sign_b, v.w));
     } else {
-      out[i] = a[i] + sign_b * b[i];
+      out[i] = a[i] + mul_rounded(sign_b, b[i]);
     }
   }
 }
@@ -340,10 +348,10 @@ __global__ void __launch_bounds__(256) q_sample_kernel(const float* __restrict__
                                                        long n_per) {
   const int b = blockIdx.y;
   const float ab = a[b];
-  const float sb = sqrtf(__fsub_rn(1.f, __fmul_rn(ab, ab)));  // (1 - a**2).sqrt()
+  const float sb = sqrtf(__fsub_rn(1.f, mul_rounded(ab, ab)));  // (1 - a**2).sqrt()
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n_per; i += 256L * gridDim.x) {
     const long o = (long)b * n_per + i;
-    out[o] = __fadd_rn(__fmul_rn(ab, x0[o]), __fmul_rn(sb, noise[o]));
+    out[o] = __fadd_rn(mul_rounded(ab, x0[o]), mul_rounded(sb, noise[o]));
   }
 }
 

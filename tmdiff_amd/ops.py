@@ -1005,11 +1005,12 @@ def ddpm_step_dev(x, eps, noise, step, coef, ms=None, out=None, frames=None, fra
 
 
 def sampler_tick(step, time_in, set_to=-1):
-    """step[0] = set_to (>= 0) or step[0] - 1; then time_in[:] = step[0] + 1 (fp32), on the device."""
+    """step[0] = set_to (>= 0) or step[0] - 1; then time_in[:] = step[0] + 1 (fp32), on the device.  time_in may be None
+    (no time input to write: only the step word moves)."""
     if step.dtype != torch.int32 or not step.is_cuda:
         raise ValueError("sampler_tick: step must be an int32 device word")
-    check(lib.tmdiff_sampler_tick(step.data_ptr(), _chk(time_in, "time_in"), time_in.numel(), int(set_to), stream_ptr()),
-          "sampler_tick")
+    check(lib.tmdiff_sampler_tick(step.data_ptr(), _chk(time_in, "time_in"), 0 if time_in is None else time_in.numel(),
+                                  int(set_to), stream_ptr()), "sampler_tick")
 
 
 def axpby(tensors, coefs, out=None):
@@ -1032,6 +1033,10 @@ class MultiAxpby:
                 _chk(t, "multi_axpby tensor")
             if not (o.numel() == a.numel() == b.numel()):
                 raise ValueError("multi_axpby: out / a / b sizes differ")
+        if not triples:                    # nothing but empty tensors: no tables, run() launches nothing
+            self.key, self.n_chunks, self._keep = (), 0, []
+            self.entries = self.chunk_tensor = self.chunk_index = None
+            return
         dev = triples[0][0].device
         self.key = tuple(t.data_ptr() for tr in triples for t in tr)
         chunk = lib.tmdiff_multi_axpby_chunk()
@@ -1051,6 +1056,8 @@ class MultiAxpby:
         return self.key != tuple(t.data_ptr() for tr in triples for t in tr if tr[0].numel() > 0)
 
     def run(self, ca, cb):
+        if self.n_chunks == 0:
+            return
         check(lib.tmdiff_multi_axpby(self.entries.data_ptr(), self.chunk_tensor.data_ptr(), self.chunk_index.data_ptr(),
                                      self.n_chunks, float(ca), float(cb), stream_ptr()), "multi_axpby")
 
