@@ -158,6 +158,58 @@ def test_active_clip_is_the_plain_step_on_scaled_gradients():
     assert pa[-1].grad is None and "exp_avg" not in oa.state.get(pa[-1], {})        # the gradient-free parameter is ignored
 
 
+def test_clipped_step_with_one_misaligned_gradient_between_guards():
+    """Three parameters of 5, chunk and chunk + 5 elements; the middle one's gradient alone starts one float past a 16-byte
+    boundary (so that tensor takes the scalar walk in the norm and in the step while its parameter and moments are aligned).
+    Every parameter, gradient and moment sits between sentinels.  The norm is within 2^-23 of fp64 (as in
+    test_norm_matches_fp64_on_the_host), two clipped steps equal the plain steps on g * coef bit for bit, and no store lands
+    outside a tensor or in a gradient."""
+    sentinel, front, back = 12345.0, 4, 64
+    sizes = (5, _chunk(), _chunk() + 5)
+    gen = torch.Generator().manual_seed(91)
+    p0 = [torch.randn(n, generator=gen) for n in sizes]
+    g0 = [torch.randn(n, generator=gen) for n in sizes]
+    want = math.sqrt(sum(float(g.double().square().sum()) for g in g0))
+
+    def build(**kw):
+        bufs = []
+
+        def put(values, off=0):
+            lo = front + off
+            buf = torch.full((lo + values.numel() + back,), sentinel, device="cuda")
+            view = buf[lo:lo + values.numel()]
+            view.copy_(values)
+            assert view.data_ptr() % 16 == 4 * off and view.is_contiguous()
+            bufs.append((buf, lo, values.numel()))
+            return view
+        params = [torch.nn.Parameter(put(v)) for v in p0]
+        opt = fused(params, **kw)
+        for k, (q, g) in enumerate(zip(params, g0)):
+            q.grad = put(g, 1 if k == 1 else 0)
+            opt.state[q]["exp_avg"], opt.state[q]["exp_avg_sq"] = put(torch.zeros_like(g)), put(torch.zeros_like(g))
+        assert params[1].data_ptr() % 16 == 0 and params[1].grad.data_ptr() % 16 == 4
+        return params, opt, bufs
+    pa, oa, bufs_a = build(max_grad_norm=0.5 * want)
+    pb, ob, bufs_b = build()
+    for it in range(2):                          # the second step starts from moments that are not zero
+        oa.step()
+        got, coef = float(oa.last_grad_norm), oa.last_clip_coef.clone()
+        print(f"step {it}: norm {got!r}, fp64 {want!r}, relative error {abs(got - want) / want:.3e}, coefficient {float(coef)!r}")
+        assert abs(got - want) <= 2.0 ** -23 * want
+        assert float(oa.last_step_ok) == 1.0 and 0.0 < float(coef) < 1.0
+        for q, g in zip(pa, g0):
+            assert torch.equal(bits(q.grad), bits(g.cuda())), "the clipped step wrote to a gradient"
+        for q, g in zip(pb, g0):
+            q.grad.copy_(g)
+            q.grad.mul_(coef)
+        ob.step()
+        same_state(oa, pa, ob, pb, f"step {it}")
+    torch.cuda.synchronize()
+    for buf, lo, n in bufs_a + bufs_b:
+        assert bool((buf[:lo] == sentinel).all()), "a store landed in front of a tensor"
+        assert bool((buf[lo + n:] == sentinel).all()), "a store landed past the end of a tensor"
+
+
 # ---- against torch ----------------------------------------------------------------------------------------------------------------
 def _torch_reference(params, groups, max_norm, grad_sets):
     """clip_grad_norm_(max_norm) + torch.optim.AdamW in fp64 on the CPU; `groups`: (index list, lr, weight_decay)"""

@@ -98,6 +98,28 @@ def test_fused_adamw_options_are_constructor_arguments_only():
     assert clip.state_dict() == plain.state_dict()                   # neither option is saved
 
 
+def test_chunk_tables_of_the_multi_tensor_kernels():
+    """ops.chunk_tables, the one builder behind MultiAxpby and FusedAdamW: chunk -> (tensor, index within it) at the sizes
+    around the chunk, and the entry bytes in both layouts (tmdiff_mt_entry: 4 x int64; tmdiff_adamw_entry: "<QQQQq")."""
+    import struct
+    from tmdiff_amd import ops
+    from tmdiff_amd._lib import lib
+    c = lib.tmdiff_multi_axpby_chunk()
+    sizes = [1, c - 1, c, c + 1, 2 * c + 5]
+    top = (1 << 63) - 16                                   # pointers up to the top of the positive int64 range
+    mt = [(0x7F0000001000 + 64 * k, top - 64 * k, 0x10 + k, n) for k, n in enumerate(sizes)]
+    adamw = [(0x7F0000001000 + 64 * k, 0x7E0000000004 + 64 * k, top - 64 * k, 0x20 + k, n) for k, n in enumerate(sizes)]
+    for rows, fmt in ((mt, "<qqqq"), (adamw, "<QQQQq")):
+        entries, chunk_tensor, chunk_index, n_chunks, host = ops.chunk_tables(rows, sizes, "cpu", pinned=False)
+        assert host is None and n_chunks == 8
+        assert chunk_tensor.dtype == chunk_index.dtype == torch.int32
+        assert chunk_tensor.tolist() == [0, 1, 2, 3, 3, 4, 4, 4]
+        assert chunk_index.tolist() == [0, 0, 0, 0, 1, 0, 1, 2]
+        assert entries.numpy().tobytes() == b"".join(struct.pack(fmt, *row) for row in rows)
+    entries, chunk_tensor, chunk_index, n_chunks, _ = ops.chunk_tables([], [], "cpu", pinned=False)
+    assert n_chunks == 0 and entries.numel() == chunk_tensor.numel() == chunk_index.numel() == 0
+
+
 # ---- the trainer on the torch.optim.AdamW path (CPU) -------------------------------------------------------------------------
 def _opt(**train):
     return {"phase": "train", "gpu_ids": None, "distributed": False, "path": {"resume": None},

@@ -165,6 +165,21 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
+// The same in double (the gradient norm of sampler.hip, the sums of loss.hip and metrics.hip): the butterfly, then the four wave
+// totals in index order.  No leading barrier: red is written once per kernel.
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
 // dbias[c] = bias_scale * sum_k part[k * cout + c], k ascending (deterministic): one workgroup of 256 threads finishes the bias
 // gradient from the [slot][cout] partial sums a weight-gradient kernel left in its workspace (backward.hip, wgrad_bf16.hip).
 __device__ __forceinline__ void finish_bias_grad(const float* __restrict__ part, int slots, int cout, float* __restrict__ dbias,

@@ -47,12 +47,6 @@ struct LossArgs {
   double* part;        // [workgroups][3]: sum rho, sum angle, sum |Lap d|
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 // the lane's four pixels of one plane (zeros outside the image)
 __device__ __forceinline__ void load_quad(const float* __restrict__ p, long off, int gx, int W, bool row_in, bool vec, float (&v)[4]) {
   v[0] = v[1] = v[2] = v[3] = 0.f;
@@ -217,7 +211,7 @@ __global__ void __launch_bounds__(NT) loss_kernel(LossArgs p) {
     }
   }
 
-  const double w0 = wave_sum(s_base), w1 = wave_sum(s_sam), w2 = wave_sum(s_lap);
+  const double w0 = tmdiff::wave_sum(s_base), w1 = tmdiff::wave_sum(s_sam), w2 = tmdiff::wave_sum(s_lap);
   if ((t & 63) == 0) red[t >> 6][0] = w0, red[t >> 6][1] = w1, red[t >> 6][2] = w2;
   __syncthreads();
   if (t < 3) p.part[(long)blockIdx.x * 3 + t] = red[0][t] + red[1][t];
@@ -244,7 +238,7 @@ __global__ void __launch_bounds__(FIN_T) loss_finalize_kernel(LossFinalArgs p) {
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    s[k] = wave_sum(s[k]);
+    s[k] = tmdiff::wave_sum(s[k]);
     if ((t & 63) == 0) red[t >> 6][k] = s[k];
   }
   __syncthreads();

@@ -53,11 +53,6 @@ struct PairArgs {
   double* part;     // [B][tiles][pair_np(C)]
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v = fminf(v, __shfl_xor(v, m, 64));
@@ -74,7 +69,7 @@ template <int N>
 __device__ __forceinline__ void waves_to_lds(const double (&v)[N], double (*red)[NBAND + 5], int lane, int wave) {
 #pragma unroll
   for (int k = 0; k < N; ++k) {
-    const double s = wave_sum(v[k]);
+    const double s = tmdiff::wave_sum(v[k]);
     if (lane == 0) red[wave][k] = s;
   }
 }
@@ -569,10 +564,8 @@ __global__ void __launch_bounds__(256) metrics_q2n_finalize_kernel(const double*
   const int t = threadIdx.x, img = blockIdx.x;
   double s = 0.0;
   for (int i = t; i < nblk; i += 256) s += vals[(long)img * nblk + i];
-  s = wave_sum(s);
-  if ((t & 63) == 0) red[t >> 6] = s;
-  __syncthreads();
-  if (t == 0) out[img] = (((red[0] + red[1]) + red[2]) + red[3]) / (double)nblk;
+  s = tmdiff::block_sum_f64(s, red);
+  if (t == 0) out[img] = s / (double)nblk;
 }
 
 // Cayley-Dickson product of two n-vectors (n a power of two; metrics.cd_mul): with p = (a, b), r = (c, d),

@@ -6,15 +6,58 @@
 // Arithmetic is in the reference's evaluation order with every product rounded on its own (mul_rounded below: no FMA
 // contraction), so a step differs from the PyTorch CPU path only through eps itself.  The one exception is axpby, whose
 // accumulation is an explicit fma per term (see axpby_kernel).
+// Two loops carry every kernel but q_sample and the quantile select:
+//   FOR_EACH_VEC / launch_elementwise: the grid-stride pass of the single-tensor kernels (DDPM step, axpby, x0, add), V = 4
+//     floats per lane where every operand is 16-byte aligned and n % 4 == 0, else V = 1; a kernel is its arithmetic on
+//     float[V] operands between load<V> and store<V>.
+//   chunk_of / walk_chunk: the multi-tensor kernels (EMA axpby, AdamW, squared norm): one workgroup per chunk of one tensor,
+//     16 bytes per lane and a scalar tail where the tensor's pointers are aligned, scalar throughout where not.
 #include <initializer_list>
 
 #include "common.h"
 
 namespace {
+using tmdiff::aligned16;
+
+// V consecutive floats at p: one 16-byte access for V = 4 (p 16-byte aligned), one dword for V = 1
+template <int V>
+__device__ __forceinline__ void load(float (&v)[V], const float* p) {
+  if constexpr (V == 4) *reinterpret_cast<float4*>(v) = *reinterpret_cast<const float4*>(p);
+  else v[0] = *p;
+}
+template <int V>
+__device__ __forceinline__ void store(float* p, const float (&v)[V]) {
+  if constexpr (V == 4) *reinterpret_cast<float4*>(p) = *reinterpret_cast<const float4*>(v);
+  else *p = v[0];
+}
+using Vec4 = std::integral_constant<int, 4>;
+using Vec1 = std::integral_constant<int, 1>;
+
+// THE grid-stride loop of the single-tensor kernels over vectors i < nvec (workgroups of 256, grid_for below).  A macro on
+// purpose, as TMDIFF_SEGMENT_OF (common.h): with the body handed to a function (a lambda by reference or by value, a functor)
+// x0_kernel<4> compiled to other instructions (packed products and sums in place of scalar ones); as text, every kernel keeps
+// the instructions it had with the loop written out.
+#define FOR_EACH_VEC(i, nvec) for (long i = blockIdx.x * 256L + threadIdx.x; i < (nvec); i += 256L * gridDim.x)
 
 inline int grid_for(long nvec) {
   long blocks = (nvec + 255) / 256;
   return (int)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks));
+}
+
+inline bool all_aligned(std::initializer_list<const void*> ps, long n) {
+  if (n % 4) return false;
+  for (const void* p : ps)
+    if (p && !aligned16(p)) return false;
+  return true;
+}
+
+// ... and THE launch: launch(Vec4 / Vec1, grid, nvec) starts the kernel's 16-byte instantiation where n % 4 == 0 and every
+// operand that is not NULL is 16-byte aligned, else the scalar one.
+template <class L>
+int launch_elementwise(std::initializer_list<const void*> operands, long n, const char* name, L&& launch) {
+  if (all_aligned(operands, n)) launch(Vec4{}, grid_for(n / 4), n / 4);
+  else launch(Vec1{}, grid_for(n), n);
+  return tmdiff::check_launch(name);
 }
 
 // a * b rounded to fp32 on its own.  __fmul_rn is a plain product to the compiler, which contracts it into the add or subtract
@@ -46,27 +89,19 @@ template <int V>
 __device__ __forceinline__ void ddpm_step_body(const float* x, const float* __restrict__ eps, const float* __restrict__ noise,
                                                const float* __restrict__ ms, float* out, float* __restrict__ img, long nvec,
                                                const DdpmCoef& k) {
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < nvec; i += 256L * gridDim.x) {
+  FOR_EACH_VEC(i, nvec) {
     float xv[V], ev[V], nv[V], mv[V], ov[V];
-    if constexpr (V == 4) {
-      *reinterpret_cast<float4*>(xv) = reinterpret_cast<const float4*>(x)[i];
-      *reinterpret_cast<float4*>(ev) = reinterpret_cast<const float4*>(eps)[i];
-      if (noise) *reinterpret_cast<float4*>(nv) = reinterpret_cast<const float4*>(noise)[i];
-      if (img) *reinterpret_cast<float4*>(mv) = reinterpret_cast<const float4*>(ms)[i];
-    } else {
-      xv[0] = x[i], ev[0] = eps[i];
-      if (noise) nv[0] = noise[i];
-      if (img) mv[0] = ms[i];
-    }
+    load<V>(xv, x + i * V);
+    load<V>(ev, eps + i * V);
+    if (noise) load<V>(nv, noise + i * V);
+    if (img) load<V>(mv, ms + i * V);
 #pragma unroll
     for (int j = 0; j < V; ++j) ov[j] = ddpm_one(xv[j], ev[j], noise ? nv[j] : 0.f, k);
-    if constexpr (V == 4) {
-      reinterpret_cast<float4*>(out)[i] = *reinterpret_cast<float4*>(ov);
-      if (img) reinterpret_cast<float4*>(img)[i] = make_float4(ov[0] + mv[0], ov[1] + mv[1], ov[2] + mv[2], ov[3] + mv[3]);
-    } else {
-      out[i] = ov[0];
-      if (img) img[i] = ov[0] + mv[0];
-    }
+    store<V>(out + i * V, ov);
+    if (!img) continue;
+#pragma unroll
+    for (int j = 0; j < V; ++j) mv[j] = ov[j] + mv[j];
+    store<V>(img + i * V, mv);
   }
 }
 
@@ -118,52 +153,66 @@ struct AxpbyArgs {
 
 template <int V>
 __global__ void __launch_bounds__(256) axpby_kernel(AxpbyArgs a, float* __restrict__ out, long nvec) {
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < nvec; i += 256L * gridDim.x) {
+  FOR_EACH_VEC(i, nvec) {
     float acc[V];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (k >= a.n_in) break;
       float v[V];
-      if constexpr (V == 4)
-        *reinterpret_cast<float4*>(v) = reinterpret_cast<const float4*>(a.in[k])[i];
-      else
-        v[0] = a.in[k][i];
+      load<V>(v, a.in[k] + i * V);
       // acc = fma(c_k, v_k, acc): one rounding per term, written out so that it depends on no contraction mode.  The
       // DPM-Solver updates are built from this kernel, and their ill-conditioned fixtures sit closer to the reference with the
       // fused sum than with a product rounded on its own.
 #pragma unroll
       for (int j = 0; j < V; ++j) acc[j] = k == 0 ? mul_rounded(a.coef[0], v[j]) : __fmaf_rn(a.coef[k], v[j], acc[j]);
     }
-    if constexpr (V == 4)
-      reinterpret_cast<float4*>(out)[i] = *reinterpret_cast<float4*>(acc);
-    else
-      out[i] = acc[0];
+    store<V>(out + i * V, acc);
   }
 }
 
-// Multi-tensor out_t = ca * a_t + cb * b_t over a list of tensors in ONE launch (the EMA update of 272 parameter
-// tensors, utils/EmaUpdater.py:23-38; one launch per tensor cost the host 272 calls per step).  Block = one chunk of at
-// most MT_CHUNK elements of one tensor; chunk -> (tensor, offset) through two small device tables.
+// ---- multi-tensor kernels: a list of tensors in ONE launch (the EMA update and the optimizer step of 272 parameter tensors;
+// one launch per tensor cost the host 272 calls per step).  Workgroup = one chunk of at most MT_CHUNK elements of one tensor;
+// chunk -> (tensor, index of the chunk within it) through two small device tables (ops.chunk_tables).
 constexpr int MT_CHUNK = 16384;
+
+// the entry and the element range [lo, hi) of this workgroup's chunk (Entry: tmdiff_mt_entry or tmdiff_adamw_entry)
+template <class Entry>
+struct Chunk { Entry e; long lo, hi; };
+template <class Entry>
+__device__ __forceinline__ Chunk<Entry> chunk_of(const Entry* __restrict__ tensors, const int32_t* __restrict__ chunk_tensor,
+                                                 const int32_t* __restrict__ chunk_index) {
+  const Entry e = tensors[chunk_tensor[blockIdx.x]];
+  const long lo = (long)chunk_index[blockIdx.x] * MT_CHUNK;
+  return {e, lo, min(lo + MT_CHUNK, (long)e.n)};
+}
+
+// THE walk over [lo, hi) by 256 lanes: vec (the tensor's pointers are 16-byte aligned; a chunk starts at a multiple of 4):
+// body(Vec4, i) on four elements per lane, then body(Vec1, i) on the tail of at most three; else body(Vec1, i) throughout.
+template <class F>
+__device__ __forceinline__ void walk_chunk(long lo, long hi, bool vec, F&& body) {
+  long i0 = lo;
+  if (vec) {
+    const long hi4 = lo + ((hi - lo) & ~3L);
+    for (long i = lo + threadIdx.x * 4L; i < hi4; i += 1024) body(Vec4{}, i);
+    i0 = hi4;
+  }
+  for (long i = i0 + threadIdx.x; i < hi; i += 256) body(Vec1{}, i);
+}
+
+// out_t = ca * a_t + cb * b_t (the EMA update, utils/EmaUpdater.py:23-38)
 __global__ void __launch_bounds__(256) multi_axpby_kernel(const tmdiff_mt_entry* __restrict__ tensors,
                                                           const int32_t* __restrict__ chunk_tensor,
                                                           const int32_t* __restrict__ chunk_index, float ca, float cb) {
-  const tmdiff_mt_entry e = tensors[chunk_tensor[blockIdx.x]];
-  const long lo = (long)chunk_index[blockIdx.x] * MT_CHUNK;
-  const long hi = min(lo + MT_CHUNK, (long)e.n);
-  const bool vec = ((reinterpret_cast<uintptr_t>(e.out) | reinterpret_cast<uintptr_t>(e.a) | reinterpret_cast<uintptr_t>(e.b)) & 15u) == 0;
-  if (vec) {
-    const long hi4 = lo + ((hi - lo) & ~3L);
-    for (long i = lo + threadIdx.x * 4L; i < hi4; i += 1024) {
-      const float4 x = *reinterpret_cast<const float4*>(e.a + i), y = *reinterpret_cast<const float4*>(e.b + i);
-      *reinterpret_cast<float4*>(e.out + i) =
-          make_float4(__fadd_rn(mul_rounded(ca, x.x), mul_rounded(cb, y.x)), __fadd_rn(mul_rounded(ca, x.y), mul_rounded(cb, y.y)),
-                      __fadd_rn(mul_rounded(ca, x.z), mul_rounded(cb, y.z)), __fadd_rn(mul_rounded(ca, x.w), mul_rounded(cb, y.w)));
-    }
-    for (long i = hi4 + threadIdx.x; i < hi; i += 256) e.out[i] = __fadd_rn(mul_rounded(ca, e.a[i]), mul_rounded(cb, e.b[i]));
-  } else {
-    for (long i = lo + threadIdx.x; i < hi; i += 256) e.out[i] = __fadd_rn(mul_rounded(ca, e.a[i]), mul_rounded(cb, e.b[i]));
-  }
+  const auto c = chunk_of(tensors, chunk_tensor, chunk_index);
+  walk_chunk(c.lo, c.hi, aligned16(c.e.out) && aligned16(c.e.a) && aligned16(c.e.b), [&](auto vt, long i) {
+    constexpr int V = decltype(vt)::value;
+    float x[V], y[V];
+    load<V>(x, c.e.a + i);
+    load<V>(y, c.e.b + i);
+#pragma unroll
+    for (int j = 0; j < V; ++j) x[j] = __fadd_rn(mul_rounded(ca, x[j]), mul_rounded(cb, y[j]));
+    store<V>(c.e.out + i, x);
+  });
 }
 
 // Multi-tensor AdamW (torch.optim.AdamW semantics: decoupled weight decay, bias-corrected moments, amsgrad off) over a list of
@@ -186,7 +235,7 @@ __device__ __forceinline__ AdamwCoef adamw_coef(const float* __restrict__ lr_dev
                    (float)sqrt(bc2), eps};
 }
 
-// the update of ONE element (the only copy: the plain and the gradient-scaled kernel both run it)
+// the update of ONE element
 __device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v, const AdamwCoef& k) {
   p = mul_rounded(p, k.decay);
   m = __fadd_rn(m, mul_rounded(k.w1, __fsub_rn(g, m)));
@@ -195,92 +244,62 @@ __device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v,
   p = __fsub_rn(p, mul_rounded(k.step_size, __fdiv_rn(m, denom)));
 }
 
-// One chunk of one tensor.  SCALED: the gradient is multiplied by `coef` (one rounding) on its way from memory to the update;
-// the product lives in registers only, the gradient tensor is never written.
+// One launch for the plain step and for the step on gradients scaled by *coef_dev (SCALED; global-norm clipping:
+// multi_sqnorm_finish_kernel below wrote it).  The product with the gradient (one rounding) lives in registers only, the gradient
+// tensor is never written.  *ok_dev == 0 (a non-finite norm) skips the step before any table read: p / m / v keep their bits.
+// The plain step passes NULL for both and reads neither.
 template <bool SCALED>
-__device__ __forceinline__ void adamw_chunk(const tmdiff_adamw_entry& e, long lo, const AdamwCoef& k, float coef) {
-  const long hi = min(lo + MT_CHUNK, (long)e.n);
-  auto one = [&](float& p, float g, float& m, float& v) __attribute__((always_inline)) {
-    adamw_one(p, SCALED ? mul_rounded(g, coef) : g, m, v, k);
-  };
-  const bool vec = ((reinterpret_cast<uintptr_t>(e.p) | reinterpret_cast<uintptr_t>(e.g) | reinterpret_cast<uintptr_t>(e.m) |
-                     reinterpret_cast<uintptr_t>(e.v)) & 15u) == 0;
-  long i0 = lo;
-  if (vec) {
-    const long hi4 = lo + ((hi - lo) & ~3L);
-    for (long i = lo + threadIdx.x * 4L; i < hi4; i += 1024) {
-      float4 p = *reinterpret_cast<float4*>(e.p + i), m = *reinterpret_cast<float4*>(e.m + i), v = *reinterpret_cast<float4*>(e.v + i);
-      const float4 g = *reinterpret_cast<const float4*>(e.g + i);
-      one(p.x, g.x, m.x, v.x); one(p.y, g.y, m.y, v.y); one(p.z, g.z, m.z, v.z); one(p.w, g.w, m.w, v.w);
-      *reinterpret_cast<float4*>(e.p + i) = p;
-      *reinterpret_cast<float4*>(e.m + i) = m;
-      *reinterpret_cast<float4*>(e.v + i) = v;
-    }
-    i0 = hi4;
-  }
-  for (long i = i0 + threadIdx.x; i < hi; i += 256) one(e.p[i], e.g[i], e.m[i], e.v[i]);
-}
-
 __global__ void __launch_bounds__(256) multi_adamw_kernel(const tmdiff_adamw_entry* __restrict__ tensors,
                                                           const int32_t* __restrict__ chunk_tensor,
                                                           const int32_t* __restrict__ chunk_index, const float* __restrict__ lr_dev,
                                                           const float* __restrict__ step_dev, float beta1, float beta2, float eps,
-                                                          float weight_decay) {
-  const tmdiff_adamw_entry e = tensors[chunk_tensor[blockIdx.x]];
-  adamw_chunk<false>(e, (long)chunk_index[blockIdx.x] * MT_CHUNK, adamw_coef(lr_dev, step_dev, beta1, beta2, eps, weight_decay), 1.f);
-}
-
-// The same step on gradients scaled by *coef_dev (global-norm clipping: multi_sqnorm_finish_kernel below wrote it).  *ok_dev == 0
-// (a non-finite norm) skips the step: nothing is read or written, p / m / v keep their bits.
-__global__ void __launch_bounds__(256) multi_adamw_scaled_kernel(const tmdiff_adamw_entry* __restrict__ tensors,
-                                                                 const int32_t* __restrict__ chunk_tensor,
-                                                                 const int32_t* __restrict__ chunk_index,
-                                                                 const float* __restrict__ lr_dev, const float* __restrict__ step_dev,
-                                                                 float beta1, float beta2, float eps, float weight_decay,
-                                                                 const float* __restrict__ coef_dev, const float* __restrict__ ok_dev) {
-  if (*ok_dev == 0.f) return;
-  const tmdiff_adamw_entry e = tensors[chunk_tensor[blockIdx.x]];
-  adamw_chunk<true>(e, (long)chunk_index[blockIdx.x] * MT_CHUNK, adamw_coef(lr_dev, step_dev, beta1, beta2, eps, weight_decay),
-                    *coef_dev);
-}
-
-// Global gradient norm in two stages, both without atomics and with a fixed summation order, so the norm has the same bits
-// from run to run and from an eager launch to a graph replay.
-// Sum over a workgroup of 256 lanes in double: xor-butterfly inside each wave, then the four wave totals in index order.
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+                                                          float weight_decay, const float* __restrict__ coef_dev,
+                                                          const float* __restrict__ ok_dev) {
+  if constexpr (SCALED)
+    if (*ok_dev == 0.f) return;
+  const auto c = chunk_of(tensors, chunk_tensor, chunk_index);
+  const tmdiff_adamw_entry& e = c.e;
+  const AdamwCoef k = adamw_coef(lr_dev, step_dev, beta1, beta2, eps, weight_decay);
+  const float coef = SCALED ? *coef_dev : 1.f;
+  walk_chunk(c.lo, c.hi, aligned16(e.p) && aligned16(e.g) && aligned16(e.m) && aligned16(e.v), [&](auto vt, long i) {
+    constexpr int V = decltype(vt)::value;
+    if constexpr (V == 1) {         // (in memory, as it always was: the compiler may not assume that p, m and v are distinct)
+      adamw_one(e.p[i], SCALED ? mul_rounded(e.g[i], coef) : e.g[i], e.m[i], e.v[i], k);
+    } else {
+      float p[V], g[V], m[V], v[V];
+      load<V>(p, e.p + i);
+      load<V>(m, e.m + i);
+      load<V>(v, e.v + i);
+      load<V>(g, e.g + i);
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
+      for (int j = 0; j < V; ++j) adamw_one(p[j], SCALED ? mul_rounded(g[j], coef) : g[j], m[j], v[j], k);
+      store<V>(e.p + i, p);
+      store<V>(e.m + i, m);
+      store<V>(e.v + i, v);
+    }
+  });
 }
 
+// Global gradient norm in two stages, both without atomics and with a fixed summation order (common.h block_sum_f64), so the
+// norm has the same bits from run to run and from an eager launch to a graph replay.
 // Stage 1: workgroup k sums g^2 over chunk k of the AdamW tables (same entries, same chunks) into partials[k].  Each lane adds
-// the squares of its strided elements in double (the square of a float is exact there), 16 bytes per load where the
-// gradient is 16-byte aligned.
+// the squares of its strided elements in double (the square of a float is exact there) in element order, 16 bytes per load
+// where the gradient is 16-byte aligned.
 __global__ void __launch_bounds__(256) multi_sqnorm_partial_kernel(const tmdiff_adamw_entry* __restrict__ tensors,
                                                                    const int32_t* __restrict__ chunk_tensor,
                                                                    const int32_t* __restrict__ chunk_index,
                                                                    double* __restrict__ partials) {
   __shared__ double red[4];
-  const tmdiff_adamw_entry e = tensors[chunk_tensor[blockIdx.x]];
-  const long lo = (long)chunk_index[blockIdx.x] * MT_CHUNK;
-  const long hi = min(lo + MT_CHUNK, (long)e.n);
+  const auto c = chunk_of(tensors, chunk_tensor, chunk_index);
   double acc = 0.0;
-  long i0 = lo;
-  if ((reinterpret_cast<uintptr_t>(e.g) & 15u) == 0) {
-    const long hi4 = lo + ((hi - lo) & ~3L);
-    for (long i = lo + threadIdx.x * 4L; i < hi4; i += 1024) {
-      const float4 g = *reinterpret_cast<const float4*>(e.g + i);
-      acc += (double)g.x * (double)g.x;
-      acc += (double)g.y * (double)g.y;
-      acc += (double)g.z * (double)g.z;
-      acc += (double)g.w * (double)g.w;
-    }
-    i0 = hi4;
-  }
-  for (long i = i0 + threadIdx.x; i < hi; i += 256) acc += (double)e.g[i] * (double)e.g[i];
-  const double total = block_sum_f64(acc, red);
+  walk_chunk(c.lo, c.hi, aligned16(c.e.g), [&](auto vt, long i) {
+    constexpr int V = decltype(vt)::value;
+    float g[V];
+    load<V>(g, c.e.g + i);
+#pragma unroll
+    for (int j = 0; j < V; ++j) acc += (double)g[j] * (double)g[j];
+  });
+  const double total = tmdiff::block_sum_f64(acc, red);
   if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
 
@@ -292,7 +311,7 @@ __global__ void __launch_bounds__(256) multi_sqnorm_finish_kernel(const double* 
   __shared__ double red[4];
   double acc = 0.0;
   for (int i = threadIdx.x; i < n_partials; i += 256) acc += partials[i];
-  const double total = block_sum_f64(acc, red);
+  const double total = tmdiff::block_sum_f64(acc, red);
   if (threadIdx.x == 0) {
     const float norm = (float)sqrt(total);
     const bool ok = isfinite(norm);
@@ -307,14 +326,10 @@ template <int V>
 __global__ void __launch_bounds__(256) x0_kernel(const float* __restrict__ x, const float* __restrict__ m,
                                                  float* __restrict__ x0, long nvec, float alpha, float sigma,
                                                  int is_x_start) {
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < nvec; i += 256L * gridDim.x) {
+  FOR_EACH_VEC(i, nvec) {
     float xv[V], mv[V], ov[V];
-    if constexpr (V == 4) {
-      *reinterpret_cast<float4*>(xv) = reinterpret_cast<const float4*>(x)[i];
-      *reinterpret_cast<float4*>(mv) = reinterpret_cast<const float4*>(m)[i];
-    } else {
-      xv[0] = x[i], mv[0] = m[i];
-    }
+    load<V>(xv, x + i * V);
+    load<V>(mv, m + i * V);
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       // model_wrapper: x_start output -> noise  (dpm_solver_pytorch.py:304-306)
@@ -322,24 +337,20 @@ __global__ void __launch_bounds__(256) x0_kernel(const float* __restrict__ x, co
       // data_prediction_fn: noise -> x0          (:451-453)
       ov[j] = __fdiv_rn(__fsub_rn(xv[j], mul_rounded(sigma, eps)), alpha);
     }
-    if constexpr (V == 4)
-      reinterpret_cast<float4*>(x0)[i] = *reinterpret_cast<float4*>(ov);
-    else
-      x0[i] = ov[0];
+    store<V>(x0 + i * V, ov);
   }
 }
 
 template <int V>
 __global__ void __launch_bounds__(256) add_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                   float* __restrict__ out, long nvec, float sign_b) {
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < nvec; i += 256L * gridDim.x) {
-    if constexpr (V == 4) {
-      const float4 u = reinterpret_cast<const float4*>(a)[i], v = reinterpret_cast<const float4*>(b)[i];
-      reinterpret_cast<float4*>(out)[i] = make_float4(u.x + mul_rounded(sign_b, v.x), u.y + mul_rounded(sign_b, v.y),
-                                                      u.z + mul_rounded(sign_b, v.z), u.w + mul_rounded(sign_b, v.w));
-    } else {
-      out[i] = a[i] + mul_rounded(sign_b, b[i]);
-    }
+  FOR_EACH_VEC(i, nvec) {
+    float u[V], v[V];
+    load<V>(u, a + i * V);
+    load<V>(v, b + i * V);
+#pragma unroll
+    for (int j = 0; j < V; ++j) u[j] = u[j] + mul_rounded(sign_b, v[j]);
+    store<V>(out + i * V, u);
   }
 }
 
@@ -513,11 +524,11 @@ __global__ void __launch_bounds__(256) quantile_gather_s_kernel(const unsigned* 
   if (b < B) s_out[b] = reinterpret_cast<const float*>(ws)[(long)b * QW_STRIDE];
 }
 
-inline bool all_aligned(std::initializer_list<const void*> ps, long n, int) {
-  if (n % 4) return false;
-  for (const void* p : ps)
-    if (p && !tmdiff::aligned16(p)) return false;
-  return true;
+// the scalars of both AdamW entry points
+int check_adamw_scalars(const char* what, float beta1, float beta2, float eps, float weight_decay) {
+  TMDIFF_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f && weight_decay >= 0.f,
+                 "%s: betas (%g, %g) eps %g weight_decay %g", what, (double)beta1, (double)beta2, (double)eps, (double)weight_decay);
+  return TMDIFF_OK;
 }
 
 }  // namespace
@@ -531,13 +542,10 @@ extern "C" int tmdiff_ddpm_step(const float* x, const float* eps, const float* n
   TMDIFF_REQUIRE(noise || sigma == 0.f, "ddpm_step: noise is NULL but sigma != 0");
   TMDIFF_REQUIRE(!img_out || ms, "ddpm_step: img_out needs ms");
   if (n == 0) return TMDIFF_OK;
-  DdpmCoef k{c_recip, c_recipm1, coef1, coef2, sigma, clip};
-  if (all_aligned({x, eps, noise, ms, out, img_out}, n, 0)) {
-    ddpm_step_kernel<4><<<grid_for(n / 4), 256, 0, as_stream(stream)>>>(x, eps, noise, ms, out, img_out, n / 4, k);
-  } else {
-    ddpm_step_kernel<1><<<grid_for(n), 256, 0, as_stream(stream)>>>(x, eps, noise, ms, out, img_out, n, k);
-  }
-  return check_launch("ddpm_step");
+  const DdpmCoef k{c_recip, c_recipm1, coef1, coef2, sigma, clip};
+  return launch_elementwise({x, eps, noise, ms, out, img_out}, n, "ddpm_step", [&](auto vt, int grid, long nvec) {
+    ddpm_step_kernel<decltype(vt)::value><<<grid, 256, 0, as_stream(stream)>>>(x, eps, noise, ms, out, img_out, nvec, k);
+  });
 }
 
 extern "C" int tmdiff_ddpm_frame_slot(int32_t t, int32_t T, int32_t frame_every) {
@@ -552,15 +560,10 @@ extern "C" int tmdiff_ddpm_step_dev(const float* x, const float* eps, const floa
   TMDIFF_REQUIRE(n >= 0 && T > 0, "ddpm_step_dev: n=%ld T=%d", (long)n, T);
   TMDIFF_REQUIRE(!frames || (ms && frame_every > 0), "ddpm_step_dev: frames need ms and frame_every > 0 (got %d)", frame_every);
   if (n == 0) return TMDIFF_OK;
-  hipStream_t st = as_stream(stream);
-  if (all_aligned({x, eps, noise, ms, out, frames}, n, 0)) {
-    ddpm_step_dev_kernel<4><<<grid_for(n / 4), 256, 0, st>>>(x, eps, noise, ms, out, frames, n / 4, n, step, coef, T,
-                                                            frame_every, clip);
-  } else {
-    ddpm_step_dev_kernel<1><<<grid_for(n), 256, 0, st>>>(x, eps, noise, ms, out, frames, n, n, step, coef, T, frame_every,
-                                                        clip);
-  }
-  return check_launch("ddpm_step_dev");
+  return launch_elementwise({x, eps, noise, ms, out, frames}, n, "ddpm_step_dev", [&](auto vt, int grid, long nvec) {
+    ddpm_step_dev_kernel<decltype(vt)::value><<<grid, 256, 0, as_stream(stream)>>>(x, eps, noise, ms, out, frames, nvec, n, step, coef,
+                                                                                  T, frame_every, clip);
+  });
 }
 
 extern "C" int tmdiff_sampler_tick(int32_t* step, float* time_in, int32_t B, int32_t set_to, tmdiff_stream_t stream) {
@@ -576,22 +579,16 @@ extern "C" int tmdiff_axpby(const float* const in[4], const float coef[4], int32
   TMDIFF_REQUIRE(in && coef && out, "axpby: NULL pointer");
   TMDIFF_REQUIRE(n_in >= 1 && n_in <= 4 && n >= 0, "axpby: n_in=%d n=%ld", n_in, (long)n);
   AxpbyArgs a;
-  bool al = n % 4 == 0 && aligned16(out);
   for (int k = 0; k < 4; ++k) {
-    a.in[k] = k < n_in ? in[k] : nullptr;
+    a.in[k] = k < n_in ? in[k] : nullptr;       // (a NULL operand does not count for the alignment)
     a.coef[k] = k < n_in ? coef[k] : 0.f;
-    if (k < n_in) {
-      TMDIFF_REQUIRE(in[k] != nullptr, "axpby: input %d is NULL", k);
-      al = al && aligned16(in[k]);
-    }
+    TMDIFF_REQUIRE(k >= n_in || in[k] != nullptr, "axpby: input %d is NULL", k);
   }
   a.n_in = n_in;
   if (n == 0) return TMDIFF_OK;
-  if (al)
-    axpby_kernel<4><<<grid_for(n / 4), 256, 0, as_stream(stream)>>>(a, out, n / 4);
-  else
-    axpby_kernel<1><<<grid_for(n), 256, 0, as_stream(stream)>>>(a, out, n);
-  return check_launch("axpby");
+  return launch_elementwise({a.in[0], a.in[1], a.in[2], a.in[3], out}, n, "axpby", [&](auto vt, int grid, long nvec) {
+    axpby_kernel<decltype(vt)::value><<<grid, 256, 0, as_stream(stream)>>>(a, out, nvec);
+  });
 }
 
 extern "C" int32_t tmdiff_multi_axpby_chunk(void) { return MT_CHUNK; }
@@ -611,11 +608,10 @@ extern "C" int tmdiff_multi_adamw(const tmdiff_adamw_entry* tensors_dev, const i
                                   float beta1, float beta2, float eps, float weight_decay, tmdiff_stream_t stream) {
   using namespace tmdiff;
   TMDIFF_REQUIRE(tensors_dev && chunk_tensor_dev && chunk_index_dev && lr_dev && step_dev && n_chunks >= 0, "multi_adamw: bad arguments");
-  TMDIFF_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f && weight_decay >= 0.f,
-                 "multi_adamw: betas (%g, %g) eps %g weight_decay %g", (double)beta1, (double)beta2, (double)eps, (double)weight_decay);
+  if (const int rc = check_adamw_scalars("multi_adamw", beta1, beta2, eps, weight_decay)) return rc;
   if (n_chunks == 0) return TMDIFF_OK;
-  multi_adamw_kernel<<<(unsigned)n_chunks, 256, 0, as_stream(stream)>>>(tensors_dev, chunk_tensor_dev, chunk_index_dev, lr_dev,
-                                                                         step_dev, beta1, beta2, eps, weight_decay);
+  multi_adamw_kernel<false><<<(unsigned)n_chunks, 256, 0, as_stream(stream)>>>(
+      tensors_dev, chunk_tensor_dev, chunk_index_dev, lr_dev, step_dev, beta1, beta2, eps, weight_decay, nullptr, nullptr);
   return check_launch("multi_adamw");
 }
 
@@ -626,10 +622,8 @@ extern "C" int tmdiff_multi_adamw_scaled(const tmdiff_adamw_entry* tensors_dev, 
   using namespace tmdiff;
   TMDIFF_REQUIRE(tensors_dev && chunk_tensor_dev && chunk_index_dev && lr_dev && step_dev && coef_dev && ok_dev && n_chunks > 0,
                  "multi_adamw_scaled: bad arguments");
-  TMDIFF_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f && weight_decay >= 0.f,
-                 "multi_adamw_scaled: betas (%g, %g) eps %g weight_decay %g", (double)beta1, (double)beta2, (double)eps,
-                 (double)weight_decay);
-  multi_adamw_scaled_kernel<<<(unsigned)n_chunks, 256, 0, as_stream(stream)>>>(
+  if (const int rc = check_adamw_scalars("multi_adamw_scaled", beta1, beta2, eps, weight_decay)) return rc;
+  multi_adamw_kernel<true><<<(unsigned)n_chunks, 256, 0, as_stream(stream)>>>(
       tensors_dev, chunk_tensor_dev, chunk_index_dev, lr_dev, step_dev, beta1, beta2, eps, weight_decay, coef_dev, ok_dev);
   return check_launch("multi_adamw_scaled");
 }
@@ -663,11 +657,9 @@ extern "C" int tmdiff_x0_from_model(const float* x, const float* model_out, floa
   using namespace tmdiff;
   TMDIFF_REQUIRE(x && model_out && x0 && n >= 0, "x0_from_model: bad arguments");
   if (n == 0) return TMDIFF_OK;
-  if (all_aligned({x, model_out, x0}, n, 0))
-    x0_kernel<4><<<grid_for(n / 4), 256, 0, as_stream(stream)>>>(x, model_out, x0, n / 4, alpha, sigma, model_is_x_start);
-  else
-    x0_kernel<1><<<grid_for(n), 256, 0, as_stream(stream)>>>(x, model_out, x0, n, alpha, sigma, model_is_x_start);
-  return check_launch("x0_from_model");
+  return launch_elementwise({x, model_out, x0}, n, "x0_from_model", [&](auto vt, int grid, long nvec) {
+    x0_kernel<decltype(vt)::value><<<grid, 256, 0, as_stream(stream)>>>(x, model_out, x0, nvec, alpha, sigma, model_is_x_start);
+  });
 }
 
 extern "C" size_t tmdiff_abs_quantile_workspace_bytes(int32_t B, int64_t /*n_per_sample*/) {
@@ -706,11 +698,9 @@ extern "C" int tmdiff_add(const float* a, const float* b, float* out, int64_t n,
   using namespace tmdiff;
   TMDIFF_REQUIRE(a && b && out && n >= 0, "add: bad arguments");
   if (n == 0) return TMDIFF_OK;
-  if (all_aligned({a, b, out}, n, 0))
-    add_kernel<4><<<grid_for(n / 4), 256, 0, as_stream(stream)>>>(a, b, out, n / 4, sign_b);
-  else
-    add_kernel<1><<<grid_for(n), 256, 0, as_stream(stream)>>>(a, b, out, n, sign_b);
-  return check_launch("add");
+  return launch_elementwise({a, b, out}, n, "add", [&](auto vt, int grid, long nvec) {
+    add_kernel<decltype(vt)::value><<<grid, 256, 0, as_stream(stream)>>>(a, b, out, nvec, sign_b);
+  });
 }
 
 extern "C" int tmdiff_q_sample(const float* x0, const float* noise, const float* a, float* out, int32_t B,

@@ -1022,6 +1022,26 @@ def axpby(tensors, coefs, out=None):
     return y
 
 
+def chunk_tables(rows, sizes, device, pinned):
+    """The device tables of the multi-tensor kernels (tmdiff_multi_axpby, tmdiff_multi_adamw, tmdiff_multi_sqnorm_partial): per tensor
+    one row of int64 (its pointers, then its element count: tmdiff_mt_entry / tmdiff_adamw_entry), and per chunk of
+    tmdiff_multi_axpby_chunk() elements its tensor and its index within that tensor (int32).  ``pinned``: pinned host tensors,
+    returned last for the caller to keep alive, and non-blocking uploads -- legal inside a HIP-graph capture, whose replay copies
+    the same bytes again; else plain copies.  Returns (entries, chunk_tensor, chunk_index, n_chunks, host or None)."""
+    chunk = lib.tmdiff_multi_axpby_chunk()
+    ct, ci = [], []
+    for k, n in enumerate(sizes):
+        nck = (n + chunk - 1) // chunk
+        ct += [k] * nck
+        ci += list(range(nck))
+    host = [torch.tensor([v for row in rows for v in row], dtype=torch.int64), torch.tensor(ct, dtype=torch.int32),
+            torch.tensor(ci, dtype=torch.int32)]
+    if pinned:
+        host = [h.pin_memory() for h in host]
+    devt = [h.to(device, non_blocking=pinned) for h in host]
+    return devt[0], devt[1], devt[2], len(ct), host if pinned else None
+
+
 class MultiAxpby:
     """out_t = ca * a_t + cb * b_t over a fixed list of (out, a, b) tensor triples in ONE launch (tmdiff_multi_axpby).
     The device tables are built once from the tensors' addresses; ``stale()`` says whether they moved."""
@@ -1039,17 +1059,9 @@ class MultiAxpby:
             return
         dev = triples[0][0].device
         self.key = tuple(t.data_ptr() for tr in triples for t in tr)
-        chunk = lib.tmdiff_multi_axpby_chunk()
-        ent, ct, ci = [], [], []
-        for k, (o, a, b) in enumerate(triples):
-            ent += [o.data_ptr(), a.data_ptr(), b.data_ptr(), o.numel()]
-            nck = (o.numel() + chunk - 1) // chunk
-            ct += [k] * nck
-            ci += list(range(nck))
-        self.entries = torch.tensor(ent, dtype=torch.int64).to(dev)           # tmdiff_mt_entry[]: 3 pointers + int64
-        self.chunk_tensor = torch.tensor(ct, dtype=torch.int32).to(dev)
-        self.chunk_index = torch.tensor(ci, dtype=torch.int32).to(dev)
-        self.n_chunks = len(ct)
+        self.entries, self.chunk_tensor, self.chunk_index, self.n_chunks, _ = chunk_tables(
+            [(o.data_ptr(), a.data_ptr(), b.data_ptr(), o.numel()) for o, a, b in triples], [o.numel() for o, _, _ in triples],
+            dev, pinned=False)
         self._keep = triples
 
     def stale(self, triples):

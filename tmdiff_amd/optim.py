@@ -13,7 +13,6 @@ gradients for the norm (tmdiff_multi_sqnorm_partial / _finish), then an AdamW la
 coefficient in registers (tmdiff_multi_adamw_scaled) -- the gradients are never rewritten and nothing is read on the host.  With
 ``skip_nonfinite`` a step whose norm is inf / NaN changes nothing at all, the step counters included."""
 import ctypes as C
-import struct
 
 import torch
 
@@ -73,22 +72,12 @@ class FusedAdamW(torch.optim.AdamW):
         tb = self._tables.get(gi)
         if tb is not None and tb["key"] == key:
             return tb
-        chunk = lib.tmdiff_multi_axpby_chunk()
-        ent, ct, ci = bytearray(), [], []
-        for k, (pp, gp, mp, vp, n) in enumerate(key):
-            ent += struct.pack("<QQQQq", pp, gp, mp, vp, n)
-            nck = (n + chunk - 1) // chunk
-            ct += [k] * nck
-            ci += list(range(nck))
-        dev = params[0].device
-        # pinned host copies + non-blocking uploads: legal inside a HIP-graph capture (the gradients of a captured step are
-        # allocated inside the capture, so their addresses -- hence this table -- are first known there); the pinned tensors
-        # stay alive with the table, a replay copies the same bytes again
-        host = [torch.frombuffer(bytearray(ent), dtype=torch.uint8).clone().pin_memory(),
-                torch.tensor(ct, dtype=torch.int32).pin_memory(), torch.tensor(ci, dtype=torch.int32).pin_memory()]
-        devt = [h.to(dev, non_blocking=True) for h in host]
-        tb = self._tables[gi] = {"key": key, "host": host, "entries": devt[0], "chunk_tensor": devt[1], "chunk_index": devt[2],
-                                 "n_chunks": len(ct)}
+        # pinned host copies + non-blocking uploads (the gradients of a captured step are allocated inside the capture, so their
+        # addresses -- hence this table -- are first known there); the pinned tensors stay alive with the table
+        entries, chunk_tensor, chunk_index, n_chunks, host = ops.chunk_tables(key, [row[4] for row in key], params[0].device,
+                                                                              pinned=True)
+        tb = self._tables[gi] = {"key": key, "host": host, "entries": entries, "chunk_tensor": chunk_tensor,
+                                 "chunk_index": chunk_index, "n_chunks": n_chunks}
         return tb
 
     def _lr_scalar(self, gi, group, dev):
