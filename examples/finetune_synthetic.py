@@ -17,6 +17,7 @@ ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the glob
 ap.add_argument("--grad-bf16", action="store_true", help="gradients of the 3x3x3 convolutions from bf16-rounded operands (fp32 sums)")
 ap.add_argument("--sam-weight", type=float, default=None, help="add w * (mean spectral angle of the fused image) to the loss")
 ap.add_argument("--lap-weight", type=float, default=None, help="add w * (mean |Laplacian| of the residual error) to the loss")
+ap.add_argument("--dssim-weight", type=float, default=None, help="add w * (1 - SSIM of the fused image, 7 x 7 windows) to the loss")
 args = ap.parse_args()
 world = tdist.init_from_env()
 rank = int(os.environ.get("RANK", "0"))
@@ -28,8 +29,8 @@ if args.max_grad_norm is not None:
     opt["train"]["max_grad_norm"] = args.max_grad_norm
 if args.grad_bf16:
     opt["train"]["grad_compute"] = "bf16"
-terms = {k: w for k, w in (("sam", args.sam_weight), ("lap", args.lap_weight)) if w is not None}
-if terms:                                   # the composite loss of tmdiff_amd.losses: one HIP kernel pair, value and gradient
+terms = {k: w for k, w in (("sam", args.sam_weight), ("lap", args.lap_weight), ("dssim", args.dssim_weight)) if w is not None}
+if terms:                                   # the composite loss of tmdiff_amd.losses: HIP kernel pairs, value and gradient
     opt["model"]["diffusion"]["loss_terms"] = terms
 torch.manual_seed(3407)                     # identical initial weights on every rank
 model = DDPM(opt)
@@ -44,5 +45,5 @@ for it in range(args.iters):
     if rank == 0:
         log = model.get_current_log()
         clip = f" grad_norm {log['grad_norm']:.3f} skipped {log['skipped']:.0f}" if "grad_norm" in log else ""
-        parts = "".join(f" {k} {float(log[k]):.4f}" for k in ("l_base", "l_sam", "l_lap") if k in log)
+        parts = "".join(f" {k} {float(log[k]):.4f}" for k in ("l_base", "l_sam", "l_lap", "l_dssim") if k in log)
         print(f"iter {it}: l_pix {float(log['l_pix']):.4f}{parts} lr {log['lr']:.2e}{clip} {1e3 * (time.perf_counter() - t0):.1f} ms", flush=True)

@@ -697,6 +697,37 @@ int tmdiff_spectral_spatial_loss(const float* x0, const float* xhat, const float
                                  tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * The SSIM loss term with its gradient (csrc/ssim_loss.hip; host definition: tmdiff_amd/losses.py ssim_loss_host):
+ *     dssim = 1 - SSIM(x_true, x_pred),  x_true = x_true_in (+ ms),  x_pred = x_pred_in (+ ms)
+ * on dense fp32 [B, C, H, W] tensors; ms (optional, may be NULL) is added to both after the loads, in fp64.
+ *  SSIM : the mean over all B C (H - win + 1)(W - win + 1) windows of S = (A1 A2) / (B1 B2), a uniform win x win window per
+ *    band plane over the 'valid' region, n = win^2, k = n / (n - 1), f the window mean, a = x_true, b = x_pred:
+ *    ux = f(a), uy = f(b), vx = k (f(a a) - ux^2), vy = k (f(b b) - uy^2), vxy = k (f(a b) - ux uy), A1 = 2 ux uy + c1,
+ *    A2 = 2 vxy + c2, B1 = ux^2 + uy^2 + c1, B2 = vx + vy + c2, c1 = (0.01 data_range)^2, c2 = (0.03 data_range)^2: what
+ *    tmdiff_metrics_pair scores.  f(a b), f(a a) and f(b b) are formed by one instruction sequence: x_pred == x_true gives
+ *    S == 1 and dssim == 0 exactly.
+ *  g (fp32 [B, C, H, W]): accumulate == 0 stores weight * d dssim / d x_pred, rounded to fp32 once; accumulate == 1 stores
+ *    fl32(g + weight * d dssim / d x_pred) (the term rides on a gradient another kernel has just written); g == NULL selects
+ *    the value-only mode, which writes no gradient (accumulate must then be 0, else TMDIFF_E_INVALID).
+ *  terms_in == NULL: out64 is fp64 [2] = dssim, ssim and out32 the float of weight * dssim.
+ *  terms_in given (fp64 [4], the out64 of tmdiff_spectral_spatial_loss): out64 is fp64 [5] = terms_in[0] + weight * dssim,
+ *    terms_in[1], terms_in[2], terms_in[3], dssim and out32 the float of entry 0.  out64 may be terms_in's own storage.
+ * Every operation after the fp32 loads is fp64.  No atomics: each workgroup (one per 16 x 32 tile of one band plane) stores one
+ * fp64 partial sum into `workspace` and one finalize launch adds them in a fixed order, so a call is reproducible bit for bit.
+ * Nothing is allocated, synchronised or copied: a call can be captured into a graph on `stream`.  16-byte accesses when
+ * W % 4 == 0 and the tensors are 16-byte aligned, scalar ones otherwise, with the same values.
+ * workspace: 8-byte aligned, tmdiff_ssim_loss_workspace_bytes(B, C, H, W, win) = 8 * B * C * ceil(H / 16) * ceil(W / 32) bytes.
+ * Limits: B, C >= 1, win odd with 3 <= win <= 11, H, W >= win, B * C * H * W <= 2^31 - 1; for anything else
+ * tmdiff_ssim_loss_supported is 0 and the workspace size is 0.  The entry point returns TMDIFF_E_UNSUPPORTED without launching
+ * for those, and for a data_range that is not finite and > 0 or a weight that is not finite and >= 0.  (Added within version 6.)
+ * ------------------------------------------------------------------------------------ */
+int tmdiff_ssim_loss_supported(int32_t B, int32_t C, int32_t H, int32_t W, int32_t win);
+size_t tmdiff_ssim_loss_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t win);
+int tmdiff_ssim_loss(const float* x_true, const float* x_pred, const float* ms, float* g, int32_t win, double data_range,
+                     double weight, int32_t accumulate, const double* terms_in, double* out64, float* out32, void* workspace,
+                     size_t workspace_bytes, int32_t B, int32_t C, int32_t H, int32_t W, tmdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Resampling of full-resolution scenes (csrc/resample.hip; host definitions: tmdiff_amd/metrics.py).  Dense fp32 planes
  * [planes, H, W]; nothing is allocated or synchronised, so a call can be captured into a graph on `stream`.
  *  pyr_down: `levels` (1 or 2) steps of OpenCV's pyrDown with its defaults -- separable [1 4 6 4 1] / 16, horizontal pass then

@@ -207,6 +207,12 @@ SIGNATURES.update({
     "tmdiff_loss_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
     "tmdiff_spectral_spatial_loss": (C.c_int, [vp] * 4 + [C.c_int32, C.c_double, C.c_double, vp, vp, vp, C.c_size_t] +
                                      [C.c_int32] * 4 + [vp]),
+    # SSIM loss term (csrc/ssim_loss.hip): x_true, x_pred, ms, g | win, data_range, weight, accumulate | terms_in, out64, out32,
+    # workspace, bytes | B, C, H, W
+    "tmdiff_ssim_loss_supported": (C.c_int, [C.c_int32] * 5),
+    "tmdiff_ssim_loss_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "tmdiff_ssim_loss": (C.c_int, [vp] * 4 + [C.c_int32, C.c_double, C.c_double, C.c_int32, vp, vp, vp, vp, C.c_size_t] +
+                         [C.c_int32] * 4 + [vp]),
     # resampling (csrc/resample.hip): (planes, H, W, levels | ratio) after the two tensors
     "tmdiff_pyr_down": (C.c_int, [vp, vp] + [C.c_int32] * 4 + [vp]),
     "tmdiff_upsample_bilinear": (C.c_int, [vp, vp] + [C.c_int32] * 4 + [vp]),

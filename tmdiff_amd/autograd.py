@@ -680,3 +680,54 @@ class SpectralSpatialLossFn(torch.autograd.Function):
 
 def spectral_spatial_loss(x0, xhat, ms, base="l1", w_sam=0.0, w_lap=0.0):
     return SpectralSpatialLossFn.apply(x0, xhat, ms, base, float(w_sam), float(w_lap))
+
+
+class SSIMLossFn(torch.autograd.Function):
+    """ops.ssim_loss as a scalar loss, in the pattern of SpectralSpatialLossFn: the forward's kernel pair writes dssim and
+    g = d dssim / d x_pred, which is saved; backward is g * grad_out for x_pred alone.  When x_pred needs no gradient the forward
+    runs in the value-only mode.  Returns (dssim float32 [], terms float64 [2] = dssim, ssim); terms is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, x_true, x_pred, win, data_range):
+        want = ctx.needs_input_grad[1]
+        terms, total, g = ops.ssim_loss(x_true.contiguous(), x_pred.contiguous(), win, data_range, 1.0, grad=want)
+        if want:
+            ctx.save_for_backward(g)
+        ctx.mark_non_differentiable(terms)
+        return total, terms
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_terms):
+        g, = ctx.saved_tensors
+        return None, g * grad_out, None, None
+
+
+def ssim_loss(x_true, x_pred, win=7, data_range=1.0):
+    return SSIMLossFn.apply(x_true, x_pred, int(win), float(data_range))
+
+
+class SpectralSpatialSSIMLossFn(torch.autograd.Function):
+    """The composite loss with the SSIM term on: ops.spectral_spatial_loss writes its four values and g, then ops.ssim_loss
+    (7 x 7 window, data range 1, on x0 + ms and xhat + ms, the sums formed in the kernel) adds w_dssim * d dssim / d xhat to g
+    and composes the five values on the device.  Returns (total float32 [], terms float64 [5]: losses.TERM_FIELDS5)."""
+
+    @staticmethod
+    def forward(ctx, x0, xhat, ms, base, w_sam, w_lap, w_dssim):
+        want = ctx.needs_input_grad[1]
+        x0, xhat, ms = x0.contiguous(), xhat.contiguous(), ms.contiguous()
+        terms4, total, g = ops.spectral_spatial_loss(x0, xhat, ms if w_sam != 0.0 else None, base, w_sam, w_lap, grad=want)
+        terms, total, g = ops.ssim_loss(x0, xhat, 7, 1.0, w_dssim, grad=g if want else False, accumulate=want, terms_in=terms4,
+                                        total=total, ms=ms)
+        if want:
+            ctx.save_for_backward(g)
+        ctx.mark_non_differentiable(terms)
+        return total, terms
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_terms):
+        g, = ctx.saved_tensors
+        return None, g * grad_out, None, None, None, None, None
+
+
+def spectral_spatial_ssim_loss(x0, xhat, ms, base="l1", w_sam=0.0, w_lap=0.0, w_dssim=0.0):
+    return SpectralSpatialSSIMLossFn.apply(x0, xhat, ms, base, float(w_sam), float(w_lap), float(w_dssim))

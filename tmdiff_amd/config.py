@@ -57,11 +57,11 @@ def parse(config, phase, gpu_ids=None, debug=False, root="experiments", make_dir
     grad_compute = (opt.get("train") or {}).get("grad_compute")      # optional: "bf16" = bf16 gradient arithmetic (model.DDPM)
     if grad_compute not in (None, "fp32", "bf16"):
         raise ValueError(f"train.grad_compute must be 'fp32' or 'bf16', got {grad_compute!r}")
-    loss_terms = ((opt.get("model") or {}).get("diffusion") or {}).get("loss_terms")   # optional: {"sam": w, "lap": w} (losses)
+    loss_terms = ((opt.get("model") or {}).get("diffusion") or {}).get("loss_terms")   # optional: {"sam": w, "lap": w, "dssim": w} (losses)
     if loss_terms is not None:
         from .losses import parse_loss_terms
         if not isinstance(loss_terms, dict):
-            raise ValueError(f"model.diffusion.loss_terms must be a mapping such as {{'sam': 0.1, 'lap': 0.5}}, got {loss_terms!r}")
+            raise ValueError(f"model.diffusion.loss_terms must be a mapping such as {{'sam': 0.1, 'lap': 0.5, 'dssim': 0.2}}, got {loss_terms!r}")
         parse_loss_terms(loss_terms)
     if gpu_ids is not None:
         opt["gpu_ids"] = [int(i) for i in str(gpu_ids).split(",")]

@@ -48,8 +48,8 @@ class GeneralDiffusion(nn.Module):
     sample_graph_captures = 0      # samplers captured so far by this object
 
     def __init__(self, denoise_fn, loss_type="l1", noise_fn=None, loss_terms=None):
-        """``loss_terms`` (ours, optional): ``{"sam": w, "lap": w}`` adds a spectral-angle and / or a Laplacian term to
-        ``loss_type`` (tmdiff_amd.losses); None or {} keeps the reference's torch loss modules."""
+        """``loss_terms`` (ours, optional): ``{"sam": w, "lap": w, "dssim": w}`` adds a spectral-angle, a Laplacian and / or an
+        SSIM (1 - SSIM) term to ``loss_type`` (tmdiff_amd.losses); None or {} keeps the reference's torch loss modules."""
         super().__init__()
         self.denoise_fn = denoise_fn
         self.loss_type = loss_type
@@ -64,7 +64,7 @@ class GeneralDiffusion(nn.Module):
             if self.loss_type not in losses.BASE_KINDS:
                 raise NotImplementedError()
             w_sam, w_lap = losses.parse_loss_terms(self.loss_terms)
-            self.loss_func = losses.SpectralSpatialLoss(self.loss_type, w_sam, w_lap).to(device)
+            self.loss_func = losses.SpectralSpatialLoss(self.loss_type, w_sam, w_lap, losses.dssim_weight(self.loss_terms)).to(device)
         elif self.loss_type == "l1":
             self.loss_func = nn.L1Loss().to(device)
         elif self.loss_type == "l2":

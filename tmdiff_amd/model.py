@@ -207,9 +207,12 @@ class DDPM(BaseModel):
 
     def _log_loss_terms(self, terms):
         """l_base, l_sam, l_lap beside l_pix when the composite loss is on (losses.SpectralSpatialLoss.last_terms: a float64 [4]
-        device tensor; its entries are logged as device scalars, read by whoever prints the log)."""
+        device tensor, [5] with l_dssim when the SSIM term is on; its entries are logged as device scalars, read by whoever prints
+        the log)."""
         if terms is not None:
             self.log_dict["l_base"], self.log_dict["l_sam"], self.log_dict["l_lap"] = terms[1], terms[2], terms[3]
+            if terms.numel() == 5:
+                self.log_dict["l_dssim"] = terms[4]
 
     def _optimize_captured(self, prompt):
         """The same step from a HIP graph (CapturedStep).  The first GRAPH_WARMUP steps of every (prompt, batch shape) run

@@ -1271,6 +1271,65 @@ def spectral_spatial_loss(x0, xhat, ms=None, base="l1", w_sam=0.0, w_lap=0.0, gr
     return y, y32, g
 
 
+# ---- SSIM loss term (csrc/ssim_loss.hip; definition: tmdiff_amd/losses.py ssim_loss_host) ------------------------------
+_SSIM_LIMITS = "B, C >= 1, win odd with 3 <= win <= 11, H, W >= win, fewer than 2^31 elements"
+
+
+def ssim_loss_supported(b, c, h, w, win=7):
+    """True when ssim_loss takes [b, c, h, w] tensors with a win x win window."""
+    return bool(lib.tmdiff_ssim_loss_supported(int(b), int(c), int(h), int(w), int(win)))
+
+
+def ssim_loss(x_true, x_pred, win=7, data_range=1.0, weight=1.0, grad=True, accumulate=False, terms_in=None, out=None, total=None,
+              workspace=None, ms=None):
+    """dssim = 1 - SSIM(x_true, x_pred) of float32 [B, C, H, W] tensors over uniform win x win windows, two launches.  Returns
+    (out, total32, g).  Without `terms_in`: out float64 [2] = dssim, ssim and total32 the float32 of weight * dssim.  With
+    `terms_in` (the float64 [4] of spectral_spatial_loss): out float64 [5] = terms_in[0] + weight * dssim, base, sam, lap, dssim
+    and total32 the float32 of entry 0.  g = weight * d dssim / d x_pred (float32, the shape of x_pred).  `grad`: True allocates g,
+    a tensor receives it, False selects the value-only mode (g is None, nothing is written).  `accumulate` adds the gradient to
+    the tensor given as `grad`.  `ms` (optional): the kernel scores x_true + ms against x_pred + ms, summed in fp64."""
+    win, data_range, weight = int(win), float(data_range), float(weight)
+    if not 0.0 < data_range < float("inf"):
+        raise ValueError(f"ssim_loss: data_range must be finite and > 0, got {data_range}")
+    if not 0.0 <= weight < float("inf"):
+        raise ValueError(f"ssim_loss: weight must be finite and not negative, got {weight}")
+    if x_true.dim() != 4 or x_true.shape != x_pred.shape or (ms is not None and ms.shape != x_true.shape):
+        raise ValueError(f"ssim_loss: need [B, C, H, W] tensors of one shape, got {tuple(x_true.shape)}, {tuple(x_pred.shape)}, "
+                         f"{None if ms is None else tuple(ms.shape)}")
+    b, c, h, w = x_true.shape
+    if not ssim_loss_supported(b, c, h, w, win):
+        raise ValueError(f"ssim_loss: B={b} C={c} H={h} W={w} win={win} is not supported ({_SSIM_LIMITS})")
+    if accumulate and not torch.is_tensor(grad):
+        raise ValueError("ssim_loss: accumulate=True needs the gradient tensor to add to as `grad`")
+    pa, pb, pm = _chk(x_true, "x_true"), _chk(x_pred, "x_pred"), _chk(ms, "ms")
+    dev = x_true.device
+    g = None
+    if grad is not False and grad is not None:
+        g = torch.empty_like(x_pred) if grad is True else grad
+        if g.shape != x_pred.shape:
+            raise ValueError(f"ssim_loss: g {tuple(g.shape)}, need {tuple(x_pred.shape)}")
+    nout = 2 if terms_in is None else 5
+    if terms_in is not None and not (terms_in.is_cuda and terms_in.dtype == torch.float64 and terms_in.is_contiguous() and
+                                     terms_in.numel() == 4):
+        raise ValueError("ssim_loss: terms_in must be a contiguous float64 [4] tensor on the GPU")
+    y = out if out is not None else torch.empty(nout, device=dev, dtype=torch.float64)
+    if not (y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and y.numel() == nout):
+        raise ValueError(f"ssim_loss: out must be a contiguous float64 [{nout}] tensor on the GPU")
+    y32 = total if total is not None else torch.empty((), device=dev, dtype=torch.float32)
+    if y32.numel() != 1:
+        raise ValueError("ssim_loss: total must hold one float32")
+    need = lib.tmdiff_ssim_loss_workspace_bytes(b, c, h, w, win)
+    ws = workspace if workspace is not None else _workspace(dev, need, "ssim_loss")
+    nbytes = ws.numel() * ws.element_size()
+    if not (ws.is_cuda and ws.is_contiguous() and nbytes >= need):
+        raise ValueError(f"ssim_loss: workspace of {nbytes} bytes, need {need}")
+    check(lib.tmdiff_ssim_loss(pa, pb, pm, _chk(g, "g"), win, data_range, weight, int(bool(accumulate)),
+                               None if terms_in is None else terms_in.data_ptr(), y.data_ptr(), _chk(y32, "total"),
+                               ws.data_ptr(), nbytes, b, c, h, w, stream_ptr()), "ssim_loss")
+    _count("ssim_loss")
+    return y, y32, g
+
+
 _Q2N_LIMITS = "1 <= C <= 16, block 8, 16 or 32, 1 <= shift <= block, mirror padding no longer than the axis, fewer than 2^31 elements"
 
 

@@ -100,6 +100,7 @@ def main(argv=None):
     ap.add_argument("--grad-compute", type=str, choices=["fp32", "bf16"], default=None, help="override opt['train']['grad_compute']")
     ap.add_argument("--sam-weight", type=float, default=None, help="override opt['model']['diffusion']['loss_terms']['sam']")
     ap.add_argument("--lap-weight", type=float, default=None, help="override opt['model']['diffusion']['loss_terms']['lap']")
+    ap.add_argument("--dssim-weight", type=float, default=None, help="override opt['model']['diffusion']['loss_terms']['dssim']")
     args = ap.parse_args(argv)
 
     world = tdist.init_from_env()
@@ -109,7 +110,7 @@ def main(argv=None):
     opt = Config.parse(args.config, args.phase, args.gpu_ids, args.debug, root=args.root, make_dirs=rank == 0)
     if args.grad_compute is not None:
         opt["train"]["grad_compute"] = args.grad_compute
-    for key, weight in (("sam", args.sam_weight), ("lap", args.lap_weight)):
+    for key, weight in (("sam", args.sam_weight), ("lap", args.lap_weight), ("dssim", args.dssim_weight)):
         if weight is not None:           # (GeneralDiffusion refuses a negative weight)
             terms = dict(opt["model"]["diffusion"]["loss_terms"] or {})
             terms[key] = weight

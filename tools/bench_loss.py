@@ -13,7 +13,14 @@ show (7 - 8 us each, profiles/r06_tiled_fused.txt) and its bytes / time should b
 With --step it also times the captured finetune step (model.DDPM, ch 32-256, batch 8 of 8 x 64 x 64, HIP graph) with the terms
 on against the same step with plain l1 -- in which none of the new code runs -- alternating the two in one process.
 
-  python tools/bench_loss.py [--reps 30] [--calls 50] [--step] [--out profiles/loss_terms.txt]"""
+--leg ssim times the SSIM term instead (tmdiff_amd.losses.SSIMLoss; csrc/ssim_loss.hip: ssim_loss_kernel + ssim_finalize_kernel,
+7 x 7 windows) at the same two shapes against 1 - SSIM composed from five grouped conv2d box filters and their autograd in fp32,
+and with --step the captured step with loss_terms = {"dssim": 0.1} against plain l1.  Beside the pair: 12 bytes per element
+(x_true, x_pred read, g written) over its time.  Expectation, stated before the run: the kernel reads every staged value
+about win + 3 times from LDS and forms 5 n fp64 multiply-adds per window, so unlike the composite pair it is bound by its own
+arithmetic and LDS reads, a few tens of microseconds at these sizes, not by launch latency.
+
+  python tools/bench_loss.py [--leg composite|ssim] [--reps 30] [--calls 50] [--step] [--out profiles/loss_terms.txt]"""
 import argparse
 import os
 import statistics
@@ -120,8 +127,60 @@ def bench_shape(shape, calls, reps, lines):
     return graph_us(pair, calls, reps)[0]
 
 
-def bench_step(reps, rounds, lines):
+def composed_dssim(a, b, box, win=7):
+    """1 - SSIM from torch operators, fp32: five box filters as grouped conv2d over the band planes"""
+    c = a.shape[1]
+    n = win * win
+    k = n / (n - 1.0)
+    f = lambda t: F.conv2d(t, box, groups=c)
+    ux, uy = f(a), f(b)
+    vx, vy, vxy = k * (f(a * a) - ux * ux), k * (f(b * b) - uy * uy), k * (f(a * b) - ux * uy)
+    c1, c2 = 0.01 ** 2, 0.03 ** 2
+    return 1.0 - (((2 * ux * uy + c1) * (2 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2))).mean()
+
+
+def bench_ssim_shape(shape, calls, reps, lines):
+    from tmdiff_amd import ops
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    a = torch.rand(*shape, device="cuda", generator=gen)
+    b = a + 0.1 * torch.randn(*shape, device="cuda", generator=gen)
+    n = a.numel()
+    out, total, g = ops.ssim_loss(a, b)
+    ws = torch.empty(max(1, ops.lib.tmdiff_ssim_loss_workspace_bytes(*shape, 7)), device="cuda", dtype=torch.uint8)
+    leaf = b.clone().requires_grad_(True)
+    box = torch.full((shape[1], 1, 7, 7), 1.0 / 49.0, device="cuda")
+
+    def pair():
+        ops.ssim_loss(a, b, grad=g, out=out, total=total, workspace=ws)
+
+    def value_only():
+        ops.ssim_loss(a, b, grad=False, out=out, total=total, workspace=ws)
+
+    def torch_ops():
+        leaf.grad = None
+        composed_dssim(a, leaf, box).backward()
+
+    torch_ops()
+    ref = float(composed_dssim(a, b, box))
+    dg = float((leaf.grad - g).norm() / g.norm())
+    lines.append(f"[{', '.join(map(str, shape))}]  {n} elements, {12 * n / 1e6:.1f} MB moved by the pair; kernel dssim {float(out[0]):.9f}, "
+                 f"torch fp32 composition {ref:.9f}, gradients differ by {dg:.1e} relative L2")
+    res = {}
+    for name, fn in (("kernel pair (value + gradient)", pair), ("kernel pair (value only)", value_only),
+                     ("torch operators, loss + backward", torch_ops)):
+        med, lo, hi = graph_us(fn, calls if fn is not torch_ops else max(1, calls // 10), reps)
+        emed, _, _ = eager_us(fn, reps)
+        rate = f"   {12 * n / (med * 1e-6) / 1e12:5.2f} TB/s" if fn is pair else ""
+        lines.append(f"  {name:<34s} {med:8.1f} us in a graph ({lo:.1f} .. {hi:.1f})   {emed:8.1f} us eager{rate}")
+        res[name] = med
+    return res["kernel pair (value + gradient)"], res["torch operators, loss + backward"]
+
+
+def bench_step(reps, rounds, lines, on=None, label=None):
     """the captured finetune step, terms on against plain l1, alternating"""
+    on = on or {"sam": W_SAM, "lap": W_LAP}
+    label = label or f"l1 + {W_SAM} sam + {W_LAP} lap (the kernel pair)"
+    names = ("l_pix", "l_base", "l_sam", "l_lap") + (("l_dssim",) if "dssim" in on else ())
     from tmdiff_amd.model import DDPM
     from tmdiff_amd.util import synthetic_tile_batch
 
@@ -140,7 +199,7 @@ def bench_step(reps, rounds, lines):
         torch.cuda.synchronize()
         return m, next(iter(m._captured.values()))
 
-    (plain, sp), (terms, st) = trainer(None), trainer({"sam": W_SAM, "lap": W_LAP})
+    (plain, sp), (terms, st) = trainer(None), trainer(on)
 
     def timed(step):
         ts = []
@@ -160,10 +219,10 @@ def bench_step(reps, rounds, lines):
     lines.append(f"captured finetune step (ch 32-256, batch 8 of 8 x 64 x 64, graph replay, device events; {rounds} alternating rounds of "
                  f"{reps} replays, median of the rounds' medians, least .. greatest round):")
     lines.append(f"  plain l1 (torch nn.L1Loss, no new code runs)   {statistics.median(a):8.3f} ms   ({min(a):.3f} .. {max(a):.3f})")
-    lines.append(f"  l1 + {W_SAM} sam + {W_LAP} lap (the kernel pair)        {statistics.median(b):8.3f} ms   ({min(b):.3f} .. {max(b):.3f})")
+    lines.append(f"  {label:<46s} {statistics.median(b):8.3f} ms   ({min(b):.3f} .. {max(b):.3f})")
     lines.append(f"  difference of the medians                      {1e3 * (statistics.median(b) - statistics.median(a)):8.1f} us")
     log = terms.get_current_log()
-    lines.append("  log of the last step with the terms on: " + " ".join(f"{k} {float(log[k]):.5f}" for k in ("l_pix", "l_base", "l_sam", "l_lap")))
+    lines.append("  log of the last step with the terms on: " + " ".join(f"{k} {float(log[k]):.5f}" for k in names))
 
 
 def main(argv=None):
@@ -173,11 +232,14 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--step", action="store_true", help="also time the captured finetune step with and without the terms")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--leg", choices=["composite", "ssim"], default="composite", help="ssim: the SSIM term's kernel pair (csrc/ssim_loss.hip)")
     args = ap.parse_args(argv)
     if args.reps < 7 or args.rounds < 7:
         raise SystemExit("bench_loss: medians of at least 7 runs")
     if not torch.cuda.is_available():
         raise SystemExit("bench_loss: needs the GPU (a time measured anywhere else says nothing)")
+    if args.leg == "ssim":
+        return main_ssim(args)
     lines = [f"# tools/bench_loss.py on {torch.cuda.get_device_name(0)}: l1 + {W_SAM} * SAM + {W_LAP} * LAP; per row the median over {args.reps} "
              f"replays of a graph of {args.calls} back-to-back evaluations (torch operators: {max(1, args.calls // 10)}), 10th .. 90th "
              f"percentile beside it, and the median of {args.reps} eager runs of 20 evaluations"]
@@ -190,6 +252,23 @@ def main(argv=None):
                  f"within 1.5 x 16 us)")
     if args.step:
         bench_step(args.reps, args.rounds, lines)
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+
+
+def main_ssim(args):
+    lines = [f"# tools/bench_loss.py --leg ssim on {torch.cuda.get_device_name(0)}: dssim = 1 - SSIM, 7 x 7 windows; per row the median over "
+             f"{args.reps} replays of a graph of {args.calls} back-to-back evaluations (torch operators: {max(1, args.calls // 10)}), 10th .. "
+             f"90th percentile beside it, and the median of {args.reps} eager runs of 20 evaluations"]
+    pairs = [bench_ssim_shape(shape, args.calls, args.reps, lines) for shape in ((8, 8, 64, 64), (32, 8, 64, 64))]
+    faster = all(p < t for p, t in pairs)
+    lines.append("the pair against the torch composition (both from a graph): " +
+                 ", ".join(f"{t / p:.2f} x" for p, t in pairs) + (" -- faster at both shapes" if faster else " -- NOT faster everywhere"))
+    if args.step:
+        bench_step(args.reps, args.rounds, lines, {"dssim": 0.1}, "l1 + 0.1 dssim (composite pair + SSIM pair)")
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if args.out:
