@@ -383,7 +383,8 @@ def test_wgrad_with_bias_gradient_on_the_side(shape):
 ])
 def test_weight_gradient_in_the_winograd_domain(case):
     """tmdiff_conv3d_wgrad_wino: F(3,4) along the bands (transform passes + per-plane MFMA accumulation + reduction with
-    A'^T) against CPU autograd in fp64 and against the direct weight-gradient kernel; deterministic."""
+    A'^T) against CPU autograd in fp64 and against the direct weight-gradient kernel; deterministic.  The kernel's edges
+    (padding, chunk and segment borders, split classes, exact-arithmetic and fp64 elementwise bounds): test_gpu_wgrad_wino_edges.py."""
     import torch.nn.functional as F
     from tmdiff_amd import ops
     B, segc, cout, N, H, W, groups, pro = case

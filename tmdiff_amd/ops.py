@@ -1471,9 +1471,12 @@ def _wgrad(entry, workspace_query, desc, g, weight_shape, want_bias, count_key, 
 def conv3d_wgrad(desc, g, weight_shape, want_bias=False, family=None):
     """dL/dw [Cout, Cin/g, k,k,k] for the convolution described by `desc` (a filled Conv3dDesc) given g = dL/dy; with
     want_bias also dL/dbias = desc.bias_scale * sum_{b,pos} g, accumulated inside the same kernel: returns (dw, dbias).
-    family: "wino" / "direct", the kernel a routing plan has chosen (plan.wgrad); None asks routing here (wgrad_wino_takes)."""
+    family: "wino" / "direct", the kernel a routing plan has chosen (plan.wgrad); None asks routing here (wgrad_wino_takes).
+    family="wino" on a convolution the Winograd kernel does not take raises ValueError before anything is allocated or counted."""
     if family is None:
         family = "wino" if wgrad_wino_takes(desc) else "direct"
+    elif family == "wino" and not lib.tmdiff_conv3d_wgrad_wino_supported(C.byref(desc)):
+        raise ValueError("conv3d_wgrad: family='wino' needs fp32 3x3x3, groups 1 or 3, N % 4 == 0 (at most 16), W % 4 == 0")
     macs = desc.B * desc.Cout * (desc.Cin // desc.groups) * desc.N * desc.H * desc.W
     if family == "wino":
         # Winograd F(3,4) along the bands (csrc/wgrad_wino.hip): 13.5 executed multiply-adds per element instead of 27
