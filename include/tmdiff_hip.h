@@ -756,6 +756,23 @@ int tmdiff_upsample_poly23(const float* x, float* y, int32_t planes, int32_t h, 
                            tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * FIR filtering with decimation (csrc/mtf.hip; host definition: tmdiff_amd/metrics.py, fir_decimate): the primitive of Wald's
+ * protocol, an MTF-matched low-pass per band followed by keeping every ratio-th sample.  Dense fp32 planes; nothing is
+ * allocated or synchronised, so a call can be captured into a graph on `stream`.
+ *   y[p, i, j] = sum_{u, v} taps[p % taps_period, u, v] * x[p, clamp(ratio i + off_y - R + u, 0, H - 1),
+ *                                                             clamp(ratio j + off_x - R + v, 0, W - 1)],   R = (K - 1) / 2
+ * a correlation (the taps are not flipped) with a replicated border; x [planes, H, W], taps [taps_period, K, K],
+ * y [planes, ceil((H - off_y) / ratio), ceil((W - off_x) / ratio)].  Only the kept samples are computed.  A pixel is one chain
+ * of fused multiply-adds from 0 over the taps in row-major order, whatever the tile, grid, plane or ratio that makes it.
+ * Checked in this order, each returning TMDIFF_E_UNSUPPORTED without launching: K odd and 1 <= K <= 41; ratio 1, 2 or 4;
+ * 0 <= off_y, off_x < ratio; H, W >= 1 and planes >= 0; taps_period >= 1 and a divisor of planes; planes * H * W <= 2^31 - 1
+ * (element offsets are 32-bit).  planes == 0, or an output without samples (H <= off_y or W <= off_x), returns TMDIFF_OK; a
+ * null tensor TMDIFF_E_INVALID.
+ * ------------------------------------------------------------------------------------ */
+int tmdiff_fir_decimate(const float* x, const float* taps, float* y, int32_t planes, int32_t taps_period, int32_t H, int32_t W,
+                        int32_t K, int32_t ratio, int32_t off_y, int32_t off_x, tmdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Standalone attention operators of core/Attention.py (imported by nothing in the reference; built because the
  * north star names them).  All fp32.
  *  attn_fwd : out = softmax(q k^T * scale [key mask]) v per (batch, head); fp32 MFMA, online softmax.

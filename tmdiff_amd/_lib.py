@@ -217,6 +217,8 @@ SIGNATURES.update({
     "tmdiff_pyr_down": (C.c_int, [vp, vp] + [C.c_int32] * 4 + [vp]),
     "tmdiff_upsample_bilinear": (C.c_int, [vp, vp] + [C.c_int32] * 4 + [vp]),
     "tmdiff_upsample_poly23": (C.c_int, [vp, vp] + [C.c_int32] * 5 + [vp]),      # ... ratio, phase
+    # FIR filtering with decimation (csrc/mtf.hip): x, taps, y | planes, taps_period, H, W, K, ratio, off_y, off_x
+    "tmdiff_fir_decimate": (C.c_int, [vp, vp, vp] + [C.c_int32] * 8 + [vp]),
 })
 
 

@@ -8,6 +8,7 @@ import ctypes as C
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib, routing
@@ -1444,6 +1445,60 @@ def upsample_poly23(x, ratio=4, out=None, phase=1):
     b, c, h, w = x.shape
     check(lib.tmdiff_upsample_poly23(px, py, b * c, h, w, ratio, phase, stream_ptr()), "upsample_poly23")
     return y
+
+
+# ---- MTF-matched filtering and decimation (csrc/mtf.hip; definitions: tmdiff_amd/metrics.py) -------------------------
+_FIR_LIMITS = "taps float32 [T, K, K] on the GPU, K odd and at most 41, T a divisor of B * C; ratio 1, 2 or 4; 0 <= offset < ratio"
+_MTF_TAPS = {}          # (gains, ratio, device) -> the uploaded [bands, 41, 41] table
+
+
+def fir_decimate_shape(h, w, ratio=1, offset=None):
+    """(H', W') of ``fir_decimate``: ceil((L - o) / ratio) per axis; ``offset`` None is ratio // 2 on both axes."""
+    from .metrics import fir_decimate_shape as shape_of
+    return shape_of(h, w, ratio, offset)[0]
+
+
+def fir_decimate(x, taps, ratio=1, offset=None, out=None):
+    """FIR filtering with decimation of x [B, C, H, W] (definition: ``metrics.fir_decimate``): plane p is correlated with
+    taps[p % T] ([T, K, K], or [K, K] for one table), the border replicated, and sampled at ``offset`` + ratio * i -> [B, C,
+    ceil((H - oy) / ratio), ceil((W - ox) / ratio)].  ``offset`` None is ratio // 2 on both axes, where ``upsample_poly23`` puts
+    the samples; a number serves both axes.  Only the kept samples are computed.  With ``out=`` nothing is allocated or
+    synchronised (graph capture)."""
+    from .metrics import fir_decimate_shape as shape_of
+    if ratio not in (1, 2, 4):
+        raise ValueError(f"fir_decimate: ratio={ratio} ({_FIR_LIMITS})")
+    if not (torch.is_tensor(taps) and taps.is_cuda and taps.dtype == torch.float32 and taps.dim() in (2, 3) and taps.is_contiguous()):
+        raise ValueError(f"fir_decimate: bad taps ({_FIR_LIMITS})")
+    t, k = (1 if taps.dim() == 2 else taps.shape[0]), taps.shape[-1]
+    if taps.shape[-2] != k or k % 2 == 0 or k > 41 or t < 1:
+        raise ValueError(f"fir_decimate: taps {tuple(taps.shape)} ({_FIR_LIMITS})")
+    oy, ox = shape_of(1, 1, ratio, offset)[1]
+    px, y, py = _resample_args("fir_decimate", x, lambda h, w: shape_of(h, w, ratio, offset)[0], out, _FIR_LIMITS)
+    b, c, h, w = x.shape
+    if (b * c) % t or taps.device != x.device:
+        raise ValueError(f"fir_decimate: taps {tuple(taps.shape)} on {taps.device} for {b * c} planes on {x.device} ({_FIR_LIMITS})")
+    check(lib.tmdiff_fir_decimate(px, taps.data_ptr(), py, b * c, t, h, w, k, ratio, oy, ox, stream_ptr()), "fir_decimate")
+    return y
+
+
+def mtf_degrade(x, gains_or_sensor, ratio=4, pan=False, out=None):
+    """Wald's degradation of x [B, C, H, W] (definition: ``metrics.mtf_degrade``): band c low-passed with the 41 x 41 MTF-matched
+    filter of its Nyquist gain and decimated by ``ratio`` at the offset ratio // 2 -> [B, C, ceil((H - o) / ratio), ...].
+    ``gains_or_sensor``: a sensor name (``metrics.mtf_gains``; with ``pan`` its PAN gain, for a one-band image), one gain per
+    band, or a number for every band.  The tap table is made on the host once per (gains, ratio, device) and kept on the
+    device: call once before capturing into a graph."""
+    from . import metrics
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
+        raise ValueError(f"mtf_degrade: need a float32 [B, C, H, W] tensor on the GPU ({_FIR_LIMITS})")
+    if ratio not in (1, 2, 4):
+        raise ValueError(f"mtf_degrade: ratio={ratio} ({_FIR_LIMITS})")
+    gains = metrics.band_gains(gains_or_sensor, x.shape[1], pan)
+    key = (gains, ratio, x.device)
+    taps = _MTF_TAPS.get(key)
+    if taps is None:
+        host = np.stack([metrics.mtf_kernel(g, ratio) for g in gains]).astype(np.float32)
+        taps = _MTF_TAPS[key] = torch.from_numpy(host).to(x.device)
+    return fir_decimate(x, taps, ratio, None, out)
 
 
 # ---- backward-side wrappers (finetune path) -----------------------------------------------------------

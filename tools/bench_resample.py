@@ -11,13 +11,20 @@ launches a few microseconds long, not HBM streaming rates: the copy of equal siz
 copy that bench_hbm_kernels.py quotes is printed for scale only.
 
 Timing: device events around `--reps` back-to-back launches after a warm-up of the same length, repeated `--rounds` times with
-the cases interleaved; the median round is reported with the least and the greatest."""
+the cases interleaved; the median round is reported with the least and the greatest.
+
+`--leg mtf`: MTF-matched filtering and decimation (csrc/mtf.hip), x4 with the 41 x 41 kernels of "WV3", at MS [1, 8, 1024, 1024]
+with PAN [1, 1, 4096, 4096] and at MS [32, 8, 256, 256] with PAN [32, 1, 1024, 1024]: the operator (`ops.mtf_degrade`) on the MS
+and on the PAN, `data.wald_pair` (both degradations, the 23-tap upsampling and the residual), and the torch composition of the
+operator -- replicate `F.pad`, the slice that starts at the offset, grouped `F.conv2d` with the ratio as its stride.  Every case
+is captured into a graph of `--graph-calls` calls; a round is the time of one replay over that count."""
 import argparse
 import os
 import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from tmdiff_amd import ops  # noqa: E402
@@ -35,16 +42,71 @@ def time_us(fn, reps):
     return e0.elapsed_time(e1) * 1e3 / reps
 
 
+def captured(fn, calls):
+    """A graph of `calls` calls of fn, after a warm-up on the capture stream."""
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        for _ in range(2):
+            fn()
+    stream.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=stream):
+        for _ in range(calls):
+            fn()
+    return graph
+
+
+def mtf_leg(args):
+    import torch.nn.functional as F
+    from tmdiff_amd import metrics
+    from tmdiff_amd.data import wald_pair
+    sensor, ratio, k = "WV3", 4, metrics.MTF_TAPS
+    ms_gains, pan_gain = metrics.mtf_gains(sensor, 8)
+
+    def composition(x, gains):
+        w = torch.from_numpy(np.stack([metrics.mtf_kernel(g, ratio) for g in gains])).float().cuda()[:, None]
+        return lambda: F.conv2d(F.pad(x, (k // 2,) * 4, mode="replicate")[..., ratio // 2:, ratio // 2:], w, stride=ratio, groups=len(gains))
+
+    cases = []          # (name, call, multiply-adds)
+    for b, h in ((1, 1024), (32, 256)):
+        ms, pan = torch.rand(b, 8, h, h, device="cuda"), torch.rand(b, 1, ratio * h, ratio * h, device="cuda")
+        lr, low = ops.mtf_degrade(ms, sensor, ratio), ops.mtf_degrade(pan, sensor, ratio, pan=True)
+        for name, x, gains, y, is_pan in (("MS ", ms, ms_gains, lr, False), ("PAN", pan, (pan_gain,), low, True)):
+            macs = y.numel() * k * k
+            ref = composition(x, gains)
+            err = float((ref() - y).abs().max())
+            print(f"{name} {list(x.shape)}: max |operator - torch composition| = {err:.3e}", flush=True)
+            cases.append((f"mtf_degrade      {name} {list(x.shape)}", lambda x=x, y=y, p=is_pan: ops.mtf_degrade(x, sensor, ratio, pan=p, out=y), macs))
+            cases.append((f"pad+slice+conv2d {name} {list(x.shape)}", ref, macs))
+        cases.append((f"wald_pair        MS  {list(ms.shape)} + PAN", lambda ms=ms, pan=pan: wald_pair(ms, pan, sensor, ratio),
+                      (lr.numel() + low.numel()) * k * k))
+    graphs = [captured(fn, args.graph_calls) for _, fn, _ in cases]
+    times = [[] for _ in cases]
+    for _ in range(args.rounds):
+        for graph, t in zip(graphs, times):
+            time_us(graph.replay, 1)
+            t.append(time_us(graph.replay, 1) / args.graph_calls)
+    print(f"{'case':52s} {'us per call (min..max)':>30s} {'GMAC/s':>9s}")
+    for (name, _, macs), t in zip(cases, times):
+        m = statistics.median(t)
+        print(f"{name:52s} {m:10.2f} ({min(t):8.2f}..{max(t):8.2f}) {macs / m / 1e3:9.1f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--leg", choices=("resample", "mtf"), default="resample")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--graph-calls", type=int, default=10, help="--leg mtf: calls captured into each graph")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_resample.py needs the GPU: a rate cannot be measured without one")
     p = torch.cuda.get_device_properties(0)
     print(f"device: {p.name} ({getattr(p, 'gcnArchName', '?')}), {p.multi_processor_count} CUs, {p.total_memory / 2 ** 30:.0f} GiB; "
           f"torch {torch.__version__}, HIP {torch.version.hip}; reps {args.reps}, rounds {args.rounds}", flush=True)
+    if args.leg == "mtf":
+        return mtf_leg(args)
 
     cases = []          # (name, kernel call, bytes, copy call, bytes the copy moves)
 
