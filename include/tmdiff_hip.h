@@ -664,6 +664,29 @@ int tmdiff_metrics_q2n(const float* x_true, int64_t true_stride_b, int64_t true_
                        tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * The spatial term of HQNR on the device (csrc/metrics.hip; definition: tmdiff_amd/metrics.py d_s_block): per band c and per
+ * non-overlapping block x block window (the grid and the mirroring of tmdiff_metrics_q2n at shift = block) the universal
+ * quality index with sample moments, Q_high = Q(ps_c, pan) and Q_low = Q(ms_exp_c, pan_lp); both are averaged over the
+ * windows and D_s = (mean_c |Q_high_c - Q_low_c|^q)^(1/q).  A window that is constant in both images, or whose means are both
+ * zero, is NaN (0 / 0) and the NaN reaches D_s: no eps is added.
+ * ps, ms_exp: fp32 [B, C, H, W] with batch and channel strides in elements; pan, pan_lp: fp32 [B, 1, H, W] with a batch
+ * stride; rows and planes dense.  out: fp64 [B, 2] = D_s, HQNR.  With d_lambda, fp64 [B] on the device, HQNR =
+ * (1 - d_lambda)^alpha (1 - D_s)^beta is written; with NULL the second column is left untouched.  maps_out: fp64
+ * [B, C, 2, ny, nx] of the windows' Q_high and Q_low, or NULL.  workspace: 8-byte aligned,
+ * tmdiff_metrics_dsblock_workspace_bytes(...) bytes.  Sums, reproducibility and graph capture as for tmdiff_metrics_pair.
+ * Extents: 1 <= C <= 16, block 8, 16 or 32, mirrored rows / columns no more than H / W, B * C * H * W <= 2^31 - 1, q > 0; for
+ * anything else tmdiff_metrics_dsblock_supported is 0, the workspace size is 0 and the entry point returns
+ * TMDIFF_E_UNSUPPORTED without launching.
+ * ------------------------------------------------------------------------------------ */
+int tmdiff_metrics_dsblock_supported(int32_t B, int32_t C, int32_t H, int32_t W, int32_t block);
+size_t tmdiff_metrics_dsblock_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t block);
+int tmdiff_metrics_dsblock(const float* ps, int64_t ps_stride_b, int64_t ps_stride_c, const float* ms_exp, int64_t ms_stride_b,
+                           int64_t ms_stride_c, const float* pan, int64_t pan_stride_b, const float* pan_lp,
+                           int64_t pan_lp_stride_b, int32_t B, int32_t C, int32_t H, int32_t W, int32_t block, double q,
+                           const double* d_lambda, double alpha, double beta, double* out, double* maps_out, void* workspace,
+                           size_t workspace_bytes, tmdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * The composite finetune loss with its gradient, one pass (csrc/loss.hip; host definition: tmdiff_amd/losses.py):
  *     L = base(xhat, x0) + w_sam * SAM(x0 + ms, xhat + ms) + w_lap * LAP(xhat - x0)
  * on dense fp32 [B, C, H, W] tensors.

@@ -202,6 +202,11 @@ SIGNATURES.update({
     "tmdiff_metrics_q2n_workspace_bytes": (C.c_size_t, [C.c_int32] * 6),
     "tmdiff_metrics_q2n": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64] + [C.c_int32] * 6 +
                            [vp, vp, vp, C.c_size_t, vp]),                    # ... block, shift, out, map_out, workspace
+    "tmdiff_metrics_dsblock_supported": (C.c_int, [C.c_int32] * 5),
+    "tmdiff_metrics_dsblock_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    # ps, strides, ms_exp, strides, pan, stride, pan_lp, stride | B, C, H, W, block | q, d_lambda, alpha, beta | out, maps, workspace
+    "tmdiff_metrics_dsblock": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp, C.c_int64, vp, C.c_int64] +
+                               [C.c_int32] * 5 + [C.c_double, vp, C.c_double, C.c_double, vp, vp, vp, C.c_size_t, vp]),
     # composite finetune loss (csrc/loss.hip): x0, xhat, ms, g | base_kind, w_sam, w_lap | out64, out32, workspace, bytes | B, C, H, W
     "tmdiff_loss_supported": (C.c_int, [C.c_int32] * 5),
     "tmdiff_loss_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),

@@ -18,6 +18,12 @@
 //                        of the pixels.  The normalised moments the definition asks for are affine in these, so no lane divides
 //                        per pixel.  The workgroup then evaluates the hypercomplex product through the sign table and stores the
 //                        block's value; metrics_q2n_finalize_kernel averages them per image in a fixed order.
+//  metrics_dsblock_kernel  the spatial term of HQNR (metrics.d_s_block): one workgroup per block x block window of one image.
+//                        The windows of pan and of the low-pass pan are staged once (mirrored like Q2n's), those of the fused
+//                        and the interpolated MS image band by band; per band two passes over LDS, the means and then the
+//                        centred sums, give Q(ps_c, pan) and Q(ms_c, pan_lp) of the window.
+//                        metrics_dsblock_finalize_kernel averages the windows per band in a fixed order, forms D_s and, given
+//                        the image's D_lambda, HQNR.
 //
 // Every sum is fp64 (products of two fp32 values are exact there): at sensor scale (mean 1000, sigma 5) a variance is a 4e4-th
 // of the raw second moment, which fp32 sums would lose entirely.  No atomics: each workgroup stores its partial sums with plain
@@ -568,6 +574,136 @@ __global__ void __launch_bounds__(256) metrics_q2n_finalize_kernel(const double*
   if (t == 0) out[img] = s / (double)nblk;
 }
 
+// ---- block-wise D_s of HQNR ----------------------------------------------------------------------------------------------
+struct DsArgs {
+  const float* ps;    // fused image
+  const float* ms;    // MS interpolated to the PAN grid
+  const float* pan;   // one band
+  const float* lp;    // low-pass PAN, one band
+  long psB, psC, msB, msC, panB, lpB;
+  int C, H, W, block, nx, nblk;
+  double* vals;       // [B][C][2][nblk]: Q(ps_c, pan), then Q(ms_c, lp), per window
+  double* map;        // the same layout, or null
+};
+
+// sum over the workgroup of N values per lane, in every lane: the waves' butterflies, then the four waves in order
+template <int N>
+__device__ __forceinline__ void wg_sum(double (&v)[N], double (*red)[NBAND + 5], int lane, int wave) {
+  __syncthreads();   // earlier readers of red are done
+  waves_to_lds<N>(v, red, lane, wave);
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+}
+
+// metrics.q_index's formula from centred sums over n1 + 1 samples.  No contraction and the host's order of operations; a window
+// constant in both images, or with both means zero, is 0 / 0 = NaN as on the host.
+__device__ __forceinline__ double uqi_of(double saa, double sbb, double sab, double ma, double mb, double n1) {
+#pragma clang fp contract(off)
+  const double d1 = saa / n1, d2 = sbb / n1, cov = sab / n1;
+  return 4.0 * cov * ma * mb / (d1 + d2) / (ma * ma + mb * mb);
+}
+
+__global__ void __launch_bounds__(256) metrics_dsblock_kernel(DsArgs p) {
+  __shared__ float win[4][32 * 32];       // the window of ps_c, ms_c, pan, lp
+  __shared__ double red[4][NBAND + 5];
+
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int block = p.block, n = block * block, lb = block == 8 ? 3 : block == 16 ? 4 : 5;
+  const int img = blockIdx.x / p.nblk, blk = blockIdx.x - img * p.nblk;
+  const int by = blk / p.nx, bx = blk - by * p.nx, y0 = by * block, x0 = bx * block;
+  const double nn = (double)n, n1 = nn - 1.0;
+
+  // staging: row H + k is row H - 1 - k (the host checked that the mirror stays inside the image)
+  auto stage = [&](const float* src, float* dst) {
+    for (int px = t; px < n; px += 256) {
+      int yy = y0 + (px >> lb), xx = x0 + (px & (block - 1));
+      yy = yy < p.H ? yy : 2 * p.H - 1 - yy;
+      xx = xx < p.W ? xx : 2 * p.W - 1 - xx;
+      dst[px] = src[yy * p.W + xx];
+    }
+  };
+  stage(p.pan + (long)img * p.panB, win[2]);
+  stage(p.lp + (long)img * p.lpB, win[3]);
+  __syncthreads();
+
+  // the two PAN windows serve every band: their means and centred squares once
+  double mp[2] = {0.0, 0.0};
+  for (int px = t; px < n; px += 256) mp[0] += (double)win[2][px], mp[1] += (double)win[3][px];
+  wg_sum<2>(mp, red, lane, wave);
+  mp[0] /= nn; mp[1] /= nn;
+  double sp[2] = {0.0, 0.0};
+  for (int px = t; px < n; px += 256) {
+    const double dp = (double)win[2][px] - mp[0], dq = (double)win[3][px] - mp[1];
+    sp[0] += dp * dp; sp[1] += dq * dq;
+  }
+  wg_sum<2>(sp, red, lane, wave);
+
+  for (int c = 0; c < p.C; ++c) {
+    __syncthreads();   // the last band's readers of win are done
+    stage(p.ps + (long)img * p.psB + (long)c * p.psC, win[0]);
+    stage(p.ms + (long)img * p.msB + (long)c * p.msC, win[1]);
+    __syncthreads();
+    double m[2] = {0.0, 0.0};
+    for (int px = t; px < n; px += 256) m[0] += (double)win[0][px], m[1] += (double)win[1][px];
+    wg_sum<2>(m, red, lane, wave);
+    m[0] /= nn; m[1] /= nn;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};   // centred: a raw second moment at sensor scale would lose the variance
+    for (int px = t; px < n; px += 256) {
+      const double da = (double)win[0][px] - m[0], db = (double)win[1][px] - m[1];
+      const double dp = (double)win[2][px] - mp[0], dq = (double)win[3][px] - mp[1];
+      s[0] += da * da; s[1] += da * dp; s[2] += db * db; s[3] += db * dq;
+    }
+    wg_sum<4>(s, red, lane, wave);
+    if (t == 0) {
+      const double qh = uqi_of(s[0], sp[0], s[1], m[0], mp[0], n1), ql = uqi_of(s[2], sp[1], s[3], m[1], mp[1], n1);
+      const long at = (((long)img * p.C + c) * 2) * p.nblk + blk;
+      p.vals[at] = qh; p.vals[at + p.nblk] = ql;
+      if (p.map) p.map[at] = qh, p.map[at + p.nblk] = ql;
+    }
+  }
+}
+
+struct DsFinalArgs {
+  const double* vals;   // [B][C][2][nblk]
+  int C, nblk;
+  double q, alpha, beta;
+  const double* dl;     // [B] D_lambda of each image, or null
+  double* out;          // [B][2]: D_s, HQNR (left alone without dl)
+};
+
+__device__ __forceinline__ double pow_exact1(double x, double e) { return e == 1.0 ? x : e == 2.0 ? x * x : pow(x, e); }
+
+// Per (band, high / low) lane t adds the windows t, t + 256, ... in order; then the waves' butterflies and the four waves in
+// order: the order depends on the number of windows alone.
+__global__ void __launch_bounds__(256) metrics_dsblock_finalize_kernel(DsFinalArgs p) {
+  __shared__ double red[2 * MAXC][4];
+  const int t = threadIdx.x, img = blockIdx.x;
+  for (int k = 0; k < 2 * p.C; ++k) {
+    const double* src = p.vals + ((long)img * 2 * p.C + k) * p.nblk;
+    double s = 0.0;
+    for (int i = t; i < p.nblk; i += 256) s += src[i];
+    s = tmdiff::wave_sum(s);
+    if ((t & 63) == 0) red[k][t >> 6] = s;
+  }
+  __syncthreads();
+  if (t != 0) return;
+  {
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    for (int c = 0; c < p.C; ++c) {
+      const double* h = red[2 * c];
+      const double* l = red[2 * c + 1];
+      const double qh = (((h[0] + h[1]) + h[2]) + h[3]) / (double)p.nblk, ql = (((l[0] + l[1]) + l[2]) + l[3]) / (double)p.nblk;
+      acc += pow_exact1(fabs(qh - ql), p.q);
+    }
+    acc /= (double)p.C;
+    const double ds = p.q == 1.0 ? acc : p.q == 2.0 ? sqrt(acc) : pow(acc, 1.0 / p.q);
+    p.out[(long)img * 2] = ds;
+    if (p.dl) p.out[(long)img * 2 + 1] = pow_exact1(1.0 - p.dl[img], p.alpha) * pow_exact1(1.0 - ds, p.beta);
+  }
+}
+
 // Cayley-Dickson product of two n-vectors (n a power of two; metrics.cd_mul): with p = (a, b), r = (c, d),
 // p r = (a c - d conj(b), conj(a) d + c b)
 void cd_mul(const double* p, const double* r, double* out, int n) {
@@ -734,6 +870,44 @@ int tmdiff_metrics_q2n(const float* x_true, int64_t true_stride_b, int64_t true_
   if (const int rc = tmdiff::check_launch("metrics_q2n")) return rc;
   metrics_q2n_finalize_kernel<<<B, 256, 0, st>>>(a.vals, a.nblk, out);
   return tmdiff::check_launch("metrics_q2n (finalize)");
+}
+
+int tmdiff_metrics_dsblock_supported(int32_t B, int32_t C, int32_t H, int32_t W, int32_t block) {
+  return q2n_ok(B, C, H, W, block, block);
+}
+
+size_t tmdiff_metrics_dsblock_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t block) {
+  Q2nGrid g;
+  if (!q2n_ok(B, C, H, W, block, block, &g)) return 0;
+  return (size_t)B * C * 2 * g.ny * g.nx * sizeof(double);
+}
+
+int tmdiff_metrics_dsblock(const float* ps, int64_t ps_stride_b, int64_t ps_stride_c, const float* ms_exp, int64_t ms_stride_b,
+                           int64_t ms_stride_c, const float* pan, int64_t pan_stride_b, const float* pan_lp, int64_t pan_lp_stride_b,
+                           int32_t B, int32_t C, int32_t H, int32_t W, int32_t block, double q, const double* d_lambda, double alpha,
+                           double beta, double* out, double* maps_out, void* workspace, size_t workspace_bytes,
+                           tmdiff_stream_t stream) {
+  Q2nGrid g;
+  if (!q2n_ok(B, C, H, W, block, block, &g) || (double)B * C * 2 * g.ny * g.nx > 2147483647.0)
+    return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "metrics_dsblock: B=%d C=%d H=%d W=%d block=%d (1 <= C <= 16, block 8, 16 or 32, mirror "
+                        "padding no longer than the axis, fewer than 2^31 elements)", B, C, H, W, block);
+  if (!(q > 0.0 && q <= 1e6) || !(alpha == alpha) || !(beta == beta))
+    return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "metrics_dsblock: q=%g alpha=%g beta=%g (q > 0, exponents not NaN)", q, alpha, beta);
+  if (B == 0) return TMDIFF_OK;
+  const size_t need = (size_t)B * C * 2 * g.ny * g.nx * sizeof(double);
+  TMDIFF_REQUIRE(ps && ms_exp && pan && pan_lp && out && workspace, "metrics_dsblock: null tensor");
+  TMDIFF_REQUIRE(ps_stride_b >= 0 && ps_stride_c >= (int64_t)H * W && ms_stride_b >= 0 && ms_stride_c >= (int64_t)H * W &&
+                     pan_stride_b >= 0 && pan_lp_stride_b >= 0, "metrics_dsblock: channel strides below a plane of %d x %d", H, W);
+  TMDIFF_REQUIRE(workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0,
+                 "metrics_dsblock: workspace of %zu bytes, %zu needed (8-byte aligned)", workspace_bytes, need);
+  const hipStream_t st = tmdiff::as_stream(stream);
+  const DsArgs a{ps, ms_exp, pan, pan_lp, ps_stride_b, ps_stride_c, ms_stride_b, ms_stride_c, pan_stride_b, pan_lp_stride_b,
+                 C, H, W, block, g.nx, g.ny * g.nx, static_cast<double*>(workspace), maps_out};
+  metrics_dsblock_kernel<<<(unsigned)((long)B * a.nblk), 256, 0, st>>>(a);
+  if (const int rc = tmdiff::check_launch("metrics_dsblock")) return rc;
+  const DsFinalArgs f{a.vals, C, a.nblk, q, alpha, beta, d_lambda, out};
+  metrics_dsblock_finalize_kernel<<<B, 256, 0, st>>>(f);
+  return tmdiff::check_launch("metrics_dsblock (finalize)");
 }
 
 }  // extern "C"

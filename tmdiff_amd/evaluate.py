@@ -31,7 +31,7 @@ def _to_nchw01(img, min_max=(0.0, 1.0)):
 
 
 def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=print, device_metrics=False,
-                full_resolution=False, q2n=False):
+                full_resolution=False, q2n=False, protocol="qnr", sensor=None):
     """``trainer`` is a ``tmdiff_amd.model.DDPM`` (or the reference's); ``dataset`` is the prompt name.
     Returns ``{"ssim_<dataset>": ..., "sam_<dataset>": ..., "sec_per_item": ...}``.
 
@@ -48,7 +48,24 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
 
     ``q2n=True`` (with ``device_metrics=True`` only, and not with ``full_resolution=True``: ValueError otherwise) adds
     ``q2n_<dataset>``: the mean over the items of ``ops.metrics_q2n`` (Q4 / Q8 on 32 x 32 blocks), accumulated on the device with
-    its workspace allocated once per shape and read in the same synchronising read."""
+    its workspace allocated once per shape and read in the same synchronising read.
+
+    ``protocol="hqnr"`` (with ``full_resolution=True`` only: ValueError otherwise) scores each item with the set the
+    PanCollection tables report instead: ``ops.metrics_hqnr(SR, MS, PAN, sensor)`` -- Khan's D_lambda, the block-wise D_s and
+    HQNR (``metrics.hqnr``) -- with the buffers made once per shape, sums kept on the device and one synchronising read.  Returns
+    ``{"d_lambda_k_<dataset>": ..., "d_s_<dataset>": ..., "hqnr_<dataset>": ..., "sec_per_item": ...}``; ValueError when the
+    visuals carry no ``MS`` or ``PAN``.  ``sensor`` names the row of ``metrics.MTF_GAINS`` (or is a pair of explicit gains); it
+    defaults to ``dataset`` when that has a row of its own -- a sensor name as it stands, never a prompt name translated -- and
+    is required otherwise.  ``protocol="qnr"`` is the behaviour and the keys described above."""
+    if protocol not in ("qnr", "hqnr"):
+        raise ValueError(f"val_dataset: protocol={protocol!r} ('qnr' or 'hqnr')")
+    hqnr = protocol == "hqnr"
+    if hqnr and not full_resolution:
+        raise ValueError("val_dataset(protocol='hqnr') scores without ground truth: it needs full_resolution=True")
+    if hqnr and sensor is None:
+        if dataset not in metrics.MTF_GAINS:
+            raise ValueError(f"val_dataset(protocol='hqnr'): {dataset!r} has no row in metrics.MTF_GAINS: give the sensor")
+        sensor = dataset
     if q2n and (full_resolution or not device_metrics):
         raise ValueError("val_dataset(q2n=True) scores on the GPU against ground truth: it needs device_metrics=True and "
                          "full_resolution=False")
@@ -64,11 +81,19 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
         trainer.feed_data(val_data)
         trainer.test(continous=continous, prompt=dataset)
         vis = trainer.get_current_visuals()
-        if full_resolution and not ("LR" in vis and "PAN" in vis):
-            raise ValueError(f"val_dataset(full_resolution=True): the visuals need 'LR' and 'PAN', got {sorted(vis)}")
+        if full_resolution and not (("MS" if hqnr else "LR") in vis and "PAN" in vis):
+            raise ValueError(f"val_dataset(full_resolution=True): the visuals need '{'MS' if hqnr else 'LR'}' and 'PAN', "
+                             f"got {sorted(vis)}")
         sr = to_hwc01(vis["SR"][-1])                       # last image of the returned stack (ref :136)
         scio.savemat(os.path.join(result_path, f"output_mulExm_{idx}.mat"), {"sr": sr * scale})
-        if full_resolution:
+        if hqnr:
+            from . import ops
+            ms_d, pan_d, sr_d = _to_nchw01(vis["MS"]), _to_nchw01(vis["PAN"]), _to_nchw01(vis["SR"][-1])
+            if sr_d.shape not in full_ws:
+                full_ws[sr_d.shape] = ops.metrics_hqnr_buffers(*sr_d.shape, sr_d.device)
+            row = ops.metrics_hqnr(sr_d, ms_d, pan_d, sensor, buffers=full_ws[sr_d.shape])[0]
+            full_sum = row if full_sum is None else full_sum + row
+        elif full_resolution:
             from . import ops
             lr_d, pan_d, sr_d = _to_nchw01(vis["LR"]), _to_nchw01(vis["PAN"]), _to_nchw01(vis["SR"][-1])
             key = (lr_d.shape, sr_d.shape)
@@ -95,8 +120,9 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
             sam_sum += metrics.sam(hr, sr)
         n += 1
     if full_resolution:
-        total = full_sum.tolist() if full_sum is not None else [0.0] * len(metrics.NOREF_FIELDS)   # the one synchronising read
-        score = {**{f"{k}_{dataset}": v / max(n, 1) for k, v in zip(metrics.NOREF_FIELDS, total)},
+        fields = metrics.HQNR_FIELDS if hqnr else metrics.NOREF_FIELDS
+        total = full_sum.tolist() if full_sum is not None else [0.0] * len(fields)   # the one synchronising read
+        score = {**{f"{k}_{dataset}": v / max(n, 1) for k, v in zip(fields, total)},
                  "sec_per_item": (time.time() - t0) / max(n, 1)}
         log(dataset, score)
         return score

@@ -1493,12 +1493,136 @@ def mtf_degrade(x, gains_or_sensor, ratio=4, pan=False, out=None):
     if ratio not in (1, 2, 4):
         raise ValueError(f"mtf_degrade: ratio={ratio} ({_FIR_LIMITS})")
     gains = metrics.band_gains(gains_or_sensor, x.shape[1], pan)
-    key = (gains, ratio, x.device)
+    return fir_decimate(x, _mtf_taps(gains, ratio, x.device), ratio, None, out)
+
+
+def _mtf_taps(gains, ratio, device):
+    """The [bands, 41, 41] float32 table of ``metrics.mtf_kernel`` on the device, made once per (gains, ratio, device)."""
+    from . import metrics
+    key = (tuple(gains), ratio, device)
     taps = _MTF_TAPS.get(key)
     if taps is None:
         host = np.stack([metrics.mtf_kernel(g, ratio) for g in gains]).astype(np.float32)
-        taps = _MTF_TAPS[key] = torch.from_numpy(host).to(x.device)
-    return fir_decimate(x, taps, ratio, None, out)
+        taps = _MTF_TAPS[key] = torch.from_numpy(host).to(device)
+    return taps
+
+
+# ---- HQNR: Khan's D_lambda, block-wise D_s (csrc/metrics.hip, csrc/mtf.hip; definitions: tmdiff_amd/metrics.py) ------
+_DSBLOCK_LIMITS = "1 <= C <= 16, block 8, 16 or 32, mirror padding no longer than the axis, fewer than 2^31 elements, q > 0"
+
+
+def metrics_dsblock_supported(b, c, h, w, block=32):
+    """True when metrics_dsblock takes a [b, c, h, w] image batch with these windows."""
+    return bool(lib.tmdiff_metrics_dsblock_supported(int(b), int(c), int(h), int(w), int(block)))
+
+
+def metrics_dsblock_workspace(b, c, h, w, device, block=32):
+    """A workspace metrics_dsblock accepts for [b, c, h, w] images (reusable; captured calls must keep it alive)."""
+    nbytes = lib.tmdiff_metrics_dsblock_workspace_bytes(int(b), int(c), int(h), int(w), int(block))
+    return torch.empty(max(1, nbytes // 8), device=device, dtype=torch.float64)
+
+
+def metrics_dsblock(ps, ms_exp, pan, pan_lp, block=32, q=1.0, out=None, maps_out=None, workspace=None, d_lambda=None, alpha=1.0,
+                    beta=1.0):
+    """The block-wise D_s of HQNR (definition: ``metrics.d_s_block``) of ps and ms_exp, float32 [B, C, H, W], with pan and
+    pan_lp, float32 [B, 1, H, W]: float64 [B].  ``out`` is a float64 [B, 2] tensor whose first column is returned; with
+    ``d_lambda``, a contiguous float64 [B] device tensor, its second column receives (1 - d_lambda)^alpha (1 - D_s)^beta and is
+    otherwise left alone.  ``maps_out``, float64 [B, C, 2, ny, nx] (``q2n_grid`` at shift = block), receives the windows'
+    Q(ps_c, pan) and Q(ms_exp_c, pan_lp).  A window constant in both images is NaN there and in D_s."""
+    if ps.shape != ms_exp.shape:
+        raise ValueError(f"metrics_dsblock: shapes {tuple(ps.shape)} and {tuple(ms_exp.shape)} differ")
+    pa, asb, asc = _planes(ps, "ps")
+    pb, bsb, bsc = _planes(ms_exp, "ms_exp")
+    b, c, h, w = ps.shape
+    pp, psb, _ = _planes(pan, "pan", 1)
+    pq, qsb, _ = _planes(pan_lp, "pan_lp", 1)
+    if tuple(pan.shape) != (b, 1, h, w) or tuple(pan_lp.shape) != (b, 1, h, w):
+        raise ValueError(f"metrics_dsblock: pan {tuple(pan.shape)} and pan_lp {tuple(pan_lp.shape)} must be [{b}, 1, {h}, {w}]")
+    block, q = int(block), float(q)
+    if not metrics_dsblock_supported(b, c, h, w, block) or not q > 0.0:
+        raise ValueError(f"metrics_dsblock: B={b} C={c} H={h} W={w} block={block} q={q} is not supported ({_DSBLOCK_LIMITS})")
+    ny, nx = q2n_grid(h, w, block, block)
+    dev = ps.device
+    y = out if out is not None else torch.empty(b, 2, device=dev, dtype=torch.float64)
+    if not (y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and tuple(y.shape) == (b, 2)):
+        raise ValueError(f"metrics_dsblock: out must be a contiguous float64 [{b}, 2] tensor on the GPU")
+    if maps_out is not None and not (maps_out.is_cuda and maps_out.dtype == torch.float64 and maps_out.is_contiguous()
+                                     and tuple(maps_out.shape) == (b, c, 2, ny, nx)):
+        raise ValueError(f"metrics_dsblock: maps_out must be a contiguous float64 [{b}, {c}, 2, {ny}, {nx}] tensor on the GPU")
+    if d_lambda is not None and not (d_lambda.is_cuda and d_lambda.dtype == torch.float64 and d_lambda.is_contiguous()
+                                     and tuple(d_lambda.shape) == (b,)):
+        raise ValueError(f"metrics_dsblock: d_lambda must be a contiguous float64 [{b}] tensor on the GPU")
+    ws = workspace if workspace is not None else metrics_dsblock_workspace(b, c, h, w, dev, block)
+    nbytes, need = ws.numel() * ws.element_size(), lib.tmdiff_metrics_dsblock_workspace_bytes(b, c, h, w, block)
+    if not (ws.is_cuda and ws.is_contiguous() and nbytes >= need):
+        raise ValueError(f"metrics_dsblock: workspace of {nbytes} bytes, need {need}")
+    check(lib.tmdiff_metrics_dsblock(pa, asb, asc, pb, bsb, bsc, pp, psb, pq, qsb, b, c, h, w, block, q,
+                                     d_lambda.data_ptr() if d_lambda is not None else None, float(alpha), float(beta),
+                                     y.data_ptr(), maps_out.data_ptr() if maps_out is not None else None, ws.data_ptr(), nbytes,
+                                     stream_ptr()), "metrics_dsblock")
+    return y[:, 0]
+
+
+def pan_lowpass(pan, sensor_or_gain, ratio=4, out=None, low=None):
+    """The PAN [B, 1, H, W] at the resolution of the MS, on its own grid (definition: ``metrics.pan_lowpass``):
+    ``upsample_poly23(mtf_degrade(pan, ..., ratio, pan=True), ratio)``; ratio 2 or 4, H and W multiples of it.  ``low``
+    lends the [B, 1, H / ratio, W / ratio] stage; with it and ``out=`` nothing is allocated (the tap table is cached as
+    ``mtf_degrade`` caches it: call once before capturing into a graph)."""
+    if not (torch.is_tensor(pan) and pan.is_cuda and pan.dim() == 4 and pan.shape[1] == 1):
+        raise ValueError("pan_lowpass: need a float32 [B, 1, H, W] tensor on the GPU")
+    if ratio not in (2, 4) or pan.shape[2] % ratio or pan.shape[3] % ratio or min(pan.shape[2:]) < ratio:
+        raise ValueError(f"pan_lowpass: shape {tuple(pan.shape)} ratio={ratio} (ratio 2 or 4, H and W multiples of it)")
+    return upsample_poly23(mtf_degrade(pan, sensor_or_gain, ratio, pan=True, out=low), ratio, out=out)
+
+
+def metrics_hqnr_buffers(b, c, h, w, device, ratio=4, block=32):
+    """Every scratch tensor of ``metrics_hqnr`` for [b, c, h, w] images: with them a second call allocates nothing and can be
+    captured into a graph.  "filtered": the MTF-filtered fused image; "pan_lp" and "pan_low": the low-pass PAN and its
+    low-resolution stage; "q2n", "d_lambda", "d_s": the chain's float64 results; "q2n_ws", "ds_ws": the kernels' workspaces."""
+    if ratio not in (2, 4) or h % ratio or w % ratio:
+        raise ValueError(f"metrics_hqnr: H={h} W={w} ratio={ratio} (ratio 2 or 4, H and W multiples of it)")
+    if not metrics_dsblock_supported(b, c, h, w, block):
+        raise ValueError(f"metrics_hqnr: B={b} C={c} H={h} W={w} block={block} is not supported ({_DSBLOCK_LIMITS})")
+    f32 = dict(device=device, dtype=torch.float32)
+    f64 = dict(device=device, dtype=torch.float64)
+    return {"shape": (b, c, h, w, ratio, block),
+            "filtered": torch.empty(b, c, h, w, **f32), "pan_lp": torch.empty(b, 1, h, w, **f32),
+            "pan_low": torch.empty(b, 1, h // ratio, w // ratio, **f32),
+            "q2n": torch.empty(b, **f64), "d_lambda": torch.empty(b, **f64), "d_s": torch.empty(b, 2, **f64),
+            "q2n_ws": metrics_q2n_workspace(b, c, h, w, device, block, block),
+            "ds_ws": metrics_dsblock_workspace(b, c, h, w, device, block)}
+
+
+def metrics_hqnr(ps, ms_exp, pan, sensor, ratio=4, block=32, alpha=1.0, beta=1.0, q=1.0, pan_lp=None, out=None, buffers=None):
+    """Khan's D_lambda, the block-wise D_s and HQNR (definition: ``metrics.hqnr``) of the fused ps [B, C, H, W] with pan
+    [B, 1, H, W] against ms_exp, the MS interpolated to the PAN grid: float64 [B, 3] in the column order of
+    metrics.HQNR_FIELDS.  ps is filtered at full scale with the sensor's 41 x 41 MTF filters (``fir_decimate`` at ratio 1) and
+    scored against ms_exp with ``metrics_q2n``; ``pan_lp`` None is ``pan_lowpass(pan, sensor's PAN gain, ratio)``;
+    ``metrics_dsblock`` then forms D_s and the product.  ``sensor``: a name or a pair (MS gains, PAN gain), as
+    ``metrics.mtf_gains`` takes them.  With ``buffers`` (``metrics_hqnr_buffers``) and ``out=`` nothing is allocated or
+    synchronised; the tap tables are cached as ``mtf_degrade`` caches its own: call once before capturing into a graph."""
+    from . import metrics
+    if not (torch.is_tensor(ps) and ps.is_cuda and ps.dim() == 4) or ps.shape != ms_exp.shape:
+        raise ValueError("metrics_hqnr: ps and ms_exp must be float32 [B, C, H, W] tensors of one shape on the GPU")
+    b, c, h, w = ps.shape
+    block = int(block)
+    buf = buffers if buffers is not None else metrics_hqnr_buffers(b, c, h, w, ps.device, ratio, block)
+    if buf["shape"] != (b, c, h, w, ratio, block) or buf["filtered"].device != ps.device:
+        raise ValueError(f"metrics_hqnr: buffers made for {buf['shape']}, the call is {(b, c, h, w, ratio, block)}")
+    ms_gains, pan_gain = metrics.mtf_gains(sensor, c)
+    y = out if out is not None else torch.empty(b, 3, device=ps.device, dtype=torch.float64)
+    if not (y.is_cuda and y.dtype == torch.float64 and tuple(y.shape) == (b, 3)):
+        raise ValueError(f"metrics_hqnr: out must be a float64 [{b}, 3] tensor on the GPU")
+    filtered = fir_decimate(ps, _mtf_taps(ms_gains, ratio, ps.device), 1, None, buf["filtered"])
+    metrics_q2n(ms_exp, filtered, block, block, out=buf["q2n"], workspace=buf["q2n_ws"])
+    torch.neg(buf["q2n"], out=buf["d_lambda"]).add_(1.0)                       # 1 - Q2n, as the host rounds it
+    if pan_lp is None:
+        pan_lp = pan_lowpass(pan, pan_gain, ratio, out=buf["pan_lp"], low=buf["pan_low"])
+    metrics_dsblock(ps, ms_exp, pan, pan_lp, block, q, out=buf["d_s"], workspace=buf["ds_ws"], d_lambda=buf["d_lambda"],
+                    alpha=alpha, beta=beta)
+    y[:, 0].copy_(buf["d_lambda"])
+    y[:, 1:].copy_(buf["d_s"])
+    return y
 
 
 # ---- backward-side wrappers (finetune path) -----------------------------------------------------------

@@ -203,14 +203,21 @@ def sample_tiled(diffusion, scene, prompt, tile=64, method="dpmsolver", steps=20
 
 
 @torch.no_grad()
-def fuse_scene(diffusion, lr_ms, pan, prompt, ratio=4, score=False, interp="bilinear", **sample_tiled_kwargs):
+def fuse_scene(diffusion, lr_ms, pan, prompt, ratio=4, score=False, interp="bilinear", sensor=None, **sample_tiled_kwargs):
     """From the raw pair to the fused scene: lr_ms [B, C, h, w] is upsampled by ``ratio`` (2 or 4) on the device into the ``MS``
     the network is conditioned on -- ``interp="bilinear"``: ``ops.upsample_bilinear``, the reference's cv2.resize(INTER_LINEAR);
     ``interp="poly23"``: ``ops.upsample_poly23``, the interpolator that made the ``lms`` of the PanCollection files, for any
     checkpoint trained on them -- and ``sample_tiled`` fuses {"MS", "PAN"} with pan [B, 1, ratio * h, ratio * w]; the other
     keyword arguments are ``sample_tiled``'s.
     ``score=True`` returns (scene, ``metrics.quality_fullres(lr_ms, pan, scene)``): D_lambda, D_s and QNR, which takes ratio 4
-    (the low-resolution PAN is two pyramid levels of pan)."""
+    (the low-resolution PAN is two pyramid levels of pan).
+    ``score="hqnr"`` returns (scene, ``metrics.quality_hqnr(ms_exp, pan, scene, sensor, ratio)``): Khan's D_lambda, the block-wise
+    D_s and HQNR, the set the PanCollection tables report.  ms_exp is ``ops.upsample_poly23(lr_ms, ratio)`` whatever ``interp``
+    is (the conditioning ``MS`` itself with "poly23"); ``sensor`` names the row of ``metrics.MTF_GAINS`` and is required."""
+    if score not in (False, True, "hqnr"):
+        raise ValueError(f"fuse_scene: score={score!r} (False, True or 'hqnr')")
+    if isinstance(score, str) and sensor is None:
+        raise ValueError("fuse_scene(score='hqnr') needs the sensor whose MTF gains shape the filters")
     if interp not in ("bilinear", "poly23"):
         raise ValueError(f"fuse_scene: interp={interp!r} ('bilinear' or 'poly23')")
     if lr_ms.dim() != 4 or pan.dim() != 4 or pan.shape[0] != lr_ms.shape[0] or pan.shape[1] != 1 or \
@@ -222,4 +229,7 @@ def fuse_scene(diffusion, lr_ms, pan, prompt, ratio=4, score=False, interp="bili
     if not score:
         return scene
     from . import metrics
+    if isinstance(score, str):
+        ms_exp = ms if interp == "poly23" else ops.upsample_poly23(lr_ms, ratio)
+        return scene, metrics.quality_hqnr(ms_exp, pan, scene.float().contiguous(), sensor, ratio)
     return scene, metrics.quality_fullres(lr_ms, pan, scene.float().contiguous())

@@ -28,6 +28,19 @@ TRAIN_SETS = (("train_qb", "QB", 4), ("train_gf2", "GF2", 4), ("train_wv3", "WV3
 VAL_SETS = (("val_QB", "QB"), ("val_GF2", "GF2"), ("val_WV3", "WV3"))
 
 
+def validation_options(dataset_opt):
+    """The keyword arguments of ``evaluate.val_dataset`` a validation dataset's options ask for: ``full_resolution`` true is QNR,
+    "hqnr" is HQNR with the optional ``sensor``; absent or false is the scoring against ground truth."""
+    full = dataset_opt.get("full_resolution")
+    if not full:
+        return {}
+    if isinstance(full, str):
+        if full.lower() != "hqnr":
+            raise ValueError(f"full_resolution: {full!r} (true, false or \"hqnr\")")
+        return {"full_resolution": True, "protocol": "hqnr", "sensor": dataset_opt.get("sensor")}
+    return {"full_resolution": True}
+
+
 def seed_all(seed=3407, rank=0, reseed_python=True):
     """reference seed_torch (:24-33).  ``random`` (the per-iteration choice of the training set, shared by all ranks)
     is seeded identically everywhere; NumPy (the timesteps of p_losses_dynamic), torch and the device generator
@@ -146,8 +159,9 @@ def main(argv=None):
         if rank == 0:                       # (validation items are few; the other ranks wait at the barrier)
             for name, prompt in VAL_SETS:
                 if name in loaders:
-                    # a validation dataset's optional "full_resolution": score without ground truth (QNR) instead of SSIM / SAM
-                    kw = {"full_resolution": True} if opt["datasets"][name].get("full_resolution") else {}
+                    # a validation dataset's optional "full_resolution": score without ground truth instead of SSIM / SAM --
+                    # true: QNR; "hqnr": Khan's D_lambda, block-wise D_s and HQNR, with the dataset's optional "sensor"
+                    kw = validation_options(opt["datasets"][name])
                     scores.update(evaluate.val_dataset(diffusion, prompt, loaders[name], results, log=logger.info, **kw))
         if world > 1:
             torch.distributed.barrier()
