@@ -165,20 +165,7 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
-// The same in double (the gradient norm of sampler.hip, the sums of loss.hip and metrics.hip): the butterfly, then the four wave
-// totals in index order.  No leading barrier: red is written once per kernel.
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
+// The same in double, for every workgroup size and any number of values per lane: stats.h.
 
 // dbias[c] = bias_scale * sum_k part[k * cout + c], k ascending (deterministic): one workgroup of 256 threads finishes the bias
 // gradient from the [slot][cout] partial sums a weight-gradient kernel left in its workspace (backward.hip, wgrad_bf16.hip).
@@ -380,14 +367,30 @@ inline int check_dropout(const tmdiff_conv3d_desc* d, const char* what) {
   return TMDIFF_OK;
 }
 
-// Grid of a tiled launch: `blocks` workgroups, whose ids the kernels decode in 32 bits; sets a.total_blocks.  Fails with a
-// message that begins with the kernel's name `what`.
+// Grid of a tiled launch: `blocks` workgroups, whose ids the kernels decode in 32 bits; set_grid also sets a.total_blocks.  Fails
+// with a message that begins with the kernel's name `what`.
+inline int check_grid(long blocks, const char* what, int code = TMDIFF_E_INVALID) {
+  if (blocks <= 0 || blocks > 0x7fffffffL) return fail(code, "%s: grid of %ld blocks", what, blocks);
+  return TMDIFF_OK;
+}
 template <class Args>
 int set_grid(Args& a, long blocks, const char* what) {
-  if (blocks <= 0 || blocks > 0x7fffffffL) return fail(TMDIFF_E_INVALID, "%s: grid of %ld blocks", what, blocks);
+  if (const int rc = check_grid(blocks, what)) return rc;
   a.total_blocks = (unsigned)blocks;
   return TMDIFF_OK;
 }
+
+// A lent workspace of `bytes` bytes at `ptr`: at least `need` bytes, 8-byte aligned -- and with it the pointers o1, o2 (NULL
+// passes) that the message names in `as`.
+inline int check_workspace(const char* what, const void* ptr, size_t bytes, size_t need, const char* as = "", const void* o1 = nullptr,
+                           const void* o2 = nullptr) {
+  const uintptr_t low = reinterpret_cast<uintptr_t>(ptr) | reinterpret_cast<uintptr_t>(o1) | reinterpret_cast<uintptr_t>(o2);
+  TMDIFF_REQUIRE(bytes >= need && (low & 7u) == 0, "%s: workspace of %zu bytes, %zu needed (8-byte aligned%s)", what, bytes, need, as);
+  return TMDIFF_OK;
+}
+
+// an element count the kernels index in 32 bits: fewer than 2^31 elements
+inline bool fits_int32(double elements) { return elements <= 2147483647.0; }
 
 // ---- Descriptor fields of the kernels' argument structs (host side).  Each sets only the fields it names. ------------------
 

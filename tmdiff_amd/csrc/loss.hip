@@ -17,15 +17,16 @@
 //                         xh with a halo of 2 in LDS, writes sign(Lap d) of the tile and a halo of 1 into LDS (w_lap = 0: no
 //                         LDS at all, the lanes read their own pixels), and stores g = dL/dxh for the band: weighted, divided
 //                         by the counts, rounded to fp32 once.  16-byte accesses when W % 4 == 0 and the tensors are 16-byte
-//                         aligned (the staged tile is then widened to a halo of 4 columns, so that a float4 lies inside the
-//                         image or outside it), scalar ones otherwise.  g == NULL: values only.
-//  loss_finalize_kernel   adds the workgroups' three partial sums in a fixed order and writes the four values.
+//                         aligned (the staged tile has a halo of 4 columns, so that a float4 lies inside the image or outside
+//                         it), scalar ones otherwise.  g == NULL: values only.
+//  loss_finalize_kernel   adds the workgroups' three partial sums (in index order, then stats.h's workgroup sum) and writes
+//                         the four values.
 //
-// Every operation after the fp32 loads is fp64.  No atomics: partial sums go to the workspace with plain vector stores, so a call
-// is reproducible bit for bit; nothing is allocated, copied or synchronised here.
+// Every operation after the fp32 loads is fp64.  No atomics: a workgroup's three sums (stats.h's workgroup sum) go to the
+// workspace with plain vector stores, so a call is reproducible bit for bit; nothing is allocated, copied or synchronised here.
 #include <cfloat>
 
-#include "common.h"
+#include "stats.h"
 
 namespace {
 
@@ -117,30 +118,7 @@ __global__ void __launch_bounds__(NT) loss_kernel(LossArgs p) {
     double glap[4] = {0.0, 0.0, 0.0, 0.0};
     if (p.do_lap) {
       __syncthreads();   // the previous band's readers are done
-      if (vec) {
-        for (int i = t; i < LH * (LS / 4); i += NT) {
-          const int ly = i / (LS / 4), lq = i - ly * (LS / 4);
-          const int yy = y0 - HALO + ly, xx = x0 - PADX + 4 * lq;
-          float4 va = make_float4(0.f, 0.f, 0.f, 0.f), vb = va;
-          if (yy >= 0 && yy < H && xx >= 0 && xx < W) {   // W % 4 == 0: the four columns are inside together
-            va = *reinterpret_cast<const float4*>(pa + (long)yy * W + xx);
-            vb = *reinterpret_cast<const float4*>(pb + (long)yy * W + xx);
-          }
-          *reinterpret_cast<float4*>(&sa[ly][4 * lq]) = va;
-          *reinterpret_cast<float4*>(&sb[ly][4 * lq]) = vb;
-        }
-      } else {
-        constexpr int NW = TW + 2 * HALO;   // the 36 columns the stencils read
-        for (int i = t; i < LH * NW; i += NT) {
-          const int ly = i / NW, lx = i - ly * NW + (PADX - HALO);
-          const int yy = y0 - HALO + ly, xx = x0 - PADX + lx;
-          const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
-          const long off = in ? (long)yy * W + xx : 0;
-          const float va = pa[off], vb = pb[off];   // (0, 0) is always a valid element
-          sa[ly][lx] = in ? va : 0.f;
-          sb[ly][lx] = in ? vb : 0.f;
-        }
-      }
+      tmdiff::stage_halo_tile<float, LH, LS, LS, NT>(sa[0], sb[0], pa, pb, nullptr, y0 - HALO, x0 - PADX, H, W, vec);
       __syncthreads();
       for (int i = t; i < SH * SW; i += NT) {
         const int sy = i / SW, sx = i - sy * SW;
@@ -211,10 +189,10 @@ __global__ void __launch_bounds__(NT) loss_kernel(LossArgs p) {
     }
   }
 
-  const double w0 = tmdiff::wave_sum(s_base), w1 = tmdiff::wave_sum(s_sam), w2 = tmdiff::wave_sum(s_lap);
-  if ((t & 63) == 0) red[t >> 6][0] = w0, red[t >> 6][1] = w1, red[t >> 6][2] = w2;
+  const double s[3] = {s_base, s_sam, s_lap};
+  tmdiff::wg_sum_store<3, 3>(s, red[0]);
   __syncthreads();
-  if (t < 3) p.part[(long)blockIdx.x * 3 + t] = red[0][t] + red[1][t];
+  if (t < 3) p.part[(long)blockIdx.x * 3 + t] = tmdiff::wg_sum_col<NT / 64, 3>(red[0], t);
 }
 
 struct LossFinalArgs {
@@ -226,26 +204,21 @@ struct LossFinalArgs {
   float* out32;           // total
 };
 
-// Lane t adds the workgroups t, t + 256, ... in order; then the waves' butterflies and the four waves in order: the order depends
-// on the number of workgroups alone.
+// Lane t adds the workgroups t, t + 256, ... in order, then the workgroup sum: the order depends on the number of workgroups alone.
 __global__ void __launch_bounds__(FIN_T) loss_finalize_kernel(LossFinalArgs p) {
   __shared__ double red[FIN_T / 64][3];
   const int t = threadIdx.x;
   double s[3] = {0.0, 0.0, 0.0};
-  for (long i = t; i < p.n; i += FIN_T) {
+  for (long i = t; i < p.n; i += FIN_T) {   // stats.h strided_sum's walk over the three columns at once: their loads overlap
 #pragma unroll
     for (int k = 0; k < 3; ++k) s[k] += p.part[i * 3 + k];
   }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    s[k] = tmdiff::wave_sum(s[k]);
-    if ((t & 63) == 0) red[t >> 6][k] = s[k];
-  }
+  tmdiff::wg_sum_store<3, 3>(s, red[0]);
   __syncthreads();
   if (t != 0) return;
   double tot[3];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) tot[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+  for (int k = 0; k < 3; ++k) tot[k] = tmdiff::wg_sum_col<FIN_T / 64, 3>(red[0], k);
   const double base = tot[0] / p.nb, sam = tot[1] / p.ns, lap = p.nl > 0.0 ? tot[2] / p.nl : 0.0;
   double total;
   {
@@ -258,7 +231,7 @@ __global__ void __launch_bounds__(FIN_T) loss_finalize_kernel(LossFinalArgs p) {
 
 bool loss_ok(int B, int C, int H, int W, int lap) {
   const int least = lap ? 3 : 1;
-  return B >= 1 && C >= 1 && C <= MAXC && H >= least && W >= least && (double)B * C * H * W <= 2147483647.0;
+  return B >= 1 && C >= 1 && C <= MAXC && H >= least && W >= least && tmdiff::fits_int32((double)B * C * H * W);
 }
 
 size_t loss_bytes(int B, int H, int W) { return (size_t)B * tiles_of(H, W) * 3 * sizeof(double); }
@@ -287,14 +260,12 @@ int tmdiff_spectral_spatial_loss(const float* x0, const float* xhat, const float
                         "2^31 elements)", B, C, H, W, lap ? 3 : 1);
   TMDIFF_REQUIRE(x0 && xhat && out64 && out32 && workspace, "spectral_spatial_loss: null tensor");
   TMDIFF_REQUIRE(ms || w_sam == 0.0, "spectral_spatial_loss: ms may be null only when w_sam == 0");
-  TMDIFF_REQUIRE(workspace_bytes >= loss_bytes(B, H, W) && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0 &&
-                     (reinterpret_cast<uintptr_t>(out64) & 7u) == 0,
-                 "spectral_spatial_loss: workspace of %zu bytes, %zu needed (8-byte aligned, as out64)", workspace_bytes,
-                 loss_bytes(B, H, W));
+  if (const int rc = tmdiff::check_workspace("spectral_spatial_loss", workspace, workspace_bytes, loss_bytes(B, H, W), ", as out64", out64))
+    return rc;
   const hipStream_t st = tmdiff::as_stream(stream);
   const int tiles_x = (W + TW - 1) / TW;
   const long tiles = tiles_of(H, W), blocks = (long)B * tiles;
-  if (blocks > 0x7fffffffL) return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "spectral_spatial_loss: grid of %ld blocks", blocks);
+  if (const int rc = tmdiff::check_grid(blocks, "spectral_spatial_loss", TMDIFF_E_UNSUPPORTED)) return rc;
   const bool sam = w_sam != 0.0;
   const bool vec = W % 4 == 0 && tmdiff::aligned16(x0) && tmdiff::aligned16(xhat) && (!sam || tmdiff::aligned16(ms)) &&
                    (!g || tmdiff::aligned16(g));

@@ -10,28 +10,30 @@
 //                        |a|^2, |b|^2) stay in registers across the band loop and become one angle per pixel after it; with four
 //                        bands the pixel's eight values stay too and give the 4 x 4 cross products of Q4.
 //  metrics_gram_kernel   channel sums and the upper triangle of sum x_i x_j over a list of up to 17 channels in two segments.
-//  *_finalize_kernel     one workgroup per image: adds the workgroups' partial sums in a fixed order, evaluates the formulas.
+//  *_finalize_kernel     one workgroup per image: adds the workgroups' partial sums (stats.h strided_sum, wg_sum), evaluates the
+//                        formulas.
 //  metrics_q2n_kernel    Q2n (Q4 / Q8, metrics.q2n): one workgroup per block x block window of one image, both images' window in
 //                        LDS as fp32 (mirrored at the bottom and the right while staging, zero bands up to a power of two).  Pass
 //                        one: per band the mean and the centred sums of the ground truth and of the fused image about that mean.
 //                        Pass two: the C x C matrix of centred cross products, each lane a T x T tile of band pairs over a slice
 //                        of the pixels.  The normalised moments the definition asks for are affine in these, so no lane divides
 //                        per pixel.  The workgroup then evaluates the hypercomplex product through the sign table and stores the
-//                        block's value; metrics_q2n_finalize_kernel averages them per image in a fixed order.
+//                        block's value; metrics_q2n_finalize_kernel averages them per image.
 //  metrics_dsblock_kernel  the spatial term of HQNR (metrics.d_s_block): one workgroup per block x block window of one image.
 //                        The windows of pan and of the low-pass pan are staged once (mirrored like Q2n's), those of the fused
 //                        and the interpolated MS image band by band; per band two passes over LDS, the means and then the
 //                        centred sums, give Q(ps_c, pan) and Q(ms_c, pan_lp) of the window.
-//                        metrics_dsblock_finalize_kernel averages the windows per band in a fixed order, forms D_s and, given
-//                        the image's D_lambda, HQNR.
+//                        metrics_dsblock_finalize_kernel averages the windows per band, forms D_s and, given the image's
+//                        D_lambda, HQNR.
 //
 // Every sum is fp64 (products of two fp32 values are exact there): at sensor scale (mean 1000, sigma 5) a variance is a 4e4-th
-// of the raw second moment, which fp32 sums would lose entirely.  No atomics: each workgroup stores its partial sums with plain
-// vector stores and the finalize kernel adds them in a fixed order, so a call is reproducible bit for bit.  Nothing is allocated,
-// copied to the host or synchronised here: the caller lends the workspace and the launches go to its stream.
+// of the raw second moment, which fp32 sums would lose entirely.  No atomics: each workgroup adds through stats.h's workgroup sum
+// and stores its partial sums with plain vector stores, and the finalize kernel adds them in index order, so a call is
+// reproducible bit for bit.  Nothing is allocated, copied to the host or synchronised here: the caller lends the workspace and the
+// launches go to its stream.
 #include <algorithm>
 
-#include "common.h"
+#include "stats.h"
 
 namespace {
 
@@ -39,6 +41,7 @@ constexpr int TH = 16, TW = 64, HALO = 3;            // tile owned by a workgrou
 constexpr int LH = TH + 2 * HALO, LW = TW + 2 * HALO;
 constexpr int LS = 72;                               // LDS row stride of the staged tile (floats)
 constexpr int NSUM = 12, NBAND = 16;                 // per band: 12 sums, then min a, max a, min b, max b
+constexpr int RED = NBAND + 5;                       // columns of a wave's row of totals
 constexpr int FIN_T = 1024, FIN_W = FIN_T / 64;      // finalize: 16 waves, each adds a fixed run of the tiles
 constexpr int MAXC = 16, MAXG = 17;                  // bands of a pair; channels of a gram
 constexpr int PAIR_K = 9, NOREF_K = 3;               // output columns
@@ -70,20 +73,10 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
-// sum over the workgroup of N values per lane -> red[w][k] holds wave w's sum (the caller syncs and adds the four in order)
-template <int N>
-__device__ __forceinline__ void waves_to_lds(const double (&v)[N], double (*red)[NBAND + 5], int lane, int wave) {
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    const double s = tmdiff::wave_sum(v[k]);
-    if (lane == 0) red[wave][k] = s;
-  }
-}
-
 __global__ void __launch_bounds__(256) metrics_pair_kernel(PairArgs p) {
   __shared__ float sa[LH][LS], sb[LH][LS];
   __shared__ double hs[5][LH][TW];        // row sums over 7 columns of a, b, a^2, b^2, ab
-  __shared__ double red[4][NBAND + 5];    // per-wave sums (17 columns: the band's 12, or the angle + 16 cross products)
+  __shared__ double red[4][RED];          // per-wave sums (17 columns: the band's 12, or the angle + 16 cross products)
 
   const int t = threadIdx.x, x = t & 63, q = t >> 6;
   const int img = blockIdx.x / p.tiles, tile = blockIdx.x - img * p.tiles;
@@ -103,15 +96,7 @@ __global__ void __launch_bounds__(256) metrics_pair_kernel(PairArgs p) {
   for (int c = 0; c < C; ++c) {
     const float* pa = p.a + (long)img * p.asB + (long)c * p.asC;
     const float* pb = p.b + (long)img * p.bsB + (long)c * p.bsC;
-    for (int i = t; i < LH * LW; i += 256) {
-      const int ly = i / LW, lx = i - ly * LW;
-      const int yy = y0 - HALO + ly, xx = x0 - HALO + lx;
-      const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
-      const int off = in ? yy * W + xx : 0;
-      const float va = pa[off], vb = pb[off];   // (0, 0) is always a valid element
-      sa[ly][lx] = in ? va : 0.f;
-      sb[ly][lx] = in ? vb : 0.f;
-    }
+    tmdiff::stage_halo_tile<float, LH, LW, LS, 256>(sa[0], sb[0], pa, pb, nullptr, y0 - HALO, x0 - HALO, H, W, false);
     __syncthreads();
 
     double s[NSUM];
@@ -182,13 +167,13 @@ __global__ void __launch_bounds__(256) metrics_pair_kernel(PairArgs p) {
         }
       }
     }
-    waves_to_lds<NSUM>(s, red, x, q);
+    tmdiff::wg_sum_store<NSUM, RED>(s, red[0]);
     {
       const float m0 = wave_min(lo_a), m1 = wave_max(hi_a), m2 = wave_min(lo_b), m3 = wave_max(hi_b);
       if (x == 0) red[q][NSUM] = m0, red[q][NSUM + 1] = m1, red[q][NSUM + 2] = m2, red[q][NSUM + 3] = m3;
     }
     __syncthreads();
-    if (t < NSUM) part[c * NBAND + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+    if (t < NSUM) part[c * NBAND + t] = tmdiff::wg_sum_col<4, RED>(red[0], t);
     else if (t < NBAND) {
       const bool least = ((t - NSUM) & 1) == 0;   // a wave without a pixel of the image holds +inf / -inf
       const double u = least ? fmin(red[0][t], red[1][t]) : fmax(red[0][t], red[1][t]);
@@ -217,9 +202,9 @@ __global__ void __launch_bounds__(256) metrics_pair_kernel(PairArgs p) {
     }
   }
   __syncthreads();   // the last band's readers of `red` are done
-  waves_to_lds<17>(e, red, x, q);
+  tmdiff::wg_sum_store<17, RED>(e, red[0]);
   __syncthreads();
-  if (t < 17) part[C * NBAND + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+  if (t < 17) part[C * NBAND + t] = tmdiff::wg_sum_col<4, RED>(red[0], t);
 }
 
 struct PairFinalArgs {
@@ -411,8 +396,9 @@ struct Q2nArgs {
 __host__ __device__ inline int q2n_tile(int Cp) { return Cp < 4 ? Cp : 4; }   // a lane owns a T x T tile of band pairs
 
 // Sum of N values per lane over groups of G consecutive lanes (G a power of two, 16 <= G <= 256, the same for the whole
-// workgroup): every lane of a group gets the group's sum.  Butterflies inside a wave, then the group's waves in order through
-// red[4][16]: a fixed order.
+// workgroup): every lane of a group gets the group's sum.  The order of stats.h over a group: the butterfly over the group's
+// lanes of a wave (offsets from half the group's lanes down to 1: its own loop, the only one narrower than a wave), then the
+// group's waves in order through red[4][16]; G = 256 is the workgroup sum.
 template <int N>
 __device__ __forceinline__ void group_sum(double (&v)[N], int G, double (*red)[16], int t) {
   const int gw = G < 64 ? G : 64;
@@ -427,11 +413,7 @@ __device__ __forceinline__ void group_sum(double (&v)[N], int G, double (*red)[1
       for (int k = 0; k < N; ++k) red[wave][k] = v[k];
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < N; ++k) {
-      double s = red[w0][k];
-      for (int i = 1; i < wpg; ++i) s += red[w0 + i][k];
-      v[k] = s;
-    }
+    for (int k = 0; k < N; ++k) v[k] = tmdiff::waves_in_order<16>(red[0], k, w0, wpg);
   }
 }
 
@@ -475,19 +457,8 @@ __global__ void __launch_bounds__(256) metrics_q2n_kernel(Q2nArgs p) {
   float* sg = q2n_lds;
   float* sf = q2n_lds + Cp * bs;
 
-  const int lb = block == 8 ? 3 : block == 16 ? 4 : 5;
-  // staging: row H + k is row H - 1 - k (the host checked that the mirror stays inside the image); bands past C are zero
-  for (int i = t; i < Cp * n; i += 256) {
-    const int c = i >> (2 * lb), px = i & (n - 1), ly = px >> lb, lx = px & (block - 1);
-    int yy = y0 + ly, xx = x0 + lx;
-    yy = yy < p.H ? yy : 2 * p.H - 1 - yy;
-    xx = xx < p.W ? xx : 2 * p.W - 1 - xx;
-    const bool in = c < p.C;
-    const int cc = in ? c : 0, off = yy * p.W + xx;
-    const float va = p.a[(long)img * p.asB + (long)cc * p.asC + off], vb = p.b[(long)img * p.bsB + (long)cc * p.bsC + off];
-    sg[c * bs + px] = in ? va : 0.f;
-    sf[c * bs + px] = in ? vb : 0.f;
-  }
+  tmdiff::stage_mirrored<256, true, 2>({sg, sf}, {p.a + (long)img * p.asB, p.b + (long)img * p.bsB}, {p.asC, p.bsC}, p.C, Cp, bs, block,
+                                       y0, x0, p.H, p.W);
   __syncthreads();
 
   // pass one: 256 / Cp lanes per band
@@ -563,14 +534,11 @@ __global__ void __launch_bounds__(256) metrics_q2n_kernel(Q2nArgs p) {
   }
 }
 
-// Lane t adds the blocks t, t + 256, ... in order; then the waves' butterflies and the four waves in order: the order depends on
-// the number of blocks alone.
+// Lane t adds the blocks t, t + 256, ... in order, then the workgroup sum: the order depends on the number of blocks alone.
 __global__ void __launch_bounds__(256) metrics_q2n_finalize_kernel(const double* vals, int nblk, double* out) {
   __shared__ double red[4];
   const int t = threadIdx.x, img = blockIdx.x;
-  double s = 0.0;
-  for (int i = t; i < nblk; i += 256) s += vals[(long)img * nblk + i];
-  s = tmdiff::block_sum_f64(s, red);
+  const double s = tmdiff::block_sum_f64(tmdiff::strided_sum(vals + (long)img * nblk, nblk, 1, t, 256), red);
   if (t == 0) out[img] = s / (double)nblk;
 }
 
@@ -586,14 +554,11 @@ struct DsArgs {
   double* map;        // the same layout, or null
 };
 
-// sum over the workgroup of N values per lane, in every lane: the waves' butterflies, then the four waves in order
+// the workgroup sum of N values per lane, in every lane, behind a barrier: earlier readers of red are done
 template <int N>
-__device__ __forceinline__ void wg_sum(double (&v)[N], double (*red)[NBAND + 5], int lane, int wave) {
-  __syncthreads();   // earlier readers of red are done
-  waves_to_lds<N>(v, red, lane, wave);
+__device__ __forceinline__ void wg_sum(double (&v)[N], double (*red)[RED]) {
   __syncthreads();
-#pragma unroll
-  for (int k = 0; k < N; ++k) v[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+  tmdiff::wg_sum<4, N, RED>(v, red[0]);
 }
 
 // metrics.q_index's formula from centred sums over n1 + 1 samples.  No contraction and the host's order of operations; a window
@@ -606,22 +571,16 @@ __device__ __forceinline__ double uqi_of(double saa, double sbb, double sab, dou
 
 __global__ void __launch_bounds__(256) metrics_dsblock_kernel(DsArgs p) {
   __shared__ float win[4][32 * 32];       // the window of ps_c, ms_c, pan, lp
-  __shared__ double red[4][NBAND + 5];
+  __shared__ double red[4][RED];
 
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int block = p.block, n = block * block, lb = block == 8 ? 3 : block == 16 ? 4 : 5;
+  const int t = threadIdx.x;
+  const int block = p.block, n = block * block;
   const int img = blockIdx.x / p.nblk, blk = blockIdx.x - img * p.nblk;
   const int by = blk / p.nx, bx = blk - by * p.nx, y0 = by * block, x0 = bx * block;
   const double nn = (double)n, n1 = nn - 1.0;
 
-  // staging: row H + k is row H - 1 - k (the host checked that the mirror stays inside the image)
   auto stage = [&](const float* src, float* dst) {
-    for (int px = t; px < n; px += 256) {
-      int yy = y0 + (px >> lb), xx = x0 + (px & (block - 1));
-      yy = yy < p.H ? yy : 2 * p.H - 1 - yy;
-      xx = xx < p.W ? xx : 2 * p.W - 1 - xx;
-      dst[px] = src[yy * p.W + xx];
-    }
+    tmdiff::stage_mirrored<256, false, 1>({dst}, {src}, {0}, 1, 1, 0, block, y0, x0, p.H, p.W);
   };
   stage(p.pan + (long)img * p.panB, win[2]);
   stage(p.lp + (long)img * p.lpB, win[3]);
@@ -630,14 +589,14 @@ __global__ void __launch_bounds__(256) metrics_dsblock_kernel(DsArgs p) {
   // the two PAN windows serve every band: their means and centred squares once
   double mp[2] = {0.0, 0.0};
   for (int px = t; px < n; px += 256) mp[0] += (double)win[2][px], mp[1] += (double)win[3][px];
-  wg_sum<2>(mp, red, lane, wave);
+  wg_sum<2>(mp, red);
   mp[0] /= nn; mp[1] /= nn;
   double sp[2] = {0.0, 0.0};
   for (int px = t; px < n; px += 256) {
     const double dp = (double)win[2][px] - mp[0], dq = (double)win[3][px] - mp[1];
     sp[0] += dp * dp; sp[1] += dq * dq;
   }
-  wg_sum<2>(sp, red, lane, wave);
+  wg_sum<2>(sp, red);
 
   for (int c = 0; c < p.C; ++c) {
     __syncthreads();   // the last band's readers of win are done
@@ -646,7 +605,7 @@ __global__ void __launch_bounds__(256) metrics_dsblock_kernel(DsArgs p) {
     __syncthreads();
     double m[2] = {0.0, 0.0};
     for (int px = t; px < n; px += 256) m[0] += (double)win[0][px], m[1] += (double)win[1][px];
-    wg_sum<2>(m, red, lane, wave);
+    wg_sum<2>(m, red);
     m[0] /= nn; m[1] /= nn;
     double s[4] = {0.0, 0.0, 0.0, 0.0};   // centred: a raw second moment at sensor scale would lose the variance
     for (int px = t; px < n; px += 256) {
@@ -654,7 +613,7 @@ __global__ void __launch_bounds__(256) metrics_dsblock_kernel(DsArgs p) {
       const double dp = (double)win[2][px] - mp[0], dq = (double)win[3][px] - mp[1];
       s[0] += da * da; s[1] += da * dp; s[2] += db * db; s[3] += db * dq;
     }
-    wg_sum<4>(s, red, lane, wave);
+    wg_sum<4>(s, red);
     if (t == 0) {
       const double qh = uqi_of(s[0], sp[0], s[1], m[0], mp[0], n1), ql = uqi_of(s[2], sp[1], s[3], m[1], mp[1], n1);
       const long at = (((long)img * p.C + c) * 2) * p.nblk + blk;
@@ -674,17 +633,14 @@ struct DsFinalArgs {
 
 __device__ __forceinline__ double pow_exact1(double x, double e) { return e == 1.0 ? x : e == 2.0 ? x * x : pow(x, e); }
 
-// Per (band, high / low) lane t adds the windows t, t + 256, ... in order; then the waves' butterflies and the four waves in
-// order: the order depends on the number of windows alone.
+// Per (band, high / low) lane t adds the windows t, t + 256, ... in order, then the workgroup sum: the order depends on the number
+// of windows alone.
 __global__ void __launch_bounds__(256) metrics_dsblock_finalize_kernel(DsFinalArgs p) {
-  __shared__ double red[2 * MAXC][4];
+  __shared__ double red[4][2 * MAXC];
   const int t = threadIdx.x, img = blockIdx.x;
   for (int k = 0; k < 2 * p.C; ++k) {
-    const double* src = p.vals + ((long)img * 2 * p.C + k) * p.nblk;
-    double s = 0.0;
-    for (int i = t; i < p.nblk; i += 256) s += src[i];
-    s = tmdiff::wave_sum(s);
-    if ((t & 63) == 0) red[k][t >> 6] = s;
+    const double s[1] = {tmdiff::strided_sum(p.vals + ((long)img * 2 * p.C + k) * p.nblk, p.nblk, 1, t, 256)};
+    tmdiff::wg_sum_store<1, 2 * MAXC>(s, red[0] + k);
   }
   __syncthreads();
   if (t != 0) return;
@@ -692,9 +648,8 @@ __global__ void __launch_bounds__(256) metrics_dsblock_finalize_kernel(DsFinalAr
 #pragma clang fp contract(off)
     double acc = 0.0;
     for (int c = 0; c < p.C; ++c) {
-      const double* h = red[2 * c];
-      const double* l = red[2 * c + 1];
-      const double qh = (((h[0] + h[1]) + h[2]) + h[3]) / (double)p.nblk, ql = (((l[0] + l[1]) + l[2]) + l[3]) / (double)p.nblk;
+      const double qh = tmdiff::wg_sum_col<4, 2 * MAXC>(red[0], 2 * c) / (double)p.nblk;
+      const double ql = tmdiff::wg_sum_col<4, 2 * MAXC>(red[0], 2 * c + 1) / (double)p.nblk;
       acc += pow_exact1(fabs(qh - ql), p.q);
     }
     acc /= (double)p.C;
@@ -737,18 +692,18 @@ int q2n_bands(int C) {
 
 struct Q2nGrid { int ny, nx; };
 bool q2n_ok(int B, int C, int H, int W, int block, int shift, Q2nGrid* g = nullptr) {
-  if (!(B >= 0 && C >= 1 && C <= MAXC && H >= 1 && W >= 1 && (double)B * C * H * W <= 2147483647.0)) return false;
+  if (!(B >= 0 && C >= 1 && C <= MAXC && H >= 1 && W >= 1 && tmdiff::fits_int32((double)B * C * H * W))) return false;
   if (!(block == 8 || block == 16 || block == 32) || shift < 1 || shift > block) return false;
   const long ny = ((long)H + shift - 1) / shift, nx = ((long)W + shift - 1) / shift;
   if ((ny - 1) * shift + block - H > H || (nx - 1) * shift + block - W > W) return false;   // the mirror stays inside the image
-  if ((double)B * ny * nx > 2147483647.0) return false;
+  if (!tmdiff::fits_int32((double)B * ny * nx)) return false;
   if (g) g->ny = (int)ny, g->nx = (int)nx;
   return true;
 }
 size_t q2n_lds_bytes(int Cp, int block) { return (size_t)2 * Cp * (block * block + Q2N_PAD) * sizeof(float); }
 
 bool extents_ok(int B, int C, int H, int W) {
-  return B >= 0 && C >= 1 && C <= MAXC && H >= 7 && W >= 7 && (double)B * C * H * W <= 2147483647.0;
+  return B >= 0 && C >= 1 && C <= MAXC && H >= 7 && W >= 7 && tmdiff::fits_int32((double)B * C * H * W);
 }
 
 size_t pair_bytes(int B, int C, int H, int W) { return (size_t)B * tiles_of(H, W) * pair_np(C) * sizeof(double); }
@@ -777,12 +732,11 @@ int tmdiff_metrics_pair(const float* x_true, int64_t true_stride_b, int64_t true
   TMDIFF_REQUIRE(x_true && x_pred && out && workspace, "metrics_pair: null tensor");
   TMDIFF_REQUIRE(true_stride_b >= 0 && true_stride_c >= (int64_t)H * W && pred_stride_b >= 0 && pred_stride_c >= (int64_t)H * W,
                  "metrics_pair: channel strides below a plane of %d x %d", H, W);
-  TMDIFF_REQUIRE(workspace_bytes >= pair_bytes(B, C, H, W) && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0,
-                 "metrics_pair: workspace of %zu bytes, %zu needed (8-byte aligned)", workspace_bytes, pair_bytes(B, C, H, W));
+  if (const int rc = tmdiff::check_workspace("metrics_pair", workspace, workspace_bytes, pair_bytes(B, C, H, W))) return rc;
   const hipStream_t st = tmdiff::as_stream(stream);
   const int tiles_x = (W + TW - 1) / TW, tiles = tiles_of(H, W);
   const long blocks = (long)B * tiles;
-  if (blocks > 0x7fffffffL) return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "metrics_pair: grid of %ld blocks", blocks);
+  if (const int rc = tmdiff::check_grid(blocks, "metrics_pair", TMDIFF_E_UNSUPPORTED)) return rc;
   const PairArgs a{x_true, x_pred, true_stride_b, true_stride_c, pred_stride_b, pred_stride_c, C, H, W, tiles_x, tiles,
                    (0.01 * data_range) * (0.01 * data_range), (0.03 * data_range) * (0.03 * data_range), static_cast<double*>(workspace)};
   metrics_pair_kernel<<<(unsigned)blocks, 256, 0, st>>>(a);
@@ -796,15 +750,14 @@ int tmdiff_metrics_noref(const float* l_ms, int64_t l_ms_stride_b, int64_t l_ms_
                          const float* l_pan, int64_t l_pan_stride_b, const float* ps, int64_t ps_stride_b, int64_t ps_stride_c, int32_t B,
                          int32_t C, int32_t H, int32_t W, int32_t h, int32_t w, double* out, void* workspace, size_t workspace_bytes,
                          tmdiff_stream_t stream) {
-  if (!extents_ok(B, C, H, W) || h < 1 || w < 1 || (double)B * C * h * w > 2147483647.0)
+  if (!extents_ok(B, C, H, W) || h < 1 || w < 1 || !tmdiff::fits_int32((double)B * C * h * w))
     return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "metrics_noref: B=%d C=%d H=%d W=%d h=%d w=%d (1 <= C <= 16, H, W >= 7, h, w >= 1, fewer than "
                         "2^31 elements)", B, C, H, W, h, w);
   if (B == 0) return TMDIFF_OK;
   TMDIFF_REQUIRE(l_ms && pan && l_pan && ps && out && workspace, "metrics_noref: null tensor");
   TMDIFF_REQUIRE(ps_stride_b >= 0 && pan_stride_b >= 0 && l_ms_stride_b >= 0 && l_pan_stride_b >= 0 && ps_stride_c >= (int64_t)H * W &&
                      l_ms_stride_c >= (int64_t)h * w, "metrics_noref: channel strides below a plane");
-  TMDIFF_REQUIRE(workspace_bytes >= noref_bytes(B, C) && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0,
-                 "metrics_noref: workspace of %zu bytes, %zu needed (8-byte aligned)", workspace_bytes, noref_bytes(B, C));
+  if (const int rc = tmdiff::check_workspace("metrics_noref", workspace, workspace_bytes, noref_bytes(B, C))) return rc;
   const hipStream_t st = tmdiff::as_stream(stream);
   const int nent = gram_entries(C + 1);
   double* hi = static_cast<double*>(workspace);
@@ -842,8 +795,7 @@ int tmdiff_metrics_q2n(const float* x_true, int64_t true_stride_b, int64_t true_
   TMDIFF_REQUIRE(x_true && x_pred && out && workspace, "metrics_q2n: null tensor");
   TMDIFF_REQUIRE(true_stride_b >= 0 && true_stride_c >= (int64_t)H * W && pred_stride_b >= 0 && pred_stride_c >= (int64_t)H * W,
                  "metrics_q2n: channel strides below a plane of %d x %d", H, W);
-  TMDIFF_REQUIRE(workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0,
-                 "metrics_q2n: workspace of %zu bytes, %zu needed (8-byte aligned)", workspace_bytes, need);
+  if (const int rc = tmdiff::check_workspace("metrics_q2n", workspace, workspace_bytes, need)) return rc;
   const hipStream_t st = tmdiff::as_stream(stream);
   const int Cp = q2n_bands(C);
   const size_t lds = q2n_lds_bytes(Cp, block);
@@ -888,7 +840,7 @@ int tmdiff_metrics_dsblock(const float* ps, int64_t ps_stride_b, int64_t ps_stri
                            double beta, double* out, double* maps_out, void* workspace, size_t workspace_bytes,
                            tmdiff_stream_t stream) {
   Q2nGrid g;
-  if (!q2n_ok(B, C, H, W, block, block, &g) || (double)B * C * 2 * g.ny * g.nx > 2147483647.0)
+  if (!q2n_ok(B, C, H, W, block, block, &g) || !tmdiff::fits_int32((double)B * C * 2 * g.ny * g.nx))
     return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "metrics_dsblock: B=%d C=%d H=%d W=%d block=%d (1 <= C <= 16, block 8, 16 or 32, mirror "
                         "padding no longer than the axis, fewer than 2^31 elements)", B, C, H, W, block);
   if (!(q > 0.0 && q <= 1e6) || !(alpha == alpha) || !(beta == beta))
@@ -898,8 +850,7 @@ int tmdiff_metrics_dsblock(const float* ps, int64_t ps_stride_b, int64_t ps_stri
   TMDIFF_REQUIRE(ps && ms_exp && pan && pan_lp && out && workspace, "metrics_dsblock: null tensor");
   TMDIFF_REQUIRE(ps_stride_b >= 0 && ps_stride_c >= (int64_t)H * W && ms_stride_b >= 0 && ms_stride_c >= (int64_t)H * W &&
                      pan_stride_b >= 0 && pan_lp_stride_b >= 0, "metrics_dsblock: channel strides below a plane of %d x %d", H, W);
-  TMDIFF_REQUIRE(workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0,
-                 "metrics_dsblock: workspace of %zu bytes, %zu needed (8-byte aligned)", workspace_bytes, need);
+  if (const int rc = tmdiff::check_workspace("metrics_dsblock", workspace, workspace_bytes, need)) return rc;
   const hipStream_t st = tmdiff::as_stream(stream);
   const DsArgs a{ps, ms_exp, pan, pan_lp, ps_stride_b, ps_stride_c, ms_stride_b, ms_stride_c, pan_stride_b, pan_lp_stride_b,
                  C, H, W, block, g.nx, g.ny * g.nx, static_cast<double*>(workspace), maps_out};

@@ -14,7 +14,7 @@
 //     16 bytes per lane and a scalar tail where the tensor's pointers are aligned, scalar throughout where not.
 #include <initializer_list>
 
-#include "common.h"
+#include "stats.h"
 
 namespace {
 using tmdiff::aligned16;
@@ -280,7 +280,7 @@ __global__ void __launch_bounds__(256) multi_adamw_kernel(const tmdiff_adamw_ent
   });
 }
 
-// Global gradient norm in two stages, both without atomics and with a fixed summation order (common.h block_sum_f64), so the
+// Global gradient norm in two stages, both without atomics and with a fixed summation order (stats.h block_sum_f64), so the
 // norm has the same bits from run to run and from an eager launch to a graph replay.
 // Stage 1: workgroup k sums g^2 over chunk k of the AdamW tables (same entries, same chunks) into partials[k].  Each lane adds
 // the squares of its strided elements in double (the square of a float is exact there) in element order, 16 bytes per load

@@ -20,15 +20,15 @@
 //                       the value sum.  P, Q, R go to LDS (0 for an origin outside the valid region), and a lane sums them
 //                       directly over the win x win windows around each of its four pixels.  g == NULL: values only, and only the
 //                       windows of the value sum are formed.  accumulate: g = fl32(g + ...), else g = fl32(...).
-//  ssim_finalize_kernel adds the workgroups' partial sums in a fixed order and writes the values (alone, or composed with the four
-//                       values of csrc/loss.hip).
+//  ssim_finalize_kernel adds the workgroups' partial sums (stats.h strided_sum, block_sum_f64) and writes the values (alone, or
+//                       composed with the four values of csrc/loss.hip).
 //
-// Every operation after the fp32 loads is fp64.  No atomics: one partial sum per workgroup goes to the workspace with a plain
-// vector store, so a call is reproducible bit for bit; nothing is allocated, copied or synchronised here.
+// Every operation after the fp32 loads is fp64.  No atomics: one partial sum per workgroup (stats.h block_sum_f64) goes to the
+// workspace with a plain vector store, so a call is reproducible bit for bit; nothing is allocated, copied or synchronised here.
 #include <cfloat>
 #include <type_traits>
 
-#include "common.h"
+#include "stats.h"
 
 namespace {
 
@@ -54,12 +54,6 @@ struct SsimArgs {
   double gscale;     // -weight / (n Nwin)
   double* part;      // [workgroups]: sum of S over the windows whose origin lies in the tile
 };
-
-template <class T>
-__device__ __forceinline__ T staged(float v, float m) {
-  if constexpr (std::is_same<T, double>::value) return (double)v + (double)m;
-  else return v;
-}
 
 // S and the three maps of one window from its five sums.  Every operation is rounded on its own, and the expressions in a and b
 // are written alike: equal sums give A1 == B1 and A2 == B2 bit for bit.
@@ -95,35 +89,7 @@ __global__ void __launch_bounds__(NT) ssim_loss_kernel(SsimArgs p) {
   const float* pb = p.xp + pbase;
   const float* pm = MS ? p.ms + pbase : nullptr;
 
-  if (p.vec) {
-    for (int i = t; i < G::LH * (G::LS / 4); i += NT) {
-      const int ly = i / (G::LS / 4), lq = i - ly * (G::LS / 4);
-      const int yy = y0 - G::HALO + ly, xx = x0 - G::PADX + 4 * lq;
-      float4 va = make_float4(0.f, 0.f, 0.f, 0.f), vb = va, vm = va;
-      if (yy >= 0 && yy < H && xx >= 0 && xx < W) {   // W % 4 == 0: the four columns are inside together
-        const long off = (long)yy * W + xx;
-        va = *reinterpret_cast<const float4*>(pa + off);
-        vb = *reinterpret_cast<const float4*>(pb + off);
-        if constexpr (MS) vm = *reinterpret_cast<const float4*>(pm + off);
-      }
-      T* da = &sa[ly * G::LS + 4 * lq];
-      T* db = &sb[ly * G::LS + 4 * lq];
-      da[0] = staged<T>(va.x, vm.x); da[1] = staged<T>(va.y, vm.y); da[2] = staged<T>(va.z, vm.z); da[3] = staged<T>(va.w, vm.w);
-      db[0] = staged<T>(vb.x, vm.x); db[1] = staged<T>(vb.y, vm.y); db[2] = staged<T>(vb.z, vm.z); db[3] = staged<T>(vb.w, vm.w);
-    }
-  } else {
-    for (int i = t; i < G::LH * G::LS; i += NT) {
-      const int ly = i / G::LS, lx = i - ly * G::LS;
-      const int yy = y0 - G::HALO + ly, xx = x0 - G::PADX + lx;
-      const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
-      const long off = in ? (long)yy * W + xx : 0;   // (0, 0) is always a valid element
-      const float va = pa[off], vb = pb[off];
-      float vm = 0.f;
-      if constexpr (MS) vm = pm[off];
-      sa[i] = in ? staged<T>(va, vm) : (T)0;
-      sb[i] = in ? staged<T>(vb, vm) : (T)0;
-    }
-  }
+  tmdiff::stage_halo_tile<T, G::LH, G::LS, G::LS, NT>(sa, sb, pa, pb, pm, y0 - G::HALO, x0 - G::PADX, H, W, p.vec != 0);
   __syncthreads();
 
   constexpr int n = WIN * WIN;
@@ -228,13 +194,10 @@ struct SsimFinalArgs {
   float* out32;             // weight * dssim; with terms_in the total
 };
 
-// Lane t adds the workgroups t, t + 256, ... in order; then the waves' butterflies and the four waves in order: the order depends
-// on the number of workgroups alone.
+// Lane t adds the workgroups t, t + 256, ... in order, then the workgroup sum: the order depends on the number of workgroups alone.
 __global__ void __launch_bounds__(FIN_T) ssim_finalize_kernel(SsimFinalArgs p) {
   __shared__ double red[FIN_T / 64];
-  double s = 0.0;
-  for (long i = threadIdx.x; i < p.n; i += FIN_T) s += p.part[i];
-  const double tot = tmdiff::block_sum_f64(s, red);
+  const double tot = tmdiff::block_sum_f64(tmdiff::strided_sum(p.part, p.n, 1, threadIdx.x, FIN_T), red);
   if (threadIdx.x != 0) return;
   const double ssim = tot / p.nwin, dssim = 1.0 - ssim;
   if (p.terms_in) {
@@ -250,7 +213,7 @@ __global__ void __launch_bounds__(FIN_T) ssim_finalize_kernel(SsimFinalArgs p) {
 }
 
 bool ssim_ok(int B, int C, int H, int W, int win) {
-  return B >= 1 && C >= 1 && win >= 3 && win <= 11 && (win & 1) && H >= win && W >= win && (double)B * C * H * W <= 2147483647.0;
+  return B >= 1 && C >= 1 && win >= 3 && win <= 11 && (win & 1) && H >= win && W >= win && tmdiff::fits_int32((double)B * C * H * W);
 }
 
 size_t ssim_bytes(int B, int C, int H, int W) { return (size_t)B * C * tiles_of(H, W) * sizeof(double); }
@@ -284,13 +247,12 @@ int tmdiff_ssim_loss(const float* x_true, const float* x_pred, const float* ms, 
                         data_range, weight);
   TMDIFF_REQUIRE(x_true && x_pred && out64 && out32 && workspace, "ssim_loss: null tensor");
   TMDIFF_REQUIRE(g || !accumulate, "ssim_loss: accumulate needs a gradient tensor");
-  TMDIFF_REQUIRE(workspace_bytes >= ssim_bytes(B, C, H, W) && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0 &&
-                     (reinterpret_cast<uintptr_t>(out64) & 7u) == 0 && (reinterpret_cast<uintptr_t>(terms_in) & 7u) == 0,
-                 "ssim_loss: workspace of %zu bytes, %zu needed (8-byte aligned, as out64 and terms_in)", workspace_bytes,
-                 ssim_bytes(B, C, H, W));
+  if (const int rc = tmdiff::check_workspace("ssim_loss", workspace, workspace_bytes, ssim_bytes(B, C, H, W), ", as out64 and terms_in",
+                                             out64, terms_in))
+    return rc;
   const hipStream_t st = tmdiff::as_stream(stream);
   const long tiles = tiles_of(H, W), blocks = (long)B * C * tiles;
-  if (blocks > 0x7fffffffL) return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "ssim_loss: grid of %ld blocks", blocks);
+  if (const int rc = tmdiff::check_grid(blocks, "ssim_loss", TMDIFF_E_UNSUPPORTED)) return rc;
   const bool vec = W % 4 == 0 && tmdiff::aligned16(x_true) && tmdiff::aligned16(x_pred) && (!ms || tmdiff::aligned16(ms)) &&
                    (!g || tmdiff::aligned16(g));
   const double nwin = (double)B * C * (H - win + 1) * (W - win + 1), r1 = 0.01 * data_range, r2 = 0.03 * data_range;

@@ -1174,16 +1174,51 @@ def _planes(t, name, c=None):
     return t.data_ptr(), (sb if t.shape[0] > 1 else 0), (sc if ch > 1 else h * w)
 
 
+def _f64(name, arg, t, shape, device, contiguous=True):
+    """``t``, or with None a new tensor: a contiguous float64 tensor of ``shape`` on the GPU, the call's argument ``arg``.  A
+    number as ``shape`` asks for that many elements in any shape."""
+    count = isinstance(shape, int)
+    y = t if t is not None else torch.empty(shape, device=device, dtype=torch.float64)
+    if not (y.is_cuda and y.dtype == torch.float64 and (y.is_contiguous() or not contiguous)
+            and (y.numel() == shape if count else tuple(y.shape) == tuple(shape))):
+        raise ValueError(f"{name}: {arg} must be a {'contiguous ' if contiguous else ''}float64 {[shape] if count else list(shape)} "
+                         f"tensor on the GPU")
+    return y
+
+
+def _lent(name, workspace, need, make):
+    """(workspace, its bytes): the lent tensor, or with None ``make()``; on the GPU, contiguous, at least ``need`` bytes."""
+    ws = workspace if workspace is not None else make()
+    nbytes = ws.numel() * ws.element_size()
+    if not (ws.is_cuda and ws.is_contiguous() and nbytes >= need):
+        raise ValueError(f"{name}: workspace of {nbytes} bytes, need {need}")
+    return ws, nbytes
+
+
+def _grad_target(name, grad, like):
+    """The tensor a loss writes its gradient to: True allocates one like ``like``, a tensor receives it, False or None selects the
+    value-only mode (None)."""
+    if grad is False or grad is None:
+        return None
+    g = torch.empty_like(like) if grad is True else grad
+    if g.shape != like.shape:
+        raise ValueError(f"{name}: g {tuple(g.shape)}, need {tuple(like.shape)}")
+    return g
+
+
+def _total32(name, total, device):
+    """The one-element float32 tensor a loss writes its total to: ``total``, or with None a new scalar."""
+    y32 = total if total is not None else torch.empty((), device=device, dtype=torch.float32)
+    if y32.numel() != 1:
+        raise ValueError(f"{name}: total must hold one float32")
+    return y32
+
+
 def _metrics_buffers(name, k, b, c, h, w, device, out, workspace):
     if not metrics_supported(b, c, h, w):
         raise ValueError(f"{name}: B={b} C={c} H={h} W={w} is not supported (1 <= C <= 16, H, W >= 7, fewer than 2^31 elements)")
-    y = out if out is not None else torch.empty(b, k, device=device, dtype=torch.float64)
-    if not (y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and tuple(y.shape) == (b, k)):
-        raise ValueError(f"{name}: out must be a contiguous float64 [{b}, {k}] tensor on the GPU")
-    ws = workspace if workspace is not None else metrics_workspace(b, c, h, w, device)
-    nbytes = ws.numel() * ws.element_size()
-    if not (ws.is_cuda and ws.is_contiguous() and nbytes >= lib.tmdiff_metrics_workspace_bytes(b, c, h, w)):
-        raise ValueError(f"{name}: workspace of {nbytes} bytes, need {lib.tmdiff_metrics_workspace_bytes(b, c, h, w)}")
+    y = _f64(name, "out", out, (b, k), device)
+    ws, nbytes = _lent(name, workspace, lib.tmdiff_metrics_workspace_bytes(b, c, h, w), lambda: metrics_workspace(b, c, h, w, device))
     return y, ws, nbytes
 
 
@@ -1249,22 +1284,11 @@ def spectral_spatial_loss(x0, xhat, ms=None, base="l1", w_sam=0.0, w_lap=0.0, gr
         raise ValueError(f"spectral_spatial_loss: B={b} C={c} H={h} W={w} is not supported ({_LOSS_LIMITS})")
     px, ph, pm = _chk(x0, "x0"), _chk(xhat, "xhat"), _chk(ms, "ms")
     dev = x0.device
-    g = None
-    if grad is not False and grad is not None:
-        g = torch.empty_like(xhat) if grad is True else grad
-        if g.shape != xhat.shape:
-            raise ValueError(f"spectral_spatial_loss: g {tuple(g.shape)}, need {tuple(xhat.shape)}")
-    y = terms if terms is not None else torch.empty(4, device=dev, dtype=torch.float64)
-    if not (y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and y.numel() == 4):
-        raise ValueError("spectral_spatial_loss: terms must be a contiguous float64 [4] tensor on the GPU")
-    y32 = total if total is not None else torch.empty((), device=dev, dtype=torch.float32)
-    if y32.numel() != 1:
-        raise ValueError("spectral_spatial_loss: total must hold one float32")
+    g = _grad_target("spectral_spatial_loss", grad, xhat)
+    y = _f64("spectral_spatial_loss", "terms", terms, 4, dev)
+    y32 = _total32("spectral_spatial_loss", total, dev)
     need = lib.tmdiff_loss_workspace_bytes(b, c, h, w, int(lap))
-    ws = workspace if workspace is not None else _workspace(dev, need, "loss")
-    nbytes = ws.numel() * ws.element_size()
-    if not (ws.is_cuda and ws.is_contiguous() and nbytes >= need):
-        raise ValueError(f"spectral_spatial_loss: workspace of {nbytes} bytes, need {need}")
+    ws, nbytes = _lent("spectral_spatial_loss", workspace, need, lambda: _workspace(dev, need, "loss"))
     check(lib.tmdiff_spectral_spatial_loss(px, ph, pm, _chk(g, "g"), LOSS_BASE_KINDS[base], w_sam, w_lap, y.data_ptr(),
                                            _chk(y32, "total"), ws.data_ptr(), nbytes, b, c, h, w, stream_ptr()),
           "spectral_spatial_loss")
@@ -1304,26 +1328,13 @@ def ssim_loss(x_true, x_pred, win=7, data_range=1.0, weight=1.0, grad=True, accu
         raise ValueError("ssim_loss: accumulate=True needs the gradient tensor to add to as `grad`")
     pa, pb, pm = _chk(x_true, "x_true"), _chk(x_pred, "x_pred"), _chk(ms, "ms")
     dev = x_true.device
-    g = None
-    if grad is not False and grad is not None:
-        g = torch.empty_like(x_pred) if grad is True else grad
-        if g.shape != x_pred.shape:
-            raise ValueError(f"ssim_loss: g {tuple(g.shape)}, need {tuple(x_pred.shape)}")
-    nout = 2 if terms_in is None else 5
-    if terms_in is not None and not (terms_in.is_cuda and terms_in.dtype == torch.float64 and terms_in.is_contiguous() and
-                                     terms_in.numel() == 4):
-        raise ValueError("ssim_loss: terms_in must be a contiguous float64 [4] tensor on the GPU")
-    y = out if out is not None else torch.empty(nout, device=dev, dtype=torch.float64)
-    if not (y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and y.numel() == nout):
-        raise ValueError(f"ssim_loss: out must be a contiguous float64 [{nout}] tensor on the GPU")
-    y32 = total if total is not None else torch.empty((), device=dev, dtype=torch.float32)
-    if y32.numel() != 1:
-        raise ValueError("ssim_loss: total must hold one float32")
+    g = _grad_target("ssim_loss", grad, x_pred)
+    if terms_in is not None:
+        _f64("ssim_loss", "terms_in", terms_in, 4, dev)
+    y = _f64("ssim_loss", "out", out, 2 if terms_in is None else 5, dev)
+    y32 = _total32("ssim_loss", total, dev)
     need = lib.tmdiff_ssim_loss_workspace_bytes(b, c, h, w, win)
-    ws = workspace if workspace is not None else _workspace(dev, need, "ssim_loss")
-    nbytes = ws.numel() * ws.element_size()
-    if not (ws.is_cuda and ws.is_contiguous() and nbytes >= need):
-        raise ValueError(f"ssim_loss: workspace of {nbytes} bytes, need {need}")
+    ws, nbytes = _lent("ssim_loss", workspace, need, lambda: _workspace(dev, need, "ssim_loss"))
     check(lib.tmdiff_ssim_loss(pa, pb, pm, _chk(g, "g"), win, data_range, weight, int(bool(accumulate)),
                                None if terms_in is None else terms_in.data_ptr(), y.data_ptr(), _chk(y32, "total"),
                                ws.data_ptr(), nbytes, b, c, h, w, stream_ptr()), "ssim_loss")
@@ -1365,16 +1376,11 @@ def metrics_q2n(x_true, x_pred, block=32, shift=32, out=None, map_out=None, work
         raise ValueError(f"metrics_q2n: B={b} C={c} H={h} W={w} block={block} shift={shift} is not supported ({_Q2N_LIMITS})")
     ny, nx = q2n_grid(h, w, block, shift)
     dev = x_true.device
-    y = out if out is not None else torch.empty(b, device=dev, dtype=torch.float64)
-    if not (y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and tuple(y.shape) == (b,)):
-        raise ValueError(f"metrics_q2n: out must be a contiguous float64 [{b}] tensor on the GPU")
-    if map_out is not None and not (map_out.is_cuda and map_out.dtype == torch.float64 and map_out.is_contiguous()
-                                    and tuple(map_out.shape) == (b, ny, nx)):
-        raise ValueError(f"metrics_q2n: map_out must be a contiguous float64 [{b}, {ny}, {nx}] tensor on the GPU")
-    ws = workspace if workspace is not None else metrics_q2n_workspace(b, c, h, w, dev, block, shift)
-    nbytes, need = ws.numel() * ws.element_size(), lib.tmdiff_metrics_q2n_workspace_bytes(b, c, h, w, block, shift)
-    if not (ws.is_cuda and ws.is_contiguous() and nbytes >= need):
-        raise ValueError(f"metrics_q2n: workspace of {nbytes} bytes, need {need}")
+    y = _f64("metrics_q2n", "out", out, (b,), dev)
+    if map_out is not None:
+        _f64("metrics_q2n", "map_out", map_out, (b, ny, nx), dev)
+    ws, nbytes = _lent("metrics_q2n", workspace, lib.tmdiff_metrics_q2n_workspace_bytes(b, c, h, w, block, shift),
+                       lambda: metrics_q2n_workspace(b, c, h, w, dev, block, shift))
     check(lib.tmdiff_metrics_q2n(pa, asb, asc, pb, bsb, bsc, b, c, h, w, block, shift, y.data_ptr(),
                                  map_out.data_ptr() if map_out is not None else None, ws.data_ptr(), nbytes, stream_ptr()),
           "metrics_q2n")
@@ -1543,19 +1549,13 @@ def metrics_dsblock(ps, ms_exp, pan, pan_lp, block=32, q=1.0, out=None, maps_out
         raise ValueError(f"metrics_dsblock: B={b} C={c} H={h} W={w} block={block} q={q} is not supported ({_DSBLOCK_LIMITS})")
     ny, nx = q2n_grid(h, w, block, block)
     dev = ps.device
-    y = out if out is not None else torch.empty(b, 2, device=dev, dtype=torch.float64)
-    if not (y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and tuple(y.shape) == (b, 2)):
-        raise ValueError(f"metrics_dsblock: out must be a contiguous float64 [{b}, 2] tensor on the GPU")
-    if maps_out is not None and not (maps_out.is_cuda and maps_out.dtype == torch.float64 and maps_out.is_contiguous()
-                                     and tuple(maps_out.shape) == (b, c, 2, ny, nx)):
-        raise ValueError(f"metrics_dsblock: maps_out must be a contiguous float64 [{b}, {c}, 2, {ny}, {nx}] tensor on the GPU")
-    if d_lambda is not None and not (d_lambda.is_cuda and d_lambda.dtype == torch.float64 and d_lambda.is_contiguous()
-                                     and tuple(d_lambda.shape) == (b,)):
-        raise ValueError(f"metrics_dsblock: d_lambda must be a contiguous float64 [{b}] tensor on the GPU")
-    ws = workspace if workspace is not None else metrics_dsblock_workspace(b, c, h, w, dev, block)
-    nbytes, need = ws.numel() * ws.element_size(), lib.tmdiff_metrics_dsblock_workspace_bytes(b, c, h, w, block)
-    if not (ws.is_cuda and ws.is_contiguous() and nbytes >= need):
-        raise ValueError(f"metrics_dsblock: workspace of {nbytes} bytes, need {need}")
+    y = _f64("metrics_dsblock", "out", out, (b, 2), dev)
+    if maps_out is not None:
+        _f64("metrics_dsblock", "maps_out", maps_out, (b, c, 2, ny, nx), dev)
+    if d_lambda is not None:
+        _f64("metrics_dsblock", "d_lambda", d_lambda, (b,), dev)
+    ws, nbytes = _lent("metrics_dsblock", workspace, lib.tmdiff_metrics_dsblock_workspace_bytes(b, c, h, w, block),
+                       lambda: metrics_dsblock_workspace(b, c, h, w, dev, block))
     check(lib.tmdiff_metrics_dsblock(pa, asb, asc, pb, bsb, bsc, pp, psb, pq, qsb, b, c, h, w, block, q,
                                      d_lambda.data_ptr() if d_lambda is not None else None, float(alpha), float(beta),
                                      y.data_ptr(), maps_out.data_ptr() if maps_out is not None else None, ws.data_ptr(), nbytes,
@@ -1584,11 +1584,11 @@ def metrics_hqnr_buffers(b, c, h, w, device, ratio=4, block=32):
     if not metrics_dsblock_supported(b, c, h, w, block):
         raise ValueError(f"metrics_hqnr: B={b} C={c} H={h} W={w} block={block} is not supported ({_DSBLOCK_LIMITS})")
     f32 = dict(device=device, dtype=torch.float32)
-    f64 = dict(device=device, dtype=torch.float64)
+    f64 = lambda arg, *shape: _f64("metrics_hqnr", arg, None, shape, device)
     return {"shape": (b, c, h, w, ratio, block),
             "filtered": torch.empty(b, c, h, w, **f32), "pan_lp": torch.empty(b, 1, h, w, **f32),
             "pan_low": torch.empty(b, 1, h // ratio, w // ratio, **f32),
-            "q2n": torch.empty(b, **f64), "d_lambda": torch.empty(b, **f64), "d_s": torch.empty(b, 2, **f64),
+            "q2n": f64("q2n", b), "d_lambda": f64("d_lambda", b), "d_s": f64("d_s", b, 2),
             "q2n_ws": metrics_q2n_workspace(b, c, h, w, device, block, block),
             "ds_ws": metrics_dsblock_workspace(b, c, h, w, device, block)}
 
@@ -1610,9 +1610,7 @@ def metrics_hqnr(ps, ms_exp, pan, sensor, ratio=4, block=32, alpha=1.0, beta=1.0
     if buf["shape"] != (b, c, h, w, ratio, block) or buf["filtered"].device != ps.device:
         raise ValueError(f"metrics_hqnr: buffers made for {buf['shape']}, the call is {(b, c, h, w, ratio, block)}")
     ms_gains, pan_gain = metrics.mtf_gains(sensor, c)
-    y = out if out is not None else torch.empty(b, 3, device=ps.device, dtype=torch.float64)
-    if not (y.is_cuda and y.dtype == torch.float64 and tuple(y.shape) == (b, 3)):
-        raise ValueError(f"metrics_hqnr: out must be a float64 [{b}, 3] tensor on the GPU")
+    y = _f64("metrics_hqnr", "out", out, (b, 3), ps.device, contiguous=False)
     filtered = fir_decimate(ps, _mtf_taps(ms_gains, ratio, ps.device), 1, None, buf["filtered"])
     metrics_q2n(ms_exp, filtered, block, block, out=buf["q2n"], workspace=buf["q2n_ws"])
     torch.neg(buf["q2n"], out=buf["d_lambda"]).add_(1.0)                       # 1 - Q2n, as the host rounds it
