@@ -796,6 +796,22 @@ int tmdiff_fir_decimate(const float* x, const float* taps, float* y, int32_t pla
                         int32_t K, int32_t ratio, int32_t off_y, int32_t off_x, tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * The adjoint of fir_decimate (csrc/mtf.hip; host definition: tmdiff_amd/metrics.py, fir_decimate_adjoint):
+ *   dx = beta * base + alpha * A^T g,   g [planes, ceil((H - off_y) / ratio), ceil((W - off_x) / ratio)],   dx, base [planes, H, W]
+ *   (A^T g)[p, y, x] = sum over (i, u, j, v) with clamp(ratio i + off_y - R + u, 0, H - 1) == y and
+ *                      clamp(ratio j + off_x - R + v, 0, W - 1) == x   of   taps[p % taps_period, u, v] * g[p, i, j]
+ * the exact transpose, the replicated border included: a border pixel collects every position that was clamped onto it.  A
+ * gather without atomics; a pixel is one chain of fused multiply-adds from 0 over its terms in lexicographic order of
+ * (i, u, j, v), whatever the tile, grid or plane that makes it, then r = alpha * acc and, when beta != 0, fma(beta, base, r).
+ * `base` may be NULL when beta == 0 (it is not read then) and may be `dx` itself.  Nothing is allocated or synchronised.
+ * The limits are fir_decimate's, checked in the same order.  planes == 0 returns TMDIFF_OK; an operator without samples
+ * (H <= off_y or W <= off_x) has A^T g = 0 and `g` may be NULL; any other null tensor is TMDIFF_E_INVALID.
+ * ------------------------------------------------------------------------------------ */
+int tmdiff_fir_decimate_adjoint(const float* g, const float* taps, const float* base, float* dx, float alpha, float beta,
+                                int32_t planes, int32_t taps_period, int32_t H, int32_t W, int32_t K, int32_t ratio, int32_t off_y,
+                                int32_t off_x, tmdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Standalone attention operators of core/Attention.py (imported by nothing in the reference; built because the
  * north star names them).  All fp32.
  *  attn_fwd : out = softmax(q k^T * scale [key mask]) v per (batch, head); fp32 MFMA, online softmax.

@@ -224,6 +224,8 @@ SIGNATURES.update({
     "tmdiff_upsample_poly23": (C.c_int, [vp, vp] + [C.c_int32] * 5 + [vp]),      # ... ratio, phase
     # FIR filtering with decimation (csrc/mtf.hip): x, taps, y | planes, taps_period, H, W, K, ratio, off_y, off_x
     "tmdiff_fir_decimate": (C.c_int, [vp, vp, vp] + [C.c_int32] * 8 + [vp]),
+    # its adjoint: g, taps, base, dx | alpha, beta | planes, taps_period, H, W, K, ratio, off_y, off_x
+    "tmdiff_fir_decimate_adjoint": (C.c_int, [vp, vp, vp, vp, C.c_float, C.c_float] + [C.c_int32] * 8 + [vp]),
 })
 
 

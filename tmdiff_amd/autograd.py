@@ -515,6 +515,28 @@ def attention(q, k, v, scale, heads=1, key_mask=None):
     return AttentionFn.apply(q, k, v, float(scale), heads, key_mask)
 
 
+class FirDecimateFn(torch.autograd.Function):
+    """ops.fir_decimate, differentiable in x: the forward is the plain call, the backward the adjoint kernel
+    (ops.fir_decimate_adjoint), a gather without atomics, so the gradient is the same bits on every run.  The operator is
+    linear: nothing is saved but the taps (through save_for_backward, so a table changed in place before the backward is
+    reported) and the extents.  No gradient flows to the taps; the backward is not differentiable again."""
+
+    @staticmethod
+    def forward(ctx, x, taps, ratio, offset):
+        y = ops.fir_decimate(x.detach(), taps, ratio, offset)          # checks x: float32 [B, C, H, W]
+        ctx.ratio, ctx.offset, ctx.hw = ratio, offset, tuple(x.shape[2:])
+        ctx.save_for_backward(taps)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        taps, = ctx.saved_tensors
+        if gy.dtype != torch.float32:
+            raise ValueError(f"FirDecimateFn: the incoming gradient is {gy.dtype}, the operator is float32")
+        return ops.fir_decimate_adjoint(gy.contiguous(), taps, ctx.hw, ctx.ratio, ctx.offset), None, None, None
+
+
 class _GemmNT(torch.autograd.Function):
     """ops.gemm_nt (a [..., K] @ w[N, K]^T + bias + residual) with its gradients: the input and weight gradients are gemm_nt
     calls on transposed operands (the transposes are torch copies), the bias gradient is ops.channel_sum over the rows."""

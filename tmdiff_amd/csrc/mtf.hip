@@ -28,6 +28,39 @@
 // The taps are the same for every lane of a workgroup: they are read through a wave-uniform address (scalar loads into SGPRs,
 // straight into the multiply-add's scalar operand) and never enter the vector path.  One LDS read per multiply-add remains: the
 // kernel is bound by the LDS read rate (profiles/mtf_degrade.txt).
+//
+// THE ADJOINT, tmdiff_fir_decimate_adjoint: dx = beta * base + alpha * A^T g for the operator A above (host definition:
+// metrics.fir_decimate_adjoint), the clamp included -- a border pixel collects every position that the replicated border
+// mapped onto it:
+//
+//   (A^T g)[p, y, x] = sum over (i, u, j, v) with clamp(ratio i + oy - R + u, 0, H - 1) == y and
+//                      clamp(ratio j + ox - R + v, 0, W - 1) == x   of   taps[p % T, u, v] * g[p, i, j]
+//
+// A gather: every dx pixel is made by one lane, no atomics, so the same bits come out of every run and of a graph replay.
+//
+// SUMMATION ORDER of a dx pixel, the same wherever it is made: acc = 0, then the terms of the sum above in lexicographic
+// order of (i, u, j, v) -- i outermost, v innermost, each ascending -- one fused multiply-add each,
+// acc = fma(taps[u][v], g[i][j], acc).  Away from the border a pixel has one u per i and one v per j: the g samples in
+// row-major order, with the tap that reaches the pixel from each.  It does not depend on the tile, the grid, the plane loop or
+// the ratio's instantiation (K is a run-time value in all three).  The kernel also walks positions (i, j) outside g, staged as zeros, and fma(t, 0, acc) == acc for every
+// finite tap t (acc starts at +0 and a sum that starts there never becomes -0): those steps change no bit.  The epilogue is
+// r = alpha * acc rounded once, then, when beta != 0, fma(beta, base, r); beta == 0 never reads base.
+//
+// A 256-lane workgroup owns 16 x 16 BLOCKS of ratio x ratio dx pixels (64 x 64 pixels at x4), a block -- every phase of the
+// decimation -- per lane.  For a block row b and a g row i = b - d the pixel rows of the block take the taps
+// u = ratio d + a + (R - oy), a = 0 .. ratio - 1: the same d, and so the same taps, for every lane.  The taps stay wave-uniform
+// scalar loads that feed the multiply-add's scalar operand, and ONE ds_read_b32 of a g sample feeds ratio^2 multiply-adds (the
+// forward: one).  The loop runs d and e (columns) downwards, which is i and j upwards.  Steps whose ratio x ratio taps all lie
+// inside the table take a path without checks; the one or two d (e) at either end check each tap, uniformly.  The g patch of
+// a tile is 16 + (K + ratio - 2) / ratio rows and columns (26 at x4 and K = 41), with a row stride of 16 (mod 32) dwords so that
+// the two block rows a ds_read_b32 serves take disjoint banks.  A row of a block is one 16-byte store at x4 (8 at x2) when the
+// row length and the pointers allow it, single dwords otherwise, with the same values.
+//
+// THE FOLDED BORDER lives in a path that interior tiles do not enter.  A tile that touches the image border stages the band's
+// taps in LDS as well, and up to 4 x 16 ratio lanes each sum one border pixel of the tile in the order above, from the g patch
+// (it holds every sample such a pixel needs: rows i <= (R - oy) / ratio for y = 0 lie below the patch's last row
+// b0 + 15 - dmin, rows i >= (H - 1 - oy - R) / ratio for y = H - 1 above its first, b0 - dmax).  The sums go through LDS to the
+// lanes that own the pixels, which store them with the rest of their block.
 #include <algorithm>
 
 #include "common.h"
@@ -94,25 +127,200 @@ void launch_fir(const float* x, const float* taps, float* y, int planes, int per
   else fir_decimate_kernel<R, 0><<<grid, 256, 0, st>>>(x, taps, y, planes, period, H, W, K, off_y, off_x);
 }
 
+template <int R>
+struct AdjPatch {
+  static constexpr int B = 16;                                   // blocks of R x R dx pixels along an edge of the tile
+  static constexpr int TS = B * R;                               // pixels along an edge of the tile
+  static constexpr int KMAX = 41;
+  static constexpr int ND = (KMAX + R - 2) / R + 1;              // most values of d (of e) that reach a block
+  static constexpr int PR = B + ND - 1;                          // rows and columns of the g patch at K = 41
+  static constexpr int PS = PR <= 48 ? 48 : 80;                  // row stride: 16 (mod 32)
+  static_assert(PS >= PR && PS % 32 == 16 && 4 * TS <= 256, "patch layout");
+};
+
+template <int R> struct FirVec { using type = float; };
+template <> struct FirVec<2> { using type = float2; };
+template <> struct FirVec<4> { using type = float4; };
+
+// The u (or v) of the terms that row (column) `pos` of an image of `len` rows collects from sample i, whose tap 0 sits at p0.
+__device__ __forceinline__ void fir_fold_range(int pos, int len, int p0, int K, int& lo, int& hi) {
+  lo = hi = pos - p0;
+  if (pos == 0) lo = 0;                  // every position <= 0 was clamped onto row 0
+  if (pos == len - 1) hi = K - 1;        // every position >= len - 1 onto the last row
+  lo = max(lo, 0);
+  hi = min(hi, K - 1);
+}
+
+// dx[pl] of the tile blockIdx.x, 16 x 16 blocks of R x R pixels; blockIdx.y walks the planes.  K is a run-time value: no loop
+// here gains from unrolling over it.
+// base may alias dx: a lane reads base where it then writes dx and nowhere else.
+template <int R>
+__global__ void __launch_bounds__(256) fir_adjoint_kernel(const float* __restrict__ g, const float* __restrict__ taps, const float* base,
+                                                          float* dx, float alpha, float beta, int planes, int period, int H, int W,
+                                                          int K, int off_y, int off_x, int vec) {
+  using P = AdjPatch<R>;
+  using V = typename FirVec<R>::type;
+  __shared__ float s[P::PR * P::PS];
+  __shared__ float st[P::KMAX * P::KMAX];   // border tiles: the band's taps
+  __shared__ float se[4 * P::TS];           // border tiles: the sums of the tile's border pixels
+  const int rad = K / 2;
+  const int HO = (H - off_y + R - 1) / R, WO = (W - off_x + R - 1) / R;
+  const int cy = rad - off_y, cx = rad - off_x;                            // u = R d + a + cy, v = R e + a + cx
+  const int dmax = (K - 1 - cy) / R, dmin = -((cy + R - 1) / R);           // the d with a tap inside the table for some a
+  const int emax = (K - 1 - cx) / R, emin = -((cx + R - 1) / R);
+  const int tiles_x = ((W + R - 1) / R + P::B - 1) / P::B;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int i0 = ty * P::B - dmax, j0 = tx * P::B - emax;                  // the g sample at the patch's origin
+  const int nr = P::B + dmax - dmin, nc = P::B + emax - emin;              // rows and columns of the patch
+  const int ylo = ty * P::TS, yhi = min(ylo + P::TS, H) - 1, xlo = tx * P::TS, xhi = min(xlo + P::TS, W) - 1;
+  const bool border = ylo == 0 || yhi == H - 1 || xlo == 0 || xhi == W - 1;
+  const int ly = threadIdx.x >> 4, lx = threadIdx.x & 15;
+  const int y0 = ylo + R * ly, x0 = xlo + R * lx;
+  for (int pl = blockIdx.y; pl < planes; pl += gridDim.y) {
+    const float* gp = g + pl * HO * WO;
+    const float* tp = taps + (pl % period) * K * K;
+    for (int idx = threadIdx.x; idx < nr * nc; idx += 256) {
+      const int r = idx / nc, c = idx - r * nc;
+      const int i = i0 + r, j = j0 + c;
+      s[r * P::PS + c] = (i >= 0 && i < HO && j >= 0 && j < WO) ? gp[i * WO + j] : 0.f;
+    }
+    if (border)
+      for (int idx = threadIdx.x; idx < K * K; idx += 256) st[idx] = tp[idx];
+    __syncthreads();
+    float acc[R][R];
+#pragma unroll
+    for (int a = 0; a < R; ++a)
+#pragma unroll
+      for (int c = 0; c < R; ++c) acc[a][c] = 0.f;
+    const float* sp = s + ly * P::PS + lx;
+    for (int dd = 0; dd <= dmax - dmin; ++dd) {                 // d = dmax - dd: the g rows upwards
+      const int ub = R * (dmax - dd) + cy;
+      const bool rows_in = ub >= 0 && ub + R <= K;
+      for (int ee = 0; ee <= emax - emin; ++ee) {
+        const int vb = R * (emax - ee) + cx;
+        const float gv = sp[dd * P::PS + ee];
+        const float* t = tp + ub * K + vb;
+        if (rows_in && vb >= 0 && vb + R <= K) {
+#pragma unroll
+          for (int a = 0; a < R; ++a)
+#pragma unroll
+            for (int c = 0; c < R; ++c) acc[a][c] = __fmaf_rn(t[a * K + c], gv, acc[a][c]);
+        } else {
+#pragma unroll
+          for (int a = 0; a < R; ++a)
+#pragma unroll
+            for (int c = 0; c < R; ++c)
+              if ((unsigned)(ub + a) < (unsigned)K && (unsigned)(vb + c) < (unsigned)K) acc[a][c] = __fmaf_rn(t[a * K + c], gv, acc[a][c]);
+        }
+      }
+    }
+    if (border) {                                               // uniform: interior tiles skip all of it
+      const int seg = threadIdx.x / P::TS, k = threadIdx.x - seg * P::TS;
+      int y = ylo + k, x = xlo + k;
+      bool have = false;
+      if (seg == 0) { y = 0; have = ylo == 0 && x <= xhi; }
+      else if (seg == 1) { y = H - 1; have = yhi == H - 1 && H > 1 && x <= xhi; }
+      else if (seg == 2) { x = 0; have = xlo == 0 && y <= yhi && y != 0 && y != H - 1; }
+      else if (seg == 3) { x = W - 1; have = xhi == W - 1 && W > 1 && y <= yhi && y != 0 && y != H - 1; }
+      if (have) {
+        const int ia = max(i0, 0), ib = min(i0 + nr, HO) - 1, ja = max(j0, 0), jb = min(j0 + nc, WO) - 1;
+        float e = 0.f;
+        for (int i = ia; i <= ib; ++i) {
+          int ulo, uhi;
+          fir_fold_range(y, H, R * i + off_y - rad, K, ulo, uhi);
+          for (int u = ulo; u <= uhi; ++u)
+            for (int j = ja; j <= jb; ++j) {
+              int vlo, vhi;
+              fir_fold_range(x, W, R * j + off_x - rad, K, vlo, vhi);
+              const float gv = s[(i - i0) * P::PS + j - j0];
+              const float* tr = st + u * K;
+              int v = vlo;
+              for (; v + 3 <= vhi; v += 4) {                    // four taps in flight ahead of the chain; the order stays
+                const float t0 = tr[v], t1 = tr[v + 1], t2 = tr[v + 2], t3 = tr[v + 3];
+                e = __fmaf_rn(t0, gv, e);
+                e = __fmaf_rn(t1, gv, e);
+                e = __fmaf_rn(t2, gv, e);
+                e = __fmaf_rn(t3, gv, e);
+              }
+              for (; v <= vhi; ++v) e = __fmaf_rn(tr[v], gv, e);
+            }
+        }
+        se[threadIdx.x] = e;
+      }
+      __syncthreads();
+    }
+    if (y0 < H && x0 < W) {
+#pragma unroll
+      for (int a = 0; a < R; ++a) {
+        const int y = y0 + a;
+        if (y >= H) break;
+        if (border) {
+#pragma unroll
+          for (int c = 0; c < R; ++c) {
+            const int x = x0 + c;
+            if (x < W && (y == 0 || y == H - 1 || x == 0 || x == W - 1))
+              acc[a][c] = se[y == 0 ? x - xlo : (y == H - 1 ? P::TS + x - xlo : (x == 0 ? 2 * P::TS + y - ylo : 3 * P::TS + y - ylo))];
+          }
+        }
+        const int o = (pl * H + y) * W + x0;
+        float r[R], b[R];
+        if (vec) {                                              // W is a multiple of R here: the row of the block is whole
+          if (beta != 0.f) *reinterpret_cast<V*>(b) = *reinterpret_cast<const V*>(base + o);
+#pragma unroll
+          for (int c = 0; c < R; ++c) {
+            r[c] = __fmul_rn(alpha, acc[a][c]);
+            if (beta != 0.f) r[c] = __fmaf_rn(beta, b[c], r[c]);
+          }
+          *reinterpret_cast<V*>(dx + o) = *reinterpret_cast<const V*>(r);
+        } else {
+#pragma unroll
+          for (int c = 0; c < R; ++c) {
+            if (x0 + c >= W) break;
+            r[c] = __fmul_rn(alpha, acc[a][c]);
+            if (beta != 0.f) r[c] = __fmaf_rn(beta, base[o + c], r[c]);
+            dx[o + c] = r[c];
+          }
+        }
+      }
+    }
+    __syncthreads();   // the next plane overwrites the patch, the taps and the border sums
+  }
+}
+
+template <int R>
+void launch_fir_adjoint(const float* g, const float* taps, const float* base, float* dx, float alpha, float beta, int planes, int period,
+                        int H, int W, int K, int off_y, int off_x, hipStream_t st) {
+  constexpr int TS = AdjPatch<R>::TS;
+  const dim3 grid((unsigned)(((H + TS - 1) / TS) * ((W + TS - 1) / TS)), (unsigned)std::min(planes, 65535));
+  const uintptr_t align = reinterpret_cast<uintptr_t>(dx) | (beta != 0.f ? reinterpret_cast<uintptr_t>(base) : 0);
+  const int vec = R > 1 && W % R == 0 && align % (4 * R) == 0;
+  fir_adjoint_kernel<R><<<grid, 256, 0, st>>>(g, taps, base, dx, alpha, beta, planes, period, H, W, K, off_y, off_x, vec);
+}
+
+// The limits of both entry points, checked in the header's order; TMDIFF_OK when the extents are taken.
+int fir_limits(const char* name, int K, int ratio, int off_y, int off_x, int H, int W, int planes, int taps_period) {
+  const char* limits = "K odd, 1 <= K <= 41; ratio 1, 2 or 4; 0 <= off_y, off_x < ratio; H, W >= 1; planes >= 0; taps_period >= 1 and "
+                       "a divisor of planes; planes * H * W <= 2^31 - 1";
+  if (K < 1 || K > 41 || K % 2 == 0) return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "%s: K=%d (%s)", name, K, limits);
+  if (ratio != 1 && ratio != 2 && ratio != 4) return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "%s: ratio=%d (%s)", name, ratio, limits);
+  if (off_y < 0 || off_y >= ratio || off_x < 0 || off_x >= ratio)
+    return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "%s: offset off_y=%d off_x=%d at ratio=%d (%s)", name, off_y, off_x, ratio, limits);
+  if (H < 1 || W < 1 || planes < 0)
+    return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "%s: bad extents planes=%d H=%d W=%d (%s)", name, planes, H, W, limits);
+  if (taps_period < 1 || planes % taps_period)
+    return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "%s: taps_period=%d with planes=%d (%s)", name, taps_period, planes, limits);
+  if ((double)planes * H * W > 2147483647.0)
+    return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "%s: planes=%d H=%d W=%d exceeds 32-bit element offsets (%s)", name, planes, H, W, limits);
+  return TMDIFF_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int tmdiff_fir_decimate(const float* x, const float* taps, float* y, int32_t planes, int32_t taps_period, int32_t H, int32_t W,
                         int32_t K, int32_t ratio, int32_t off_y, int32_t off_x, tmdiff_stream_t stream) {
-  const char* limits = "K odd, 1 <= K <= 41; ratio 1, 2 or 4; 0 <= off_y, off_x < ratio; H, W >= 1; planes >= 0; taps_period >= 1 and "
-                       "a divisor of planes; planes * H * W <= 2^31 - 1";
-  if (K < 1 || K > 41 || K % 2 == 0) return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "fir_decimate: K=%d (%s)", K, limits);
-  if (ratio != 1 && ratio != 2 && ratio != 4) return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "fir_decimate: ratio=%d (%s)", ratio, limits);
-  if (off_y < 0 || off_y >= ratio || off_x < 0 || off_x >= ratio)
-    return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "fir_decimate: offset off_y=%d off_x=%d at ratio=%d (%s)", off_y, off_x, ratio, limits);
-  if (H < 1 || W < 1 || planes < 0)
-    return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "fir_decimate: bad extents planes=%d H=%d W=%d (%s)", planes, H, W, limits);
-  if (taps_period < 1 || planes % taps_period)
-    return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "fir_decimate: taps_period=%d with planes=%d (%s)", taps_period, planes, limits);
-  if ((double)planes * H * W > 2147483647.0)
-    return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "fir_decimate: planes=%d H=%d W=%d exceeds 32-bit element offsets (%s)", planes, H, W,
-                        limits);
+  if (const int rc = fir_limits("fir_decimate", K, ratio, off_y, off_x, H, W, planes, taps_period)) return rc;
   if (planes == 0 || H <= off_y || W <= off_x) return TMDIFF_OK;   // no plane, or no sample at o + ratio * i inside the image
   TMDIFF_REQUIRE(x && taps && y, "fir_decimate: null tensor");
   const hipStream_t st = tmdiff::as_stream(stream);
@@ -120,6 +328,20 @@ int tmdiff_fir_decimate(const float* x, const float* taps, float* y, int32_t pla
   else if (ratio == 2) launch_fir<2>(x, taps, y, planes, taps_period, H, W, K, off_y, off_x, st);
   else launch_fir<1>(x, taps, y, planes, taps_period, H, W, K, off_y, off_x, st);
   return tmdiff::check_launch("fir_decimate");
+}
+
+int tmdiff_fir_decimate_adjoint(const float* g, const float* taps, const float* base, float* dx, float alpha, float beta, int32_t planes,
+                                int32_t taps_period, int32_t H, int32_t W, int32_t K, int32_t ratio, int32_t off_y, int32_t off_x,
+                                tmdiff_stream_t stream) {
+  if (const int rc = fir_limits("fir_decimate_adjoint", K, ratio, off_y, off_x, H, W, planes, taps_period)) return rc;
+  if (planes == 0) return TMDIFF_OK;
+  TMDIFF_REQUIRE(taps && dx && (base || beta == 0.f), "fir_decimate_adjoint: null tensor");
+  TMDIFF_REQUIRE(g || H <= off_y || W <= off_x, "fir_decimate_adjoint: null tensor");   // an operator without samples has no g
+  const hipStream_t st = tmdiff::as_stream(stream);
+  if (ratio == 4) launch_fir_adjoint<4>(g, taps, base, dx, alpha, beta, planes, taps_period, H, W, K, off_y, off_x, st);
+  else if (ratio == 2) launch_fir_adjoint<2>(g, taps, base, dx, alpha, beta, planes, taps_period, H, W, K, off_y, off_x, st);
+  else launch_fir_adjoint<1>(g, taps, base, dx, alpha, beta, planes, taps_period, H, W, K, off_y, off_x, st);
+  return tmdiff::check_launch("fir_decimate_adjoint");
 }
 
 }  // extern "C"

@@ -36,7 +36,9 @@ def wald_pair(ms, pan, sensor, ratio=4):
     multiples of ``ratio``: the trainer's dictionary with HR = ms, LR = mtf_degrade(ms) [H / ratio], PAN = mtf_degrade(pan) with
     the sensor's PAN gain [H], MS = upsample_poly23(LR, ratio) [H] and Res = HR - MS.  ``sensor``: a key of
     ``metrics.MTF_GAINS`` (any other name takes the default row) or explicit gains (MS gains, PAN gain).  Tensors on the GPU go
-    through the device operators (float32); host tensors and arrays through the float64 definitions of ``metrics``."""
+    through the device operators (float32); host tensors and arrays through the float64 definitions of ``metrics``.  On the
+    device LR and PAN are differentiable in ms and pan (``ops.mtf_degrade``: the backward is the adjoint kernel); MS, the
+    interpolation of LR, carries no gradient."""
     from . import metrics
     if ratio not in (2, 4):
         raise ValueError(f"wald_pair: ratio={ratio} (2 or 4)")

@@ -1456,6 +1456,8 @@ def upsample_poly23(x, ratio=4, out=None, phase=1):
 # ---- MTF-matched filtering and decimation (csrc/mtf.hip; definitions: tmdiff_amd/metrics.py) -------------------------
 _FIR_LIMITS = "taps float32 [T, K, K] on the GPU, K odd and at most 41, T a divisor of B * C; ratio 1, 2 or 4; 0 <= offset < ratio"
 _MTF_TAPS = {}          # (gains, ratio, device) -> the uploaded [bands, 41, 41] table
+_MTF_STEP_TAPS = {}     # (gains, ratio, device, scales) -> a scaled copy; the last _MTF_STEP_TAPS_MAX of them, oldest dropped first
+_MTF_STEP_TAPS_MAX = 8
 
 
 def fir_decimate_shape(h, w, ratio=1, offset=None):
@@ -1469,16 +1471,17 @@ def fir_decimate(x, taps, ratio=1, offset=None, out=None):
     taps[p % T] ([T, K, K], or [K, K] for one table), the border replicated, and sampled at ``offset`` + ratio * i -> [B, C,
     ceil((H - oy) / ratio), ceil((W - ox) / ratio)].  ``offset`` None is ratio // 2 on both axes, where ``upsample_poly23`` puts
     the samples; a number serves both axes.  Only the kept samples are computed.  With ``out=`` nothing is allocated or
-    synchronised (graph capture)."""
+    synchronised (graph capture).  Differentiable in x: with grad mode on and ``x.requires_grad`` the result carries a backward
+    that is the adjoint kernel (``fir_decimate_adjoint``); the taps get no gradient and ``out=`` is refused.  Otherwise the call
+    is the plain one."""
     from .metrics import fir_decimate_shape as shape_of
-    if ratio not in (1, 2, 4):
-        raise ValueError(f"fir_decimate: ratio={ratio} ({_FIR_LIMITS})")
-    if not (torch.is_tensor(taps) and taps.is_cuda and taps.dtype == torch.float32 and taps.dim() in (2, 3) and taps.is_contiguous()):
-        raise ValueError(f"fir_decimate: bad taps ({_FIR_LIMITS})")
-    t, k = (1 if taps.dim() == 2 else taps.shape[0]), taps.shape[-1]
-    if taps.shape[-2] != k or k % 2 == 0 or k > 41 or t < 1:
-        raise ValueError(f"fir_decimate: taps {tuple(taps.shape)} ({_FIR_LIMITS})")
-    oy, ox = shape_of(1, 1, ratio, offset)[1]
+    if torch.is_tensor(x) and x.requires_grad and torch.is_grad_enabled():
+        # differentiable in x: the backward is the adjoint kernel (autograd.FirDecimateFn); no gradient flows to the taps
+        if out is not None:
+            raise ValueError("fir_decimate: out= cannot be given for an input that requires grad (the result joins the autograd graph)")
+        from .autograd import FirDecimateFn
+        return FirDecimateFn.apply(x, taps, ratio, offset)
+    t, k, (oy, ox) = _fir_taps("fir_decimate", taps, ratio, offset)
     px, y, py = _resample_args("fir_decimate", x, lambda h, w: shape_of(h, w, ratio, offset)[0], out, _FIR_LIMITS)
     b, c, h, w = x.shape
     if (b * c) % t or taps.device != x.device:
@@ -1487,12 +1490,65 @@ def fir_decimate(x, taps, ratio=1, offset=None, out=None):
     return y
 
 
+def _fir_taps(name, taps, ratio, offset):
+    """(T, K, (oy, ox)) of a FIR call after the checks that do not need the image."""
+    from .metrics import fir_decimate_shape as shape_of
+    if ratio not in (1, 2, 4):
+        raise ValueError(f"{name}: ratio={ratio} ({_FIR_LIMITS})")
+    if not (torch.is_tensor(taps) and taps.is_cuda and taps.dtype == torch.float32 and taps.dim() in (2, 3) and taps.is_contiguous()):
+        raise ValueError(f"{name}: bad taps ({_FIR_LIMITS})")
+    t, k = (1 if taps.dim() == 2 else taps.shape[0]), taps.shape[-1]
+    if taps.shape[-2] != k or k % 2 == 0 or k > 41 or t < 1:
+        raise ValueError(f"{name}: taps {tuple(taps.shape)} ({_FIR_LIMITS})")
+    return t, k, shape_of(1, 1, ratio, offset)[1]
+
+
+def fir_decimate_adjoint(g, taps, shape, ratio=1, offset=None, out=None, base=None, alpha=1.0, beta=0.0):
+    """``beta * base + alpha * A^T g`` for A = ``fir_decimate(., taps, ratio, offset)`` on [B, C, H, W] images with ``shape`` =
+    (H, W) (definition: ``metrics.fir_decimate_adjoint``): g [B, C, H', W'] with (H', W') = ``fir_decimate_shape(H, W, ratio,
+    offset)`` -> [B, C, H, W], the exact transpose, the replicated border included.  ``base`` [B, C, H, W] is needed when
+    ``beta != 0``, is not read when ``beta == 0``, and may be ``out`` itself; ``out`` must not overlap ``g`` or ``taps`` (other
+    tiles still read them).  One kernel, a gather without atomics: the same bits on every run.  With ``out=`` nothing is
+    allocated or synchronised (graph capture)."""
+    from .metrics import fir_decimate_shape as shape_of
+    name = "fir_decimate_adjoint"
+    t, k, (oy, ox) = _fir_taps(name, taps, ratio, offset)
+    h, w = (int(n) for n in shape)
+    if h < 1 or w < 1:
+        raise ValueError(f"{name}: shape {(h, w)} (extents >= 1)")
+    if not (torch.is_tensor(g) and g.is_cuda and g.dtype == torch.float32 and g.dim() == 4 and g.is_contiguous()):
+        raise ValueError(f"{name}: need a contiguous float32 [B, C, H', W'] tensor on the GPU ({_FIR_LIMITS})")
+    b, c = g.shape[:2]
+    if tuple(g.shape[2:]) != shape_of(h, w, ratio, offset)[0]:
+        raise ValueError(f"{name}: g {tuple(g.shape)} is not [B, C, {shape_of(h, w, ratio, offset)[0]}], the extent of fir_decimate "
+                         f"on {h} x {w} at ratio {ratio}, offset ({oy}, {ox})")
+    if b * c * h * w > 2 ** 31 - 1:
+        raise ValueError(f"{name}: shape {(b, c, h, w)} is not supported ({_FIR_LIMITS}; fewer than 2^31 elements)")
+    if (b * c) % t or taps.device != g.device:
+        raise ValueError(f"{name}: taps {tuple(taps.shape)} on {taps.device} for {b * c} planes on {g.device} ({_FIR_LIMITS})")
+    full = (b, c, h, w)
+    y = out if out is not None else torch.empty(full, device=g.device, dtype=torch.float32)
+    if tuple(y.shape) != full:
+        raise ValueError(f"{name}: out must be {full}, got {tuple(y.shape)}")
+    for other, what in ((g, "g"), (taps, "taps")):
+        lo, hi = other.data_ptr(), other.data_ptr() + 4 * other.numel()
+        if y.data_ptr() < hi and lo < y.data_ptr() + 4 * y.numel():
+            raise ValueError(f"{name}: out overlaps {what}")
+    alpha, beta = float(alpha), float(beta)
+    if beta != 0.0 and (base is None or tuple(base.shape) != full):
+        raise ValueError(f"{name}: beta={beta} needs base of shape {full}")
+    pb = _chk(base, "base") if beta != 0.0 else None
+    check(lib.tmdiff_fir_decimate_adjoint(g.data_ptr(), taps.data_ptr(), pb, _chk(y, "out"), alpha, beta, b * c, t, h, w, k, ratio,
+                                          oy, ox, stream_ptr()), name)
+    return y
+
+
 def mtf_degrade(x, gains_or_sensor, ratio=4, pan=False, out=None):
     """Wald's degradation of x [B, C, H, W] (definition: ``metrics.mtf_degrade``): band c low-passed with the 41 x 41 MTF-matched
     filter of its Nyquist gain and decimated by ``ratio`` at the offset ratio // 2 -> [B, C, ceil((H - o) / ratio), ...].
     ``gains_or_sensor``: a sensor name (``metrics.mtf_gains``; with ``pan`` its PAN gain, for a one-band image), one gain per
     band, or a number for every band.  The tap table is made on the host once per (gains, ratio, device) and kept on the
-    device: call once before capturing into a graph."""
+    device: call once before capturing into a graph.  Differentiable in x as ``fir_decimate`` is."""
     from . import metrics
     if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
         raise ValueError(f"mtf_degrade: need a float32 [B, C, H, W] tensor on the GPU ({_FIR_LIMITS})")
@@ -1502,14 +1558,32 @@ def mtf_degrade(x, gains_or_sensor, ratio=4, pan=False, out=None):
     return fir_decimate(x, _mtf_taps(gains, ratio, x.device), ratio, None, out)
 
 
-def _mtf_taps(gains, ratio, device):
-    """The [bands, 41, 41] float32 table of ``metrics.mtf_kernel`` on the device, made once per (gains, ratio, device)."""
+def mtf_degrade_adjoint(g, gains_or_sensor, shape, ratio=4, pan=False, out=None, base=None, alpha=1.0, beta=0.0):
+    """``beta * base + alpha * A^T g`` for A = ``mtf_degrade(., gains_or_sensor, ratio, pan)`` on [B, C, H, W] images with
+    ``shape`` = (H, W) (definition: ``metrics.mtf_degrade_adjoint``): g [B, C, H', W'] -> [B, C, H, W] through
+    ``fir_decimate_adjoint`` with the cached tap table of ``mtf_degrade``: call once before capturing into a graph."""
     from . import metrics
-    key = (tuple(gains), ratio, device)
-    taps = _MTF_TAPS.get(key)
+    if not (torch.is_tensor(g) and g.is_cuda and g.dim() == 4):
+        raise ValueError(f"mtf_degrade_adjoint: need a float32 [B, C, H', W'] tensor on the GPU ({_FIR_LIMITS})")
+    if ratio not in (1, 2, 4):
+        raise ValueError(f"mtf_degrade_adjoint: ratio={ratio} ({_FIR_LIMITS})")
+    gains = metrics.band_gains(gains_or_sensor, g.shape[1], pan)
+    return fir_decimate_adjoint(g, _mtf_taps(gains, ratio, g.device), shape, ratio, None, out, base, alpha, beta)
+
+
+def _mtf_taps(gains, ratio, device, scales=None):
+    """The [bands, 41, 41] float32 table of ``metrics.mtf_kernel`` on the device, made once per (gains, ratio, device).
+    ``scales``: a factor per band, applied in float64 before the rounding (the per-band step of ``tiling.consistency_refine``);
+    such tables live in a cache of their own that keeps the last few, so sweeping ``relax`` does not pile up device memory."""
+    from . import metrics
+    cache = _MTF_TAPS if scales is None else _MTF_STEP_TAPS
+    key = (tuple(gains), ratio, device) if scales is None else (tuple(gains), ratio, device, tuple(scales))
+    taps = cache.get(key)
     if taps is None:
-        host = np.stack([metrics.mtf_kernel(g, ratio) for g in gains]).astype(np.float32)
-        taps = _MTF_TAPS[key] = torch.from_numpy(host).to(device)
+        host = np.stack([metrics.mtf_kernel(g, ratio) * (1.0 if scales is None else scales[i]) for i, g in enumerate(gains)])
+        taps = cache[key] = torch.from_numpy(host.astype(np.float32)).to(device)
+        while scales is not None and len(cache) > _MTF_STEP_TAPS_MAX:
+            del cache[next(iter(cache))]          # dicts keep insertion order: the oldest
     return taps
 
 
@@ -1572,7 +1646,8 @@ def pan_lowpass(pan, sensor_or_gain, ratio=4, out=None, low=None):
         raise ValueError("pan_lowpass: need a float32 [B, 1, H, W] tensor on the GPU")
     if ratio not in (2, 4) or pan.shape[2] % ratio or pan.shape[3] % ratio or min(pan.shape[2:]) < ratio:
         raise ValueError(f"pan_lowpass: shape {tuple(pan.shape)} ratio={ratio} (ratio 2 or 4, H and W multiples of it)")
-    return upsample_poly23(mtf_degrade(pan, sensor_or_gain, ratio, pan=True, out=low), ratio, out=out)
+    # a metric's stage, not a differentiable degradation: pan.requires_grad changes nothing here
+    return upsample_poly23(mtf_degrade(pan.detach(), sensor_or_gain, ratio, pan=True, out=low), ratio, out=out)
 
 
 def metrics_hqnr_buffers(b, c, h, w, device, ratio=4, block=32):
@@ -1611,7 +1686,8 @@ def metrics_hqnr(ps, ms_exp, pan, sensor, ratio=4, block=32, alpha=1.0, beta=1.0
         raise ValueError(f"metrics_hqnr: buffers made for {buf['shape']}, the call is {(b, c, h, w, ratio, block)}")
     ms_gains, pan_gain = metrics.mtf_gains(sensor, c)
     y = _f64("metrics_hqnr", "out", out, (b, 3), ps.device, contiguous=False)
-    filtered = fir_decimate(ps, _mtf_taps(ms_gains, ratio, ps.device), 1, None, buf["filtered"])
+    # the metric is not differentiable: ps.requires_grad changes nothing here
+    filtered = fir_decimate(ps.detach(), _mtf_taps(ms_gains, ratio, ps.device), 1, None, buf["filtered"])
     metrics_q2n(ms_exp, filtered, block, block, out=buf["q2n"], workspace=buf["q2n_ws"])
     torch.neg(buf["q2n"], out=buf["d_lambda"]).add_(1.0)                       # 1 - Q2n, as the host rounds it
     if pan_lp is None:

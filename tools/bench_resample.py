@@ -17,7 +17,11 @@ the cases interleaved; the median round is reported with the least and the great
 with PAN [1, 1, 4096, 4096] and at MS [32, 8, 256, 256] with PAN [32, 1, 1024, 1024]: the operator (`ops.mtf_degrade`) on the MS
 and on the PAN, `data.wald_pair` (both degradations, the 23-tap upsampling and the residual), and the torch composition of the
 operator -- replicate `F.pad`, the slice that starts at the offset, grouped `F.conv2d` with the ratio as its stride.  Every case
-is captured into a graph of `--graph-calls` calls; a round is the time of one replay over that count."""
+is captured into a graph of `--graph-calls` calls; a round is the time of one replay over that count.
+
+`--leg adjoint`: the adjoint (`ops.mtf_degrade_adjoint`) at the same four shapes against torch autograd's backward of that
+composition, the forward kernel's own time beside it, and `tiling.consistency_refine` (8 steps) at [1, 8, 1024, 1024]; timed the
+same way."""
 import argparse
 import os
 import statistics
@@ -93,12 +97,75 @@ def mtf_leg(args):
         print(f"{name:52s} {m:10.2f} ({min(t):8.2f}..{max(t):8.2f}) {macs / m / 1e3:9.1f}", flush=True)
 
 
+def adjoint_leg(args):
+    """`--leg adjoint`: ops.mtf_degrade_adjoint at the four shapes of `--leg mtf` against the backward of the torch composition
+    (autograd through replicate F.pad, the slice and the grouped strided F.conv2d), with the forward kernel's own time at the
+    same shape beside it (the two have the same multiply-adds), the same at a batch of 64 x 64 training patches, where every tile
+    is a four-corner tile, and tiling.consistency_refine at [1, 8, 1024, 1024], 8 steps.
+    Every case of the project's is a graph of `--graph-calls` calls; torch's backward runs eagerly (see below)."""
+    import torch.nn.functional as F
+    from tmdiff_amd import metrics
+    from tmdiff_amd.tiling import consistency_refine
+    sensor, ratio, k = "WV3", 4, metrics.MTF_TAPS
+    ms_gains, pan_gain = metrics.mtf_gains(sensor, 8)
+    cases = []          # (name, call, multiply-adds)
+    shapes = [(name, shape, gains, is_pan) for b, h in ((1, 1024), (32, 256))
+              for name, shape, gains, is_pan in (("MS ", (b, 8, h, h), ms_gains, False), ("PAN", (b, 1, ratio * h, ratio * h), (pan_gain,), True))]
+    # a batch of training patches, as data.wald_pair and autograd see them: every 64 x 64 tile has all four corners
+    shapes.append(("MS ", (32, 8, 64, 64), ms_gains, False))
+    for name, shape, gains, is_pan in shapes:
+        x = torch.rand(*shape, device="cuda")
+        y = ops.mtf_degrade(x, sensor, ratio, pan=is_pan)
+        g = torch.randn_like(y)
+        dx = ops.mtf_degrade_adjoint(g, sensor, shape[2:], ratio, pan=is_pan)
+        w = torch.from_numpy(np.stack([metrics.mtf_kernel(gn, ratio) for gn in gains])).float().cuda()[:, None]
+        xr = x.clone().requires_grad_()
+        yr = F.conv2d(F.pad(xr, (k // 2,) * 4, mode="replicate")[..., ratio // 2:, ratio // 2:], w, stride=ratio, groups=len(gains))
+
+        def backward(xr=xr, yr=yr, g=g):
+            xr.grad = None
+            yr.backward(g, retain_graph=True)
+
+        backward()
+        err = float((xr.grad - dx).abs().max())
+        print(f"{name} {list(shape)}: max |adjoint - torch backward| = {err:.3e}", flush=True)
+        macs = y.numel() * k * k
+        cases.append((f"mtf_degrade_adjoint      {name} {list(shape)}",
+                      lambda g=g, dx=dx, s=shape, p=is_pan: ops.mtf_degrade_adjoint(g, sensor, s[2:], ratio, pan=p, out=dx), macs))
+        cases.append((f"mtf_degrade (forward)    {name} {list(shape)}", lambda x=x, y=y, p=is_pan: ops.mtf_degrade(x, sensor, ratio, pan=p, out=y), macs))
+        cases.append((f"backward of pad+slice+conv2d {name} {list(shape)}", backward, macs))
+    fused = torch.rand(1, 8, 1024, 1024, device="cuda")
+    lr = ops.mtf_degrade(torch.rand(1, 8, 1024, 1024, device="cuda"), sensor, ratio)
+    out = torch.empty_like(fused)
+    consistency_refine(fused, lr, sensor, ratio, iters=1, out=out)          # the tap tables and the operator norms, once
+    cases.append(("consistency_refine 8 steps [1, 8, 1024, 1024]", lambda: consistency_refine(fused, lr, sensor, ratio, iters=8, out=out),
+                  8 * 2 * lr.numel() * k * k))
+    # The project's calls are captured; torch's backward is not: the autograd engine issues its kernels on the stream of the
+    # forward pass, not on the capturing one, so it is timed eagerly, `--graph-calls` calls back to back between two events.
+    runs = [(lambda fn=fn: [fn() for _ in range(args.graph_calls)]) if name.startswith("backward of") else captured(fn, args.graph_calls).replay
+            for name, fn, _ in cases]
+    times = [[] for _ in cases]
+    for _ in range(args.rounds):
+        for run, t in zip(runs, times):
+            time_us(run, 1)
+            t.append(time_us(run, 1) / args.graph_calls)
+    print(f"{'case':56s} {'us per call (min..max)':>30s} {'GMAC/s':>9s}")
+    med = {}
+    for (name, _, macs), t in zip(cases, times):
+        m = med[name] = statistics.median(t)
+        print(f"{name:56s} {m:10.2f} ({min(t):8.2f}..{max(t):8.2f}) {macs / m / 1e3:9.1f}", flush=True)
+    names = [n for n, _, _ in cases]
+    for i in range(0, len(names) - 1, 3):
+        a, f, t = (med[n] for n in names[i:i + 3])
+        print(f"{names[i][24:]:28s} adjoint / forward kernel {a / f:5.2f}   torch backward / adjoint {t / a:6.1f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("resample", "mtf"), default="resample")
+    ap.add_argument("--leg", choices=("resample", "mtf", "adjoint"), default="resample")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--graph-calls", type=int, default=10, help="--leg mtf: calls captured into each graph")
+    ap.add_argument("--graph-calls", type=int, default=10, help="--leg mtf / adjoint: calls captured into each graph")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_resample.py needs the GPU: a rate cannot be measured without one")
@@ -107,6 +174,8 @@ def main():
           f"torch {torch.__version__}, HIP {torch.version.hip}; reps {args.reps}, rounds {args.rounds}", flush=True)
     if args.leg == "mtf":
         return mtf_leg(args)
+    if args.leg == "adjoint":
+        return adjoint_leg(args)
 
     cases = []          # (name, kernel call, bytes, copy call, bytes the copy moves)
 
