@@ -812,6 +812,34 @@ int tmdiff_fir_decimate_adjoint(const float* g, const float* taps, const float* 
                                 int32_t off_x, tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * MTF-GLP pansharpening (host definitions: tmdiff_amd/metrics.py, pan_lowpass_bands / glp_moments / mtf_glp).  Dense fp32
+ * tensors; nothing is allocated or synchronised, no atomics, the same bits on every run and on a graph replay.
+ *  fir_decimate_bank (csrc/mtf.hip): a filter bank on ONE plane per image, y[b, t] = fir_decimate(x[b], taps[t]); x [images, H, W],
+ *             taps [tables, K, K], y [images, tables, H', W'].  The kernel of fir_decimate: a workgroup stages the clamped patch
+ *             once and walks the tables over it; a pixel has fir_decimate's summation order, so y equals fir_decimate on the
+ *             tables-fold copy of x bit for bit.  Limits: images >= 0, tables >= 1, then fir_decimate's on images * tables
+ *             planes, in its order.  images == 0 or an output without samples returns TMDIFF_OK.
+ *  glp_moments (csrc/metrics.hip): ms_exp, pan_lp [B, C, H, W], pan [B, H, W] -> out, float64 [B, C, 7]: the population
+ *             moments mean(M_c), mean(L_c), mean(P), var(M_c), var(L_c), cov(M_c, L_c), var(P).  One pass; every value has its
+ *             plane's first pixel subtracted in fp64 after the load (a pilot), sums and products are fp64; partial sums per
+ *             workgroup in `workspace` (8-byte aligned, tmdiff_glp_moments_workspace_bytes), a finalize launch adds them in
+ *             index order.  The workspace then starts with the finished sums, float64 [B, C, 7]: S_dm, S_dl, S_dp, S_dm.dm,
+ *             S_dl.dl, S_dm.dl, S_dp.dp with d = value - pilot.  Limits: B >= 0, 1 <= C <= 16, H, W >= 1, B * C * H * W <=
+ *             2^31 - 1; otherwise TMDIFF_E_UNSUPPORTED and a workspace size of 0.
+ *  glp_inject (csrc/fusion.hip): out [B, C, H, W] from ms_exp, pan, pan_lp and the device-resident `moments` of glp_moments;
+ *             mode 0 "glp", 1 "cbd", 2 "hpm".  The band's gains are formed on the device, the formula is evaluated in fp64 and
+ *             rounded to fp32 once.  out may be ms_exp; it must not overlap pan, pan_lp or moments.  Limits: glp_moments'.
+ *             (Added within version 6.)
+ * ------------------------------------------------------------------------------------ */
+int tmdiff_fir_decimate_bank(const float* x, const float* taps, float* y, int32_t images, int32_t tables, int32_t H, int32_t W,
+                             int32_t K, int32_t ratio, int32_t off_y, int32_t off_x, tmdiff_stream_t stream);
+size_t tmdiff_glp_moments_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int tmdiff_glp_moments(const float* ms_exp, const float* pan, const float* pan_lp, int32_t B, int32_t C, int32_t H, int32_t W,
+                       double* out, void* workspace, size_t workspace_bytes, tmdiff_stream_t stream);
+int tmdiff_glp_inject(const float* ms_exp, const float* pan, const float* pan_lp, const double* moments, float* out, int32_t B,
+                      int32_t C, int32_t H, int32_t W, int32_t mode, tmdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Standalone attention operators of core/Attention.py (imported by nothing in the reference; built because the
  * north star names them).  All fp32.
  *  attn_fwd : out = softmax(q k^T * scale [key mask]) v per (batch, head); fp32 MFMA, online softmax.

@@ -226,6 +226,12 @@ SIGNATURES.update({
     "tmdiff_fir_decimate": (C.c_int, [vp, vp, vp] + [C.c_int32] * 8 + [vp]),
     # its adjoint: g, taps, base, dx | alpha, beta | planes, taps_period, H, W, K, ratio, off_y, off_x
     "tmdiff_fir_decimate_adjoint": (C.c_int, [vp, vp, vp, vp, C.c_float, C.c_float] + [C.c_int32] * 8 + [vp]),
+    # MTF-GLP: the filter bank: x, taps, y | images, tables, H, W, K, ratio, off_y, off_x
+    "tmdiff_fir_decimate_bank": (C.c_int, [vp, vp, vp] + [C.c_int32] * 8 + [vp]),
+    # ms_exp, pan, pan_lp | B, C, H, W | out, workspace, bytes;  ms_exp, pan, pan_lp, moments, out | B, C, H, W, mode
+    "tmdiff_glp_moments_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "tmdiff_glp_moments": (C.c_int, [vp, vp, vp] + [C.c_int32] * 4 + [vp, vp, C.c_size_t, vp]),
+    "tmdiff_glp_inject": (C.c_int, [vp] * 5 + [C.c_int32] * 5 + [vp]),
 })
 
 

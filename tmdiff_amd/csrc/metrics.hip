@@ -862,3 +862,153 @@ int tmdiff_metrics_dsblock(const float* ps, int64_t ps_stride_b, int64_t ps_stri
 }
 
 }  // extern "C"
+
+// ---- The injection statistics of MTF-GLP (metrics.glp_moments): per band the population means, variances and the covariance of
+// M = ms_exp and L = pan_lp, and the mean and variance of P = pan, as device values for glp_inject_kernel (fusion.hip).
+//
+//  glp_moments_kernel    one workgroup per chunk of 4096 consecutive pixels of one image; lane t owns the four pixels from
+//                        chunk + 4 (256 k + t) on, k = 0 .. 3, and adds them in that order (k, then the pixel) whether they
+//                        arrive as one 16-byte load or as four scalar ones.  It reads P once, forms its two sums, then walks the
+//                        bands with five sums each.  Seven partial sums per band and chunk go to the workspace.
+//  glp_moments_finalize_kernel  one workgroup per (band, image): lane t adds chunks t, t + 256, ... (strided_sum), the
+//                        workgroup adds the lanes (wg_sum), lane 0 forms the moments.
+//
+// CONDITIONING: the second moments are taken about a PILOT, not about zero and not about the mean: every value has the first
+// pixel of its own plane subtracted in fp64 right after the load (exact for fp32 data of one binade range), d = v - v[0], and
+// the sums are of d and of products of two d's.  mean = v[0] + S_d / n, var = S_dd / n - (S_d / n)^2: the subtraction that
+// remains cancels at most (range / sigma)^2 of fp64's 2^53, where raw squares would cancel (mean / sigma)^2.  One pass over
+// the images, no second pass for the means.  A constant plane has d == 0 everywhere and a variance of exactly 0.
+// The finished sums are kept as well, ahead of the partial sums in the workspace: [B, C, 7] doubles in the order
+// S_dm, S_dl, S_dp, S_dm.dm, S_dl.dl, S_dm.dl, S_dp.dp.  Summation order: stats.h, and nothing else; no atomics.
+namespace {
+
+constexpr int GLP_QUADS = 4, GLP_PIX = 256 * 4 * GLP_QUADS;   // pixels of a workgroup's chunk
+constexpr int GLP_K = 7;
+
+inline bool glp_ok(int B, int C, int H, int W) {
+  return B >= 0 && C >= 1 && C <= MAXC && H >= 1 && W >= 1 && tmdiff::fits_int32((double)std::max(B, 1) * C * H * W);
+}
+inline int glp_chunks(long n) { return (int)((n + GLP_PIX - 1) / GLP_PIX); }
+inline size_t glp_bytes(int B, int C, int H, int W) {
+  return ((size_t)B * C * GLP_K + (size_t)B * glp_chunks((long)H * W) * (5 * C + 2)) * sizeof(double);
+}
+
+struct GlpArgs {
+  const float* m;   // ms_exp [B, C, n]
+  const float* l;   // pan_lp [B, C, n]
+  const float* p;   // pan    [B, n]
+  int B, C, n, chunks, vec;
+  double* sums;     // [B, C, 7]
+  double* part;     // [B, chunks, 5 C + 2]
+  double* out;      // [B, C, 7]
+};
+
+// The lane's four pixels from px on as differences from the pilot; a pixel past the plane's end is the pilot itself: d == 0.
+__device__ __forceinline__ void glp_load(const float* plane, long px, int n, bool vec, double pilot, double (&d)[4]) {
+  if (vec && px < n) {                                            // n % 4 == 0 here: the four lie inside together
+    const float4 v = *reinterpret_cast<const float4*>(plane + px);
+    d[0] = (double)v.x - pilot, d[1] = (double)v.y - pilot, d[2] = (double)v.z - pilot, d[3] = (double)v.w - pilot;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) d[e] = px + e < n ? (double)plane[px + e] - pilot : 0.0;
+  }
+}
+
+__global__ void __launch_bounds__(256) glp_moments_kernel(GlpArgs a) {
+  __shared__ double red[4 * 5];
+  const int chunk = blockIdx.x;
+  const long px0 = (long)chunk * GLP_PIX + 4 * threadIdx.x;
+  const int ld = 5 * a.C + 2;
+  for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
+    double* dst = a.part + ((long)b * a.chunks + chunk) * ld;
+    {
+      const float* pp = a.p + (long)b * a.n;
+      const double pilot = pp[0];
+      double v[2] = {0.0, 0.0};
+#pragma unroll
+      for (int k = 0; k < GLP_QUADS; ++k) {
+        double d[4];
+        glp_load(pp, px0 + k * 1024, a.n, a.vec, pilot, d);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[0] += d[e], v[1] += d[e] * d[e];
+      }
+      __syncthreads();                                            // the image before may still read red
+      tmdiff::wg_sum<4, 2, 2>(v, red);
+      if (threadIdx.x == 0) dst[5 * a.C] = v[0], dst[5 * a.C + 1] = v[1];
+    }
+    for (int c = 0; c < a.C; ++c) {
+      const float* mp = a.m + ((long)b * a.C + c) * a.n;
+      const float* lp = a.l + ((long)b * a.C + c) * a.n;
+      const double pm = mp[0], pl = lp[0];
+      double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int k = 0; k < GLP_QUADS; ++k) {
+        double dm[4], dl[4];
+        glp_load(mp, px0 + k * 1024, a.n, a.vec, pm, dm);
+        glp_load(lp, px0 + k * 1024, a.n, a.vec, pl, dl);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          v[0] += dm[e], v[1] += dl[e], v[2] += dm[e] * dm[e], v[3] += dl[e] * dl[e], v[4] += dm[e] * dl[e];
+      }
+      __syncthreads();                                            // the band before may still read red
+      tmdiff::wg_sum<4, 5, 5>(v, red);
+      if (threadIdx.x == 0)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) dst[5 * c + k] = v[k];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) glp_moments_finalize_kernel(GlpArgs a) {
+  __shared__ double red[4 * GLP_K];
+  const int c = blockIdx.x, ld = 5 * a.C + 2;
+  for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
+    const double* src = a.part + (long)b * a.chunks * ld;
+    double v[GLP_K];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) v[k] = tmdiff::strided_sum(src + 5 * c + k, a.chunks, ld, threadIdx.x, 256);
+    v[5] = tmdiff::strided_sum(src + 5 * a.C, a.chunks, ld, threadIdx.x, 256);
+    v[6] = tmdiff::strided_sum(src + 5 * a.C + 1, a.chunks, ld, threadIdx.x, 256);
+    __syncthreads();
+    tmdiff::wg_sum<4, GLP_K, GLP_K>(v, red);
+    if (threadIdx.x == 0) {
+      const long bc = (long)b * a.C + c;
+      const double n = (double)a.n, pm = a.m[bc * a.n], pl = a.l[bc * a.n], pp = a.p[(long)b * a.n];
+      const double em = v[0] / n, el = v[1] / n, ep = v[5] / n;
+      double* s = a.sums + bc * GLP_K;
+      s[0] = v[0], s[1] = v[1], s[2] = v[5], s[3] = v[2], s[4] = v[3], s[5] = v[4], s[6] = v[6];
+      double* o = a.out + bc * GLP_K;               // metrics.GLP_MOMENT_FIELDS
+      o[0] = pm + em, o[1] = pl + el, o[2] = pp + ep;
+      o[3] = v[2] / n - em * em, o[4] = v[3] / n - el * el, o[5] = v[4] / n - em * el, o[6] = v[6] / n - ep * ep;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t tmdiff_glp_moments_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
+  return glp_ok(B, C, H, W) ? glp_bytes(B, C, H, W) : 0;
+}
+
+int tmdiff_glp_moments(const float* ms_exp, const float* pan, const float* pan_lp, int32_t B, int32_t C, int32_t H, int32_t W,
+                       double* out, void* workspace, size_t workspace_bytes, tmdiff_stream_t stream) {
+  if (!glp_ok(B, C, H, W))
+    return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "glp_moments: B=%d C=%d H=%d W=%d (B >= 0, 1 <= C <= 16, H, W >= 1, fewer than 2^31 "
+                        "elements)", B, C, H, W);
+  if (B == 0) return TMDIFF_OK;
+  TMDIFF_REQUIRE(ms_exp && pan && pan_lp && out && workspace, "glp_moments: null tensor");
+  if (const int rc = tmdiff::check_workspace("glp_moments", workspace, workspace_bytes, glp_bytes(B, C, H, W))) return rc;
+  const hipStream_t st = tmdiff::as_stream(stream);
+  const int n = H * W, chunks = glp_chunks(n);
+  double* ws = static_cast<double*>(workspace);
+  const int vec = n % 4 == 0 && tmdiff::aligned16(ms_exp) && tmdiff::aligned16(pan) && tmdiff::aligned16(pan_lp);
+  const GlpArgs a{ms_exp, pan_lp, pan, B, C, n, chunks, vec, ws, ws + (size_t)B * C * GLP_K, out};
+  glp_moments_kernel<<<dim3((unsigned)chunks, (unsigned)std::min(B, 65535)), 256, 0, st>>>(a);
+  if (const int rc = tmdiff::check_launch("glp_moments")) return rc;
+  glp_moments_finalize_kernel<<<dim3((unsigned)C, (unsigned)std::min(B, 65535)), 256, 0, st>>>(a);
+  return tmdiff::check_launch("glp_moments (finalize)");
+}
+
+}  // extern "C"

@@ -29,6 +29,12 @@
 // straight into the multiply-add's scalar operand) and never enter the vector path.  One LDS read per multiply-add remains: the
 // kernel is bound by the LDS read rate (profiles/mtf_degrade.txt).
 //
+// THE FILTER BANK, tmdiff_fir_decimate_bank: y[b, t] = fir_decimate(x[b], taps[t]) for ONE plane per image and T tables (the PAN
+// seen through every MS band's filter, metrics.pan_lowpass_bands).  The same kernel body: the workgroup stages the clamped
+// patch of x[b] once and walks the T tables over it, so the input is read once instead of T times and no T-fold copy of it
+// exists.  Tile, patch layout, scalar tap loads and the summation order of an output pixel are the ones above: y[b, t] equals
+// tmdiff_fir_decimate on the expanded copy bit for bit.
+//
 // THE ADJOINT, tmdiff_fir_decimate_adjoint: dx = beta * base + alpha * A^T g for the operator A above (host definition:
 // metrics.fir_decimate_adjoint), the clamp included -- a border pixel collects every position that the replicated border
 // mapped onto it:
@@ -77,10 +83,18 @@ struct FirPatch {
   static_assert(PW * R >= PC && (R * RS) % 32 == 16, "patch layout");
 };
 
-// y[pl, oy0 + i, ox0 + j] of the 16 x 16 tile blockIdx.x; blockIdx.y walks the planes.  KC: K at compile time, 0 = kr.
-template <int R, int KC>
+// y[pl, oy0 + i, ox0 + j] of the 16 x 16 tile blockIdx.x; blockIdx.y walks the staged planes.  KC: K at compile time, 0 = kr.
+// One body serves the two entry points; what differs is which output planes a staged input plane q feeds and with which table:
+//   BANK = false (fir_decimate):       `groups` = planes; plane q makes y[q] with table q % period
+//   BANK = true  (fir_decimate_bank):  `groups` = images; plane q makes y[q * period + t] with table t, t = 0 .. period - 1,
+//                                      from ONE staging of the patch
+template <bool BANK> __device__ __forceinline__ int fir_tables(int period) { return BANK ? period : 1; }
+template <bool BANK> __device__ __forceinline__ int fir_table(int q, int t, int period) { return BANK ? t : q % period; }
+template <bool BANK> __device__ __forceinline__ int fir_out_plane(int q, int t, int period) { return BANK ? q * period + t : q; }
+
+template <int R, int KC, bool BANK>
 __global__ void __launch_bounds__(256) fir_decimate_kernel(const float* __restrict__ x, const float* __restrict__ taps,
-                                                           float* __restrict__ y, int planes, int period, int H, int W, int kr, int off_y,
+                                                           float* __restrict__ y, int groups, int period, int H, int W, int kr, int off_y,
                                                            int off_x) {
   using P = FirPatch<R>;
   __shared__ float s[P::PC * P::RS];
@@ -94,8 +108,8 @@ __global__ void __launch_bounds__(256) fir_decimate_kernel(const float* __restri
   const int gy0 = R * oy0 + off_y - rad, gx0 = R * ox0 + off_x - rad;  // its first row and column in the image
   const int i = threadIdx.x >> 4, j = threadIdx.x & 15;
   const bool live = i < oh && j < ow;
-  for (int pl = blockIdx.y; pl < planes; pl += gridDim.y) {
-    const float* xp = x + pl * H * W;
+  for (int q = blockIdx.y; q < groups; q += gridDim.y) {
+    const float* xp = x + q * H * W;
     for (int idx = threadIdx.x; idx < nr * P::PC; idx += 256) {
       const int r = idx / P::PC, c = idx - r * P::PC;
       if (c >= nc) continue;
@@ -104,27 +118,37 @@ __global__ void __launch_bounds__(256) fir_decimate_kernel(const float* __restri
     }
     __syncthreads();
     if (live) {
-      const float* tp = taps + (pl % period) * K * K;
       const float* sp = s + R * i * P::RS + j;
-      float acc = 0.f;
-      for (int u = 0; u < K; ++u) {
+      for (int t = 0; t < fir_tables<BANK>(period); ++t) {
+        const float* tp = taps + fir_table<BANK>(q, t, period) * K * K;
+        float acc = 0.f;
+        for (int u = 0; u < K; ++u) {
 #pragma unroll
-        for (int v = 0; v < K; ++v) acc = __fmaf_rn(tp[u * K + v], sp[u * P::RS + (v % R) * P::PW + v / R], acc);
+          for (int v = 0; v < K; ++v) acc = __fmaf_rn(tp[u * K + v], sp[u * P::RS + (v % R) * P::PW + v / R], acc);
+        }
+        y[(fir_out_plane<BANK>(q, t, period) * HO + oy0 + i) * WO + ox0 + j] = acc;
       }
-      y[(pl * HO + oy0 + i) * WO + ox0 + j] = acc;
     }
     __syncthreads();   // the next plane overwrites the patch
   }
 }
 
-template <int R>
-void launch_fir(const float* x, const float* taps, float* y, int planes, int period, int H, int W, int K, int off_y, int off_x,
+template <int R, bool BANK>
+void launch_fir(const float* x, const float* taps, float* y, int groups, int period, int H, int W, int K, int off_y, int off_x,
                 hipStream_t st) {
   constexpr int T = FirPatch<R>::T;
   const int HO = (H - off_y + R - 1) / R, WO = (W - off_x + R - 1) / R;
-  const dim3 grid((unsigned)(((HO + T - 1) / T) * ((WO + T - 1) / T)), (unsigned)std::min(planes, 65535));
-  if (K == 41) fir_decimate_kernel<R, 41><<<grid, 256, 0, st>>>(x, taps, y, planes, period, H, W, K, off_y, off_x);
-  else fir_decimate_kernel<R, 0><<<grid, 256, 0, st>>>(x, taps, y, planes, period, H, W, K, off_y, off_x);
+  const dim3 grid((unsigned)(((HO + T - 1) / T) * ((WO + T - 1) / T)), (unsigned)std::min(groups, 65535));
+  if (K == 41) fir_decimate_kernel<R, 41, BANK><<<grid, 256, 0, st>>>(x, taps, y, groups, period, H, W, K, off_y, off_x);
+  else fir_decimate_kernel<R, 0, BANK><<<grid, 256, 0, st>>>(x, taps, y, groups, period, H, W, K, off_y, off_x);
+}
+
+template <bool BANK>
+void launch_fir_ratio(const float* x, const float* taps, float* y, int groups, int period, int H, int W, int K, int ratio, int off_y,
+                      int off_x, hipStream_t st) {
+  if (ratio == 4) launch_fir<4, BANK>(x, taps, y, groups, period, H, W, K, off_y, off_x, st);
+  else if (ratio == 2) launch_fir<2, BANK>(x, taps, y, groups, period, H, W, K, off_y, off_x, st);
+  else launch_fir<1, BANK>(x, taps, y, groups, period, H, W, K, off_y, off_x, st);
 }
 
 template <int R>
@@ -323,11 +347,21 @@ int tmdiff_fir_decimate(const float* x, const float* taps, float* y, int32_t pla
   if (const int rc = fir_limits("fir_decimate", K, ratio, off_y, off_x, H, W, planes, taps_period)) return rc;
   if (planes == 0 || H <= off_y || W <= off_x) return TMDIFF_OK;   // no plane, or no sample at o + ratio * i inside the image
   TMDIFF_REQUIRE(x && taps && y, "fir_decimate: null tensor");
-  const hipStream_t st = tmdiff::as_stream(stream);
-  if (ratio == 4) launch_fir<4>(x, taps, y, planes, taps_period, H, W, K, off_y, off_x, st);
-  else if (ratio == 2) launch_fir<2>(x, taps, y, planes, taps_period, H, W, K, off_y, off_x, st);
-  else launch_fir<1>(x, taps, y, planes, taps_period, H, W, K, off_y, off_x, st);
+  launch_fir_ratio<false>(x, taps, y, planes, taps_period, H, W, K, ratio, off_y, off_x, tmdiff::as_stream(stream));
   return tmdiff::check_launch("fir_decimate");
+}
+
+int tmdiff_fir_decimate_bank(const float* x, const float* taps, float* y, int32_t images, int32_t tables, int32_t H, int32_t W,
+                             int32_t K, int32_t ratio, int32_t off_y, int32_t off_x, tmdiff_stream_t stream) {
+  if (images < 0 || tables < 1 || (double)images * tables > 2147483647.0)
+    return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "fir_decimate_bank: images=%d tables=%d (images >= 0, tables >= 1, and the limits of "
+                        "fir_decimate on images * tables planes)", images, tables);
+  // the output [images, tables] has the most planes: its element count bounds the input's
+  if (const int rc = fir_limits("fir_decimate_bank", K, ratio, off_y, off_x, H, W, images * tables, tables)) return rc;
+  if (images == 0 || H <= off_y || W <= off_x) return TMDIFF_OK;
+  TMDIFF_REQUIRE(x && taps && y, "fir_decimate_bank: null tensor");
+  launch_fir_ratio<true>(x, taps, y, images, tables, H, W, K, ratio, off_y, off_x, tmdiff::as_stream(stream));
+  return tmdiff::check_launch("fir_decimate_bank");
 }
 
 int tmdiff_fir_decimate_adjoint(const float* g, const float* taps, const float* base, float* dx, float alpha, float beta, int32_t planes,

@@ -12,6 +12,7 @@ import torch
 from . import metrics
 
 IMG_SCALE = {"GF2": 1023.0}          # every other sensor: 2047 (ref :134)
+BASELINES = ("exp", "glp", "cbd", "hpm")   # val_dataset(baselines=...): the interpolated MS and the three modes of metrics.mtf_glp
 
 
 def to_hwc01(img, min_max=(0.0, 1.0)):
@@ -31,7 +32,7 @@ def _to_nchw01(img, min_max=(0.0, 1.0)):
 
 
 def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=print, device_metrics=False,
-                full_resolution=False, q2n=False, protocol="qnr", sensor=None):
+                full_resolution=False, q2n=False, protocol="qnr", sensor=None, baselines=()):
     """``trainer`` is a ``tmdiff_amd.model.DDPM`` (or the reference's); ``dataset`` is the prompt name.
     Returns ``{"ssim_<dataset>": ..., "sam_<dataset>": ..., "sec_per_item": ...}``.
 
@@ -56,15 +57,28 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
     ``{"d_lambda_k_<dataset>": ..., "d_s_<dataset>": ..., "hqnr_<dataset>": ..., "sec_per_item": ...}``; ValueError when the
     visuals carry no ``MS`` or ``PAN``.  ``sensor`` names the row of ``metrics.MTF_GAINS`` (or is a pair of explicit gains); it
     defaults to ``dataset`` when that has a row of its own -- a sensor name as it stands, never a prompt name translated -- and
-    is required otherwise.  ``protocol="qnr"`` is the behaviour and the keys described above."""
+    is required otherwise.  ``protocol="qnr"`` is the behaviour and the keys described above.
+
+    ``baselines``: names out of ``BASELINES`` -- "exp", the interpolated ``MS`` itself, and "glp", "cbd", "hpm", the visuals'
+    ``MS`` and ``PAN`` fused classically by ``ops.mtf_glp`` in that mode (``metrics.mtf_glp``; buffers made once per shape).
+    Each is scored with the same metric set as the network in the mode that is active (``device_metrics=True``, or
+    ``full_resolution=True`` with either protocol; the host-metric mode raises ValueError) under the keys
+    ``"<metric>_<dataset>@<baseline>"``; the sums stay on the device and join the single synchronising read.  ``sensor`` is
+    resolved as for ``protocol="hqnr"``.  ``baselines=()`` changes nothing: the same keys, values and launches."""
+    baselines = tuple(baselines)
+    if [b for b in baselines if b not in BASELINES] or len(set(baselines)) != len(baselines):
+        raise ValueError(f"val_dataset: baselines={baselines!r} (distinct names out of {BASELINES})")
+    if baselines and not (device_metrics or full_resolution):
+        raise ValueError("val_dataset(baselines=...) scores on the GPU: it needs device_metrics=True or full_resolution=True")
     if protocol not in ("qnr", "hqnr"):
         raise ValueError(f"val_dataset: protocol={protocol!r} ('qnr' or 'hqnr')")
     hqnr = protocol == "hqnr"
     if hqnr and not full_resolution:
         raise ValueError("val_dataset(protocol='hqnr') scores without ground truth: it needs full_resolution=True")
-    if hqnr and sensor is None:
+    if (hqnr or baselines) and sensor is None:
         if dataset not in metrics.MTF_GAINS:
-            raise ValueError(f"val_dataset(protocol='hqnr'): {dataset!r} has no row in metrics.MTF_GAINS: give the sensor")
+            raise ValueError(f"val_dataset({'protocol=' + repr('hqnr') if hqnr else 'baselines=...'}): {dataset!r} has no row in "
+                             f"metrics.MTF_GAINS: give the sensor")
         sensor = dataset
     if q2n and (full_resolution or not device_metrics):
         raise ValueError("val_dataset(q2n=True) scores on the GPU against ground truth: it needs device_metrics=True and "
@@ -76,6 +90,20 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
     n = 0
     dev_sum, dev_ws, q2n_ws = None, {}, {}
     full_sum, full_ws = None, {}
+    base_sum, glp_ws = {}, {}
+
+    def score_baselines(ms_d, pan_d, score_row):
+        """Adds score_row(fused) of every baseline to its running sum; ms_d, pan_d: the item's MS and PAN in [0, 1]."""
+        from . import ops
+        for name in baselines:
+            fused = ms_d
+            if name != "exp":
+                if ms_d.shape not in glp_ws:
+                    glp_ws[ms_d.shape] = (ops.mtf_glp_buffers(*ms_d.shape, ms_d.device), torch.empty_like(ms_d))
+                buf, out = glp_ws[ms_d.shape]
+                fused = ops.mtf_glp(ms_d, pan_d, sensor, 4, name, out=out, buffers=buf)
+            row = score_row(fused)
+            base_sum[name] = row if name not in base_sum else base_sum[name] + row
     t0 = time.time()
     for idx, val_data in enumerate(val_loader):
         trainer.feed_data(val_data)
@@ -84,6 +112,8 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
         if full_resolution and not (("MS" if hqnr else "LR") in vis and "PAN" in vis):
             raise ValueError(f"val_dataset(full_resolution=True): the visuals need '{'MS' if hqnr else 'LR'}' and 'PAN', "
                              f"got {sorted(vis)}")
+        if baselines and not ("MS" in vis and "PAN" in vis):
+            raise ValueError(f"val_dataset(baselines=...): the visuals need 'MS' and 'PAN', got {sorted(vis)}")
         sr = to_hwc01(vis["SR"][-1])                       # last image of the returned stack (ref :136)
         scio.savemat(os.path.join(result_path, f"output_mulExm_{idx}.mat"), {"sr": sr * scale})
         if hqnr:
@@ -93,6 +123,8 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
                 full_ws[sr_d.shape] = ops.metrics_hqnr_buffers(*sr_d.shape, sr_d.device)
             row = ops.metrics_hqnr(sr_d, ms_d, pan_d, sensor, buffers=full_ws[sr_d.shape])[0]
             full_sum = row if full_sum is None else full_sum + row
+            if baselines:
+                score_baselines(ms_d, pan_d, lambda f: ops.metrics_hqnr(f, ms_d, pan_d, sensor, buffers=full_ws[sr_d.shape])[0])
         elif full_resolution:
             from . import ops
             lr_d, pan_d, sr_d = _to_nchw01(vis["LR"]), _to_nchw01(vis["PAN"]), _to_nchw01(vis["SR"][-1])
@@ -103,6 +135,8 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
             l_pan, ws = full_ws[key]
             row = ops.metrics_noref(lr_d, pan_d, ops.pyr_down(pan_d, 2, out=l_pan), sr_d, workspace=ws)[0]
             full_sum = row if full_sum is None else full_sum + row
+            if baselines:
+                score_baselines(_to_nchw01(vis["MS"]), pan_d, lambda f: ops.metrics_noref(lr_d, pan_d, l_pan, f, workspace=ws)[0])
         elif "HR" in vis and device_metrics:
             from . import ops
             hr_d, sr_d = _to_nchw01(vis["HR"]), _to_nchw01(vis["SR"][-1])
@@ -114,6 +148,11 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
                     q2n_ws[hr_d.shape] = ops.metrics_q2n_workspace(*hr_d.shape, hr_d.device)
                 row = torch.cat([row, ops.metrics_q2n(hr_d, sr_d, workspace=q2n_ws[hr_d.shape])])
             dev_sum = row if dev_sum is None else dev_sum + row
+            if baselines:
+                def pair_row(f):
+                    r = ops.metrics_pair(hr_d, f, 1.0, workspace=dev_ws[hr_d.shape])[0]
+                    return torch.cat([r, ops.metrics_q2n(hr_d, f, workspace=q2n_ws[hr_d.shape])]) if q2n else r
+                score_baselines(_to_nchw01(vis["MS"]), _to_nchw01(vis["PAN"]), pair_row)
         elif "HR" in vis:
             hr = to_hwc01(vis["HR"])
             ssim_sum += metrics.ssim(hr, sr, 1)
@@ -121,16 +160,27 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
         n += 1
     if full_resolution:
         fields = metrics.HQNR_FIELDS if hqnr else metrics.NOREF_FIELDS
-        total = full_sum.tolist() if full_sum is not None else [0.0] * len(fields)   # the one synchronising read
+        if base_sum:                                                                  # the baselines join the one read
+            total = torch.cat([full_sum] + [base_sum[b] for b in baselines]).tolist()
+        else:
+            total = full_sum.tolist() if full_sum is not None else [0.0] * len(fields)   # the one synchronising read
         score = {**{f"{k}_{dataset}": v / max(n, 1) for k, v in zip(fields, total)},
                  "sec_per_item": (time.time() - t0) / max(n, 1)}
+        for i, b in enumerate(baselines if base_sum else ()):
+            score.update({f"{k}_{dataset}@{b}": v / max(n, 1) for k, v in zip(fields, total[(i + 1) * len(fields):])})
         log(dataset, score)
         return score
     extra = {}
     if dev_sum is not None:
-        total = dict(zip(metrics.PAIR_FIELDS + ("q2n",), dev_sum.tolist()))          # the one synchronising read
+        names = metrics.PAIR_FIELDS + (("q2n",) if q2n else ())
+        flat = (torch.cat([dev_sum] + [base_sum[b] for b in baselines]) if base_sum else dev_sum).tolist()   # the one synchronising read
+        total = dict(zip(names, flat))
         ssim_sum, sam_sum = total["ssim"], total["sam"]
-        extra = {f"{k}_{dataset}": total[k] / max(n, 1) for k in ("psnr", "ergas", "scc", "cc", "q") + (("q2n",) if q2n else ())}
+        kept = ("psnr", "ergas", "scc", "cc", "q") + (("q2n",) if q2n else ())
+        extra = {f"{k}_{dataset}": total[k] / max(n, 1) for k in kept}
+        for i, b in enumerate(baselines if base_sum else ()):
+            part = dict(zip(names, flat[(i + 1) * len(names):]))
+            extra.update({f"{k}_{dataset}@{b}": part[k] / max(n, 1) for k in ("ssim", "sam") + kept})
     score = {f"ssim_{dataset}": ssim_sum / max(n, 1), f"sam_{dataset}": sam_sum / max(n, 1),
              "sec_per_item": (time.time() - t0) / max(n, 1), **extra}
     log(dataset, score)

@@ -1699,6 +1699,173 @@ def metrics_hqnr(ps, ms_exp, pan, sensor, ratio=4, block=32, alpha=1.0, beta=1.0
     return y
 
 
+# ---- MTF-GLP: the classical baselines (csrc/mtf.hip, csrc/metrics.hip, csrc/fusion.hip; definitions: tmdiff_amd/metrics.py)
+_GLP_LIMITS = ("contiguous float32 tensors on the GPU, ms_exp and pan_lp [B, C, H, W], pan [B, 1, H, W]; 1 <= C <= 16; ratio 2 or 4, "
+               "H and W multiples of it; fewer than 2^31 elements")
+
+
+def _glp_dense(name, arg, t, shape=None):
+    """``t`` must be a contiguous float32 tensor on the GPU, of ``shape`` when that is given."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        raise ValueError(f"{name}: {arg} must be a contiguous float32 tensor on the GPU ({_GLP_LIMITS})")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: {arg} is {tuple(t.shape)}, need {tuple(shape)} ({_GLP_LIMITS})")
+    return t
+
+
+def _glp_images(name, ms_exp, pan, pan_lp=None, ratio=None):
+    """(B, C, H, W) of a GLP call after the checks on its images."""
+    _glp_dense(name, "ms_exp", ms_exp)
+    if ms_exp.dim() != 4:
+        raise ValueError(f"{name}: ms_exp is {tuple(ms_exp.shape)}, need [B, C, H, W] ({_GLP_LIMITS})")
+    b, c, h, w = ms_exp.shape
+    if not 1 <= c <= 16 or min(b, h, w) < 1 or ms_exp.numel() > 2 ** 31 - 1:
+        raise ValueError(f"{name}: B={b} C={c} H={h} W={w} is not supported ({_GLP_LIMITS})")
+    if ratio is not None and (ratio not in (2, 4) or h % ratio or w % ratio):
+        raise ValueError(f"{name}: H={h} W={w} ratio={ratio} is not supported ({_GLP_LIMITS})")
+    _glp_dense(name, "pan", pan, (b, 1, h, w))
+    if pan_lp is not None:
+        _glp_dense(name, "pan_lp", pan_lp, (b, c, h, w))
+    return b, c, h, w
+
+
+def _overlaps(a, b):
+    """True when the bytes of two dense tensors intersect."""
+    lo, hi = b.data_ptr(), b.data_ptr() + b.numel() * b.element_size()
+    return a.data_ptr() < hi and lo < a.data_ptr() + a.numel() * a.element_size()
+
+
+def fir_decimate_bank(x, taps, ratio=1, offset=None, out=None):
+    """A filter bank on one plane per image (definition: ``metrics.fir_decimate`` of each pair): x [B, H, W] or [B, 1, H, W],
+    taps [T, K, K] -> y [B, T, H', W'] with y[b, t] = ``fir_decimate(x[b], taps[t], ratio, offset)``, bit for bit what
+    ``fir_decimate`` gives on ``x.expand(B, T, H, W).contiguous()`` -- without that T-fold copy: a workgroup stages a patch of
+    x[b] once and walks the T tables over it.  With ``out=`` nothing is allocated or synchronised (graph capture).  Not
+    differentiable: x is detached."""
+    from .metrics import fir_decimate_shape as shape_of
+    name = "fir_decimate_bank"
+    t, k, (oy, ox) = _fir_taps(name, taps, ratio, offset)
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+            and (x.dim() == 3 or (x.dim() == 4 and x.shape[1] == 1))):
+        raise ValueError(f"{name}: need a contiguous float32 [B, H, W] or [B, 1, H, W] tensor on the GPU ({_FIR_LIMITS})")
+    x = x.detach()
+    b, (h, w) = x.shape[0], x.shape[-2:]
+    if min(h, w) < 1 or taps.device != x.device or b * t * h * w > 2 ** 31 - 1:
+        raise ValueError(f"{name}: x {tuple(x.shape)} on {x.device} with taps {tuple(taps.shape)} on {taps.device} is not supported "
+                         f"({_FIR_LIMITS}; fewer than 2^31 elements in B * T * H * W)")
+    shape = (b, t, *shape_of(h, w, ratio, offset)[0])
+    y = out if out is not None else torch.empty(shape, device=x.device, dtype=torch.float32)
+    if tuple(y.shape) != shape:
+        raise ValueError(f"{name}: out must be {shape}, got {tuple(y.shape)}")
+    py = _chk(y, "out")
+    if _overlaps(y, x) or _overlaps(y, taps):
+        raise ValueError(f"{name}: out overlaps x or taps")
+    check(lib.tmdiff_fir_decimate_bank(x.data_ptr(), taps.data_ptr(), py, b, t, h, w, k, ratio, oy, ox, stream_ptr()), name)
+    return y
+
+
+def pan_lowpass_bands(pan, sensor_or_gains, bands, ratio=4, out=None, low=None):
+    """The PAN [B, 1, H, W] seen through every MS band's MTF (definition: ``metrics.pan_lowpass_bands``): [B, C, H, W] with band
+    c = ``upsample_poly23(fir_decimate(pan, mtf_kernel(g_c, ratio), ratio), ratio)``, g_c the gains of the MS bands
+    (``metrics.band_gains(sensor_or_gains, bands)``), not the PAN gain as in ``pan_lowpass``.  ``fir_decimate_bank`` filters the
+    one PAN plane with the C tables.  The float64 definition sets the PAN's mean aside before this chain and adds it back (the
+    interpolator loses 1.21e-9 of a constant); that is a fiftieth of float32's resolution, and the device runs the chain as
+    it stands.  ``low`` lends the [B, C, H / ratio, W / ratio] stage; with it and ``out=`` nothing is
+    allocated (the tap table is cached as ``mtf_degrade`` caches it: call once before capturing into a graph).  Not
+    differentiable: pan is detached."""
+    from . import metrics
+    name = "pan_lowpass_bands"
+    if not (torch.is_tensor(pan) and pan.is_cuda and pan.dim() == 4 and pan.shape[1] == 1):
+        raise ValueError(f"{name}: need a float32 [B, 1, H, W] tensor on the GPU ({_GLP_LIMITS})")
+    bands = int(bands)
+    if ratio not in (2, 4) or pan.shape[2] % ratio or pan.shape[3] % ratio or min(pan.shape[2:]) < ratio or not 1 <= bands <= 16:
+        raise ValueError(f"{name}: shape {tuple(pan.shape)} ratio={ratio} bands={bands} is not supported ({_GLP_LIMITS})")
+    gains = metrics.band_gains(sensor_or_gains, bands)
+    return upsample_poly23(fir_decimate_bank(pan, _mtf_taps(gains, ratio, pan.device), ratio, None, low), ratio, out=out)
+
+
+def glp_moments_workspace(b, c, h, w, device):
+    """A workspace ``glp_moments`` accepts for [b, c, h, w] images (reusable; captured calls must keep it alive).  After a call
+    its first b * c * 7 doubles are the finished sums about the pilots (include/tmdiff_hip.h)."""
+    return torch.empty(max(1, lib.tmdiff_glp_moments_workspace_bytes(int(b), int(c), int(h), int(w)) // 8), device=device,
+                       dtype=torch.float64)
+
+
+def glp_moments(ms_exp, pan, pan_lp, out=None, workspace=None):
+    """The injection statistics of MTF-GLP (definition: ``metrics.glp_moments``): float64 [B, C, 7] in the column order of
+    ``metrics.GLP_MOMENT_FIELDS`` -- the population means, variances and covariance of ms_exp and pan_lp per band, the mean and
+    variance of pan -- from one pass over the three images, as device values.  Sums in fp64 in one fixed order, no atomics: the
+    same bits on every run.  With ``out=`` and ``workspace=`` nothing is allocated or synchronised.  Not differentiable: the
+    inputs are detached."""
+    b, c, h, w = _glp_images("glp_moments", ms_exp, pan, pan_lp)
+    y = _f64("glp_moments", "out", out, (b, c, 7), ms_exp.device)
+    ws, nbytes = _lent("glp_moments", workspace, lib.tmdiff_glp_moments_workspace_bytes(b, c, h, w),
+                       lambda: glp_moments_workspace(b, c, h, w, ms_exp.device))
+    check(lib.tmdiff_glp_moments(ms_exp.detach().data_ptr(), pan.detach().data_ptr(), pan_lp.detach().data_ptr(), b, c, h, w,
+                                 y.data_ptr(), ws.data_ptr(), nbytes, stream_ptr()), "glp_moments")
+    return y
+
+
+def glp_inject(ms_exp, pan, pan_lp, moments, mode, out=None):
+    """The injection of MTF-GLP (definition: ``metrics.glp_inject``, the formulas of ``metrics.mtf_glp``): the fused [B, C, H, W]
+    from ms_exp, pan, pan_lp and ``moments``, the float64 [B, C, 7] device tensor of ``glp_moments``; ``mode`` "glp", "cbd" or
+    "hpm".  The band gains are formed on the device from the moments -- nothing is read on the host -- and every pixel is
+    evaluated in fp64 and rounded to fp32 once.  ``out`` may be ms_exp itself (in place); it must not overlap pan, pan_lp or
+    moments.  With ``out=`` nothing is allocated or synchronised.  Not differentiable: the inputs are detached."""
+    from . import metrics
+    if mode not in metrics.GLP_MODES:
+        raise ValueError(f"glp_inject: mode={mode!r} (one of {metrics.GLP_MODES})")
+    b, c, h, w = _glp_images("glp_inject", ms_exp, pan, pan_lp)
+    mo = _f64("glp_inject", "moments", moments, (b, c, 7), ms_exp.device)
+    y = _glp_dense("glp_inject", "out", out if out is not None else torch.empty_like(ms_exp), (b, c, h, w))
+    for other, what in ((pan, "pan"), (pan_lp, "pan_lp"), (mo, "moments")):
+        if _overlaps(y, other):
+            raise ValueError(f"glp_inject: out overlaps {what}")
+    if y.data_ptr() != ms_exp.data_ptr() and _overlaps(y, ms_exp):
+        raise ValueError("glp_inject: out overlaps ms_exp without being ms_exp")
+    check(lib.tmdiff_glp_inject(ms_exp.detach().data_ptr(), pan.detach().data_ptr(), pan_lp.detach().data_ptr(), mo.data_ptr(),
+                                y.data_ptr(), b, c, h, w, metrics.GLP_MODES.index(mode), stream_ptr()), "glp_inject")
+    return y
+
+
+def mtf_glp_buffers(b, c, h, w, device, ratio=4):
+    """Every scratch tensor of ``mtf_glp`` for [b, c, h, w] images: with them and ``out=`` a call allocates nothing and can be
+    captured into a graph.  "pan_lp" and "pan_low": the per-band low-pass PAN and its low-resolution stage; "moments": the
+    float64 [b, c, 7] statistics; "ws": the workspace of ``glp_moments``."""
+    b, c, h, w = int(b), int(c), int(h), int(w)
+    if not 1 <= c <= 16 or min(b, h, w) < 1 or ratio not in (2, 4) or h % ratio or w % ratio or b * c * h * w > 2 ** 31 - 1:
+        raise ValueError(f"mtf_glp: B={b} C={c} H={h} W={w} ratio={ratio} is not supported ({_GLP_LIMITS})")
+    f32 = dict(device=device, dtype=torch.float32)
+    return {"shape": (b, c, h, w, ratio), "pan_lp": torch.empty(b, c, h, w, **f32),
+            "pan_low": torch.empty(b, c, h // ratio, w // ratio, **f32),
+            "moments": torch.empty(b, c, 7, device=device, dtype=torch.float64), "ws": glp_moments_workspace(b, c, h, w, device)}
+
+
+def mtf_glp(ms_exp, pan, sensor, ratio=4, mode="hpm", pan_lp=None, out=None, buffers=None):
+    """MTF-GLP pansharpening on the device (definition: ``metrics.mtf_glp``): the fused [B, C, H, W] from ms_exp, the MS
+    interpolated to the PAN grid, and pan [B, 1, H, W]; ``mode`` "glp" (additive), "cbd" (regression gain) or "hpm"
+    (multiplicative).  ``pan_lp`` None is ``pan_lowpass_bands(pan, MS gains of sensor, C, ratio)``; ``glp_moments`` then leaves
+    the statistics on the device and ``glp_inject`` forms the gains there and writes the result.  ``sensor``: a name or a pair
+    (MS gains, PAN gain), as ``metrics.mtf_gains`` takes them.  ``out`` may be ms_exp.  With ``buffers`` (``mtf_glp_buffers``) and
+    ``out=`` nothing is allocated or synchronised; the tap table is cached as ``mtf_degrade`` caches its own: call once before
+    capturing into a graph.  Not differentiable: the inputs are detached."""
+    from . import metrics
+    if mode not in metrics.GLP_MODES:
+        raise ValueError(f"mtf_glp: mode={mode!r} (one of {metrics.GLP_MODES})")
+    b, c, h, w = _glp_images("mtf_glp", ms_exp, pan, pan_lp, ratio)
+    if out is not None:
+        _glp_dense("mtf_glp", "out", out, (b, c, h, w))
+        for other, what in ((pan, "pan"), (pan_lp, "pan_lp")):
+            if other is not None and _overlaps(out, other):
+                raise ValueError(f"mtf_glp: out overlaps {what}")
+    buf = buffers if buffers is not None else mtf_glp_buffers(b, c, h, w, ms_exp.device, ratio)
+    if buf["shape"] != (b, c, h, w, ratio) or buf["pan_lp"].device != ms_exp.device:
+        raise ValueError(f"mtf_glp: buffers made for {buf['shape']}, the call is {(b, c, h, w, ratio)}")
+    if pan_lp is None:
+        pan_lp = pan_lowpass_bands(pan, metrics.mtf_gains(sensor, c)[0], c, ratio, out=buf["pan_lp"], low=buf["pan_low"])
+    mo = glp_moments(ms_exp, pan, pan_lp, out=buf["moments"], workspace=buf["ws"])
+    return glp_inject(ms_exp, pan, pan_lp, mo, mode, out=out)
+
+
 # ---- backward-side wrappers (finetune path) -----------------------------------------------------------
 
 

@@ -293,3 +293,44 @@ def fuse_scene(diffusion, lr_ms, pan, prompt, ratio=4, score=False, interp="bili
         ms_exp = ms if interp == "poly23" else ops.upsample_poly23(lr_ms, ratio)
         return scene, metrics.quality_hqnr(ms_exp, pan, scene.float().contiguous(), sensor, ratio)
     return scene, metrics.quality_fullres(lr_ms, pan, scene.float().contiguous())
+
+
+@torch.no_grad()
+def classical_fuse(lr_ms, pan, sensor, ratio=4, mode="hpm", score=False, consistency=None):
+    """From the raw pair to a classical fused scene, the MTF-GLP row of the tables: lr_ms [B, C, h, w] is interpolated with the
+    23-tap polynomial kernel into ms_exp and fused with pan [B, 1, ratio * h, ratio * w] by ``mtf_glp`` in ``mode`` ("glp",
+    "cbd" or "hpm"; definition: ``metrics.mtf_glp``).  ``sensor`` names the row of ``metrics.MTF_GAINS`` (or is a pair of
+    explicit gains).  Tensors on the GPU go through the operators (``ops.upsample_poly23``, ``ops.mtf_glp``); host tensors and
+    arrays go through the float64 definitions.  ``score`` and ``consistency`` mean what they mean in ``fuse_scene``:
+    ``score=True`` returns (scene, ``metrics.quality_fullres(lr_ms, pan, scene)``), ``score="hqnr"`` returns (scene,
+    ``metrics.quality_hqnr(ms_exp, pan, scene, sensor, ratio)``) with the ms_exp that was already made, and
+    ``consistency={"iters": n, "relax": w}`` refines the scene with ``consistency_refine`` against lr_ms first.  Scores exist on
+    the device only (ValueError for host data).  Not differentiable."""
+    from . import metrics
+    if score not in (False, True, "hqnr"):
+        raise ValueError(f"classical_fuse: score={score!r} (False, True or 'hqnr')")
+    if mode not in metrics.GLP_MODES:
+        raise ValueError(f"classical_fuse: mode={mode!r} (one of {metrics.GLP_MODES})")
+    if consistency is not None and (not isinstance(consistency, dict) or set(consistency) - {"iters", "relax"}):
+        raise ValueError(f"classical_fuse: consistency={consistency!r} (None or a dict with 'iters' and 'relax')")
+    if ratio not in (2, 4) or len(lr_ms.shape) != 4 or len(pan.shape) != 4 or pan.shape[0] != lr_ms.shape[0] or pan.shape[1] != 1 or \
+            tuple(pan.shape[2:]) != (ratio * lr_ms.shape[2], ratio * lr_ms.shape[3]):
+        raise ValueError(f"classical_fuse: pan {tuple(pan.shape)} is not [B, 1, {ratio} h, {ratio} w] of lr_ms {tuple(lr_ms.shape)} "
+                         f"(ratio 2 or 4)")
+    if torch.is_tensor(lr_ms) and lr_ms.is_cuda:
+        lr_ms, pan = lr_ms.detach().float().contiguous(), pan.detach().float().contiguous()
+        ms_exp = ops.upsample_poly23(lr_ms, ratio)
+        scene = ops.mtf_glp(ms_exp, pan, sensor, ratio, mode)
+        if consistency is not None:
+            scene = consistency_refine(scene, lr_ms, sensor, ratio, out=scene, **consistency)
+        if not score:
+            return scene
+        if isinstance(score, str):
+            return scene, metrics.quality_hqnr(ms_exp, pan, scene, sensor, ratio)
+        return scene, metrics.quality_fullres(lr_ms, pan, scene)
+    if score:
+        raise ValueError("classical_fuse: scores are made on the GPU; score host data with the host functions of metrics")
+    scene = metrics.mtf_glp(metrics.upsample_poly23(lr_ms, ratio), pan, sensor, ratio, mode)
+    if consistency is not None:
+        scene = consistency_refine(scene, lr_ms, sensor, ratio, **consistency)
+    return torch.from_numpy(scene) if torch.is_tensor(lr_ms) and not torch.is_tensor(scene) else scene

@@ -30,15 +30,21 @@ VAL_SETS = (("val_QB", "QB"), ("val_GF2", "GF2"), ("val_WV3", "WV3"))
 
 def validation_options(dataset_opt):
     """The keyword arguments of ``evaluate.val_dataset`` a validation dataset's options ask for: ``full_resolution`` true is QNR,
-    "hqnr" is HQNR with the optional ``sensor``; absent or false is the scoring against ground truth."""
+    "hqnr" is HQNR with the optional ``sensor``; absent or false is the scoring against ground truth.  ``baselines``, beside it: a
+    list out of ``evaluate.BASELINES`` ("exp", "glp", "cbd", "hpm") scored with the same set on the same files, with the optional
+    ``sensor``; it needs ``full_resolution`` (the scoring against ground truth here runs on the host)."""
     full = dataset_opt.get("full_resolution")
+    base = dataset_opt.get("baselines")
+    extra = {"baselines": tuple(base), "sensor": dataset_opt.get("sensor")} if base else {}
     if not full:
+        if base:
+            raise ValueError("baselines: scored on the GPU beside the network, which needs full_resolution (true or \"hqnr\")")
         return {}
     if isinstance(full, str):
         if full.lower() != "hqnr":
             raise ValueError(f"full_resolution: {full!r} (true, false or \"hqnr\")")
-        return {"full_resolution": True, "protocol": "hqnr", "sensor": dataset_opt.get("sensor")}
-    return {"full_resolution": True}
+        return {"full_resolution": True, "protocol": "hqnr", "sensor": dataset_opt.get("sensor"), **extra}
+    return {"full_resolution": True, **extra}
 
 
 def seed_all(seed=3407, rank=0, reseed_python=True):

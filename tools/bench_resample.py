@@ -21,7 +21,13 @@ is captured into a graph of `--graph-calls` calls; a round is the time of one re
 
 `--leg adjoint`: the adjoint (`ops.mtf_degrade_adjoint`) at the same four shapes against torch autograd's backward of that
 composition, the forward kernel's own time beside it, and `tiling.consistency_refine` (8 steps) at [1, 8, 1024, 1024]; timed the
-same way."""
+same way.
+
+`--leg glp`: the MTF-GLP baselines at MS [1, 8, 1024, 1024] "WV3" and [1, 4, 2048, 2048] "QB", PAN of the same extent: the filter
+bank (`ops.fir_decimate_bank`) against `ops.fir_decimate` on the expanded PAN with the `expand().contiguous()` inside the timing;
+`ops.glp_moments` + `ops.glp_inject` against the same arithmetic composed from torch operators (float64 statistics, float32
+injection); `ops.mtf_glp` whole.  The elementwise kernels are printed with the bytes they move and their share of a
+device-to-device copy of as many bytes, timed in the same rounds.  Captured and timed as `--leg mtf`."""
 import argparse
 import os
 import statistics
@@ -160,9 +166,74 @@ def adjoint_leg(args):
         print(f"{names[i][24:]:28s} adjoint / forward kernel {a / f:5.2f}   torch backward / adjoint {t / a:6.1f}", flush=True)
 
 
+def glp_leg(args):
+    """`--leg glp`: see the module's docstring."""
+    from tmdiff_amd import metrics
+    ratio = 4
+    cases = []          # (name, call, bytes moved or 0)
+    for sensor, (b, c, h) in (("WV3", (1, 8, 1024)), ("QB", (1, 4, 2048))):
+        shape = [b, c, h, h]
+        ms, pan = 0.1 + 0.8 * torch.rand(b, c, h, h, device="cuda"), 0.1 + 0.8 * torch.rand(b, 1, h, h, device="cuda")
+        gains = metrics.mtf_gains(sensor, c)[0]
+        taps = ops._mtf_taps(gains, ratio, pan.device)
+        buf, out = ops.mtf_glp_buffers(b, c, h, h, "cuda", ratio), torch.empty_like(ms)
+        lp = ops.pan_lowpass_bands(pan, gains, c, ratio, out=buf["pan_lp"], low=buf["pan_low"])
+        mo = ops.glp_moments(ms, pan, lp, out=buf["moments"], workspace=buf["ws"])
+        low2 = torch.empty_like(buf["pan_low"])
+
+        def expanded(pan=pan, taps=taps, low2=low2, c=c):
+            return ops.fir_decimate(pan.expand(-1, c, -1, -1).contiguous(), taps, ratio, None, low2)
+
+        def composed(ms=ms, pan=pan, lp=lp, out=out):
+            m64, l64, p64 = ms.double(), lp.double(), pan.double()
+            mean_m, mean_l, mean_p = m64.mean((2, 3), keepdim=True), l64.mean((2, 3), keepdim=True), p64.mean((2, 3), keepdim=True)
+            var_m, var_l = ((m64 - mean_m) ** 2).mean((2, 3), keepdim=True), ((l64 - mean_l) ** 2).mean((2, 3), keepdim=True)
+            a = (var_m / var_l).sqrt()
+            pc, plc = a * (p64 - mean_p) + mean_m, a * (l64 - mean_p) + mean_m
+            return out.copy_(m64 * pc / (plc + 2.0 ** -52))
+
+        err = float((expanded() - ops.fir_decimate_bank(pan, taps, ratio, None, buf["pan_low"])).abs().max())
+        ref = composed().clone()
+        got = ops.glp_inject(ms, pan, lp, mo, "hpm", out=out)
+        print(f"{sensor} {shape}: max |bank - expanded| = {err:.1e}; max |moments + inject - torch composition| = "
+              f"{float((got - ref).abs().max()):.3e}", flush=True)
+        plane = 4 * b * h * h
+        src, dst = torch.empty((3 * c + 1) * plane // 8, device="cuda"), torch.empty((3 * c + 1) * plane // 8, device="cuda")
+        src2, dst2 = torch.empty((2 * c + 1) * plane // 8, device="cuda"), torch.empty((2 * c + 1) * plane // 8, device="cuda")
+        cases += [
+            (f"fir_decimate_bank            {sensor} {shape}", lambda pan=pan, taps=taps, buf=buf: ops.fir_decimate_bank(pan, taps, ratio, None, buf["pan_low"]), 0),
+            (f"expand + fir_decimate        {sensor} {shape}", expanded, 0),
+            (f"glp_moments                  {sensor} {shape}", lambda ms=ms, pan=pan, lp=lp, buf=buf: ops.glp_moments(ms, pan, lp, out=buf["moments"], workspace=buf["ws"]), (2 * c + 1) * plane),
+            (f"copy of (2 C + 1) planes     {sensor} {shape}", lambda s=src2, d=dst2: d.copy_(s), (2 * c + 1) * plane),
+            (f"glp_inject hpm               {sensor} {shape}", lambda ms=ms, pan=pan, lp=lp, mo=mo, out=out: ops.glp_inject(ms, pan, lp, mo, "hpm", out=out), (3 * c + 1) * plane),
+            (f"glp_inject cbd               {sensor} {shape}", lambda ms=ms, pan=pan, lp=lp, mo=mo, out=out: ops.glp_inject(ms, pan, lp, mo, "cbd", out=out), (3 * c + 1) * plane),
+            (f"copy of (3 C + 1) planes     {sensor} {shape}", lambda s=src, d=dst: d.copy_(s), (3 * c + 1) * plane),
+            (f"torch moments + hpm          {sensor} {shape}", composed, 0),
+            (f"mtf_glp hpm (whole)          {sensor} {shape}", lambda ms=ms, pan=pan, s=sensor, out=out, buf=buf: ops.mtf_glp(ms, pan, s, ratio, "hpm", out=out, buffers=buf), 0),
+        ]
+    graphs = [captured(fn, args.graph_calls) for _, fn, _ in cases]
+    times = [[] for _ in cases]
+    for _ in range(args.rounds):
+        for graph, t in zip(graphs, times):
+            time_us(graph.replay, 1)
+            t.append(time_us(graph.replay, 1) / args.graph_calls)
+    print(f"{'case':56s} {'us per call (min..max)':>30s} {'MiB moved':>10s} {'GB/s':>8s}")
+    med = {}
+    for (name, _, nbytes), t in zip(cases, times):
+        m = med[name] = statistics.median(t)
+        rate = f"{nbytes / 2 ** 20:10.1f} {nbytes / m / 1e3:8.1f}" if nbytes else ""
+        print(f"{name:56s} {m:10.2f} ({min(t):8.2f}..{max(t):8.2f}) {rate}", flush=True)
+    names = [n for n, _, _ in cases]
+    for i in range(0, len(names), 9):
+        n = names[i:i + 9]
+        print(f"{n[0][29:]:24s} expanded / bank {med[n[1]] / med[n[0]]:5.2f}   moments: of copy {med[n[3]] / med[n[2]]:5.2f}   "
+              f"inject hpm: of copy {med[n[6]] / med[n[4]]:5.2f}   cbd: {med[n[6]] / med[n[5]]:5.2f}   "
+              f"torch / (moments + inject) {med[n[7]] / (med[n[2]] + med[n[4]]):6.1f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("resample", "mtf", "adjoint"), default="resample")
+    ap.add_argument("--leg", choices=("resample", "mtf", "adjoint", "glp"), default="resample")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--graph-calls", type=int, default=10, help="--leg mtf / adjoint: calls captured into each graph")
@@ -176,6 +247,8 @@ def main():
         return mtf_leg(args)
     if args.leg == "adjoint":
         return adjoint_leg(args)
+    if args.leg == "glp":
+        return glp_leg(args)
 
     cases = []          # (name, kernel call, bytes, copy call, bytes the copy moves)
 
