@@ -840,6 +840,34 @@ int tmdiff_glp_inject(const float* ms_exp, const float* pan, const float* pan_lp
                       int32_t C, int32_t H, int32_t W, int32_t mode, tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Component-substitution pansharpening: GS, GSA, Brovey (csrc/cs_fusion.hip; host definitions: tmdiff_amd/metrics.py,
+ * plane_moments / cs_coeffs / cs_inject / cs_fuse).  Dense tensors; nothing is allocated or synchronised, no atomics, the same
+ * bits on every run and on a graph replay.
+ *  plane_gram: ms [B, C, H, W], pan [B, 1, H, W] fp32 -> out, float64 [B, C + 1, C + 2]: the planes are the C bands, then the
+ *             PAN; columns 0 .. C are their population covariance matrix (exactly symmetric), column C + 1 their means.  One
+ *             pass with v_mfma_f64_16x16x4_f64 over tiles whose rows are the planes, minus their first pixel (a pilot), and a
+ *             plane of ones; partial tiles per workgroup in `workspace` (8-byte aligned, tmdiff_plane_gram_workspace_bytes), a
+ *             finalize launch adds them in index order.  The workspace then starts with the finished raw sums, float64
+ *             [B, C + 2, C + 2] in the order bands, PAN, ones: sums of products of d = value - pilot, column C + 1 the sums of d,
+ *             the corner n.  The summation order is written in the source's header.  Limits: B >= 0, 1 <= C <= 14, H, W >= 1,
+ *             B * C * H * W <= 2^31 - 1; otherwise TMDIFF_E_UNSUPPORTED and a workspace size of 0.
+ *  cs_coeffs: full, low: float64 [B, C + 1, C + 2] of plane_gram at the PAN scale and at the reduced scale (low may be null unless
+ *             mode is 1) -> out, float64 [B, 2 C + 3]: alpha[C], g[C], a, mean_I, mean_P.  mode 0 "gs", 1 "gsa", 2 "brovey".
+ *             gsa solves S_lr alpha = c_lr by a root-free unpivoted Cholesky factorisation (L D L') in one lane; a pivot <= 0 gives NaN.
+ *  cs_inject: out [B, C, H, W] from ms_exp, pan and the device-resident `coef` of cs_coeffs; I = sum_k alpha_k M_k,
+ *             P_I = a (P - mean_P) + mean_I; modes 0, 1: F_c = M_c + g_c (P_I - I); mode 2: F_c = M_c P_I / (I + 2^-52), in
+ *             fp64, rounded to fp32 once.  out may be ms_exp; it must not overlap pan or coef.  Limits: plane_gram's.
+ *             (Added within version 6.)
+ * ------------------------------------------------------------------------------------ */
+size_t tmdiff_plane_gram_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int tmdiff_plane_gram(const float* ms, const float* pan, int32_t B, int32_t C, int32_t H, int32_t W, double* out, void* workspace,
+                      size_t workspace_bytes, tmdiff_stream_t stream);
+int tmdiff_cs_coeffs(const double* full, const double* low, double* out, int32_t B, int32_t C, int32_t mode,
+                     tmdiff_stream_t stream);
+int tmdiff_cs_inject(const float* ms_exp, const float* pan, const double* coef, float* out, int32_t B, int32_t C, int32_t H,
+                     int32_t W, int32_t mode, tmdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Standalone attention operators of core/Attention.py (imported by nothing in the reference; built because the
  * north star names them).  All fp32.
  *  attn_fwd : out = softmax(q k^T * scale [key mask]) v per (batch, head); fp32 MFMA, online softmax.

@@ -232,6 +232,12 @@ SIGNATURES.update({
     "tmdiff_glp_moments_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
     "tmdiff_glp_moments": (C.c_int, [vp, vp, vp] + [C.c_int32] * 4 + [vp, vp, C.c_size_t, vp]),
     "tmdiff_glp_inject": (C.c_int, [vp] * 5 + [C.c_int32] * 5 + [vp]),
+    # component substitution: ms, pan | B, C, H, W | out, workspace, bytes;  full, low, out | B, C, mode;
+    # ms_exp, pan, coef, out | B, C, H, W, mode
+    "tmdiff_plane_gram_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "tmdiff_plane_gram": (C.c_int, [vp, vp] + [C.c_int32] * 4 + [vp, vp, C.c_size_t, vp]),
+    "tmdiff_cs_coeffs": (C.c_int, [vp, vp, vp] + [C.c_int32] * 3 + [vp]),
+    "tmdiff_cs_inject": (C.c_int, [vp] * 4 + [C.c_int32] * 5 + [vp]),
 })
 
 

@@ -13,6 +13,7 @@ from . import metrics
 
 IMG_SCALE = {"GF2": 1023.0}          # every other sensor: 2047 (ref :134)
 BASELINES = ("exp", "glp", "cbd", "hpm")   # val_dataset(baselines=...): the interpolated MS and the three modes of metrics.mtf_glp
+CS_BASELINES = ("cs-gs", "cs-gsa", "cs-brovey")   # ... and "cs-" + the methods of metrics.cs_fuse (component substitution)
 
 
 def to_hwc01(img, min_max=(0.0, 1.0)):
@@ -64,10 +65,13 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
     Each is scored with the same metric set as the network in the mode that is active (``device_metrics=True``, or
     ``full_resolution=True`` with either protocol; the host-metric mode raises ValueError) under the keys
     ``"<metric>_<dataset>@<baseline>"``; the sums stay on the device and join the single synchronising read.  ``sensor`` is
-    resolved as for ``protocol="hqnr"``.  ``baselines=()`` changes nothing: the same keys, values and launches."""
+    resolved as for ``protocol="hqnr"``.  ``baselines=()`` changes nothing: the same keys, values and launches.
+    The names of ``CS_BASELINES`` ("cs-gs", "cs-gsa", "cs-brovey") are accepted beside them: the same visuals fused by
+    ``ops.cs_fuse`` with that method (``metrics.cs_fuse``; buffers made once per shape), scored and reported the same way
+    (``"<metric>_<dataset>@cs-gsa"``)."""
     baselines = tuple(baselines)
-    if [b for b in baselines if b not in BASELINES] or len(set(baselines)) != len(baselines):
-        raise ValueError(f"val_dataset: baselines={baselines!r} (distinct names out of {BASELINES})")
+    if [b for b in baselines if b not in BASELINES + CS_BASELINES] or len(set(baselines)) != len(baselines):
+        raise ValueError(f"val_dataset: baselines={baselines!r} (distinct names out of {BASELINES + CS_BASELINES})")
     if baselines and not (device_metrics or full_resolution):
         raise ValueError("val_dataset(baselines=...) scores on the GPU: it needs device_metrics=True or full_resolution=True")
     if protocol not in ("qnr", "hqnr"):
@@ -90,14 +94,19 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
     n = 0
     dev_sum, dev_ws, q2n_ws = None, {}, {}
     full_sum, full_ws = None, {}
-    base_sum, glp_ws = {}, {}
+    base_sum, glp_ws, cs_ws = {}, {}, {}
 
     def score_baselines(ms_d, pan_d, score_row):
         """Adds score_row(fused) of every baseline to its running sum; ms_d, pan_d: the item's MS and PAN in [0, 1]."""
         from . import ops
         for name in baselines:
             fused = ms_d
-            if name != "exp":
+            if name in CS_BASELINES:
+                if ms_d.shape not in cs_ws:
+                    cs_ws[ms_d.shape] = (ops.cs_fuse_buffers(*ms_d.shape, ms_d.device), torch.empty_like(ms_d))
+                buf, out = cs_ws[ms_d.shape]
+                fused = ops.cs_fuse(ms_d, pan_d, sensor, 4, name[3:], out=out, buffers=buf)
+            elif name != "exp":
                 if ms_d.shape not in glp_ws:
                     glp_ws[ms_d.shape] = (ops.mtf_glp_buffers(*ms_d.shape, ms_d.device), torch.empty_like(ms_d))
                 buf, out = glp_ws[ms_d.shape]

@@ -1866,6 +1866,162 @@ def mtf_glp(ms_exp, pan, sensor, ratio=4, mode="hpm", pan_lp=None, out=None, buf
     return glp_inject(ms_exp, pan, pan_lp, mo, mode, out=out)
 
 
+# ---- component substitution: GS, GSA, Brovey (csrc/cs_fusion.hip; definitions: tmdiff_amd/metrics.py) ---------------------------
+_CS_LIMITS = ("contiguous float32 tensors on the GPU, ms [B, C, H, W], pan [B, 1, H, W]; 1 <= C <= 14; ratio 2 or 4, H and W "
+              "multiples of it; fewer than 2^31 elements")
+
+
+def _cs_dense(name, arg, t, shape=None):
+    """``t`` must be a contiguous float32 tensor on the GPU, of ``shape`` when that is given."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        raise ValueError(f"{name}: {arg} must be a contiguous float32 tensor on the GPU ({_CS_LIMITS})")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: {arg} is {tuple(t.shape)}, need {tuple(shape)} ({_CS_LIMITS})")
+    return t
+
+
+def _cs_images(name, ms, pan, ratio=None):
+    """(B, C, H, W) of a component-substitution call after the checks on its images."""
+    _cs_dense(name, "ms", ms)
+    if ms.dim() != 4:
+        raise ValueError(f"{name}: ms is {tuple(ms.shape)}, need [B, C, H, W] ({_CS_LIMITS})")
+    b, c, h, w = ms.shape
+    if not 1 <= c <= 14 or min(b, h, w) < 1 or ms.numel() > 2 ** 31 - 1:
+        raise ValueError(f"{name}: B={b} C={c} H={h} W={w} is not supported ({_CS_LIMITS})")
+    if ratio is not None and (ratio not in (2, 4) or h % ratio or w % ratio):
+        raise ValueError(f"{name}: H={h} W={w} ratio={ratio} is not supported ({_CS_LIMITS})")
+    _cs_dense(name, "pan", pan, (b, 1, h, w))
+    return b, c, h, w
+
+
+def _cs_mode(name, method):
+    from . import metrics
+    if method not in metrics.CS_METHODS:
+        raise ValueError(f"{name}: method={method!r} (one of {metrics.CS_METHODS})")
+    return metrics.CS_METHODS.index(method)
+
+
+def plane_moments_workspace(b, c, h, w, device):
+    """A workspace ``plane_moments`` accepts for [b, c, h, w] images (reusable; captured calls must keep it alive).  After a call
+    its first b * (c + 2)^2 doubles are the finished raw sums about the pilots (include/tmdiff_hip.h)."""
+    return torch.empty(max(1, lib.tmdiff_plane_gram_workspace_bytes(int(b), int(c), int(h), int(w)) // 8), device=device,
+                       dtype=torch.float64)
+
+
+def plane_moments(ms, pan, out=None, workspace=None):
+    """The joint second moments of all bands and the PAN (definition: ``metrics.plane_moments``): float64 [B, C + 1, C + 2], the
+    population covariance matrix of the planes (the C bands of ms, then pan) and, in the last column, their means, as device
+    values from one pass over the images: the (C + 2) x (C + 2) Gram matrix of the planes and a plane of ones is accumulated
+    with the fp64 matrix instruction.  Sums in fp64 in one fixed order, no atomics: the same bits on every run; the matrix is
+    exactly symmetric.  With ``out=`` and ``workspace=`` nothing is allocated or synchronised.  Not differentiable: the inputs
+    are detached."""
+    b, c, h, w = _cs_images("plane_moments", ms, pan)
+    y = _f64("plane_moments", "out", out, (b, c + 1, c + 2), ms.device)
+    ws, nbytes = _lent("plane_moments", workspace, lib.tmdiff_plane_gram_workspace_bytes(b, c, h, w),
+                       lambda: plane_moments_workspace(b, c, h, w, ms.device))
+    check(lib.tmdiff_plane_gram(ms.detach().data_ptr(), pan.detach().data_ptr(), b, c, h, w, y.data_ptr(), ws.data_ptr(), nbytes,
+                                stream_ptr()), "plane_moments")
+    return y
+
+
+def cs_coeffs(full, low, method, out=None):
+    """The constants of a component-substitution fusion (definition: ``metrics.cs_coeffs``): float64 [B, 2 C + 3] = alpha, g, a,
+    mean_I, mean_P from ``full``, the float64 [B, C + 1, C + 2] device tensor of ``plane_moments`` at the PAN scale, and for
+    "gsa" ``low``, the same at the reduced scale (None otherwise).  "gsa" solves its C x C system by a root-free unpivoted Cholesky
+    factorisation on the device; a singular system gives NaN.  Nothing is read on the host; with ``out=`` nothing is allocated."""
+    mode = _cs_mode("cs_coeffs", method)
+    if not (torch.is_tensor(full) and full.dim() == 3 and full.shape[2] == full.shape[1] + 1 and 2 <= full.shape[1] <= 15):
+        raise ValueError("cs_coeffs: full must be a float64 [B, C + 1, C + 2] tensor on the GPU, 1 <= C <= 14")
+    b, c = full.shape[0], full.shape[1] - 1
+    full = _f64("cs_coeffs", "full", full, (b, c + 1, c + 2), None)
+    if method == "gsa":
+        if low is None:
+            raise ValueError("cs_coeffs: method 'gsa' needs the reduced-scale moments `low`")
+        low = _f64("cs_coeffs", "low", low, (b, c + 1, c + 2), None)
+        if low.device != full.device:
+            raise ValueError("cs_coeffs: full and low are on different devices")
+    else:
+        low = None
+    y = _f64("cs_coeffs", "out", out, (b, 2 * c + 3), full.device)
+    for other, what in ((full, "full"), (low, "low")):
+        if other is not None and _overlaps(y, other):
+            raise ValueError(f"cs_coeffs: out overlaps {what}")
+    check(lib.tmdiff_cs_coeffs(full.detach().data_ptr(), low.detach().data_ptr() if low is not None else None, y.data_ptr(), b, c, mode,
+                               stream_ptr()), "cs_coeffs")
+    return y
+
+
+def cs_inject(ms_exp, pan, coef, method, out=None):
+    """The injection of component substitution (definition: ``metrics.cs_inject``): the fused [B, C, H, W] from ms_exp, pan and
+    ``coef``, the float64 [B, 2 C + 3] device tensor of ``cs_coeffs``; ``method`` "gs", "gsa" or "brovey".  Every pixel is
+    evaluated in fp64 and rounded to fp32 once.  ``out`` may be ms_exp itself (in place); it must not overlap pan or coef.
+    With ``out=`` nothing is allocated or synchronised.  Not differentiable: the inputs are detached."""
+    mode = _cs_mode("cs_inject", method)
+    b, c, h, w = _cs_images("cs_inject", ms_exp, pan)
+    co = _f64("cs_inject", "coef", coef, (b, 2 * c + 3), ms_exp.device)
+    y = _cs_dense("cs_inject", "out", out if out is not None else torch.empty_like(ms_exp), (b, c, h, w))
+    for other, what in ((pan, "pan"), (co, "coef")):
+        if _overlaps(y, other):
+            raise ValueError(f"cs_inject: out overlaps {what}")
+    if y.data_ptr() != ms_exp.data_ptr() and _overlaps(y, ms_exp):
+        raise ValueError("cs_inject: out overlaps ms_exp without being ms_exp")
+    check(lib.tmdiff_cs_inject(ms_exp.detach().data_ptr(), pan.detach().data_ptr(), co.detach().data_ptr(), y.data_ptr(), b, c, h, w,
+                               mode, stream_ptr()), "cs_inject")
+    return y
+
+
+def cs_fuse_buffers(b, c, h, w, device, ratio=4):
+    """Every scratch tensor of ``cs_fuse`` for [b, c, h, w] images: with them and ``out=`` a call allocates nothing and can be
+    captured into a graph.  "full", "low": the float64 [b, c + 1, c + 2] moments at the two scales; "coef": the float64
+    [b, 2 c + 3] constants; "ms_low", "pan_low": the reduced-scale pair of "gsa"; "ws", "ws_low": the workspaces of
+    ``plane_moments``."""
+    b, c, h, w = int(b), int(c), int(h), int(w)
+    if not 1 <= c <= 14 or min(b, h, w) < 1 or ratio not in (2, 4) or h % ratio or w % ratio or b * c * h * w > 2 ** 31 - 1:
+        raise ValueError(f"cs_fuse: B={b} C={c} H={h} W={w} ratio={ratio} is not supported ({_CS_LIMITS})")
+    f32, f64 = dict(device=device, dtype=torch.float32), dict(device=device, dtype=torch.float64)
+    return {"shape": (b, c, h, w, ratio), "full": torch.empty(b, c + 1, c + 2, **f64), "low": torch.empty(b, c + 1, c + 2, **f64),
+            "coef": torch.empty(b, 2 * c + 3, **f64), "ms_low": torch.empty(b, c, h // ratio, w // ratio, **f32),
+            "pan_low": torch.empty(b, 1, h // ratio, w // ratio, **f32), "ws": plane_moments_workspace(b, c, h, w, device),
+            "ws_low": plane_moments_workspace(b, c, h // ratio, w // ratio, device)}
+
+
+def cs_fuse(ms_exp, pan, sensor=None, ratio=4, method="gsa", lr_ms=None, out=None, buffers=None):
+    """Component-substitution pansharpening on the device (definition: ``metrics.cs_fuse``): the fused [B, C, H, W] from ms_exp,
+    the MS interpolated to the PAN grid, and pan [B, 1, H, W]; ``method`` "gs" (Gram-Schmidt, mean intensity), "gsa" (adaptive
+    Gram-Schmidt) or "brovey".  ``plane_moments`` leaves the joint moments on the device, ``cs_coeffs`` forms the constants
+    there and ``cs_inject`` writes the result.  "gsa" regresses the reduced-scale PAN, ``mtf_degrade(pan, PAN gain of sensor,
+    ratio)``, on the reduced-scale MS: ``lr_ms`` [B, C, H / ratio, W / ratio], or with None the samples
+    ms_exp[..., ratio // 2::ratio, ratio // 2::ratio], which are the raw MS when ms_exp came from ``upsample_poly23``.  ``sensor``
+    (a name or a pair (MS gains, PAN gain), as ``metrics.mtf_gains`` takes them) is needed for "gsa" only.  ``out`` may be
+    ms_exp.  With ``buffers`` (``cs_fuse_buffers``) and ``out=`` nothing is allocated or synchronised; the tap table is cached as
+    ``mtf_degrade`` caches its own: call once before capturing into a graph.  Not differentiable: the inputs are detached."""
+    from . import metrics
+    _cs_mode("cs_fuse", method)
+    b, c, h, w = _cs_images("cs_fuse", ms_exp, pan, ratio)
+    ms_exp, pan = ms_exp.detach(), pan.detach()
+    if out is not None:
+        _cs_dense("cs_fuse", "out", out, (b, c, h, w))
+        if _overlaps(out, pan):
+            raise ValueError("cs_fuse: out overlaps pan")
+    buf = buffers if buffers is not None else cs_fuse_buffers(b, c, h, w, ms_exp.device, ratio)
+    if buf["shape"] != (b, c, h, w, ratio) or buf["full"].device != ms_exp.device:
+        raise ValueError(f"cs_fuse: buffers made for {buf['shape']}, the call is {(b, c, h, w, ratio)}")
+    low = None
+    if method == "gsa":
+        if sensor is None:
+            raise ValueError("cs_fuse: method 'gsa' needs the sensor whose PAN gain shapes the reduced-scale PAN")
+        gain = metrics.mtf_gains(sensor, c)[1]
+        if lr_ms is None:
+            ms_low = buf["ms_low"]
+            ms_low.copy_(ms_exp[..., ratio // 2::ratio, ratio // 2::ratio])
+        else:
+            ms_low = _cs_dense("cs_fuse", "lr_ms", lr_ms, (b, c, h // ratio, w // ratio)).detach()
+        pan_low = mtf_degrade(pan, gain, ratio, out=buf["pan_low"])
+        low = plane_moments(ms_low, pan_low, out=buf["low"], workspace=buf["ws_low"])
+    full = plane_moments(ms_exp, pan, out=buf["full"], workspace=buf["ws"])
+    return cs_inject(ms_exp, pan, cs_coeffs(full, low, method, out=buf["coef"]), method, out=out)
+
+
 # ---- backward-side wrappers (finetune path) -----------------------------------------------------------
 
 

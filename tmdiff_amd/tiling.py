@@ -296,6 +296,40 @@ def fuse_scene(diffusion, lr_ms, pan, prompt, ratio=4, score=False, interp="bili
 
 
 @torch.no_grad()
+def _classical(name, on_device, on_host, lr_ms, pan, sensor, ratio, score, consistency):
+    """The body ``classical_fuse`` and ``cs_fuse`` share: the checks, the interpolation, the fusion ``on_device(ms_exp, pan)`` or
+    ``on_host(ms_exp, pan)``, ``consistency_refine`` and the scores."""
+    from . import metrics
+    if score not in (False, True, "hqnr"):
+        raise ValueError(f"{name}: score={score!r} (False, True or 'hqnr')")
+    if consistency is not None and (not isinstance(consistency, dict) or set(consistency) - {"iters", "relax"}):
+        raise ValueError(f"{name}: consistency={consistency!r} (None or a dict with 'iters' and 'relax')")
+    if (consistency is not None or isinstance(score, str)) and sensor is None:
+        raise ValueError(f"{name}: consistency=... and score='hqnr' need the sensor whose MTF gains shape the filters")
+    if ratio not in (2, 4) or len(lr_ms.shape) != 4 or len(pan.shape) != 4 or pan.shape[0] != lr_ms.shape[0] or pan.shape[1] != 1 or \
+            tuple(pan.shape[2:]) != (ratio * lr_ms.shape[2], ratio * lr_ms.shape[3]):
+        raise ValueError(f"{name}: pan {tuple(pan.shape)} is not [B, 1, {ratio} h, {ratio} w] of lr_ms {tuple(lr_ms.shape)} "
+                         f"(ratio 2 or 4)")
+    if torch.is_tensor(lr_ms) and lr_ms.is_cuda:
+        lr_ms, pan = lr_ms.detach().float().contiguous(), pan.detach().float().contiguous()
+        ms_exp = ops.upsample_poly23(lr_ms, ratio)
+        scene = on_device(ms_exp, pan, lr_ms)
+        if consistency is not None:
+            scene = consistency_refine(scene, lr_ms, sensor, ratio, out=scene, **consistency)
+        if not score:
+            return scene
+        if isinstance(score, str):
+            return scene, metrics.quality_hqnr(ms_exp, pan, scene, sensor, ratio)
+        return scene, metrics.quality_fullres(lr_ms, pan, scene)
+    if score:
+        raise ValueError(f"{name}: scores are made on the GPU; score host data with the host functions of metrics")
+    scene = on_host(metrics.upsample_poly23(lr_ms, ratio), pan, lr_ms)
+    if consistency is not None:
+        scene = consistency_refine(scene, lr_ms, sensor, ratio, **consistency)
+    return torch.from_numpy(scene) if torch.is_tensor(lr_ms) and not torch.is_tensor(scene) else scene
+
+
+@torch.no_grad()
 def classical_fuse(lr_ms, pan, sensor, ratio=4, mode="hpm", score=False, consistency=None):
     """From the raw pair to a classical fused scene, the MTF-GLP row of the tables: lr_ms [B, C, h, w] is interpolated with the
     23-tap polynomial kernel into ms_exp and fused with pan [B, 1, ratio * h, ratio * w] by ``mtf_glp`` in ``mode`` ("glp",
@@ -305,32 +339,31 @@ def classical_fuse(lr_ms, pan, sensor, ratio=4, mode="hpm", score=False, consist
     ``score=True`` returns (scene, ``metrics.quality_fullres(lr_ms, pan, scene)``), ``score="hqnr"`` returns (scene,
     ``metrics.quality_hqnr(ms_exp, pan, scene, sensor, ratio)``) with the ms_exp that was already made, and
     ``consistency={"iters": n, "relax": w}`` refines the scene with ``consistency_refine`` against lr_ms first.  Scores exist on
-    the device only (ValueError for host data).  Not differentiable."""
+    the device only (ValueError for host data).  Not differentiable.  The component-substitution methods are ``cs_fuse``."""
     from . import metrics
     if score not in (False, True, "hqnr"):
         raise ValueError(f"classical_fuse: score={score!r} (False, True or 'hqnr')")
     if mode not in metrics.GLP_MODES:
         raise ValueError(f"classical_fuse: mode={mode!r} (one of {metrics.GLP_MODES})")
-    if consistency is not None and (not isinstance(consistency, dict) or set(consistency) - {"iters", "relax"}):
-        raise ValueError(f"classical_fuse: consistency={consistency!r} (None or a dict with 'iters' and 'relax')")
-    if ratio not in (2, 4) or len(lr_ms.shape) != 4 or len(pan.shape) != 4 or pan.shape[0] != lr_ms.shape[0] or pan.shape[1] != 1 or \
-            tuple(pan.shape[2:]) != (ratio * lr_ms.shape[2], ratio * lr_ms.shape[3]):
-        raise ValueError(f"classical_fuse: pan {tuple(pan.shape)} is not [B, 1, {ratio} h, {ratio} w] of lr_ms {tuple(lr_ms.shape)} "
-                         f"(ratio 2 or 4)")
-    if torch.is_tensor(lr_ms) and lr_ms.is_cuda:
-        lr_ms, pan = lr_ms.detach().float().contiguous(), pan.detach().float().contiguous()
-        ms_exp = ops.upsample_poly23(lr_ms, ratio)
-        scene = ops.mtf_glp(ms_exp, pan, sensor, ratio, mode)
-        if consistency is not None:
-            scene = consistency_refine(scene, lr_ms, sensor, ratio, out=scene, **consistency)
-        if not score:
-            return scene
-        if isinstance(score, str):
-            return scene, metrics.quality_hqnr(ms_exp, pan, scene, sensor, ratio)
-        return scene, metrics.quality_fullres(lr_ms, pan, scene)
-    if score:
-        raise ValueError("classical_fuse: scores are made on the GPU; score host data with the host functions of metrics")
-    scene = metrics.mtf_glp(metrics.upsample_poly23(lr_ms, ratio), pan, sensor, ratio, mode)
-    if consistency is not None:
-        scene = consistency_refine(scene, lr_ms, sensor, ratio, **consistency)
-    return torch.from_numpy(scene) if torch.is_tensor(lr_ms) and not torch.is_tensor(scene) else scene
+    return _classical("classical_fuse", lambda ms_exp, p, lr: ops.mtf_glp(ms_exp, p, sensor, ratio, mode),
+                      lambda ms_exp, p, lr: metrics.mtf_glp(ms_exp, p, sensor, ratio, mode), lr_ms, pan, sensor, ratio, score,
+                      consistency)
+
+
+@torch.no_grad()
+def cs_fuse(lr_ms, pan, sensor=None, ratio=4, method="gsa", score=False, consistency=None):
+    """The sibling of ``classical_fuse`` for the component-substitution row of the tables: lr_ms [B, C, h, w] is interpolated
+    with the 23-tap polynomial kernel into ms_exp and fused with pan [B, 1, ratio * h, ratio * w] by ``cs_fuse`` with ``method``
+    "gs", "gsa" or "brovey" (definition: ``metrics.cs_fuse``); "gsa" takes lr_ms itself as its reduced-scale MS.  ``sensor`` is
+    needed by "gsa", by ``consistency`` and by ``score="hqnr"``.  Device tensors go through ``ops.cs_fuse``, host tensors and
+    arrays through the float64 definition; ``score`` and ``consistency`` are ``classical_fuse``'s.  Not differentiable."""
+    from . import metrics
+    if score not in (False, True, "hqnr"):
+        raise ValueError(f"cs_fuse: score={score!r} (False, True or 'hqnr')")
+    if method not in metrics.CS_METHODS:
+        raise ValueError(f"cs_fuse: method={method!r} (one of {metrics.CS_METHODS})")
+    if method == "gsa" and sensor is None:
+        raise ValueError("cs_fuse: method 'gsa' needs the sensor whose PAN gain shapes the reduced-scale PAN")
+    return _classical("cs_fuse", lambda ms_exp, p, lr: ops.cs_fuse(ms_exp, p, sensor, ratio, method, lr_ms=lr),
+                      lambda ms_exp, p, lr: metrics.cs_fuse(ms_exp, p, sensor, ratio, method, lr_ms=lr), lr_ms, pan, sensor, ratio,
+                      score, consistency)

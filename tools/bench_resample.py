@@ -27,7 +27,12 @@ same way.
 bank (`ops.fir_decimate_bank`) against `ops.fir_decimate` on the expanded PAN with the `expand().contiguous()` inside the timing;
 `ops.glp_moments` + `ops.glp_inject` against the same arithmetic composed from torch operators (float64 statistics, float32
 injection); `ops.mtf_glp` whole.  The elementwise kernels are printed with the bytes they move and their share of a
-device-to-device copy of as many bytes, timed in the same rounds.  Captured and timed as `--leg mtf`."""
+device-to-device copy of as many bytes, timed in the same rounds.  Captured and timed as `--leg mtf`.
+
+`--leg cs`: the component-substitution baselines at the same two sizes: `ops.plane_moments` (the fp64 matrix-instruction Gram
+kernel) beside a copy that moves the bytes of its C + 1 planes, beside `ops.glp_moments` and its own copy, and against the torch
+composition (cast to fp64, centre, `X @ X.T`); `ops.cs_inject` beside a copy that moves its 2 C + 1 planes; `ops.cs_fuse` whole for
+each method against the same chain composed from torch operators.  Captured and timed as `--leg mtf`."""
 import argparse
 import os
 import statistics
@@ -231,9 +236,107 @@ def glp_leg(args):
               f"torch / (moments + inject) {med[n[7]] / (med[n[2]] + med[n[4]]):6.1f}", flush=True)
 
 
+def cs_leg(args):
+    """`--leg cs`: see the module's docstring."""
+    from tmdiff_amd import metrics
+    ratio = 4
+    cases = []          # (name, call, bytes moved or 0)
+    for sensor, (b, c, h) in (("WV3", (1, 8, 1024)), ("QB", (1, 4, 2048))):
+        shape = [b, c, h, h]
+        ms, pan = 0.1 + 0.8 * torch.rand(b, c, h, h, device="cuda"), 0.1 + 0.8 * torch.rand(b, 1, h, h, device="cuda")
+        pan = (0.5 * pan + 0.5 * ms.mean(1, keepdim=True)).contiguous()
+        lp = 0.1 + 0.8 * torch.rand(b, c, h, h, device="cuda")
+        buf, out = ops.cs_fuse_buffers(b, c, h, h, "cuda", ratio), torch.empty_like(ms)
+        gbuf = ops.mtf_glp_buffers(b, c, h, h, "cuda", ratio)
+        full = ops.plane_moments(ms, pan, out=buf["full"], workspace=buf["ws"])
+        coef = ops.cs_coeffs(full, None, "gs").clone()
+        gain = metrics.mtf_gains(sensor, c)[1]
+        ops.mtf_degrade(pan, gain, ratio, out=buf["pan_low"])                       # warm: the tap table is cached
+
+        def moments64(x, p):
+            """[B, C + 1, C + 2] from torch operators: cast to fp64, centre, X @ X.T."""
+            x64 = torch.cat([x, p], 1).double().flatten(2)
+            mean = x64.mean(2, keepdim=True)
+            d = x64 - mean
+            return torch.cat([d @ d.transpose(1, 2) / d.shape[2], mean], 2)
+
+        def inject64(ms, pan, alpha, g, a, mean_i, mean_p, method, out):
+            m64, p64 = ms.double(), pan.double()
+            inten = (alpha[:, :, None, None] * m64).sum(1, keepdim=True)
+            pi = a * (p64 - mean_p) + mean_i
+            return out.copy_(m64 * pi / (inten + 2.0 ** -52) if method == "brovey" else m64 + g[:, :, None, None] * (pi - inten))
+
+        def composed(method, ms=ms, pan=pan, out=out, c=c, gain=gain, buf=buf):
+            mo = moments64(ms, pan)
+            if method == "gsa":
+                low = moments64(ms[..., ratio // 2::ratio, ratio // 2::ratio], ops.mtf_degrade(pan, gain, ratio, out=buf["pan_low"]))
+                alpha = torch.linalg.solve(low[:, :c, :c], low[:, :c, c])     # not capturable: this row is timed eagerly
+            else:
+                alpha = torch.full((ms.shape[0], c), 1.0 / c, device=ms.device, dtype=torch.float64)
+            sa = (mo[:, :c, :c] @ alpha[:, :, None])[:, :, 0]
+            var_i = (alpha * sa).sum(1)
+            mean_i = (alpha * mo[:, :c, c + 1]).sum(1)
+            return inject64(ms, pan, alpha, sa / var_i[:, None], (var_i / mo[:, c, c]).sqrt()[:, None, None, None],
+                            mean_i[:, None, None, None], mo[:, c, c + 1][:, None, None, None], method, out)
+
+        err_m = float((moments64(ms, pan) - full).abs().max())
+        errs = []
+        for method in metrics.CS_METHODS:
+            ref = composed(method).clone()
+            errs.append(float((ops.cs_fuse(ms, pan, sensor, ratio, method, out=out, buffers=buf) - ref).abs().max()))
+        print(f"{sensor} {shape}: max |plane_moments - torch composition| = {err_m:.3e}; max |cs_fuse - torch composition| = "
+              + " / ".join(f"{e:.3e}" for e in errs) + " (gs / gsa / brovey)", flush=True)
+        plane = 4 * b * h * h
+        src1, dst1 = torch.empty((c + 1) * plane // 8, device="cuda"), torch.empty((c + 1) * plane // 8, device="cuda")
+        src2, dst2 = torch.empty((2 * c + 1) * plane // 8, device="cuda"), torch.empty((2 * c + 1) * plane // 8, device="cuda")
+        cases += [
+            (f"plane_moments                {sensor} {shape}", lambda ms=ms, pan=pan, buf=buf: ops.plane_moments(ms, pan, out=buf["full"], workspace=buf["ws"]), (c + 1) * plane),
+            (f"copy moving (C + 1) planes   {sensor} {shape}", lambda s=src1, d=dst1: d.copy_(s), (c + 1) * plane),
+            (f"glp_moments                  {sensor} {shape}", lambda ms=ms, pan=pan, lp=lp, g=gbuf: ops.glp_moments(ms, pan, lp, out=g["moments"], workspace=g["ws"]), (2 * c + 1) * plane),
+            (f"copy moving (2 C + 1) planes {sensor} {shape}", lambda s=src2, d=dst2: d.copy_(s), (2 * c + 1) * plane),
+            (f"torch fp64 X @ X.T           {sensor} {shape}", lambda ms=ms, pan=pan: moments64(ms, pan), 0),
+            (f"cs_inject gsa                {sensor} {shape}", lambda ms=ms, pan=pan, coef=coef, out=out: ops.cs_inject(ms, pan, coef, "gsa", out=out), (2 * c + 1) * plane),
+            (f"cs_inject brovey             {sensor} {shape}", lambda ms=ms, pan=pan, coef=coef, out=out: ops.cs_inject(ms, pan, coef, "brovey", out=out), (2 * c + 1) * plane),
+            (f"copy moving (2 C + 1) planes (again) {sensor} {shape}", lambda s=src2, d=dst2: d.copy_(s), (2 * c + 1) * plane),
+            (f"cs_coeffs gsa                {sensor} {shape}", lambda full=full, buf=buf: ops.cs_coeffs(full, full, "gsa", out=buf["coef"]), 0),
+        ]
+        for method in metrics.CS_METHODS:
+            cases += [
+                (f"cs_fuse {method:6s} (whole)       {sensor} {shape}", lambda ms=ms, pan=pan, s=sensor, m=method, out=out, buf=buf: ops.cs_fuse(ms, pan, s, ratio, m, out=out, buffers=buf), 0),
+                (f"torch composition {method:6s}{' (eager)' if method == 'gsa' else '':8s} {sensor} {shape}", lambda m=method, f=composed: f(m), -1 if method == "gsa" else 0),
+            ]
+    class Eager:                # a case that cannot be captured: the same number of calls, launched one by one
+        def __init__(self, fn):
+            self.fn = fn
+
+        def replay(self):
+            for _ in range(args.graph_calls):
+                self.fn()
+
+    graphs = [Eager(fn) if nbytes < 0 else captured(fn, args.graph_calls) for _, fn, nbytes in cases]
+    times = [[] for _ in cases]
+    for _ in range(args.rounds):
+        for graph, t in zip(graphs, times):
+            time_us(graph.replay, 1)
+            t.append(time_us(graph.replay, 1) / args.graph_calls)
+    print(f"{'case':56s} {'us per call (min..max)':>30s} {'MiB moved':>10s} {'GB/s':>8s}")
+    med = {}
+    for (name, _, nbytes), t in zip(cases, times):
+        m = med[name] = statistics.median(t)
+        rate = f"{nbytes / 2 ** 20:10.1f} {nbytes / m / 1e3:8.1f}" if nbytes > 0 else ""
+        print(f"{name:56s} {m:10.2f} ({min(t):8.2f}..{max(t):8.2f}) {rate}", flush=True)
+    names = [n for n, _, _ in cases]
+    for i in range(0, len(names), 15):
+        n = names[i:i + 15]
+        print(f"{n[0][29:]:24s} plane_moments: of its bytes copied {med[n[1]] / med[n[0]]:5.2f} (glp_moments: {med[n[3]] / med[n[2]]:5.2f})   "
+              f"torch X @ X.T / plane_moments {med[n[4]] / med[n[0]]:6.1f}   cs_inject: of copy, gsa {med[n[7]] / med[n[5]]:5.2f} "
+              f"brovey {med[n[7]] / med[n[6]]:5.2f}   torch / cs_fuse: gs {med[n[10]] / med[n[9]]:5.1f} gsa {med[n[12]] / med[n[11]]:5.1f} "
+              f"brovey {med[n[14]] / med[n[13]]:5.1f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("resample", "mtf", "adjoint", "glp"), default="resample")
+    ap.add_argument("--leg", choices=("resample", "mtf", "adjoint", "glp", "cs"), default="resample")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--graph-calls", type=int, default=10, help="--leg mtf / adjoint: calls captured into each graph")
@@ -249,6 +352,8 @@ def main():
         return adjoint_leg(args)
     if args.leg == "glp":
         return glp_leg(args)
+    if args.leg == "cs":
+        return cs_leg(args)
 
     cases = []          # (name, kernel call, bytes, copy call, bytes the copy moves)
 
