@@ -868,6 +868,34 @@ int tmdiff_cs_inject(const float* ms_exp, const float* pan, const double* coef, 
                      int32_t W, int32_t mode, tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * BDSD pansharpening: band-dependent spatial detail (csrc/bdsd.hip; host definitions: tmdiff_amd/metrics.py, bdsd_moments /
+ * bdsd_coeffs / bdsd_inject / bdsd).  Dense tensors; nothing is allocated or synchronised, no atomics, the same bits on every
+ * run and on a graph replay.  An H x W image is cut into non-overlapping square blocks of side `bs` / `block` (0: the whole image
+ * is one block), block (iy, ix) at index iy * (W / side) + ix.
+ *  bdsd_gram:  low_lp, low_ms [B, C, H, W], low_pan [B, 1, H, W] fp32 (the reduced scale) -> out, float64 [B, blocks, C + 1,
+ *              2 C + 1] = N | R per block: N = Hm' Hm with Hm = [low_lp_0 .. low_lp_{C-1}, low_pan] over the block's pixels
+ *              (exactly symmetric), R = Hm' D with D_c = low_ms_c - low_lp_c formed in fp64.  Raw sums.  One pass with two
+ *              v_mfma_f64_16x16x4_f64 per four pixels of each plane that share the A operand; partial sums per workgroup in
+ *              `workspace` (8-byte aligned, tmdiff_bdsd_gram_workspace_bytes), a finalize launch adds them in index order.  The
+ *              summation order is written in the source's header.  Limits: B >= 0, 1 <= C <= 15, H, W >= 1, B * C * H * W <=
+ *              2^31 - 1, bs 0 or a divisor of H and W; otherwise TMDIFF_E_UNSUPPORTED and a workspace size of 0.
+ *  bdsd_solve: moments, float64 [systems, C + 1, 2 C + 1] -> out, float64 [systems, C + 1, C]: column c solves N gamma_c = R_c by
+ *              a root-free unpivoted Cholesky factorisation (L D L') in one lane per system; a pivot <= 0 gives NaN in that
+ *              system.
+ *  bdsd_inject: out [B, C, H, W] from ms_exp, pan [B, 1, H, W] and the device-resident weights `gamma` of bdsd_solve, float64
+ *              [B, blocks, C + 1, C]: F_c = M_c + sum_k gamma[k][c] M_k + gamma[C][c] P with the weights of the pixel's block,
+ *              one fp64 chain of fused multiply-adds in that order, rounded to fp32 once.  out may be ms_exp; it must not
+ *              overlap pan or gamma.  Limits: bdsd_gram's, with `block` the full-scale side.
+ *              (Added within version 6.)
+ * ------------------------------------------------------------------------------------ */
+size_t tmdiff_bdsd_gram_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t bs);
+int tmdiff_bdsd_gram(const float* low_lp, const float* low_pan, const float* low_ms, int32_t B, int32_t C, int32_t H, int32_t W,
+                     int32_t bs, double* out, void* workspace, size_t workspace_bytes, tmdiff_stream_t stream);
+int tmdiff_bdsd_solve(const double* moments, double* out, int32_t systems, int32_t C, tmdiff_stream_t stream);
+int tmdiff_bdsd_inject(const float* ms_exp, const float* pan, const double* gamma, float* out, int32_t B, int32_t C, int32_t H,
+                       int32_t W, int32_t block, tmdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Standalone attention operators of core/Attention.py (imported by nothing in the reference; built because the
  * north star names them).  All fp32.
  *  attn_fwd : out = softmax(q k^T * scale [key mask]) v per (batch, head); fp32 MFMA, online softmax.

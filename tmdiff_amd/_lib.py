@@ -238,6 +238,12 @@ SIGNATURES.update({
     "tmdiff_plane_gram": (C.c_int, [vp, vp] + [C.c_int32] * 4 + [vp, vp, C.c_size_t, vp]),
     "tmdiff_cs_coeffs": (C.c_int, [vp, vp, vp] + [C.c_int32] * 3 + [vp]),
     "tmdiff_cs_inject": (C.c_int, [vp] * 4 + [C.c_int32] * 5 + [vp]),
+    # BDSD: low_lp, low_pan, low_ms | B, C, H, W, bs | out, workspace, bytes;  moments, out | systems, C;
+    # ms_exp, pan, gamma, out | B, C, H, W, block
+    "tmdiff_bdsd_gram_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "tmdiff_bdsd_gram": (C.c_int, [vp, vp, vp] + [C.c_int32] * 5 + [vp, vp, C.c_size_t, vp]),
+    "tmdiff_bdsd_solve": (C.c_int, [vp, vp] + [C.c_int32] * 2 + [vp]),
+    "tmdiff_bdsd_inject": (C.c_int, [vp] * 4 + [C.c_int32] * 5 + [vp]),
 })
 
 

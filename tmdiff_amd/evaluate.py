@@ -14,6 +14,8 @@ from . import metrics
 IMG_SCALE = {"GF2": 1023.0}          # every other sensor: 2047 (ref :134)
 BASELINES = ("exp", "glp", "cbd", "hpm")   # val_dataset(baselines=...): the interpolated MS and the three modes of metrics.mtf_glp
 CS_BASELINES = ("cs-gs", "cs-gsa", "cs-brovey")   # ... and "cs-" + the methods of metrics.cs_fuse (component substitution)
+BDSD_BASELINES = ("bdsd", "bdsd-local")    # ... and metrics.bdsd with one set of weights per image / per 128 x 128 block
+BDSD_LOCAL_BLOCK = 128
 
 
 def to_hwc01(img, min_max=(0.0, 1.0)):
@@ -68,10 +70,13 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
     resolved as for ``protocol="hqnr"``.  ``baselines=()`` changes nothing: the same keys, values and launches.
     The names of ``CS_BASELINES`` ("cs-gs", "cs-gsa", "cs-brovey") are accepted beside them: the same visuals fused by
     ``ops.cs_fuse`` with that method (``metrics.cs_fuse``; buffers made once per shape), scored and reported the same way
-    (``"<metric>_<dataset>@cs-gsa"``)."""
+    (``"<metric>_<dataset>@cs-gsa"``).  So are the names of ``BDSD_BASELINES``: "bdsd", ``ops.bdsd`` with one set of weights per
+    image, and "bdsd-local", with weights per 128 x 128 block (``"<metric>_<dataset>@bdsd"``); "bdsd-local" raises ValueError
+    naming the shape when the visuals' extents are not multiples of 128."""
     baselines = tuple(baselines)
-    if [b for b in baselines if b not in BASELINES + CS_BASELINES] or len(set(baselines)) != len(baselines):
-        raise ValueError(f"val_dataset: baselines={baselines!r} (distinct names out of {BASELINES + CS_BASELINES})")
+    known = BASELINES + CS_BASELINES + BDSD_BASELINES
+    if [b for b in baselines if b not in known] or len(set(baselines)) != len(baselines):
+        raise ValueError(f"val_dataset: baselines={baselines!r} (distinct names out of {known})")
     if baselines and not (device_metrics or full_resolution):
         raise ValueError("val_dataset(baselines=...) scores on the GPU: it needs device_metrics=True or full_resolution=True")
     if protocol not in ("qnr", "hqnr"):
@@ -94,7 +99,7 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
     n = 0
     dev_sum, dev_ws, q2n_ws = None, {}, {}
     full_sum, full_ws = None, {}
-    base_sum, glp_ws, cs_ws = {}, {}, {}
+    base_sum, glp_ws, cs_ws, bdsd_ws = {}, {}, {}, {}
 
     def score_baselines(ms_d, pan_d, score_row):
         """Adds score_row(fused) of every baseline to its running sum; ms_d, pan_d: the item's MS and PAN in [0, 1]."""
@@ -106,6 +111,15 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
                     cs_ws[ms_d.shape] = (ops.cs_fuse_buffers(*ms_d.shape, ms_d.device), torch.empty_like(ms_d))
                 buf, out = cs_ws[ms_d.shape]
                 fused = ops.cs_fuse(ms_d, pan_d, sensor, 4, name[3:], out=out, buffers=buf)
+            elif name in BDSD_BASELINES:
+                block = BDSD_LOCAL_BLOCK if name == "bdsd-local" else None
+                if block and (ms_d.shape[2] % block or ms_d.shape[3] % block):
+                    raise ValueError(f"val_dataset(baselines=('bdsd-local',)): the visuals are {tuple(ms_d.shape)}; H and W must be "
+                                     f"multiples of the block side {block}")
+                if (ms_d.shape, block) not in bdsd_ws:
+                    bdsd_ws[ms_d.shape, block] = (ops.bdsd_buffers(*ms_d.shape, ms_d.device, 4, block), torch.empty_like(ms_d))
+                buf, out = bdsd_ws[ms_d.shape, block]
+                fused = ops.bdsd(ms_d, pan_d, sensor, 4, block, out=out, buffers=buf)
             elif name != "exp":
                 if ms_d.shape not in glp_ws:
                     glp_ws[ms_d.shape] = (ops.mtf_glp_buffers(*ms_d.shape, ms_d.device), torch.empty_like(ms_d))

@@ -2022,6 +2022,150 @@ def cs_fuse(ms_exp, pan, sensor=None, ratio=4, method="gsa", lr_ms=None, out=Non
     return cs_inject(ms_exp, pan, cs_coeffs(full, low, method, out=buf["coef"]), method, out=out)
 
 
+# ---- BDSD: block-wise regression and injection (csrc/bdsd.hip; definitions: tmdiff_amd/metrics.py) ---------------------------------
+_BDSD_LIMITS = ("contiguous float32 tensors on the GPU, ms [B, C, H, W], pan [B, 1, H, W]; 1 <= C <= 15; ratio 2 or 4, H and W "
+                "multiples of it; block None or a multiple of the ratio that divides H and W; fewer than 2^31 elements")
+
+
+def _bdsd_dense(name, arg, t, shape=None):
+    """``t`` must be a contiguous float32 tensor on the GPU, of ``shape`` when that is given."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        raise ValueError(f"{name}: {arg} must be a contiguous float32 tensor on the GPU ({_BDSD_LIMITS})")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: {arg} is {tuple(t.shape)}, need {tuple(shape)} ({_BDSD_LIMITS})")
+    return t
+
+
+def _bdsd_images(name, ms, pan, ratio=None, block=None):
+    """(B, C, H, W, blocks down, blocks across) of a BDSD call after the checks on its images; ``block`` is a side at their scale."""
+    _bdsd_dense(name, "ms", ms)
+    if ms.dim() != 4:
+        raise ValueError(f"{name}: ms is {tuple(ms.shape)}, need [B, C, H, W] ({_BDSD_LIMITS})")
+    b, c, h, w = ms.shape
+    extents = _bdsd_extents(name, b, c, h, w, ratio, block)
+    _bdsd_dense(name, "pan", pan, (b, 1, h, w))
+    return extents
+
+
+def _bdsd_extents(name, b, c, h, w, ratio=None, block=None):
+    """(B, C, H, W, blocks down, blocks across) after the checks on the extents."""
+    b, c, h, w = int(b), int(c), int(h), int(w)
+    if not 1 <= c <= 15 or min(b, h, w) < 1 or b * c * h * w > 2 ** 31 - 1:
+        raise ValueError(f"{name}: B={b} C={c} H={h} W={w} is not supported ({_BDSD_LIMITS})")
+    if ratio is not None and (ratio not in (2, 4) or h % ratio or w % ratio):
+        raise ValueError(f"{name}: H={h} W={w} ratio={ratio} is not supported ({_BDSD_LIMITS})")
+    if block is not None and (isinstance(block, bool) or int(block) != block or block < 1 or block % (ratio or 1) or h % block or w % block):
+        raise ValueError(f"{name}: block={block!r} for H={h} W={w} ratio={ratio or 1} is not supported ({_BDSD_LIMITS})")
+    return b, c, h, w, (1 if block is None else h // int(block)), (1 if block is None else w // int(block))
+
+
+def bdsd_moments_workspace(b, c, h, w, device, bs=None):
+    """A workspace ``bdsd_moments`` accepts for [b, c, h, w] reduced-scale images in blocks of side ``bs`` (reusable; captured
+    calls must keep it alive)."""
+    b, c, h, w, _, _ = _bdsd_extents("bdsd_moments", b, c, h, w, None, bs)
+    return torch.empty(max(1, lib.tmdiff_bdsd_gram_workspace_bytes(b, c, h, w, int(bs or 0)) // 8), device=device, dtype=torch.float64)
+
+
+def bdsd_moments(low_lp, low_pan, low_ms, bs=None, out=None, workspace=None):
+    """The normal equations of BDSD per block (definition: ``metrics.bdsd_moments``): float64 [B, nby, nbx, C + 1, 2 C + 1] = N | R
+    from the reduced-scale images low_lp, low_ms [B, C, h, w] and low_pan [B, 1, h, w], N = Hm' Hm over the regressors (the C
+    low-pass bands, then the PAN) and R = Hm' D over the targets D_c = low_ms_c - low_lp_c, as device values from one pass: both
+    products are accumulated with the fp64 matrix instruction.  ``bs``: the side of the blocks at this scale, None for the whole
+    image.  Sums in fp64 in one fixed order, no atomics: the same bits on every run; N is exactly symmetric.  With ``out=`` and
+    ``workspace=`` nothing is allocated or synchronised.  Not differentiable: the inputs are detached."""
+    b, c, h, w, nby, nbx = _bdsd_images("bdsd_moments", low_lp, low_pan, None, bs)
+    _bdsd_dense("bdsd_moments", "low_ms", low_ms, (b, c, h, w))
+    y = _f64("bdsd_moments", "out", out, (b, nby, nbx, c + 1, 2 * c + 1), low_lp.device)
+    ws, nbytes = _lent("bdsd_moments", workspace, lib.tmdiff_bdsd_gram_workspace_bytes(b, c, h, w, int(bs or 0)),
+                       lambda: bdsd_moments_workspace(b, c, h, w, low_lp.device, bs))
+    check(lib.tmdiff_bdsd_gram(low_lp.detach().data_ptr(), low_pan.detach().data_ptr(), low_ms.detach().data_ptr(), b, c, h, w,
+                               int(bs or 0), y.data_ptr(), ws.data_ptr(), nbytes, stream_ptr()), "bdsd_moments")
+    return y
+
+
+def bdsd_coeffs(moments, out=None):
+    """The weights of BDSD (definition: ``metrics.bdsd_coeffs``): float64 [B, nby, nbx, C + 1, C] from ``moments``, the float64
+    [B, nby, nbx, C + 1, 2 C + 1] device tensor of ``bdsd_moments``; column c solves N gamma_c = R[:, c] by a root-free unpivoted
+    Cholesky factorisation on the device, one block per wave; a singular block gets NaN, the others are left alone.  Nothing is
+    read on the host; with ``out=`` nothing is allocated."""
+    if not (torch.is_tensor(moments) and moments.dim() == 5 and moments.shape[4] == 2 * moments.shape[3] - 1 and 2 <= moments.shape[3] <= 16):
+        raise ValueError("bdsd_coeffs: moments must be a float64 [B, nby, nbx, C + 1, 2 C + 1] tensor on the GPU, 1 <= C <= 15")
+    b, nby, nbx, k = moments.shape[:4]
+    mo = _f64("bdsd_coeffs", "moments", moments, tuple(moments.shape), None)
+    y = _f64("bdsd_coeffs", "out", out, (b, nby, nbx, k, k - 1), mo.device)
+    if _overlaps(y, mo):
+        raise ValueError("bdsd_coeffs: out overlaps moments")
+    if b * nby * nbx > 2 ** 31 - 1:
+        raise ValueError(f"bdsd_coeffs: {b * nby * nbx} blocks (fewer than 2^31)")
+    check(lib.tmdiff_bdsd_solve(mo.detach().data_ptr(), y.data_ptr(), b * nby * nbx, k - 1, stream_ptr()), "bdsd_coeffs")
+    return y
+
+
+def bdsd_inject(ms_exp, pan, gamma, block=None, out=None):
+    """The injection of BDSD (definition: ``metrics.bdsd_inject``): the fused [B, C, H, W] from ms_exp, pan and ``gamma``, the
+    float64 [B, nby, nbx, C + 1, C] device tensor of ``bdsd_coeffs``: F_c = M_c + sum_k gamma[k, c] M_k + gamma[C, c] P with the
+    weights of the block the pixel lies in (``block``: the full-scale side, None for one block), evaluated in fp64 and rounded to
+    fp32 once.  ``out`` may be ms_exp itself (in place); it must not overlap pan or gamma.  With ``out=`` nothing is allocated or
+    synchronised.  Not differentiable: the inputs are detached."""
+    b, c, h, w, nby, nbx = _bdsd_images("bdsd_inject", ms_exp, pan, None, block)
+    g = _f64("bdsd_inject", "gamma", gamma, (b, nby, nbx, c + 1, c), ms_exp.device)
+    y = _bdsd_dense("bdsd_inject", "out", out if out is not None else torch.empty_like(ms_exp), (b, c, h, w))
+    for other, what in ((pan, "pan"), (g, "gamma")):
+        if _overlaps(y, other):
+            raise ValueError(f"bdsd_inject: out overlaps {what}")
+    if y.data_ptr() != ms_exp.data_ptr() and _overlaps(y, ms_exp):
+        raise ValueError("bdsd_inject: out overlaps ms_exp without being ms_exp")
+    check(lib.tmdiff_bdsd_inject(ms_exp.detach().data_ptr(), pan.detach().data_ptr(), g.detach().data_ptr(), y.data_ptr(), b, c, h, w,
+                                 int(block or 0), stream_ptr()), "bdsd_inject")
+    return y
+
+
+def bdsd_buffers(b, c, h, w, device, ratio=4, block=None):
+    """Every scratch tensor of ``bdsd`` for [b, c, h, w] images: with them and ``out=`` a call allocates nothing and can be
+    captured into a graph.  "ms_low", "lp_low", "pan_low": the reduced-scale MS, its low-pass and the reduced PAN; "moments",
+    "gamma": the float64 normal equations and weights per block; "ws": the workspace of ``bdsd_moments``."""
+    b, c, h, w, nby, nbx = _bdsd_extents("bdsd", b, c, h, w, ratio, block)
+    f32, f64 = dict(device=device, dtype=torch.float32), dict(device=device, dtype=torch.float64)
+    bs = None if block is None else int(block) // ratio
+    return {"shape": (b, c, h, w, ratio, block), "ms_low": torch.empty(b, c, h // ratio, w // ratio, **f32),
+            "lp_low": torch.empty(b, c, h // ratio, w // ratio, **f32), "pan_low": torch.empty(b, 1, h // ratio, w // ratio, **f32),
+            "moments": torch.empty(b, nby, nbx, c + 1, 2 * c + 1, **f64), "gamma": torch.empty(b, nby, nbx, c + 1, c, **f64),
+            "ws": bdsd_moments_workspace(b, c, h // ratio, w // ratio, device, bs)}
+
+
+def bdsd(ms_exp, pan, sensor, ratio=4, block=None, lr_ms=None, out=None, buffers=None):
+    """BDSD pansharpening on the device (definition: ``metrics.bdsd``): the fused [B, C, H, W] from ms_exp, the MS interpolated to
+    the PAN grid, and pan [B, 1, H, W].  The reduced scale is made by the existing filters in float32: the reduced MS is ``lr_ms``
+    [B, C, H / ratio, W / ratio], or with None the samples ms_exp[..., ratio // 2::ratio, ratio // 2::ratio] (the raw MS when ms_exp
+    came from ``upsample_poly23``); its low-pass is ``fir_decimate`` with the MS bands' MTF table at ratio 1; the reduced PAN is
+    ``mtf_degrade(pan, PAN gain of sensor, ratio)``.  ``bdsd_moments`` then leaves the normal equations of every block on the
+    device, ``bdsd_coeffs`` solves them there and ``bdsd_inject`` writes the result.  ``block``: the full-scale side of the blocks
+    that get weights of their own, a multiple of ``ratio`` that divides H and W; None fits one set to the whole image.
+    ``sensor``: a name or a pair (MS gains, PAN gain), as ``metrics.mtf_gains`` takes them.  ``out`` may be ms_exp.  With
+    ``buffers`` (``bdsd_buffers``) and ``out=`` nothing is allocated or synchronised; the tap tables are cached as ``mtf_degrade``
+    caches its own: call once before capturing into a graph.  Not differentiable: the inputs are detached."""
+    from . import metrics
+    b, c, h, w, _, _ = _bdsd_images("bdsd", ms_exp, pan, ratio, block)
+    ms_exp, pan = ms_exp.detach(), pan.detach()
+    if out is not None:
+        _bdsd_dense("bdsd", "out", out, (b, c, h, w))
+        if _overlaps(out, pan):
+            raise ValueError("bdsd: out overlaps pan")
+    buf = buffers if buffers is not None else bdsd_buffers(b, c, h, w, ms_exp.device, ratio, block)
+    if buf["shape"] != (b, c, h, w, ratio, block) or buf["moments"].device != ms_exp.device:
+        raise ValueError(f"bdsd: buffers made for {buf['shape']}, the call is {(b, c, h, w, ratio, block)}")
+    ms_gains, pan_gain = metrics.mtf_gains(sensor, c)
+    if lr_ms is None:
+        ms_low = buf["ms_low"]
+        ms_low.copy_(ms_exp[..., ratio // 2::ratio, ratio // 2::ratio])
+    else:
+        ms_low = _bdsd_dense("bdsd", "lr_ms", lr_ms, (b, c, h // ratio, w // ratio)).detach()
+    lp_low = fir_decimate(ms_low, _mtf_taps(ms_gains, ratio, ms_exp.device), 1, None, buf["lp_low"])
+    pan_low = mtf_degrade(pan, pan_gain, ratio, out=buf["pan_low"])
+    mo = bdsd_moments(lp_low, pan_low, ms_low, None if block is None else int(block) // ratio, out=buf["moments"], workspace=buf["ws"])
+    return bdsd_inject(ms_exp, pan, bdsd_coeffs(mo, out=buf["gamma"]), block, out=out)
+
+
 # ---- backward-side wrappers (finetune path) -----------------------------------------------------------
 
 

@@ -367,3 +367,21 @@ def cs_fuse(lr_ms, pan, sensor=None, ratio=4, method="gsa", score=False, consist
     return _classical("cs_fuse", lambda ms_exp, p, lr: ops.cs_fuse(ms_exp, p, sensor, ratio, method, lr_ms=lr),
                       lambda ms_exp, p, lr: metrics.cs_fuse(ms_exp, p, sensor, ratio, method, lr_ms=lr), lr_ms, pan, sensor, ratio,
                       score, consistency)
+
+
+@torch.no_grad()
+def bdsd_fuse(lr_ms, pan, sensor, ratio=4, block=None, score=False, consistency=None):
+    """The sibling of ``cs_fuse`` for the BDSD row of the tables: lr_ms [B, C, h, w] is interpolated with the 23-tap polynomial
+    kernel into ms_exp and fused with pan [B, 1, ratio * h, ratio * w] by ``bdsd`` (definition: ``metrics.bdsd``), which takes lr_ms
+    itself as its reduced-scale MS.  ``block``: the full-scale side of the blocks that get weights of their own (a multiple of
+    ``ratio`` that divides both extents), None for one set of weights per image.  ``sensor`` is always needed: its gains shape the
+    reduced scale.  Device tensors go through ``ops.bdsd``, host tensors and arrays through the float64 definition; ``score`` and
+    ``consistency`` are ``classical_fuse``'s.  Not differentiable."""
+    from . import metrics
+    if score not in (False, True, "hqnr"):
+        raise ValueError(f"bdsd_fuse: score={score!r} (False, True or 'hqnr')")
+    if sensor is None:
+        raise ValueError("bdsd_fuse: needs the sensor whose MTF gains shape the reduced-scale images")
+    return _classical("bdsd_fuse", lambda ms_exp, p, lr: ops.bdsd(ms_exp, p, sensor, ratio, block, lr_ms=lr),
+                      lambda ms_exp, p, lr: metrics.bdsd(ms_exp, p, sensor, ratio, block, lr_ms=lr), lr_ms, pan, sensor, ratio, score,
+                      consistency)

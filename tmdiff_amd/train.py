@@ -32,7 +32,8 @@ def validation_options(dataset_opt):
     """The keyword arguments of ``evaluate.val_dataset`` a validation dataset's options ask for: ``full_resolution`` true is QNR,
     "hqnr" is HQNR with the optional ``sensor``; absent or false is the scoring against ground truth.  ``baselines``, beside it: a
     list out of ``evaluate.BASELINES`` ("exp", "glp", "cbd", "hpm") and ``evaluate.CS_BASELINES`` ("cs-gs", "cs-gsa", "cs-brovey":
-    component substitution, ``metrics.cs_fuse``) scored with the same set on the same files, with the optional ``sensor``; it
+    component substitution, ``metrics.cs_fuse``) and ``evaluate.BDSD_BASELINES`` ("bdsd", "bdsd-local": ``metrics.bdsd`` with weights
+    per image or per 128 x 128 block) scored with the same set on the same files, with the optional ``sensor``; it
     needs ``full_resolution`` (the scoring against ground truth here runs on the host)."""
     full = dataset_opt.get("full_resolution")
     base = dataset_opt.get("baselines")

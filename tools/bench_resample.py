@@ -32,7 +32,13 @@ device-to-device copy of as many bytes, timed in the same rounds.  Captured and 
 `--leg cs`: the component-substitution baselines at the same two sizes: `ops.plane_moments` (the fp64 matrix-instruction Gram
 kernel) beside a copy that moves the bytes of its C + 1 planes, beside `ops.glp_moments` and its own copy, and against the torch
 composition (cast to fp64, centre, `X @ X.T`); `ops.cs_inject` beside a copy that moves its 2 C + 1 planes; `ops.cs_fuse` whole for
-each method against the same chain composed from torch operators.  Captured and timed as `--leg mtf`."""
+each method against the same chain composed from torch operators.  Captured and timed as `--leg mtf`.
+
+`--leg bdsd`: BDSD at the same two sizes, with one set of weights per image and with one per 128 x 128 block: the two filters of
+the reduced scale, `ops.bdsd_moments`, `ops.bdsd_coeffs`, `ops.bdsd_inject` beside a copy that moves its 2 C + 1 planes and beside
+`ops.cs_inject` at the same shape, and `ops.bdsd` whole against the chain composed from torch operators (the same two filters,
+then an fp64 `einsum` Gram, `torch.linalg.solve` and an `einsum` injection per block; launched eagerly, the solve cannot be
+captured).  Captured and timed as `--leg mtf`."""
 import argparse
 import os
 import statistics
@@ -334,9 +340,92 @@ def cs_leg(args):
               f"brovey {med[n[14]] / med[n[13]]:5.1f}", flush=True)
 
 
+def bdsd_leg(args):
+    """`--leg bdsd`: see the module's docstring."""
+    from tmdiff_amd import metrics
+    ratio = 4
+    cases = []          # (name, call, bytes moved, 0, or -1 for a case that is timed eagerly)
+    groups = []         # (title, names of: inject, its copy, cs_inject, whole, torch composition)
+    for sensor, (b, c, h) in (("WV3", (1, 8, 1024)), ("QB", (1, 4, 2048))):
+        shape = [b, c, h, h]
+        ms, pan = 0.1 + 0.8 * torch.rand(b, c, h, h, device="cuda"), 0.1 + 0.8 * torch.rand(b, 1, h, h, device="cuda")
+        pan = (0.5 * pan + 0.5 * ms.mean(1, keepdim=True)).contiguous()
+        out = torch.empty_like(ms)
+        ms_gains, pan_gain = metrics.mtf_gains(sensor, c)
+        taps = ops._mtf_taps(ms_gains, ratio, ms.device)
+        plane = 4 * b * h * h
+        src, dst = torch.empty((2 * c + 1) * plane // 8, device="cuda"), torch.empty((2 * c + 1) * plane // 8, device="cuda")
+        cs_buf = ops.cs_fuse_buffers(b, c, h, h, "cuda", ratio)
+        coef = ops.cs_coeffs(ops.plane_moments(ms, pan, out=cs_buf["full"], workspace=cs_buf["ws"]), None, "gs").clone()
+        for block in (None, 128):
+            buf = ops.bdsd_buffers(b, c, h, h, "cuda", ratio, block)
+            bs = None if block is None else block // ratio
+            tag = f"{sensor} {shape} block {block}"
+
+            def composed(ms=ms, pan=pan, out=out, buf=buf, taps=taps, gain=pan_gain, side=h if block is None else block, c=c):
+                """The chain from torch operators: the two filters are the project's, then fp64 einsum Gram, torch.linalg.solve
+                and an einsum injection per block."""
+                low = buf["ms_low"].copy_(ms[..., ratio // 2::ratio, ratio // 2::ratio])
+                lp = ops.fir_decimate(low, taps, 1, None, buf["lp_low"])
+                pl = ops.mtf_degrade(pan, gain, ratio, out=buf["pan_low"])
+
+                def tiles(x, s):
+                    n, k, hh, ww = x.shape
+                    return x.reshape(n, k, hh // s, s, ww // s, s).permute(0, 2, 4, 1, 3, 5)
+                hm = tiles(torch.cat([lp, pl], 1).double(), side // ratio).flatten(4)
+                d = tiles(low.double() - lp.double(), side // ratio).flatten(4)
+                gamma = torch.linalg.solve(torch.einsum("...in,...jn->...ij", hm, hm), torch.einsum("...in,...jn->...ij", hm, d))
+                m64 = ms.double()
+                f = torch.einsum("byxkc,byxkij->byxcij", gamma, tiles(torch.cat([m64, pan.double()], 1), side))
+                return out.copy_(m64 + f.permute(0, 3, 1, 4, 2, 5).reshape(m64.shape))
+
+            ref = composed().clone()
+            got = ops.bdsd(ms, pan, sensor, ratio, block, out=out, buffers=buf)
+            print(f"{tag}: max |bdsd - torch composition| = {float((got - ref).abs().max()):.3e}", flush=True)
+            mo, gamma, low = buf["moments"], buf["gamma"].clone(), buf["ms_low"]
+            names = [f"bdsd_inject                  {tag}", f"copy moving (2 C + 1) planes {tag}", f"cs_inject gsa                {tag}",
+                     f"bdsd (whole)                 {tag}", f"torch composition (eager)    {tag}"]
+            groups.append((tag, names))
+            cases += [
+                (f"fir_decimate MS x1           {tag}", lambda low=low, taps=taps, buf=buf: ops.fir_decimate(low, taps, 1, None, buf["lp_low"]), 0),
+                (f"mtf_degrade PAN              {tag}", lambda pan=pan, g=pan_gain, buf=buf: ops.mtf_degrade(pan, g, ratio, out=buf["pan_low"]), 0),
+                (f"bdsd_moments                 {tag}", lambda buf=buf, bs=bs: ops.bdsd_moments(buf["lp_low"], buf["pan_low"], buf["ms_low"], bs, out=buf["moments"], workspace=buf["ws"]), (2 * c + 1) * plane // ratio ** 2),
+                (f"bdsd_coeffs                  {tag}", lambda mo=mo, buf=buf: ops.bdsd_coeffs(mo, out=buf["gamma"]), 0),
+                (names[0], lambda ms=ms, pan=pan, g=gamma, block=block, out=out: ops.bdsd_inject(ms, pan, g, block, out=out), (2 * c + 1) * plane),
+                (names[1], lambda s=src, d=dst: d.copy_(s), (2 * c + 1) * plane),
+                (names[2], lambda ms=ms, pan=pan, coef=coef, out=out: ops.cs_inject(ms, pan, coef, "gsa", out=out), (2 * c + 1) * plane),
+                (names[3], lambda ms=ms, pan=pan, s=sensor, block=block, out=out, buf=buf: ops.bdsd(ms, pan, s, ratio, block, out=out, buffers=buf), 0),
+                (names[4], composed, -1),
+            ]
+
+    class Eager:                # a case that cannot be captured: the same number of calls, launched one by one
+        def __init__(self, fn):
+            self.fn = fn
+
+        def replay(self):
+            for _ in range(args.graph_calls):
+                self.fn()
+
+    graphs = [Eager(fn) if nbytes < 0 else captured(fn, args.graph_calls) for _, fn, nbytes in cases]
+    times = [[] for _ in cases]
+    for _ in range(args.rounds):
+        for graph, t in zip(graphs, times):
+            time_us(graph.replay, 1)
+            t.append(time_us(graph.replay, 1) / args.graph_calls)
+    print(f"{'case':68s} {'us per call (min..max)':>30s} {'MiB moved':>10s} {'GB/s':>8s}")
+    med = {}
+    for (name, _, nbytes), t in zip(cases, times):
+        m = med[name] = statistics.median(t)
+        rate = f"{nbytes / 2 ** 20:10.1f} {nbytes / m / 1e3:8.1f}" if nbytes > 0 else ""
+        print(f"{name:68s} {m:10.2f} ({min(t):8.2f}..{max(t):8.2f}) {rate}", flush=True)
+    for tag, n in groups:
+        print(f"{tag:36s} of copy: bdsd_inject {med[n[1]] / med[n[0]]:5.2f}, cs_inject gsa {med[n[1]] / med[n[2]]:5.2f}   "
+              f"torch composition / bdsd {med[n[4]] / med[n[3]]:6.1f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("resample", "mtf", "adjoint", "glp", "cs"), default="resample")
+    ap.add_argument("--leg", choices=("resample", "mtf", "adjoint", "glp", "cs", "bdsd"), default="resample")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--graph-calls", type=int, default=10, help="--leg mtf / adjoint: calls captured into each graph")
@@ -354,6 +443,8 @@ def main():
         return glp_leg(args)
     if args.leg == "cs":
         return cs_leg(args)
+    if args.leg == "bdsd":
+        return bdsd_leg(args)
 
     cases = []          # (name, kernel call, bytes, copy call, bytes the copy moves)
 
