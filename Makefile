@@ -9,7 +9,7 @@ HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -Wal
 
 all: $(LIB)
 
-build/%.o: $(CSRC)/% include/tmdiff_hip.h $(CSRC)/common.h $(CSRC)/stats.h $(CSRC)/epilogue.h $(CSRC)/bufaddr.h
+build/%.o: $(CSRC)/% include/tmdiff_hip.h $(CSRC)/common.h $(CSRC)/stats.h $(CSRC)/classical.h $(CSRC)/epilogue.h $(CSRC)/bufaddr.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 

@@ -15,8 +15,8 @@
 //                        loads with the same values); 0.0 on rows past the last regressor / target and on pixels past the end.
 //                        For each e it issues v_mfma_f64_16x16x4_f64 twice with the regressor register as A: once with the same
 //                        register as B (N += Hm' Hm) and once with the target register as B (R += Hm' D); instruction e adds the
-//                        products at the pixels step + 4 k + e, k = 0 .. 3 being the instruction's K index.  Four doubles per
-//                        lane hold a tile: col = lane & 15, row = (lane >> 4) + 4 reg.
+//                        products at the pixels step + 4 k + e, k = 0 .. 3 being the instruction's K index.  The two tiles'
+//                        layout: classical.h.
 //  SUMMATION ORDER of one entry of N or R: inside a wave one accumulator chain over its steps in ascending order and e ascending
 //                        inside a step; the four waves' tiles through LDS in ascending wave index (waves_in_order, stats.h); the
 //                        chunk's entries go to the workspace; bdsd_gram_finalize_kernel, one workgroup per (image, block) with
@@ -24,27 +24,22 @@
 //                        N's upper triangle mirrored: exactly symmetric.
 //  WHY THE MATRIX PIPE   The layout of plane_gram_kernel (cs_fusion.hip) extends directly: the second product shares the A operand,
 //                        so the targets cost one more instruction per e and no further loads of the regressors.
-//  bdsd_solve_kernel     one wave per (image, block); lane 0 runs the unpivoted root-free Cholesky factorisation N = L D L' and,
-//                        per column of R, the two triangular solves in fp64 in the loop order of metrics.bdsd_coeffs, every product
-//                        and difference rounded on its own (no contraction).  A pivot that is not positive: NaN for that block.
+//  bdsd_solve_kernel     one wave per (image, block); lane 0 factors N once (ldl_factor, classical.h) and solves per column of R
+//                        (ldl_solve).  A pivot that is not positive: NaN for that block.
 //  bdsd_inject_kernel<C> A workgroup's tile is 1024 consecutive pixels q of one full-scale block, so one set of weights serves it:
 //                        the block's (C + 1) x C weights go to LDS (at most 1920 bytes).  A lane owns four consecutive q, reads
 //                        all C bands and the PAN of them into fp32 registers before it writes anything (`out` may be ms_exp),
 //                        and evaluates per band one fp64 chain  acc = M_c;  acc = fma(gamma[k][c], M_k, acc), k = 0 .. C - 1;
-//                        acc = fma(gamma[C][c], P, acc), rounded to fp32 once.  16-byte accesses where the four pixels lie in one
-//                        row at an aligned address (block width % 4 == 0, W % 4 == 0, aligned bases), scalar ones with the same
-//                        values otherwise.  Traffic: 2 C + 1 planes.
-#include <algorithm>
-
-#include "stats.h"
+//                        acc = fma(gamma[C][c], P, acc), rounded to fp32 once.  Quads (classical.h) as 16-byte accesses where the
+//                        four pixels lie in one row at an aligned address (block width % 4 == 0, W % 4 == 0, aligned bases).
+//                        Traffic: 2 C + 1 planes.
+#include "classical.h"
 
 namespace {
 
 constexpr int BDSD_MAXC = 15;
 constexpr int BG_PIX = 4096;                    // pixels of a workgroup's chunk
 constexpr int BG_STEPS = BG_PIX / 16 / 4;       // steps of 16 pixels per wave
-
-typedef double bdsd_acc __attribute__((ext_vector_type(4)));
 
 // (by, bx) of a block: the whole image with bs == 0.  False when bs does not tile the image.
 inline bool bdsd_sides(int h, int w, int bs, int& by, int& bx) {
@@ -54,8 +49,7 @@ inline bool bdsd_sides(int h, int w, int bs, int& by, int& bx) {
 }
 inline bool bdsd_ok(int B, int C, int H, int W, int bs) {
   int by, bx;
-  return B >= 0 && C >= 1 && C <= BDSD_MAXC && H >= 1 && W >= 1 && tmdiff::fits_int32((double)std::max(B, 1) * C * H * W) &&
-         bdsd_sides(H, W, bs, by, bx);
+  return tmdiff::planes_ok(B, C, BDSD_MAXC, H, W) && bdsd_sides(H, W, bs, by, bx);
 }
 inline int bdsd_entries(int C) { return (C + 1) * (2 * C + 1); }
 inline int bdsd_chunks(long n) { return (int)((n + BG_PIX - 1) / BG_PIX); }
@@ -78,14 +72,10 @@ struct BdsdGramArgs {
 // block's n pixels.
 __device__ __forceinline__ void bdsd_load(const float* plane, int org, long q, int n, int bx, int w, bool vec, float (&v)[4]) {
   if (plane && vec && q < n) {                                    // bx % 4 == 0 here: the four lie inside one row together
-    const int q0 = (int)q;
-    *reinterpret_cast<float4*>(v) = *reinterpret_cast<const float4*>(plane + org + (q0 / bx) * w + q0 % bx);
+    *reinterpret_cast<float4*>(v) = *reinterpret_cast<const float4*>(plane + tmdiff::block_offset(org, q, n, bx, w));
   } else {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int qe = (int)min(q + e, (long)n - 1);
-      v[e] = plane && q + e < n ? plane[org + (qe / bx) * w + qe % bx] : 0.f;
-    }
+    for (int e = 0; e < 4; ++e) v[e] = plane && q + e < n ? plane[tmdiff::block_offset(org, q + e, n, bx, w)] : 0.f;
   }
 }
 
@@ -99,7 +89,7 @@ __global__ void __launch_bounds__(256) bdsd_gram_kernel(BdsdGramArgs a) {
   for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
     const float* reg = p < a.C ? a.lp + ((long)b * a.C + p) * plane : p == a.C ? a.pan + (long)b * plane : nullptr;
     const float* raw = p < a.C ? a.ms + ((long)b * a.C + p) * plane : nullptr;
-    bdsd_acc accn = {0.0, 0.0, 0.0, 0.0}, accr = {0.0, 0.0, 0.0, 0.0};
+    tmdiff::gram_tile accn = {0.0, 0.0, 0.0, 0.0}, accr = {0.0, 0.0, 0.0, 0.0};
     // the wave's steps that begin inside the block: the same count in every lane of the wave
     const long left = (long)n - (long)chunk * BG_PIX - 16 * wave;
     const int steps = left <= 0 ? 0 : (int)min((long)BG_STEPS, (left + 63) / 64);
@@ -116,11 +106,8 @@ __global__ void __launch_bounds__(256) bdsd_gram_kernel(BdsdGramArgs a) {
       }
     }
     __syncthreads();                                              // the image before may still read red
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      red[wave * 512 + ((lane >> 4) + 4 * r) * 16 + p] = accn[r];
-      red[wave * 512 + 256 + ((lane >> 4) + 4 * r) * 16 + p] = accr[r];
-    }
+    tmdiff::store_gram_tile<512>(red, wave, 0, lane, accn);
+    tmdiff::store_gram_tile<512>(red, wave, 256, lane, accr);
     __syncthreads();
     const int row = threadIdx.x >> 4, col = threadIdx.x & 15;
     double* dst = a.part + (((long)b * a.nblk + blk) * a.chunks + chunk) * (k1 * ld) + row * ld;
@@ -150,7 +137,6 @@ struct BdsdSolveArgs {
 };
 
 __global__ void __launch_bounds__(64) bdsd_solve_kernel(BdsdSolveArgs a) {
-#pragma clang fp contract(off)
   constexpr int K = BDSD_MAXC + 1;
   __shared__ double fac[K * K], piv[K], z[K], gam[K];
   if (threadIdx.x != 0) return;
@@ -159,29 +145,9 @@ __global__ void __launch_bounds__(64) bdsd_solve_kernel(BdsdSolveArgs a) {
   for (int s = blockIdx.x; s < a.systems; s += gridDim.x) {
     const double* mo = a.mo + (long)s * k1 * ld;
     double* out = a.out + (long)s * k1 * C;
-    bool bad = false;
-    for (int j = 0; j < k1; ++j) {
-      double dj = mo[j * ld + j];
-      for (int q = 0; q < j; ++q) dj = dj - fac[j * K + q] * (fac[j * K + q] * piv[q]);
-      bad = bad || !(dj > 0.0);
-      piv[j] = dj;
-      for (int i = j + 1; i < k1; ++i) {
-        double t = mo[i * ld + j];
-        for (int q = 0; q < j; ++q) t = t - fac[i * K + q] * (fac[j * K + q] * piv[q]);
-        fac[i * K + j] = t / dj;
-      }
-    }
-    for (int col = 0; col < C; ++col) {
-      for (int i = 0; i < k1; ++i) {                              // L z = R_c, then w = z / D
-        double t = mo[i * ld + k1 + col];
-        for (int q = 0; q < i; ++q) t = t - fac[i * K + q] * z[q];
-        z[i] = t;
-      }
-      for (int i = k1 - 1; i >= 0; --i) {                         // L' gamma_c = w
-        double t = z[i] / piv[i];
-        for (int q = i + 1; q < k1; ++q) t = t - fac[q * K + i] * gam[q];
-        gam[i] = t;
-      }
+    const bool bad = tmdiff::ldl_factor<K>(mo, ld, k1, fac, piv);
+    for (int col = 0; col < C; ++col) {                           // N gamma_c = R_c, column k1 + col of mo
+      tmdiff::ldl_solve<K>(mo + k1 + col, ld, k1, fac, piv, z, gam);
       for (int i = 0; i < k1; ++i) out[i * C + col] = bad ? nan : gam[i];
     }
   }
@@ -203,36 +169,19 @@ __global__ void __launch_bounds__(256) bdsd_inject_kernel(BdsdInjectArgs a) {
   const int org = (blk / a.nbx) * a.bh * a.W + (blk % a.nbx) * a.bw, n = a.bh * a.bw;
   const long q = ((long)tile * 256 + threadIdx.x) * 4;
   const long plane = (long)a.H * a.W;
-  int off[4];                                   // a pixel past the block's end is never accessed: its offset is the block's first
+  int off[4];                                   // a pixel past the block's end is never accessed: its offset is the block's last
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int qe = (int)min(q + e, (long)n - 1);
-    off[e] = q + e < n ? org + (qe / a.bw) * a.W + qe % a.bw : org;
-  }
+  for (int e = 0; e < 4; ++e) off[e] = tmdiff::block_offset(org, q + e, n, a.bw, a.W);
   const int cnt = (int)max((long)0, min((long)4, n - q));
   for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
     __syncthreads();                            // the image before may still read wt
     if ((int)threadIdx.x < (C + 1) * C) wt[threadIdx.x] = a.gamma[((long)b * a.nblk + blk) * ((C + 1) * C) + threadIdx.x];
     __syncthreads();
     if (cnt == 0) continue;
-    const float* pp = a.p + (long)b * plane;
-    float pv[4] = {0.f, 0.f, 0.f, 0.f}, mv[C][4];
-    if (a.vec) *reinterpret_cast<float4*>(pv) = *reinterpret_cast<const float4*>(pp + off[0]);
-    else
+    float pv[4], mv[C][4];
+    tmdiff::load_quad(a.p + (long)b * plane, off, a.vec, cnt, pv);
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (e < cnt) pv[e] = pp[off[e]];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const float* src = a.m + ((long)b * C + c) * plane;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) mv[c][e] = 0.f;
-      if (a.vec) *reinterpret_cast<float4*>(mv[c]) = *reinterpret_cast<const float4*>(src + off[0]);
-      else
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (e < cnt) mv[c][e] = src[off[e]];
-    }
+    for (int c = 0; c < C; ++c) tmdiff::load_quad(a.m + ((long)b * C + c) * plane, off, a.vec, cnt, mv[c]);
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       double acc[4];
@@ -248,21 +197,9 @@ __global__ void __launch_bounds__(256) bdsd_inject_kernel(BdsdInjectArgs a) {
       float f[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) f[e] = (float)fma(gp, (double)pv[e], acc[e]);
-      float* dst = a.out + ((long)b * C + c) * plane;
-      if (a.vec) *reinterpret_cast<float4*>(dst + off[0]) = *reinterpret_cast<const float4*>(f);
-      else
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (e < cnt) dst[off[e]] = f[e];
+      tmdiff::store_quad(a.out + ((long)b * C + c) * plane, off, a.vec, cnt, f);
     }
   }
-}
-
-template <int C>
-void bdsd_inject_launch(const BdsdInjectArgs& a, int bands, dim3 grid, hipStream_t st) {
-  if constexpr (C > BDSD_MAXC) return;
-  else if (bands == C) bdsd_inject_kernel<C><<<grid, 256, 0, st>>>(a);
-  else bdsd_inject_launch<C + 1>(a, bands, grid, st);
 }
 
 const char* const BDSD_LIMITS = "B >= 0, 1 <= C <= 15, H, W >= 1, fewer than 2^31 elements; the block side 0 (the whole image) or a "
@@ -322,7 +259,9 @@ int tmdiff_bdsd_inject(const float* ms_exp, const float* pan, const double* gamm
   if (const int rc = tmdiff::check_grid((long)nblk * tiles, "bdsd_inject", TMDIFF_E_UNSUPPORTED)) return rc;
   const int vec = bw % 4 == 0 && W % 4 == 0 && tmdiff::aligned16(ms_exp) && tmdiff::aligned16(pan) && tmdiff::aligned16(out);
   const BdsdInjectArgs a{ms_exp, pan, gamma, out, B, H, W, bh, bw, nbx, nblk, tiles, vec};
-  bdsd_inject_launch<1>(a, C, dim3((unsigned)(nblk * tiles), (unsigned)std::min(B, 65535)), tmdiff::as_stream(stream));
+  const dim3 grid((unsigned)(nblk * tiles), (unsigned)std::min(B, 65535));
+  const hipStream_t st = tmdiff::as_stream(stream);
+  tmdiff::dispatch_bands<BDSD_MAXC>(C, [&](auto c) { bdsd_inject_kernel<decltype(c)::value><<<grid, 256, 0, st>>>(a); });
   return tmdiff::check_launch("bdsd_inject");
 }
 

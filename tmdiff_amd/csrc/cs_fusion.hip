@@ -6,13 +6,12 @@
 //  plane_gram_kernel     The planes of an image are its C bands, the PAN and a plane of ones: C + 2 <= 16 rows of a 16 x 16 tile.
 //                        One workgroup of 256 takes a chunk of GRAM_PIX consecutive flattened pixels of one image, wave w the
 //                        GRAM_PIX / 4 pixels from chunk + w GRAM_PIX / 4 on, in steps of 16 pixels.  In a step, lane l holds
-//                        plane p = l & 15 at the four pixels step + 4 (l >> 4) + e, e = 0 .. 3 (one 16-byte load per lane, or
-//                        four scalar ones with the same values: 64 contiguous bytes per plane and step), as fp64 minus the
-//                        plane's pilot, the image's first pixel of that plane; 1.0 on the ones row; 0.0 on rows >= C + 2 and on
-//                        pixels past the end.  It then issues v_mfma_f64_16x16x4_f64 four times, e ascending, with that
-//                        register as both A and B: instruction e adds to G[i][j] the products of planes i and j at the pixels
-//                        step + 4 k + e, k = 0 .. 3 being the instruction's K index (the order inside it is the hardware's and
-//                        is fixed).  Four doubles per lane hold the tile: col = lane & 15, row = (lane >> 4) + 4 reg.
+//                        plane p = l & 15 at the four pixels step + 4 (l >> 4) + e, e = 0 .. 3 (load_quad_minus_pilot,
+//                        classical.h: 64 contiguous bytes per plane and step), as fp64 minus the plane's pilot; 1.0 on the
+//                        ones row; 0.0 on rows >= C + 2 and on pixels past the end.  It then issues v_mfma_f64_16x16x4_f64
+//                        four times, e ascending, with that register as both A and B: instruction e adds to G[i][j] the
+//                        products of planes i and j at the pixels step + 4 k + e, k = 0 .. 3 being the instruction's K index
+//                        (the order inside it is the hardware's and is fixed).  The tile's layout: classical.h.
 //  SUMMATION ORDER of one entry G[i][j]: inside a wave one accumulator chain over the steps in ascending order and e ascending
 //                        inside a step; the four waves' tiles through LDS in ascending wave index (waves_in_order, stats.h);
 //                        the chunk's tile goes to the workspace; plane_gram_finalize_kernel, one workgroup per image with lane
@@ -23,16 +22,14 @@
 //                        i <= j, mirrored into the lower triangle: the output is exactly symmetric.
 //  CONDITIONING: as glp_moments (metrics.hip): moments about a pilot, one pass; a constant plane has d == 0 everywhere and a
 //                        variance and covariances of exactly 0.
-//  cs_coeffs_kernel      one wave per image; lane 0 runs the unpivoted root-free Cholesky factorisation S_lr = L D L' and the two
-//                        triangular solves in fp64 in the loop order of metrics.cs_coeffs, every product and difference rounded
-//                        on its own as there (no contraction: a duplicated band's pivot is then exactly non-positive).
+//  cs_coeffs_kernel      one wave per image; lane 0 solves S_lr alpha = c_lr by ldl_factor and ldl_solve (classical.h) and forms
+//                        the other constants in the loop order of metrics.cs_coeffs, every product and sum rounded on its own.
 //  cs_inject_kernel<C>   elementwise: the 2 C + 3 constants go to LDS once per image, a lane owns four consecutive pixels,
-//                        reads all C bands of them into registers, forms I = sum_k alpha_k M_k in fp64 in ascending k, evaluates
-//                        the formula in fp64 and rounds to fp32 once.  `out` may be ms_exp: a lane has read every band of its
-//                        pixels before it writes any and nobody else touches them.  Traffic: 2 C + 1 planes.
-#include <algorithm>
-
-#include "stats.h"
+//                        reads all C bands of them into registers (load_quad, classical.h), forms I = sum_k alpha_k M_k in fp64
+//                        in ascending k, evaluates the formula in fp64 and rounds to fp32 once.  `out` may be ms_exp: a lane has
+//                        read every band of its pixels before it writes any and nobody else touches them.  Traffic: 2 C + 1
+//                        planes.
+#include "classical.h"
 
 namespace {
 
@@ -43,11 +40,6 @@ constexpr int GRAM_DEPTH = 8;                   // steps whose loads are issued 
 constexpr int GRAM_AHEAD = 32;                  // chunks whose partial sums the finalize kernel loads together
 static_assert(GRAM_STEPS % GRAM_DEPTH == 0, "whole batches");
 
-typedef double gram_acc __attribute__((ext_vector_type(4)));
-
-inline bool cs_ok(int B, int C, int H, int W) {
-  return B >= 0 && C >= 1 && C <= CS_MAXC && H >= 1 && W >= 1 && tmdiff::fits_int32((double)std::max(B, 1) * C * H * W);
-}
 inline int gram_chunks(long n) { return (int)((n + GRAM_PIX - 1) / GRAM_PIX); }
 inline size_t gram_bytes(int B, int C, int H, int W) {
   return ((size_t)B * (C + 2) * (C + 2) + (size_t)B * gram_chunks((long)H * W) * 256) * sizeof(double);
@@ -62,17 +54,6 @@ struct GramArgs {
   double* out;        // [B, C + 1, C + 2]
 };
 
-// The lane's four values from pixel px on.  plane: the lane's plane, or null on the ones row (fill 1) and the rows past it
-// (fill 0).  A pixel past the end is the pilot itself on a plane and 0 elsewhere, so value - pilot is 0 everywhere there.
-__device__ __forceinline__ void gram_load(const float* plane, float pilot, float fill, long px, int n, bool vec, float (&v)[4]) {
-  if (plane && vec && px < n) {                                   // n % 4 == 0 here: the four lie inside together
-    *reinterpret_cast<float4*>(v) = *reinterpret_cast<const float4*>(plane + px);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = px + e < n ? (plane ? plane[px + e] : fill) : pilot;
-  }
-}
-
 __global__ void __launch_bounds__(256) plane_gram_kernel(GramArgs a) {
   __shared__ double red[4 * 256];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, p = lane & 15;
@@ -80,32 +61,29 @@ __global__ void __launch_bounds__(256) plane_gram_kernel(GramArgs a) {
   for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
     const float* plane = p < a.C ? a.ms + ((long)b * a.C + p) * a.n : p == a.C ? a.pan + (long)b * a.n : nullptr;
     const float pilot = plane ? plane[0] : 0.f, fill = p == a.C + 1 ? 1.f : 0.f;
-    const double dp = pilot;
-    gram_acc acc = {0.0, 0.0, 0.0, 0.0};
-    float cur[GRAM_DEPTH][4], nxt[GRAM_DEPTH][4];
+    tmdiff::gram_tile acc = {0.0, 0.0, 0.0, 0.0};
+    double cur[GRAM_DEPTH][4], nxt[GRAM_DEPTH][4];
 #pragma unroll
-    for (int s = 0; s < GRAM_DEPTH; ++s) gram_load(plane, pilot, fill, px0 + 16 * s, a.n, a.vec, cur[s]);
+    for (int s = 0; s < GRAM_DEPTH; ++s)
+      tmdiff::load_quad_minus_pilot(plane, plane != nullptr, pilot, fill, px0 + 16 * s, a.n, a.vec, cur[s]);
 #pragma unroll
     for (int s0 = 0; s0 < GRAM_STEPS; s0 += GRAM_DEPTH) {
       if (s0 + GRAM_DEPTH < GRAM_STEPS) {
 #pragma unroll
-        for (int s = 0; s < GRAM_DEPTH; ++s) gram_load(plane, pilot, fill, px0 + 16 * (s0 + GRAM_DEPTH + s), a.n, a.vec, nxt[s]);
+        for (int s = 0; s < GRAM_DEPTH; ++s)
+          tmdiff::load_quad_minus_pilot(plane, plane != nullptr, pilot, fill, px0 + 16 * (s0 + GRAM_DEPTH + s), a.n, a.vec, nxt[s]);
       }
 #pragma unroll
       for (int s = 0; s < GRAM_DEPTH; ++s)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const double d = (double)cur[s][e] - dp;
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(d, d, acc, 0, 0, 0);
-        }
+        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[s][e], cur[s][e], acc, 0, 0, 0);
 #pragma unroll
       for (int s = 0; s < GRAM_DEPTH; ++s)
 #pragma unroll
         for (int e = 0; e < 4; ++e) cur[s][e] = nxt[s][e];
     }
     __syncthreads();                                              // the image before may still read red
-#pragma unroll
-    for (int r = 0; r < 4; ++r) red[wave * 256 + ((lane >> 4) + 4 * r) * 16 + p] = acc[r];
+    tmdiff::store_gram_tile<256>(red, wave, 0, lane, acc);
     __syncthreads();
     const int row = threadIdx.x >> 4, col = threadIdx.x & 15;
     if (row < a.C + 2 && col < a.C + 2)
@@ -168,29 +146,10 @@ __global__ void __launch_bounds__(64) cs_coeffs_kernel(CoefArgs a) {
     const double* full = a.full + (long)b * (C + 1) * ld;
     double* out = a.out + (long)b * (2 * C + 3);
     bool bad = false;
-    if (a.mode == 1) {
+    if (a.mode == 1) {                                            // S_lr alpha = c_lr, column C of low
       const double* low = a.low + (long)b * (C + 1) * ld;
-      for (int j = 0; j < C; ++j) {
-        double dj = low[j * ld + j];
-        for (int k = 0; k < j; ++k) dj = dj - fac[j * CS_MAXC + k] * (fac[j * CS_MAXC + k] * piv[k]);
-        bad = bad || !(dj > 0.0);
-        piv[j] = dj;
-        for (int i = j + 1; i < C; ++i) {
-          double t = low[i * ld + j];
-          for (int k = 0; k < j; ++k) t = t - fac[i * CS_MAXC + k] * (fac[j * CS_MAXC + k] * piv[k]);
-          fac[i * CS_MAXC + j] = t / dj;
-        }
-      }
-      for (int i = 0; i < C; ++i) {                               // L z = c_lr, then w = z / D
-        double t = low[i * ld + C];
-        for (int k = 0; k < i; ++k) t = t - fac[i * CS_MAXC + k] * y[k];
-        y[i] = t;
-      }
-      for (int i = C - 1; i >= 0; --i) {                          // L' alpha = w
-        double t = y[i] / piv[i];
-        for (int k = i + 1; k < C; ++k) t = t - fac[k * CS_MAXC + i] * alpha[k];
-        alpha[i] = t;
-      }
+      bad = tmdiff::ldl_factor<CS_MAXC>(low, ld, C, fac, piv);
+      tmdiff::ldl_solve<CS_MAXC>(low + C, ld, C, fac, piv, y, alpha);
     } else {
       for (int k = 0; k < C; ++k) alpha[k] = 1.0 / (double)C;
     }
@@ -234,24 +193,10 @@ __global__ void __launch_bounds__(256) cs_inject_kernel(CsInjectArgs a) {
     __syncthreads();
     if (px >= a.n) continue;
     const int cnt = (int)min((long)4, a.n - px);
-    const float* pp = a.p + (long)b * a.n + px;
-    float pv[4] = {0.f, 0.f, 0.f, 0.f}, mv[C][4];
-    if (a.vec) *reinterpret_cast<float4*>(pv) = *reinterpret_cast<const float4*>(pp);
-    else
+    float pv[4], mv[C][4];
+    tmdiff::load_quad(a.p + (long)b * a.n + px, a.vec, cnt, pv);
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (e < cnt) pv[e] = pp[e];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const long o = ((long)b * C + c) * a.n + px;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) mv[c][e] = 0.f;
-      if (a.vec) *reinterpret_cast<float4*>(mv[c]) = *reinterpret_cast<const float4*>(a.m + o);
-      else
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (e < cnt) mv[c][e] = a.m[o + e];
-    }
+    for (int c = 0; c < C; ++c) tmdiff::load_quad(a.m + ((long)b * C + c) * a.n + px, a.vec, cnt, mv[c]);
     double in[4] = {0.0, 0.0, 0.0, 0.0}, pi[4];
 #pragma unroll
     for (int c = 0; c < C; ++c)
@@ -261,7 +206,6 @@ __global__ void __launch_bounds__(256) cs_inject_kernel(CsInjectArgs a) {
     for (int e = 0; e < 4; ++e) pi[e] = cst[2 * C] * ((double)pv[e] - cst[2 * C + 2]) + cst[2 * C + 1];
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-      const long o = ((long)b * C + c) * a.n + px;
       const double gc = cst[C + c];
       float f[4];
 #pragma unroll
@@ -269,20 +213,9 @@ __global__ void __launch_bounds__(256) cs_inject_kernel(CsInjectArgs a) {
         const double r = a.mode == 2 ? (double)mv[c][e] * pi[e] / (in[e] + 0x1p-52) : (double)mv[c][e] + gc * (pi[e] - in[e]);
         f[e] = (float)r;
       }
-      if (a.vec) *reinterpret_cast<float4*>(a.out + o) = *reinterpret_cast<const float4*>(f);
-      else
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (e < cnt) a.out[o + e] = f[e];
+      tmdiff::store_quad(a.out + ((long)b * C + c) * a.n + px, a.vec, cnt, f);
     }
   }
-}
-
-template <int C>
-void cs_inject_launch(const CsInjectArgs& a, int bands, dim3 grid, hipStream_t st) {
-  if constexpr (C > CS_MAXC) return;
-  else if (bands == C) cs_inject_kernel<C><<<grid, 256, 0, st>>>(a);
-  else cs_inject_launch<C + 1>(a, bands, grid, st);
 }
 
 }  // namespace
@@ -290,12 +223,12 @@ void cs_inject_launch(const CsInjectArgs& a, int bands, dim3 grid, hipStream_t s
 extern "C" {
 
 size_t tmdiff_plane_gram_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
-  return cs_ok(B, C, H, W) ? gram_bytes(B, C, H, W) : 0;
+  return tmdiff::planes_ok(B, C, CS_MAXC, H, W) ? gram_bytes(B, C, H, W) : 0;
 }
 
 int tmdiff_plane_gram(const float* ms, const float* pan, int32_t B, int32_t C, int32_t H, int32_t W, double* out, void* workspace,
                       size_t workspace_bytes, tmdiff_stream_t stream) {
-  if (!cs_ok(B, C, H, W))
+  if (!tmdiff::planes_ok(B, C, CS_MAXC, H, W))
     return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "plane_gram: B=%d C=%d H=%d W=%d (B >= 0, 1 <= C <= 14, H, W >= 1, fewer than 2^31 "
                         "elements)", B, C, H, W);
   if (B == 0) return TMDIFF_OK;
@@ -329,7 +262,7 @@ int tmdiff_cs_coeffs(const double* full, const double* low, double* out, int32_t
 
 int tmdiff_cs_inject(const float* ms_exp, const float* pan, const double* coef, float* out, int32_t B, int32_t C, int32_t H,
                      int32_t W, int32_t mode, tmdiff_stream_t stream) {
-  if (!cs_ok(B, C, H, W) || mode < 0 || mode > 2)
+  if (!tmdiff::planes_ok(B, C, CS_MAXC, H, W) || mode < 0 || mode > 2)
     return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "cs_inject: B=%d C=%d H=%d W=%d mode=%d (B >= 0, 1 <= C <= 14, H, W >= 1, fewer than "
                         "2^31 elements; mode 0 gs, 1 gsa, 2 brovey)", B, C, H, W, mode);
   if (B == 0) return TMDIFF_OK;
@@ -339,7 +272,8 @@ int tmdiff_cs_inject(const float* ms_exp, const float* pan, const double* coef, 
   const int vec = n % 4 == 0 && tmdiff::aligned16(ms_exp) && tmdiff::aligned16(pan) && tmdiff::aligned16(out);
   const CsInjectArgs a{ms_exp, pan, coef, out, B, n, mode, vec};
   const dim3 grid((unsigned)(((long)n + 1023) / 1024), (unsigned)std::min(B, 65535));
-  cs_inject_launch<1>(a, C, grid, tmdiff::as_stream(stream));
+  const hipStream_t st = tmdiff::as_stream(stream);
+  tmdiff::dispatch_bands<CS_MAXC>(C, [&](auto c) { cs_inject_kernel<decltype(c)::value><<<grid, 256, 0, st>>>(a); });
   return tmdiff::check_launch("cs_inject");
 }
 

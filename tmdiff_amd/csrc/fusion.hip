@@ -12,10 +12,10 @@
 // A lane owns four consecutive pixels of a plane and walks the bands with the four PAN values in registers: P is read once,
 // M_c and L_c once each, F_c written once -- 3 C + 1 planes of traffic.  16-byte loads and stores when W % 4 == 0 and the
 // pointers allow it, scalar ones otherwise, with the same values.  `out` may be ms_exp: a lane reads a pixel of M before it
-// writes that pixel and nobody else touches it.
-#include <algorithm>
-
-#include "common.h"
+// writes that pixel and nobody else touches it.  The quads keep their own text, not load_quad / store_quad of classical.h:
+// with that form the compiler merges the fourth pixel of the two paths and turns each of this kernel's 16-byte accesses into
+// one of 12 and one of 4 bytes (profiles/classical_refactor.txt, section 2).
+#include "classical.h"
 
 namespace {
 
@@ -81,7 +81,7 @@ extern "C" {
 
 int tmdiff_glp_inject(const float* ms_exp, const float* pan, const float* pan_lp, const double* moments, float* out, int32_t B,
                       int32_t C, int32_t H, int32_t W, int32_t mode, tmdiff_stream_t stream) {
-  if (B < 0 || C < 1 || C > MAXC || H < 1 || W < 1 || !tmdiff::fits_int32((double)std::max(B, 1) * C * H * W) || mode < 0 || mode > 2)
+  if (!tmdiff::planes_ok(B, C, MAXC, H, W) || mode < 0 || mode > 2)
     return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "glp_inject: B=%d C=%d H=%d W=%d mode=%d (B >= 0, 1 <= C <= 16, H, W >= 1, fewer than "
                         "2^31 elements; mode 0 glp, 1 cbd, 2 hpm)", B, C, H, W, mode);
   if (B == 0) return TMDIFF_OK;

@@ -33,7 +33,7 @@
 // launches go to its stream.
 #include <algorithm>
 
-#include "stats.h"
+#include "classical.h"
 
 namespace {
 
@@ -867,8 +867,8 @@ int tmdiff_metrics_dsblock(const float* ps, int64_t ps_stride_b, int64_t ps_stri
 // M = ms_exp and L = pan_lp, and the mean and variance of P = pan, as device values for glp_inject_kernel (fusion.hip).
 //
 //  glp_moments_kernel    one workgroup per chunk of 4096 consecutive pixels of one image; lane t owns the four pixels from
-//                        chunk + 4 (256 k + t) on, k = 0 .. 3, and adds them in that order (k, then the pixel) whether they
-//                        arrive as one 16-byte load or as four scalar ones.  It reads P once, forms its two sums, then walks the
+//                        chunk + 4 (256 k + t) on, k = 0 .. 3 (load_quad_minus_pilot, classical.h), and adds them in that order
+//                        (k, then the pixel).  It reads P once, forms its two sums, then walks the
 //                        bands with five sums each.  Seven partial sums per band and chunk go to the workspace.
 //  glp_moments_finalize_kernel  one workgroup per (band, image): lane t adds chunks t, t + 256, ... (strided_sum), the
 //                        workgroup adds the lanes (wg_sum), lane 0 forms the moments.
@@ -885,9 +885,6 @@ namespace {
 constexpr int GLP_QUADS = 4, GLP_PIX = 256 * 4 * GLP_QUADS;   // pixels of a workgroup's chunk
 constexpr int GLP_K = 7;
 
-inline bool glp_ok(int B, int C, int H, int W) {
-  return B >= 0 && C >= 1 && C <= MAXC && H >= 1 && W >= 1 && tmdiff::fits_int32((double)std::max(B, 1) * C * H * W);
-}
 inline int glp_chunks(long n) { return (int)((n + GLP_PIX - 1) / GLP_PIX); }
 inline size_t glp_bytes(int B, int C, int H, int W) {
   return ((size_t)B * C * GLP_K + (size_t)B * glp_chunks((long)H * W) * (5 * C + 2)) * sizeof(double);
@@ -903,17 +900,6 @@ struct GlpArgs {
   double* out;      // [B, C, 7]
 };
 
-// The lane's four pixels from px on as differences from the pilot; a pixel past the plane's end is the pilot itself: d == 0.
-__device__ __forceinline__ void glp_load(const float* plane, long px, int n, bool vec, double pilot, double (&d)[4]) {
-  if (vec && px < n) {                                            // n % 4 == 0 here: the four lie inside together
-    const float4 v = *reinterpret_cast<const float4*>(plane + px);
-    d[0] = (double)v.x - pilot, d[1] = (double)v.y - pilot, d[2] = (double)v.z - pilot, d[3] = (double)v.w - pilot;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) d[e] = px + e < n ? (double)plane[px + e] - pilot : 0.0;
-  }
-}
-
 __global__ void __launch_bounds__(256) glp_moments_kernel(GlpArgs a) {
   __shared__ double red[4 * 5];
   const int chunk = blockIdx.x;
@@ -923,12 +909,12 @@ __global__ void __launch_bounds__(256) glp_moments_kernel(GlpArgs a) {
     double* dst = a.part + ((long)b * a.chunks + chunk) * ld;
     {
       const float* pp = a.p + (long)b * a.n;
-      const double pilot = pp[0];
+      const float pilot = pp[0];
       double v[2] = {0.0, 0.0};
 #pragma unroll
       for (int k = 0; k < GLP_QUADS; ++k) {
         double d[4];
-        glp_load(pp, px0 + k * 1024, a.n, a.vec, pilot, d);
+        tmdiff::load_quad_minus_pilot(pp, true, pilot, 0.f, px0 + k * 1024, a.n, a.vec, d);
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[0] += d[e], v[1] += d[e] * d[e];
       }
@@ -939,13 +925,13 @@ __global__ void __launch_bounds__(256) glp_moments_kernel(GlpArgs a) {
     for (int c = 0; c < a.C; ++c) {
       const float* mp = a.m + ((long)b * a.C + c) * a.n;
       const float* lp = a.l + ((long)b * a.C + c) * a.n;
-      const double pm = mp[0], pl = lp[0];
+      const float pm = mp[0], pl = lp[0];
       double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int k = 0; k < GLP_QUADS; ++k) {
         double dm[4], dl[4];
-        glp_load(mp, px0 + k * 1024, a.n, a.vec, pm, dm);
-        glp_load(lp, px0 + k * 1024, a.n, a.vec, pl, dl);
+        tmdiff::load_quad_minus_pilot(mp, true, pm, 0.f, px0 + k * 1024, a.n, a.vec, dm);
+        tmdiff::load_quad_minus_pilot(lp, true, pl, 0.f, px0 + k * 1024, a.n, a.vec, dl);
 #pragma unroll
         for (int e = 0; e < 4; ++e)
           v[0] += dm[e], v[1] += dl[e], v[2] += dm[e] * dm[e], v[3] += dl[e] * dl[e], v[4] += dm[e] * dl[e];
@@ -989,12 +975,12 @@ __global__ void __launch_bounds__(256) glp_moments_finalize_kernel(GlpArgs a) {
 extern "C" {
 
 size_t tmdiff_glp_moments_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
-  return glp_ok(B, C, H, W) ? glp_bytes(B, C, H, W) : 0;
+  return tmdiff::planes_ok(B, C, MAXC, H, W) ? glp_bytes(B, C, H, W) : 0;
 }
 
 int tmdiff_glp_moments(const float* ms_exp, const float* pan, const float* pan_lp, int32_t B, int32_t C, int32_t H, int32_t W,
                        double* out, void* workspace, size_t workspace_bytes, tmdiff_stream_t stream) {
-  if (!glp_ok(B, C, H, W))
+  if (!tmdiff::planes_ok(B, C, MAXC, H, W))
     return tmdiff::fail(TMDIFF_E_UNSUPPORTED, "glp_moments: B=%d C=%d H=%d W=%d (B >= 0, 1 <= C <= 16, H, W >= 1, fewer than 2^31 "
                         "elements)", B, C, H, W);
   if (B == 0) return TMDIFF_OK;

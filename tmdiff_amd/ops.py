@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory and the current HIP stream; ever
 these ops runs in libtmdiff_hip.so.  All wrappers require CUDA(HIP) fp32 contiguous
 tensors and raise otherwise -- there is no eager fallback.
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -1704,28 +1705,48 @@ _GLP_LIMITS = ("contiguous float32 tensors on the GPU, ms_exp and pan_lp [B, C, 
                "H and W multiples of it; fewer than 2^31 elements")
 
 
-def _glp_dense(name, arg, t, shape=None):
-    """``t`` must be a contiguous float32 tensor on the GPU, of ``shape`` when that is given."""
+# What the wrappers of the three families (MTF-GLP here, component substitution and BDSD below) check alike.  A family is the name
+# its messages give the MS image, its largest C and its limits text.
+_Family = collections.namedtuple("_Family", "ms max_c limits")
+_GLP = _Family("ms_exp", 16, _GLP_LIMITS)
+
+
+def _dense(fam, name, arg, t, shape=None):
+    """``t`` must be dense float32 device memory, of ``shape`` when that is given."""
     if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-        raise ValueError(f"{name}: {arg} must be a contiguous float32 tensor on the GPU ({_GLP_LIMITS})")
+        raise ValueError(f"{name}: {arg} must be a contiguous float32 tensor on the GPU ({fam.limits})")
     if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name}: {arg} is {tuple(t.shape)}, need {tuple(shape)} ({_GLP_LIMITS})")
+        raise ValueError(f"{name}: {arg} is {tuple(t.shape)}, need {tuple(shape)} ({fam.limits})")
     return t
+
+
+def _extents(fam, name, b, c, h, w, ratio=None, block=None):
+    """(B, C, H, W, blocks down, blocks across) after the checks on the extents; ``block`` (BDSD) is a side at the images' scale."""
+    b, c, h, w = int(b), int(c), int(h), int(w)
+    if not 1 <= c <= fam.max_c or min(b, h, w) < 1 or b * c * h * w > 2 ** 31 - 1:
+        raise ValueError(f"{name}: B={b} C={c} H={h} W={w} is not supported ({fam.limits})")
+    if ratio is not None and (ratio not in (2, 4) or h % ratio or w % ratio):
+        raise ValueError(f"{name}: H={h} W={w} ratio={ratio} is not supported ({fam.limits})")
+    if block is not None and (isinstance(block, bool) or int(block) != block or block < 1 or block % (ratio or 1) or h % block or w % block):
+        raise ValueError(f"{name}: block={block!r} for H={h} W={w} ratio={ratio or 1} is not supported ({fam.limits})")
+    return b, c, h, w, (1 if block is None else h // int(block)), (1 if block is None else w // int(block))
+
+
+def _images(fam, name, ms, pan, ratio=None, block=None):
+    """The extents of ``_extents`` after the checks on the MS image [B, C, H, W] and the PAN [B, 1, H, W] of a call."""
+    _dense(fam, name, fam.ms, ms)
+    if ms.dim() != 4:
+        raise ValueError(f"{name}: {fam.ms} is {tuple(ms.shape)}, need [B, C, H, W] ({fam.limits})")
+    extents = _extents(fam, name, *ms.shape, ratio, block)
+    _dense(fam, name, "pan", pan, (extents[0], 1, *extents[2:4]))
+    return extents
 
 
 def _glp_images(name, ms_exp, pan, pan_lp=None, ratio=None):
     """(B, C, H, W) of a GLP call after the checks on its images."""
-    _glp_dense(name, "ms_exp", ms_exp)
-    if ms_exp.dim() != 4:
-        raise ValueError(f"{name}: ms_exp is {tuple(ms_exp.shape)}, need [B, C, H, W] ({_GLP_LIMITS})")
-    b, c, h, w = ms_exp.shape
-    if not 1 <= c <= 16 or min(b, h, w) < 1 or ms_exp.numel() > 2 ** 31 - 1:
-        raise ValueError(f"{name}: B={b} C={c} H={h} W={w} is not supported ({_GLP_LIMITS})")
-    if ratio is not None and (ratio not in (2, 4) or h % ratio or w % ratio):
-        raise ValueError(f"{name}: H={h} W={w} ratio={ratio} is not supported ({_GLP_LIMITS})")
-    _glp_dense(name, "pan", pan, (b, 1, h, w))
+    b, c, h, w = _images(_GLP, name, ms_exp, pan, ratio)[:4]
     if pan_lp is not None:
-        _glp_dense(name, "pan_lp", pan_lp, (b, c, h, w))
+        _dense(_GLP, name, "pan_lp", pan_lp, (b, c, h, w))
     return b, c, h, w
 
 
@@ -1733,6 +1754,43 @@ def _overlaps(a, b):
     """True when the bytes of two dense tensors intersect."""
     lo, hi = b.data_ptr(), b.data_ptr() + b.numel() * b.element_size()
     return a.data_ptr() < hi and lo < a.data_ptr() + a.numel() * a.element_size()
+
+
+def _chain_out(fam, name, out, shape, others):
+    """The rule on the ``out`` of a whole chain, when one is given: of ``shape`` and clear of every tensor in ``others``, pairs
+    (tensor or None, its name).  That it may be ms_exp itself, and nothing else of ms_exp, is left to the injection."""
+    if out is not None:
+        _dense(fam, name, "out", out, shape)
+        for other, what in others:
+            if other is not None and _overlaps(out, other):
+                raise ValueError(f"{name}: out overlaps {what}")
+    return out
+
+
+def _inject_out(fam, name, out, ms_exp, others):
+    """The output of an injection, ``out`` or a new tensor: it may be ms_exp itself (in place) and must not overlap anything else."""
+    y = _chain_out(fam, name, out if out is not None else torch.empty_like(ms_exp), tuple(ms_exp.shape), others)
+    if y.data_ptr() != ms_exp.data_ptr() and _overlaps(y, ms_exp):
+        raise ValueError(f"{name}: out overlaps ms_exp without being ms_exp")
+    return y
+
+
+def _chain_buffers(name, buffers, make, shape, probe, device):
+    """``buffers`` of a chain, or with None ``make()``: they must have been made for ``shape`` on ``device`` (``probe`` names one)."""
+    buf = buffers if buffers is not None else make()
+    if buf["shape"] != shape or buf[probe].device != device:
+        raise ValueError(f"{name}: buffers made for {buf['shape']}, the call is {shape}")
+    return buf
+
+
+def _reduced_ms(fam, name, ms_exp, lr_ms, ratio, stage):
+    """The reduced-scale MS of a chain: ``lr_ms`` [B, C, H / ratio, W / ratio], or with None the samples
+    ms_exp[..., ratio // 2::ratio, ratio // 2::ratio] copied into ``stage``."""
+    if lr_ms is None:
+        stage.copy_(ms_exp[..., ratio // 2::ratio, ratio // 2::ratio])
+        return stage
+    b, c, h, w = ms_exp.shape
+    return _dense(fam, name, "lr_ms", lr_ms, (b, c, h // ratio, w // ratio)).detach()
 
 
 def fir_decimate_bank(x, taps, ratio=1, offset=None, out=None):
@@ -1816,12 +1874,7 @@ def glp_inject(ms_exp, pan, pan_lp, moments, mode, out=None):
         raise ValueError(f"glp_inject: mode={mode!r} (one of {metrics.GLP_MODES})")
     b, c, h, w = _glp_images("glp_inject", ms_exp, pan, pan_lp)
     mo = _f64("glp_inject", "moments", moments, (b, c, 7), ms_exp.device)
-    y = _glp_dense("glp_inject", "out", out if out is not None else torch.empty_like(ms_exp), (b, c, h, w))
-    for other, what in ((pan, "pan"), (pan_lp, "pan_lp"), (mo, "moments")):
-        if _overlaps(y, other):
-            raise ValueError(f"glp_inject: out overlaps {what}")
-    if y.data_ptr() != ms_exp.data_ptr() and _overlaps(y, ms_exp):
-        raise ValueError("glp_inject: out overlaps ms_exp without being ms_exp")
+    y = _inject_out(_GLP, "glp_inject", out, ms_exp, ((pan, "pan"), (pan_lp, "pan_lp"), (mo, "moments")))
     check(lib.tmdiff_glp_inject(ms_exp.detach().data_ptr(), pan.detach().data_ptr(), pan_lp.detach().data_ptr(), mo.data_ptr(),
                                 y.data_ptr(), b, c, h, w, metrics.GLP_MODES.index(mode), stream_ptr()), "glp_inject")
     return y
@@ -1852,14 +1905,9 @@ def mtf_glp(ms_exp, pan, sensor, ratio=4, mode="hpm", pan_lp=None, out=None, buf
     if mode not in metrics.GLP_MODES:
         raise ValueError(f"mtf_glp: mode={mode!r} (one of {metrics.GLP_MODES})")
     b, c, h, w = _glp_images("mtf_glp", ms_exp, pan, pan_lp, ratio)
-    if out is not None:
-        _glp_dense("mtf_glp", "out", out, (b, c, h, w))
-        for other, what in ((pan, "pan"), (pan_lp, "pan_lp")):
-            if other is not None and _overlaps(out, other):
-                raise ValueError(f"mtf_glp: out overlaps {what}")
-    buf = buffers if buffers is not None else mtf_glp_buffers(b, c, h, w, ms_exp.device, ratio)
-    if buf["shape"] != (b, c, h, w, ratio) or buf["pan_lp"].device != ms_exp.device:
-        raise ValueError(f"mtf_glp: buffers made for {buf['shape']}, the call is {(b, c, h, w, ratio)}")
+    _chain_out(_GLP, "mtf_glp", out, (b, c, h, w), ((pan, "pan"), (pan_lp, "pan_lp")))
+    buf = _chain_buffers("mtf_glp", buffers, lambda: mtf_glp_buffers(b, c, h, w, ms_exp.device, ratio), (b, c, h, w, ratio), "pan_lp",
+                         ms_exp.device)
     if pan_lp is None:
         pan_lp = pan_lowpass_bands(pan, metrics.mtf_gains(sensor, c)[0], c, ratio, out=buf["pan_lp"], low=buf["pan_low"])
     mo = glp_moments(ms_exp, pan, pan_lp, out=buf["moments"], workspace=buf["ws"])
@@ -1871,27 +1919,7 @@ _CS_LIMITS = ("contiguous float32 tensors on the GPU, ms [B, C, H, W], pan [B, 1
               "multiples of it; fewer than 2^31 elements")
 
 
-def _cs_dense(name, arg, t, shape=None):
-    """``t`` must be a contiguous float32 tensor on the GPU, of ``shape`` when that is given."""
-    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-        raise ValueError(f"{name}: {arg} must be a contiguous float32 tensor on the GPU ({_CS_LIMITS})")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name}: {arg} is {tuple(t.shape)}, need {tuple(shape)} ({_CS_LIMITS})")
-    return t
-
-
-def _cs_images(name, ms, pan, ratio=None):
-    """(B, C, H, W) of a component-substitution call after the checks on its images."""
-    _cs_dense(name, "ms", ms)
-    if ms.dim() != 4:
-        raise ValueError(f"{name}: ms is {tuple(ms.shape)}, need [B, C, H, W] ({_CS_LIMITS})")
-    b, c, h, w = ms.shape
-    if not 1 <= c <= 14 or min(b, h, w) < 1 or ms.numel() > 2 ** 31 - 1:
-        raise ValueError(f"{name}: B={b} C={c} H={h} W={w} is not supported ({_CS_LIMITS})")
-    if ratio is not None and (ratio not in (2, 4) or h % ratio or w % ratio):
-        raise ValueError(f"{name}: H={h} W={w} ratio={ratio} is not supported ({_CS_LIMITS})")
-    _cs_dense(name, "pan", pan, (b, 1, h, w))
-    return b, c, h, w
+_CS = _Family("ms", 14, _CS_LIMITS)
 
 
 def _cs_mode(name, method):
@@ -1915,7 +1943,7 @@ def plane_moments(ms, pan, out=None, workspace=None):
     with the fp64 matrix instruction.  Sums in fp64 in one fixed order, no atomics: the same bits on every run; the matrix is
     exactly symmetric.  With ``out=`` and ``workspace=`` nothing is allocated or synchronised.  Not differentiable: the inputs
     are detached."""
-    b, c, h, w = _cs_images("plane_moments", ms, pan)
+    b, c, h, w = _images(_CS, "plane_moments", ms, pan)[:4]
     y = _f64("plane_moments", "out", out, (b, c + 1, c + 2), ms.device)
     ws, nbytes = _lent("plane_moments", workspace, lib.tmdiff_plane_gram_workspace_bytes(b, c, h, w),
                        lambda: plane_moments_workspace(b, c, h, w, ms.device))
@@ -1957,14 +1985,9 @@ def cs_inject(ms_exp, pan, coef, method, out=None):
     evaluated in fp64 and rounded to fp32 once.  ``out`` may be ms_exp itself (in place); it must not overlap pan or coef.
     With ``out=`` nothing is allocated or synchronised.  Not differentiable: the inputs are detached."""
     mode = _cs_mode("cs_inject", method)
-    b, c, h, w = _cs_images("cs_inject", ms_exp, pan)
+    b, c, h, w = _images(_CS, "cs_inject", ms_exp, pan)[:4]
     co = _f64("cs_inject", "coef", coef, (b, 2 * c + 3), ms_exp.device)
-    y = _cs_dense("cs_inject", "out", out if out is not None else torch.empty_like(ms_exp), (b, c, h, w))
-    for other, what in ((pan, "pan"), (co, "coef")):
-        if _overlaps(y, other):
-            raise ValueError(f"cs_inject: out overlaps {what}")
-    if y.data_ptr() != ms_exp.data_ptr() and _overlaps(y, ms_exp):
-        raise ValueError("cs_inject: out overlaps ms_exp without being ms_exp")
+    y = _inject_out(_CS, "cs_inject", out, ms_exp, ((pan, "pan"), (co, "coef")))
     check(lib.tmdiff_cs_inject(ms_exp.detach().data_ptr(), pan.detach().data_ptr(), co.detach().data_ptr(), y.data_ptr(), b, c, h, w,
                                mode, stream_ptr()), "cs_inject")
     return y
@@ -1997,25 +2020,17 @@ def cs_fuse(ms_exp, pan, sensor=None, ratio=4, method="gsa", lr_ms=None, out=Non
     ``mtf_degrade`` caches its own: call once before capturing into a graph.  Not differentiable: the inputs are detached."""
     from . import metrics
     _cs_mode("cs_fuse", method)
-    b, c, h, w = _cs_images("cs_fuse", ms_exp, pan, ratio)
+    b, c, h, w = _images(_CS, "cs_fuse", ms_exp, pan, ratio)[:4]
     ms_exp, pan = ms_exp.detach(), pan.detach()
-    if out is not None:
-        _cs_dense("cs_fuse", "out", out, (b, c, h, w))
-        if _overlaps(out, pan):
-            raise ValueError("cs_fuse: out overlaps pan")
-    buf = buffers if buffers is not None else cs_fuse_buffers(b, c, h, w, ms_exp.device, ratio)
-    if buf["shape"] != (b, c, h, w, ratio) or buf["full"].device != ms_exp.device:
-        raise ValueError(f"cs_fuse: buffers made for {buf['shape']}, the call is {(b, c, h, w, ratio)}")
+    _chain_out(_CS, "cs_fuse", out, (b, c, h, w), ((pan, "pan"),))
+    buf = _chain_buffers("cs_fuse", buffers, lambda: cs_fuse_buffers(b, c, h, w, ms_exp.device, ratio), (b, c, h, w, ratio), "full",
+                         ms_exp.device)
     low = None
     if method == "gsa":
         if sensor is None:
             raise ValueError("cs_fuse: method 'gsa' needs the sensor whose PAN gain shapes the reduced-scale PAN")
         gain = metrics.mtf_gains(sensor, c)[1]
-        if lr_ms is None:
-            ms_low = buf["ms_low"]
-            ms_low.copy_(ms_exp[..., ratio // 2::ratio, ratio // 2::ratio])
-        else:
-            ms_low = _cs_dense("cs_fuse", "lr_ms", lr_ms, (b, c, h // ratio, w // ratio)).detach()
+        ms_low = _reduced_ms(_CS, "cs_fuse", ms_exp, lr_ms, ratio, buf["ms_low"])
         pan_low = mtf_degrade(pan, gain, ratio, out=buf["pan_low"])
         low = plane_moments(ms_low, pan_low, out=buf["low"], workspace=buf["ws_low"])
     full = plane_moments(ms_exp, pan, out=buf["full"], workspace=buf["ws"])
@@ -2027,42 +2042,13 @@ _BDSD_LIMITS = ("contiguous float32 tensors on the GPU, ms [B, C, H, W], pan [B,
                 "multiples of it; block None or a multiple of the ratio that divides H and W; fewer than 2^31 elements")
 
 
-def _bdsd_dense(name, arg, t, shape=None):
-    """``t`` must be a contiguous float32 tensor on the GPU, of ``shape`` when that is given."""
-    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-        raise ValueError(f"{name}: {arg} must be a contiguous float32 tensor on the GPU ({_BDSD_LIMITS})")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name}: {arg} is {tuple(t.shape)}, need {tuple(shape)} ({_BDSD_LIMITS})")
-    return t
-
-
-def _bdsd_images(name, ms, pan, ratio=None, block=None):
-    """(B, C, H, W, blocks down, blocks across) of a BDSD call after the checks on its images; ``block`` is a side at their scale."""
-    _bdsd_dense(name, "ms", ms)
-    if ms.dim() != 4:
-        raise ValueError(f"{name}: ms is {tuple(ms.shape)}, need [B, C, H, W] ({_BDSD_LIMITS})")
-    b, c, h, w = ms.shape
-    extents = _bdsd_extents(name, b, c, h, w, ratio, block)
-    _bdsd_dense(name, "pan", pan, (b, 1, h, w))
-    return extents
-
-
-def _bdsd_extents(name, b, c, h, w, ratio=None, block=None):
-    """(B, C, H, W, blocks down, blocks across) after the checks on the extents."""
-    b, c, h, w = int(b), int(c), int(h), int(w)
-    if not 1 <= c <= 15 or min(b, h, w) < 1 or b * c * h * w > 2 ** 31 - 1:
-        raise ValueError(f"{name}: B={b} C={c} H={h} W={w} is not supported ({_BDSD_LIMITS})")
-    if ratio is not None and (ratio not in (2, 4) or h % ratio or w % ratio):
-        raise ValueError(f"{name}: H={h} W={w} ratio={ratio} is not supported ({_BDSD_LIMITS})")
-    if block is not None and (isinstance(block, bool) or int(block) != block or block < 1 or block % (ratio or 1) or h % block or w % block):
-        raise ValueError(f"{name}: block={block!r} for H={h} W={w} ratio={ratio or 1} is not supported ({_BDSD_LIMITS})")
-    return b, c, h, w, (1 if block is None else h // int(block)), (1 if block is None else w // int(block))
+_BDSD = _Family("ms", 15, _BDSD_LIMITS)
 
 
 def bdsd_moments_workspace(b, c, h, w, device, bs=None):
     """A workspace ``bdsd_moments`` accepts for [b, c, h, w] reduced-scale images in blocks of side ``bs`` (reusable; captured
     calls must keep it alive)."""
-    b, c, h, w, _, _ = _bdsd_extents("bdsd_moments", b, c, h, w, None, bs)
+    b, c, h, w, _, _ = _extents(_BDSD, "bdsd_moments", b, c, h, w, None, bs)
     return torch.empty(max(1, lib.tmdiff_bdsd_gram_workspace_bytes(b, c, h, w, int(bs or 0)) // 8), device=device, dtype=torch.float64)
 
 
@@ -2073,8 +2059,8 @@ def bdsd_moments(low_lp, low_pan, low_ms, bs=None, out=None, workspace=None):
     products are accumulated with the fp64 matrix instruction.  ``bs``: the side of the blocks at this scale, None for the whole
     image.  Sums in fp64 in one fixed order, no atomics: the same bits on every run; N is exactly symmetric.  With ``out=`` and
     ``workspace=`` nothing is allocated or synchronised.  Not differentiable: the inputs are detached."""
-    b, c, h, w, nby, nbx = _bdsd_images("bdsd_moments", low_lp, low_pan, None, bs)
-    _bdsd_dense("bdsd_moments", "low_ms", low_ms, (b, c, h, w))
+    b, c, h, w, nby, nbx = _images(_BDSD, "bdsd_moments", low_lp, low_pan, None, bs)
+    _dense(_BDSD, "bdsd_moments", "low_ms", low_ms, (b, c, h, w))
     y = _f64("bdsd_moments", "out", out, (b, nby, nbx, c + 1, 2 * c + 1), low_lp.device)
     ws, nbytes = _lent("bdsd_moments", workspace, lib.tmdiff_bdsd_gram_workspace_bytes(b, c, h, w, int(bs or 0)),
                        lambda: bdsd_moments_workspace(b, c, h, w, low_lp.device, bs))
@@ -2107,14 +2093,9 @@ def bdsd_inject(ms_exp, pan, gamma, block=None, out=None):
     weights of the block the pixel lies in (``block``: the full-scale side, None for one block), evaluated in fp64 and rounded to
     fp32 once.  ``out`` may be ms_exp itself (in place); it must not overlap pan or gamma.  With ``out=`` nothing is allocated or
     synchronised.  Not differentiable: the inputs are detached."""
-    b, c, h, w, nby, nbx = _bdsd_images("bdsd_inject", ms_exp, pan, None, block)
+    b, c, h, w, nby, nbx = _images(_BDSD, "bdsd_inject", ms_exp, pan, None, block)
     g = _f64("bdsd_inject", "gamma", gamma, (b, nby, nbx, c + 1, c), ms_exp.device)
-    y = _bdsd_dense("bdsd_inject", "out", out if out is not None else torch.empty_like(ms_exp), (b, c, h, w))
-    for other, what in ((pan, "pan"), (g, "gamma")):
-        if _overlaps(y, other):
-            raise ValueError(f"bdsd_inject: out overlaps {what}")
-    if y.data_ptr() != ms_exp.data_ptr() and _overlaps(y, ms_exp):
-        raise ValueError("bdsd_inject: out overlaps ms_exp without being ms_exp")
+    y = _inject_out(_BDSD, "bdsd_inject", out, ms_exp, ((pan, "pan"), (g, "gamma")))
     check(lib.tmdiff_bdsd_inject(ms_exp.detach().data_ptr(), pan.detach().data_ptr(), g.detach().data_ptr(), y.data_ptr(), b, c, h, w,
                                  int(block or 0), stream_ptr()), "bdsd_inject")
     return y
@@ -2124,7 +2105,7 @@ def bdsd_buffers(b, c, h, w, device, ratio=4, block=None):
     """Every scratch tensor of ``bdsd`` for [b, c, h, w] images: with them and ``out=`` a call allocates nothing and can be
     captured into a graph.  "ms_low", "lp_low", "pan_low": the reduced-scale MS, its low-pass and the reduced PAN; "moments",
     "gamma": the float64 normal equations and weights per block; "ws": the workspace of ``bdsd_moments``."""
-    b, c, h, w, nby, nbx = _bdsd_extents("bdsd", b, c, h, w, ratio, block)
+    b, c, h, w, nby, nbx = _extents(_BDSD, "bdsd", b, c, h, w, ratio, block)
     f32, f64 = dict(device=device, dtype=torch.float32), dict(device=device, dtype=torch.float64)
     bs = None if block is None else int(block) // ratio
     return {"shape": (b, c, h, w, ratio, block), "ms_low": torch.empty(b, c, h // ratio, w // ratio, **f32),
@@ -2145,21 +2126,13 @@ def bdsd(ms_exp, pan, sensor, ratio=4, block=None, lr_ms=None, out=None, buffers
     ``buffers`` (``bdsd_buffers``) and ``out=`` nothing is allocated or synchronised; the tap tables are cached as ``mtf_degrade``
     caches its own: call once before capturing into a graph.  Not differentiable: the inputs are detached."""
     from . import metrics
-    b, c, h, w, _, _ = _bdsd_images("bdsd", ms_exp, pan, ratio, block)
+    b, c, h, w, _, _ = _images(_BDSD, "bdsd", ms_exp, pan, ratio, block)
     ms_exp, pan = ms_exp.detach(), pan.detach()
-    if out is not None:
-        _bdsd_dense("bdsd", "out", out, (b, c, h, w))
-        if _overlaps(out, pan):
-            raise ValueError("bdsd: out overlaps pan")
-    buf = buffers if buffers is not None else bdsd_buffers(b, c, h, w, ms_exp.device, ratio, block)
-    if buf["shape"] != (b, c, h, w, ratio, block) or buf["moments"].device != ms_exp.device:
-        raise ValueError(f"bdsd: buffers made for {buf['shape']}, the call is {(b, c, h, w, ratio, block)}")
+    _chain_out(_BDSD, "bdsd", out, (b, c, h, w), ((pan, "pan"),))
+    buf = _chain_buffers("bdsd", buffers, lambda: bdsd_buffers(b, c, h, w, ms_exp.device, ratio, block), (b, c, h, w, ratio, block),
+                         "moments", ms_exp.device)
     ms_gains, pan_gain = metrics.mtf_gains(sensor, c)
-    if lr_ms is None:
-        ms_low = buf["ms_low"]
-        ms_low.copy_(ms_exp[..., ratio // 2::ratio, ratio // 2::ratio])
-    else:
-        ms_low = _bdsd_dense("bdsd", "lr_ms", lr_ms, (b, c, h // ratio, w // ratio)).detach()
+    ms_low = _reduced_ms(_BDSD, "bdsd", ms_exp, lr_ms, ratio, buf["ms_low"])
     lp_low = fir_decimate(ms_low, _mtf_taps(ms_gains, ratio, ms_exp.device), 1, None, buf["lp_low"])
     pan_low = mtf_degrade(pan, pan_gain, ratio, out=buf["pan_low"])
     mo = bdsd_moments(lp_low, pan_low, ms_low, None if block is None else int(block) // ratio, out=buf["moments"], workspace=buf["ws"])
