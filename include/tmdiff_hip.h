@@ -896,6 +896,37 @@ int tmdiff_bdsd_inject(const float* ms_exp, const float* pan, const double* gamm
                        int32_t W, int32_t block, tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Conjugate gradients for Wald's consistency (csrc/cg.hip; host definition: tmdiff_amd/metrics.py, consistency_solve; the
+ * driver: tmdiff_amd/ops.py, consistency_solve): per-plane dot products and the vector updates of CGLS with coefficients that
+ * stay on the device.  Dense fp32 planes [planes, n]; nothing is allocated or synchronised, no atomics, no fences, the same
+ * bits on every run and on a graph replay.  The chunks of a plane, the summation order and the coefficients' rounding are
+ * written in the source's header.
+ *  plane_dots_partials (host function): the partial sums of a plane of n elements, 1 .. 256, a function of n alone.
+ *  plane_dots:    partials0[planes, plane_dots_partials(n0)] of <a0, b0> per plane, summed in fp64, and, when partials1 is not
+ *                 NULL, partials1[planes, plane_dots_partials(n1)] of <a1, b1> over planes of n1 elements in the same launch.
+ *                 b may be a (a squared norm: the plane is read once).
+ *  plane_totals:  out[pl * items + k] = the total of the `count` partial sums at partials + k * item_stride + pl * count, added
+ *                 in the order every consumer below adds them.
+ *  cg_step:       alpha = gamma / (qq + damp * pp) per plane from the partial sums gamma, pp [planes, partials(n_full)] and qq
+ *                 [planes, partials(n_low)] (pp is not read when damp == 0), 0 where the denominator is 0, rounded to float
+ *                 once; d = fma(alpha, p, d) over n_full elements (first != 0: d = alpha * p, d is not read), r = fma(-alpha, q, r)
+ *                 over n_low elements, and rr [planes, partials(n_low)] = the partial sums of the new <r, r>.
+ *  cg_direction:  beta = gamma_new / gamma_old per plane, 0 where gamma_old is 0, rounded to float once; p = fma(beta, p, s); pp
+ *                 (may be NULL) = the partial sums of the new <p, p>.
+ *                 Limits: planes >= 0, n >= 0, planes * n <= 2^31 - 1, damp >= 0; otherwise TMDIFF_E_UNSUPPORTED.
+ *                 (Added within version 6.)
+ * ------------------------------------------------------------------------------------ */
+int32_t tmdiff_plane_dots_partials(int32_t n);
+int tmdiff_plane_dots(const float* a0, const float* b0, int32_t n0, double* partials0, const float* a1, const float* b1, int32_t n1,
+                      double* partials1, int32_t planes, tmdiff_stream_t stream);
+int tmdiff_plane_totals(const double* partials, double* out, int32_t planes, int32_t count, int32_t items, int64_t item_stride,
+                        tmdiff_stream_t stream);
+int tmdiff_cg_step(const float* p, const float* q, float* d, float* r, const double* gamma, const double* qq, const double* pp,
+                   double damp, double* rr, int32_t planes, int32_t n_full, int32_t n_low, int32_t first, tmdiff_stream_t stream);
+int tmdiff_cg_direction(const float* s, float* p, const double* gamma_new, const double* gamma_old, double* pp, int32_t planes,
+                        int32_t n_full, tmdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Standalone attention operators of core/Attention.py (imported by nothing in the reference; built because the
  * north star names them).  All fp32.
  *  attn_fwd : out = softmax(q k^T * scale [key mask]) v per (batch, head); fp32 MFMA, online softmax.

@@ -244,6 +244,14 @@ SIGNATURES.update({
     "tmdiff_bdsd_gram": (C.c_int, [vp, vp, vp] + [C.c_int32] * 5 + [vp, vp, C.c_size_t, vp]),
     "tmdiff_bdsd_solve": (C.c_int, [vp, vp] + [C.c_int32] * 2 + [vp]),
     "tmdiff_bdsd_inject": (C.c_int, [vp] * 4 + [C.c_int32] * 5 + [vp]),
+    # conjugate gradients for Wald's consistency (csrc/cg.hip): a0, b0, n0, partials0, a1, b1, n1, partials1 | planes;
+    # partials, out | planes, count, items, item_stride;  p, q, d, r, gamma, qq, pp | damp | rr | planes, n_full, n_low, first;
+    # s, p, gamma_new, gamma_old, pp | planes, n_full
+    "tmdiff_plane_dots_partials": (C.c_int32, [C.c_int32]),
+    "tmdiff_plane_dots": (C.c_int, [vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_int32, vp]),
+    "tmdiff_plane_totals": (C.c_int, [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp]),
+    "tmdiff_cg_step": (C.c_int, [vp] * 7 + [C.c_double, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
+    "tmdiff_cg_direction": (C.c_int, [vp] * 5 + [C.c_int32, C.c_int32, vp]),
 })
 
 

@@ -208,10 +208,17 @@ class GeneralDiffusion(nn.Module):
         return self.p_sample_loop(x_in, prompt)        # the reference's positional slip, kept (ref :339)
 
     @torch.no_grad()
-    def sample(self, x_in, prompt, return_all=False, method="ddpm", steps=None):
-        """Clean entry point: fused image(s) for ``prompt``; method 'ddpm' (T steps) or 'dpmsolver'."""
+    def sample(self, x_in, prompt, return_all=False, method="ddpm", steps=None, consistency=None):
+        """Clean entry point: fused image(s) for ``prompt``; method 'ddpm' (T steps) or 'dpmsolver'.  ``consistency``: the
+        in-loop projection of ``sample_by_dpmsolver``; 'ddpm' refuses it (its loop treats the network output as noise inside
+        the fused ``ddpm_step``)."""
         if method == "dpmsolver":
-            return self.sample_by_dpmsolver(x_in, prompt, **({"steps": steps} if steps else {}))
+            kw = {"steps": steps} if steps else {}
+            if consistency is not None:
+                kw["consistency"] = consistency
+            return self.sample_by_dpmsolver(x_in, prompt, **kw)
+        if consistency is not None:
+            raise ValueError("sample: consistency=... needs method='dpmsolver' (the DDPM loop has no data prediction to project)")
         stack = self.p_sample_loop(x_in, continous=True, prompt=prompt)
         b = x_in["Res"].shape[0]
         return stack if return_all else stack[-b:]
@@ -227,28 +234,71 @@ class GeneralDiffusion(nn.Module):
         return NoiseScheduleVP(schedule="discrete", betas=self.betas)
 
     def _solve(self, x_in, prompt, model_type, model_kwargs, steps, order, method, denoise_to_zero=True, x_T=None, ns=None,
-               time_table=None, **wrap_kw):
-        """x_T / ns: given by the graph runner (drawn / built outside its capture); time_table: see _WrappedModel."""
+               time_table=None, project=None, **wrap_kw):
+        """x_T / ns: given by the graph runner (drawn / built outside its capture); time_table: see _WrappedModel; project:
+        applied to every data prediction after dynamic thresholding (``_consistency_projection``)."""
         x_T = self._noise(x_in["Res"]) if x_T is None else x_T
         ns = self._dpm_schedule() if ns is None else ns
         model_fn = model_wrapper(self.denoise_fn, ns, model_type=model_type, model_kwargs=model_kwargs, **wrap_kw)
         model_fn.time_table = time_table
         solver = DPM_Solver(model_fn, ns, algorithm_type="dpmsolver++", correcting_x0_fn="dynamic_thresholding")
+        if project is not None:
+            threshold = solver.correcting_x0_fn
+            solver.correcting_x0_fn = lambda x0, t=None: project(threshold(x0, t))
         x = solver.sample(x_T, steps=steps, order=order, skip_type="logSNR", method=method,
                           denoise_to_zero=denoise_to_zero)
         self.last_solver = solver
         return ops.add(x, x_in["MS"])
 
     @torch.no_grad()
-    def sample_by_dpmsolver(self, x_in, prompt, steps=30):
+    def sample_by_dpmsolver(self, x_in, prompt, steps=30, consistency=None):
         """ref :227-255: x_start-parameterised DPM-Solver++, singlestep order 3, logSNR grid, dynamic
-        thresholding, denoise-to-zero => steps + 1 network evaluations (reference hard-codes steps=30)."""
+        thresholding, denoise-to-zero => steps + 1 network evaluations (reference hard-codes steps=30).
+        ``consistency={"lr_ms": tensor, "sensor": name, "ratio": 4, "iters": 4, "damp": 0.0}`` (the last three optional) pulls
+        every data prediction, the denoise-to-zero one included, onto the known measurement, in the DDNM style: after dynamic
+        thresholding the predicted scene f0 = x0 + MS gets the correction d of ``ops.consistency_solve`` against lr_ms
+        ([B, C, H', W'], the extent of ``mtf_degrade`` at ``ratio``), and x0 += d.  With damp = 0 the solve converges to the
+        minimum-norm correction A^+ (lr_ms - A f0), the projection onto A f = lr_ms.  Buffers are made once per run.  With
+        ``consistency`` given the run is eager, also when ``sample_graph`` is on; ``None`` is the call without the argument."""
         x_in = self._prep_inputs(x_in)
-        if sample_graph.usable(self, x_in):
+        project = None if consistency is None else self._consistency_projection(x_in, consistency)
+        if project is None and sample_graph.usable(self, x_in):
             return sample_graph.dpmsolver(self, x_in, prompt, steps)
         with self._cached(x_in, prompt):
             return self._solve(x_in, prompt, "x_start", {"PAN": x_in["PAN"], "MS": x_in["MS"], "prompt": prompt},
-                               steps, 3, "singlestep")
+                               steps, 3, "singlestep", project=project)
+
+    @staticmethod
+    def _consistency_projection(x_in, consistency):
+        """x0 -> x0 + d for the ``consistency`` options of ``sample_by_dpmsolver``, with the buffers of the run."""
+        from . import metrics
+        if not isinstance(consistency, dict) or "lr_ms" not in consistency or "sensor" not in consistency or \
+                set(consistency) - {"lr_ms", "sensor", "ratio", "iters", "damp"}:
+            raise ValueError(f"sample_by_dpmsolver: consistency needs 'lr_ms' and 'sensor' and takes 'ratio', 'iters' and 'damp', "
+                             f"got {sorted(consistency) if isinstance(consistency, dict) else consistency!r}")
+        ms = x_in["MS"]
+        ratio, iters, damp = consistency.get("ratio", 4), consistency.get("iters", 4), consistency.get("damp", 0.0)
+        if ratio not in (1, 2, 4) or int(iters) != iters or iters < 0 or not float(damp) >= 0.0:
+            raise ValueError(f"sample_by_dpmsolver: consistency ratio={ratio} iters={iters} damp={damp} (ratio 1, 2 or 4, iters a "
+                             f"whole number >= 0, damp >= 0)")
+        b, c, h, w = ms.shape
+        lr = consistency["lr_ms"]
+        if not torch.is_tensor(lr) or tuple(lr.shape) != (b, c, *ops.fir_decimate_shape(h, w, ratio)) or lr.device != ms.device:
+            raise ValueError(f"sample_by_dpmsolver: consistency lr_ms must be the degradation of MS {tuple(ms.shape)} at ratio "
+                             f"{ratio} on {ms.device}, got {tuple(lr.shape) if torch.is_tensor(lr) else lr!r}")
+        lr = lr.detach().float().contiguous()
+        taps = ops._mtf_taps(metrics.band_gains(consistency["sensor"], c), ratio, ms.device)
+        ws = ops.consistency_solve_workspace(b, c, h, w, ratio, iters, ms.device)
+        f0, d = torch.empty_like(ms), torch.empty_like(ms)
+
+        def project(x0):
+            # x0 is changed in place, as the thresholding before it does: data_prediction_fn hands both a tensor of their own
+            # (ops.x0_from_model allocates its result), never the network's output or the sampler's state
+            ops.add(x0, ms, out=f0)
+            ops.consistency_solve(f0, lr, taps, ratio, iters, damp, out=f0, correction_out=d, workspace=ws)
+            return ops.add(x0, d, out=x0)
+
+        return project
 
     # The next three exist in the reference (:257-335) but pass arguments WavBEST.forward does not take
     # (a `wav` tensor, swapped PAN/MS order), so they fail there as they do here; kept for the API surface.

@@ -1588,6 +1588,155 @@ def _mtf_taps(gains, ratio, device, scales=None):
     return taps
 
 
+# ---- Wald consistency as a CGLS solve (csrc/cg.hip; definition: metrics.consistency_solve) ---------------------------
+def plane_dots_partials(n):
+    """The partial sums ``plane_dots`` keeps for a plane of n elements (1 .. 256, a function of n alone)."""
+    return int(lib.tmdiff_plane_dots_partials(int(n)))
+
+
+def _dot_planes(name, t, like=None):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()):
+        raise ValueError(f"{name}: need contiguous float32 [B, C, H, W] tensors on the GPU")
+    if like is not None and (t.shape != like.shape or t.device != like.device):
+        raise ValueError(f"{name}: operands {tuple(like.shape)} and {tuple(t.shape)} do not belong together")
+    if t.numel() > 2 ** 31 - 1:
+        raise ValueError(f"{name}: shape {tuple(t.shape)} is not supported (fewer than 2^31 elements)")
+    return t.detach()
+
+
+def _launch_dots(name, ops2, planes):
+    """One launch for up to two dots: ops2 = [(a, b, partial sums)], the planes of each pair of their own extent."""
+    (a0, b0, p0), (a1, b1, p1) = ops2[0], (ops2[1] if len(ops2) > 1 else (None, None, None))
+    n = lambda t: 0 if t is None else t.shape[2] * t.shape[3]
+    ptr = lambda t: None if t is None else t.data_ptr()
+    check(lib.tmdiff_plane_dots(ptr(a0), ptr(b0), n(a0), ptr(p0), ptr(a1), ptr(b1), n(a1), ptr(p1), planes, stream_ptr()), name)
+
+
+def plane_dots(a, b=None, out=None, workspace=None):
+    """Per-plane inner products <a, b> of float32 [B, C, H, W] tensors, float64 [B, C]; ``b`` None: the squared norms <a, a>.
+    ``a`` (and ``b``) may be a pair of tensors with the same [B, C] and extents of their own: both dots are made by one launch and
+    the result is float64 [2, B, C].  Summed in fp64 in one fixed order that depends on the plane's extent alone (csrc/cg.hip):
+    each workgroup writes the partial sum of its chunk into ``workspace`` (float64, B * C * ``plane_dots_partials(H * W)`` elements
+    per dot), a second launch adds a plane's partials.  No atomics, no host read: the same bits on every run; with ``out=`` and
+    ``workspace=`` nothing is allocated or synchronised."""
+    name = "plane_dots"
+    pair = isinstance(a, (tuple, list))
+    aa = list(a) if pair else [a]
+    bb = [None] * len(aa) if b is None else (list(b) if pair and isinstance(b, (tuple, list)) else [b])
+    if len(aa) not in (1, 2) or len(bb) != len(aa):
+        raise ValueError(f"{name}: one tensor or a pair of them, and b to match")
+    aa = [_dot_planes(name, t) for t in aa]
+    bb = [x if y is None else _dot_planes(name, y, x) for x, y in zip(aa, bb)]
+    bc = tuple(aa[0].shape[:2])
+    if any(tuple(t.shape[:2]) != bc or t.device != aa[0].device for t in aa):
+        raise ValueError(f"{name}: the operands of a pair share [B, C] and the device")
+    planes = bc[0] * bc[1]
+    counts = [plane_dots_partials(t.shape[2] * t.shape[3]) for t in aa]
+    need = planes * sum(counts)
+    ws, _ = _lent(name, workspace, 8 * need, lambda: torch.empty(max(1, need), device=aa[0].device, dtype=torch.float64))
+    if ws.dtype != torch.float64:
+        raise ValueError(f"{name}: workspace must be float64")
+    y = _f64(name, "out", out, (2, *bc) if pair else bc, aa[0].device)
+    parts, lo = [], 0
+    for cnt in counts:
+        parts.append(ws.view(-1)[lo:lo + planes * cnt])
+        lo += planes * cnt
+    _launch_dots(name, list(zip(aa, bb, parts)), planes)
+    for k, (cnt, part) in enumerate(zip(counts, parts)):
+        check(lib.tmdiff_plane_totals(part.data_ptr(), (y[k] if pair else y).data_ptr(), planes, cnt, 1, 0, stream_ptr()), name)
+    return y
+
+
+def consistency_solve_workspace(b, c, h, w, ratio, iters, device):
+    """The buffers ``consistency_solve`` accepts for [b, c, h, w] scenes at ``ratio`` and up to ``iters`` iterations (reusable;
+    captured calls must keep them alive): the float32 vectors r, q (low resolution) and d, s, p (full resolution) and the float64
+    partial sums of the dots."""
+    lh, lw = fir_decimate_shape(h, w, ratio)
+    planes = b * c
+    cf, cl = plane_dots_partials(h * w), plane_dots_partials(lh * lw)
+    f32 = lambda *shape: torch.empty(shape, device=device, dtype=torch.float32)
+    return {"r": f32(b, c, lh, lw), "q": f32(b, c, lh, lw), "d": f32(b, c, h, w), "s": f32(b, c, h, w), "p": f32(b, c, h, w),
+            "partials": torch.empty(planes * (3 * cf + (int(iters) + 2) * cl), device=device, dtype=torch.float64)}
+
+
+def consistency_solve(f0, lr_ms, taps, ratio, iters, damp=0.0, out=None, correction_out=None, info_out=None, workspace=None):
+    """Wald's consistency as a solve (definition: ``metrics.consistency_solve``): ``iters`` steps of CGLS, per plane, on
+    min ||A f - lr_ms||^2 + damp ||f - f0||^2 for A = ``fir_decimate(., taps, ratio)`` at the offset ratio // 2, started from the
+    correction d = 0; returns f = f0 + d in ``out`` (allocated when None; may be ``f0``).  f0 [B, C, H, W], lr_ms [B, C, H', W']
+    the extent of ``fir_decimate``, taps as ``fir_decimate`` takes them.  ``correction_out`` receives d, ``info_out`` (float64
+    [B, C, iters + 1]) the squared residual norm ||r||^2 per plane before the first iteration and after every one, as the
+    recurrence carries it.  With damp = 0 the iterates converge to f0 + A^+ (lr_ms - A f0), the projection onto the consistent
+    scenes.  An iteration is six launches: ``fir_decimate`` (q = A p), the dot <q, q>, the step (d += alpha p, r -= alpha q and the
+    partial sums of ||r||^2), ``fir_decimate_adjoint`` (s = A^T r - damp d), the dot <s, s> and the direction (p = s + beta p);
+    alpha and beta are formed on the device from the partial sums, 0 where their denominator is 0, so a plane that is already
+    consistent comes back as it went in and no plane sees another.  The last iteration's direction is not formed: nothing reads
+    it.  With ``out``, ``workspace`` (``consistency_solve_workspace``) and whichever of ``correction_out`` / ``info_out`` is wanted
+    given, nothing is allocated or synchronised and the call can be captured into a graph.  Limits: ``fir_decimate``'s."""
+    name = "consistency_solve"
+    if int(iters) != iters or iters < 0 or not float(damp) >= 0.0:
+        raise ValueError(f"{name}: iters={iters} damp={damp} (iters a whole number >= 0, damp >= 0)")
+    iters, damp = int(iters), float(damp)
+    _fir_taps(name, taps, ratio, None)
+    f0 = _dot_planes(name, f0)
+    b, c, h, w = f0.shape
+    low = (b, c, *fir_decimate_shape(h, w, ratio))
+    if not (torch.is_tensor(lr_ms) and lr_ms.is_cuda and lr_ms.dtype == torch.float32 and lr_ms.is_contiguous()) or tuple(lr_ms.shape) != low:
+        raise ValueError(f"{name}: lr_ms must be a contiguous float32 {list(low)} tensor on the GPU, the degradation of f0 "
+                         f"{tuple(f0.shape)} at ratio {ratio}")
+    y = out if out is not None else torch.empty_like(f0)
+    ws = workspace if workspace is not None else consistency_solve_workspace(b, c, h, w, ratio, iters, f0.device)
+    d = correction_out if correction_out is not None else ws["d"]
+    for t, what in ((y, "out"), (d, "correction_out"), (ws["s"], "workspace s"), (ws["p"], "workspace p")):
+        if tuple(t.shape) != tuple(f0.shape):
+            raise ValueError(f"{name}: {what} must be {tuple(f0.shape)}, got {tuple(t.shape)}")
+        _chk(t, what)
+    r, q, s, p = ws["r"], ws["q"], ws["s"], ws["p"]
+    if tuple(r.shape) != low or tuple(q.shape) != low:
+        raise ValueError(f"{name}: workspace r, q must be {low}")
+    planes, nf, nl = b * c, h * w, low[2] * low[3]
+    cf, cl = plane_dots_partials(nf), plane_dots_partials(nl)
+    part = ws["partials"]
+    if not (part.is_cuda and part.dtype == torch.float64 and part.is_contiguous() and part.numel() >= planes * (3 * cf + (iters + 2) * cl)):
+        raise ValueError(f"{name}: workspace partials: float64, at least {planes * (3 * cf + (iters + 2) * cl)} elements")
+    part = part.view(-1)
+    gam = [part[:planes * cf], part[planes * cf:2 * planes * cf]]
+    pp = part[2 * planes * cf:3 * planes * cf]
+    qq = part[3 * planes * cf:3 * planes * cf + planes * cl]
+    rr0 = 3 * planes * cf + planes * cl
+    rr = [part[rr0 + k * planes * cl:rr0 + (k + 1) * planes * cl] for k in range(iters + 1)]
+    info = None if info_out is None else _f64(name, "info_out", info_out, (b, c, iters + 1), f0.device)
+    lr = lr_ms.detach()
+    fir_decimate(f0, taps, ratio, None, q)
+    add(lr, q, -1.0, out=r)                                         # r = lr - A f0
+    if iters == 0:
+        if info is not None:
+            _launch_dots(name, [(r, r, rr[0])], planes)
+        if correction_out is not None:
+            d.zero_()
+    else:
+        fir_decimate_adjoint(r, taps, (h, w), ratio, None, p)       # s = A^T r (d = 0) and p = s
+        _launch_dots(name, [(r, r, rr[0]), (p, p, gam[0])], planes)
+    for k in range(iters):
+        fir_decimate(p, taps, ratio, None, q)
+        _launch_dots(name, [(q, q, qq)], planes)
+        ppk = None if damp == 0.0 else (gam[0] if k == 0 else pp)  # <p, p>: at the start p = s
+        check(lib.tmdiff_cg_step(p.data_ptr(), q.data_ptr(), d.data_ptr(), r.data_ptr(), gam[k % 2].data_ptr(), qq.data_ptr(),
+                                 None if ppk is None else ppk.data_ptr(), damp, rr[k + 1].data_ptr(), planes, nf, nl, int(k == 0),
+                                 stream_ptr()), name)
+        if k + 1 < iters:
+            fir_decimate_adjoint(r, taps, (h, w), ratio, None, s, d, 1.0, -damp)
+            _launch_dots(name, [(s, s, gam[(k + 1) % 2])], planes)
+            check(lib.tmdiff_cg_direction(s.data_ptr(), p.data_ptr(), gam[(k + 1) % 2].data_ptr(), gam[k % 2].data_ptr(),
+                                          None if damp == 0.0 else pp.data_ptr(), planes, nf, stream_ptr()), name)
+    if iters:
+        add(f0, d, out=y)
+    elif y.data_ptr() != f0.data_ptr():
+        y.copy_(f0)
+    if info is not None:
+        check(lib.tmdiff_plane_totals(rr[0].data_ptr(), info.data_ptr(), planes, cl, iters + 1, planes * cl, stream_ptr()), name)
+    return y
+
+
 # ---- HQNR: Khan's D_lambda, block-wise D_s (csrc/metrics.hip, csrc/mtf.hip; definitions: tmdiff_amd/metrics.py) ------
 _DSBLOCK_LIMITS = "1 <= C <= 16, block 8, 16 or 32, mirror padding no longer than the axis, fewer than 2^31 elements, q > 0"
 

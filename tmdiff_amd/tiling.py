@@ -153,8 +153,12 @@ def unpatch_16(patch):
     return split_tiles(p[None], p.shape[1] // 4, p.shape[2] // 4)
 
 
+_IN_LOOP_NEEDS_FUSED = ("consistency inside the sampler steps needs the fused tile mode (overlap=k), where the sampler steps the scene "
+                        "as a whole: in the independent mode a tile's border is not the scene's replicate border")
+
+
 @torch.no_grad()
-def sample_tiled(diffusion, scene, prompt, tile=64, method="dpmsolver", steps=20, max_batch=32, overlap=None):
+def sample_tiled(diffusion, scene, prompt, tile=64, method="dpmsolver", steps=20, max_batch=32, overlap=None, consistency=None):
     """Fuse a large scene tile by tile.  ``scene`` = {'MS': [B,C,H,W], 'PAN': [B,1,H,W]} (Res optional).
 
     ``overlap=None`` (independent mode): disjoint tiles, one diffusion chain per tile with its own noise and its own
@@ -168,7 +172,13 @@ def sample_tiled(diffusion, scene, prompt, tile=64, method="dpmsolver", steps=20
     and no seam is left.  Scene extents need not be multiples of the tile.  The UNet work grows by about
     (tile / (tile - k))^2.  Not covered: more than one rank (ValueError; use the independent mode -- sharding tiles per
     step needs an all-gather per step), captured-graph sampling (the fused mode runs eagerly, with the same result, also
-    when ``sample_graph`` is on), the gather folded into the stem kernel, training."""
+    when ``sample_graph`` is on), the gather folded into the stem kernel, training.
+
+    ``consistency``: the in-loop projection of ``GeneralDiffusion.sample_by_dpmsolver``, handed to ``diffusion.sample``; fused
+    mode only, because there the sampler steps the scene as a whole -- a tile's border is not the scene's replicate border, so
+    the independent mode raises ValueError."""
+    if consistency is not None and overlap is None:
+        raise ValueError(_IN_LOOP_NEEDS_FUSED)
     if overlap is not None:
         if tdist.dist.is_initialized() and tdist.dist.get_world_size() > 1:
             raise ValueError("sample_tiled: the fused mode (overlap=k) runs on one rank only; use the independent mode "
@@ -180,7 +190,8 @@ def sample_tiled(diffusion, scene, prompt, tile=64, method="dpmsolver", steps=20
         wrapped = TiledDenoiser(net, tile, overlap, max_batch)
         diffusion.denoise_fn = wrapped
         try:
-            return diffusion.sample(x_in, prompt, method=method, **({"steps": steps} if method == "dpmsolver" else {}))
+            return diffusion.sample(x_in, prompt, method=method, **({"steps": steps} if method == "dpmsolver" else {}),
+                                    **({} if consistency is None else {"consistency": consistency}))
         finally:
             diffusion.denoise_fn = net
             wrapped.end_condition_cache()
@@ -252,6 +263,76 @@ def consistency_refine(fused, lr_ms, sensor, ratio=4, iters=8, relax=1.0, out=No
 
 
 @torch.no_grad()
+def consistency_solve(fused, lr_ms, sensor, ratio=4, iters=8, damp=0.0, out=None):
+    """Solve for Wald's consistency A(fused) = lr_ms where ``consistency_refine`` refines towards it: ``iters`` steps of conjugate
+    gradients on the normal equations (CGLS) of min ||A f - lr_ms||^2 + damp ||f - fused||^2, per plane, started at ``fused``
+    (definition: ``metrics.consistency_solve``).  An iteration costs one A and one A^T, as a Landweber step does, and eight of
+    them leave 6 to 9 times less residual than eight Landweber steps (0.055 against 0.32 of the start on the 4 x 48 x 48
+    white-noise scene of tests/test_consistency_cg_host.py).  With damp = 0 the iterates converge to the projection of ``fused``
+    onto the consistent scenes; damp > 0 keeps the result near ``fused`` at the price of a residual that settles above zero.
+    Arguments and checks are ``consistency_refine``'s, with ``damp`` >= 0 in place of ``relax``.  Tensors on the GPU go through
+    ``ops.consistency_solve`` (nothing is read back; the tap table is cached on first use: call once before capturing); host
+    tensors and arrays go through the float64 definition.  ``out`` (device): receives the result and may be ``fused``."""
+    from . import metrics
+    if not float(damp) >= 0.0 or int(iters) != iters or iters < 0:
+        raise ValueError(f"consistency_solve: damp={damp} iters={iters} (damp >= 0, iters a whole number >= 0)")
+    if len(fused.shape) != 4 or tuple(lr_ms.shape) != (*fused.shape[:2], *metrics.fir_decimate_shape(*fused.shape[2:], ratio)[0]):
+        raise ValueError(f"consistency_solve: fused {tuple(fused.shape)} and lr_ms {tuple(lr_ms.shape)} ([B, C, H, W] and its "
+                         f"degradation at ratio {ratio})")
+    gains = metrics.band_gains(sensor, fused.shape[1])
+    if torch.is_tensor(fused) and fused.is_cuda:
+        if ratio not in (1, 2, 4):
+            raise ValueError(f"consistency_solve: ratio={ratio} (1, 2 or 4 on the device)")
+        f = fused.detach().float().contiguous()
+        if out is None:
+            out = torch.empty_like(f)
+        return ops.consistency_solve(f, lr_ms.detach().float().contiguous(), ops._mtf_taps(gains, ratio, f.device), ratio, iters,
+                                     damp, out=out)
+    f = metrics.consistency_solve(fused, lr_ms, gains, ratio, iters, damp)
+    return torch.from_numpy(f) if torch.is_tensor(fused) else f
+
+
+def _consistency_options(name, consistency, in_loop_allowed=False):
+    """The ``consistency`` option of the fuse functions, checked: None, or (method, keyword arguments of the post-hoc call or None
+    when it is switched off, options of the in-loop projection or None).  "method" is "landweber" (the default: ``consistency_refine``
+    with "iters" and "relax") or "cg" (``consistency_solve`` with "iters" and "damp"; in ``fuse_scene`` also "in_loop" and
+    "iters_post")."""
+    if consistency is None:
+        return None
+    keys = {"method", "iters", "relax", "damp"} | ({"in_loop", "iters_post"} if in_loop_allowed else set())
+    if not isinstance(consistency, dict) or set(consistency) - keys:
+        raise ValueError(f"{name}: consistency={consistency!r} (None or a dict with 'iters' and 'relax', or with 'method': 'cg', "
+                         f"'iters' and 'damp'{', in_loop and iters_post' if in_loop_allowed else ''})")
+    method = consistency.get("method", "landweber")
+    if method not in ("landweber", "cg"):
+        raise ValueError(f"{name}: consistency method {method!r} ('landweber' or 'cg')")
+    refused = {"landweber": ("damp", "in_loop", "iters_post"), "cg": ("relax",)}[method]
+    if any(k in consistency for k in refused):
+        raise ValueError(f"{name}: consistency={consistency!r}: method {method!r} does not take {' / '.join(repr(k) for k in refused)}")
+    if method == "landweber":
+        return method, {k: consistency[k] for k in ("iters", "relax") if k in consistency}, None
+    post = {k: consistency[k] for k in ("iters", "damp") if k in consistency}
+    loop = None
+    if consistency.get("in_loop"):
+        loop = dict(post)
+        if "iters_post" in consistency:
+            post["iters"] = consistency["iters_post"]
+    elif "iters_post" in consistency:
+        raise ValueError(f"{name}: consistency 'iters_post' goes with 'in_loop': True")
+    for opts in (post, loop or {}):
+        if "iters" in opts and (int(opts["iters"]) != opts["iters"] or opts["iters"] < 0) or not float(opts.get("damp", 0.0)) >= 0.0:
+            raise ValueError(f"{name}: consistency={consistency!r} (iters whole numbers >= 0, damp >= 0)")
+    return method, (None if loop is not None and post.get("iters", 8) == 0 else post), loop
+
+
+def _apply_consistency(options, scene, lr_ms, sensor, ratio, **kw):
+    method, post, _ = options
+    if post is None:
+        return scene
+    return (consistency_refine if method == "landweber" else consistency_solve)(scene, lr_ms, sensor, ratio, **post, **kw)
+
+
+@torch.no_grad()
 def fuse_scene(diffusion, lr_ms, pan, prompt, ratio=4, score=False, interp="bilinear", sensor=None, consistency=None,
                **sample_tiled_kwargs):
     """From the raw pair to the fused scene: lr_ms [B, C, h, w] is upsampled by ``ratio`` (2 or 4) on the device into the ``MS``
@@ -266,14 +347,20 @@ def fuse_scene(diffusion, lr_ms, pan, prompt, ratio=4, score=False, interp="bili
     is (the conditioning ``MS`` itself with "poly23"); ``sensor`` names the row of ``metrics.MTF_GAINS`` and is required.
     ``consistency={"iters": n, "relax": w}`` (either key optional) refines the stitched scene with ``consistency_refine`` against
     lr_ms before it is returned or scored, and needs ``sensor``; ``None`` changes nothing.  The refinement lowers the residual
-    A(scene) - lr_ms, fast in its smooth part and slowly in the rest (see ``consistency_refine``); it does not solve for it."""
+    A(scene) - lr_ms, fast in its smooth part and slowly in the rest (see ``consistency_refine``); it does not solve for it.
+    ``consistency={"method": "cg", "iters": n, "damp": w}`` solves for it instead, with ``consistency_solve``; "method" defaults
+    to "landweber", the path above, which refuses "damp" as "cg" refuses "relax".  With "cg", ``"in_loop": True`` also hands the
+    raw lr_ms to the sampler, which then projects every data prediction of the DPM-Solver run onto A f = lr_ms
+    (``GeneralDiffusion.sample_by_dpmsolver``) with the same "iters" and "damp"; that needs the fused tile mode (``overlap=k``) and
+    raises ValueError in the independent one.  The post-hoc solve still runs, with "iters_post" iterations when that key is
+    given, unless "iters_post" is 0."""
     if score not in (False, True, "hqnr"):
         raise ValueError(f"fuse_scene: score={score!r} (False, True or 'hqnr')")
-    if consistency is not None:
-        if sensor is None:
-            raise ValueError("fuse_scene(consistency=...) needs the sensor whose MTF gains shape the degradation")
-        if not isinstance(consistency, dict) or set(consistency) - {"iters", "relax"}:
-            raise ValueError(f"fuse_scene: consistency={consistency!r} (None or a dict with 'iters' and 'relax')")
+    if consistency is not None and sensor is None:
+        raise ValueError("fuse_scene(consistency=...) needs the sensor whose MTF gains shape the degradation")
+    options = _consistency_options("fuse_scene", consistency, in_loop_allowed=True)
+    if options is not None and options[2] is not None and sample_tiled_kwargs.get("overlap") is None:
+        raise ValueError(_IN_LOOP_NEEDS_FUSED)          # sample_tiled's refusal, before any device work is done
     if isinstance(score, str) and sensor is None:
         raise ValueError("fuse_scene(score='hqnr') needs the sensor whose MTF gains shape the filters")
     if interp not in ("bilinear", "poly23"):
@@ -283,9 +370,11 @@ def fuse_scene(diffusion, lr_ms, pan, prompt, ratio=4, score=False, interp="bili
         raise ValueError(f"fuse_scene: pan {tuple(pan.shape)} is not [B, 1, {ratio} h, {ratio} w] of lr_ms {tuple(lr_ms.shape)}")
     lr_ms, pan = lr_ms.float().contiguous(), pan.float().contiguous()
     ms = ops.upsample_poly23(lr_ms, ratio) if interp == "poly23" else ops.upsample_bilinear(lr_ms, ratio)
+    if options is not None and options[2] is not None:
+        sample_tiled_kwargs = dict(sample_tiled_kwargs, consistency={"lr_ms": lr_ms, "sensor": sensor, "ratio": ratio, **options[2]})
     scene = sample_tiled(diffusion, {"MS": ms, "PAN": pan}, prompt, **sample_tiled_kwargs)
-    if consistency is not None:
-        scene = consistency_refine(scene, lr_ms, sensor, ratio, **consistency)
+    if options is not None:
+        scene = _apply_consistency(options, scene, lr_ms, sensor, ratio)
     if not score:
         return scene
     from . import metrics
@@ -302,8 +391,7 @@ def _classical(name, on_device, on_host, lr_ms, pan, sensor, ratio, score, consi
     from . import metrics
     if score not in (False, True, "hqnr"):
         raise ValueError(f"{name}: score={score!r} (False, True or 'hqnr')")
-    if consistency is not None and (not isinstance(consistency, dict) or set(consistency) - {"iters", "relax"}):
-        raise ValueError(f"{name}: consistency={consistency!r} (None or a dict with 'iters' and 'relax')")
+    options = _consistency_options(name, consistency)
     if (consistency is not None or isinstance(score, str)) and sensor is None:
         raise ValueError(f"{name}: consistency=... and score='hqnr' need the sensor whose MTF gains shape the filters")
     if ratio not in (2, 4) or len(lr_ms.shape) != 4 or len(pan.shape) != 4 or pan.shape[0] != lr_ms.shape[0] or pan.shape[1] != 1 or \
@@ -314,8 +402,8 @@ def _classical(name, on_device, on_host, lr_ms, pan, sensor, ratio, score, consi
         lr_ms, pan = lr_ms.detach().float().contiguous(), pan.detach().float().contiguous()
         ms_exp = ops.upsample_poly23(lr_ms, ratio)
         scene = on_device(ms_exp, pan, lr_ms)
-        if consistency is not None:
-            scene = consistency_refine(scene, lr_ms, sensor, ratio, out=scene, **consistency)
+        if options is not None:
+            scene = _apply_consistency(options, scene, lr_ms, sensor, ratio, out=scene)
         if not score:
             return scene
         if isinstance(score, str):
@@ -324,8 +412,8 @@ def _classical(name, on_device, on_host, lr_ms, pan, sensor, ratio, score, consi
     if score:
         raise ValueError(f"{name}: scores are made on the GPU; score host data with the host functions of metrics")
     scene = on_host(metrics.upsample_poly23(lr_ms, ratio), pan, lr_ms)
-    if consistency is not None:
-        scene = consistency_refine(scene, lr_ms, sensor, ratio, **consistency)
+    if options is not None:
+        scene = _apply_consistency(options, scene, lr_ms, sensor, ratio)
     return torch.from_numpy(scene) if torch.is_tensor(lr_ms) and not torch.is_tensor(scene) else scene
 
 
@@ -338,7 +426,8 @@ def classical_fuse(lr_ms, pan, sensor, ratio=4, mode="hpm", score=False, consist
     arrays go through the float64 definitions.  ``score`` and ``consistency`` mean what they mean in ``fuse_scene``:
     ``score=True`` returns (scene, ``metrics.quality_fullres(lr_ms, pan, scene)``), ``score="hqnr"`` returns (scene,
     ``metrics.quality_hqnr(ms_exp, pan, scene, sensor, ratio)``) with the ms_exp that was already made, and
-    ``consistency={"iters": n, "relax": w}`` refines the scene with ``consistency_refine`` against lr_ms first.  Scores exist on
+    ``consistency={"iters": n, "relax": w}`` refines the scene with ``consistency_refine`` against lr_ms first
+    (``{"method": "cg", "iters": n, "damp": w}``: solves with ``consistency_solve``).  Scores exist on
     the device only (ValueError for host data).  Not differentiable.  The component-substitution methods are ``cs_fuse``."""
     from . import metrics
     if score not in (False, True, "hqnr"):

@@ -38,7 +38,15 @@ each method against the same chain composed from torch operators.  Captured and 
 the reduced scale, `ops.bdsd_moments`, `ops.bdsd_coeffs`, `ops.bdsd_inject` beside a copy that moves its 2 C + 1 planes and beside
 `ops.cs_inject` at the same shape, and `ops.bdsd` whole against the chain composed from torch operators (the same two filters,
 then an fp64 `einsum` Gram, `torch.linalg.solve` and an `einsum` injection per block; launched eagerly, the solve cannot be
-captured).  Captured and timed as `--leg mtf`."""
+captured).  Captured and timed as `--leg mtf`.
+
+`--leg cg`: Wald's consistency as a solve (csrc/cg.hip) at [1, 8, 1024, 1024] and [32, 8, 64, 64], x4 "WV3":
+`ops.consistency_solve` (buffers and workspace given) at 8 iterations against `tiling.consistency_refine` at 8 steps in the same
+run, the launch kinds of an iteration on their own (degradation, adjoint, the dots, the step, the direction) with the bytes the
+elementwise ones move, and the residual ratio ||lr - A f|| / ||lr - A f0|| each method reaches from `upsample_poly23(lr)`.  The
+step and the direction are timed with a numerator of exactly 0 (alpha = beta = 0): the same loads, multiply-adds and stores,
+and the vectors stay as they are over the replays.  Captured and timed as
+`--leg mtf`."""
 import argparse
 import os
 import statistics
@@ -423,9 +431,73 @@ def bdsd_leg(args):
               f"torch composition / bdsd {med[n[4]] / med[n[3]]:6.1f}", flush=True)
 
 
+def cg_leg(args):
+    """`--leg cg`: see the module's docstring."""
+    from tmdiff_amd import metrics
+    from tmdiff_amd._lib import check, lib
+    from tmdiff_amd.tiling import consistency_refine
+    sensor, ratio, iters = "WV3", 4, 8
+    taps = ops._mtf_taps(metrics.band_gains(sensor, 8), ratio, torch.device("cuda", torch.cuda.current_device()))
+    cases, groups = [], []          # (name, call, bytes moved or 0); (shape, names)
+    for shape in ((1, 8, 1024, 1024), (32, 8, 64, 64)):
+        b, c, h, w = shape
+        truth = torch.rand(*shape, device="cuda")
+        lr = ops.mtf_degrade(truth, sensor, ratio)
+        f0 = ops.upsample_poly23(lr, ratio)
+        out, out2 = torch.empty_like(f0), torch.empty_like(f0)
+        ws = ops.consistency_solve_workspace(b, c, h, w, ratio, iters, "cuda")
+        res = lambda f, lr=lr: float((lr - ops.mtf_degrade(f, sensor, ratio)).double().pow(2).sum().sqrt())
+        solve = lambda f0=f0, lr=lr, out=out, ws=ws: ops.consistency_solve(f0, lr, taps, ratio, iters, out=out, workspace=ws)
+        refine = lambda f0=f0, lr=lr, out2=out2: consistency_refine(f0, lr, sensor, ratio, iters=iters, out=out2)
+        solve(), refine()
+        print(f"{list(shape)}: residual ratio after {iters} iterations: consistency_solve {res(out) / res(f0):.4f}, "
+              f"consistency_refine {res(out2) / res(f0):.4f}", flush=True)
+        planes, nf, nl = b * c, h * w, lr.shape[2] * lr.shape[3]
+        r, q, d, sv, p, part = ws["r"], ws["q"], ws["d"], ws["s"], ws["p"], ws["partials"]
+        cf, cl = ops.plane_dots_partials(nf), ops.plane_dots_partials(nl)
+        g0, g1 = part[:planes * cf], part[planes * cf:2 * planes * cf]
+        qq = part[3 * planes * cf:3 * planes * cf + planes * cl]
+        rr = part[3 * planes * cf + planes * cl:3 * planes * cf + 2 * planes * cl]
+        zero = torch.zeros(planes * cf, device="cuda", dtype=torch.float64)          # a numerator of 0: alpha = beta = 0
+
+        def step(p=p, q=q, d=d, r=r, zero=zero, qq=qq, rr=rr, planes=planes, nf=nf, nl=nl):
+            check(lib.tmdiff_cg_step(p.data_ptr(), q.data_ptr(), d.data_ptr(), r.data_ptr(), zero.data_ptr(), qq.data_ptr(), None, 0.0,
+                                     rr.data_ptr(), planes, nf, nl, 0, ops.stream_ptr()))
+
+        def direction(sv=sv, p=p, zero=zero, g0=g0, planes=planes, nf=nf):
+            check(lib.tmdiff_cg_direction(sv.data_ptr(), p.data_ptr(), zero.data_ptr(), g0.data_ptr(), None, planes, nf, ops.stream_ptr()))
+
+        tag = f"{list(shape)}"
+        names = [f"{n:28s} {tag}" for n in ("consistency_solve 8 iterations", "consistency_refine 8 steps", "fir_decimate (A p)",
+                                            "fir_decimate_adjoint (A^T r)", "dot <q, q> (low)", "dot <s, s> (full)", "cg_step", "cg_direction")]
+        groups.append((tag, names))
+        cases += [(names[0], solve, 0), (names[1], refine, 0),
+                  (names[2], lambda p=p, q=q: ops.fir_decimate(p, taps, ratio, None, q), 0),
+                  (names[3], lambda r=r, sv=sv, h=h, w=w: ops.fir_decimate_adjoint(r, taps, (h, w), ratio, None, sv), 0),
+                  (names[4], lambda q=q, qq=qq, planes=planes: ops._launch_dots("plane_dots", [(q, q, qq)], planes), 4 * planes * nl),
+                  (names[5], lambda sv=sv, g1=g1, planes=planes: ops._launch_dots("plane_dots", [(sv, sv, g1)], planes), 4 * planes * nf),
+                  (names[6], step, 4 * planes * (3 * nf + 3 * nl)), (names[7], direction, 4 * planes * 3 * nf)]
+    graphs = [captured(fn, args.graph_calls) for _, fn, _ in cases]
+    times = [[] for _ in cases]
+    for _ in range(args.rounds):
+        for graph, t in zip(graphs, times):
+            time_us(graph.replay, 1)
+            t.append(time_us(graph.replay, 1) / args.graph_calls)
+    print(f"{'case':52s} {'us per call (min..max)':>30s} {'MiB moved':>10s} {'GB/s':>8s}")
+    med = {}
+    for (name, _, nbytes), t in zip(cases, times):
+        m = med[name] = statistics.median(t)
+        rate = f"{nbytes / 2 ** 20:10.1f} {nbytes / m / 1e3:8.1f}" if nbytes else ""
+        print(f"{name:52s} {m:10.2f} ({min(t):8.2f}..{max(t):8.2f}) {rate}", flush=True)
+    for tag, n in groups:
+        new = med[n[4]] + med[n[5]] + med[n[6]] + med[n[7]]
+        print(f"{tag:20s} solve / refine {med[n[0]] / med[n[1]]:5.2f}   per iteration: A + A^T {med[n[2]] + med[n[3]]:8.2f} us, "
+              f"dots + step + direction {new:8.2f} us ({new / (med[n[2]] + med[n[3]]):5.2f} of the pair)", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("resample", "mtf", "adjoint", "glp", "cs", "bdsd"), default="resample")
+    ap.add_argument("--leg", choices=("resample", "mtf", "adjoint", "glp", "cs", "bdsd", "cg"), default="resample")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--graph-calls", type=int, default=10, help="--leg mtf / adjoint: calls captured into each graph")
@@ -445,6 +517,8 @@ def main():
         return cs_leg(args)
     if args.leg == "bdsd":
         return bdsd_leg(args)
+    if args.leg == "cg":
+        return cg_leg(args)
 
     cases = []          # (name, kernel call, bytes, copy call, bytes the copy moves)
 
