@@ -273,6 +273,24 @@ size_t tmdiff_conv3d_wf_workspace_bytes(const tmdiff_conv3d_desc* d);
 int32_t tmdiff_conv3d_wf_plan(int32_t B, int32_t Cin, int32_t Cout, int32_t N, int32_t H, int32_t W, int32_t groups, int32_t llm,
                               int64_t* tiles);
 int tmdiff_conv3d_wf_fwd(const tmdiff_conv3d_desc* d, void* workspace, tmdiff_stream_t stream);
+
+/* ---- 3x3x3 convolution, Winograd in two dimensions for the deep layers: F(4,3) along the bands x F(2,3) along the width ----
+ * (csrc/conv3d_w2.hip).  72 instead of tmdiff_conv3d_wf_fwd's 108 multiply-adds per input channel, four bands and column pair,
+ * as three launches over Winograd-domain arrays in `workspace`: an input pass (the consumer's shift / scale / act prologue
+ * applied on the way), one GEMM per Winograd plane (24 planes, K = 3 row taps x Cin), an output pass with the usual epilogue
+ * out = (conv + bias_scale * bias + residual) * out_scale and second output y2.  Takes: fp32, groups 1, ONE input tensor, no
+ * mask / dropout, N = 8 or 4, even W <= 16, 4 <= H <= 32, Cin >= 128 (a multiple of 32), Cout >= 256 (a multiple of 64), none
+ * of rc_x / y_ll / y_hi / y2_s2d / xp_out; everything else: TMDIFF_E_UNSUPPORTED (tmdiff_conv3d_w2_supported says so
+ * beforehand -- use tmdiff_conv3d_wf_fwd).  `workspace`: tmdiff_conv3d_w2_workspace_bytes(d) bytes (the transformed input and
+ * the plane products), 16-byte aligned, lent by the caller.  d->w_packed = tmdiff_conv3d_w2_pack_weights(w [Cout, Cin, 3,3,3])
+ * (tmdiff_conv3d_w2_packed_bytes bytes: 72 floats per weight pair).  stages: 0 = the whole convolution; else a bit mask of the
+ * launches that run (1 input pass, 2 GEMM, 4 output pass: timing).  Agrees with tmdiff_conv3d_fwd to 2e-5 of the output's
+ * largest element. */
+int tmdiff_conv3d_w2_supported(const tmdiff_conv3d_desc* d);
+size_t tmdiff_conv3d_w2_workspace_bytes(const tmdiff_conv3d_desc* d);
+size_t tmdiff_conv3d_w2_packed_bytes(int32_t Cout, int32_t Cin);
+int tmdiff_conv3d_w2_pack_weights(const float* w, float* packed, int32_t Cout, int32_t Cin, tmdiff_stream_t stream);
+int tmdiff_conv3d_w2_fwd(const tmdiff_conv3d_desc* d, void* workspace, int32_t stages, tmdiff_stream_t stream);
 /* `Conv_0` (3x3x3) of a down block and the halved Haar LL band of its output as ONE convolution (as tmdiff_conv3d_ll_fwd: same
  * descriptor -- H, W the INPUT extents, outputs at half of them, bias multiplied by 2 * ll_scale) WITH Winograd F(4,3) along the
  * bands on top: the LL band acts on (h, w) only, so the composed 3x4x4 stride-2 kernel keeps its three band taps -- 16 x 6 / 4 =

@@ -408,11 +408,11 @@ class WavBEST(nn.Module):
         return prep
 
     # ---- fused building blocks -------------------------------------------------------------------
-    def _conv(self, P, name, segs, use_bias=True, bias_scale=1.0, bias=None, emit=False, **kw):
+    def _conv(self, P, name, segs, use_bias=True, bias_scale=1.0, bias=None, emit=False, w2=True, **kw):
         """One convolution of the fused inference graph on the kernel family tmdiff_amd.routing picks for its extents.
         bias: another module's bias instead of this one's (a folded res_conv's).  emit: the consumer's prologue spec, as in
         ops.conv3d; given as None (a consumer that turns out to want no second output) the result is (y, None), so such a
-        call site unpacks (y, y2) either way."""
+        call site unpacks (y, y2) either way.  w2=False: the launch is not offered to conv3d_w2."""
         m = self.get_submodule(name)
         if bias is None:
             bias = m.bias.detach() if (use_bias and m.bias is not None) else None
@@ -435,7 +435,13 @@ class WavBEST(nn.Module):
                 ww["wf"] = ops.pack_conv_weight_wino(m.weight.detach().float().contiguous(), groups=m.groups, mode=2, planes=6)
             return ww["wf"]
 
-        weights = ops.ConvWeights(lambda: P["w"][name], packed_wf if ww is not None else None, packed if ww is not None else None)
+        def packed_w2():                  # conv3d_w2: F(4,3) x F(2,3), the deep layers (routing.wino2d_route)
+            if "w2" not in ww:
+                ww["w2"] = ops.pack_conv_weight_w2(m.weight.detach().float().contiguous())
+            return ww["w2"]
+
+        weights = ops.ConvWeights(lambda: P["w"][name], packed_wf if ww is not None else None, packed if ww is not None else None,
+                                  packed_w2 if (w2 and ww is not None and m.groups == 1) else None)
         out = ops.conv3d_auto(segs, weights, m.out_channels, groups=m.groups, math=math, bias=bias, bias_scale=bias_scale, **kw)
         return (out, None) if emit is None else out
 
@@ -528,10 +534,12 @@ class WavBEST(nn.Module):
         return (y, y2, None, plan.s2d) if want_ll else (y, y2)
 
     def _conv0(self, P, name, x, pre):
-        """Conv_0 of a wavelet block on SiLU(x): from the producer's second output when there is one."""
+        """Conv_0 of a wavelet block on SiLU(x): from the producer's second output when there is one.  It stays on conv3d_wf,
+        the kernel whose epilogue writes its Haar transform (plan "dwt"), also where a switch takes that fusion away: the
+        convolution launches of an A/B run of the fusion are then the same ones (w2=False)."""
         if pre is None:
-            return self._conv(P, name + ".Conv_0", [x], in_act=True)
-        return self._conv(P, name + ".Conv_0", [pre], x_bf16_shape=tuple(x.shape[2:]) if pre.dtype == torch.int16 else None)
+            return self._conv(P, name + ".Conv_0", [x], in_act=True, w2=False)
+        return self._conv(P, name + ".Conv_0", [pre], x_bf16_shape=tuple(x.shape[2:]) if pre.dtype == torch.int16 else None, w2=False)
 
     def _down(self, P, S, name, x, flag, want_high, pre=None, emit=None, fuse=False, xq=None, s2d=False):
         """WaveletUPorDown(down=True) (ref :369-414); /2 folded into the DWT, LL-only when the

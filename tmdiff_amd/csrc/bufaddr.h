@@ -27,6 +27,13 @@ __device__ __forceinline__ float4 load4(rsrc r, unsigned voff) {
   const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0);
   return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
+__device__ __forceinline__ float2 load2(rsrc r, unsigned voff) {
+  const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, 0, 0);
+  return make_float2(__uint_as_float(v.x), __uint_as_float(v.y));
+}
+__device__ __forceinline__ void store(rsrc r, unsigned voff, float t) {
+  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(t), r, voff, 0, 0);
+}
 __device__ __forceinline__ void store4(rsrc r, unsigned voff, float4 t) {
   const u32x4 v = {__float_as_uint(t.x), __float_as_uint(t.y), __float_as_uint(t.z), __float_as_uint(t.w)};
   __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, 0, 0);
@@ -48,6 +55,8 @@ struct rsrc {};
 __device__ __forceinline__ rsrc make(const void*, unsigned) { return {}; }
 __device__ __forceinline__ float load(rsrc, unsigned, unsigned) { return 0.f; }
 __device__ __forceinline__ float4 load4(rsrc, unsigned) { return make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ float2 load2(rsrc, unsigned) { return make_float2(0.f, 0.f); }
+__device__ __forceinline__ void store(rsrc, unsigned, float) {}
 __device__ __forceinline__ void store4(rsrc, unsigned, float4) {}
 __device__ __forceinline__ void store4(rsrc, unsigned, uint4) {}
 __device__ __forceinline__ void store2(rsrc, unsigned, float2) {}

@@ -34,6 +34,8 @@ class KernelConfig:
     wf_min_fill        TMDIFF_WF_MIN_FILL       0.7      planes that fill less of conv3d_wf's tiles go to the fallback
     wino_min_blocks    TMDIFF_WINO_MIN_BLOCKS   256      Winograd grids below this many workgroups go to the direct kernels
                                                          (1 = force the production family onto small test batches)
+    wino2d             TMDIFF_WINO2D            True     deep layers (routing.wino2d_ok) on conv3d_w2: Winograd along the width as well,
+                                                         as transform passes + one GEMM per plane; False = conv3d_wf
     ll_compose         TMDIFF_LL_COMPOSE        True     main-branch Conv_0 + halved LL band as one composed convolution
     wfll               TMDIFF_WFLL              True     ... with Winograd on top (conv3d_wf's composed-LL mode) in inference
     train_ll_wino      TMDIFF_TRAIN_LL_WINO     True     ... and in the finetune forward; False = conv3d_ll there
@@ -89,6 +91,7 @@ class KernelConfig:
         "train_two_streams": ("TMDIFF_TRAIN_STREAMS", _FLAG(True), True),
         "sample_graph": ("TMDIFF_SAMPLE_GRAPH", _FLAG(False), False),
         "grad_bf16": ("TMDIFF_GRAD_BF16", _FLAG(False), False),
+        "wino2d": ("TMDIFF_WINO2D", _FLAG(True), True),
     }
 
     def __init__(self, env=None):
@@ -729,8 +732,8 @@ class ConvWeights:
     (pack_conv_weight_wino mode | 2, planes 6), wino(planes) (fallback kernels).  Any callable may be None: that family is
     then not offered for this weight (conv3d_auto falls through to the next rule)."""
 
-    def __init__(self, direct, wf=None, wino=None):
-        self.direct, self.wf, self.wino = direct, wf, wino
+    def __init__(self, direct, wf=None, wino=None, w2=None):
+        self.direct, self.wf, self.wino, self.w2 = direct, wf, wino, w2      # w2(): pack_conv_weight_w2 (conv3d_w2)
 
 
 def conv3d_auto(segs, weights, cout, groups=1, math="fp32", emit=None, keep_y=True, xp_out=None, x_bf16_shape=None, family=None,
@@ -747,6 +750,11 @@ def conv3d_auto(segs, weights, cout, groups=1, math="fp32", emit=None, keep_y=Tr
     masked, dropout, plain = kw.get("in_mask") is not None, kw.get("drop") is not None, _plain(segs, kw)
     fam = family or routing.conv3_family(b, cin, cout, n, h, w, groups, plain=plain, masked=masked, dropout=dropout,
                                          keep_xp=xp_out is not None)
+    if (fam in ("wf", "wf_pair") and weights.w2 is not None and family is None and xp_out is None and len(segs) == 1 and
+            not masked and not dropout and kw.get("res_conv") is None and
+            not (emit is not None and (emit.get("s2d") or emit.get("ll") or emit.get("dwt"))) and
+            routing.wino2d_route(b, cin, cout, n, h, w, groups)):
+        return conv3d_w2(segs[0], weights.w2(), cout, emit=emit, keep_y=keep_y, **kw)
     if fam in ("wf", "wf_pair") and weights.wf is not None:
         return conv3d_wf(segs, weights.wf(), cout, emit=emit, keep_y=keep_y, groups=groups, xp_out=xp_out, **kw)
     if fam in ("wino4", "wino2") and weights.wino is not None:
@@ -805,6 +813,38 @@ def conv3d_wf(segs, w_packed, cout, emit=None, keep_y=True, groups=1, xp_out=Non
     flops = 2.0 * b * cout * ((d.Cin // groups) * 13.5 + d.rc_cin) * n * h * w
     _launch(lib.tmdiff_conv3d_wf_fwd, d, (ws,), "conv3d_wf_fwd", "conv3d_wf_fwd", flops, 3, f" +rc{d.rc_cin}" if d.rc_cin else "")
     return (y_ll, *y_hi) if want_dwt else (y2, y_ll) if want_ll else _result(y, y2)
+
+
+def pack_conv_weight_w2(w):
+    """[Cout, Cin, 3, 3, 3] -> the weights of conv3d_w2: (G_band (x) G_w) w as [24 planes][dh][Cin / 4][Cout][4] floats."""
+    cout, cin = w.shape[0], w.shape[1]
+    nb = lib.tmdiff_conv3d_w2_packed_bytes(cout, cin)
+    if tuple(w.shape[2:]) != (3, 3, 3) or nb == 0:
+        raise ValueError(f"pack_conv_weight_w2: weight shape {tuple(w.shape)} not supported")
+    out = torch.empty(nb // 4, device=w.device, dtype=torch.float32)
+    check(lib.tmdiff_conv3d_w2_pack_weights(_chk(w.detach(), "w"), out.data_ptr(), cout, cin, stream_ptr()), "conv3d_w2_pack_weights")
+    return out
+
+
+def conv3d_w2(x, w_packed, cout, emit=None, keep_y=True, stages=0, **kw):
+    """conv3d([x], ...) (fp32, 3x3x3, groups 1) with Winograd along the bands AND the width (csrc/conv3d_w2.hip): an input pass
+    (the prologue keywords in_shift / in_scale / in_act are applied on the way), one GEMM per Winograd plane, an output pass with
+    bias / residual / out_scale / emit as in conv3d.  The Winograd-domain arrays live in the per-stream scratch "w2", lent to
+    the library like the split-K workspace.  w_packed from pack_conv_weight_w2; shapes: routing.wino2d_ok.  stages: a bit mask
+    of the launches that run (1 input pass, 2 GEMM, 4 output pass; timing), 0 = all."""
+    b, _, n, h, w = x.shape
+    dev = x.device
+    if emit is not None and (emit.get("s2d") or emit.get("ll") or emit.get("dwt")):
+        raise ValueError("conv3d_w2: no space-to-depth / LL / Haar outputs (conv3d_wf writes those)")
+    y, y2 = _outputs("conv3d_w2", dev, (b, cout, n, h, w), keep_y, emit, (b, cout, n, h, w))
+    d = make_conv_desc([x], w_packed, cout, 3, y, y2=y2, **kw, **_emit_kw(emit))
+    if not lib.tmdiff_conv3d_w2_supported(C.byref(d)):
+        raise ValueError("conv3d_w2: shape not supported (routing.wino2d_ok)")
+    nws = lib.tmdiff_conv3d_w2_workspace_bytes(C.byref(d))
+    ws = _workspace(dev, nws, "w2").data_ptr()
+    # EXECUTED flops: 24 planes x 3 row taps per tile of four bands and two columns = 9 multiply-adds per (ci, co, output)
+    _launch(lib.tmdiff_conv3d_w2_fwd, d, (ws, int(stages)), "conv3d_w2_fwd", "conv3d_w2_fwd", 2.0 * b * cout * d.Cin * 9.0 * n * h * w)
+    return _result(y, y2)
 
 
 def pack_conv_weight_ll(w, ll_scale=0.5):

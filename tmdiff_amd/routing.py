@@ -170,6 +170,29 @@ def supported(query, b, cin, cout, n, h, w, groups=1, **fields):
     return r
 
 
+def wino2d_ok(b, cin, cout, n, h, w, groups=1):
+    """The shapes conv3d_w2 (Winograd along the bands and the width: transform passes + one GEMM per plane) takes: the deep
+    layers -- fp32, groups 1, 8 or 4 bands, Cout >= 256 (% 64), Cin >= 128 (% 32), planes of even width <= 16 and 4 .. 32 rows,
+    Winograd-domain arrays within 32-bit byte offsets per plane.  The mirror of tmdiff_conv3d_w2_supported for a convolution
+    on ONE plain-or-prologue input tensor with a y / y2 / residual epilogue (tests/test_conv3d_w2_host.py holds the two together)."""
+    if groups != 1 or b <= 0 or n not in (4, 8) or w < 2 or w > 16 or w % 2 or h < 4 or h > 32:
+        return False
+    if cin < 128 or cin % 32 or cout < 256 or cout % 64:
+        return False
+    q, tw = b * (n // 4), w // 2
+    ip, op = (h + 2) * tw, h * tw
+    g = max(1, min(q, 256 // op, 384 // ip))
+    return (4 * cin * q * ip < (1 << 31) and 4 * cout * q * op < (1 << 31) and 12 * cin * cout < (1 << 31) and q <= 65535 and
+            ((q + g - 1) // g) * (cout // 64) * 24 < 0x7fffffff)
+
+
+def wino2d_route(b, cin, cout, n, h, w, groups=1):
+    """True when a convolution of these extents that conv3_family gave to conv3d_wf runs on conv3d_w2 instead (config.wino2d).
+    ops.conv3d_auto adds what it knows of the launch: one input tensor, no mask / dropout, no folded 1x1x1, no LL / Haar /
+    space-to-depth output -- those launches stay on conv3d_wf."""
+    return bool(_config().wino2d and wino2d_ok(b, cin, cout, n, h, w, groups))
+
+
 def wfll_route(b, cin, cout, n, h, w):
     """True when conv3d_wf's composed-LL mode takes Conv_0 + LL of a [b, cin, n, h, w] input (h, w: full resolution)."""
     if not (_config().wfll and n in (4, 8) and h % 2 == 0 and w % 8 == 0 and cout % 32 == 0):
