@@ -106,7 +106,7 @@ typedef struct tmdiff_conv3d_desc {
    * the step bumps before the graph runs) every replay still draws a fresh mask -- and forward, weight gradient and
    * prologue backward of one step still agree, since all three read the same word.  (ABI v6) */
   const uint64_t* drop_seed_dev;
-  /* Optional folded "residual convolution" (tmdiff_conv3d_wf_fwd only; ABI v6): y = (conv(x') + bias + rc_w^T rc_x) * out_scale,
+  /* Optional folded "residual convolution" (tmdiff_conv3d_wf_fwd, tmdiff_conv3d_w2_fwd; ABI v6): y = (conv(x') + bias + rc_w^T rc_x) * out_scale,
    * i.e. the 1x1x1 res_conv of a ResBlock (Hyper_unet_general.py:231, :248) on the block's RAW input rc_x [B, rc_cin, N, H, W],
    * accumulated on the matrix pipe where its consumer conv21 would have added it -- no launch of its own, its result never
    * written and read back.  rc_w = the weight [Cout, rc_cin, 1, 1, 1] as PyTorch holds it (contiguous, NOT packed); the
@@ -115,12 +115,12 @@ typedef struct tmdiff_conv3d_desc {
   const float* rc_x;
   const float* rc_w;
   int32_t rc_cin;
-  /* Optional third output (tmdiff_conv3d_wf_fwd only; ABI v6): the HALVED LL BAND of y, (a + b + c + d) / 4 over every 2 x 2 pixel
+  /* Optional third output (tmdiff_conv3d_wf_fwd, tmdiff_conv3d_w2_fwd; ABI v6): the HALVED LL BAND of y, (a + b + c + d) / 4 over every 2 x 2 pixel
    * block, [B, Cout, N, H/2, W/2] -- all a down block reads of its ResBlock's raw output (its Conv_2 path,
    * Hyper_unet_general.py:374, :390, :396), so that neither y nor an LL-only DWT pass over it is needed.  Needs y == NULL and
    * y2 != NULL, 8 bands, even H, W % 4 == 0, planes wider than 8 columns, an unsplit grid; else TMDIFF_E_UNSUPPORTED. */
   float* y_ll;
-  /* ... and with y_hi[0..2] != NULL (then y2 == NULL): the WHOLE Haar transform of y instead of y (tmdiff_conv3d_wf_fwd only; ABI v6) --
+  /* ... and with y_hi[0..2] != NULL (then y2 == NULL): the WHOLE Haar transform of y instead of y (tmdiff_conv3d_wf_fwd, tmdiff_conv3d_w2_fwd; ABI v6) --
    * y_hi = LH, HL, HH = (a - b + c - d) / 2, (a + b - c - d) / 2, (a - b - c + d) / 2 of every 2 x 2 block (a b / c d), and y_ll = the
    * halved LL band passed through the second output's prologue, act2(LL / 2 + y2_shift) * y2_scale: what a down block whose high
    * bands are kept makes of its Conv_0 output (DWT, then Conv_1's prologue on the LL band; Hyper_unet_general.py:388-396,
@@ -138,7 +138,8 @@ typedef struct tmdiff_conv3d_desc {
   float* xp_out;
   const float* xp_shift;
   int32_t xp_shift_stride, xp_act;
-  /* != 0 (tmdiff_conv3d_wf_fwd only, even H, W % 4 == 0, a grid that does not split its input channels): y2 is written in
+  /* != 0 (tmdiff_conv3d_wf_fwd: even H, W % 4 == 0, a grid that does not split its input channels; tmdiff_conv3d_w2_fwd: 8 bands,
+   * even H): y2 is written in
    * "space to depth" form [B, 4 Cout, N, H/2, W/2], channel 4 co + 2 ph + pw holding y2[co][n][2i + ph][2j + pw] -- the input
    * form of tmdiff_conv3d_wfll_fwd (the down blocks' Conv_0 + LL band, Hyper_unet_general.py:371-372, :389, :396). */
   int32_t y2_s2d;
@@ -279,14 +280,20 @@ int tmdiff_conv3d_wf_fwd(const tmdiff_conv3d_desc* d, void* workspace, tmdiff_st
  * as three launches over Winograd-domain arrays in `workspace`: an input pass (the consumer's shift / scale / act prologue
  * applied on the way), one GEMM per Winograd plane (24 planes, K = 3 row taps x Cin), an output pass with the usual epilogue
  * out = (conv + bias_scale * bias + residual) * out_scale and second output y2.  Takes: fp32, groups 1, ONE input tensor, no
- * mask / dropout, N = 8 or 4, even W <= 16, 4 <= H <= 32, Cin >= 128 (a multiple of 32), Cout >= 256 (a multiple of 64), none
- * of rc_x / y_ll / y_hi / y2_s2d / xp_out; everything else: TMDIFF_E_UNSUPPORTED (tmdiff_conv3d_w2_supported says so
- * beforehand -- use tmdiff_conv3d_wf_fwd).  `workspace`: tmdiff_conv3d_w2_workspace_bytes(d) bytes (the transformed input and
+ * mask / dropout, N = 8 or 4, even W <= 16, 4 <= H <= 32, Cin >= 128 (a multiple of 32), Cout >= 256 (a multiple of 64), no
+ * xp_out.  tmdiff_conv3d_w2_supported answers 1 for such a descriptor with none of rc_x / y_ll / y_hi / y2_s2d (the plain
+ * epilogue: the output pass takes one plane row per workgroup).  tmdiff_conv3d_w2_epilogue_supported answers 1 for those and
+ * for the descriptors whose epilogue the row-pair output pass writes (even H): a folded 1x1x1 (rc_x / rc_w / rc_cin under
+ * tmdiff_conv3d_wf_fwd's conditions: rc_cin % 32 == 0, at most 512, residual NULL; accumulated on the matrix pipe inside the
+ * output pass), and on 8 bands y_ll (y NULL, y2 set), y_ll + y_hi[0..2] (y and y2 NULL) and y2_s2d, as defined at the fields.
+ * tmdiff_conv3d_w2_fwd takes exactly the descriptors of the second query; everything else: TMDIFF_E_UNSUPPORTED (use
+ * tmdiff_conv3d_wf_fwd).  `workspace`: tmdiff_conv3d_w2_workspace_bytes(d) bytes (the transformed input and
  * the plane products), 16-byte aligned, lent by the caller.  d->w_packed = tmdiff_conv3d_w2_pack_weights(w [Cout, Cin, 3,3,3])
  * (tmdiff_conv3d_w2_packed_bytes bytes: 72 floats per weight pair).  stages: 0 = the whole convolution; else a bit mask of the
  * launches that run (1 input pass, 2 GEMM, 4 output pass: timing).  Agrees with tmdiff_conv3d_fwd to 2e-5 of the output's
  * largest element. */
 int tmdiff_conv3d_w2_supported(const tmdiff_conv3d_desc* d);
+int tmdiff_conv3d_w2_epilogue_supported(const tmdiff_conv3d_desc* d);
 size_t tmdiff_conv3d_w2_workspace_bytes(const tmdiff_conv3d_desc* d);
 size_t tmdiff_conv3d_w2_packed_bytes(int32_t Cout, int32_t Cin);
 int tmdiff_conv3d_w2_pack_weights(const float* w, float* packed, int32_t Cout, int32_t Cin, tmdiff_stream_t stream);

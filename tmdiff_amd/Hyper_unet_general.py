@@ -533,13 +533,15 @@ class WavBEST(nn.Module):
                            x_bf16_shape=shape if name + ".conv21" in P["bf16"] else None, **rckw)
         return (y, y2, None, plan.s2d) if want_ll else (y, y2)
 
-    def _conv0(self, P, name, x, pre):
-        """Conv_0 of a wavelet block on SiLU(x): from the producer's second output when there is one.  It stays on conv3d_wf,
-        the kernel whose epilogue writes its Haar transform (plan "dwt"), also where a switch takes that fusion away: the
-        convolution launches of an A/B run of the fusion are then the same ones (w2=False)."""
+    def _conv0(self, P, name, x, pre, w2=False):
+        """Conv_0 of a wavelet block on SiLU(x): from the producer's second output when there is one.  This unfused form (an up
+        block, or a switch took the plan "dwt" away) is not offered to conv3d_w2 (w2=False) -- except, at _down, where
+        TMDIFF_EMIT_DWT=0 took away a fused launch that conv3d_w2 runs: the convolution launches of an A/B run of that fusion are
+        then the same ones.  The fused form goes through _conv at _down and reaches conv3d_w2's row-pair output pass by itself
+        (routing.wino2d_epilogue_route)."""
         if pre is None:
-            return self._conv(P, name + ".Conv_0", [x], in_act=True, w2=False)
-        return self._conv(P, name + ".Conv_0", [pre], x_bf16_shape=tuple(x.shape[2:]) if pre.dtype == torch.int16 else None, w2=False)
+            return self._conv(P, name + ".Conv_0", [x], in_act=True, w2=w2)
+        return self._conv(P, name + ".Conv_0", [pre], x_bf16_shape=tuple(x.shape[2:]) if pre.dtype == torch.int16 else None, w2=w2)
 
     def _down(self, P, S, name, x, flag, want_high, pre=None, emit=None, fuse=False, xq=None, s2d=False):
         """WaveletUPorDown(down=True) (ref :369-414); /2 folded into the DWT, LL-only when the
@@ -548,12 +550,14 @@ class WavBEST(nn.Module):
         shape = x.shape if x is not None else (*xq.shape[:3], 2 * xq.shape[3], 2 * xq.shape[4])
         plan = self._down_plan(P, name, shape, not want_high, pre is not None and pre.dtype == torch.float32, s2d, fuse)
         pro = self._spec(P, S, shift=None if flag else name + ".Dense_0", scale=name + ".dense1")      # Conv_1's prologue
-        # high bands kept (condition branch): where Conv_0 runs on conv3d_wf unsplit, its epilogue writes the Haar transform of its
+        # high bands kept (condition branch): where Conv_0 runs on conv3d_wf unsplit (or conv3d_w2), its epilogue writes the Haar transform of its
         # output -- LL through Conv_1's prologue, LH, HL, HH -- instead of the output: no full-resolution tensor, no DWT pass
         if plan.conv0 == "dwt":
             hll, *bands = self._conv(P, name + ".Conv_0", [pre], keep_y=False, emit=dict(pro, dwt=True))
         elif plan.conv0 is None:
-            hh = self._conv0(P, name, x, pre)
+            c0 = self.get_submodule(name + ".Conv_0")    # (emit_dwt switched off: Conv_0 stays on the kernel its fused launch runs on)
+            hh = self._conv0(P, name, x, pre, w2=want_high and not ops.config.emit_dwt and routing.wino2d_epilogue_route(
+                shape[0], c0.in_channels, c0.out_channels, *shape[2:], quarter=True))
         # The reference runs the 1x1x1 Conv_2 at full resolution and keeps the halved LL band of its output (:390, :396).
         # Both are linear and act on different axes (channels / the 2x2 pixel block), and the halved LL band of a
         # constant is that constant, so LL(Conv_2(x)) / 2 == Conv_2(LL(x) / 2): the convolution runs on a quarter of

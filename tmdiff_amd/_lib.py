@@ -61,6 +61,7 @@ SIGNATURES = {
     "tmdiff_conv3d_wf_splitk_workspace_bytes": (C.c_size_t, [C.POINTER(Conv3dDesc)]),
     "tmdiff_conv3d_wf_fwd": (C.c_int, [C.POINTER(Conv3dDesc), vp, vp]),
     "tmdiff_conv3d_w2_supported": (C.c_int, [C.POINTER(Conv3dDesc)]),
+    "tmdiff_conv3d_w2_epilogue_supported": (C.c_int, [C.POINTER(Conv3dDesc)]),
     "tmdiff_conv3d_w2_workspace_bytes": (C.c_size_t, [C.POINTER(Conv3dDesc)]),
     "tmdiff_conv3d_w2_packed_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "tmdiff_conv3d_w2_pack_weights": (C.c_int, [vp, vp, C.c_int32, C.c_int32, vp]),

@@ -35,12 +35,40 @@ struct W2Plan {
   size_t xh_floats, mh_floats;
 };
 
-bool w2_shape_ok(const tmdiff_conv3d_desc* d) {
+// the extents and the input side: what the input pass and the GEMM take, whatever the epilogue writes
+bool w2_extents_ok(const tmdiff_conv3d_desc* d) {
   if (!d || d->ksize != 3 || d->groups != 1 || d->x_bf16 || d->y2_bf16 || d->nseg != 1) return false;
   if (d->B <= 0 || (d->N != 4 && d->N != 8) || d->W < 2 || d->W > 16 || d->W % 2 || d->H < 4 || d->H > 32) return false;
   if (d->Cin < 128 || d->Cin % 32 || d->Cout < 256 || d->Cout % W2_CO || d->seg_c[0] != d->Cin) return false;
-  // what the passes do not do: mask / dropout on the input, the folded 1x1x1, the quarter-resolution outputs, the side x'
-  if (d->in_mask || d->drop_p > 0.f || d->rc_x || d->rc_cin || d->y_ll || d->y_hi[0] || d->y2_s2d || d->xp_out) return false;
+  // what the passes do not do: mask / dropout on the input, the side x'
+  if (d->in_mask || d->drop_p > 0.f || d->xp_out) return false;
+  return true;
+}
+
+bool w2_folds(const tmdiff_conv3d_desc* d) { return d->rc_x || d->rc_w || d->rc_cin; }
+bool w2_quarter(const tmdiff_conv3d_desc* d) { return d->y_ll || d->y_hi[0] || d->y_hi[1] || d->y_hi[2] || d->y2_s2d; }
+
+// the plain y / y2 / residual epilogue (tmdiff_conv3d_w2_supported): the one-row output pass
+bool w2_shape_ok(const tmdiff_conv3d_desc* d) { return w2_extents_ok(d) && !w2_folds(d) && !w2_quarter(d); }
+
+// ... and the epilogues of the row-pair output pass on top (tmdiff_conv3d_w2_epilogue_supported): the folded 1x1x1 under
+// conv3d_wf's conditions, the quarter-resolution outputs (LL, Haar, space-to-depth) on 8 bands; both on an even number of rows
+bool w2_epilogue_ok(const tmdiff_conv3d_desc* d) {
+  if (!w2_extents_ok(d)) return false;
+  if (!w2_folds(d) && !w2_quarter(d)) return true;
+  if (d->H % 2) return false;
+  if (w2_quarter(d) && d->N != 8) return false;
+  if (d->y_ll) {       // instead of y: beside a second output, or with the three high bands through its prologue
+    const bool dwt = d->y_hi[0] != nullptr;
+    if (d->y || (dwt ? (d->y2 || d->y2_s2d || !d->y_hi[1] || !d->y_hi[2]) : !d->y2)) return false;
+  } else if (d->y_hi[0] || d->y_hi[1] || d->y_hi[2]) {
+    return false;
+  }
+  if (d->y2_s2d && !d->y2) return false;
+  if (w2_folds(d)) {
+    if (!d->rc_x || d->rc_cin <= 0 || d->rc_cin % 32 || d->rc_cin > 512 || d->residual) return false;
+    if ((long)d->rc_cin * d->N * d->H * d->W >= (1L << 30)) return false;      // (conv3d_wf's wf_rc_fits)
+  }
   return true;
 }
 
@@ -59,8 +87,10 @@ W2Plan w2_plan(const tmdiff_conv3d_desc* d) {
 bool w2_fits(const tmdiff_conv3d_desc* d, const W2Plan& p) {
   // 32-bit byte offsets inside one plane k of U, x^ and m^; grid limits of the passes; the output pass addresses 32 channels
   // of a sample through one descriptor
+  // (32 channels at full resolution = the 128 of the space-to-depth form = four times the 32 of a quarter-size output)
   const size_t xk = p.xh_floats / 24 * 4, mk = p.mh_floats / 24 * 4, uk = (size_t)3 * d->Cin * d->Cout * 4;
-  return xk < (1ull << 31) && mk < (1ull << 31) && uk < (1ull << 31) && p.Q <= 65535 &&
+  const size_t yk = (size_t)32 * d->N * d->H * d->W * 4;
+  return xk < (1ull << 31) && mk < (1ull << 31) && uk < (1ull << 31) && yk < (1ull << 31) && p.Q <= 65535 &&
          (long)p.ptiles * (d->Cout / W2_CO) * 24 < 0x7fffffffL;
 }
 
@@ -339,6 +369,13 @@ struct W2OutArgs {
   int y2_shift_stride, y2_scale_stride, y2_act;
   int Cout, N, H, W, T, TW, OP;
   long QOP;
+  // the row-pair form only: quarter-resolution outputs, the second output's form, the folded 1x1x1
+  float* y_ll;
+  float* y_hi[3];
+  int y2_s2d;
+  const float* rc_x;
+  const float* rc_w;
+  int rc_cin;
 };
 
 template <bool Y, bool RES, bool Y2>
@@ -408,6 +445,187 @@ __global__ void __launch_bounds__(256) w2_output_kernel(const W2OutArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Output pass, row-pair form: one workgroup = the plane rows 2 hp, 2 hp + 1 of image q x 32 output channels, so that a
+// thread of the write-out holds the whole 2 x 2 block (a b / c d) of a column pair -- what the quarter-resolution outputs
+// are made of (tmdiff_hip.h: y_ll, y_hi, y2_s2d).  The transforms are those of the one-row form, once per row, into one LDS
+// tile [band][row][channel][column]; every full-resolution value goes through the same operations in the same order
+// (bit-identical y / y2), the 2 x 2 sums follow conv3d_wf's epilogue ((a + b) + (c + d) and the like).
+// RC: the folded 1x1x1 "residual convolution" (desc.rc_*), added to the tile BEFORE the epilogue arithmetic on the matrix
+// pipe, as conv3d_wf does it: wave wv owns band wv = one 32 x 32 block of (channels) x (2 rows x 16 columns); the
+// accumulator starts as the tile's values, a K-step is two input channels (lane half = channel parity group), the lane's x
+// values come from global memory through a buffer descriptor over the sample's rc_cin channels (rows of 16 floats), its
+// weights as float4 straight from the PyTorch-layout [Cout][rc_cin] (16 KB per channel tile at 128 channels: cache
+// resident); 32 channels in flight while the previous 32 are multiplied.  Channel order inside a group of 8: lane half 0
+// takes 0..3, half 1 takes 4..7 -- any order does, as long as both operands agree.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int W2_RS = 32 * 17 + 16;   // floats per (band, row) block: the two rows of a band sixteen banks apart
+
+template <bool RES, bool RC>
+__global__ void __launch_bounds__(256) w2_output2_kernel(const W2OutArgs a) {
+#pragma clang fp contract(off)   // (the shared epilogue's rounding: epilogue.h)
+  __shared__ float tile[8 * W2_RS];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, khalf = lane >> 5;
+  const int cc = blockIdx.x, hp = blockIdx.y, q = blockIdx.z;
+  const int b = q / a.T, t = q % a.T;
+  const int hw = a.H * a.W;
+  const long plane = (long)a.N * hw;
+
+  // ---- the folded 1x1x1's operands: requested first, multiplied after the transforms
+  const int ngrp = RC ? a.rc_cin / 32 : 0;
+  const buf::rsrc xr = buf::make(RC ? a.rc_x + (long)b * a.rc_cin * plane : nullptr, RC ? (unsigned)((long)a.rc_cin * plane * 4) : 0u);
+  const int rrow = l31 >> 4, rcol = l31 & 15;     // MFMA column l31 = (row, column) of band wv
+  // (a column past the plane: any valid address, the value is never stored)
+  const unsigned xo = (unsigned)((4 * khalf * (int)plane + (rcol < a.W ? ((4 * t + wv) * a.H + 2 * hp + rrow) * a.W + rcol : 0)) * 4);
+  const unsigned ch_bytes = (unsigned)(plane * 4);
+  const float* wrow = RC ? a.rc_w + (long)(cc * 32 + l31) * a.rc_cin + 4 * khalf : nullptr;
+  float4 aw0[4], aw1[4];
+  float xv0[16], xv1[16];
+  auto fetch = [&](int jg, float4 (&aw)[4], float (&xv)[16]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) aw[i] = *reinterpret_cast<const float4*>(wrow + jg * 32 + 8 * i);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) xv[4 * i + e] = buf::load(xr, xo, (unsigned)(jg * 32 + 8 * i + e) * ch_bytes);
+  };
+  if constexpr (RC) fetch(0, aw0, xv0);
+
+  // ---- A^T_w and A^T_band of both rows into the tile (the one-row form's arithmetic)
+  {
+    const int co_l = tid & 31, tw = tid >> 5;
+    if (tw < a.TW) {
+      const long kstride = a.QOP * a.Cout;
+#pragma unroll
+      for (int row = 0; row < 2; ++row) {
+        const float* src = a.mh + ((long)q * a.OP + (2 * hp + row) * a.TW + tw) * a.Cout + cc * 32 + co_l;
+        float r[6][2];
+#pragma unroll
+        for (int kb = 0; kb < 6; ++kb) {
+          const float m0 = src[(kb * 4 + 0) * kstride], m1 = src[(kb * 4 + 1) * kstride], m2 = src[(kb * 4 + 2) * kstride],
+                      m3 = src[(kb * 4 + 3) * kstride];
+          r[kb][0] = (m0 + m1) + m2;
+          r[kb][1] = (m1 - m2) - m3;
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const float p12 = r[1][j] + r[2][j], d12 = r[1][j] - r[2][j], p34 = r[3][j] + r[4][j], d34 = r[3][j] - r[4][j];
+          float* dst = tile + row * W2_RS + co_l * 17 + 2 * tw + j;
+          dst[0 * 2 * W2_RS] = (r[0][j] + p12) + p34;
+          dst[1 * 2 * W2_RS] = d12 + 2.f * d34;
+          dst[2 * 2 * W2_RS] = p12 + 4.f * p34;
+          dst[3 * 2 * W2_RS] = (d12 + 8.f * d34) + r[5][j];
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  if constexpr (RC) {
+    // register r of a lane is channel (r & 3) + 8 (r >> 2) + 4 khalf of the block, the lane its position
+    float* const tb = tile + (wv * 2 + rrow) * W2_RS + 4 * khalf * 17 + rcol;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = tb[((r & 3) + 8 * (r >> 2)) * 17];
+    auto mma = [&](const float4 (&aw)[4], const float (&xv)[16]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[i].x, xv[4 * i + 0], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[i].y, xv[4 * i + 1], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[i].z, xv[4 * i + 2], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[i].w, xv[4 * i + 3], acc, 0, 0, 0);
+      }
+    };
+    for (int jg = 0; jg < ngrp; jg += 2) {
+      if (jg + 1 < ngrp) fetch(jg + 1, aw1, xv1);
+      mma(aw0, xv0);
+      if (jg + 1 < ngrp) {
+        if (jg + 2 < ngrp) fetch(jg + 2, aw0, xv0);
+        mma(aw1, xv1);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) tb[((r & 3) + 8 * (r >> 2)) * 17] = acc[r];
+    __syncthreads();
+  }
+
+  // ---- write-out: thread = (channel, band, column pair), pairs fastest; both rows of the pair
+  const long cb = ((long)b * a.Cout + cc * 32) * plane;
+  const unsigned span = (unsigned)(32 * plane * 4);
+  const bool want_y = a.y != nullptr, want_y2 = a.y2 != nullptr, want_ll = a.y_ll != nullptr, want_hi = a.y_hi[0] != nullptr;   // (uniform)
+  const buf::rsrc ry = buf::make(want_y ? a.y + cb : nullptr, want_y ? span : 0u);
+  const buf::rsrc rr = buf::make(RES ? a.residual + cb : nullptr, RES ? span : 0u);
+  // (the space-to-depth form [B, 4 Cout, N, H/2, W/2]: the tile's 128 quarter-size channels start at the same float)
+  const buf::rsrc r2 = buf::make(want_y2 ? a.y2 + cb : nullptr, want_y2 ? span : 0u);
+  // the quarter-size outputs: the same 32 channels, a quarter plane each
+  const long cbq = cb >> 2;
+  const unsigned spanq = span >> 2;
+  const buf::rsrc rll = buf::make(want_ll ? a.y_ll + cbq : nullptr, want_ll ? spanq : 0u);
+  const buf::rsrc rh0 = buf::make(want_hi ? a.y_hi[0] + cbq : nullptr, want_hi ? spanq : 0u);
+  const buf::rsrc rh1 = buf::make(want_hi ? a.y_hi[1] + cbq : nullptr, want_hi ? spanq : 0u);
+  const buf::rsrc rh2 = buf::make(want_hi ? a.y_hi[2] + cbq : nullptr, want_hi ? spanq : 0u);
+  const int hq = a.H >> 1, wq = a.W >> 1;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int i = tid + 256 * it;
+    const int wp = i & 7, band = (i >> 3) & 3, co_l = i >> 5;
+    const int co = cc * 32 + co_l;
+    const int n = 4 * t + band;
+    const bool ok = wp < a.TW;
+    const unsigned o0 = ok ? (unsigned)(((co_l * a.N + n) * a.H + 2 * hp) * a.W + 2 * wp) * 4u : buf::kOutside;   // row 2 hp
+    const unsigned o1 = buf::at(o0, (unsigned)a.W * 4u);                                                            // row 2 hp + 1
+    const unsigned oq = ok ? (unsigned)(((co_l * a.N + n) * hq + hp) * wq + wp) * 4u : buf::kOutside;              // quarter plane
+    const float* s = tile + band * 2 * W2_RS + co_l * 17 + 2 * wp;
+    float v[4] = {s[0], s[1], s[W2_RS], s[W2_RS + 1]};      // a b / c d
+    const float bias_t = a.bias ? a.bias[co] * a.bias_scale : 0.f;
+    float2 res0 = make_float2(0.f, 0.f), res1 = make_float2(0.f, 0.f);
+    if constexpr (RES) res0 = buf::load2(rr, o0), res1 = buf::load2(rr, o1);
+    v[0] = (v[0] + bias_t + res0.x) * a.out_scale;
+    v[1] = (v[1] + bias_t + res0.y) * a.out_scale;
+    v[2] = (v[2] + bias_t + res1.x) * a.out_scale;
+    v[3] = (v[3] + bias_t + res1.y) * a.out_scale;
+    if (want_y) {
+      buf::store2(ry, o0, make_float2(v[0], v[1]));
+      buf::store2(ry, o1, make_float2(v[2], v[3]));
+    }
+    const float sh2 = a.y2_shift ? a.y2_shift[(long)b * a.y2_shift_stride + co] : 0.f;
+    const float sc2 = a.y2_scale ? a.y2_scale[(long)b * a.y2_scale_stride + co] : 1.f;
+    if (want_y2) {
+      float u[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float x = v[e] + sh2;
+        const float xa = silu_f(x);
+        u[e] = (a.y2_act ? xa : x) * sc2;
+      }
+      if (a.y2_s2d) {      // channel 4 co + 2 ph + pw, each a quarter plane
+        const unsigned os = ok ? (unsigned)(((4 * co_l * a.N + n) * hq + hp) * wq + wp) * 4u : buf::kOutside;
+        const unsigned qplane4 = (unsigned)(plane >> 2) * 4u;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) buf::store(r2, buf::at(os, (unsigned)e * qplane4), u[e]);
+      } else {
+        buf::store2(r2, o0, make_float2(u[0], u[1]));
+        buf::store2(r2, o1, make_float2(u[2], u[3]));
+      }
+    }
+    if (want_ll) {
+      const float ll = ((v[0] + v[1]) + (v[2] + v[3])) * 0.25f;
+      if (want_hi) {       // the whole transform: LL / 2 through the second output's prologue, LH, HL, HH
+        const float x = ll + sh2;
+        const float xa = silu_f(x);
+        buf::store(rll, oq, (a.y2_act ? xa : x) * sc2);
+        buf::store(rh0, oq, ((v[0] - v[1]) + (v[2] - v[3])) * 0.5f);
+        buf::store(rh1, oq, ((v[0] + v[1]) - (v[2] + v[3])) * 0.5f);
+        buf::store(rh2, oq, ((v[0] - v[1]) - (v[2] - v[3])) * 0.5f);
+      } else {
+        buf::store(rll, oq, ll);
+      }
+    }
+  }
+}
+
 }  // namespace
 
 /* 1 if tmdiff_conv3d_w2_fwd takes the convolution described by d (else: tmdiff_conv3d_wf_fwd) */
@@ -415,8 +633,13 @@ extern "C" int tmdiff_conv3d_w2_supported(const tmdiff_conv3d_desc* d) {
   return w2_shape_ok(d) && w2_fits(d, w2_plan(d)) ? 1 : 0;
 }
 
+/* ... and 1 as well for the descriptors whose epilogue the row-pair output pass writes: a folded 1x1x1 (rc_*), y_ll, y_hi, y2_s2d */
+extern "C" int tmdiff_conv3d_w2_epilogue_supported(const tmdiff_conv3d_desc* d) {
+  return w2_epilogue_ok(d) && w2_fits(d, w2_plan(d)) ? 1 : 0;
+}
+
 extern "C" size_t tmdiff_conv3d_w2_workspace_bytes(const tmdiff_conv3d_desc* d) {
-  if (!w2_shape_ok(d)) return 0;
+  if (!w2_epilogue_ok(d)) return 0;
   const W2Plan p = w2_plan(d);
   return (p.xh_floats + p.mh_floats) * sizeof(float);
 }
@@ -439,15 +662,18 @@ extern "C" int tmdiff_conv3d_w2_pack_weights(const float* w, float* packed, int3
 extern "C" int tmdiff_conv3d_w2_fwd(const tmdiff_conv3d_desc* d, void* workspace, int32_t stages, tmdiff_stream_t stream) {
   using namespace tmdiff;
   TMDIFF_REQUIRE(d && workspace, "conv3d_w2_fwd: NULL pointer");
-  if (!w2_shape_ok(d))
+  if (!w2_epilogue_ok(d))
     return fail(TMDIFF_E_UNSUPPORTED, "conv3d_w2_fwd: fp32 3x3x3, groups 1, one input tensor, 4 or 8 bands, even W <= 16, 4 <= H <= 32, "
-                                      "Cin >= 128 (%% 32), Cout >= 256 (%% 64), plain y / y2 / residual epilogue");
+                                      "Cin >= 128 (%% 32), Cout >= 256 (%% 64); a folded 1x1x1 (rc_cin %% 32 == 0, at most 512, no residual) "
+                                      "and LL / Haar / space-to-depth outputs (8 bands) on even H");
   const W2Plan p = w2_plan(d);
   if (!w2_fits(d, p)) return fail(TMDIFF_E_UNSUPPORTED, "conv3d_w2_fwd: tensor too large for 32-bit offsets");
-  TMDIFF_REQUIRE(d->seg_x[0] && d->w_packed && (d->y || d->y2), "conv3d_w2_fwd: input, weights and an output");
+  TMDIFF_REQUIRE(d->seg_x[0] && d->w_packed && (d->y || d->y2 || d->y_ll), "conv3d_w2_fwd: input, weights and an output");
   TMDIFF_REQUIRE(aligned16(d->seg_x[0]) && aligned16(workspace) && aligned16(d->w_packed) && aligned16(d->y) && aligned16(d->y2) &&
-                     aligned16(d->residual),
+                     aligned16(d->residual) && aligned16(d->y_ll) && aligned16(d->y_hi[0]) && aligned16(d->y_hi[1]) &&
+                     aligned16(d->y_hi[2]) && aligned16(d->rc_x) && aligned16(d->rc_w),
                  "conv3d_w2_fwd: 16-byte aligned tensors / workspace");
+  TMDIFF_REQUIRE(!d->rc_x || d->rc_w, "conv3d_w2_fwd: rc_x without rc_w");
   hipStream_t st = as_stream(stream);
   float* xh = static_cast<float*>(workspace);
   float* mh = xh + p.xh_floats;
@@ -484,9 +710,17 @@ extern "C" int tmdiff_conv3d_w2_fwd(const tmdiff_conv3d_desc* d, void* workspace
     a.y2_scale_stride = bank_stride(d->y2_scale_stride, d->Cout);
     a.Cout = d->Cout; a.N = d->N; a.H = d->H; a.W = d->W; a.T = p.T; a.TW = p.TW; a.OP = p.OP;
     a.QOP = (long)p.Q * p.OP;
+    a.y_ll = d->y_ll; a.y2_s2d = d->y2 && d->y2_s2d ? 1 : 0;
+    for (int i = 0; i < 3; ++i) a.y_hi[i] = d->y_hi[0] ? d->y_hi[i] : nullptr;
+    a.rc_x = d->rc_x; a.rc_w = d->rc_w; a.rc_cin = d->rc_cin;
     const dim3 grid((unsigned)(d->Cout / 32), (unsigned)d->H, (unsigned)p.Q);
 #define TMDIFF_W2_OUT(Y, R, Y2) w2_output_kernel<Y, R, Y2><<<grid, 256, 0, st>>>(a)
-    if (d->y) {
+    if (w2_folds(d) || w2_quarter(d)) {      // the row-pair form (w2_epilogue_ok: even H)
+      const dim3 grid2((unsigned)(d->Cout / 32), (unsigned)(d->H / 2), (unsigned)p.Q);
+      if (d->rc_x) w2_output2_kernel<false, true><<<grid2, 256, 0, st>>>(a);
+      else if (d->residual) w2_output2_kernel<true, false><<<grid2, 256, 0, st>>>(a);
+      else w2_output2_kernel<false, false><<<grid2, 256, 0, st>>>(a);
+    } else if (d->y) {
       if (d->residual) { if (d->y2) TMDIFF_W2_OUT(true, true, true); else TMDIFF_W2_OUT(true, true, false); }
       else             { if (d->y2) TMDIFF_W2_OUT(true, false, true); else TMDIFF_W2_OUT(true, false, false); }
     } else {

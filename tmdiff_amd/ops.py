@@ -36,6 +36,7 @@ class KernelConfig:
                                                          (1 = force the production family onto small test batches)
     wino2d             TMDIFF_WINO2D            True     deep layers (routing.wino2d_ok) on conv3d_w2: Winograd along the width as well,
                                                          as transform passes + one GEMM per plane; False = conv3d_wf
+    wino2d_epilogue    TMDIFF_WINO2D_EPILOGUE   True     ... also the launches with a folded 1x1x1 / LL / Haar / space-to-depth epilogue
     ll_compose         TMDIFF_LL_COMPOSE        True     main-branch Conv_0 + halved LL band as one composed convolution
     wfll               TMDIFF_WFLL              True     ... with Winograd on top (conv3d_wf's composed-LL mode) in inference
     train_ll_wino      TMDIFF_TRAIN_LL_WINO     True     ... and in the finetune forward; False = conv3d_ll there
@@ -92,6 +93,7 @@ class KernelConfig:
         "sample_graph": ("TMDIFF_SAMPLE_GRAPH", _FLAG(False), False),
         "grad_bf16": ("TMDIFF_GRAD_BF16", _FLAG(False), False),
         "wino2d": ("TMDIFF_WINO2D", _FLAG(True), True),
+        "wino2d_epilogue": ("TMDIFF_WINO2D_EPILOGUE", _FLAG(True), True),
     }
 
     def __init__(self, env=None):
@@ -393,10 +395,10 @@ def make_conv_desc(segs, w_packed, cout, ksize, y, groups=1, bias=None, bias_sca
     A y2 of dtype int16 is written as bf16 units [B, Cout/8, N*H*W, 8]; x_bf16_shape = (N, H, W) says that segs[0] is
     such a tensor (bf16 entry point only).  drop = (seed, p): in-kernel dropout of the prologue output (no mask tensor).
     out_div = 2: outputs / residual at half the H and W of the input (tmdiff_conv3d_ll_fwd).  y2_s2d: y2 in space-to-depth
-    form [B, 4 Cout, N, H/2, W/2] (tmdiff_conv3d_wf_fwd only); x_s2d: segs[0] is such a tensor and the descriptor is that of
+    form [B, 4 Cout, N, H/2, W/2] (tmdiff_conv3d_wf_fwd / _w2_fwd); x_s2d: segs[0] is such a tensor and the descriptor is that of
     the convolution on the full-resolution tensor it stands for (tmdiff_conv3d_wfll_fwd).  res_conv = (x_raw [B, Cx, N, H, W],
     the 1x1x1 weight [Cout, Cx, 1, 1, 1] itself (contiguous fp32, not packed), Cx): a ResBlock's res_conv folded into the epilogue (tmdiff_conv3d_wf_fwd
-    only; desc.rc_*) -- the caller passes res_conv's bias as `bias` and no residual.  side_xp = dict(out= [B, Cin, N, H, W], shift=, shift_stride=,
+    / _w2_fwd; desc.rc_*) -- the caller passes res_conv's bias as `bias` and no residual.  side_xp = dict(out= [B, Cin, N, H, W], shift=, shift_stride=,
     act=): a 1x1x1 convolution on the bandwidth kernel also writes act(x + shift) of its (segmented) input there -- the prologue
     output another convolution of the same input wants (desc.xp_*; routing.k1_side_xp)."""
     d = Conv3dDesc()
@@ -651,7 +653,7 @@ def conv3d(segs, w_packed, cout, ksize, out=None, math="fp32", pack_input=None, 
     xp_out (fp32, 3x3x3): a [B, Cin, N, H, W] tensor that receives the prologue output x' (forces the staged kernel, whose
     prologue pass writes it there instead of the shared scratch) -- the training path keeps it for the weight gradient."""
     if kw.get("res_conv") is not None or kw.get("y_ll") is not None or (emit is not None and (emit.get("ll") or emit.get("dwt"))):
-        raise ValueError("conv3d: only conv3d_wf folds a residual convolution into its epilogue / writes the LL band")
+        raise ValueError("conv3d: only conv3d_wf / conv3d_w2 fold a residual convolution into their epilogue / write the LL band")
     b, _, n, h, w = segs[0].shape if x_bf16_shape is None else (segs[0].shape[0], None, *x_bf16_shape)
     dev = segs[0].device
     bf16 = math == "bf16"
@@ -751,10 +753,12 @@ def conv3d_auto(segs, weights, cout, groups=1, math="fp32", emit=None, keep_y=Tr
     fam = family or routing.conv3_family(b, cin, cout, n, h, w, groups, plain=plain, masked=masked, dropout=dropout,
                                          keep_xp=xp_out is not None)
     if (fam in ("wf", "wf_pair") and weights.w2 is not None and family is None and xp_out is None and len(segs) == 1 and
-            not masked and not dropout and kw.get("res_conv") is None and
-            not (emit is not None and (emit.get("s2d") or emit.get("ll") or emit.get("dwt"))) and
-            routing.wino2d_route(b, cin, cout, n, h, w, groups)):
-        return conv3d_w2(segs[0], weights.w2(), cout, emit=emit, keep_y=keep_y, **kw)
+            not masked and not dropout):
+        rc = kw.get("res_conv")
+        quarter = bool(emit is not None and (emit.get("s2d") or emit.get("ll") or emit.get("dwt")))
+        if (routing.wino2d_epilogue_route(b, cin, cout, n, h, w, groups, int(rc[2]) if rc is not None else 0, quarter)
+                if (rc is not None or quarter) else routing.wino2d_route(b, cin, cout, n, h, w, groups)):
+            return conv3d_w2(segs[0], weights.w2(), cout, emit=emit, keep_y=keep_y, **kw)
     if fam in ("wf", "wf_pair") and weights.wf is not None:
         return conv3d_wf(segs, weights.wf(), cout, emit=emit, keep_y=keep_y, groups=groups, xp_out=xp_out, **kw)
     if fam in ("wino4", "wino2") and weights.wino is not None:
@@ -763,7 +767,7 @@ def conv3d_auto(segs, weights, cout, groups=1, math="fp32", emit=None, keep_y=Tr
         return fallback.conv3d_wino(segs, weights.wino(planes), cout, planes, emit=emit, keep_y=keep_y, groups=groups,
                                     xp_out=xp_out, **kw)
     if (emit is not None and (emit.get("s2d") or emit.get("ll") or emit.get("dwt"))) or kw.get("res_conv") is not None:
-        raise ValueError("conv3d_auto: only conv3d_wf writes a space-to-depth second output / folds a residual convolution "
+        raise ValueError("conv3d_auto: only conv3d_wf / conv3d_w2 write a space-to-depth second output / fold a residual convolution "
                          "(ask routing.wf_route first)")
     if fam not in ("staged", "fused"):      # (a direct family named by conv3_family is direct_family's answer already)
         fam = routing.direct_family(cin, cout, groups, plain, masked, dropout, xp_out is not None, extents=(b, n, h, w))
@@ -829,22 +833,44 @@ def pack_conv_weight_w2(w):
 def conv3d_w2(x, w_packed, cout, emit=None, keep_y=True, stages=0, **kw):
     """conv3d([x], ...) (fp32, 3x3x3, groups 1) with Winograd along the bands AND the width (csrc/conv3d_w2.hip): an input pass
     (the prologue keywords in_shift / in_scale / in_act are applied on the way), one GEMM per Winograd plane, an output pass with
-    bias / residual / out_scale / emit as in conv3d.  The Winograd-domain arrays live in the per-stream scratch "w2", lent to
-    the library like the split-K workspace.  w_packed from pack_conv_weight_w2; shapes: routing.wino2d_ok.  stages: a bit mask
-    of the launches that run (1 input pass, 2 GEMM, 4 output pass; timing), 0 = all."""
+    bias / residual / out_scale / emit as in conv3d -- and, as conv3d_wf (same checks, same return conventions), emit's s2d /
+    ll / dwt outputs and res_conv= (the folded 1x1x1, multiplied inside the output pass).  The Winograd-domain arrays live in
+    the per-stream scratch "w2", lent to the library like the split-K workspace.  w_packed from pack_conv_weight_w2; shapes:
+    routing.wino2d_ok, with those epilogues routing.wino2d_epilogue_ok.  stages: a bit mask of the launches that run (1 input
+    pass, 2 GEMM, 4 output pass; timing), 0 = all."""
     b, _, n, h, w = x.shape
     dev = x.device
-    if emit is not None and (emit.get("s2d") or emit.get("ll") or emit.get("dwt")):
-        raise ValueError("conv3d_w2: no space-to-depth / LL / Haar outputs (conv3d_wf writes those)")
-    y, y2 = _outputs("conv3d_w2", dev, (b, cout, n, h, w), keep_y, emit, (b, cout, n, h, w))
-    d = make_conv_desc([x], w_packed, cout, 3, y, y2=y2, **kw, **_emit_kw(emit))
-    if not lib.tmdiff_conv3d_w2_supported(C.byref(d)):
-        raise ValueError("conv3d_w2: shape not supported (routing.wino2d_ok)")
+    s2d = bool(emit is not None and emit.get("s2d"))
+    want_ll = bool(emit is not None and emit.get("ll"))      # third output: LL(y) / 2 instead of y (returns (y2, y_ll))
+    want_dwt = bool(emit is not None and emit.get("dwt"))    # the whole Haar transform instead of y: returns (LL', LH, HL, HH)
+    if want_dwt and (s2d or want_ll):
+        raise ValueError("conv3d_w2: emit dwt=True excludes s2d / ll")
+    want_ll = want_ll or want_dwt
+    if want_ll and keep_y:
+        raise ValueError("conv3d_w2: the LL output replaces y (keep_y=False)")
+    rc = kw.get("res_conv")
+    if rc is not None and kw.get("residual") is not None:
+        raise ValueError("conv3d_w2: res_conv excludes a residual tensor")
+    if (s2d or want_ll or rc is not None) and not routing.wino2d_epilogue_ok(b, x.shape[1], cout, n, h, w, 1,
+                                                                             int(rc[2]) if rc is not None else 0, s2d or want_ll):
+        raise ValueError("conv3d_w2: this launch cannot fold a 1x1x1 / write a space-to-depth / LL output "
+                         "(ask routing.wino2d_epilogue_ok first)")
+    q = (b, cout, n, h // 2, w // 2)
+    y_ll = torch.empty(*q, device=dev, dtype=torch.float32) if want_ll else None
+    y_hi = [torch.empty(*q, device=dev, dtype=torch.float32) for _ in range(3)] if want_dwt else None
+    y, y2 = _outputs("conv3d_w2", dev, (b, cout, n, h, w), keep_y, emit,
+                     None if want_dwt else ((b, 4 * cout, n, h // 2, w // 2) if s2d else (b, cout, n, h, w)))
+    d = make_conv_desc([x], w_packed, cout, 3, y, y2=y2, y2_s2d=s2d, y_ll=y_ll, y_hi=y_hi, **kw, **_emit_kw(emit))
+    if not lib.tmdiff_conv3d_w2_epilogue_supported(C.byref(d)):
+        raise ValueError("conv3d_w2: shape not supported (routing.wino2d_ok / wino2d_epilogue_ok)")
     nws = lib.tmdiff_conv3d_w2_workspace_bytes(C.byref(d))
     ws = _workspace(dev, nws, "w2").data_ptr()
-    # EXECUTED flops: 24 planes x 3 row taps per tile of four bands and two columns = 9 multiply-adds per (ci, co, output)
-    _launch(lib.tmdiff_conv3d_w2_fwd, d, (ws, int(stages)), "conv3d_w2_fwd", "conv3d_w2_fwd", 2.0 * b * cout * d.Cin * 9.0 * n * h * w)
-    return _result(y, y2)
+    # EXECUTED flops: 24 planes x 3 row taps per tile of four bands and two columns = 9 multiply-adds per (ci, co, output), plus
+    # the folded res_conv's rc_cin multiply-adds per output
+    flops = 2.0 * b * cout * (d.Cin * 9.0 + d.rc_cin) * n * h * w
+    _launch(lib.tmdiff_conv3d_w2_fwd, d, (ws, int(stages)), "conv3d_w2_fwd", "conv3d_w2_fwd", flops, 3,
+            f" +rc{d.rc_cin}" if d.rc_cin else "")
+    return (y_ll, *y_hi) if want_dwt else (y2, y_ll) if want_ll else _result(y, y2)
 
 
 def pack_conv_weight_ll(w, ll_scale=0.5):

@@ -188,9 +188,33 @@ def wino2d_ok(b, cin, cout, n, h, w, groups=1):
 
 def wino2d_route(b, cin, cout, n, h, w, groups=1):
     """True when a convolution of these extents that conv3_family gave to conv3d_wf runs on conv3d_w2 instead (config.wino2d).
-    ops.conv3d_auto adds what it knows of the launch: one input tensor, no mask / dropout, no folded 1x1x1, no LL / Haar /
-    space-to-depth output -- those launches stay on conv3d_wf."""
+    ops.conv3d_auto adds what it knows of the launch: one input tensor, no mask / dropout; a launch with a folded 1x1x1 or an
+    LL / Haar / space-to-depth output asks wino2d_epilogue_route instead."""
     return bool(_config().wino2d and wino2d_ok(b, cin, cout, n, h, w, groups))
+
+
+def wino2d_epilogue_ok(b, cin, cout, n, h, w, groups=1, rc_cin=0, quarter=False):
+    """The launches conv3d_w2 takes beyond wino2d_ok's plain epilogue, on its row-pair output pass: the shapes of wino2d_ok
+    with a folded 1x1x1 of rc_cin input channels (rc_cin % 32 == 0, at most 512; no residual tensor beside it) and / or, quarter,
+    the quarter-resolution outputs (LL instead of y, the whole Haar transform, the space-to-depth second output: 8 bands) --
+    either on an even number of rows.  The mirror of tmdiff_conv3d_w2_epilogue_supported for the descriptors ops.conv3d_w2
+    builds (tests/test_conv3d_w2_epilogue_host.py holds the two together); with neither it is wino2d_ok."""
+    if not wino2d_ok(b, cin, cout, n, h, w, groups):
+        return False
+    if not rc_cin and not quarter:
+        return True
+    if h % 2 or (quarter and n != 8):
+        return False
+    return not rc_cin or (rc_cin > 0 and rc_cin % 32 == 0 and rc_cin <= 512 and rc_cin * n * h * w < (1 << 30))
+
+
+def wino2d_epilogue_route(b, cin, cout, n, h, w, groups=1, rc_cin=0, quarter=False):
+    """True when a conv3d_wf launch with a folded 1x1x1 and / or quarter-resolution outputs runs on conv3d_w2 instead: both
+    switches (config.wino2d, config.wino2d_epilogue) and wino2d_epilogue_ok.  All three classes of the benchmark step
+    (256->256 at 8x16x16: LL + folded 1x1x1 with a plain or a space-to-depth second output, the whole Haar transform)
+    measured faster than on conv3d_wf (profiles/wino2d_epilogue.txt): none is held back."""
+    cfg = _config()
+    return bool(cfg.wino2d and cfg.wino2d_epilogue and wino2d_epilogue_ok(b, cin, cout, n, h, w, groups, rc_cin, quarter))
 
 
 def wfll_route(b, cin, cout, n, h, w):
