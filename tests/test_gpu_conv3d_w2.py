@@ -3,7 +3,8 @@ plane, against fp64 torch.nn.functional.conv3d on the CPU followed by the fp64 e
 conv3d_wf, the kernel these launches ran on before (printed; profiles/wino2d.txt holds both columns).
 
 Shapes are small, not the workload's: B = 2, 128 -> 256 channels, planes 8x8x8 and 8x16x16, one 4-band case, one ragged plane
-(8x12x10: five column pairs, tiles that end inside a block of 32 positions, a last GEMM tile with fewer images).  The bound is the
+(8x12x10: five column pairs, a GEMM tile that ends inside a block of 32 positions -- but no last tile with fewer images than G:
+Q = 4 = G there; test_gpu_conv3d_w2_edges.py has that and the other shape families).  The bound is the
 one test_conv3d_winograd_in_kernel_transform and the fold tests hold, 2e-5 of the output's largest element, tightened to twice
 the worst error this path measured on these cases (profiles/wino2d.txt): the nested transform adds one stage to conv3d_wf's."""
 import numpy as np
