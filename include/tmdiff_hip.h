@@ -776,6 +776,37 @@ int tmdiff_ssim_loss(const float* x_true, const float* x_pred, const float* ms, 
                      size_t workspace_bytes, int32_t B, int32_t C, int32_t H, int32_t W, tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * The local PAN-correlation loss with its gradient (csrc/local_corr.hip; host definition: tmdiff_amd/metrics.py
+ * local_corr_loss):
+ *     loss = mean over b, c and windows of max(0, rho_max[c] - rho),   D_rho = 1 - mean rho
+ * on dense fp32 x [B, C, H, W] and pan [B, 1, H, W].
+ *  rho : the correlation coefficient of a band and the PAN inside a win x win window, every window at stride 1, 'valid',
+ *    n = win^2, from two-pass centred sums: mx = sum(x) / n, mp = sum(p) / n, then S_xx = sum (x - mx)^2, S_pp = sum (p - mp)^2,
+ *    S_xp = sum (x - mx)(p - mp); rho = S_xp / sqrt(S_xx S_pp), and 0 where S_xx S_pp == 0 exactly (no eps: a window that is
+ *    constant in either image gives exactly 0 and no gradient).  A window is active iff rho < rho_max[c].
+ *  rho_max : fp64 [C] on the device, or NULL for 1.0 in every band.
+ *  g (fp32 [B, C, H, W]): accumulate == 0 stores weight * d loss / d x, rounded to fp32 once; accumulate == 1 stores
+ *    fl32(g + weight * d loss / d x); g == NULL selects the value-only mode, which writes no gradient (accumulate must then be
+ *    0, else TMDIFF_E_INVALID).  pan gets no gradient.
+ *  out64 : fp64 [2] = loss, mean rho.  per_image (fp64 [B], may be NULL): the mean rho of each image.  out32 : the float of
+ *    weight * loss.
+ * Every operation after the fp32 loads is fp64.  No atomics: each workgroup (one per image and 16 x 32 tile, walking the bands
+ * with the PAN tile staged once) stores two fp64 partial sums into `workspace` and one finalize launch adds them in a fixed
+ * order, image by image, so a call is reproducible bit for bit and an image's mean does not depend on the batch it is in.
+ * Nothing is allocated, synchronised or copied: a call can be captured into a graph on `stream`.  16-byte accesses when
+ * W % 4 == 0 and the tensors are 16-byte aligned, scalar ones otherwise, with the same values.
+ * workspace: 8-byte aligned, tmdiff_local_corr_loss_workspace_bytes(B, C, H, W, win) = 16 * B * ceil(H / 16) * ceil(W / 32) bytes.
+ * Limits: B >= 1, 1 <= C <= 16, 2 <= win <= 8 (even and odd), H, W >= win, B * C * H * W <= 2^31 - 1; for anything else
+ * tmdiff_local_corr_loss_supported is 0 and the workspace size is 0.  The entry point returns TMDIFF_E_UNSUPPORTED without
+ * launching for those, and for a weight that is not finite and >= 0.  (Added within version 6.)
+ * ------------------------------------------------------------------------------------ */
+int tmdiff_local_corr_loss_supported(int32_t B, int32_t C, int32_t H, int32_t W, int32_t win);
+size_t tmdiff_local_corr_loss_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t win);
+int tmdiff_local_corr_loss(const float* x, const float* pan, float* g, const double* rho_max, int32_t win, double weight,
+                           int32_t accumulate, double* out64, double* per_image, float* out32, void* workspace,
+                           size_t workspace_bytes, int32_t B, int32_t C, int32_t H, int32_t W, tmdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Resampling of full-resolution scenes (csrc/resample.hip; host definitions: tmdiff_amd/metrics.py).  Dense fp32 planes
  * [planes, H, W]; nothing is allocated or synchronised, so a call can be captured into a graph on `stream`.
  *  pyr_down: `levels` (1 or 2) steps of OpenCV's pyrDown with its defaults -- separable [1 4 6 4 1] / 16, horizontal pass then

@@ -224,6 +224,12 @@ SIGNATURES.update({
     "tmdiff_ssim_loss_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
     "tmdiff_ssim_loss": (C.c_int, [vp] * 4 + [C.c_int32, C.c_double, C.c_double, C.c_int32, vp, vp, vp, vp, C.c_size_t] +
                          [C.c_int32] * 4 + [vp]),
+    # local PAN-correlation loss (csrc/local_corr.hip): x, pan, g, rho_max | win, weight, accumulate | out64, per_image, out32,
+    # workspace, bytes | B, C, H, W
+    "tmdiff_local_corr_loss_supported": (C.c_int, [C.c_int32] * 5),
+    "tmdiff_local_corr_loss_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "tmdiff_local_corr_loss": (C.c_int, [vp] * 4 + [C.c_int32, C.c_double, C.c_int32, vp, vp, vp, vp, C.c_size_t] +
+                               [C.c_int32] * 4 + [vp]),
     # resampling (csrc/resample.hip): (planes, H, W, levels | ratio) after the two tensors
     "tmdiff_pyr_down": (C.c_int, [vp, vp] + [C.c_int32] * 4 + [vp]),
     "tmdiff_upsample_bilinear": (C.c_int, [vp, vp] + [C.c_int32] * 4 + [vp]),

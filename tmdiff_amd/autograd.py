@@ -753,3 +753,32 @@ class SpectralSpatialSSIMLossFn(torch.autograd.Function):
 
 def spectral_spatial_ssim_loss(x0, xhat, ms, base="l1", w_sam=0.0, w_lap=0.0, w_dssim=0.0):
     return SpectralSpatialSSIMLossFn.apply(x0, xhat, ms, base, float(w_sam), float(w_lap), float(w_dssim))
+
+
+class LocalCorrLossFn(torch.autograd.Function):
+    """ops.local_corr_loss as a scalar loss, in the pattern of SSIMLossFn: the forward's kernel pair writes the loss and
+    g = d loss / d x, which is saved; backward is g * grad_out for x alone (pan gets None, also when it asks for a gradient).
+    When x needs no gradient the forward runs in the value-only mode, saves nothing, and backward returns None for everything.  Returns (loss float32 [], terms float64 [2] = loss, mean rho); terms is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, pan, win, rho_max):
+        want = ctx.needs_input_grad[0]
+        terms, total, g = ops.local_corr_loss(x.contiguous(), pan.contiguous(), win, rho_max, 1.0, grad=want)
+        ctx.has_g = want
+        if want:
+            ctx.save_for_backward(g)
+        ctx.mark_non_differentiable(terms)
+        return total, terms
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_terms):
+        if not ctx.has_g:                    # only pan asked for a gradient, and it gets none
+            return None, None, None, None
+        g, = ctx.saved_tensors
+        return g * grad_out, None, None, None
+
+
+def local_corr_loss(x, pan, win=4, rho_max=None):
+    if rho_max is not None:
+        rho_max = tuple(float(v) for v in rho_max) if hasattr(rho_max, "__len__") else float(rho_max)
+    return LocalCorrLossFn.apply(x, pan, int(win), rho_max)

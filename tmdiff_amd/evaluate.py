@@ -35,7 +35,7 @@ def _to_nchw01(img, min_max=(0.0, 1.0)):
 
 
 def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=print, device_metrics=False,
-                full_resolution=False, q2n=False, protocol="qnr", sensor=None, baselines=()):
+                full_resolution=False, q2n=False, protocol="qnr", sensor=None, baselines=(), d_rho=False):
     """``trainer`` is a ``tmdiff_amd.model.DDPM`` (or the reference's); ``dataset`` is the prompt name.
     Returns ``{"ssim_<dataset>": ..., "sam_<dataset>": ..., "sec_per_item": ...}``.
 
@@ -72,7 +72,13 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
     ``ops.cs_fuse`` with that method (``metrics.cs_fuse``; buffers made once per shape), scored and reported the same way
     (``"<metric>_<dataset>@cs-gsa"``).  So are the names of ``BDSD_BASELINES``: "bdsd", ``ops.bdsd`` with one set of weights per
     image, and "bdsd-local", with weights per 128 x 128 block (``"<metric>_<dataset>@bdsd"``); "bdsd-local" raises ValueError
-    naming the shape when the visuals' extents are not multiples of 128."""
+    naming the shape when the visuals' extents are not multiples of 128.
+
+    ``d_rho=True`` (with ``full_resolution=True`` only: ValueError otherwise) adds ``d_rho_<dataset>``, the local PAN-correlation
+    index ``metrics.d_rho`` of SR against PAN with 4 x 4 windows (``ops.local_corr_loss`` in its value-only mode; the sums stay on
+    the device and join the single synchronising read), and ``d_rho_<dataset>@<baseline>`` for every baseline."""
+    if d_rho and not full_resolution:
+        raise ValueError("val_dataset(d_rho=True) scores without ground truth: it needs full_resolution=True")
     baselines = tuple(baselines)
     known = BASELINES + CS_BASELINES + BDSD_BASELINES
     if [b for b in baselines if b not in known] or len(set(baselines)) != len(baselines):
@@ -127,6 +133,18 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
                 fused = ops.mtf_glp(ms_d, pan_d, sensor, 4, name, out=out, buffers=buf)
             row = score_row(fused)
             base_sum[name] = row if name not in base_sum else base_sum[name] + row
+
+    def with_d_rho(score_row, pan_d):
+        """score_row, or with d_rho=True score_row with 1 - the mean rho of the image appended"""
+        if not d_rho:
+            return score_row
+        from . import ops
+
+        def both(f):
+            mean_rho = torch.empty(f.shape[0], device=f.device, dtype=torch.float64)
+            ops.local_corr_loss(f, pan_d, 4, grad=False, per_image=mean_rho)
+            return torch.cat([score_row(f), 1.0 - mean_rho[:1]])          # image 0, as the rows beside it ([0])
+        return both
     t0 = time.time()
     for idx, val_data in enumerate(val_loader):
         trainer.feed_data(val_data)
@@ -144,10 +162,11 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
             ms_d, pan_d, sr_d = _to_nchw01(vis["MS"]), _to_nchw01(vis["PAN"]), _to_nchw01(vis["SR"][-1])
             if sr_d.shape not in full_ws:
                 full_ws[sr_d.shape] = ops.metrics_hqnr_buffers(*sr_d.shape, sr_d.device)
-            row = ops.metrics_hqnr(sr_d, ms_d, pan_d, sensor, buffers=full_ws[sr_d.shape])[0]
+            score_row = with_d_rho(lambda f: ops.metrics_hqnr(f, ms_d, pan_d, sensor, buffers=full_ws[sr_d.shape])[0], pan_d)
+            row = score_row(sr_d)
             full_sum = row if full_sum is None else full_sum + row
             if baselines:
-                score_baselines(ms_d, pan_d, lambda f: ops.metrics_hqnr(f, ms_d, pan_d, sensor, buffers=full_ws[sr_d.shape])[0])
+                score_baselines(ms_d, pan_d, score_row)
         elif full_resolution:
             from . import ops
             lr_d, pan_d, sr_d = _to_nchw01(vis["LR"]), _to_nchw01(vis["PAN"]), _to_nchw01(vis["SR"][-1])
@@ -156,10 +175,12 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
                 full_ws[key] = (torch.empty(1, 1, *ops.pyr_down_shape(*pan_d.shape[2:]), device=pan_d.device),
                                 ops.metrics_workspace(*sr_d.shape, sr_d.device))
             l_pan, ws = full_ws[key]
-            row = ops.metrics_noref(lr_d, pan_d, ops.pyr_down(pan_d, 2, out=l_pan), sr_d, workspace=ws)[0]
+            ops.pyr_down(pan_d, 2, out=l_pan)
+            score_row = with_d_rho(lambda f: ops.metrics_noref(lr_d, pan_d, l_pan, f, workspace=ws)[0], pan_d)
+            row = score_row(sr_d)
             full_sum = row if full_sum is None else full_sum + row
             if baselines:
-                score_baselines(_to_nchw01(vis["MS"]), pan_d, lambda f: ops.metrics_noref(lr_d, pan_d, l_pan, f, workspace=ws)[0])
+                score_baselines(_to_nchw01(vis["MS"]), pan_d, score_row)
         elif "HR" in vis and device_metrics:
             from . import ops
             hr_d, sr_d = _to_nchw01(vis["HR"]), _to_nchw01(vis["SR"][-1])
@@ -182,7 +203,7 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
             sam_sum += metrics.sam(hr, sr)
         n += 1
     if full_resolution:
-        fields = metrics.HQNR_FIELDS if hqnr else metrics.NOREF_FIELDS
+        fields = (metrics.HQNR_FIELDS if hqnr else metrics.NOREF_FIELDS) + (("d_rho",) if d_rho else ())
         if base_sum:                                                                  # the baselines join the one read
             total = torch.cat([full_sum] + [base_sum[b] for b in baselines]).tolist()
         else:

@@ -197,3 +197,31 @@ class SSIMLoss(nn.Module):
         total, terms = autograd.ssim_loss(x_true, x_pred, self.win, self.data_range)
         self.last_terms = terms
         return total
+
+
+class LocalCorrLoss(nn.Module):
+    """``forward(x, pan)`` -> the float32 scalar mean of max(0, rho_max_c - rho) over the bands and all win x win windows, rho the
+    local correlation coefficient of a band of x [B, C, H, W] with pan [B, 1, H, W] (``metrics.local_corr_loss``), differentiable
+    in ``x``, from the HIP kernel pair of csrc/local_corr.hip (float32 tensors on the GPU; there is no host path behind it).
+    ``rho_max``: None (1.0), a number, or one per band.  ``last_terms``: the float64 [2] device tensor (loss, mean rho) of the
+    last call; no host read happens here."""
+
+    def __init__(self, win=4, rho_max=None):
+        super().__init__()
+        if not (isinstance(win, int) and 2 <= win <= 8):
+            raise ValueError(f"LocalCorrLoss: win must be a whole number with 2 <= win <= 8, got {win!r}")
+        if rho_max is not None:
+            rho_max = tuple(float(v) for v in rho_max) if hasattr(rho_max, "__len__") else float(rho_max)
+            if not all(math.isfinite(v) for v in (rho_max if isinstance(rho_max, tuple) else (rho_max,))):
+                raise ValueError(f"LocalCorrLoss: rho_max must be finite, got {rho_max!r}")
+        self.win, self.rho_max = win, rho_max
+        self.last_terms = None
+
+    def extra_repr(self):
+        return f"win={self.win}, rho_max={self.rho_max}"
+
+    def forward(self, x, pan):
+        from . import autograd
+        total, terms = autograd.local_corr_loss(x, pan, self.win, self.rho_max)
+        self.last_terms = terms
+        return total

@@ -1409,6 +1409,73 @@ def ssim_loss(x_true, x_pred, win=7, data_range=1.0, weight=1.0, grad=True, accu
     return y, y32, g
 
 
+# ---- local PAN-correlation loss (csrc/local_corr.hip; definition: tmdiff_amd/metrics.py local_corr_loss) ----------------
+_LCORR_LIMITS = "B >= 1, 1 <= C <= 16, 2 <= win <= 8, H, W >= win, fewer than 2^31 elements"
+LOCAL_CORR_TILE = (16, 32)     # rows x columns of the kernel's tile (TH, TW of csrc/local_corr.hip), for every window size
+_LCORR_RHO_MAX = {}            # (values, device) -> the uploaded float64 [C] table; the last _LCORR_RHO_MAX_TABLES, oldest dropped first
+_LCORR_RHO_MAX_TABLES = 8
+
+
+def local_corr_loss_supported(b, c, h, w, win=4):
+    """True when local_corr_loss takes x [b, c, h, w] with a win x win window."""
+    return bool(lib.tmdiff_local_corr_loss_supported(int(b), int(c), int(h), int(w), int(win)))
+
+
+def _rho_max_table(rho_max, c, device):
+    """None, or the float64 [C] device table of ``rho_max`` (a number or C numbers), made once per (values, device): call once
+    before capturing.  The cache keeps the last few tables, so sweeping ``rho_max`` does not pile up device memory; as with the
+    scaled tap tables of ``_mtf_taps``, a captured graph reads the table it recorded, so more than _LCORR_RHO_MAX_TABLES other
+    values must not pass through here between its capture and its last replay."""
+    if rho_max is None:
+        return None
+    vals = tuple(float(v) for v in rho_max) if isinstance(rho_max, (list, tuple)) or hasattr(rho_max, "__len__") else (float(rho_max),)
+    vals = vals * c if len(vals) == 1 else vals
+    if len(vals) != c or not all(v == v and abs(v) < float("inf") for v in vals):
+        raise ValueError(f"local_corr_loss: rho_max={rho_max!r} (None, a finite number, or one per band: {c})")
+    key = (vals, device)
+    if key not in _LCORR_RHO_MAX:
+        _LCORR_RHO_MAX[key] = torch.tensor(vals, dtype=torch.float64).to(device)
+        while len(_LCORR_RHO_MAX) > _LCORR_RHO_MAX_TABLES:
+            del _LCORR_RHO_MAX[next(iter(_LCORR_RHO_MAX))]          # dicts keep insertion order: the oldest
+    return _LCORR_RHO_MAX[key]
+
+
+def local_corr_loss(x, pan, win=4, rho_max=None, weight=1.0, grad=True, accumulate=False, out=None, per_image=None, total=None,
+                    workspace=None):
+    """The mean over b, c and all win x win windows ('valid', stride 1) of max(0, rho_max_c - rho), rho the correlation
+    coefficient of band c of x [B, C, H, W] with pan [B, 1, H, W] inside the window (float32 on the GPU; definition:
+    ``metrics.local_corr_loss``), two launches.  Returns (out, total32, g): out float64 [2] = loss, mean rho; total32 the
+    float32 of weight * loss; g = weight * d loss / d x (float32, the shape of x; the PAN gets none).  ``rho_max``: None (1.0), a
+    number or C numbers, kept on the device as a cached float64 table.  ``grad``: True allocates g, a tensor receives it, False
+    selects the value-only mode (g is None, nothing is written).  ``accumulate`` adds the gradient to the tensor given as
+    ``grad``.  ``per_image``: a float64 [B] tensor that receives each image's mean rho (1 - D_rho)."""
+    win, weight = int(win), float(weight)
+    if not 0.0 <= weight < float("inf"):
+        raise ValueError(f"local_corr_loss: weight must be finite and not negative, got {weight}")
+    if x.dim() != 4 or pan.dim() != 4 or tuple(pan.shape) != (x.shape[0], 1, *x.shape[2:]):
+        raise ValueError(f"local_corr_loss: need x [B, C, H, W] and pan [B, 1, H, W], got {tuple(x.shape)}, {tuple(pan.shape)}")
+    b, c, h, w = x.shape
+    if not local_corr_loss_supported(b, c, h, w, win):
+        raise ValueError(f"local_corr_loss: B={b} C={c} H={h} W={w} win={win} is not supported ({_LCORR_LIMITS})")
+    if accumulate and not torch.is_tensor(grad):
+        raise ValueError("local_corr_loss: accumulate=True needs the gradient tensor to add to as `grad`")
+    px, pp = _chk(x, "x"), _chk(pan, "pan")
+    dev = x.device
+    table = _rho_max_table(rho_max, c, dev)
+    g = _grad_target("local_corr_loss", grad, x)
+    y = _f64("local_corr_loss", "out", out, 2, dev)
+    if per_image is not None:
+        _f64("local_corr_loss", "per_image", per_image, (b,), dev)
+    y32 = _total32("local_corr_loss", total, dev)
+    need = lib.tmdiff_local_corr_loss_workspace_bytes(b, c, h, w, win)
+    ws, nbytes = _lent("local_corr_loss", workspace, need, lambda: _workspace(dev, need, "local_corr_loss"))
+    check(lib.tmdiff_local_corr_loss(px, pp, _chk(g, "g"), None if table is None else table.data_ptr(), win, weight,
+                                     int(bool(accumulate)), y.data_ptr(), None if per_image is None else per_image.data_ptr(),
+                                     _chk(y32, "total"), ws.data_ptr(), nbytes, b, c, h, w, stream_ptr()), "local_corr_loss")
+    _count("local_corr_loss")
+    return y, y32, g
+
+
 _Q2N_LIMITS = "1 <= C <= 16, block 8, 16 or 32, 1 <= shift <= block, mirror padding no longer than the axis, fewer than 2^31 elements"
 
 

@@ -20,7 +20,18 @@ and with --step the captured step with loss_terms = {"dssim": 0.1} against plain
 about win + 3 times from LDS and forms 5 n fp64 multiply-adds per window, so unlike the composite pair it is bound by its own
 arithmetic and LDS reads, a few tens of microseconds at these sizes, not by launch latency.
 
-  python tools/bench_loss.py [--leg composite|ssim] [--reps 30] [--calls 50] [--step] [--out profiles/loss_terms.txt]"""
+--leg lcorr times the local PAN-correlation loss (tmdiff_amd.losses.LocalCorrLoss; csrc/local_corr.hip: local_corr_kernel +
+local_corr_finalize, 4 x 4 windows, rho_max 1) at [8, 8, 64, 64] and at [1, 8, 1024, 1024], a full-resolution scene, value-only
+and with the gradient, against mean max(0, 1 - rho) composed from five F.avg_pool2d box filters, elementwise operators and their
+autograd in fp32 (one-pass moments and a clamp where the kernel has two-pass sums and exact zeros).  Beside the pair: bytes moved
+(x and pan read, g written) over its time.  Expectation, stated before the run: the small shape has 64 workgroups of 8 bands
+each on 256 CUs and is bound by the latency of two dependent launches plus one workgroup's walk over its bands; the large
+shape has 2048 workgroups, reads 36 MB and writes 32 MB (11 us at the copy rate) and does about 100 fp64 operations per window
+and band on 1.3 x the windows (the halo), so it should be bound by fp64 arithmetic and LDS reads at a few tens of microseconds.
+(Measured, profiles/local_corr.txt: 286 us, ten times the estimate.  The cause is not measured; the leading candidate is
+register-limited occupancy, one workgroup per CU at win = 4.)
+
+  python tools/bench_loss.py [--leg composite|ssim|lcorr] [--reps 30] [--calls 50] [--step] [--out profiles/loss_terms.txt]"""
 import argparse
 import os
 import statistics
@@ -176,6 +187,57 @@ def bench_ssim_shape(shape, calls, reps, lines):
     return res["kernel pair (value + gradient)"], res["torch operators, loss + backward"]
 
 
+def composed_lcorr(x, pan, win=4):
+    """mean max(0, 1 - rho) from torch operators, fp32: five box means, one-pass moments, a clamp under the square root"""
+    f = lambda t: F.avg_pool2d(t, win, 1)
+    mx, mp = f(x), f(pan)
+    vxx, vpp, vxp = f(x * x) - mx * mx, f(pan * pan) - mp * mp, f(x * pan) - mx * mp
+    rho = vxp / torch.sqrt((vxx * vpp).clamp_min(1e-20))
+    return (1.0 - rho).clamp_min(0.0).mean()
+
+
+def bench_lcorr_shape(shape, calls, reps, lines):
+    from tmdiff_amd import ops
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    x = torch.rand(*shape, device="cuda", generator=gen)
+    pan = 0.6 * x.mean(1, keepdim=True) + 0.4 * torch.rand(shape[0], 1, *shape[2:], device="cuda", generator=gen)
+    n = x.numel()
+    moved = 4 * (2 * n + pan.numel())
+    out, total, g = ops.local_corr_loss(x, pan, 4)
+    ws = torch.empty(max(1, ops.lib.tmdiff_local_corr_loss_workspace_bytes(*shape, 4)), device="cuda", dtype=torch.uint8)
+    leaf = x.clone().requires_grad_(True)
+
+    def pair():
+        ops.local_corr_loss(x, pan, 4, grad=g, out=out, total=total, workspace=ws)
+
+    def value_only():
+        ops.local_corr_loss(x, pan, 4, grad=False, out=out, total=total, workspace=ws)
+
+    def torch_ops():
+        leaf.grad = None
+        composed_lcorr(leaf, pan).backward()
+
+    def torch_value():
+        with torch.no_grad():
+            composed_lcorr(x, pan)
+
+    torch_ops()
+    ref = float(composed_lcorr(x, pan))
+    dg = float((leaf.grad - g).norm() / g.norm())
+    lines.append(f"[{', '.join(map(str, shape))}]  {n} elements, {moved / 1e6:.1f} MB moved by the pair; kernel loss {float(out[0]):.9f}, "
+                 f"torch fp32 composition {ref:.9f}, gradients differ by {dg:.1e} relative L2")
+    res = {}
+    for name, fn in (("kernel pair (value + gradient)", pair), ("kernel pair (value only)", value_only),
+                     ("torch operators, loss + backward", torch_ops), ("torch operators, loss only", torch_value)):
+        slow = fn in (torch_ops, torch_value)
+        med, lo, hi = graph_us(fn, max(1, calls // 10) if slow else calls, reps)
+        emed, _, _ = eager_us(fn, reps)
+        rate = f"   {moved / (med * 1e-6) / 1e12:5.2f} TB/s" if fn is pair else ""
+        lines.append(f"  {name:<34s} {med:8.1f} us in a graph ({lo:.1f} .. {hi:.1f})   {emed:8.1f} us eager{rate}")
+        res[name] = med
+    return res
+
+
 def bench_step(reps, rounds, lines, on=None, label=None):
     """the captured finetune step, terms on against plain l1, alternating"""
     on = on or {"sam": W_SAM, "lap": W_LAP}
@@ -232,7 +294,8 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--step", action="store_true", help="also time the captured finetune step with and without the terms")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--leg", choices=["composite", "ssim"], default="composite", help="ssim: the SSIM term's kernel pair (csrc/ssim_loss.hip)")
+    ap.add_argument("--leg", choices=["composite", "ssim", "lcorr"], default="composite",
+                    help="ssim: the SSIM term's kernel pair (csrc/ssim_loss.hip); lcorr: the local PAN-correlation loss (csrc/local_corr.hip)")
     args = ap.parse_args(argv)
     if args.reps < 7 or args.rounds < 7:
         raise SystemExit("bench_loss: medians of at least 7 runs")
@@ -240,6 +303,8 @@ def main(argv=None):
         raise SystemExit("bench_loss: needs the GPU (a time measured anywhere else says nothing)")
     if args.leg == "ssim":
         return main_ssim(args)
+    if args.leg == "lcorr":
+        return main_lcorr(args)
     lines = [f"# tools/bench_loss.py on {torch.cuda.get_device_name(0)}: l1 + {W_SAM} * SAM + {W_LAP} * LAP; per row the median over {args.reps} "
              f"replays of a graph of {args.calls} back-to-back evaluations (torch operators: {max(1, args.calls // 10)}), 10th .. 90th "
              f"percentile beside it, and the median of {args.reps} eager runs of 20 evaluations"]
@@ -269,6 +334,23 @@ def main_ssim(args):
                  ", ".join(f"{t / p:.2f} x" for p, t in pairs) + (" -- faster at both shapes" if faster else " -- NOT faster everywhere"))
     if args.step:
         bench_step(args.reps, args.rounds, lines, {"dssim": 0.1}, "l1 + 0.1 dssim (composite pair + SSIM pair)")
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+
+
+def main_lcorr(args):
+    lines = [f"# tools/bench_loss.py --leg lcorr on {torch.cuda.get_device_name(0)}: mean max(0, 1 - rho), 4 x 4 windows; per row the median "
+             f"over {args.reps} replays of a graph of {args.calls} back-to-back evaluations (torch operators: {max(1, args.calls // 10)}), 10th "
+             f".. 90th percentile beside it, and the median of {args.reps} eager runs of 20 evaluations"]
+    rows = [bench_lcorr_shape(shape, args.calls, args.reps, lines) for shape in ((8, 8, 64, 64), (1, 8, 1024, 1024))]
+    for what, k, t in (("value + gradient", "kernel pair (value + gradient)", "torch operators, loss + backward"),
+                       ("value only", "kernel pair (value only)", "torch operators, loss only")):
+        ratios = [r[t] / r[k] for r in rows]
+        lines.append(f"the pair against the torch composition, {what} (both from a graph): " + ", ".join(f"{v:.2f} x" for v in ratios) +
+                     (" -- faster at both shapes" if all(v > 1.0 for v in ratios) else " -- NOT faster everywhere"))
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if args.out:
