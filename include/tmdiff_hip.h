@@ -983,6 +983,34 @@ int tmdiff_cg_direction(const float* s, float* p, const double* gamma_new, const
                         int32_t n_full, tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * TV pansharpening (csrc/tv.hip; host definitions: tmdiff_amd/metrics.py, tv_pd_step / tv_norm / tv_pansharpen; the driver:
+ * tmdiff_amd/ops.py, tv_pansharpen): the band-coupled part of a Condat-Vu iteration and the vector total variation.  Dense fp32
+ * images [B, C, H, W], pan [B, 1, H, W], weights float64 [B, C + 1] on the device (the band weights, then an offset).  Forward
+ * differences with a zero last column / row; the transpose never reads ph[:, W - 1] nor pv[H - 1, :].  Nothing is allocated or
+ * synchronised, no atomics, the same bits on every run and on a graph replay; the summation orders are written in the source's
+ * header.
+ *  tv_pd_step: with s = sum_c w_c x_c + w_C - pan per pixel,
+ *                x'  = u - tau (gamma w_c s + D^T p)            rounded to fp32 once
+ *                q   = p + sigma D (2 x' - x)                   from x' as stored, both components, all bands
+ *                p'  = q / max(1, |q| / lam)                    |q| over the 2 C components of the pixel; lam == 0: p' = 0
+ *              in fp64 after the loads.  One workgroup per 16 x 32 tile computes x' on the tile plus one column and one row and
+ *              stores only the tile.  Every input is read with a halo, so no output may overlap an input or another output
+ *              (TMDIFF_E_INVALID): the caller ping-pongs x and p.  tau > 0, sigma, lam, gamma >= 0.
+ *  tv_norm:    out, float64 [B] = sum over the pixels of sqrt(sum_c (Dh x_c)^2 + (Dv x_c)^2), no eps; one partial sum per tile in
+ *              `workspace` (8-byte aligned, tmdiff_tv_norm_workspace_bytes), a finalize launch adds them in index order.
+ *              Limits of all three: B >= 0, 1 <= C <= 16, H, W >= 1, B * C * H * W <= 2^31 - 1; otherwise TMDIFF_E_UNSUPPORTED,
+ *              a workspace size of 0 and tv_supported == 0.
+ *              (Added within version 6.)
+ * ------------------------------------------------------------------------------------ */
+int tmdiff_tv_supported(int32_t B, int32_t C, int32_t H, int32_t W);
+int tmdiff_tv_pd_step(const float* u, const float* x, const float* pan, const float* ph, const float* pv, const double* weights,
+                      double tau, double sigma, double lam, double gamma, float* x_out, float* ph_out, float* pv_out, int32_t B,
+                      int32_t C, int32_t H, int32_t W, tmdiff_stream_t stream);
+size_t tmdiff_tv_norm_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int tmdiff_tv_norm(const float* x, int32_t B, int32_t C, int32_t H, int32_t W, double* out, void* workspace, size_t workspace_bytes,
+                   tmdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Standalone attention operators of core/Attention.py (imported by nothing in the reference; built because the
  * north star names them).  All fp32.
  *  attn_fwd : out = softmax(q k^T * scale [key mask]) v per (batch, head); fp32 MFMA, online softmax.

@@ -264,6 +264,12 @@ SIGNATURES.update({
     "tmdiff_plane_totals": (C.c_int, [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp]),
     "tmdiff_cg_step": (C.c_int, [vp] * 7 + [C.c_double, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]),
     "tmdiff_cg_direction": (C.c_int, [vp] * 5 + [C.c_int32, C.c_int32, vp]),
+    # TV pansharpening (csrc/tv.hip): u, x, pan, ph, pv, weights | tau, sigma, lam, gamma | x', ph', pv' | B, C, H, W;
+    # x | B, C, H, W | out, workspace, bytes
+    "tmdiff_tv_supported": (C.c_int, [C.c_int32] * 4),
+    "tmdiff_tv_pd_step": (C.c_int, [vp] * 6 + [C.c_double] * 4 + [vp] * 3 + [C.c_int32] * 4 + [vp]),
+    "tmdiff_tv_norm_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "tmdiff_tv_norm": (C.c_int, [vp] + [C.c_int32] * 4 + [vp, vp, C.c_size_t, vp]),
 })
 
 

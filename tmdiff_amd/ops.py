@@ -2421,6 +2421,162 @@ def bdsd(ms_exp, pan, sensor, ratio=4, block=None, lr_ms=None, out=None, buffers
     return bdsd_inject(ms_exp, pan, bdsd_coeffs(mo, out=buf["gamma"]), block, out=out)
 
 
+# ---- TV pansharpening: the variational row (csrc/tv.hip; definitions: tmdiff_amd/metrics.py) --------------------------------------
+_TV_LIMITS = ("contiguous float32 tensors on the GPU, images [B, C, H, W], pan [B, 1, H, W]; weights None, [C + 1], [B, C + 1] or a "
+              "float64 [B, C + 1] tensor on the GPU; 1 <= C <= 16; fewer than 2^31 elements")
+_TV = _Family("x", 16, _TV_LIMITS)
+_TV_WEIGHTS = {}        # (values, B, device) -> the uploaded float64 [B, C + 1] table; the last _TV_WEIGHTS_MAX of them
+_TV_WEIGHTS_MAX = 8
+
+
+def tv_supported(b, c, h, w):
+    """True when ``tv_pd_step`` / ``tv_norm`` take [b, c, h, w] images: 1 <= c <= 16, h, w >= 1, fewer than 2^31 elements."""
+    return bool(lib.tmdiff_tv_supported(int(b), int(c), int(h), int(w)))
+
+
+def _tv_weights(name, weights, b, c, device):
+    """(the float64 [B, C + 1] device table, its host copy or None): host values are uploaded once per (values, B, device)."""
+    from . import metrics
+    if torch.is_tensor(weights) and weights.is_cuda:
+        return _f64(name, "weights", weights, (b, c + 1), device).detach(), None
+    try:
+        host = metrics.tv_weights(weights, b, c, name)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: weights for {b} images of {c} bands ({_TV_LIMITS})") from None
+    key = (host.tobytes(), b, device)
+    table = _TV_WEIGHTS.get(key)
+    if table is None:
+        table = _TV_WEIGHTS[key] = torch.from_numpy(np.array(host)).to(device)
+        while len(_TV_WEIGHTS) > _TV_WEIGHTS_MAX:
+            del _TV_WEIGHTS[next(iter(_TV_WEIGHTS))]          # dicts keep insertion order: the oldest
+    return table, host
+
+
+def _tv_scalars(name, tau, sigma, lam, gamma):
+    tau, sigma, lam, gamma = float(tau), float(sigma), float(lam), float(gamma)
+    if not (tau > 0.0 and sigma >= 0.0 and lam >= 0.0 and gamma >= 0.0) or float("inf") in (tau, sigma, lam, gamma):
+        raise ValueError(f"{name}: tau={tau} sigma={sigma} lam={lam} gamma={gamma} (tau > 0, the others >= 0, all finite)")
+    return tau, sigma, lam, gamma
+
+
+def tv_pd_step(u, x, ph, pv, pan, weights, tau, sigma, lam, gamma, out_x=None, out_p=None):
+    """The band-coupled part of one Condat-Vu iteration of TV pansharpening (definition: ``metrics.tv_pd_step`` with
+    storage=np.float32), one launch: with u = x - tau A^T (A x - lr_ms) made by the caller and s = sum_c w_c x_c + w_C - pan,
+      x' = u - tau (gamma w_c s + D^T p);   q = p + sigma D (2 x' - x);   p' = q / max(1, |q| / lam)   (lam == 0: p' = 0)
+    with |q| over the 2 C components of a pixel; fp64 after the loads, every stored value rounded once.  u, x, ph, pv [B, C, H, W],
+    pan [B, 1, H, W]; ``weights``: None (1 / C per band, offset 0), a length C + 1 sequence or a [B, C + 1] array (uploaded once
+    and kept), or a float64 [B, C + 1] tensor on the GPU.  Returns (x', ph', pv'); ``out_x`` and ``out_p`` = (ph', pv') receive
+    them.  NO ALIASING: a workgroup computes x' on its tile plus one column and one row and reads p one pixel further, so every
+    input is read where another workgroup stores; an output that overlaps an input or another output raises ValueError, and a
+    loop ping-pongs x and p (``tv_pansharpen`` does).  With the outputs given nothing is allocated or synchronised (graph
+    capture).  No atomics: the same bits on every run, and a batch equals its samples."""
+    name = "tv_pd_step"
+    b, c, h, w = _images(_TV, name, x, pan)[:4]
+    for t, what in ((u, "u"), (ph, "ph"), (pv, "pv")):
+        _dense(_TV, name, what, t, (b, c, h, w))
+    tau, sigma, lam, gamma = _tv_scalars(name, tau, sigma, lam, gamma)
+    wts, _ = _tv_weights(name, weights, b, c, x.device)
+    xo = _dense(_TV, name, "out_x", out_x if out_x is not None else torch.empty_like(x), (b, c, h, w))
+    if out_p is not None and len(out_p) != 2:
+        raise ValueError(f"{name}: out_p is the pair (ph', pv')")
+    pho, pvo = out_p if out_p is not None else (torch.empty_like(x), torch.empty_like(x))
+    _dense(_TV, name, "out_p[0]", pho, (b, c, h, w))
+    _dense(_TV, name, "out_p[1]", pvo, (b, c, h, w))
+    ins = ((u, "u"), (x, "x"), (ph, "ph"), (pv, "pv"), (pan, "pan"), (wts, "weights"))
+    outs = ((xo, "out_x"), (pho, "out_p[0]"), (pvo, "out_p[1]"))
+    for i, (o, what) in enumerate(outs):
+        for other, which in ins + outs[i + 1:]:
+            if _overlaps(o, other):
+                raise ValueError(f"{name}: {what} overlaps {which} (every input is read with a halo: ping-pong)")
+    check(lib.tmdiff_tv_pd_step(u.detach().data_ptr(), x.detach().data_ptr(), pan.detach().data_ptr(), ph.detach().data_ptr(),
+                                pv.detach().data_ptr(), wts.data_ptr(), tau, sigma, lam, gamma, xo.data_ptr(), pho.data_ptr(),
+                                pvo.data_ptr(), b, c, h, w, stream_ptr()), name)
+    return xo, pho, pvo
+
+
+def tv_norm_workspace(b, c, h, w, device):
+    """A workspace ``tv_norm`` accepts for [b, c, h, w] images (reusable; captured calls must keep it alive)."""
+    b, c, h, w = _extents(_TV, "tv_norm", b, c, h, w)[:4]
+    return torch.empty(max(1, lib.tmdiff_tv_norm_workspace_bytes(b, c, h, w) // 8), device=device, dtype=torch.float64)
+
+
+def tv_norm(x, out=None, workspace=None):
+    """The vector total variation per image (definition: ``metrics.tv_norm``): float64 [B] = sum over the pixels of
+    sqrt(sum_c (Dh x_c)^2 + (Dv x_c)^2) for x [B, C, H, W], forward differences with a zero last column / row, no eps.  fp64
+    after the loads; one partial sum per 16 x 32 tile in ``workspace``, added in a fixed order by a second launch: the same bits
+    on every run.  With ``out=`` and ``workspace=`` (``tv_norm_workspace``) nothing is allocated or synchronised."""
+    _dense(_TV, "tv_norm", "x", x)
+    if x.dim() != 4:
+        raise ValueError(f"tv_norm: x is {tuple(x.shape)}, need [B, C, H, W] ({_TV_LIMITS})")
+    b, c, h, w = _extents(_TV, "tv_norm", *x.shape)[:4]
+    y = _f64("tv_norm", "out", out, (b,), x.device)
+    ws, nbytes = _lent("tv_norm", workspace, lib.tmdiff_tv_norm_workspace_bytes(b, c, h, w), lambda: tv_norm_workspace(b, c, h, w, x.device))
+    check(lib.tmdiff_tv_norm(x.detach().data_ptr(), b, c, h, w, y.data_ptr(), ws.data_ptr(), nbytes, stream_ptr()), "tv_norm")
+    return y
+
+
+def tv_buffers(b, c, h, w, device, ratio=4):
+    """Every scratch tensor of ``tv_pansharpen`` for [b, c, h, w] full-scale images: with them and ``out=`` a call allocates
+    nothing and can be captured.  "x": the second scene of the ping-pong (the other is ``out``); "u": the scene after the
+    gradient step on the data term; "p": the dual variable twice over, [2 (ping-pong), 2 (h, v), B, C, H, W]; "low", "r": A x and
+    the residual at the reduced scale."""
+    b, c, h, w = _extents(_TV, "tv_buffers", b, c, h, w, ratio)[:4]
+    f32 = lambda *shape: torch.empty(shape, device=device, dtype=torch.float32)
+    return {"shape": (b, c, h, w, ratio), "x": f32(b, c, h, w), "u": f32(b, c, h, w), "p": f32(2, 2, b, c, h, w),
+            "low": f32(b, c, h // ratio, w // ratio), "r": f32(b, c, h // ratio, w // ratio)}
+
+
+def tv_pansharpen(lr_ms, pan, sensor, ratio=4, iters=100, lam=1e-3, gamma=1.0, weights=None, x0=None, out=None, buffers=None):
+    """TV pansharpening on the device (definition: ``metrics.tv_pansharpen`` with storage=np.float32): ``iters`` Condat-Vu
+    iterations on  J = 1/2 ||A x - lr_ms||^2 + gamma/2 ||sum_c w_c x_c + w_C - pan||^2 + lam TV(x),  A = ``mtf_degrade(., sensor,
+    ratio)``, for lr_ms [B, C, h, w] and pan [B, 1, ratio h, ratio w], started from ``upsample_poly23(lr_ms, ratio)`` unless ``x0``
+    [B, C, ratio h, ratio w] is given, with p = 0 and the steps of ``metrics.tv_step_sizes``.  ``sensor``: a name or one gain per
+    band (``metrics.band_gains``).  Four launches per iteration: ``fir_decimate``, ``add`` (the residual),
+    ``fir_decimate_adjoint`` with base = x, alpha = -tau, beta = 1 into u, and ``tv_pd_step``, which ping-pongs x between ``out``
+    and a buffer so that the last iterate lands in ``out``.  ``weights`` as ``tv_pd_step`` takes them; host values cost nothing
+    per call, while a device tensor is read back once to size the steps (that synchronises: give host values to capture).
+    ``lam`` = 1e-3 for data in [0, 1] is an UNTUNED default.  With ``buffers`` (``tv_buffers``) and ``out`` a call allocates
+    nothing, reads nothing on the host and can be captured after one warm-up call (the tap table and the weights are cached on
+    first use).  ``out`` may be ``x0``; it must not overlap anything else."""
+    from . import metrics
+    name = "tv_pansharpen"
+    _dense(_TV, name, "lr_ms", lr_ms)
+    if lr_ms.dim() != 4 or ratio not in (2, 4):
+        raise ValueError(f"{name}: lr_ms is {tuple(lr_ms.shape)} at ratio {ratio}, need [B, C, h, w] and ratio 2 or 4 ({_TV_LIMITS})")
+    if int(iters) != iters or iters < 0:
+        raise ValueError(f"{name}: iters={iters} (a whole number >= 0)")
+    b, c, h, w = _extents(_TV, name, lr_ms.shape[0], lr_ms.shape[1], ratio * lr_ms.shape[2], ratio * lr_ms.shape[3], ratio)[:4]
+    _dense(_TV, name, "pan", pan, (b, 1, h, w))
+    lr, pan, iters = lr_ms.detach(), pan.detach(), int(iters)
+    gains = metrics.band_gains(sensor, c)
+    wts, host = _tv_weights(name, weights, b, c, lr.device)
+    tau, sigma = metrics.tv_step_sizes(gains, ratio, host if host is not None else wts.cpu().numpy(), gamma)
+    tau, sigma, lam, gamma = _tv_scalars(name, tau, sigma, lam, gamma)
+    others = [(pan, "pan"), (lr, "lr_ms"), (wts, "weights")]
+    if x0 is not None:
+        _dense(_TV, name, "x0", x0, (b, c, h, w))
+        x0 = x0.detach()
+    y = _chain_out(_TV, name, out if out is not None else torch.empty(b, c, h, w, device=lr.device), (b, c, h, w), others)
+    if x0 is not None and y.data_ptr() != x0.data_ptr() and _overlaps(y, x0):
+        raise ValueError(f"{name}: out overlaps x0 without being x0")
+    buf = _chain_buffers(name, buffers, lambda: tv_buffers(b, c, h, w, lr.device, ratio), (b, c, h, w, ratio), "x", lr.device)
+    taps = _mtf_taps(gains, ratio, lr.device)
+    xs = (y, buf["x"]) if iters % 2 == 0 else (buf["x"], y)               # iterate k lives in xs[k % 2]: the last one in out
+    if x0 is None:
+        upsample_poly23(lr, ratio, out=xs[0])
+    elif xs[0].data_ptr() != x0.data_ptr():
+        xs[0].copy_(x0)
+    if iters:
+        buf["p"][0].zero_()
+    for k in range(iters):
+        x, (ph, pv) = xs[k % 2], buf["p"][k % 2]
+        fir_decimate(x, taps, ratio, None, buf["low"])
+        add(buf["low"], lr, -1.0, out=buf["r"])
+        fir_decimate_adjoint(buf["r"], taps, (h, w), ratio, None, buf["u"], x, -tau, 1.0)
+        tv_pd_step(buf["u"], x, ph, pv, pan, wts, tau, sigma, lam, gamma, out_x=xs[(k + 1) % 2], out_p=tuple(buf["p"][(k + 1) % 2]))
+    return y
+
+
 # ---- backward-side wrappers (finetune path) -----------------------------------------------------------
 
 

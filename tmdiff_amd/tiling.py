@@ -554,3 +554,44 @@ def bdsd_fuse(lr_ms, pan, sensor, ratio=4, block=None, score=False, consistency=
     return _classical("bdsd_fuse", lambda ms_exp, p, lr: ops.bdsd(ms_exp, p, sensor, ratio, block, lr_ms=lr),
                       lambda ms_exp, p, lr: metrics.bdsd(ms_exp, p, sensor, ratio, block, lr_ms=lr), lr_ms, pan, sensor, ratio, score,
                       consistency)
+
+
+def tv_regress_weights(lr_ms, pan, sensor, ratio=4):
+    """The weights ``tv_fuse(weights="regress")`` gives the PAN term: float64 [B, C + 1], per image the least-squares fit of
+    ``metrics.mtf_degrade(pan, PAN gain of sensor, ratio)`` by the C bands of lr_ms and a constant (the band weights, then the
+    offset).  A float64 solve on the host: device tensors are copied there first, which synchronises."""
+    from . import metrics
+    host = lambda t: np.asarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t, dtype=np.float64)
+    lr = host(lr_ms)
+    b, c = lr.shape[:2]
+    low = metrics.mtf_degrade(host(pan), metrics.mtf_gains(sensor, c)[1], ratio)
+    rows = [np.linalg.lstsq(np.concatenate([lr[i].reshape(c, -1), np.ones((1, lr[i][0].size))]).T, low[i].reshape(-1), rcond=None)[0]
+            for i in range(b)]
+    return np.stack(rows)
+
+
+@torch.no_grad()
+def tv_fuse(lr_ms, pan, sensor, ratio=4, iters=100, lam=1e-3, gamma=1.0, weights="equal", score=False, consistency=None):
+    """The sibling of ``bdsd_fuse`` for the variational row of the tables: TV pansharpening of lr_ms [B, C, h, w] with pan
+    [B, 1, ratio * h, ratio * w] (definition: ``metrics.tv_pansharpen``): ``iters`` primal-dual iterations on
+    1/2 ||A x - lr_ms||^2 + gamma/2 ||sum_c w_c x_c + w_C - pan||^2 + lam TV(x), started from the 23-tap interpolation of lr_ms.
+    ``weights``: "equal" (1 / C per band, offset 0), "regress" (``tv_regress_weights``: a host solve per image, which
+    synchronises), or an explicit [C + 1] or [B, C + 1] array.  ``lam`` = 1e-3 for data in [0, 1] is an untuned default.
+    ``sensor`` is always needed: its gains shape A (a row of ``metrics.MTF_GAINS`` or a pair of explicit gains).  Device tensors go through ``ops.tv_pansharpen``, host tensors and arrays
+    through the float64 definition; ``score`` and ``consistency`` are ``classical_fuse``'s.  Not differentiable."""
+    from . import metrics
+    if score not in (False, True, "hqnr"):
+        raise ValueError(f"tv_fuse: score={score!r} (False, True or 'hqnr')")
+    if sensor is None:
+        raise ValueError("tv_fuse: needs the sensor whose MTF gains shape the degradation")
+    if isinstance(weights, str) and weights not in ("equal", "regress"):
+        raise ValueError(f"tv_fuse: weights={weights!r} ('equal', 'regress' or an explicit [C + 1] or [B, C + 1] array)")
+
+    def table(lr, p):
+        if isinstance(weights, str):
+            return None if weights == "equal" else tv_regress_weights(lr, p, sensor, ratio)
+        return weights
+    gains = lambda lr: metrics.mtf_gains(sensor, lr.shape[1])[0]
+    return _classical("tv_fuse", lambda ms_exp, p, lr: ops.tv_pansharpen(lr, p, gains(lr), ratio, iters, lam, gamma, table(lr, p), x0=ms_exp),
+                      lambda ms_exp, p, lr: metrics.tv_pansharpen(lr, p, gains(lr), ratio, iters, lam, gamma, table(lr, p), x0=ms_exp),
+                      lr_ms, pan, sensor, ratio, score, consistency)

@@ -46,7 +46,12 @@ run, the launch kinds of an iteration on their own (degradation, adjoint, the do
 elementwise ones move, and the residual ratio ||lr - A f|| / ||lr - A f0|| each method reaches from `upsample_poly23(lr)`.  The
 step and the direction are timed with a numerator of exactly 0 (alpha = beta = 0): the same loads, multiply-adds and stores,
 and the vectors stay as they are over the replays.  Captured and timed as
-`--leg mtf`."""
+`--leg mtf`.
+
+`--leg tv`: TV pansharpening (csrc/tv.hip) at [1, 8, 1024, 1024] "WV3" and [1, 4, 2048, 2048] "QB", x4: `ops.tv_pd_step` alone
+against a device-to-device copy of the 7 C + 1 planes it moves, `ops.tv_norm`, `ops.tv_pansharpen` at 100 iterations and the same
+iteration composed from torch operators (A as pad + conv2d, A^T as its autograd backward, the coupled part elementwise).
+Captured and timed as `--leg mtf`; the 100-iteration calls are captured once per graph."""
 import argparse
 import os
 import statistics
@@ -495,9 +500,93 @@ def cg_leg(args):
               f"dots + step + direction {new:8.2f} us ({new / (med[n[2]] + med[n[3]]):5.2f} of the pair)", flush=True)
 
 
+def tv_leg(args):
+    """`--leg tv`: see the module's docstring."""
+    import torch.nn.functional as F
+    from tmdiff_amd import metrics
+    iters, ratio, lam, gamma, k = 100, 4, 1e-3, 1.0, metrics.MTF_TAPS
+    cases, groups = [], []          # (name, call, bytes moved or 0, calls per graph); (tag, names)
+    for sensor, shape in (("WV3", (1, 8, 1024, 1024)), ("QB", (1, 4, 2048, 2048))):
+        b, c, h, w = shape
+        gains = metrics.band_gains(sensor, c)
+        truth = torch.rand(*shape, device="cuda")
+        lr, pan = ops.mtf_degrade(truth, sensor, ratio), truth.mean(1, keepdim=True).contiguous()
+        wt = metrics.tv_weights(None, b, c)
+        tau, sigma = metrics.tv_step_sizes(gains, ratio, wt, gamma)
+        buf, out = ops.tv_buffers(b, c, h, w, "cuda", ratio), torch.empty(*shape, device="cuda")
+        solve = lambda lr=lr, pan=pan, out=out, buf=buf, sensor=sensor: ops.tv_pansharpen(lr, pan, sensor, ratio, iters, lam, gamma, out=out, buffers=buf)
+        solve()
+        x, u, p0, p1 = out, buf["u"], buf["p"][0], buf["p"][1]
+        xn = torch.empty_like(x)
+        step = lambda u=u, x=x, p0=p0, p1=p1, pan=pan, xn=xn, tau=tau, sigma=sigma: ops.tv_pd_step(
+            u, x, p0[0], p0[1], pan, None, tau, sigma, lam, gamma, out_x=xn, out_p=(p1[0], p1[1]))
+        moved = 4 * (7 * c + 1) * b * h * w
+        src = torch.empty(moved // 8, device="cuda").normal_()
+        dst = torch.empty_like(src)
+        val, ws = torch.empty(b, device="cuda", dtype=torch.float64), ops.tv_norm_workspace(b, c, h, w, "cuda")
+        # the same iteration from torch operators
+        wk = torch.from_numpy(np.stack([metrics.mtf_kernel(g, ratio) for g in gains])).float().cuda()[:, None]
+        wv = torch.from_numpy(wt[:, :c]).float().cuda()[:, :, None, None]
+        a_of = lambda t, wk=wk, c=c: F.conv2d(F.pad(t, (k // 2,) * 4, mode="replicate")[..., ratio // 2:, ratio // 2:], wk, stride=ratio, groups=c)
+
+        def composed(lr=lr, pan=pan, a_of=a_of, wv=wv, tau=tau, sigma=sigma):
+            xt = ops.upsample_poly23(lr, ratio)
+            ph, pv = torch.zeros_like(xt), torch.zeros_like(xt)
+            for _ in range(iters):
+                with torch.enable_grad():
+                    xr = xt.detach().requires_grad_(True)
+                    g, = torch.autograd.grad(0.5 * (a_of(xr) - lr).pow(2).sum(), xr)
+                s = (wv * xt).sum(1, keepdim=True) - pan
+                dt = -ph
+                dt[..., :, -1] = 0
+                dt[..., :, 1:] += ph[..., :, :-1]
+                dt[..., :-1, :] -= pv[..., :-1, :]
+                dt[..., 1:, :] += pv[..., :-1, :]
+                new = xt - tau * (g + gamma * wv * s + dt)
+                bar = 2 * new - xt
+                qh, qv = ph.clone(), pv.clone()
+                qh[..., :, :-1] += sigma * (bar[..., :, 1:] - bar[..., :, :-1])
+                qv[..., :-1, :] += sigma * (bar[..., 1:, :] - bar[..., :-1, :])
+                scale = ((qh * qh + qv * qv).sum(1, keepdim=True).sqrt() / lam).clamp(min=1.0)
+                xt, ph, pv = new, qh / scale, qv / scale
+            return xt
+        gap = float((composed() - out).abs().max())
+        print(f"{list(shape)} {sensor}: max |tv_pansharpen - torch composition| after {iters} iterations = {gap:.3e}; "
+              f"tv_norm start {float(ops.tv_norm(ops.upsample_poly23(lr, ratio))[0]):.1f} -> {float(ops.tv_norm(out)[0]):.1f}", flush=True)
+        tag = f"{list(shape)}"
+        names = [f"{n:30s} {tag}" for n in ("tv_pd_step", "copy of 7 C + 1 planes", "tv_norm", "tv_pansharpen 100 iterations",
+                                            "torch composition 100 iterations")]
+        groups.append((tag, names))
+        cases += [(names[0], step, moved, args.graph_calls), (names[1], lambda src=src, dst=dst: dst.copy_(src), moved, args.graph_calls),
+                  (names[2], lambda x=x, val=val, ws=ws: ops.tv_norm(x, out=val, workspace=ws), 4 * c * b * h * w, args.graph_calls),
+                  (names[3], solve, 0, 1), (names[4], composed, 0, 1)]
+    runs = []                       # a graph's replay; the eager call where torch cannot capture the composition
+    for name, fn, _, calls in cases:
+        try:
+            runs.append((captured(fn, calls).replay, calls))
+        except RuntimeError as e:
+            torch.cuda.synchronize()
+            print(f"{name.strip()}: not captured ({str(e).splitlines()[0][:80]}); timed eagerly", flush=True)
+            runs.append((fn, 1))
+    times = [[] for _ in cases]
+    for _ in range(args.rounds):
+        for (run, calls), t in zip(runs, times):
+            time_us(run, 1)
+            t.append(time_us(run, 1) / calls)
+    print(f"{'case':52s} {'us per call (min..max)':>34s} {'MiB moved':>10s} {'GB/s':>8s}")
+    med = {}
+    for (name, _, nbytes, _), t in zip(cases, times):
+        m = med[name] = statistics.median(t)
+        rate = f"{nbytes / 2 ** 20:10.1f} {nbytes / m / 1e3:8.1f}" if nbytes else ""
+        print(f"{name:52s} {m:12.2f} ({min(t):10.2f}..{max(t):10.2f}) {rate}", flush=True)
+    for tag, n in groups:
+        print(f"{tag:20s} tv_pd_step / copy {med[n[0]] / med[n[1]]:5.2f}   tv_pd_step share of an iteration {100 * med[n[0]] / med[n[3]]:.2f}   "
+              f"torch composition / tv_pansharpen {med[n[4]] / med[n[3]]:5.1f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("resample", "mtf", "adjoint", "glp", "cs", "bdsd", "cg"), default="resample")
+    ap.add_argument("--leg", choices=("resample", "mtf", "adjoint", "glp", "cs", "bdsd", "cg", "tv"), default="resample")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--graph-calls", type=int, default=10, help="--leg mtf / adjoint: calls captured into each graph")
@@ -519,6 +608,8 @@ def main():
         return bdsd_leg(args)
     if args.leg == "cg":
         return cg_leg(args)
+    if args.leg == "tv":
+        return tv_leg(args)
 
     cases = []          # (name, kernel call, bytes, copy call, bytes the copy moves)
 
