@@ -1011,6 +1011,34 @@ int tmdiff_tv_norm(const float* x, int32_t B, int32_t C, int32_t H, int32_t W, d
                    tmdiff_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * A-trous wavelet pansharpening (csrc/atrous.hip; host definitions: tmdiff_amd/metrics.py, atrous_lowpass / awlp_inject / awlp; the
+ * driver: tmdiff_amd/ops.py, awlp): the approximation plane of the undecimated transform with the B3-spline filter and the ATWT /
+ * AWLP injection.  Dense fp32 images.  Nothing is allocated or synchronised, no atomics, the same bits on every run and on a graph
+ * replay; the summation order is written in the source's header.
+ *  atrous_lowpass: out [B, C, H, W] = c_levels of every plane of x [B, C, H, W]: c_l = h_l * c_{l-1} with the separable
+ *              (1, 4, 6, 4, 1) / 16 dilated by 2^(l-1) and every index clamped into the plane at every level; fp64 after the
+ *              loads, each level rounded to fp32 once.  x is c_{first-1} (first = 1: the image) and the levels first ..
+ *              first + levels - 1 run in one launch (one workgroup per 32 x 32 tile, the halo of 2^first (2^levels - 1) pixels
+ *              staged in LDS); they equal `levels` single-level calls, first counting up, bit for bit.  x is read with a halo:
+ *              out must not overlap x (TMDIFF_E_INVALID).  Limits: B, C, H, W >= 1, H, W <= 2^30, B * C * H * W <= 2^31 - 1,
+ *              first, levels >= 1, first + levels <= 4; otherwise TMDIFF_E_UNSUPPORTED and atrous_supported == 0.
+ *  awlp_inject: out [B, C, H, W] from ms_exp [B, C, H, W], pan and pan_lp [B, H, W] (ONE low-pass plane per image) and moments,
+ *              float64 [B, C + 1, C + 2] on the device, 8-byte aligned: the layout of tmdiff_plane_gram for (ms_exp, pan_lp), of
+ *              which the diagonal is read.  With a_c = sqrt(var(M_c) / var(L)), D = P - L and I = (sum_k M_k) / C:
+ *                mode 0 "atwt":  F_c = M_c + a_c D        mode 1 "awlp":  F_c = M_c + ((M_c / I) a_c) D, and M_c where I == 0
+ *              in fp64, rounded to fp32 once; var(L) == 0 is non-finite throughout.  out may be ms_exp itself; it must not
+ *              overlap anything else (the caller checks).  Limits: B >= 1, 1 <= C <= 14, H, W >= 1, B * C * H * W <= 2^31 - 1,
+ *              mode 0 or 1; otherwise TMDIFF_E_UNSUPPORTED.
+ *              Both check their extents before the pointers (TMDIFF_E_INVALID for a null one) and before any launch.
+ *              (Added within version 6.)
+ * ------------------------------------------------------------------------------------ */
+int tmdiff_atrous_supported(int32_t B, int32_t C, int32_t H, int32_t W, int32_t levels, int32_t first);
+int tmdiff_atrous_lowpass(const float* x, float* out, int32_t B, int32_t C, int32_t H, int32_t W, int32_t levels, int32_t first,
+                          tmdiff_stream_t stream);
+int tmdiff_awlp_inject(const float* ms_exp, const float* pan, const float* pan_lp, const double* moments, float* out, int32_t B,
+                       int32_t C, int32_t H, int32_t W, int32_t mode, tmdiff_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Standalone attention operators of core/Attention.py (imported by nothing in the reference; built because the
  * north star names them).  All fp32.
  *  attn_fwd : out = softmax(q k^T * scale [key mask]) v per (batch, head); fp32 MFMA, online softmax.

@@ -270,6 +270,11 @@ SIGNATURES.update({
     "tmdiff_tv_pd_step": (C.c_int, [vp] * 6 + [C.c_double] * 4 + [vp] * 3 + [C.c_int32] * 4 + [vp]),
     "tmdiff_tv_norm_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
     "tmdiff_tv_norm": (C.c_int, [vp] + [C.c_int32] * 4 + [vp, vp, C.c_size_t, vp]),
+    # a-trous wavelet pansharpening (csrc/atrous.hip): B, C, H, W, levels, first; x, out | B, C, H, W, levels, first;
+    # ms_exp, pan, pan_lp, moments, out | B, C, H, W, mode
+    "tmdiff_atrous_supported": (C.c_int, [C.c_int32] * 6),
+    "tmdiff_atrous_lowpass": (C.c_int, [vp, vp] + [C.c_int32] * 6 + [vp]),
+    "tmdiff_awlp_inject": (C.c_int, [vp] * 5 + [C.c_int32] * 5 + [vp]),
 })
 
 

@@ -17,6 +17,7 @@ CS_BASELINES = ("cs-gs", "cs-gsa", "cs-brovey")   # ... and "cs-" + the methods 
 BDSD_BASELINES = ("bdsd", "bdsd-local")    # ... and metrics.bdsd with one set of weights per image / per 128 x 128 block
 BDSD_LOCAL_BLOCK = 128
 TV_BASELINES = ("tv",)                     # ... and metrics.tv_pansharpen at its defaults (100 iterations, lam 1e-3, equal weights)
+ATROUS_BASELINES = ("atwt", "awlp")        # ... and metrics.awlp in its two modes (a-trous wavelet pansharpening; no sensor involved)
 
 
 def to_hwc01(img, min_max=(0.0, 1.0)):
@@ -75,7 +76,8 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
     image, and "bdsd-local", with weights per 128 x 128 block (``"<metric>_<dataset>@bdsd"``); "bdsd-local" raises ValueError
     naming the shape when the visuals' extents are not multiples of 128.  So is "tv" (``TV_BASELINES``): ``ops.tv_pansharpen`` at its
     defaults, with the samples MS[..., 2::4, 2::4] as its lr_ms and MS as its start (``"<metric>_<dataset>@tv"``; buffers made
-    once per shape).
+    once per shape).  So are "atwt" and "awlp" (``ATROUS_BASELINES``): ``ops.awlp`` in that mode (``"<metric>_<dataset>@awlp"``;
+    buffers made once per shape).
 
     ``d_rho=True`` (with ``full_resolution=True`` only: ValueError otherwise) adds ``d_rho_<dataset>``, the local PAN-correlation
     index ``metrics.d_rho`` of SR against PAN with 4 x 4 windows (``ops.local_corr_loss`` in its value-only mode; the sums stay on
@@ -83,7 +85,7 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
     if d_rho and not full_resolution:
         raise ValueError("val_dataset(d_rho=True) scores without ground truth: it needs full_resolution=True")
     baselines = tuple(baselines)
-    known = BASELINES + CS_BASELINES + BDSD_BASELINES + TV_BASELINES
+    known = BASELINES + CS_BASELINES + BDSD_BASELINES + TV_BASELINES + ATROUS_BASELINES
     if [b for b in baselines if b not in known] or len(set(baselines)) != len(baselines):
         raise ValueError(f"val_dataset: baselines={baselines!r} (distinct names out of {known})")
     if baselines and not (device_metrics or full_resolution):
@@ -108,7 +110,7 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
     n = 0
     dev_sum, dev_ws, q2n_ws = None, {}, {}
     full_sum, full_ws = None, {}
-    base_sum, glp_ws, cs_ws, bdsd_ws, tv_ws = {}, {}, {}, {}, {}
+    base_sum, glp_ws, cs_ws, bdsd_ws, tv_ws, awlp_ws = {}, {}, {}, {}, {}, {}
 
     def score_baselines(ms_d, pan_d, score_row):
         """Adds score_row(fused) of every baseline to its running sum; ms_d, pan_d: the item's MS and PAN in [0, 1]."""
@@ -136,6 +138,11 @@ def val_dataset(trainer, dataset, val_loader, result_root, continous=False, log=
                 buf, out, low = tv_ws[ms_d.shape]
                 low.copy_(ms_d[..., 2::4, 2::4])
                 fused = ops.tv_pansharpen(low, pan_d, sensor, 4, x0=ms_d, out=out, buffers=buf)
+            elif name in ATROUS_BASELINES:
+                if ms_d.shape not in awlp_ws:
+                    awlp_ws[ms_d.shape] = (ops.awlp_buffers(*ms_d.shape, ms_d.device, 4), torch.empty_like(ms_d))
+                buf, out = awlp_ws[ms_d.shape]
+                fused = ops.awlp(ms_d, pan_d, 4, name, out=out, buffers=buf)
             elif name != "exp":
                 if ms_d.shape not in glp_ws:
                     glp_ws[ms_d.shape] = (ops.mtf_glp_buffers(*ms_d.shape, ms_d.device), torch.empty_like(ms_d))

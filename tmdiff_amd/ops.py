@@ -2577,6 +2577,110 @@ def tv_pansharpen(lr_ms, pan, sensor, ratio=4, iters=100, lam=1e-3, gamma=1.0, w
     return y
 
 
+# ---- a-trous wavelet pansharpening: ATWT and AWLP (csrc/atrous.hip; definitions: tmdiff_amd/metrics.py) ---------------------------
+_AWLP_LIMITS = ("contiguous float32 tensors on the GPU, ms_exp [B, C, H, W], pan and pan_lp [B, 1, H, W]; 1 <= C <= 14; ratio 2 or 4; "
+                "fewer than 2^31 elements")
+_AWLP = _Family("ms_exp", 14, _AWLP_LIMITS)
+_ATROUS_LIMITS = ("a contiguous float32 [B, C, H, W] or [B, H, W] tensor on the GPU; B, C, H, W >= 1, H, W <= 2^30, fewer than 2^31 "
+                  "elements; first, levels >= 1, first + levels <= 4")
+
+
+def atrous_supported(b, c, h, w, levels=2, first=1):
+    """True when ``atrous_lowpass`` takes [b, c, h, w] images at ``levels`` from ``first``: every extent >= 1, fewer than 2^31
+    elements, first and levels >= 1, first + levels <= 4."""
+    return bool(lib.tmdiff_atrous_supported(int(b), int(c), int(h), int(w), int(levels), int(first)))
+
+
+def atrous_lowpass(x, levels=2, out=None, first=1):
+    """The approximation plane of the a-trous transform of every plane of x [B, C, H, W], [B, 1, H, W] or [B, H, W] (definition:
+    ``metrics.atrous_lowpass`` with storage=np.float32): ``levels`` (1 .. 3) passes of the separable B3 filter (1, 4, 6, 4, 1) / 16
+    with its taps 2^(l-1) apart, indices clamped into the plane at every level; fp64 after the loads, every level rounded to
+    fp32 once.  All levels run in ONE launch on a tile staged with its halo of 2 (2^levels - 1) pixels, and equal ``levels``
+    single-level calls bit for bit: ``first`` > 1 takes x for c_{first-1} and runs the levels first .. first + levels - 1, so
+    ``atrous_lowpass(atrous_lowpass(x, 1), 1, first=2)`` is ``atrous_lowpass(x, 2)``.  Returns a tensor of x's shape.  x is read with a halo that other workgroups own: ``out`` must
+    not overlap x (ValueError).  With ``out=`` nothing is allocated or synchronised (graph capture).  No atomics: the same bits
+    on every run, and a batch equals its samples.  Not differentiable: x is detached."""
+    from . import metrics
+    name = "atrous_lowpass"
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() in (3, 4)):
+        raise ValueError(f"{name}: x must be {_ATROUS_LIMITS}")
+    try:
+        levels, first = metrics._atrous_levels(name, levels, first)
+    except TypeError:
+        raise ValueError(f"{name}: levels={levels!r} first={first!r} (whole numbers >= 1, first + levels <= 4)") from None
+    x = x.detach()
+    b, c, (h, w) = x.shape[0], (x.shape[1] if x.dim() == 4 else 1), x.shape[-2:]
+    if not lib.tmdiff_atrous_supported(b, c, h, w, levels, first):
+        raise ValueError(f"{name}: x {tuple(x.shape)} levels={levels} is not supported ({_ATROUS_LIMITS})")
+    y = out if out is not None else torch.empty_like(x)
+    if not (torch.is_tensor(y) and y.is_cuda and y.dtype == torch.float32 and y.is_contiguous() and y.shape == x.shape
+            and y.device == x.device):
+        raise ValueError(f"{name}: out must be a contiguous float32 {tuple(x.shape)} tensor on x's device")
+    if _overlaps(y, x):
+        raise ValueError(f"{name}: out overlaps x (x is read with a halo that other workgroups own)")
+    check(lib.tmdiff_atrous_lowpass(x.data_ptr(), y.data_ptr(), b, c, h, w, levels, first, stream_ptr()), name)
+    return y
+
+
+def _awlp_mode(name, mode):
+    from . import metrics
+    if mode not in metrics.ATROUS_MODES:
+        raise ValueError(f"{name}: mode={mode!r} (one of {metrics.ATROUS_MODES})")
+    return metrics.ATROUS_MODES.index(mode)
+
+
+def awlp_inject(ms_exp, pan, pan_lp, moments, mode, out=None):
+    """The injection of a-trous wavelet pansharpening (definition: ``metrics.awlp_inject``): the fused [B, C, H, W] from ms_exp, pan
+    and pan_lp [B, 1, H, W] -- ONE low-pass plane per image -- and ``moments``, the float64 [B, C + 1, C + 2] device tensor of
+    ``plane_moments(ms_exp, pan_lp)``.  With a_c = sqrt(var(M_c) / var(L)) formed on the device from the moments' diagonal
+    (nothing is read on the host), D = P - L and I = (sum_k M_k) / C:
+      "atwt":  F_c = M_c + a_c D          "awlp":  F_c = M_c + ((M_c / I) a_c) D,  and F_c = M_c where I == 0
+    in fp64, rounded to fp32 once; a constant pan_lp gives a non-finite result throughout.  ``out`` may be ms_exp itself (in
+    place: a lane reads all bands of its pixels before it stores any); it must not overlap pan, pan_lp or moments.  With ``out=``
+    nothing is allocated or synchronised.  Not differentiable: the inputs are detached."""
+    name = "awlp_inject"
+    m = _awlp_mode(name, mode)
+    b, c, h, w = _images(_AWLP, name, ms_exp, pan)[:4]
+    _dense(_AWLP, name, "pan_lp", pan_lp, (b, 1, h, w))
+    mo = _f64(name, "moments", moments, (b, c + 1, c + 2), ms_exp.device)
+    y = _inject_out(_AWLP, name, out, ms_exp, ((pan, "pan"), (pan_lp, "pan_lp"), (mo, "moments")))
+    check(lib.tmdiff_awlp_inject(ms_exp.detach().data_ptr(), pan.detach().data_ptr(), pan_lp.detach().data_ptr(), mo.detach().data_ptr(),
+                                 y.data_ptr(), b, c, h, w, m, stream_ptr()), name)
+    return y
+
+
+def awlp_buffers(b, c, h, w, device, ratio=4):
+    """Every scratch tensor of ``awlp`` for [b, c, h, w] images: with them and ``out=`` a call allocates nothing and can be captured
+    into a graph.  "pan_lp": the a-trous low-pass PAN [b, 1, h, w]; "moments": the float64 [b, c + 1, c + 2] moments of the bands
+    and that plane; "ws": the workspace of ``plane_moments``."""
+    b, c, h, w = _extents(_AWLP, "awlp_buffers", b, c, h, w)[:4]
+    if ratio not in (2, 4):
+        raise ValueError(f"awlp_buffers: ratio={ratio} is not supported ({_AWLP_LIMITS})")
+    return {"shape": (b, c, h, w, ratio), "pan_lp": torch.empty(b, 1, h, w, device=device, dtype=torch.float32),
+            "moments": torch.empty(b, c + 1, c + 2, device=device, dtype=torch.float64), "ws": plane_moments_workspace(b, c, h, w, device)}
+
+
+def awlp(ms_exp, pan, ratio=4, mode="awlp", out=None, buffers=None):
+    """A-trous wavelet pansharpening on the device (definition: ``metrics.awlp`` with storage=np.float32): the fused [B, C, H, W]
+    from ms_exp, the MS interpolated to the PAN grid, and pan [B, 1, H, W]; ``mode`` "atwt" (additive) or "awlp" (proportional,
+    Otazu et al. 2005).  Three launches and a finalize: ``atrous_lowpass(pan, log2(ratio))`` makes the one low-pass plane L,
+    ``plane_moments(ms_exp, L)`` leaves the variances on the device, ``awlp_inject`` forms the gains there and writes the result.
+    No sensor is involved.  ``out`` may be ms_exp.  With ``buffers`` (``awlp_buffers``) and ``out=`` nothing is allocated or
+    synchronised and the call can be captured into a graph.  Not differentiable: the inputs are detached."""
+    name = "awlp"
+    _awlp_mode(name, mode)
+    b, c, h, w = _images(_AWLP, name, ms_exp, pan)[:4]
+    if ratio not in (2, 4):
+        raise ValueError(f"{name}: ratio={ratio} is not supported ({_AWLP_LIMITS})")
+    ms_exp, pan = ms_exp.detach(), pan.detach()
+    _chain_out(_AWLP, name, out, (b, c, h, w), ((pan, "pan"),))
+    buf = _chain_buffers(name, buffers, lambda: awlp_buffers(b, c, h, w, ms_exp.device, ratio), (b, c, h, w, ratio), "pan_lp",
+                         ms_exp.device)
+    low = atrous_lowpass(pan, 1 if ratio == 2 else 2, out=buf["pan_lp"])
+    mo = plane_moments(ms_exp, low, out=buf["moments"], workspace=buf["ws"])
+    return awlp_inject(ms_exp, pan, low, mo, mode, out=out)
+
+
 # ---- backward-side wrappers (finetune path) -----------------------------------------------------------
 
 

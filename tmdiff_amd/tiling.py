@@ -595,3 +595,19 @@ def tv_fuse(lr_ms, pan, sensor, ratio=4, iters=100, lam=1e-3, gamma=1.0, weights
     return _classical("tv_fuse", lambda ms_exp, p, lr: ops.tv_pansharpen(lr, p, gains(lr), ratio, iters, lam, gamma, table(lr, p), x0=ms_exp),
                       lambda ms_exp, p, lr: metrics.tv_pansharpen(lr, p, gains(lr), ratio, iters, lam, gamma, table(lr, p), x0=ms_exp),
                       lr_ms, pan, sensor, ratio, score, consistency)
+
+
+@torch.no_grad()
+def awlp_fuse(lr_ms, pan, sensor=None, ratio=4, mode="awlp", score=False, consistency=None):
+    """The sibling of ``cs_fuse`` for the wavelet rows of the tables: lr_ms [B, C, h, w] is interpolated with the 23-tap polynomial
+    kernel into ms_exp and fused with pan [B, 1, ratio * h, ratio * w] by a-trous wavelet pansharpening in ``mode`` "atwt"
+    (additive) or "awlp" (proportional; definition: ``metrics.awlp``).  The method itself involves no sensor: ``sensor`` is needed
+    only by ``consistency`` and by ``score="hqnr"``.  Device tensors go through ``ops.awlp``, host tensors and arrays through the
+    float64 definition; ``score`` and ``consistency`` are ``classical_fuse``'s.  Not differentiable."""
+    from . import metrics
+    if score not in (False, True, "hqnr"):
+        raise ValueError(f"awlp_fuse: score={score!r} (False, True or 'hqnr')")
+    if mode not in metrics.ATROUS_MODES:
+        raise ValueError(f"awlp_fuse: mode={mode!r} (one of {metrics.ATROUS_MODES})")
+    return _classical("awlp_fuse", lambda ms_exp, p, lr: ops.awlp(ms_exp, p, ratio, mode),
+                      lambda ms_exp, p, lr: metrics.awlp(ms_exp, p, ratio, mode), lr_ms, pan, sensor, ratio, score, consistency)

@@ -51,7 +51,15 @@ and the vectors stay as they are over the replays.  Captured and timed as
 `--leg tv`: TV pansharpening (csrc/tv.hip) at [1, 8, 1024, 1024] "WV3" and [1, 4, 2048, 2048] "QB", x4: `ops.tv_pd_step` alone
 against a device-to-device copy of the 7 C + 1 planes it moves, `ops.tv_norm`, `ops.tv_pansharpen` at 100 iterations and the same
 iteration composed from torch operators (A as pad + conv2d, A^T as its autograd backward, the coupled part elementwise).
-Captured and timed as `--leg mtf`; the 100-iteration calls are captured once per graph."""
+Captured and timed as `--leg mtf`; the 100-iteration calls are captured once per graph.
+
+`--leg atrous`: a-trous wavelet pansharpening (csrc/atrous.hip) at the same two sizes: `ops.atrous_lowpass` of the PAN plane at
+two levels against a device-to-device copy of the bytes it moves (one plane in, one out) and against the torch composition
+(replicate `F.pad` plus dilated `F.conv2d` per level), `ops.awlp_inject` against a copy of its 2 C + 2 planes with
+`ops.cs_inject` in the same run, and `ops.awlp` whole against `ops.mtf_glp(mode="glp")` whole.  Captured and timed as `--leg mtf`.
+THE ESTIMATE, written before the first run: both kernels are bound by HBM -- `atrous_lowpass` within 1.5 times its copy (28 LDS
+reads and about 50 fp64 operations per pixel should hide behind 8 bytes of traffic), `awlp_inject` at the 0.6 to 0.9 of its copy
+that `cs_inject` and `bdsd_inject` reach.  What the run says about it is recorded in profiles/atrous.txt."""
 import argparse
 import os
 import statistics
@@ -584,9 +592,73 @@ def tv_leg(args):
               f"torch composition / tv_pansharpen {med[n[4]] / med[n[3]]:5.1f}", flush=True)
 
 
+def atrous_leg(args):
+    """`--leg atrous`: see the module's docstring."""
+    import torch.nn.functional as F
+    from tmdiff_amd import metrics
+    ratio, levels = 4, 2
+    cases, groups = [], []          # (name, call, bytes moved or 0); (tag, names)
+    taps = torch.tensor(metrics.ATROUS_TAPS, device="cuda")
+    kernel = torch.outer(taps, taps)[None, None]
+
+    def composed(pan):
+        c = pan
+        for level in range(levels):
+            d = 1 << level
+            c = F.conv2d(F.pad(c, (2 * d,) * 4, mode="replicate"), kernel, dilation=d)
+        return c
+
+    for sensor, shape in (("WV3", (1, 8, 1024, 1024)), ("QB", (1, 4, 2048, 2048))):
+        b, c, h, w = shape
+        ms, pan = torch.rand(*shape, device="cuda"), torch.rand(b, 1, h, w, device="cuda")
+        buf, out = ops.awlp_buffers(b, c, h, w, "cuda", ratio), torch.empty(*shape, device="cuda")
+        gbuf, gout = ops.mtf_glp_buffers(b, c, h, w, "cuda", ratio), torch.empty(*shape, device="cuda")
+        whole = lambda ms=ms, pan=pan, out=out, buf=buf: ops.awlp(ms, pan, ratio, "awlp", out=out, buffers=buf)
+        glp = lambda ms=ms, pan=pan, gout=gout, gbuf=gbuf, sensor=sensor: ops.mtf_glp(ms, pan, sensor, ratio, "glp", out=gout, buffers=gbuf)
+        whole(), glp()
+        low, mo = buf["pan_lp"], buf["moments"]
+        gap = float((composed(pan) - low).abs().max())          # replicate padding of c_{l-1} is the clamped read of c_{l-1}
+        print(f"{list(shape)}: max |atrous_lowpass - torch composition| = {gap:.3e}", flush=True)
+        coef = ops.cs_coeffs(ops.plane_moments(ms, pan), None, "gs")
+        cout = torch.empty_like(ms)
+        copies = {}
+        for planes in (2, 2 * c + 2, 2 * c + 1):
+            src = torch.empty(planes * b * h * w // 2, device="cuda").normal_()
+            copies[planes] = (src, torch.empty_like(src))
+        tag = f"{list(shape)}"
+        names = [f"{n:30s} {tag}" for n in ("atrous_lowpass levels 2", "copy of 2 planes", "pad + dilated conv2d x 2", "awlp_inject",
+                                            "copy of 2 C + 2 planes", "cs_inject", "copy of 2 C + 1 planes", "awlp whole",
+                                            "mtf_glp glp whole")]
+        groups.append((tag, names))
+        plane = 4 * b * h * w
+        cp = lambda k: (lambda s=copies[k][0], d=copies[k][1]: d.copy_(s))
+        cases += [(names[0], lambda pan=pan, low=low: ops.atrous_lowpass(pan, levels, out=low), 2 * plane), (names[1], cp(2), 2 * plane),
+                  (names[2], lambda pan=pan: composed(pan), 2 * plane),
+                  (names[3], lambda ms=ms, pan=pan, low=low, mo=mo, out=out: ops.awlp_inject(ms, pan, low, mo, "awlp", out=out), (2 * c + 2) * plane),
+                  (names[4], cp(2 * c + 2), (2 * c + 2) * plane),
+                  (names[5], lambda ms=ms, pan=pan, coef=coef, cout=cout: ops.cs_inject(ms, pan, coef, "gs", out=cout), (2 * c + 1) * plane),
+                  (names[6], cp(2 * c + 1), (2 * c + 1) * plane), (names[7], whole, 0), (names[8], glp, 0)]
+    graphs = [captured(fn, args.graph_calls) for _, fn, _ in cases]
+    times = [[] for _ in cases]
+    for _ in range(args.rounds):
+        for graph, t in zip(graphs, times):
+            time_us(graph.replay, 1)
+            t.append(time_us(graph.replay, 1) / args.graph_calls)
+    print(f"{'case':52s} {'us per call (min..max)':>34s} {'MiB moved':>10s} {'GB/s':>8s}")
+    med = {}
+    for (name, _, nbytes), t in zip(cases, times):
+        m = med[name] = statistics.median(t)
+        rate = f"{nbytes / 2 ** 20:10.1f} {nbytes / m / 1e3:8.1f}" if nbytes else ""
+        print(f"{name:52s} {m:12.2f} ({min(t):10.2f}..{max(t):10.2f}) {rate}", flush=True)
+    for tag, n in groups:
+        print(f"{tag:20s} atrous_lowpass / copy {med[n[0]] / med[n[1]]:5.2f}   torch composition / atrous_lowpass {med[n[2]] / med[n[0]]:5.1f}   "
+              f"awlp_inject / copy {med[n[3]] / med[n[4]]:5.2f}   cs_inject / copy {med[n[5]] / med[n[6]]:5.2f}   "
+              f"awlp / mtf_glp {med[n[7]] / med[n[8]]:5.2f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("resample", "mtf", "adjoint", "glp", "cs", "bdsd", "cg", "tv"), default="resample")
+    ap.add_argument("--leg", choices=("resample", "mtf", "adjoint", "glp", "cs", "bdsd", "cg", "tv", "atrous"), default="resample")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--graph-calls", type=int, default=10, help="--leg mtf / adjoint: calls captured into each graph")
@@ -610,6 +682,8 @@ def main():
         return cg_leg(args)
     if args.leg == "tv":
         return tv_leg(args)
+    if args.leg == "atrous":
+        return atrous_leg(args)
 
     cases = []          # (name, kernel call, bytes, copy call, bytes the copy moves)
 
