@@ -844,7 +844,8 @@ int wf_forward(const tmdiff_conv3d_desc* d, void* workspace, tmdiff_stream_t str
   if (llm) rc = wf_pair(d) ? launch<2, 8, 16, true, true>(a, st) : (d->N == 8 ? launch<2, 8, 16, false, true>(a, st) : launch<1, 16, 16, false, true>(a, st));
   else rc = wf_pair(d) ? launch<2, 8, 16, true>(a, st) : (d->N == 8 ? launch<2, 8, 16>(a, st) : launch<1, 16, 16>(a, st));
   if (rc || !a.part) return rc;
-  return finish_splitk(a, d, plane, d->bias_scale, st);
+  // (a.bias_scale: with bias_mul, as the unsplit epilogue applies it -- the composed-LL mode at ll_scale != 0.5)
+  return finish_splitk(a, d, plane, a.bias_scale, st);
 }
 
 // the descriptor of the composed-LL convolution as the kernel sees it: the space-to-depth input has 4 x the channels at half
@@ -866,6 +867,8 @@ __constant__ float kG6[6][3] = {{0.25f, 0.f, 0.f},           {-1.f / 6.f, -1.f /
 // (conv3d_ll.hip), its four (a, b) taps per (row parity ph, column parity pw) -- a = 1 + 2 i (ph = 0) or 2 i (ph = 1), b likewise
 // -- and G along dn:  packed[ci][ph][pw][i * 2 + j][k][co].
 __global__ void __launch_bounds__(256) wfll_pack_kernel(const float* __restrict__ w, float* __restrict__ packed, int Cout, int Cin, float s) {
+#pragma clang fp contract(off)     // (as wino_pack_row: every product with 1/6, 1/12, 1/24 rounded by itself -- a fused multiply-add
+                                   //  keeps the constant's rounding error, which a cancelling sum G c then returns instead of zero)
   const long r = blockIdx.x * 256L + threadIdx.x;
   if (r >= (long)Cout * Cin) return;
   const int co = (int)(r % Cout), ci = (int)(r / Cout);

@@ -797,6 +797,15 @@ def conv3d_wf(segs, w_packed, cout, emit=None, keep_y=True, groups=1, xp_out=Non
             raise ValueError("conv3d_wf: this launch cannot write a space-to-depth / LL output (ask routing.wf_quarter_ok first)")
     if want_ll and keep_y:
         raise ValueError("conv3d_wf: the LL output replaces y (keep_y=False)")
+    # what the library would refuse only after the launch has been counted: the pair mode (8 bands x 8 columns) writes no LL /
+    # Haar output and folds no residual convolution, the LL / Haar output needs 8 bands, the fold groups 1 and 32 k <= 512 channels
+    pair = n == 8 and w == 8
+    if want_ll and (pair or n != 8):
+        raise ValueError("conv3d_wf: the LL / Haar output needs 8 bands and planes wider than 8 columns")
+    rc = kw.get("res_conv")
+    if rc is not None and (pair or groups != 1 or int(rc[2]) <= 0 or int(rc[2]) % 32 or int(rc[2]) > 512):
+        raise ValueError("conv3d_wf: a folded residual convolution needs groups 1, rc_cin % 32 == 0 (at most 512) and planes "
+                         "wider than 8 columns")
     q = (b, cout, n, h // 2, w // 2)       # (allocated before y and y2 -- y is None whenever y_ll is wanted)
     y_ll = torch.empty(*q, device=dev, dtype=torch.float32) if want_ll else None
     y_hi = [torch.empty(*q, device=dev, dtype=torch.float32) for _ in range(3)] if want_dwt else None
